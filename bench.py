@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — evaluated atom-pairs/s of the run_arpeggio hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms A]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--atoms A] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path (InteractionComplex.run_arpeggio,
 interactions.py:329-347: selection, the neighbour grid of the pass, 5 A neighbour search + fused
@@ -17,14 +17,16 @@ halo exchanged over RCCL before the timed region; the ranks meet over plain TCP
 (arpeggio_amd/rendezvous.py) and the timed region is bracketed by arp_device_synchronize +
 barrier — no PyTorch in this process.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the
-dominant kernel (HIP-event time on the context's own stream, SURVEY 8d's compulsory bytes of
-that kernel) and `cpu_baseline` (the C oracle timed on one host core on a bounded sample of
-the same workload).  The GPU legs run back to back; the CPU baselines come last.
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line on rank 0 with
+the headline (`value`, `ms_per_step` = timed region / K, ...).  --dump-outputs DIR writes the
+result bags of the last timed step (dump_outputs).  --full adds every other figure: per-kernel
+times and `roofline` for the dominant kernel (HIP-event time on the context's own stream,
+SURVEY 8d's compulsory bytes of that kernel), the extra GPU legs and configurations back to
+back, then `cpu_baseline` (the C oracle timed on one host core on a bounded sample of the same
+workload) and the other CPU baselines.
 """
 import argparse
 import json
-import math
 import os
 import sys
 import time
@@ -46,8 +48,13 @@ def parse():
     ap.add_argument('--atoms', type=int, default=100_000,
                     help='atoms per GPU (weak scaling): 100 000 = BASELINE configs[2] on every GPU, at N = 1 and at N > 1 alike; '
                          '--gpus 8 --atoms 250000 is configs[3] (2 M atoms on 8 GPUs)')
-    ap.add_argument('--min-seconds', type=float, default=2.0,
-                    help='the K timed steps are repeated as a block until the timed region is at least this long')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-kernel times and rooflines, the pass on a kept grid, several structures in flight, '
+                         'end to end, the other BASELINE configurations, the multi-GPU legs and the CPU baselines (the --no-* options '
+                         'below switch parts of it off)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write the five result bags of the last step (canonical order) to DIR/<bag>_<column>.npy '
+                         'as float32 / float64, at most 64 MB in all')
     ap.add_argument('--no-end-to-end', action='store_true', help='skip the fresh-structure-per-step measurement')
     ap.add_argument('--cutoff', type=float, default=5.0)
     ap.add_argument('--vdw-comp', type=float, default=0.1)
@@ -96,6 +103,31 @@ def survey_8d_bytes(kernel, n_binned, ncell, n_pairs):
     if kernel == 'sift':         # hydrogen / bond side arrays + the output records
         return 16 * n_binned + 16 * n_pairs
     raise KeyError(kernel)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, out_dir, prefix=''):
+    """--dump-outputs: the five result bags of the last pass as a caller receives them (arp_fetch_packed: every bag in its
+    canonical order), one .npy per column.  Ids become float64, the narrower columns float32 (both exact).  Above 64 MB in
+    all, the same rows of each bag are kept from a sample fixed by the bag's length and seed 0."""
+    bags, _ = ctx.fetch_packed()
+    cols = {}
+    for bag, arrs in bags.items():
+        for k, v in arrs.items():
+            v = np.asarray(v)
+            wide = v.dtype == np.float64 or (v.dtype.kind in 'iu' and v.dtype.itemsize >= 4)
+            cols[f'{prefix}{bag}_{k}'] = (bag, v.astype(np.float64 if wide else np.float32))
+    total = sum(v.nbytes for _, v in cols.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    rows = {}
+    for bag, arrs in bags.items():
+        n = len(next(iter(arrs.values()))) if arrs else 0
+        rows[bag] = None if keep >= 1.0 else np.sort(np.random.default_rng(0).choice(n, int(n * keep), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (bag, v) in cols.items():
+        np.save(os.path.join(out_dir, name + '.npy'), v if rows[bag] is None else v[rows[bag]])
 
 
 def _timed_passes(step, min_s=0.25, min_n=50, warm=8):
@@ -326,7 +358,7 @@ def dry_run(args, rank, local_rank, world, timeout):
         rdzv.barrier()
     if rank == 0:
         # the legs a real run of this launch adds to its line beside the weak-scaling headline (multi_gpu.*)
-        strong = (args.atoms == 100_000 and not args.no_config4 and CONFIG4_ATOMS % world == 0 and (world > 1 or not args.no_other_configs))
+        strong = (args.full and args.atoms == 100_000 and not args.no_config4 and CONFIG4_ATOMS % world == 0 and (world > 1 or not args.no_other_configs))
         legs = {'config4_strong': {'workload': config4_workload(world), 'n_gpus': world, 'atoms_per_gpu': CONFIG4_ATOMS // world, 'scaling': 'strong'} if strong else None}
         print(json.dumps({'dry_run': True, 'n_gpus': world, 'ranks': everybody, 'allreduce_sum': total, 'legs': legs,
                           'config': {'workload': per_gpu_workload(args.atoms), 'atoms_per_gpu': args.atoms}}), flush=True)
@@ -359,18 +391,40 @@ def bench_batch(args):
     for _ in range(5 + args.warmup):
         counts = step()
     ctx.device_synchronize()
-    t_trial = time.perf_counter()
-    for _ in range(args.steps):
-        counts = step()
-    repeats = max(1, int(math.ceil(args.min_seconds / max(time.perf_counter() - t_trial, 1e-6))))
-    ctx.device_synchronize()
     t1 = time.perf_counter()
-    for _ in range(repeats * args.steps):
+    for _ in range(args.steps):
         counts = step()
     ctx.device_synchronize()
     elapsed = time.perf_counter() - t1
-    timed_steps = repeats * args.steps
+    timed_steps = args.steps
     st = ctx.stats()
+    ms_per_step = elapsed / timed_steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs)
+    line = {
+        'metric': 'evaluated atom-pairs/s', 'value': round(st['candidates'] * timed_steps / elapsed, 1), 'unit': 'candidate atom-pairs/s',
+        'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'timed_steps': timed_steps,
+        'timed_region_s': round(elapsed, 6), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f64 distance test / f32+f64 SIFt', 'data': 'synthetic',
+        'config': {'workload': f'{B} structures of the 1tqn_h stand-in family (BASELINE configs[1]; {len(distinct)} distinct synthetic chains of 480 residues + '
+                               f'haem-like ligand + waters, ~5.9 k atoms each incl. explicit hydrogens, repeated) in ONE pass (arp_set_batch), whole structures, 5 A cutoff',
+                   'structures_per_pass': B, 'atoms_per_pass': int(big.n_atoms), 'cutoff_A': args.cutoff, 'vdw_comp': args.vdw_comp, 'parallelism': 'single'},
+        'structures_per_s': round(B * timed_steps / elapsed, 1), 'us_per_structure': round(ms_per_step / B * 1e3, 3),
+        'pairs': {'candidates': float(st['candidates']), 'accepted': float(st['accepted']), 'contacts_emitted': float(st['emitted']),
+                  'bags': {k: int(v) for k, v in counts.items()}},
+        'setup_s': round(gen_s, 2),
+    }
+    if args.full:
+        line.update(batch_extras(args, ctx, step, st, big, pcs, off, distinct, ms_per_step))
+    print(json.dumps(line))
+    ctx.close()
+
+
+def batch_extras(args, ctx, step, st, big, pcs, off, distinct, ms_per_step):
+    """--full keys of the --batch line: per-kernel times and roofline, the pass on a kept grid, the structures one at a time,
+    a fresh batch every step, the C oracle."""
+    from arpeggio_amd import _capi, batch as _batch
+    B = args.batch
     ctx.set_profiling(True)
     ctx.kernel_times(reset=True)
     for _ in range(args.steps):
@@ -380,7 +434,6 @@ def bench_batch(args):
     per_kernel = {k: (v['ms'] / max(v['launches'], 1)) for k, v in ktimes.items() if v['launches']}
     dom = max((k for k in ('search', 'sift') if k in per_kernel), key=lambda k: per_kernel[k])
     b_alg = algorithmic_bytes(dom, st['binned'], st['cells'], st['emitted'], int(big.h_xyz.shape[0]))
-    ms_per_step = elapsed / timed_steps * 1e3
     # the same batch on the grid the pass before it built (see main(): pass_with_grid_kept)
     ctx.set_grid_reuse(True)
     for _ in range(5):
@@ -445,29 +498,17 @@ def bench_batch(args):
                'ms_per_structure': round(cpu_s / len(distinct) * 1e3, 2),
                'sample': f'one full run_arpeggio pass of the C oracle (oracle/ref_c.c, gcc -O2, 1 thread) over each of the {len(distinct)} distinct '
                          f'structures of the batch, {cpu_s:.2f} s; pairs counted as the GPU counts them'}
-    line = {
-        'metric': 'evaluated atom-pairs/s', 'value': round(st['candidates'] * timed_steps / elapsed, 1), 'unit': 'candidate atom-pairs/s',
-        'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'timed_steps': timed_steps,
-        'timed_region_s': round(elapsed, 3), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': 'f64 distance test / f32+f64 SIFt', 'data': 'synthetic',
-        'config': {'workload': f'{B} structures of the 1tqn_h stand-in family (BASELINE configs[1]; {len(distinct)} distinct synthetic chains of 480 residues + '
-                               f'haem-like ligand + waters, ~5.9 k atoms each incl. explicit hydrogens, repeated) in ONE pass (arp_set_batch), whole structures, 5 A cutoff',
-                   'structures_per_pass': B, 'atoms_per_pass': int(big.n_atoms), 'cutoff_A': args.cutoff, 'vdw_comp': args.vdw_comp, 'parallelism': 'single'},
-        'structures_per_s': round(B * timed_steps / elapsed, 1), 'us_per_structure': round(ms_per_step / B * 1e3, 3),
+    return {
         'single_structure_pass_ms': {'mean': round(float(np.mean(single_ms)), 4), 'min': round(float(np.min(single_ms)), 4), 'max': round(float(np.max(single_ms)), 4),
                                      'note': 'resident pass of each distinct structure alone on the same context'},
         'speedup_vs_one_at_a_time': round(float(np.mean(single_ms)) / (ms_per_step / B), 2),
-        'pairs': {'candidates': float(st['candidates']), 'accepted': float(st['accepted']), 'contacts_emitted': float(st['emitted']),
-                  'bags': {k: int(v) for k, v in counts.items()}},
         'kernel_ms': {k: round(v, 5) for k, v in per_kernel.items()}, 'pass_with_grid_kept': grid_kept,
         'roofline': {'kernel': f'k_{dom}', 'bound': 'hbm', 'achieved': round(b_alg / (per_kernel[dom] * 1e-3) / 1e9, 2), 'peak': 8000.0, 'unit': 'GB/s',
                      'frac': round(b_alg / (per_kernel[dom] * 1e-3) / 1e9 / 8000.0, 6), 'traffic': None,
                      'algorithmic_bytes_per_launch': int(b_alg), 'avg_launch_ms': round(per_kernel[dom], 5),
                      'note': 'HIP-event duration of the dominant kernel in this run; no PMC run of this workload is committed, hence traffic = null'},
-        'cpu_baseline': cpu, 'end_to_end': e2e, 'setup_s': round(gen_s, 2),
+        'cpu_baseline': cpu, 'end_to_end': e2e,
     }
-    print(json.dumps(line))
-    ctx.close()
 
 
 def main():
@@ -585,8 +626,7 @@ def main():
     # runs the same pass twice on one structure, so nothing a pass made may be reused by the next one).
     ctx.set_grid_reuse(False)
     # set-up, not steps: the first passes size the result buffers (a pass is re-run when one was too small); reported
-    # in the line as `setup_passes`.  Then the W warm-up steps and the timed region: the K steps, repeated as a block
-    # until the region is at least --min-seconds long (K x repeats steps are timed; `steps` stays K).
+    # in the line as `setup_passes`.  Then the W warm-up steps and the timed region: exactly the K steps.
     SETUP_PASSES = 5
     for _ in range(SETUP_PASSES):
         counts = step()
@@ -594,44 +634,36 @@ def main():
         counts = step()
     sync_all()
     ctx.host_times(reset=True)
-    # How many blocks of K steps fill --min-seconds is settled ONCE, before the timed region, from an untimed trial block (all
-    # ranks take the largest answer): the timed region itself holds steps only — at N > 1 no collective that N = 1 would not have.
-    t_trial = time.perf_counter()
-    for _ in range(args.steps):
-        counts = step()
-    trial_s = max(time.perf_counter() - t_trial, 1e-6)
-    repeats = max(1, int(math.ceil(args.min_seconds / trial_s)))
-    if rdzv is not None:
-        repeats = int(rdzv.allreduce(np.array([float(repeats)]), 'max')[0])
-    sync_all()
-    ctx.host_times(reset=True)
     t0 = time.perf_counter()
-    for _ in range(repeats):
-        for _ in range(args.steps):
-            counts = step()          # blocks until the pass has published its counters (one host wait per step)
+    for _ in range(args.steps):
+        counts = step()          # blocks until the pass has published its counters (one host wait per step)
     sync_all()
     elapsed = time.perf_counter() - t0
-    timed_steps = args.steps * repeats
+    timed_steps = args.steps
     host_times = ctx.host_times(reset=True)
     st = ctx.stats()
-    # Per-kernel durations: the same K steps once more with every launch bracketed by HIP events on the
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, f'rank{rank}_' if world > 1 else '')
+    # Per-kernel durations (--full): the same K steps once more with every launch bracketed by HIP events on the
     # context's streams (recording ~50 events per step costs ~0.1 ms per step, so it is kept out of `value`).
-    ctx.set_profiling(True)
-    ctx.kernel_times(reset=True)
-    sync_all()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    sync_all()
-    elapsed_profiled = time.perf_counter() - t1
-    ktimes = ctx.kernel_times(reset=True)
-    ctx.set_profiling(False)
+    ktimes, elapsed_profiled = {}, None
+    if args.full:
+        ctx.set_profiling(True)
+        ctx.kernel_times(reset=True)
+        sync_all()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        sync_all()
+        elapsed_profiled = time.perf_counter() - t1
+        ktimes = ctx.kernel_times(reset=True)
+        ctx.set_profiling(False)
 
-    # ---- extra GPU legs (world == 1; informational, never `value`), back to back before any CPU baseline ----
+    # ---- extra GPU legs (--full, world == 1; informational, never `value`), back to back before any CPU baseline ----
     # (a) the pass that KEEPS the grid of the pass before it: a whole-structure pass over a resident structure whose grid
     #     the library caches — two launches instead of three
     grid_kept = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             ctx.set_grid_reuse(True)
             for _ in range(5):
@@ -658,7 +690,7 @@ def main():
     # thread, as INTEGRATION.md prescribes; the passes of different contexts overlap on the GPU (each has its own
     # streams), which hides the per-pass launch gaps and the host round trip that bound the single-stream figure.
     in_flight = None
-    if world == 1 and args.inflight > 1:
+    if world == 1 and args.full and args.inflight > 1:
         try:
             import threading
             ctxs = [ctx] + [_capi.Context(local_rank) for _ in range(args.inflight - 1)]
@@ -709,7 +741,7 @@ def main():
     # BASELINE configs[0]'s use of the reference (`-s /A/508/`: a ligand and its binding site) on the stand-in: the selection is
     # expanded (k_expand_small), selection_plus compacted into the pass's grid (k_compact_atoms), then search + per-pair kernel
     ligand_pass = None
-    if world == 1 and args.workload == 'standin':
+    if world == 1 and args.full and args.workload == 'standin':
         try:
             lig = (np.asarray(pc.res_seq)[np.asarray(pc.res_id)] == 508).astype(np.uint8)
             if lig.sum() > 0:
@@ -734,7 +766,7 @@ def main():
     # four different seeds of the same workload.  Measured with one context (latency of one structure) and with three
     # contexts on three host threads (upload / pass / download of consecutive structures overlap).
     end_to_end, e2e_host = None, None
-    if world == 1 and not args.no_end_to_end:
+    if world == 1 and args.full and not args.no_end_to_end:
         try:
             import threading
             if args.workload == 'standin':
@@ -830,7 +862,7 @@ def main():
             end_to_end = {'error': repr(exc)}
     # the other single-GPU configurations of BASELINE.json (stand-in whole / ligand, rings): GPU parts here, CPU parts with the baselines below
     other_configs = None
-    if world == 1 and args.workload == 'config3' and not args.no_other_configs:
+    if world == 1 and args.full and args.workload == 'config3' and not args.no_other_configs:
         try:
             other_configs = other_single_gpu_configs(args, local_rank)
         except Exception as exc:   # never lose the main line over the extra measurement
@@ -871,7 +903,7 @@ def main():
     #     all-reduce of the residue sets are inside every timed step
     # (c) at N = 8 with the default workload: BASELINE configs[3] itself, 250 000 atoms per GPU = 2 M atoms
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         multi = {}
         try:
             from arpeggio_amd import sharding
@@ -993,7 +1025,7 @@ def main():
         except Exception as exc:   # never lose the main line over the extra measurements
             multi['error'] = repr(exc)      # (a rank that fails alone leaves the others in a collective: the rendezvous' time-out ends the run)
 
-    if world == 1 and args.workload == 'config3' and args.atoms == 100_000 and not args.no_other_configs and not args.no_config4:
+    if world == 1 and args.full and args.workload == 'config3' and args.atoms == 100_000 and not args.no_other_configs and not args.no_config4:
         try:
             c4 = config4_single_gpu(args, local_rank)
             multi = {'config4_strong': dict(c4, scaling='strong')}
@@ -1023,111 +1055,113 @@ def main():
     ms_per_step = elapsed / timed_steps * 1e3
     value = cand_all * timed_steps / elapsed
 
-    # ---------------- roofline of the dominant kernel (rank 0) ----------------
-    # The dominant kernel is the one with the longest HIP-event duration in this run; its bytes are SURVEY 8d's compulsory
-    # bytes of that stage (survey_8d_bytes: no intermediate pair list).  roofline_all_kernels gives every kernel of the pass
-    # under both byte models, roofline_pass the whole pass (140 N + 16 P over ms_per_step), roofline_valu the issue-rate view.
-    per_kernel = {k: (v['ms'] / max(v['launches'], 1)) for k, v in ktimes.items() if v['launches']}
-    candidates_for_dominant = {k: per_kernel[k] for k in ('bin', 'search', 'sift', 'mark_search') if k in per_kernel}
-    dom = max(candidates_for_dominant, key=candidates_for_dominant.get)
-    dom_tie = None
-    try:      # two kernels within 3 % of each other by HIP events (search and per-pair kernel are): the committed rocprofv3 averages decide
-        pj0 = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
-        if args.atoms == 100_000 and world == 1 and args.workload == 'config3':
-            order = sorted(candidates_for_dominant, key=candidates_for_dominant.get, reverse=True)
-            if len(order) > 1 and candidates_for_dominant[order[1]] > 0.97 * candidates_for_dominant[order[0]]:
-                ns = {k: pj0['kernels'].get(f'k_{k}', {}).get('rocprof_avg_ns') for k in order[:2]}
-                if all(ns.values()):
-                    dom = max(order[:2], key=lambda k: ns[k])
-                    dom_tie = {k: round(candidates_for_dominant[k], 5) for k in order[:2]}
-    except (OSError, ValueError, KeyError):
-        pass
-    dom_ms = candidates_for_dominant[dom]
-    ncell = st['cells']
-    n_h = int(pc.h_xyz.shape[0]) if getattr(pc, 'h_xyz', None) is not None else 0
+    per_kernel, roofline, roofline_all, roofline_valu, roofline_pass = {}, None, None, None, None
+    if args.full:
+        # ---------------- roofline of the dominant kernel (rank 0) ----------------
+        # The dominant kernel is the one with the longest HIP-event duration in this run; its bytes are SURVEY 8d's compulsory
+        # bytes of that stage (survey_8d_bytes: no intermediate pair list).  roofline_all_kernels gives every kernel of the pass
+        # under both byte models, roofline_pass the whole pass (140 N + 16 P over ms_per_step), roofline_valu the issue-rate view.
+        per_kernel = {k: (v['ms'] / max(v['launches'], 1)) for k, v in ktimes.items() if v['launches']}
+        candidates_for_dominant = {k: per_kernel[k] for k in ('bin', 'search', 'sift', 'mark_search') if k in per_kernel}
+        dom = max(candidates_for_dominant, key=candidates_for_dominant.get)
+        dom_tie = None
+        try:      # two kernels within 3 % of each other by HIP events (search and per-pair kernel are): the committed rocprofv3 averages decide
+            pj0 = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
+            if args.atoms == 100_000 and world == 1 and args.workload == 'config3':
+                order = sorted(candidates_for_dominant, key=candidates_for_dominant.get, reverse=True)
+                if len(order) > 1 and candidates_for_dominant[order[1]] > 0.97 * candidates_for_dominant[order[0]]:
+                    ns = {k: pj0['kernels'].get(f'k_{k}', {}).get('rocprof_avg_ns') for k in order[:2]}
+                    if all(ns.values()):
+                        dom = max(order[:2], key=lambda k: ns[k])
+                        dom_tie = {k: round(candidates_for_dominant[k], 5) for k in order[:2]}
+        except (OSError, ValueError, KeyError):
+            pass
+        dom_ms = candidates_for_dominant[dom]
+        ncell = st['cells']
+        n_h = int(pc.h_xyz.shape[0]) if getattr(pc, 'h_xyz', None) is not None else 0
 
-    def n_of(k):
-        return st['binned'] if k != 'mark_search' else pc.n_atoms
-    b_alg = survey_8d_bytes(dom, n_of(dom), ncell, emitted)
-    achieved = b_alg / (dom_ms * 1e-3) / 1e9
-    # HBM bytes and VALU instructions per launch from the PMC counters of the last committed rocprofv3 run
-    # (profiles/pmc_traffic.json, written by tools/export_profile.py; separate --pmc passes, gfx950 FETCH_SIZE correction applied)
-    pj = None
-    try:
-        pj = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
-        if not (args.atoms == 100_000 and world == 1 and args.workload == 'config3'):
-            pj = None
-    except (OSError, ValueError):
+        def n_of(k):
+            return st['binned'] if k != 'mark_search' else pc.n_atoms
+        b_alg = survey_8d_bytes(dom, n_of(dom), ncell, emitted)
+        achieved = b_alg / (dom_ms * 1e-3) / 1e9
+        # HBM bytes and VALU instructions per launch from the PMC counters of the last committed rocprofv3 run
+        # (profiles/pmc_traffic.json, written by tools/export_profile.py; separate --pmc passes, gfx950 FETCH_SIZE correction applied)
         pj = None
-    traffic = traffic_src = None
-    committed = None
-    if pj is not None and f'k_{dom}' in pj.get('kernels', {}):
-        traffic = pj['kernels'][f'k_{dom}'].get('hbm_bytes_per_launch')
-        traffic_src = pj.get('source')
-        ns = pj['kernels'][f'k_{dom}'].get('rocprof_avg_ns')
-        if ns:      # the same figure with rocprofv3's average duration of the committed profile (HIP-event brackets read 1 - 2 us long)
-            committed = {'avg_launch_ms': round(ns * 1e-6, 5), 'achieved': round(b_alg / (ns * 1e-9) / 1e9, 2),
-                         'frac': round(b_alg / (ns * 1e-9) / 1e9 / HBM_PEAK_GBS, 6), 'source': pj.get('source')}
-    # The number that actually bounds these kernels: VALU issue.  SQ_INSTS_VALU of the committed PMC run (per launch) / launch duration
-    # against the MEASURED issue rates of this chip (tools/micro/valu_issue.hip -> profiles/round6_valu_issue.json): a wave64
-    # instruction of the plain VOP2 / f32-FMA kind issues every ~2.4 cycles per SIMD (SIMD-32 x 2 passes: 1.0e9 /s/SIMD), but packed
-    # f32, f64, compares, carries, three-operand integer forms and v_readlane — what the distance loop of k_search and the float64
-    # geometry of k_sift are made of — every ~4.2 cycles (0.58e9 /s/SIMD).  `frac` is against the full rate (a lower bound of how busy
-    # the VALUs are), `frac_half_rate` against the half rate (an upper bound); through round 5 an assumed 1024 x 2.4 GHz / 4 stood here.
-    VALU_PEAK, VALU_PEAK_HALF, valu_src = 1024 * 2.4e9 / 2.0, 1024 * 2.4e9 / 4.0, 'assumed: no profiles/round6_valu_issue.json'
-    try:
-        vj = json.load(open(os.path.join(ROOT, 'profiles', 'round6_valu_issue.json')))
-        VALU_PEAK = float(vj['valu_issue_peak_per_s_chip'])
-        VALU_PEAK_HALF = float(vj['valu_issue_half_rate_per_s_per_simd']) * int(vj['simds'])
-        valu_src = 'measured: profiles/round6_valu_issue.json (tools/micro/valu_issue.hip, all 1024 SIMDs, 8 waves per SIMD)'
-    except (OSError, ValueError, KeyError):
-        pass
-    roofline_valu = None
-    if pj is not None:
-        roofline_valu = {'issue_peak_per_s': VALU_PEAK, 'issue_peak_half_rate_per_s': VALU_PEAK_HALF, 'peak_source': valu_src,
-                         'source': f'instruction counts from the committed profile, NOT this run ({pj.get("source")}); durations of this run', 'kernels': {}}
-        total_insts = 0
-        for k_, ms_ in candidates_for_dominant.items():
-            pv = pj['kernels'].get(f'k_{k_}', {})
-            if 'valu_insts_per_launch' in pv:
-                total_insts += pv['valu_insts_per_launch']
-                rate = pv['valu_insts_per_launch'] / (ms_ * 1e-3)
-                roofline_valu['kernels'][f'k_{k_}'] = {'valu_wave_instructions_per_launch': pv['valu_insts_per_launch'],
-                                                       'frac': round(rate / VALU_PEAK, 4), 'frac_half_rate': round(rate / VALU_PEAK_HALF, 4)}
-        if total_insts:
-            roofline_valu['pass'] = {'valu_wave_instructions_per_pass': total_insts, 'ms_per_step': round(ms_per_step, 4),
-                                     'frac': round(total_insts / (ms_per_step * 1e-3) / VALU_PEAK, 4),
-                                     'frac_half_rate': round(total_insts / (ms_per_step * 1e-3) / VALU_PEAK_HALF, 4)}
-    roofline = {'kernel': f'k_{dom}', 'bound': 'hbm', 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                'frac': round(achieved / HBM_PEAK_GBS, 6), 'traffic': traffic,
-                'traffic_source': (None if traffic_src is None else f'committed profile, NOT this run: {traffic_src}'),
-                'algorithmic_bytes_per_launch': int(b_alg),
-                'bytes_model': {'bin': 'SURVEY 8d bin + sort / scatter passes: 92 N', 'search': 'SURVEY 8d: each sorted record once, 32 N + 4 (C + 1); the 8 B / pair list it writes is an intermediate of the split design, not counted',
-                                'sift': 'SURVEY 8d: side arrays + output records, 16 N + 16 P; the pair list and the record gathers are not counted',
-                                'mark_search': '32 N + 4 (C + 1)'}[dom],
-                'avg_launch_ms': round(dom_ms, 5), 'with_rocprofv3_duration_of_the_committed_profile': committed,
-                'dominant_kernel_rule': 'longest average HIP-event duration among the kernels of the pass in this run (kernel_ms); two kernels within 3 % of each other: the one '
-                                        'with the longer rocprofv3 average in the committed profile' + (' — applied here: %s' % dom_tie if dom_tie else ''),
-                'note': 'VALU-issue-bound geometry kernels (roofline_valu); the HBM fraction is small by construction: register-tiled pair tests '
-                        'move ~35 MB per 100 k-atom pass (SURVEY 8d)'}
+        try:
+            pj = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
+            if not (args.atoms == 100_000 and world == 1 and args.workload == 'config3'):
+                pj = None
+        except (OSError, ValueError):
+            pj = None
+        traffic = traffic_src = None
+        committed = None
+        if pj is not None and f'k_{dom}' in pj.get('kernels', {}):
+            traffic = pj['kernels'][f'k_{dom}'].get('hbm_bytes_per_launch')
+            traffic_src = pj.get('source')
+            ns = pj['kernels'][f'k_{dom}'].get('rocprof_avg_ns')
+            if ns:      # the same figure with rocprofv3's average duration of the committed profile (HIP-event brackets read 1 - 2 us long)
+                committed = {'avg_launch_ms': round(ns * 1e-6, 5), 'achieved': round(b_alg / (ns * 1e-9) / 1e9, 2),
+                             'frac': round(b_alg / (ns * 1e-9) / 1e9 / HBM_PEAK_GBS, 6), 'source': pj.get('source')}
+        # The number that actually bounds these kernels: VALU issue.  SQ_INSTS_VALU of the committed PMC run (per launch) / launch duration
+        # against the MEASURED issue rates of this chip (tools/micro/valu_issue.hip -> profiles/round6_valu_issue.json): a wave64
+        # instruction of the plain VOP2 / f32-FMA kind issues every ~2.4 cycles per SIMD (SIMD-32 x 2 passes: 1.0e9 /s/SIMD), but packed
+        # f32, f64, compares, carries, three-operand integer forms and v_readlane — what the distance loop of k_search and the float64
+        # geometry of k_sift are made of — every ~4.2 cycles (0.58e9 /s/SIMD).  `frac` is against the full rate (a lower bound of how busy
+        # the VALUs are), `frac_half_rate` against the half rate (an upper bound); through round 5 an assumed 1024 x 2.4 GHz / 4 stood here.
+        VALU_PEAK, VALU_PEAK_HALF, valu_src = 1024 * 2.4e9 / 2.0, 1024 * 2.4e9 / 4.0, 'assumed: no profiles/round6_valu_issue.json'
+        try:
+            vj = json.load(open(os.path.join(ROOT, 'profiles', 'round6_valu_issue.json')))
+            VALU_PEAK = float(vj['valu_issue_peak_per_s_chip'])
+            VALU_PEAK_HALF = float(vj['valu_issue_half_rate_per_s_per_simd']) * int(vj['simds'])
+            valu_src = 'measured: profiles/round6_valu_issue.json (tools/micro/valu_issue.hip, all 1024 SIMDs, 8 waves per SIMD)'
+        except (OSError, ValueError, KeyError):
+            pass
+        roofline_valu = None
+        if pj is not None:
+            roofline_valu = {'issue_peak_per_s': VALU_PEAK, 'issue_peak_half_rate_per_s': VALU_PEAK_HALF, 'peak_source': valu_src,
+                             'source': f'instruction counts from the committed profile, NOT this run ({pj.get("source")}); durations of this run', 'kernels': {}}
+            total_insts = 0
+            for k_, ms_ in candidates_for_dominant.items():
+                pv = pj['kernels'].get(f'k_{k_}', {})
+                if 'valu_insts_per_launch' in pv:
+                    total_insts += pv['valu_insts_per_launch']
+                    rate = pv['valu_insts_per_launch'] / (ms_ * 1e-3)
+                    roofline_valu['kernels'][f'k_{k_}'] = {'valu_wave_instructions_per_launch': pv['valu_insts_per_launch'],
+                                                           'frac': round(rate / VALU_PEAK, 4), 'frac_half_rate': round(rate / VALU_PEAK_HALF, 4)}
+            if total_insts:
+                roofline_valu['pass'] = {'valu_wave_instructions_per_pass': total_insts, 'ms_per_step': round(ms_per_step, 4),
+                                         'frac': round(total_insts / (ms_per_step * 1e-3) / VALU_PEAK, 4),
+                                         'frac_half_rate': round(total_insts / (ms_per_step * 1e-3) / VALU_PEAK_HALF, 4)}
+        roofline = {'kernel': f'k_{dom}', 'bound': 'hbm', 'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                    'frac': round(achieved / HBM_PEAK_GBS, 6), 'traffic': traffic,
+                    'traffic_source': (None if traffic_src is None else f'committed profile, NOT this run: {traffic_src}'),
+                    'algorithmic_bytes_per_launch': int(b_alg),
+                    'bytes_model': {'bin': 'SURVEY 8d bin + sort / scatter passes: 92 N', 'search': 'SURVEY 8d: each sorted record once, 32 N + 4 (C + 1); the 8 B / pair list it writes is an intermediate of the split design, not counted',
+                                    'sift': 'SURVEY 8d: side arrays + output records, 16 N + 16 P; the pair list and the record gathers are not counted',
+                                    'mark_search': '32 N + 4 (C + 1)'}[dom],
+                    'avg_launch_ms': round(dom_ms, 5), 'with_rocprofv3_duration_of_the_committed_profile': committed,
+                    'dominant_kernel_rule': 'longest average HIP-event duration among the kernels of the pass in this run (kernel_ms); two kernels within 3 % of each other: the one '
+                                            'with the longer rocprofv3 average in the committed profile' + (' — applied here: %s' % dom_tie if dom_tie else ''),
+                    'note': 'VALU-issue-bound geometry kernels (roofline_valu); the HBM fraction is small by construction: register-tiled pair tests '
+                            'move ~35 MB per 100 k-atom pass (SURVEY 8d)'}
 
-    # the same figure for every big kernel of the pass (informational; `roofline` above is the dominant one)
-    roofline_all = {}
-    for k, ms in candidates_for_dominant.items():
-        b8 = survey_8d_bytes(k, n_of(k), ncell, emitted)
-        bi = algorithmic_bytes(k, n_of(k), ncell, emitted, n_h)
-        roofline_all[f'k_{k}'] = {'avg_launch_ms': round(ms, 5), 'survey_8d_bytes_per_launch': int(b8),
-                                  'frac': round(b8 / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
-                                  'bytes_as_implemented': int(bi), 'frac_as_implemented': round(bi / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)}
-    b_pass = 140 * st['binned'] + 16 * emitted
-    roofline_pass = {'bytes_per_pass': int(b_pass), 'bytes_model': 'SURVEY 8d: B_alg = 140 N + 16 P (grid build included)', 'ms_per_step': round(ms_per_step, 4),
-                     'achieved': round(b_pass / (ms_per_step * 1e-3) / 1e9, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': round(b_pass / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)} if world == 1 else None
+        # the same figure for every big kernel of the pass (informational; `roofline` above is the dominant one)
+        roofline_all = {}
+        for k, ms in candidates_for_dominant.items():
+            b8 = survey_8d_bytes(k, n_of(k), ncell, emitted)
+            bi = algorithmic_bytes(k, n_of(k), ncell, emitted, n_h)
+            roofline_all[f'k_{k}'] = {'avg_launch_ms': round(ms, 5), 'survey_8d_bytes_per_launch': int(b8),
+                                      'frac': round(b8 / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
+                                      'bytes_as_implemented': int(bi), 'frac_as_implemented': round(bi / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)}
+        b_pass = 140 * st['binned'] + 16 * emitted
+        roofline_pass = {'bytes_per_pass': int(b_pass), 'bytes_model': 'SURVEY 8d: B_alg = 140 N + 16 P (grid build included)', 'ms_per_step': round(ms_per_step, 4),
+                         'achieved': round(b_pass / (ms_per_step * 1e-3) / 1e9, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                         'frac': round(b_pass / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 6)} if world == 1 else None
 
     # ---------------- CPU baseline: the C oracle on one host core, bounded sample ----------------
     gpu_legs_s = t_gpu_legs_done - t_gpu_legs_begin
     cpu = None
-    if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only, as the bench contract says)
+    if args.full and not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only, as the bench contract says)
         import oracle
         ns = min(args.cpu_sample_atoms, args.atoms)
         spc = synth.config3(ns, seed=3) if (world > 1 or (ns != args.atoms and args.workload == 'config3')) else pc
@@ -1233,11 +1267,10 @@ def main():
             other_configs['config4_2m_atoms']['cpu_baseline'] = cb
     if ligand_pass is None and other_configs is not None:
         ligand_pass = other_configs.get('standin_ligand')
-    e2e_ms_sorted = (end_to_end or {}).get('ms_per_structure')
     line = {
         'metric': 'evaluated atom-pairs/s', 'value': round(value, 1), 'unit': 'candidate atom-pairs/s',
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
-        'timed_steps': timed_steps, 'timed_region_s': round(elapsed, 3), 'setup_passes': SETUP_PASSES, 'untimed_trial_steps': args.steps,
+        'timed_steps': timed_steps, 'timed_region_s': round(elapsed, 6), 'setup_passes': SETUP_PASSES,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64 distance test / f32+f64 SIFt',
         'data': 'synthetic',
         'config': {'workload': workload, 'atoms_per_gpu': args.atoms, 'cutoff_A': args.cutoff, 'vdw_comp': args.vdw_comp,
@@ -1246,39 +1279,43 @@ def main():
                                                         f'{"; BASELINE configs[3]" if args.atoms * world == 2_000_000 else ""}), one-cell halo over RCCL')},
         'step_definition': 'one whole run_arpeggio pass over the resident structure that BUILDS its contact grid (k_compact_atoms + k_search + k_sift_planes, '
                            'arp_set_grid_reuse(0)); nothing a pass made is reused by the next one',
-        # wall clock per structure = a FRESH structure end to end, canonical order included (end_to_end); null when that leg was skipped
-        'wall_clock_per_structure_ms': e2e_ms_sorted,
-        'wall_clock_per_structure_definition': 'end_to_end.ms_per_structure: upload + first pass + device sort + one-copy fetch of all five bags, new structure every step',
-        'run_arpeggio_on_an_unseen_structure_ms': (end_to_end or {}).get('run_arpeggio_on_an_unseen_structure_ms'),
         'pairs': {'candidates': cand_all, 'accepted': acc_all, 'contacts_emitted': emitted_all,
                   'expansion_candidates_6A': exp_all, 'bags': counts},
         'accepted_pairs_per_s': round(acc_all * timed_steps / elapsed, 1),
-        'kernel_ms': {k: round(v, 5) for k, v in per_kernel.items()},
-        'kernel_launches_per_step': {k: v['launches'] / args.steps for k, v in ktimes.items() if v['launches']},
-        'ms_per_step_profiled_pass': round(elapsed_profiled / args.steps * 1e3, 4),
-        'roofline_all_kernels': roofline_all,
-        'throughput_several_in_flight': in_flight,
-        'cpu_baseline_all_cores': cpu_mc,
-        'cpu_baseline_python': cpu_py,
         'host_us_per_step': {k: round(v, 1) for k, v in host_times.items() if k != 'passes'} if world == 1 else None,
-        'launch_mode': 'three launches on one HIP stream per pass: k_compact_atoms (kernel_ms.bin: the contact grid of the pass), k_search, k_sift_planes (per-pair evaluation + ring/amide loops; kernel_ms: search / sift); the last launch publishes the counters; one host wait per step (pinned completion word, bounded spin); kernel_ms from a second pass of the same steps with HIP events (each bracket adds ~4 us to a small kernel; rocprofv3 averages are in profiles/)',
         'per_step_exchange': (None if world == 1 else ('selection_plus halo bits (P2P) + residue sets (all-reduce MAX) over RCCL' if args.staged_exchange else 'none: whole-structure selection, every rank knows selection_plus and the residue sets (DESIGN.md 6)')),
         'rccl_ranks_seen': rccl_ranks_seen,
-        'multi_gpu': multi,
         'halo_exchange_ms': round(halo_ms, 3), 'halo_exchange_bytes_sent_rank0': halo_bytes, 'shard_setup_ms': round(shard_setup_ms, 2), 'shard_setup_breakdown_ms': shard_timings,
         'halo_exchange': (halo_note if world > 1 else None),
         'scaling_note': (None if world == 1 else f'weak scaling: every GPU owns one config-3 cube of {args.atoms} atoms (+ a one-cell halo) — the workload of the N = 1 line with the same --atoms'),
         'setup_s': round(gen_s, 2), 'home_atoms_rank0': n_local_home,
-        'gpu_legs_s': round(gpu_legs_s, 2),
-        'end_to_end': end_to_end,
-        'end_to_end_ms_per_structure': e2e_ms_sorted,
-        'get_contacts_ms': (end_to_end or {}).get('get_contacts_ms'),
-        'roofline_valu': roofline_valu,
-        'roofline_pass': roofline_pass,
-        'pass_with_grid_kept': grid_kept, 'ligand_selection_pass': ligand_pass,
-        'configs': other_configs,
-        'roofline': roofline, 'cpu_baseline': cpu,
     }
+    if args.full:
+        e2e_ms_sorted = (end_to_end or {}).get('ms_per_structure')
+        line.update({
+            # wall clock per structure = a FRESH structure end to end, canonical order included (end_to_end); null when that leg was skipped
+            'wall_clock_per_structure_ms': e2e_ms_sorted,
+            'wall_clock_per_structure_definition': 'end_to_end.ms_per_structure: upload + first pass + device sort + one-copy fetch of all five bags, new structure every step',
+            'run_arpeggio_on_an_unseen_structure_ms': (end_to_end or {}).get('run_arpeggio_on_an_unseen_structure_ms'),
+            'kernel_ms': {k: round(v, 5) for k, v in per_kernel.items()},
+            'kernel_launches_per_step': {k: v['launches'] / args.steps for k, v in ktimes.items() if v['launches']},
+            'ms_per_step_profiled_pass': round(elapsed_profiled / args.steps * 1e3, 4),
+            'roofline_all_kernels': roofline_all,
+            'throughput_several_in_flight': in_flight,
+            'cpu_baseline_all_cores': cpu_mc,
+            'cpu_baseline_python': cpu_py,
+            'launch_mode': 'three launches on one HIP stream per pass: k_compact_atoms (kernel_ms.bin: the contact grid of the pass), k_search, k_sift_planes (per-pair evaluation + ring/amide loops; kernel_ms: search / sift); the last launch publishes the counters; one host wait per step (pinned completion word, bounded spin); kernel_ms from a second pass of the same steps with HIP events (each bracket adds ~4 us to a small kernel; rocprofv3 averages are in profiles/)',
+            'multi_gpu': multi,
+            'gpu_legs_s': round(gpu_legs_s, 2),
+            'end_to_end': end_to_end,
+            'end_to_end_ms_per_structure': e2e_ms_sorted,
+            'get_contacts_ms': (end_to_end or {}).get('get_contacts_ms'),
+            'roofline_valu': roofline_valu,
+            'roofline_pass': roofline_pass,
+            'pass_with_grid_kept': grid_kept, 'ligand_selection_pass': ligand_pass,
+            'configs': other_configs,
+            'roofline': roofline, 'cpu_baseline': cpu,
+        })
     if world > 1 and comm_device is not None and rccl_ranks_seen != world:
         line['error'] = f'the RCCL communicator holds {rccl_ranks_seen} ranks, not {world}: this is not an {world}-GPU measurement'
     print(json.dumps(line), flush=True)

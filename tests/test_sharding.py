@@ -232,8 +232,9 @@ def _worker(rank, world, port, q):
 @pytest.mark.parametrize('world,worker', [(2, '_worker'), (3, '_worker'), (2, '_worker_staged'), (3, '_worker_staged')])
 def test_gloo_halo_exchange_and_selection_combine(world, worker):
     """One process per rank over gloo: exchanged halos == global-knowledge halos, combined masks == global
-    _make_selection, union of owned results == unsharded result."""
-    import torch.multiprocessing as mp
+    _make_selection, union of owned results == unsharded result.  The ranks import torch; this process must not (its HIP
+    runtime and RCCL beside the library's crash at exit when the GPU tests share the process)."""
+    import multiprocessing as mp
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
@@ -319,7 +320,7 @@ def _launch_bench_dry(nproc, port, extra_env=None, timeout=240):
     env = dict(os.environ, MASTER_ADDR='127.0.0.1')
     env.update(extra_env or {})
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={nproc}', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(nproc), '--steps', '5', '--warmup', '1', '--dry-run']
+           '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(nproc), '--steps', '5', '--warmup', '1', '--full', '--dry-run']
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=root)
 
 
@@ -356,10 +357,10 @@ def test_bench_gpus_2_as_the_driver_launches_it_up_to_the_first_hip_call():
     assert len({r['uid_crc32'] for r in eight['ranks']}) == 1 and eight['config'] == four['config']
     # the same per-GPU workload at N = 1 (what SCALE divides by) as at N > 1
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--dry-run'], capture_output=True, text=True, timeout=120, cwd=root)
+    one = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--dry-run'], capture_output=True, text=True, timeout=120, cwd=root)
     one_line = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith('{')][-1])
     assert one_line['config'] == first['config'] == four['config'] and one_line['config']['atoms_per_gpu'] == 100_000
-    # the strong-scaling leg (BASELINE configs[3]: ONE 2 M-atom structure cut into N slabs) is part of the line at EVERY N, N = 1 included
+    # the strong-scaling leg (BASELINE configs[3]: ONE 2 M-atom structure cut into N slabs) is part of the --full line at EVERY N, N = 1 included
     for n, line in ((1, one_line), (2, first), (4, four), (8, eight)):
         leg = line['legs']['config4_strong']
         assert leg['n_gpus'] == n and leg['atoms_per_gpu'] * n == 2_000_000 and leg['scaling'] == 'strong' and '2000000 atoms' in leg['workload']
