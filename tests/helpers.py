@@ -67,6 +67,18 @@ def deg_close(a, b, tol=1e-4):
     return bool(np.all(both_nan | (np.abs(a - b) <= tol)))
 
 
+def planes_differences(got, exp, keys_exact, keys_angle, tol=1e-4):
+    """Columns of a ring / amide bag that differ from the expected one: keys_exact compared as arrays, keys_angle by deg_close."""
+    return [k for k in keys_exact if not np.array_equal(got[k], exp[k])] + [k for k in keys_angle if not deg_close(got[k], exp[k], tol)]
+
+
+def assert_planes_equal(got, exp, keys_exact, keys_angle, tol=1e-4):
+    for k in keys_exact:
+        assert np.array_equal(got[k], exp[k]), k
+    for k in keys_angle:
+        assert deg_close(got[k], exp[k], tol), k
+
+
 def known_answer_packs():
     """Tiny packs that isolate one branch each of interactions.py:693-936 (used on CPU and GPU)."""
     from arpeggio_amd.core import config

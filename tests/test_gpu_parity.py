@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import assert_planes_equal as _assert_planes_equal
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,14 +28,6 @@ def _assert_contacts_equal(got, exp):
     for k in ('i', 'j', 'sift', 'ctype'):
         assert np.array_equal(got[k], exp[k]), k
     assert np.array_equal(got['dist'].view(np.uint32), exp['dist'].view(np.uint32)), 'distance not bit-identical'
-
-
-def _assert_planes_equal(got, exp, keys_exact, keys_angle, tol=1e-4):
-    from helpers import deg_close
-    for k in keys_exact:
-        assert np.array_equal(got[k], exp[k]), k
-    for k in keys_angle:
-        assert deg_close(got[k], exp[k], tol), k
 
 
 @pytest.mark.parametrize('n,seed', [(3000, 1), (20000, 3)])
