@@ -86,6 +86,9 @@ struct Grid {
 };
 
 struct Bag {  // outputs of one ring/amide kernel, resident in HBM until fetched
+    const int slot;           // its record counter (C_AP ... C_GP)
+    const bool d, f;          // its columns besides a, b, u0-u2: d0-d3 (double), f0-f2 (float)
+    Bag(int slot_, bool d_, bool f_) : slot(slot_), d(d_), f(f_) {}
     // the arrays are sub-ranges of ONE allocation (slab), so that a small bag reaches the host with one copy
     DevBuf<uint8_t> slab;
     DevBuf<int> a, b;
@@ -102,6 +105,14 @@ struct Bag {  // outputs of one ring/amide kernel, resident in HBM until fetched
     void release() { a.release(); b.release(); d0.release(); d1.release(); d2.release(); d3.release(); f0.release();
                      f1.release(); f2.release(); u0.release(); u1.release(); u2.release(); slab.release(); cap = 0; slab_bytes = 0;
                      valid = false; staged_version = 0; }
+};
+
+// scratch of the radix sort (arp_sort.h: radix_sort): keys and payload double-buffered, digit table, digit totals
+struct SortScratch {
+    DevBuf<unsigned long long> key[2], val[2];
+    DevBuf<int> table;
+    DevBuf<long long> total;
+    void release() { key[0].release(); key[1].release(); val[0].release(); val[1].release(); table.release(); total.release(); }
 };
 
 // the used prefixes of every array of every bag, gathered into one device buffer for one copy to the host
@@ -202,6 +213,29 @@ enum Slot { SLOT_BIN = 0, SLOT_SCAN = 1, SLOT_SCATTER = 2, SLOT_UNUSED = 3, SLOT
 
 struct EventPair { int slot; hipEvent_t a, b; };
 
+// What the contact grid of a whole-structure pass was built from: a pass with an equal key reuses it (arp_ctx::grid_reuse)
+struct GridKey {
+    double radius = 0.0;
+    uint64_t static_epoch = 0, sel_epoch = 0;
+    bool fuse_sets = false, init_plus = false, all_res = false;
+    bool operator==(const GridKey& o) const {
+        return radius == o.radius && static_epoch == o.static_epoch && sel_epoch == o.sel_epoch && fuse_sets == o.fuse_sets &&
+               init_plus == o.init_plus && all_res == o.all_res;
+    }
+};
+// What a balance hint of k_search (sb_tile) was made for: grid, launch shape, and what its entries are (by_atoms: atom
+// positions, k_balance_atoms; else tiles, k_balance_blocks)
+struct HintKey {
+    bool by_atoms = false;
+    uint64_t static_epoch = 0, sel_epoch = 0;
+    double radius = 0.0;
+    int blocks = 0, tx = 0;
+    bool operator==(const HintKey& o) const {
+        return by_atoms == o.by_atoms && static_epoch == o.static_epoch && sel_epoch == o.sel_epoch && radius == o.radius &&
+               blocks == o.blocks && tx == o.tx;
+    }
+};
+
 }  // namespace
 
 struct arp_ctx {
@@ -278,18 +312,12 @@ struct arp_ctx {
     bool s_cell_valid = false;                  // ... written by the build of the grid that is in place
     DevBuf<int> sb_tile;                        // k_search's runs of tiles with equal numbers of atoms (k_balance_blocks): a hint from the pass before
     bool sb_valid = false;
-    uint64_t sb_static_epoch = 0, sb_sel_epoch = 0;
-    double sb_radius = 0.0;
-    int sb_blocks = 0, sb_tx = 0;
-    bool sb_whole = false;
-    bool sb_by_atoms = false, sb_seen_by_atoms = false;      // what the entries of sb_tile are: tiles, or atom positions (k_balance_atoms)
+    HintKey sb_key;                                          // ... what it was made for
     DevBuf<int> sb_cw, sb_cwp, sb_sums;                      // weight per cell, its running sum, tile totals of that scan
-    // (the grid key of the last pass that ran WITHOUT a hint: the hint is worked out by the second such pass over one grid — a
+    // (the key of the last pass that ran WITHOUT a hint: the hint is worked out by the second such pass over one grid — a
     // structure that is evaluated once, the usual case, never pays for it)
     bool sb_seen = false;
-    uint64_t sb_seen_static_epoch = 0, sb_seen_sel_epoch = 0;
-    double sb_seen_radius = 0.0;
-    int sb_seen_blocks = 0, sb_seen_tx = 0;
+    HintKey sb_seen_key;
     unsigned int compact_epoch = 0;
     bool static_dirty = true;
     // The contact grid of a WHOLE-STRUCTURE pass (every atom selected: selection_plus = all atoms, I:1395 / 1407) depends on the
@@ -299,9 +327,9 @@ struct arp_ctx {
     // NeighborSearch(selection_plus) (I:1442).  arp_set_grid_reuse(ctx, 0) switches the reuse off (bench.py reports both).
     bool grid_reuse = true;
     bool sort_after_pass = false;     // arp_set_sort_after_pass
-    bool cg_valid = false, cg_fuse = false, cg_init_plus = false, cg_all_res = false, cg_pending = false, cg_reused = false;
-    double cg_radius = 0.0;
-    uint64_t static_epoch = 0, sel_epoch = 0, cg_static_epoch = 0, cg_sel_epoch = 0;
+    bool cg_valid = false, cg_pending = false, cg_reused = false;
+    GridKey cg_key;                   // what the grid in place was built from
+    uint64_t static_epoch = 0, sel_epoch = 0;
     int64_t cg_binned = 0;
     double host_enqueue_us = 0, host_wait_us = 0;   // arp_run_launch: time spent enqueueing / waiting (arp_get_host_times)
     int64_t host_passes = 0;
@@ -330,10 +358,7 @@ struct arp_ctx {
     DevBuf<uint8_t> out_ct;
     int64_t n_contacts = 0;
     // ---- canonical (i, j) order of the atom-atom bag, made on the device (arp_sort.h; arp_atom_contacts_sort)
-    DevBuf<unsigned long long> sort_key[2];
-    DevBuf<unsigned long long> sort_val[2];
-    DevBuf<int> sort_table;
-    DevBuf<long long> sort_total;
+    SortScratch sort_aa;
     DevBuf<uint8_t> sorted_slab;        // the five sorted columns (+ the packed ring / amide bags of a packed fetch) in one piece
     size_t srt_off[5] = {0, 0, 0, 0, 0};  // byte offsets of i, j, distance, SIFt, contact type in sorted_slab
     size_t srt_bytes = 0;               // bytes of the five columns
@@ -382,11 +407,10 @@ struct arp_ctx {
     bool fuse_sets = false;        // the contact-grid build of the current pass also makes the residue / ring / amide sets
     bool init_plus_in_bin = false; // ... and writes selection_plus = selection (whole-structure selection)
     // ---- device-resident result bags of the ring / amide kernels
-    Bag bag_ap, bag_pp, bag_gg, bag_gp;
+    Bag bag_ap{C_AP, true, false}, bag_pp{C_PP, true, false}, bag_gg{C_GG, false, true}, bag_gp{C_GP, true, false};
     DevBuf<uint32_t> bag_perm_big[4];   // ... of a bag beyond BAG_SORT_MAX records (bag_order_large)
-    DevBuf<unsigned long long> bagsort_key[2], bagsort_val[2];
-    DevBuf<int> bagsort_table, bagsort_i, bagsort_j;
-    DevBuf<long long> bagsort_total;
+    SortScratch sort_bags;                // ... the radix sort's scratch for them
+    DevBuf<int> bagsort_i, bagsort_j;
     DevBuf<uint16_t> bagsort_s;
     DevBuf<uint8_t> bagsort_ct;
     DevBuf<uint32_t> bag_perm;     // canonical order of the small ring / amide bags (k_bag_order), BAG_SORT_MAX indices per bag
@@ -462,6 +486,57 @@ int download(arp_ctx* c, T* dst, const T* src, size_t n) {
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : dflt;
+}
+
+// Every ARP_* switch of this file: read once per process, the first time one is asked for (sw()).  Default, clamp, meaning.
+// (arp_json.h reads ARP_EXPORT_THREADS / ARP_EXPORT_MMAP on every call.)
+struct Switches {
+    // ---- grids
+    int deterministic = env_int("ARP_DETERMINISTIC", 0);                        // 1: fixed order inside a cell (k_cellsort), centre grids by the general path
+    int chained_scan = env_int("ARP_CHAINED_SCAN", 1);                          // 0: large contact grids scan in two launches, never by k_scan_tiles_chained
+    int compact_512_max_rows = env_int("ARP_COMPACT_512_MAX_ROWS", 150000);     // k_compact_atoms: 512 rows per block up to this many atoms, 1024 beyond
+    // ---- contact search (k_search)
+    int search_blocks = env_int("ARP_SEARCH_BLOCKS", 0);                        // > 0: this many blocks (rounded up to a multiple of 8)
+    int search_cpw = std::max(1, env_int("ARP_SEARCH_CPW", 12));                // cells per wave, at most
+    int search_tile = env_int("ARP_SEARCH_TILE", -1);                           // -1: tiles of two cells on large grids, 1 / 2: always that tile
+    int search_tile_min_cells = env_int("ARP_SEARCH_TILE_MIN_CELLS", 60000);    // ... large: this many cells
+    int search_balance = env_int("ARP_SEARCH_BALANCE", -1);                     // blocks split atoms: -1 on sparse / clumped grids, 0 never, 1 always
+    int search_apb = std::max(8, env_int("ARP_SEARCH_APB", 128));               // ... atoms per block then
+    int balance_hint = env_int("ARP_SEARCH_BALANCE_HINT", 1);                   // 0: no balance hint from the passes before
+    int cell_weight_x16 = std::max(0, env_int("ARP_SEARCH_CELL_WEIGHT_X16", 64));   // k_balance_blocks: weight of a cell in sixteenths of an atom
+    int balance_hint_atoms = env_int("ARP_SEARCH_BALANCE_HINT_ATOMS", 1);       // 0: no hint for blocks that split atoms (k_balance_atoms)
+    int balance_hint_eager = env_int("ARP_SEARCH_BALANCE_HINT_EAGER", 0);       // 1: the hint is made by the first pass over a grid, not the second
+    int w_unit = std::max(0, env_int("ARP_SEARCH_W_UNIT", 100));                // k_cell_weights: wave instructions per unit of work,
+    int w_chunk = std::max(0, env_int("ARP_SEARCH_W_CHUNK", 85));               // ... per chunk,
+    int w_test_x8 = std::max(0, env_int("ARP_SEARCH_W_TEST_X8", 2));            // ... per eight distance tests
+    // ---- per-pair kernel (k_sift, k_sift_planes)
+    int sift_bpc = env_int("ARP_SIFT_BPC", 0);                                  // > 0: blocks per CU instead of the occupancy arp_create measured
+    int sift_ppb = std::max(64, env_int("ARP_SIFT_PPB", 256));                  // pairs per block the launch is sized for
+    int64_t stream_out_bytes = (int64_t)env_int("ARP_STREAM_OUT_MB", 96) << 20;  // streaming stores above this many bytes of records
+    int sift_shares = env_int("ARP_SIFT_SHARES", 1);                            // 0: equal blocks per pair-list segment, not by the last pass's sizes
+    int sift_seg_by_block = env_int("ARP_SIFT_SEG_BY_BLOCK", 0);                // 1: segment by block index even where blocks go round-robin over XCDs
+    // ---- ring / amide loops
+    int plane_ipw = std::max(1, env_int("ARP_PLANE_IPW", 4));                   // grid walks: rings / amides per wavefront
+    int plane_cpw = std::max(1, env_int("ARP_PLANE_CPW", 16));                  // list blocks of a pass: chunks of 64 entries per wave, at most
+    double plane_chunk_factor = env_int("ARP_PLANE_CHUNK_FACTOR_X10", 10) / 10.0;   // ... chunks per wave against the sift batches per wave
+    int planes_mode = env_int("ARP_PLANES_MODE", 0);                            // 0: the lists in the sift launch, 1: a kernel of their own on the second stream
+    int bag_lists = env_int("ARP_BAG_LISTS", 2);                                // arp_*_launch: bit k = loop k from its list, else by its grid walk
+    // ---- sorts and fetches
+    int sort_small = env_int("ARP_SORT_SMALL", 1);                              // 0: no one-launch sort of a small atom-atom bag (k_sort_small)
+    int sort_small_blocks = std::max(1, std::min(64, env_int("ARP_SORT_SMALL_BLOCKS", SORT_SMALL_BLOCKS)));   // ... its blocks
+    size_t fetch_direct_max = (size_t)std::max(0, env_int("ARP_FETCH_DIRECT_MAX_KB", 1024)) << 10;   // packed fetches up to this size by a kernel, not the copy engine
+    // ---- passes, uploads, waits
+    int inkernel_publish = env_int("ARP_INKERNEL_PUBLISH", 1);                  // 0: the counters of a pass by k_publish_counters, not by its last kernel
+    int spin_wait = env_int("ARP_SPIN_WAIT", 1);                                // 0: the end of a pass by hipStreamSynchronize, not by polling
+    int join_spin_us = env_int("ARP_JOIN_SPIN_US", 25);                         // polling for the upload's lists before a stream wait, microseconds
+    int grids_with_upload = env_int("ARP_GRIDS_WITH_UPLOAD", 1);                // 0: centre grids and lists of a blob in its first pass, not with the upload
+    int upload_aside = env_int("ARP_UPLOAD_ASIDE", 1);                          // 0: ... with the upload, but on the main stream
+    int lists_with_upload = env_int("ARP_LISTS_WITH_UPLOAD", 1);                // 0: only the grids with the upload, the lists in the first pass
+    int static_with_upload = env_int("ARP_STATIC_WITH_UPLOAD", 1);              // 0: a blob's static columns in its first pass, not ahead of the verdict
+};
+const Switches& sw() {
+    static const Switches s{};
+    return s;
 }
 
 inline int nblocks(int64_t work, int threads, int max_blocks = 2048) {
@@ -609,22 +684,23 @@ int grid_desc_for(arp_ctx* c, GridDesc& d, const double lo[3], const double hi[3
     return ARP_OK;
 }
 
-// exclusive scan of the cell histogram: one launch up to 32768 cells, two (tiles + fix-up) above
-int enqueue_scan(arp_ctx* c, Grid& G, u64* total_out = nullptr, hipStream_t st = nullptr) {
-    if (!st) st = c->stream;
-    const int ncell = G.d.ncell;
-    Prof p(c, SLOT_SCAN, st);
-    if (ncell <= 4096) {
-        hipLaunchKernelGGL((k_scan_small<4>), dim3(1), dim3(1024), 0, st, G.cnt.p, ncell, G.start.p, total_out);
-    } else if (ncell <= 16384) {
-        hipLaunchKernelGGL((k_scan_small<16>), dim3(1), dim3(1024), 0, st, G.cnt.p, ncell, G.start.p, total_out);
-    } else if (ncell <= 32768) {
-        hipLaunchKernelGGL((k_scan_small<32>), dim3(1), dim3(1024), 0, st, G.cnt.p, ncell, G.start.p, total_out);
-    } else {
-        // tiles of 16384 counters, two launches (a 1 M-atom contact grid has 10 tiles)
+// Exclusive scan of a cell histogram (in place when in == out): out[ncell] = the total, also written to *total_out if given.
+// The one choice of kernels for every grid: ONE 1024-thread block up to 32768 cells; above that tiles of 16384 counters and a
+// fix-up, two launches (a 1 M-atom contact grid has 10 tiles; their totals go to sums).  The caller brackets it with Prof.
+int enqueue_scan(arp_ctx* c, hipStream_t st, const int* in, int ncell, int* out, DevBuf<int>& sums, u64* total_out = nullptr) {
+    if (ncell > 32768) {
         const int ntiles = (ncell + TILE_CELLS - 1) / TILE_CELLS;
-        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, st, G.cnt.p, ncell, G.start.p, G.sums.p);
-        hipLaunchKernelGGL(k_scan_fix, dim3((ncell + 4095) / 4096), dim3(1024), 0, st, G.start.p, ncell, G.sums.p, ntiles, total_out);
+        HIPCHK(c, sums.reserve((size_t)ntiles + 2));
+        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, st, in, ncell, out, sums.p);
+        hipLaunchKernelGGL(k_scan_fix, dim3((ncell + 4095) / 4096), dim3(1024), 0, st, out, ncell, sums.p, ntiles, total_out);
+    } else if (in != out) {
+        if (ncell <= 4096) hipLaunchKernelGGL((k_scan_small<4>), dim3(1), dim3(1024), 0, st, in, ncell, out, total_out);
+        else if (ncell <= 16384) hipLaunchKernelGGL((k_scan_small<16>), dim3(1), dim3(1024), 0, st, in, ncell, out, total_out);
+        else hipLaunchKernelGGL((k_scan_small<32>), dim3(1), dim3(1024), 0, st, in, ncell, out, total_out);
+    } else {      // (no total_out in place)
+        if (ncell <= 4096) hipLaunchKernelGGL((k_scan_inplace<4>), dim3(1), dim3(1024), 0, st, out, ncell);
+        else if (ncell <= 16384) hipLaunchKernelGGL((k_scan_inplace<16>), dim3(1), dim3(1024), 0, st, out, ncell);
+        else hipLaunchKernelGGL((k_scan_inplace<32>), dim3(1), dim3(1024), 0, st, out, ncell);
     }
     return check_launch(c, "k_scan");
 }
@@ -665,15 +741,17 @@ int build_grid(arp_ctx* c, Grid& G, P pts, int n, const double lo[3], const doub
             CHK(check_launch(c, "k_bin"));
         }
     }
-    CHK(enqueue_scan(c, G));
+    {
+        Prof p(c, SLOT_SCAN);
+        CHK(enqueue_scan(c, c->stream, G.cnt.p, ncell, G.start.p, G.sums));
+    }
     {
         Prof p(c, SLOT_SCATTER);
         if (n > 0) {
             hipLaunchKernelGGL(k_scatter, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, G.cell_of.p, G.start.p, G.cnt.p, G.perm.p);
             // The order inside a cell does not change any result set (pairs are oriented by packed
             // id and callers sort); ARP_DETERMINISTIC=1 additionally fixes the device-side order.
-            static const int deterministic = env_int("ARP_DETERMINISTIC", 0);
-            if (deterministic)
+            if (sw().deterministic)
                 hipLaunchKernelGGL(k_cellsort, dim3(nblocks(ncell, 256)), dim3(256), 0, c->stream, ncell, G.start.p, G.perm.p);
             CHK(check_launch(c, "k_scatter/k_cellsort"));
         }
@@ -695,9 +773,8 @@ int join_upload_lists(arp_ctx* c, bool must = false) {
         // In front of the last launch of a pass: the host is tens of microseconds ahead of the device there (grid build and search
         // are queued), the lists a few short of done — asking again for a little while costs the device nothing, a wait on the
         // stream costs it ~6 us between search and per-pair kernel.
-        static const int spin_us = env_int("ARP_JOIN_SPIN_US", 25);
         const auto t0 = std::chrono::steady_clock::now();
-        while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < spin_us) {
+        while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < sw().join_spin_us) {
             if (hipEventQuery(c->ev_uplists) == hipSuccess) { c->uplists_pending = false; return ARP_OK; }
             (void)hipGetLastError();
         }
@@ -763,16 +840,9 @@ int ensure_static(arp_ctx* c, double radius = 0.0) {
             hipLaunchKernelGGL(k_static_bin, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->st_xyzm.p, d, hist, c->sp_cr.p);
         }
         CHK(check_launch(c, "k_prepare_static"));
-        if (d.ncell <= 4096) hipLaunchKernelGGL((k_scan_inplace<4>), dim3(1), dim3(1024), 0, c->stream, hist, d.ncell);
-        else if (d.ncell <= 16384) hipLaunchKernelGGL((k_scan_inplace<16>), dim3(1), dim3(1024), 0, c->stream, hist, d.ncell);
-        else if (d.ncell <= 32768) hipLaunchKernelGGL((k_scan_inplace<32>), dim3(1), dim3(1024), 0, c->stream, hist, d.ncell);
-        else {      // larger grids (a batch of structures side by side: 10^6 cells): tiles of 16384 counters, two launches — one block
-                    // walking them with a running carry was 177 us of a 64-structure batch's first pass
-            const int ntiles = (d.ncell + TILE_CELLS - 1) / TILE_CELLS;
-            HIPCHK(c, c->sp_sums.reserve((size_t)ntiles + 2));
-            hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, c->stream, hist, d.ncell, hist, c->sp_sums.p);
-            hipLaunchKernelGGL(k_scan_fix, dim3((d.ncell + 4095) / 4096), dim3(1024), 0, c->stream, hist, d.ncell, c->sp_sums.p, ntiles, (unsigned long long*)nullptr);
-        }
+        // (larger grids — a batch of structures side by side: 10^6 cells — by tiles: one block walking them with a running carry
+        // was 177 us of a 64-structure batch's first pass)
+        CHK(enqueue_scan(c, c->stream, hist, d.ncell, hist, c->sp_sums));
         hipLaunchKernelGGL(k_static_permute, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->sp_cr.p, hist, c->st_xyzm.p,
                            c->st_aux.p, c->st_qa.p, c->st_h.p, c->sp_xyzm.p, c->sp_aux.p, c->sp_qa.p, c->sp_h.p, c->sp_cell.p,
                            c->ahead_seq ? (const int*)c->upload_bad.p : (const int*)nullptr, c->ahead_seq);
@@ -801,6 +871,17 @@ StaticAtoms static_atoms(arp_ctx* c) {
     r.plus = c->sel_made ? c->plus.p : nullptr;
     r.all = (c->sel_made && c->sel_all) ? 1 : 0;
     return r;
+}
+
+// k_scan_scatter_atoms<S> for steps = S chunks of 16 x 256 cells of the start table in LDS (1 ... 9).  (The deduced return type
+// instantiates the chain where it is called, in the order S = 1 ... 9: the kernels keep their places in the code object.)
+template <int S = 1, class... Args>
+auto launch_scan_scatter(int steps, dim3 grid, hipStream_t st, Args... args) {
+    if (S == 9 || steps <= S) {
+        hipLaunchKernelGGL((k_scan_scatter_atoms<S>), grid, dim3(1024), S * 16384, st, args...);
+        return;
+    }
+    if constexpr (S < 9) launch_scan_scatter<S + 1>(steps, grid, st, args...);
 }
 
 // Grid over the atoms selected by the (req, forb) meta masks (or an explicit mask): three launches —
@@ -847,27 +928,13 @@ int build_atom_grid(arp_ctx* c, Grid& G, DevBuf<float4>& sx, DevBuf<int4>& sa, D
         if (ncell <= SCAN_LDS_CELLS) {   // start table in LDS: scan + scatter in one launch
             Prof p(c, SLOT_SCATTER, st);
             const int steps = (ncell + 16 * 256 - 1) / (16 * 256);
-#define LAUNCH_SS(S) hipLaunchKernelGGL((k_scan_scatter_atoms<S>), dim3(nb), dim3(1024), (S) * 16384, st, r, n, ncell, G.cell_rank.p, hist, \
-                                        G.start.p, total_out, sx.p, sa.p, rec, c->s_h.p, gm)
-            switch (steps) {
-                case 1: LAUNCH_SS(1); break;
-                case 2: LAUNCH_SS(2); break;
-                case 3: LAUNCH_SS(3); break;
-                case 4: LAUNCH_SS(4); break;
-                case 5: LAUNCH_SS(5); break;
-                case 6: LAUNCH_SS(6); break;
-                case 7: LAUNCH_SS(7); break;
-                case 8: LAUNCH_SS(8); break;
-                default: LAUNCH_SS(9); break;
-            }
-#undef LAUNCH_SS
+            launch_scan_scatter(steps, dim3(nb), st, r, n, ncell, G.cell_rank.p, hist, G.start.p, total_out, sx.p, sa.p, rec, c->s_h.p, gm);
             CHK(check_launch(c, "k_scan_scatter_atoms"));
         } else {
             {
                 Prof p(c, SLOT_SCAN, st);
                 const int ntiles = (ncell + TILE_CELLS - 1) / TILE_CELLS;
-                static const int chained = env_int("ARP_CHAINED_SCAN", 1);
-                if (chained && ntiles <= CHAIN_TILES && ntiles <= 2 * c->num_cu) {   // one launch: the tiles hand their totals on themselves (all resident at once)
+                if (sw().chained_scan && ntiles <= CHAIN_TILES && ntiles <= 2 * c->num_cu) {   // one launch: the tiles hand their totals on themselves (all resident at once)
                     bool fresh = false;
                     HIPCHK(c, G.chain.reserve(CHAIN_TILES, &fresh));
                     if (fresh || G.chain_epoch == 0xFFFFFFFFu) {   // new buffer, or the launch number wraps: no stale word may match a future one
@@ -877,11 +944,10 @@ int build_atom_grid(arp_ctx* c, Grid& G, DevBuf<float4>& sx, DevBuf<int4>& sa, D
                     ++G.chain_epoch;
                     hipLaunchKernelGGL(k_scan_tiles_chained, dim3(ntiles), dim3(1024), 0, st, hist, ncell, G.start.p, G.chain.p, G.chain_epoch, total_out,
                                        (int*)(c->d_ctr + ctr_dev(C_ERR)));
+                    CHK(check_launch(c, "k_scan"));
                 } else {
-                    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, st, hist, ncell, G.start.p, G.sums.p);
-                    hipLaunchKernelGGL(k_scan_fix, dim3((ncell + 4095) / 4096), dim3(1024), 0, st, G.start.p, ncell, G.sums.p, ntiles, total_out);
+                    CHK(enqueue_scan(c, st, hist, ncell, G.start.p, G.sums, total_out));
                 }
-                CHK(check_launch(c, "k_scan"));
             }
             Prof p(c, SLOT_SCATTER, st);
             hipLaunchKernelGGL(k_scatter_atoms, dim3(nblocks(n, 256)), dim3(256), 0, st, r, n, G.cell_rank.p, G.start.p, sx.p, sa.p, rec, c->s_h.p, gm);
@@ -918,8 +984,7 @@ int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t
     CHK(ensure_static(c, radius));
     if (n > 0) {
         Prof p(c, SLOT_BIN);
-        static const int compact_small_max = env_int("ARP_COMPACT_512_MAX_ROWS", 150000);
-        const int rows_per_block = n <= compact_small_max ? 512 : 1024;
+        const int rows_per_block = n <= sw().compact_512_max_rows ? 512 : 1024;
         const int nb = (n + rows_per_block - 1) / rows_per_block;
         bool fresh = false;
         HIPCHK(c, c->compact_chain.reserve((size_t)nb, &fresh));
@@ -968,8 +1033,7 @@ int search_blocks(const GridDesc& d, int cpw = 1) {
 // the CUs given three blocks have half as much work again as those given two, and the kernel lasts as long as the former
 // (100 k atoms: 38.3 -> 35.3 us with 768)
 int search_blocks_balanced(const arp_ctx* c, const GridDesc& d, int cpw) {
-    static const int forced = env_int("ARP_SEARCH_BLOCKS", 0);
-    if (forced > 0) return (forced + 7) & ~7;
+    if (sw().search_blocks > 0) return (sw().search_blocks + 7) & ~7;
     const int nb = search_blocks(d, cpw), R = c->search_resident;
     if (R < 8 || 2 * nb < R) return nb;
     return std::min(std::max(1, (nb + R / 2) / R) * R, 8192) & ~7;
@@ -1000,8 +1064,7 @@ int collect_counters(arp_ctx* c) {  // the only stream sync of a pass
     // The pass ends by storing its number in pinned memory (pass_end in the last kernel, or k_publish_counters):
     // polling that word wakes the host ~10 us sooner than hipStreamSynchronize.  Bounded: after 2 ms (or with a
     // caller-owned stream or ARP_SPIN_WAIT=0) the runtime's own wait takes over.
-    static const int spin = env_int("ARP_SPIN_WAIT", 1);
-    if (spin && !c->external_stream) {
+    if (sw().spin_wait && !c->external_stream) {
         volatile u64* flag = c->h_ctr_pinned + C_COUNT;
         const auto t0 = std::chrono::steady_clock::now();
         for (int it = 0; *flag != c->publish_seq; ++it) {
@@ -1081,10 +1144,9 @@ int ensure_amide_grid(arp_ctx* c) {
 // both centre grids in one launch when they are small (k_point_grids); otherwise each by the general path
 int ensure_center_grids(arp_ctx* c) {
     CHK(join_upload_lists(c));      // (whoever asks for the grids on the main stream reads them there)
-    static const int deterministic = env_int("ARP_DETERMINISTIC", 0);
     const bool want_r = c->nring > 0 && !c->ring_grid.valid, want_a = c->namide > 0 && !c->amide_grid.valid;
     const int small_points = 16384;
-    if ((want_r || want_a) && !deterministic && c->nring <= small_points && c->namide <= small_points) {
+    if ((want_r || want_a) && !sw().deterministic && c->nring <= small_points && c->namide <= small_points) {
         PointGridJob<PtsD3> jr{};
         PointGridJob<PtsF3> ja{};
         bool fits = true;
@@ -1207,7 +1269,8 @@ int ensure_default_selection(arp_ctx* c) {  // whole structure selected (I:1395 
     return enqueue_selection(c, 6.0);   // an uploaded selection that was not expanded yet is expanded here
 }
 
-int bag_reserve(arp_ctx* c, Bag& b, size_t cap, bool d, bool f) {
+int bag_reserve(arp_ctx* c, Bag& b, size_t cap) {
+    const bool d = b.d, f = b.f;
     cap = cap + cap / 4 + 64;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t bi = al(cap * sizeof(int)), bd = al(cap * sizeof(double)), bf = al(cap * sizeof(float)), bu = al(cap);
@@ -1246,7 +1309,7 @@ int bag_download(arp_ctx* c, const Bag& b, T* dst, const DevBuf<T>& src, int idx
 // until 64 are there for a full-lane evaluation, so a wave should see a few items; every item costs a few dependent
 // loads, so not too many (sweep in profiles/README.md)
 int plane_blocks(int64_t items) {
-    static const int ipw = std::max(1, env_int("ARP_PLANE_IPW", 4));
+    const int ipw = sw().plane_ipw;
     return nblocks((items + ipw - 1) / ipw * 64, 256, PLANE_BLOCKS);
 }
 // The four ring / amide kernels: prepare_* sizes the bag, clears its counter and fills the kernel arguments
@@ -1255,24 +1318,17 @@ int plane_blocks(int64_t items) {
 int prepare_atom_plane(arp_ctx* c, AtomPlaneArgs& a, int& nb, bool contact_grid = false) {  // I:947-1062
     Bag& b = c->bag_ap;
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 8 + 256, true, false));
-    CHK(zero_counter(c, C_AP, 1));
+    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 8 + 256));
+    CHK(zero_counter(c, b.slot, 1));
     if (c->nring == 0 || c->n == 0) return ARP_OK;
-    if (contact_grid) {   // the grid of the pass (selection_plus without hydrogens): atom_plane_cg_body
-        a = AtomPlaneArgs{c->atom_grid.d, c->atom_grid.start.p, c->s_xyzm.p, c->s_aux.p, (int)c->nring, c->ring_c.p, c->ring_n.p,
-                          c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->plus.p, c->has_group_owner ? c->ring_home.p : nullptr,
-                          c->has_group_owner ? c->ring_gid.p : nullptr, c->has_gid ? c->gid.p : nullptr, (long long)b.cap,
-                          b.a.p, b.b.p, b.d0.p, b.d1.p, b.u0.p, b.u1.p, c->d_ctr + ctr_dev(C_AP),
-                          c->st_xyzm.p, c->sel_made ? c->sel.p : nullptr, (c->sel_made && c->sel_all) ? 1 : 0};
-        nb = plane_blocks(c->nring);
-        return ARP_OK;
-    }
-    // all-atom 6 A grid (I:960 radius): the one the selection expansion has just built, if it is still current
-    if (!(c->all_grid_current && c->all_grid.valid && c->all_grid.radius == 6.0)) CHK(build_all_grid(c, 6.0));
-    a = AtomPlaneArgs{c->all_grid.d, c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)c->nring, c->ring_c.p, c->ring_n.p,
-                      c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->plus.p, c->has_group_owner ? c->ring_home.p : nullptr,
-                      c->has_group_owner ? c->ring_gid.p : nullptr, c->has_gid ? c->gid.p : nullptr, (long long)b.cap,
-                      b.a.p, b.b.p, b.d0.p, b.d1.p, b.u0.p, b.u1.p, c->d_ctr + ctr_dev(C_AP),
+    // contact_grid: the grid of the pass (selection_plus without hydrogens, atom_plane_cg_body); else the all-atom 6 A grid
+    // (I:960 radius): the one the selection expansion has just built, if it is still current
+    if (!contact_grid && !(c->all_grid_current && c->all_grid.valid && c->all_grid.radius == 6.0)) CHK(build_all_grid(c, 6.0));
+    const Grid& G = contact_grid ? c->atom_grid : c->all_grid;
+    a = AtomPlaneArgs{G.d, G.start.p, contact_grid ? c->s_xyzm.p : c->a_xyzm.p, contact_grid ? c->s_aux.p : c->a_aux.p, (int)c->nring,
+                      c->ring_c.p, c->ring_n.p, c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->plus.p,
+                      c->has_group_owner ? c->ring_home.p : nullptr, c->has_group_owner ? c->ring_gid.p : nullptr, c->has_gid ? c->gid.p : nullptr,
+                      (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.u0.p, b.u1.p, c->d_ctr + ctr_dev(b.slot),
                       c->st_xyzm.p, c->sel_made ? c->sel.p : nullptr, (c->sel_made && c->sel_all) ? 1 : 0};
     nb = plane_blocks(c->nring);
     return ARP_OK;
@@ -1280,82 +1336,63 @@ int prepare_atom_plane(arp_ctx* c, AtomPlaneArgs& a, int& nb, bool contact_grid 
 int prepare_plane_plane(arp_ctx* c, PlanePlaneArgs& a, int& nb) {  // I:1064-1194
     Bag& b = c->bag_pp;
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 16 + 256, true, false));
-    CHK(zero_counter(c, C_PP, 1));
+    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 16 + 256));
+    CHK(zero_counter(c, b.slot, 1));
     if (c->nring == 0) return ARP_OK;
     CHK(ensure_ring_grid(c));
     a = PlanePlaneArgs{c->ring_grid.d, c->ring_grid.start.p, c->ring_grid.perm.p, (int)c->nring, c->ring_c.p, c->ring_n.p,
                        c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->has_group_owner ? c->ring_home.p : nullptr,
                        c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.d2.p,
-                       b.d3.p, b.u0.p, b.u1.p, b.u2.p, c->d_ctr + ctr_dev(C_PP)};
+                       b.d3.p, b.u0.p, b.u1.p, b.u2.p, c->d_ctr + ctr_dev(b.slot)};
     nb = plane_blocks(c->nring);
     return ARP_OK;
 }
 int prepare_group_group(arp_ctx* c, GroupGroupArgs& a, int& nb) {  // I:1217-1300
     Bag& b = c->bag_gg;
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256, false, true));
-    CHK(zero_counter(c, C_GG, 1));
+    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256));
+    CHK(zero_counter(c, b.slot, 1));
     if (c->namide == 0) return ARP_OK;
     CHK(ensure_amide_grid(c));
     a = GroupGroupArgs{c->amide_grid.d, c->amide_grid.start.p, c->amide_grid.perm.p, (int)c->namide, c->am_c.p, c->am_n.p,
                        c->am_sel.p, c->am_plus.p, c->has_group_owner ? c->am_home.p : nullptr,
                        c->has_group_owner ? c->am_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.f0.p, b.f1.p, b.f2.p,
-                       b.u0.p, c->d_ctr + ctr_dev(C_GG)};
+                       b.u0.p, c->d_ctr + ctr_dev(b.slot)};
     nb = plane_blocks(c->namide);
     return ARP_OK;
 }
 int prepare_group_plane(arp_ctx* c, GroupPlaneArgs& a, int& nb) {  // I:1302-1382
     Bag& b = c->bag_gp;
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256, true, false));
-    CHK(zero_counter(c, C_GP, 1));
+    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256));
+    CHK(zero_counter(c, b.slot, 1));
     if (c->namide == 0 || c->nring == 0) return ARP_OK;
     CHK(ensure_ring_grid(c));
     a = GroupPlaneArgs{c->ring_grid.d, c->ring_grid.start.p, c->ring_grid.perm.p, (int)c->namide, c->am_c.p, c->am_n.p,
                        c->am_sel.p, c->am_plus.p, c->ring_c.p, c->ring_n.p, c->ring_sel.p, c->ring_plus.p,
                        c->has_group_owner ? c->am_home.p : nullptr, c->has_group_owner ? c->am_gid.p : nullptr,
                        c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.d2.p,
-                       b.u0.p, c->d_ctr + ctr_dev(C_GP)};
+                       b.u0.p, c->d_ctr + ctr_dev(b.slot)};
     nb = plane_blocks(c->namide);
     return ARP_OK;
 }
 
-int enqueue_atom_plane(arp_ctx* c, hipStream_t st) {
-    AtomPlaneArgs a{};
+// One ring / amide loop alone by its grid walk (arp_planes.h); kind: 0 atom-plane, 1 plane-plane, 2 group-group, 3 group-plane
+template <class Args, class Prepare>
+int enqueue_walk(arp_ctx* c, Prepare prepare, void (*kernel)(Args), const char* what) {
+    Args a{};
     int nb = 0;
-    CHK(prepare_atom_plane(c, a, nb));
+    CHK(prepare(c, a, nb));
     if (!nb) return ARP_OK;
-    Prof p(c, SLOT_PLANES, st);
-    hipLaunchKernelGGL(k_atom_plane, dim3(nb), dim3(256), 0, st, a);
-    return check_launch(c, "k_atom_plane");
+    Prof p(c, SLOT_PLANES, c->stream);
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, c->stream, a);
+    return check_launch(c, what);
 }
-int enqueue_plane_plane(arp_ctx* c, hipStream_t st) {
-    PlanePlaneArgs a{};
-    int nb = 0;
-    CHK(prepare_plane_plane(c, a, nb));
-    if (!nb) return ARP_OK;
-    Prof p(c, SLOT_PLANES, st);
-    hipLaunchKernelGGL(k_plane_plane, dim3(nb), dim3(256), 0, st, a);
-    return check_launch(c, "k_plane_plane");
-}
-int enqueue_group_group(arp_ctx* c, hipStream_t st) {
-    GroupGroupArgs a{};
-    int nb = 0;
-    CHK(prepare_group_group(c, a, nb));
-    if (!nb) return ARP_OK;
-    Prof p(c, SLOT_PLANES, st);
-    hipLaunchKernelGGL(k_group_group, dim3(nb), dim3(256), 0, st, a);
-    return check_launch(c, "k_group_group");
-}
-int enqueue_group_plane(arp_ctx* c, hipStream_t st) {
-    GroupPlaneArgs a{};
-    int nb = 0;
-    CHK(prepare_group_plane(c, a, nb));
-    if (!nb) return ARP_OK;
-    Prof p(c, SLOT_PLANES, st);
-    hipLaunchKernelGGL(k_group_plane, dim3(nb), dim3(256), 0, st, a);
-    return check_launch(c, "k_group_plane");
+int enqueue_bag_walk(arp_ctx* c, int kind) {
+    if (kind == 0) return enqueue_walk(c, [](arp_ctx* c, AtomPlaneArgs& a, int& nb) { return prepare_atom_plane(c, a, nb); }, k_atom_plane, "k_atom_plane");
+    if (kind == 1) return enqueue_walk(c, prepare_plane_plane, k_plane_plane, "k_plane_plane");
+    if (kind == 2) return enqueue_walk(c, prepare_group_group, k_group_group, "k_group_group");
+    return enqueue_walk(c, prepare_group_plane, k_group_plane, "k_group_plane");
 }
 // Static candidate lists of the ring / amide loops (arp_planes.h): built on the stream when the structure changed.
 PlaneLists plane_lists(arp_ctx* c) {
@@ -1405,6 +1442,16 @@ int ensure_plane_lists(arp_ctx* c) {
     return ARP_OK;
 }
 
+// f(S, G) with S, G = std::integral_constant<int, 0 or 1>: two run-time bits as the template parameters of a kernel.  (The
+// deduced return types instantiate f where this is called, in the order below: the kernels keep their places in the code object.)
+template <class F>
+auto with_bits(bool s, bool g, F f) {
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    if (s) { if (g) f(I1{}, I1{}); else f(I1{}, I0{}); }
+    else { if (g) f(I0{}, I1{}); else f(I0{}, I0{}); }
+}
+
 // The pass proper: _calculate_atom_contacts (I:693-936) = contact grid (bin + scan/scatter), neighbour search, fused
 // per-pair kernel; with_planes: the four ring / amide loops (I:938-1382) ride in the last launch (k_sift_planes).
 // fuse_sets (arp_run_launch): the grid build also produces the residue / ring / amide sets of I:1413-1437.
@@ -1420,9 +1467,9 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
     // the grid of the previous whole-structure pass, if nothing it depends on has changed (see grid_reuse)
     const bool all_res_now = c->whole_structure && c->sel_all;
     const bool whole = c->sel_made && c->sel_all && c->n > 0;
-    const bool reuse_grid = c->grid_reuse && whole && c->cg_valid && !c->cg_pending && c->atom_grid.valid && c->cg_radius == cutoff &&
-                            c->cg_static_epoch == c->static_epoch && c->cg_sel_epoch == c->sel_epoch && c->cg_fuse == c->fuse_sets &&
-                            c->cg_init_plus == c->init_plus_in_bin && c->cg_all_res == all_res_now && !c->static_dirty && c->sp_radius == cutoff;
+    auto grid_key = [&]() { return GridKey{cutoff, c->static_epoch, c->sel_epoch, c->fuse_sets, c->init_plus_in_bin, all_res_now}; };
+    const bool reuse_grid = c->grid_reuse && whole && c->cg_valid && !c->cg_pending && c->atom_grid.valid && c->cg_key == grid_key() &&
+                            !c->static_dirty && c->sp_radius == cutoff;
     c->cg_reused = reuse_grid;
     if (c->fuse_sets) {
         const size_t nres = (size_t)std::max<int64_t>(c->nres, 1);
@@ -1459,8 +1506,8 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         c->cg_valid = false;
         CHK(build_contact_grid_compact(c, cutoff, M_PLUS, M_HYDROGEN, c->d_ctr + ctr_dev(C_BINNED), c->init_plus_in_bin ? c->plus.p : nullptr, rm));
         if (whole) {      // what this grid was built from; its atom count arrives with the counters of the pass (finish_contacts)
-            c->cg_valid = true; c->cg_pending = true; c->cg_radius = cutoff; c->cg_static_epoch = c->static_epoch; c->cg_sel_epoch = c->sel_epoch;
-            c->cg_fuse = c->fuse_sets; c->cg_init_plus = c->init_plus_in_bin; c->cg_all_res = all_res_now;
+            c->cg_valid = true; c->cg_pending = true;
+            c->cg_key = grid_key();      // (after the build: ensure_static may have made a new spatial order)
         }
     }
     if (masks_after_bin && c->nring + c->namide > 0) {
@@ -1487,86 +1534,62 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         // and a wave's cells are a serial chain (1tqn_h stand-in: 22 -> 16 us).
         // (twelve since the waves of a block CLAIM their work: a longer list per block evens out better — 1 M atoms 196 -> 176 us —;
         // three was the optimum of the static three-cells-per-wave assignment)
-        static const int cpw_max = std::max(1, env_int("ARP_SEARCH_CPW", 12));
-        const int cpw = std::max(1, std::min(cpw_max, c->atom_grid.d.ncell / (SEARCH_WAVES * 2 * c->num_cu)));
+        const int cpw = std::max(1, std::min(sw().search_cpw, c->atom_grid.d.ncell / (SEARCH_WAVES * 2 * c->num_cu)));
         // tiles of two x-adjacent cells (k_search): fewer, fuller units — worth it where a wave still has several to claim
-        static const int tile_mode = env_int("ARP_SEARCH_TILE", -1);      // -1: by size, 1 / 2: always
-        static const int tile_min_cells = env_int("ARP_SEARCH_TILE_MIN_CELLS", 60000);
-        const int tile_x = tile_mode > 0 ? std::min(tile_mode, 2) : (c->atom_grid.d.ncell >= tile_min_cells ? 2 : 1);
+        const int tile_x = sw().search_tile > 0 ? std::min(sw().search_tile, 2) : (c->atom_grid.d.ncell >= sw().search_tile_min_cells ? 2 : 1);
         // Sparse grids (fewer atoms than cells: a protein in its box, a ligand's selection_plus, a batch): the blocks split the
         // ATOMS of the grid evenly instead of its cells (k_search, cell_of_pos) and their number goes with the atoms — what the
         // grid's build reported last time, all atoms of the structure before that is known.
-        static const int balance_mode = env_int("ARP_SEARCH_BALANCE", -1);     // -1: by sparsity, 0: never, 1: whenever the cells of the rows are known
         const int64_t atoms_est = c->cg_reused ? c->cg_binned : (c->stats[4] == c->atom_grid.d.ncell && c->stats[3] > 0 ? c->stats[3] : c->n);
         // ... and so do the blocks of a CLUMPED structure (cells with hundreds of atoms: a chain folded onto itself), which the
         // previous pass over this structure gives away by its distance tests per atom (uniform protein density: ~80)
         const bool clumped = c->stats[3] > 0 && c->stats[4] == c->atom_grid.d.ncell && c->stats[0] > 150 * c->stats[3];
-        const bool by_atoms = c->s_cell_valid && (balance_mode == 1 || (balance_mode < 0 && ((int64_t)c->atom_grid.d.ncell > atoms_est || clumped)));
+        const bool by_atoms = c->s_cell_valid && (sw().search_balance == 1 || (sw().search_balance < 0 && ((int64_t)c->atom_grid.d.ncell > atoms_est || clumped)));
         int nblocks_search = search_blocks_balanced(c, c->atom_grid.d, cpw);
         if (by_atoms) {
             const int R = c->search_resident;
-            static const int atoms_per_block = std::max(8, env_int("ARP_SEARCH_APB", 128));
-            int nbk = (int)std::min<int64_t>(std::max<int64_t>((atoms_est + atoms_per_block - 1) / atoms_per_block, 8), 8192);
+            int nbk = (int)std::min<int64_t>(std::max<int64_t>((atoms_est + sw().search_apb - 1) / sw().search_apb, 8), 8192);
             nbk = (nbk + 7) & ~7;
             nblocks_search = (R >= 8 && 2 * nbk >= R) ? std::min(std::max(1, (nbk + R / 2) / R) * R, 8192) & ~7 : nbk;
         }
-        static const int hint_mode = env_int("ARP_SEARCH_BALANCE_HINT", 1);
-        static const int cell_w16 = std::max(0, env_int("ARP_SEARCH_CELL_WEIGHT_X16", 64));      // weight of a cell in sixteenths of an atom
-        static const int hint_atoms = env_int("ARP_SEARCH_BALANCE_HINT_ATOMS", 1);      // ... also for blocks that take runs of atoms (k_balance_atoms)
-        const bool hint_wanted = hint_mode && whole && (!by_atoms || hint_atoms);
-        const bool hint_ok = hint_wanted && c->sb_valid && c->sb_by_atoms == by_atoms && c->sb_static_epoch == c->static_epoch && c->sb_sel_epoch == c->sel_epoch &&
-                             c->sb_radius == cutoff && c->sb_blocks == nblocks_search && c->sb_tx == tile_x && c->sb_tile.p;
+        const bool hint_wanted = sw().balance_hint && whole && (!by_atoms || sw().balance_hint_atoms);
+        const HintKey hint_key{by_atoms, c->static_epoch, c->sel_epoch, cutoff, nblocks_search, tile_x};
+        const bool hint_ok = hint_wanted && c->sb_valid && c->sb_key == hint_key && c->sb_tile.p;
         const int* const balance_hint = hint_ok ? (const int*)c->sb_tile.p : (const int*)nullptr;
-        if (tile_x == 2) {
-            hipLaunchKernelGGL((k_search<MODE_CONTACTS, 2>), dim3(nblocks_search), dim3(64 * SEARCH_WAVES), 0,
+        auto search = [&](auto tx) {
+            hipLaunchKernelGGL((k_search<MODE_CONTACTS, decltype(tx)::value>), dim3(nblocks_search), dim3(64 * SEARCH_WAVES), 0,
                                c->stream, c->atom_grid.d, c->atom_grid.start.p, c->s_xyzm.p, c->s_aux.p, cutoff * cutoff,
                                include_seq_adj, c->has_home ? 1 : 0, c->pairs.p, (u64)segcap, c->d_ctr + ctr_dev(C_SEG_PAIRS), c->d_ctr + ctr_dev(C_STAT_CAND),
                                c->d_ctr + ctr_dev(C_STAT_ACC), (uint8_t*)nullptr, masks_after_bin ? GroupMasks{} : gm,
                                by_atoms ? (const int*)c->s_cell.p : (const int*)nullptr, balance_hint);
-        } else {
-            hipLaunchKernelGGL((k_search<MODE_CONTACTS>), dim3(nblocks_search), dim3(64 * SEARCH_WAVES), 0,
-                               c->stream, c->atom_grid.d, c->atom_grid.start.p, c->s_xyzm.p, c->s_aux.p, cutoff * cutoff,
-                               include_seq_adj, c->has_home ? 1 : 0, c->pairs.p, (u64)segcap, c->d_ctr + ctr_dev(C_SEG_PAIRS), c->d_ctr + ctr_dev(C_STAT_CAND),
-                               c->d_ctr + ctr_dev(C_STAT_ACC), (uint8_t*)nullptr, masks_after_bin ? GroupMasks{} : gm,
-                               by_atoms ? (const int*)c->s_cell.p : (const int*)nullptr, balance_hint);
-        }
+        };
+        if (tile_x == 2) search(std::integral_constant<int, 2>{});
+        else search(std::integral_constant<int, 1>{});
         // the hint for the LATER passes over this grid (same structure, selection, cutoff, launch shape), made behind the search of
         // the SECOND pass over it: the launch sits between the search and the per-pair kernel of that pass (6 us + a gap: a tenth
         // of a structure's first pass when it was made there), and a structure that is evaluated once never needs it.  First and
         // second pass run on equal runs of cells.
         if (hint_wanted && !hint_ok && nblocks_search >= 16) {
-            const bool seen = c->sb_seen && c->sb_seen_by_atoms == by_atoms && c->sb_seen_static_epoch == c->static_epoch && c->sb_seen_sel_epoch == c->sel_epoch &&
-                              c->sb_seen_radius == cutoff && c->sb_seen_blocks == nblocks_search && c->sb_seen_tx == tile_x;
-            static const int hint_eager = env_int("ARP_SEARCH_BALANCE_HINT_EAGER", 0);
-            if (seen || hint_eager) {
+            const bool seen = c->sb_seen && c->sb_seen_key == hint_key;
+            if (seen || sw().balance_hint_eager) {
                 HIPCHK(c, c->sb_tile.reserve((size_t)nblocks_search + 1));
                 if (!by_atoms) {
                     hipLaunchKernelGGL(k_balance_blocks, dim3(nblocks(nblocks_search + 1, 256)), dim3(256), 0, c->stream, c->atom_grid.d, c->atom_grid.start.p,
-                                       nblocks_search, tile_x, cell_w16, c->sb_tile.p);
+                                       nblocks_search, tile_x, sw().cell_weight_x16, c->sb_tile.p);
                 } else {
                     // runs of ATOMS of equal weight: weight per cell, its running sum (the scans of the grid builds), one binary search per block
                     const int ncell = c->atom_grid.d.ncell;
-                    static const int w_unit = std::max(0, env_int("ARP_SEARCH_W_UNIT", 100)), w_chunk = std::max(0, env_int("ARP_SEARCH_W_CHUNK", 85)),
-                                     w_test8 = std::max(0, env_int("ARP_SEARCH_W_TEST_X8", 2));      // (k_cell_weights: wave instructions per unit, per chunk, per eight distance tests)
                     HIPCHK(c, c->sb_cw.reserve(scan_padded(ncell))); HIPCHK(c, c->sb_cwp.reserve(scan_padded(ncell)));
-                    hipLaunchKernelGGL(k_cell_weights, dim3(nblocks(ncell, 256, 2048)), dim3(256), 0, c->stream, c->atom_grid.d, c->atom_grid.start.p, w_unit, w_chunk, w_test8, c->sb_cw.p);
-                    if (ncell <= 4096) hipLaunchKernelGGL((k_scan_small<4>), dim3(1), dim3(1024), 0, c->stream, c->sb_cw.p, ncell, c->sb_cwp.p, (u64*)nullptr);
-                    else if (ncell <= 16384) hipLaunchKernelGGL((k_scan_small<16>), dim3(1), dim3(1024), 0, c->stream, c->sb_cw.p, ncell, c->sb_cwp.p, (u64*)nullptr);
-                    else if (ncell <= 32768) hipLaunchKernelGGL((k_scan_small<32>), dim3(1), dim3(1024), 0, c->stream, c->sb_cw.p, ncell, c->sb_cwp.p, (u64*)nullptr);
-                    else {
-                        const int ntiles = (ncell + TILE_CELLS - 1) / TILE_CELLS;
-                        HIPCHK(c, c->sb_sums.reserve((size_t)ntiles + 2));
-                        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, c->stream, c->sb_cw.p, ncell, c->sb_cwp.p, c->sb_sums.p);
-                        hipLaunchKernelGGL(k_scan_fix, dim3((ncell + 4095) / 4096), dim3(1024), 0, c->stream, c->sb_cwp.p, ncell, c->sb_sums.p, ntiles, (unsigned long long*)nullptr);
-                    }
+                    hipLaunchKernelGGL(k_cell_weights, dim3(nblocks(ncell, 256, 2048)), dim3(256), 0, c->stream, c->atom_grid.d, c->atom_grid.start.p, sw().w_unit, sw().w_chunk, sw().w_test_x8, c->sb_cw.p);
+                    CHK(enqueue_scan(c, c->stream, c->sb_cw.p, ncell, c->sb_cwp.p, c->sb_sums));
                     hipLaunchKernelGGL(k_balance_atoms, dim3(nblocks(nblocks_search + 1, 256)), dim3(256), 0, c->stream, c->atom_grid.d, c->atom_grid.start.p,
                                        (const int*)c->sb_cwp.p, nblocks_search, c->sb_tile.p);
                 }
-                c->sb_valid = true; c->sb_by_atoms = by_atoms; c->sb_static_epoch = c->static_epoch; c->sb_sel_epoch = c->sel_epoch; c->sb_radius = cutoff;
-                c->sb_blocks = nblocks_search; c->sb_tx = tile_x; c->sb_whole = whole;
+                c->sb_valid = true;
+                c->sb_key = hint_key;
             } else {
-                c->sb_seen = true; c->sb_seen_by_atoms = by_atoms; c->sb_seen_static_epoch = c->static_epoch; c->sb_seen_sel_epoch = c->sel_epoch; c->sb_seen_radius = cutoff;
-                c->sb_seen_blocks = nblocks_search; c->sb_seen_tx = tile_x;
+                c->sb_seen = true;
+                c->sb_seen_key = hint_key;
             }
         }
         return check_launch(c, "k_search<CONTACTS>");
@@ -1583,8 +1606,7 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         CHK(join_upload_lists(c, /*must=*/true));      // (the list blocks of this launch read what the upload's second stream made)
         Prof p(c, SLOT_SIFT);
         // (the blocks split their work statically: all of them must be resident from the start)
-        static const int sift_bpc_env = env_int("ARP_SIFT_BPC", 0);
-        const int sift_blocks_per_cu = sift_bpc_env > 0 ? sift_bpc_env : c->sift_per_cu;
+        const int sift_blocks_per_cu = sw().sift_bpc > 0 ? sw().sift_bpc : c->sift_per_cu;
         SiftArgs sa{c->pairs.p, c->d_ctr + ctr_dev(C_SEG_PAIRS), (u64)segcap, c->s_xyzm.p, c->s_qa.p, c->s_h.p, {0, 0, 0, 0, 0, 0, 0, 0},
                           SiftSide{c->rad_tab.p, c->rad.p, c->xyz.p, c->h_off.p, c->bond_off.p, c->sb.p, c->longest_bond.p}, c->bond_idx.p, c->h_xyz_d.p,
                           c->has_gid ? c->gid.p : nullptr, vdw_comp, c->out_i.p, c->out_j.p, c->out_d.p, c->out_s.p, c->out_ct.p,
@@ -1592,22 +1614,20 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         // No more sift blocks than the pairs can feed (one batch of 64 per wave and block at least): what the previous pass over
         // this structure found, or ~13 per heavy atom for the first one.  A protein-sized structure then runs 70-odd blocks
         // instead of 1024, whose start-up and end-of-pass tickets were most of the kernel (stand-in: 25 -> 16 us).
-        static const int pairs_per_block = std::max(64, env_int("ARP_SIFT_PPB", 256));
+        const int pairs_per_block = sw().sift_ppb;
         const int64_t expect = (c->contacts_expected > 0) ? c->contacts_expected : (int64_t)c->n * 13;
-        static const int64_t stream_bytes = (int64_t)env_int("ARP_STREAM_OUT_MB", 96) << 20;
-        const bool stream_out = expect * 15 > stream_bytes;     // (15 B per record)
+        const bool stream_out = expect * 15 > sw().stream_out_bytes;     // (15 B per record)
         const int by_work = (int)std::min<int64_t>((expect + pairs_per_block - 1) / pairs_per_block + PAIR_SEGS, 1 << 20);
         const int slots = merged_ ? std::max(c->num_cu * sift_blocks_per_cu - np, 8 * PAIR_SEGS) : c->num_cu * sift_blocks_per_cu;
         const int nsift = std::max(std::min(slots, by_work), 8 * PAIR_SEGS) & ~(PAIR_SEGS - 1);
         // (four variants each: streaming stores or not, global ids or not — template parameters of the kernels, see sift_body)
         {   // a segment's share of the sift blocks goes with its size in the pass before (k_sift: nblk)
-            static const int shares = env_int("ARP_SIFT_SHARES", 1);
             const int B = nsift / PAIR_SEGS;
             uint64_t tot = 0;
             for (int k = 0; k < PAIR_SEGS; ++k) tot += c->seg_last[k];
             int given = 0, big = 0;
             for (int k = 0; k < PAIR_SEGS; ++k) {
-                sa.nblk[k] = (shares && tot > 0 && B > 1) ? std::max(1, (int)((double)nsift * (double)c->seg_last[k] / (double)tot + 0.5)) : B;
+                sa.nblk[k] = (sw().sift_shares && tot > 0 && B > 1) ? std::max(1, (int)((double)nsift * (double)c->seg_last[k] / (double)tot + 0.5)) : B;
                 given += sa.nblk[k];
                 if (sa.nblk[k] > sa.nblk[big]) big = k;
             }
@@ -1620,19 +1640,16 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
                 for (int k = 1; k < PAIR_SEGS; ++k) if (sa.nblk[k] > sa.nblk[big]) big = k;
             }
         }
-#define LAUNCH_SIFT_PLANES(S, G) hipLaunchKernelGGL((k_sift_planes<S, G>), dim3(np + nsift), dim3(256), 0, c->stream, sa, nsift, ap, pp, gg, gp, plane_lists(c), \
-                                                    c->d_ctr + ctr_dev(C_PLIST), np, c->pub)
-#define LAUNCH_SIFT(S, G) hipLaunchKernelGGL((k_sift<S, G>), dim3(nsift), dim3(256), 0, c->stream, sa, c->pub)
         const bool with_gid = sa.gid != nullptr;
-        if (merged_) {
-            if (stream_out) { if (with_gid) LAUNCH_SIFT_PLANES(1, 1); else LAUNCH_SIFT_PLANES(1, 0); }
-            else { if (with_gid) LAUNCH_SIFT_PLANES(0, 1); else LAUNCH_SIFT_PLANES(0, 0); }
-        } else {
-            if (stream_out) { if (with_gid) LAUNCH_SIFT(1, 1); else LAUNCH_SIFT(1, 0); }
-            else { if (with_gid) LAUNCH_SIFT(0, 1); else LAUNCH_SIFT(0, 0); }
-        }
-#undef LAUNCH_SIFT_PLANES
-#undef LAUNCH_SIFT
+        if (merged_)
+            with_bits(stream_out, with_gid, [&](auto S, auto G) {
+                hipLaunchKernelGGL((k_sift_planes<decltype(S)::value, decltype(G)::value>), dim3(np + nsift), dim3(256), 0, c->stream, sa, nsift,
+                                   ap, pp, gg, gp, plane_lists(c), c->d_ctr + ctr_dev(C_PLIST), np, c->pub);
+            });
+        else
+            with_bits(stream_out, with_gid, [&](auto S, auto G) {
+                hipLaunchKernelGGL((k_sift<decltype(S)::value, decltype(G)::value>), dim3(nsift), dim3(256), 0, c->stream, sa, c->pub);
+            });
         return check_launch(c, "k_sift");
     };
     // A structure's FIRST pass (fork_lists): the list chain (~55 us at 100 k atoms) is longer than grid build + search (~43 us), and
@@ -1679,16 +1696,13 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         // inside the time the sift blocks need (sweep in profiles/README.md); ring-heavy structures get more blocks, up to half the slots.
         // ... and fewer when the sift part itself is short: a list chunk takes about as long as a batch of 64 pairs (2.3 vs 2.5-3 us
         // in the block traces of round 2, profiles/README.md), and a sift wave of a small structure has only a batch or two.
-        static const int cpw_max = std::max(1, env_int("ARP_PLANE_CPW", 16));
         const int64_t expect_pairs = (c->contacts_expected > 0) ? c->contacts_expected : (int64_t)c->n * 13;
         const double batches_per_wave = (double)expect_pairs / (64.0 * 4.0 * std::min<double>(c->num_cu * 4.0, std::max(1.0, expect_pairs / 256.0)));
-        static const double chunk_factor = env_int("ARP_PLANE_CHUNK_FACTOR_X10", 10) / 10.0;
-        const int chunks_per_wave = std::max(2, std::min(cpw_max, (int)(chunk_factor * batches_per_wave + 0.5)));
+        const int chunks_per_wave = std::max(2, std::min(sw().plane_cpw, (int)(sw().plane_chunk_factor * batches_per_wave + 0.5)));
         np = (int)std::min<long long>(std::max<long long>((entries + 256 * chunks_per_wave - 1) / (256 * chunks_per_wave), 8), 2 * c->num_cu);
         np = (np + 7) & ~7;
     }
-    static const int planes_mode = env_int("ARP_PLANES_MODE", 0);   // 0: one grid with the sift kernel; 1: second stream
-    const bool merged = have_planes && c->n > 0 && !lists_forked && (planes_mode == 0 || c->external_stream);
+    const bool merged = have_planes && c->n > 0 && !lists_forked && (sw().planes_mode == 0 || c->external_stream);
     const bool planes_alone = (have_planes && !merged) || lists_forked;   // (forked: launched whatever it holds — it ends the pass with the per-pair kernel)
     hipStream_t st2 = c->external_stream ? c->stream : c->stream2;   // a caller-owned stream: everything in order on it
     if (planes_alone && !lists_forked && c->pub.expected) c->pub.expected = (c->n > 0) ? 2 : 1;
@@ -1749,6 +1763,53 @@ void sorted_layout(size_t k, size_t off[5], size_t* bytes, size_t first_col_entr
     off[4] = off[3] + al256(k * sizeof(uint16_t));
     *bytes = off[4] + al256(k * sizeof(uint8_t));
 }
+// Canonical order of a bag by the radix sort of arp_sort.h: keys {first id << idbits | second id}, the other columns riding in
+// the payload.  Radix passes over the bits of the first id — or, small_nbin > 0, ONE launch that groups the records by first id
+// (k_sort_small, small_nbin ids) —, then the runs of equal first id ordered by the second in one launch (k_sort_runs).  A holds
+// the columns in and out; the scratch is sized for cap >= k records.
+int id_bits(int64_t idmax) {      // significant bits of the ids 0 ... idmax (at least one)
+    int bits = 1;
+    while (((int64_t)1 << bits) <= idmax) ++bits;
+    return bits;
+}
+int radix_sort(arp_ctx* c, SortScratch& s, SortArgs& A, size_t k, size_t cap, int idbits, int small_nbin, const char* what) {
+    const int passes = (idbits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
+    HIPCHK(c, s.key[0].reserve(cap)); HIPCHK(c, s.val[0].reserve(cap));
+    if (passes > 1) { HIPCHK(c, s.key[1].reserve(cap)); HIPCHK(c, s.val[1].reserve(cap)); }
+    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
+    if (tiles > ((long long)1 << 30) / SORT_BINS) FAIL(c, ARP_E_CAPACITY, std::string(what) + ": too many records for the digit table");
+    const int tstride = (int)((tiles + 3) & ~3ll);
+    HIPCHK(c, s.table.reserve((size_t)SORT_BINS * (size_t)tstride));
+    HIPCHK(c, s.total.reserve(SORT_BINS));
+    A.n = (long long)k; A.T = (int)tiles; A.tstride = tstride; A.jbits = idbits;
+    A.table = s.table.p; A.total = s.total.p;
+    int last = 0;      // the key / payload buffer the last launch wrote
+    if (small_nbin > 0) {
+        A.key_out = s.key[0].p;
+        A.val_out = s.val[0].p;
+        hipLaunchKernelGGL(k_sort_small, dim3(std::min(sw().sort_small_blocks, small_nbin)), dim3(SORT_SMALL_THREADS), 0, c->stream, A, small_nbin);
+    } else {
+        int shift = idbits;
+        for (int ps = 0; ps < passes; ++ps) {
+            A.first = ps == 0; A.last = 0;
+            A.shift = shift;
+            A.bits = idbits / passes + (ps < idbits % passes ? 1 : 0);
+            shift += A.bits;
+            A.key_in = ps > 0 ? s.key[(ps - 1) & 1].p : nullptr;
+            A.val_in = ps > 0 ? s.val[(ps - 1) & 1].p : nullptr;
+            A.key_out = s.key[ps & 1].p;
+            A.val_out = s.val[ps & 1].p;
+            hipLaunchKernelGGL(k_sort_hist, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
+            hipLaunchKernelGGL(k_sort_scan, dim3(1 << A.bits), dim3(SORT_THREADS), 0, c->stream, A);
+            hipLaunchKernelGGL(k_sort_scatter, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
+        }
+        last = (passes - 1) & 1;
+    }
+    A.key_in = s.key[last].p;
+    A.val_in = s.val[last].p;
+    hipLaunchKernelGGL(k_sort_runs, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, A);
+    return check_launch(c, what);
+}
 int sort_contacts(arp_ctx* c, size_t extra_bytes = 0) {
     if (!c->contacts_valid) FAIL(c, ARP_E_ARG, "arp_atom_contacts_sort: no atom-contact results (call a launch first)");
     const size_t k = (size_t)c->n_contacts;
@@ -1773,66 +1834,17 @@ int sort_contacts(arp_ctx* c, size_t extra_bytes = 0) {
     if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_atom_contacts_sort: 2^31 records or more (the digit table's prefixes are 32-bit)");
     // significant bits of an atom index: packed ids of the resident structure, global ids on a shard
     const int64_t idmax = c->has_gid ? (c->gid_max >= 0 ? c->gid_max : ((int64_t)1 << 31) - 1) : std::max<int64_t>(c->n - 1, 1);
-    int idbits = 1;
-    while (((int64_t)1 << idbits) <= idmax) ++idbits;
-    // radix passes over the bits of i only; the runs of equal i are ordered by j in one launch (k_sort_runs)
-    const int passes = (idbits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
-    const size_t cap = std::max(k, c->out_i.cap);
-    HIPCHK(c, c->sort_key[0].reserve(cap)); HIPCHK(c, c->sort_val[0].reserve(cap));
-    if (passes > 1) { HIPCHK(c, c->sort_key[1].reserve(cap)); HIPCHK(c, c->sort_val[1].reserve(cap)); }
-    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
-    if (tiles > ((long long)1 << 30) / SORT_BINS) FAIL(c, ARP_E_CAPACITY, "arp_atom_contacts_sort: too many records for the digit table");
-    const int tstride = (int)((tiles + 3) & ~3ll);
-    HIPCHK(c, c->sort_table.reserve((size_t)SORT_BINS * (size_t)tstride));
-    HIPCHK(c, c->sort_total.reserve(SORT_BINS));
     SortArgs A{};
     A.ci = c->out_i.p; A.cj = c->out_j.p;
     A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
     uint8_t* slab = c->sorted_slab.p;
     A.i_out = (int*)(slab + off[0]); A.j_out = (int*)(slab + off[1]); A.d_out = (float*)(slab + off[2]);
     A.s_out = (uint16_t*)(slab + off[3]); A.ct_out = slab + off[4];
-    A.n = (long long)k;
-    A.T = (int)tiles;
-    A.tstride = tstride;
-    A.jbits = idbits;
-    A.table = c->sort_table.p;
-    A.total = c->sort_total.p;
     A.row_out = csr ? A.i_out : nullptr;
     A.nrows = (int)rows;
     // a small bag: one block groups the records by bgn atom in one launch (k_sort_small)
-    static const int small_mode = env_int("ARP_SORT_SMALL", 1);
-    const bool small = small_mode && k <= (size_t)SORT_SMALL_MAX_RECORDS && idmax + 1 <= (int64_t)SORT_SMALL_MAX_BINS;
-    if (small) {
-        const int nbin = (int)idmax + 1;
-        A.key_out = c->sort_key[0].p;
-        A.val_out = c->sort_val[0].p;
-        static const int small_blocks = std::max(1, std::min(64, env_int("ARP_SORT_SMALL_BLOCKS", SORT_SMALL_BLOCKS)));
-        hipLaunchKernelGGL(k_sort_small, dim3(std::min(small_blocks, nbin)), dim3(SORT_SMALL_THREADS), 0, c->stream, A, nbin);
-        A.key_in = c->sort_key[0].p;
-        A.val_in = c->sort_val[0].p;
-        hipLaunchKernelGGL(k_sort_runs, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, A);
-        CHK(check_launch(c, "k_sort_small"));
-        c->contacts_sorted = true;
-        return ARP_OK;
-    }
-    int shift = idbits;       // (key = i << idbits | j)
-    for (int ps = 0; ps < passes; ++ps) {
-        A.first = ps == 0; A.last = 0;
-        A.shift = shift;
-        A.bits = idbits / passes + (ps < idbits % passes ? 1 : 0);
-        shift += A.bits;
-        A.key_in = ps > 0 ? c->sort_key[(ps - 1) & 1].p : nullptr;
-        A.val_in = ps > 0 ? c->sort_val[(ps - 1) & 1].p : nullptr;
-        A.key_out = c->sort_key[ps & 1].p;
-        A.val_out = c->sort_val[ps & 1].p;
-        hipLaunchKernelGGL(k_sort_hist, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1 << A.bits), dim3(SORT_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
-    }
-    A.key_in = c->sort_key[(passes - 1) & 1].p;
-    A.val_in = c->sort_val[(passes - 1) & 1].p;
-    hipLaunchKernelGGL(k_sort_runs, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, A);
-    CHK(check_launch(c, "k_sort_scatter"));
+    const bool small = sw().sort_small && k <= (size_t)SORT_SMALL_MAX_RECORDS && idmax + 1 <= (int64_t)SORT_SMALL_MAX_BINS;
+    CHK(radix_sort(c, c->sort_aa, A, k, std::max(k, c->out_i.cap), id_bits(idmax), small ? (int)idmax + 1 : 0, "arp_atom_contacts_sort"));
     c->contacts_sorted = true;
     return ARP_OK;
 }
@@ -1855,8 +1867,8 @@ int finish_plane_lists(arp_ctx* c, bool grow) {
     }
     return again;
 }
-bool finish_bag(arp_ctx* c, Bag& b, int slot) {
-    const u64 k = c->h_ctr[slot];
+bool finish_bag(arp_ctx* c, Bag& b) {
+    const u64 k = c->h_ctr[b.slot];
     if (k > b.cap) return true;
     b.count = (int64_t)k;
     b.valid = true;
@@ -1869,10 +1881,10 @@ int grow_pairs(arp_ctx* c) {
     HIPCHK(c, c->pairs.reserve(need));
     return ARP_OK;
 }
-int grow_bag(arp_ctx* c, Bag& b, int slot, bool d, bool f) {
-    const size_t need = (size_t)c->h_ctr[slot];
+int grow_bag(arp_ctx* c, Bag& b) {
+    const size_t need = (size_t)c->h_ctr[b.slot];
     b.release();
-    return bag_reserve(c, b, need, d, f);
+    return bag_reserve(c, b, need);
 }
 int device_error(arp_ctx* c) {
     if ((int)(uint32_t)c->h_ctr[C_ERR] == ARP_E_XBOND_NBR)
@@ -1909,37 +1921,44 @@ int enqueue_bag_from_lists(arp_ctx* c, int kind) {
     hipLaunchKernelGGL(k_planes, dim3(blocks), dim3(256), 0, c->stream, ap, pp, gg, gp, plane_lists(c), c->d_ctr + ctr_dev(C_PLIST), PublishArgs{nullptr, nullptr, 0, 0}, 1 << kind);
     return check_launch(c, "k_planes (one list)");
 }
-int bag_launch_lists(arp_ctx* c, Bag& b, int slot, bool d, bool f, int kind, int64_t* count) {
+// One ring / amide loop alone (arp_*_launch), from its candidate list or by its grid walk (ARP_BAG_LISTS), once more while a
+// bag or a list was too small (re-sized: a list is rebuilt by the next attempt)
+int bag_launch(arp_ctx* c, Bag& b, int kind, int64_t* count) {
+    const bool from_lists = ((sw().bag_lists >> kind) & 1) != 0;
     HIPCHK(c, hipSetDevice(c->device));
     CHK(ensure_default_selection(c));
     for (int attempt = 0;; ++attempt) {
-        CHK(enqueue_bag_from_lists(c, kind));
+        CHK(from_lists ? enqueue_bag_from_lists(c, kind) : enqueue_bag_walk(c, kind));
         CHK(read_counters(c));
         collect_events(c);
-        const bool list_small = finish_plane_lists(c, /*grow=*/true) != 0;      // (a list that was too small is re-sized and rebuilt by the next attempt)
-        const bool bag_small = finish_bag(c, b, slot);
+        const bool list_small = from_lists && finish_plane_lists(c, /*grow=*/true) != 0;
+        const bool bag_small = finish_bag(c, b);
         if (!list_small && !bag_small) break;
-        if (attempt == 3) FAIL(c, ARP_E_CAPACITY, "result bag could not be sized");
-        if (bag_small) CHK(grow_bag(c, b, slot, d, f));
+        if (attempt == (from_lists ? 3 : 2)) FAIL(c, ARP_E_CAPACITY, "result bag could not be sized");
+        if (bag_small) CHK(grow_bag(c, b));
     }
     if (count) *count = b.count;
     return ARP_OK;
 }
 
-template <class F>
-int bag_launch(arp_ctx* c, Bag& b, int slot, bool d, bool f, F enqueue, int64_t* count) {
-    HIPCHK(c, hipSetDevice(c->device));
-    CHK(ensure_default_selection(c));
-    for (int attempt = 0;; ++attempt) {
-        CHK(enqueue(c, c->stream));
-        CHK(read_counters(c));
-        collect_events(c);
-        if (!finish_bag(c, b, slot)) break;
-        if (attempt == 2) FAIL(c, ARP_E_CAPACITY, "result bag could not be sized");
-        CHK(grow_bag(c, b, slot, d, f));
+// The end of a whole pass (arp_run_wait, arp_run_stage), after its counters have arrived: publish every result and re-size what
+// was too small.  Returns 1 when the pass must run again, 0 when it is done, < 0 on an error.
+int finish_pass(arp_ctx* c) {
+    int again = 0;
+    if (finish_contacts(c)) { CHK(grow_pairs(c)); again = 1; }
+    for (Bag* b : {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp})
+        if (finish_bag(c, *b)) { CHK(grow_bag(c, *b)); again = 1; }
+    const int lists = finish_plane_lists(c, true);
+    if (lists < 0) return lists;
+    return again | lists;
+}
+void pass_counts(arp_ctx* c, int64_t counts[5]) {      // expansion statistics and record counts of a finished pass
+    c->stats[5] = (int64_t)c->h_ctr[C_MARK_CAND];
+    c->stats[6] = (int64_t)c->h_ctr[C_MARK_ACC];
+    if (counts) {
+        counts[0] = c->n_contacts; counts[1] = c->bag_pp.count; counts[2] = c->bag_ap.count;
+        counts[3] = c->bag_gg.count; counts[4] = c->bag_gp.count;
     }
-    if (count) *count = b.count;
-    return ARP_OK;
 }
 
 }  // namespace
@@ -2031,8 +2050,7 @@ int arp_create(int device, arp_ctx** out) {
             (void)hipFree(probe);
         }
         (void)hipGetLastError();
-        static const int force_by_block = env_int("ARP_SIFT_SEG_BY_BLOCK", 0);
-        c->xcd_round_robin = rr && !force_by_block;
+        c->xcd_round_robin = rr && !sw().sift_seg_by_block;
     }
     *out = c;
     return ARP_OK;
@@ -2058,8 +2076,7 @@ void arp_destroy(arp_ctx* c) {
     c->pairs.release(); c->out_i.release(); c->out_j.release(); c->out_d.release(); c->out_s.release(); c->out_ct.release();
     c->bag_ap.release(); c->bag_pp.release(); c->bag_gg.release(); c->bag_gp.release();
     c->bag_pack.release(); c->bag_perm.release();
-    c->sort_key[0].release(); c->sort_key[1].release(); c->sort_val[0].release(); c->sort_val[1].release();
-    c->sort_table.release(); c->sort_total.release(); c->sorted_slab.release();
+    c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
     c->rec_home.release(); c->rec_face[0].release(); c->rec_face[1].release(); c->sh_scan.release(); c->sh_src.release();
@@ -2527,13 +2544,11 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
     PublishArgs pub{c->d_ctr, c->h_ctr_pinned, 0, 0};
     if (polled) { pub.expected = 1; pub.seq = ++c->publish_seq; }
     // (what the second stream waits for below is the structure's copy, not its validation: the event goes in front of the kernel)
-    static const int grids_with_upload = env_int("ARP_GRIDS_WITH_UPLOAD", 1);
-    static const int upload_aside = env_int("ARP_UPLOAD_ASIDE", 1);
     // (not when the context's last structure was a batch: the next call is arp_set_batch again, which throws away whatever was made
     // for the concatenation as ONE structure — whose overlaid coordinates make for enormous candidate lists on top: a batch of 64
     // stand-ins took 3.2 instead of 1.4 ms end to end)
-    const bool with_upload = grids_with_upload && polled && h.n > 0 && h.nring + h.namide > 0 && !after_batch;
-    const bool on_second = with_upload && upload_aside && c->stream2 && c->ev_upload && c->ev_uplists;
+    const bool with_upload = sw().grids_with_upload && polled && h.n > 0 && h.nring + h.namide > 0 && !after_batch;
+    const bool on_second = with_upload && sw().upload_aside && c->stream2 && c->ev_upload && c->ev_uplists;
     // single-bond neighbour coordinates, ring / amide masks, bookkeeping: as the classic setters leave them (before the launches
     // below, which read some of it: ownership flags, the batch, the static state)
     const size_t n1 = (size_t)std::max<int64_t>(h.n, 1);
@@ -2593,8 +2608,7 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
             std::swap(c->stream, c->stream2);
         }
         int rc = ensure_center_grids(c);
-        static const int lists_with_upload = env_int("ARP_LISTS_WITH_UPLOAD", 1);
-        if (rc == ARP_OK && lists_with_upload) rc = ensure_plane_lists(c);      // (the four candidate lists need nothing else: see ar_enumerate)
+        if (rc == ARP_OK && sw().lists_with_upload) rc = ensure_plane_lists(c);      // (the four candidate lists need nothing else: see ar_enumerate)
         if (on_second) {
             std::swap(c->stream, c->stream2);
             if (rc == ARP_OK) {
@@ -2612,8 +2626,7 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
     // the validation kernel and the first launch of the pass, at 100 k atoms), and leave at once when the check has failed
     // (upload_bad: the arrays they would index are what the check is about).  A pass with another cell edge re-orders the columns
     // as it does for any resident structure.
-    static const int static_ahead = env_int("ARP_STATIC_WITH_UPLOAD", 1);
-    if (static_ahead && polled && h.n > 0 && c->last_cutoff > 0 && !after_batch) {
+    if (sw().static_with_upload && polled && h.n > 0 && c->last_cutoff > 0 && !after_batch) {
         c->ahead_seq = bc.seq;
         const int rc = ensure_static(c, c->last_cutoff);
         c->ahead_seq = 0;
@@ -3273,14 +3286,6 @@ int bag_order_large(arp_ctx* c, const int* first, const int* second, size_t k, i
     HIPCHK(c, perm.reserve(2 * k));                       // [0, k): the permutation; [k, 2 k): the indices as the sort's input column
     HIPCHK(c, c->bagsort_i.reserve(k)); HIPCHK(c, c->bagsort_j.reserve(k));
     HIPCHK(c, c->bagsort_s.reserve(2 * k)); HIPCHK(c, c->bagsort_ct.reserve(2 * k));
-    int idbits = 1;
-    while (((int64_t)1 << idbits) <= std::max<int64_t>(idmax, 1)) ++idbits;
-    const int passes = (idbits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
-    for (int q = 0; q < 2; ++q) { HIPCHK(c, c->bagsort_key[q].reserve(k)); HIPCHK(c, c->bagsort_val[q].reserve(k)); }
-    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
-    const int tstride = (int)((tiles + 3) & ~3ll);
-    HIPCHK(c, c->bagsort_table.reserve((size_t)SORT_BINS * (size_t)tstride));
-    HIPCHK(c, c->bagsort_total.reserve(SORT_BINS));
     float* const idx_in = reinterpret_cast<float*>(perm.p + k);
     hipLaunchKernelGGL(k_iota_bits, dim3(nblocks((int64_t)k, 256, 1024)), dim3(256), 0, c->stream, (long long)k, idx_in, c->bagsort_s.p + k, c->bagsort_ct.p + k);
     SortArgs A{};
@@ -3288,26 +3293,7 @@ int bag_order_large(arp_ctx* c, const int* first, const int* second, size_t k, i
     A.d_in = idx_in; A.s_in = c->bagsort_s.p + k; A.ct_in = c->bagsort_ct.p + k;
     A.i_out = c->bagsort_i.p; A.j_out = c->bagsort_j.p; A.d_out = reinterpret_cast<float*>(perm.p);
     A.s_out = c->bagsort_s.p; A.ct_out = c->bagsort_ct.p;
-    A.n = (long long)k; A.T = (int)tiles; A.tstride = tstride; A.jbits = idbits;
-    A.table = c->bagsort_table.p; A.total = c->bagsort_total.p;
-    int shift = idbits;
-    for (int ps = 0; ps < passes; ++ps) {
-        A.first = ps == 0; A.last = 0;
-        A.shift = shift;
-        A.bits = idbits / passes + (ps < idbits % passes ? 1 : 0);
-        shift += A.bits;
-        A.key_in = ps > 0 ? c->bagsort_key[(ps - 1) & 1].p : nullptr;
-        A.val_in = ps > 0 ? c->bagsort_val[(ps - 1) & 1].p : nullptr;
-        A.key_out = c->bagsort_key[ps & 1].p;
-        A.val_out = c->bagsort_val[ps & 1].p;
-        hipLaunchKernelGGL(k_sort_hist, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1 << A.bits), dim3(SORT_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(A.T), dim3(SORT_THREADS), 0, c->stream, A);
-    }
-    A.key_in = c->bagsort_key[(passes - 1) & 1].p;
-    A.val_in = c->bagsort_val[(passes - 1) & 1].p;
-    hipLaunchKernelGGL(k_sort_runs, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, A);
-    return check_launch(c, "bag_order_large");
+    return radix_sort(c, c->sort_bags, A, k, k, id_bits(idmax), 0, "bag_order_large");
 }
 
 // Every result of the last pass with ONE copy: the atom-atom bag in canonical order (sorted on the device if it is not yet)
@@ -3402,9 +3388,8 @@ int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts
         // A small piece (a protein's bags: a few hundred kilobytes) into a page-locked, device-visible buffer is written by a kernel:
         // the copy engine needs ~10 us to get going, which is as long as such a copy takes (stand-in end to end 0.155 -> see
         // profiles/README.md).  Anything larger, or a pageable buffer: the copy engine.
-        static const size_t direct_max = (size_t)std::max(0, env_int("ARP_FETCH_DIRECT_MAX_KB", 1024)) << 10;
         void* host_dev = nullptr;
-        if (total <= direct_max && host_bytes >= ((total + 15) & ~(uint64_t)15) && c->sorted_slab.cap >= ((total + 15) & ~(size_t)15)) {      // (whole quads on both sides)
+        if (total <= sw().fetch_direct_max && host_bytes >= ((total + 15) & ~(uint64_t)15) && c->sorted_slab.cap >= ((total + 15) & ~(size_t)15)) {      // (whole quads on both sides)
             hipPointerAttribute_t at{};
             if (hipPointerGetAttributes(&at, host) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) host_dev = at.devicePointer;
             else (void)hipGetLastError();
@@ -3502,27 +3487,10 @@ int arp_atom_integer_sifts(arp_ctx* c, uint8_t* out_isift) {
 // atoms of a ring's cells as it meets them, does less); the two amide loops 19 - 20 us either way (a chain of five dependent round
 // trips whatever evaluates 1.5 k records).  ARP_BAG_LISTS: bit k = loop k from its list (default 2: plane-plane), 0 = every loop by
 // its grid walk as through round 5, 15 = all four from the lists (the way a whole pass evaluates them).
-static bool bag_walk(int kind = 1) { static const int v = env_int("ARP_BAG_LISTS", 2); return ((v >> kind) & 1) == 0; }
-int arp_atom_plane_launch(arp_ctx* c, int64_t* count) {
-    if (!c) return ARP_E_ARG;
-    if (!bag_walk(0)) return bag_launch_lists(c, c->bag_ap, C_AP, true, false, 0, count);
-    return bag_launch(c, c->bag_ap, C_AP, true, false, enqueue_atom_plane, count);
-}
-int arp_plane_plane_launch(arp_ctx* c, int64_t* count) {
-    if (!c) return ARP_E_ARG;
-    if (!bag_walk(1)) return bag_launch_lists(c, c->bag_pp, C_PP, true, false, 1, count);
-    return bag_launch(c, c->bag_pp, C_PP, true, false, enqueue_plane_plane, count);
-}
-int arp_group_group_launch(arp_ctx* c, int64_t* count) {
-    if (!c) return ARP_E_ARG;
-    if (!bag_walk(2)) return bag_launch_lists(c, c->bag_gg, C_GG, false, true, 2, count);
-    return bag_launch(c, c->bag_gg, C_GG, false, true, enqueue_group_group, count);
-}
-int arp_group_plane_launch(arp_ctx* c, int64_t* count) {
-    if (!c) return ARP_E_ARG;
-    if (!bag_walk(3)) return bag_launch_lists(c, c->bag_gp, C_GP, true, false, 3, count);
-    return bag_launch(c, c->bag_gp, C_GP, true, false, enqueue_group_plane, count);
-}
+int arp_atom_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_ap, 0, count) : ARP_E_ARG; }
+int arp_plane_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_pp, 1, count) : ARP_E_ARG; }
+int arp_group_group_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_gg, 2, count) : ARP_E_ARG; }
+int arp_group_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_gp, 3, count) : ARP_E_ARG; }
 
 #define FETCH_PROLOGUE(bag, what)                                                                  \
     if (!c || !count) return ARP_E_ARG;                                                           \
@@ -3677,9 +3645,8 @@ int run_pass_enqueue(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
         CHK(ensure_static(c, cutoff));       // (the spatial order of the columns is the one of this pass's cells)
         c->last_cutoff = cutoff;
         // The pass ends inside its last kernel (k_sift_planes): the last block to finish publishes the counters.
-        static const int inkernel_publish = env_int("ARP_INKERNEL_PUBLISH", 1);
         c->pub = PublishArgs{c->d_ctr, c->h_ctr_pinned, 0, 0};
-        if (inkernel_publish && !c->external_stream) {
+        if (sw().inkernel_publish && !c->external_stream) {
             c->pub.expected = 1;
             c->pub.seq = ++c->publish_seq;
         }
@@ -3722,17 +3689,6 @@ int run_pass_enqueue(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
 
 int run_pass_wait(arp_ctx* c, int64_t counts[5]) {
     HIPCHK(c, hipSetDevice(c->device));
-    auto any_overflow = [&](bool grow) -> int {   // returns 1 when a buffer was too small (and regrows it if asked)
-        int again = 0;
-        if (finish_contacts(c)) { if (grow) CHK(grow_pairs(c)); again = 1; }
-        if (finish_bag(c, c->bag_ap, C_AP)) { if (grow) CHK(grow_bag(c, c->bag_ap, C_AP, true, false)); again = 1; }
-        if (finish_bag(c, c->bag_pp, C_PP)) { if (grow) CHK(grow_bag(c, c->bag_pp, C_PP, true, false)); again = 1; }
-        if (finish_bag(c, c->bag_gg, C_GG)) { if (grow) CHK(grow_bag(c, c->bag_gg, C_GG, false, true)); again = 1; }
-        if (finish_bag(c, c->bag_gp, C_GP)) { if (grow) CHK(grow_bag(c, c->bag_gp, C_GP, true, false)); again = 1; }
-        const int lists = finish_plane_lists(c, grow);
-        if (lists < 0) return lists;
-        return again | lists;
-    };
     for (int attempt = 0;; ++attempt) {
         const auto t1 = std::chrono::steady_clock::now();
         CHK(collect_counters(c));
@@ -3740,18 +3696,13 @@ int run_pass_wait(arp_ctx* c, int64_t counts[5]) {
         c->host_wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
         ++c->host_passes;
         collect_events(c);
-        const int again = any_overflow(true);
+        const int again = finish_pass(c);
         if (again < 0) return again;
         if (!again) break;
         if (attempt == 2) FAIL(c, ARP_E_CAPACITY, "arp_run_launch: result buffers could not be sized");
         CHK(run_pass_enqueue(c, c->pending_cutoff, c->pending_comp, c->pending_seq_adj, c->pending_expand));   // a buffer was too small: once more
     }
-    c->stats[5] = (int64_t)c->h_ctr[C_MARK_CAND];
-    c->stats[6] = (int64_t)c->h_ctr[C_MARK_ACC];
-    if (counts) {
-        counts[0] = c->n_contacts; counts[1] = c->bag_pp.count; counts[2] = c->bag_ap.count;
-        counts[3] = c->bag_gg.count; counts[4] = c->bag_gp.count;
-    }
+    pass_counts(c, counts);
     const int rc_dev = device_error(c);
     if (rc_dev == ARP_OK && c->sort_after_pass && c->contacts_valid && c->n_contacts > 0 && c->n_contacts < ((int64_t)1 << 31)) {
         // (room for the ring / amide bags behind the sorted columns, as arp_fetch_packed lays them out: at most 52 bytes a record
@@ -3851,26 +3802,12 @@ int arp_run_stage(arp_ctx* c, int stage, double cutoff, double vdw_comp, int inc
         CHK(enqueue_counter_copy(c));
         CHK(collect_counters(c));
         collect_events(c);
-        int again = 0;
-        if (finish_contacts(c)) { CHK(grow_pairs(c)); again = 1; }
-        if (finish_bag(c, c->bag_ap, C_AP)) { CHK(grow_bag(c, c->bag_ap, C_AP, true, false)); again = 1; }
-        if (finish_bag(c, c->bag_pp, C_PP)) { CHK(grow_bag(c, c->bag_pp, C_PP, true, false)); again = 1; }
-        if (finish_bag(c, c->bag_gg, C_GG)) { CHK(grow_bag(c, c->bag_gg, C_GG, false, true)); again = 1; }
-        if (finish_bag(c, c->bag_gp, C_GP)) { CHK(grow_bag(c, c->bag_gp, C_GP, true, false)); again = 1; }
-        {
-            const int lists = finish_plane_lists(c, true);
-            if (lists < 0) return lists;
-            again |= lists;
-        }
+        const int again = finish_pass(c);
+        if (again < 0) return again;
         if (!again) break;
         if (attempt == 2) FAIL(c, ARP_E_CAPACITY, "arp_run_stage: result buffers could not be sized");
     }
-    c->stats[5] = (int64_t)c->h_ctr[C_MARK_CAND];
-    c->stats[6] = (int64_t)c->h_ctr[C_MARK_ACC];
-    if (counts) {
-        counts[0] = c->n_contacts; counts[1] = c->bag_pp.count; counts[2] = c->bag_ap.count;
-        counts[3] = c->bag_gg.count; counts[4] = c->bag_gp.count;
-    }
+    pass_counts(c, counts);
     return device_error(c);
 }
 
