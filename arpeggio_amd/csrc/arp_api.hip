@@ -386,7 +386,6 @@ struct arp_ctx {
     DevBuf<u64> plist_count;       // [4]
     bool plist_count_cleared = false;   // k_point_grids has just zeroed them (same stream, same pass)
     bool lists_dirty = true;
-    bool lists_from_upload = false;   // the lists in place were made with the upload of the resident structure (validate_resident_blob): composing its static columns does not stale them
     long long plist_known[4] = {-1, -1, -1, -1};   // entries the lists held at the end of the last pass (-1: not known yet)
     DevBuf<uint8_t> blob_dev;      // device copy of the last arp_set_blob upload (the input arrays are views into it)
     int64_t blob_nbond = 0, blob_nh = 0, blob_nrad = 0;
@@ -610,6 +609,77 @@ void make_grid_desc(GridDesc& d, const double lo[3], const double hi[3], double 
     d.place = nullptr; d.sid_atom = nullptr; d.sid_ring = nullptr; d.sid_amide = nullptr;
 }
 
+// What a caller can replace, for inputs_changed.  IN_BATCH_GRIDS is no input: batch_grid_desc replaced the grid tables of the
+// batch (every slot held another radius).
+enum : unsigned {
+    IN_ATOMS = 1u << 0, IN_RESIDUES = 1u << 1, IN_BONDS = 1u << 2, IN_HYDROGENS = 1u << 3,
+    IN_NEIGHBOURS = 1u << 4,        // single-bond neighbours: indices or coordinates
+    IN_RINGS = 1u << 5, IN_AMIDES = 1u << 6, IN_OWNERSHIP = 1u << 7, IN_GROUP_OWNERSHIP = 1u << 8,
+    IN_SELECTION = 1u << 9, IN_SELECTION_STATE = 1u << 10, IN_BATCH = 1u << 11, IN_WHOLE_STRUCTURE = 1u << 12,
+    IN_EVERYTHING = (1u << 13) - 1,   // a new structure: blob upload, shard assembly, an upload abandoned
+    IN_BATCH_GRIDS = 1u << 13,
+};
+
+// The one place that marks derived state stale because an input changed; whoever builds an artefact sets it valid again.
+//
+//   input                  static  lists  contact  all-atom  centre  batch  selection  default    results
+//                          columns        grid     grid      grids                     selection
+//   atoms                  x       x      x        x         (b)     x      x          x          x
+//   residues               x       x      x        x                        x                     x
+//   bonds, hydrogens       x       x                                                              x
+//   single-bond nbrs       x       x                                                              x
+//   rings / amides         x       x                         own(b)  x      x                     x
+//   ownership              x       x      x        x         (b)     x                            x
+//   group ownership        x       x                         (b)     x                            x
+//   selection                                      x                        x                     x
+//   selection state        x (s)   x      x        x                        x                     x
+//   batch                  x       x      x        x         x       x                            x
+//   whole structure                                                                               x
+//   batch grid tables      x (k)   x      x        x         x                                    (no input)
+//
+// static columns: k_prepare_static's records and their spatial order; the contact count of the last pass that sizes the sift
+//   launch goes with them.  The lists are made beside them (from the centre grids and the atoms as uploaded), so whatever
+//   stales the columns stales the lists at the same moment.
+// (s) the static columns read no selection; a staged shard pass recomposes them all the same (a change of that is a change of
+//   the kernels the staged path launches).  (k) the same structure in new grid tables keeps its contact count.
+// contact grid: what atom_grid was built from; the whole-structure reuse also checks its GridKey.  all-atom grid: M_SEL is in
+//   its records.
+// centre grids: a ring / amide upload voids its own grid; (b) both, when a batch partition was in force: they were built in
+//   its layout.  A reset with no partition in force voids none (the shard path sets ownership over grids made with the upload).
+// batch: the partition was declared for the arrays that were resident then (arp_set_batch again after the change); its grid
+//   tables go with it.  arp_set_batch records the new partition after this call.
+// selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
+//   with everything selected (I:1395) and no whole-structure assertion.
+// results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.
+void inputs_changed(arp_ctx* c, unsigned what) {
+    const unsigned columns = IN_EVERYTHING & ~(IN_SELECTION | IN_WHOLE_STRUCTURE);
+    const unsigned partition = IN_ATOMS | IN_RINGS | IN_AMIDES | IN_OWNERSHIP | IN_GROUP_OWNERSHIP | IN_BATCH;
+    const unsigned layout = IN_BATCH | IN_BATCH_GRIDS;
+    if (what & (columns | IN_BATCH_GRIDS)) c->static_dirty = c->lists_dirty = true;
+    if (what & columns) c->contacts_expected = 0;
+    if (what & (IN_ATOMS | IN_RESIDUES | IN_OWNERSHIP | IN_SELECTION_STATE | layout)) c->atom_grid.valid = false;
+    if (what & (IN_ATOMS | IN_RESIDUES | IN_OWNERSHIP | IN_SELECTION | IN_SELECTION_STATE | layout)) c->all_grid_current = false;
+    const bool relaid = (what & layout) || ((what & partition) && c->batch_n > 0);
+    if (relaid || (what & IN_RINGS)) c->ring_grid.valid = false;
+    if (relaid || (what & IN_AMIDES)) c->amide_grid.valid = false;
+    if (what & partition) {
+        c->batch_n = 0;
+        for (auto& g : c->batch_grid) g.valid = false;
+    }
+    if (what & (IN_ATOMS | IN_RESIDUES | IN_RINGS | IN_AMIDES | IN_SELECTION | IN_SELECTION_STATE)) {
+        c->sel_made = false;
+        ++c->sel_epoch;
+    }
+    if (what & IN_ATOMS) {
+        c->sel_uploaded = c->sel_prefilled = c->sel_all = c->whole_structure = false;
+        c->nsel = -1;
+    }
+    if (what & IN_EVERYTHING) {
+        c->contacts_valid = false;
+        c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
+    }
+}
+
 // Several structures in one grid (arp_set_batch): every structure gets the cells its own box needs at this cell edge and a
 // place in a common grid — shelves along x, rows along y, layers along z, one empty cell between neighbours in every
 // direction, the whole as near to a cube as the largest structure allows.  Cached per radius.
@@ -622,8 +692,7 @@ int batch_grid_desc(arp_ctx* c, GridDesc& d, double radius) {
     if (!slot) {   // every slot holds another radius: start over (grids built with the old tables are rebuilt)
         for (auto& g : c->batch_grid) g.valid = false;
         slot = &c->batch_grid[0];
-        c->static_dirty = true; c->lists_from_upload = false; c->lists_dirty = true;
-        c->atom_grid.valid = false; c->all_grid_current = false; c->ring_grid.valid = false; c->amide_grid.valid = false;
+        inputs_changed(c, IN_BATCH_GRIDS);
     }
     const int64_t B = c->batch_n;
     double edge = radius * (1.0 + 1e-6);
@@ -672,10 +741,6 @@ int batch_grid_desc(arp_ctx* c, GridDesc& d, double radius) {
     slot->d = g; slot->radius = radius; slot->valid = true;
     d = g;
     return ARP_OK;
-}
-void batch_reset(arp_ctx* c) {   // a new upload: one structure until arp_set_batch says otherwise
-    c->batch_n = 0;
-    for (auto& g : c->batch_grid) g.valid = false;
 }
 // the grid of a pass over the resident structure(s)
 int grid_desc_for(arp_ctx* c, GridDesc& d, const double lo[3], const double hi[3], double radius) {
@@ -793,9 +858,6 @@ int ensure_static(arp_ctx* c, double radius = 0.0) {
     if (!columns && c->sp_radius == radius) return ARP_OK;
     const int n = (int)c->n;
     if (columns) {
-        if (!c->lists_from_upload) c->lists_dirty = true;      // (lists made with the upload read what these columns are composed from)
-        c->lists_from_upload = false;
-        c->contacts_expected = 0;
         HIPCHK(c, c->st_qa.reserve((size_t)std::max(n, 1)));
         HIPCHK(c, c->st_h.reserve((size_t)std::max(n, 1)));
         HIPCHK(c, c->st_aux.reserve((size_t)std::max(n, 1)));
@@ -2119,7 +2181,7 @@ int arp_set_atoms(arp_ctx* c, int64_t n, const float* xyz, const double* vdw, co
     HIPCHK(c, hipSetDevice(c->device));
     // uploads below are enqueued together; whatever the exit path, they are complete before the staging vectors die
     struct SyncOnExit { arp_ctx* c; ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); } } sync_on_exit{c};
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_ATOMS);
     c->n = n;
     c->h_xyz.assign(xyz, xyz + 3 * n);
     host_bbox(xyz, n, c->lo, c->hi);
@@ -2171,16 +2233,6 @@ int arp_set_atoms(arp_ctx* c, int64_t n, const float* xyz, const double* vdw, co
     CHK(upload_done(c));   // (the staging vectors above live until here)
     c->has_gid = c->has_home = false;
     c->gid_max = -1;
-    batch_reset(c);
-    c->sel_made = false;
-    c->sel_uploaded = false;   // a new structure starts with the default selection: everything (I:1395)
-    c->sel_prefilled = false;
-    c->nsel = -1;
-    c->sel_all = false;
-    c->whole_structure = false;
-    c->contacts_valid = false;
-    c->atom_grid.valid = false;
-    c->all_grid_current = false;
     return ARP_OK;
 }
 
@@ -2189,49 +2241,43 @@ int arp_set_residues(arp_ctx* c, int64_t nres, const uint8_t* res_flags, const i
     if (nres < 0 || (nres > 0 && (!res_flags || !prev || !next))) FAIL(c, ARP_E_ARG, "arp_set_residues: bad input");
     if (nres <= c->max_res_id) FAIL(c, ARP_E_ARG, "arp_set_residues: an atom refers to a residue beyond the table");
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_RESIDUES);
     c->nres = nres;
     CHK(upload(c, c->res_flags, res_flags, (size_t)nres));
     CHK(upload(c, c->res_prev, prev, (size_t)nres));
     CHK(upload(c, c->res_next, next, (size_t)nres));
     c->has_res = true;
-    c->atom_grid.valid = false;
-    c->all_grid_current = false;
-    c->sel_made = false;
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
 int arp_set_bonds(arp_ctx* c, const int32_t* bond_off, const int32_t* bond_idx) {
     if (!c || !bond_off) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_BONDS);
     if (!csr_ok(bond_off, c->n)) FAIL(c, ARP_E_ARG, "arp_set_bonds: offsets must start at 0 and never decrease");
     const int64_t m = bond_off[c->n];
     if (m < 0 || (m > 0 && !bond_idx)) FAIL(c, ARP_E_ARG, "arp_set_bonds: bad CSR");
     CHK(upload(c, c->bond_off, bond_off, (size_t)c->n + 1));
     CHK(upload(c, c->bond_idx, bond_idx, (size_t)m));
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
 int arp_set_hydrogens(arp_ctx* c, const int32_t* h_off, const double* h_xyz) {
     if (!c || !h_off) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_HYDROGENS);
     if (!csr_ok(h_off, c->n)) FAIL(c, ARP_E_ARG, "arp_set_hydrogens: offsets must start at 0 and never decrease");
     const int64_t m = h_off[c->n];
     if (m < 0 || (m > 0 && !h_xyz)) FAIL(c, ARP_E_ARG, "arp_set_hydrogens: bad CSR");
     CHK(upload(c, c->h_off, h_off, (size_t)c->n + 1));
     CHK(upload(c, c->h_xyz_d, h_xyz, (size_t)m * 3));
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
 int arp_set_single_bond_neighbours(arp_ctx* c, const int32_t* sb_nbr) {
     if (!c || (c->n > 0 && !sb_nbr)) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_NEIGHBOURS);
     for (int64_t i = 0; i < c->n; ++i)
         if (sb_nbr[i] < -1 || sb_nbr[i] >= c->n) FAIL(c, ARP_E_ARG, "arp_set_single_bond_neighbours: index out of range");
     // the neighbour's coordinates are gathered on the device from the uploaded atoms (x, y, z, 1) / (0, 0, 0, 0)
@@ -2242,7 +2288,6 @@ int arp_set_single_bond_neighbours(arp_ctx* c, const int32_t* sb_nbr) {
         CHK(check_launch(c, "k_gather_neighbours"));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
@@ -2257,8 +2302,7 @@ int arp_set_rings(arp_ctx* c, int64_t nring, const double* center, const double*
         c->max_ring_res = std::max<int64_t>(c->max_ring_res, ring_res[i]);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    batch_reset(c);      // (the partition of a batch was declared for the arrays that were resident then: arp_set_batch again after this call)
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_RINGS);
     c->nring = nring;
     host_bbox_d(center, nring, c->ring_lo, c->ring_hi);
     CHK(upload(c, c->ring_c, center, (size_t)nring * 3));
@@ -2266,8 +2310,6 @@ int arp_set_rings(arp_ctx* c, int64_t nring, const double* center, const double*
     CHK(upload(c, c->ring_res, ring_res, (size_t)nring));
     HIPCHK(c, c->ring_sel.reserve((size_t)std::max<int64_t>(nring, 1)));
     HIPCHK(c, c->ring_plus.reserve((size_t)std::max<int64_t>(nring, 1)));
-    c->ring_grid.valid = false;
-    c->sel_made = false;
     c->has_group_owner = false;
     return ARP_OK;
 }
@@ -2283,8 +2325,7 @@ int arp_set_amides(arp_ctx* c, int64_t namide, const float* center, const float*
         c->max_amide_res = std::max<int64_t>(c->max_amide_res, amide_res[i]);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    batch_reset(c);      // (the partition of a batch was declared for the arrays that were resident then: arp_set_batch again after this call)
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_AMIDES);
     c->namide = namide;
     host_bbox(center, namide, c->am_lo, c->am_hi);
     CHK(upload(c, c->am_c, center, (size_t)namide * 3));
@@ -2292,8 +2333,6 @@ int arp_set_amides(arp_ctx* c, int64_t namide, const float* center, const float*
     CHK(upload(c, c->am_res, amide_res, (size_t)namide));
     HIPCHK(c, c->am_sel.reserve((size_t)std::max<int64_t>(namide, 1)));
     HIPCHK(c, c->am_plus.reserve((size_t)std::max<int64_t>(namide, 1)));
-    c->amide_grid.valid = false;
-    c->sel_made = false;
     c->has_group_owner = false;
     return ARP_OK;
 }
@@ -2555,17 +2594,11 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
     HIPCHK(c, c->sb.reserve(n1));
     HIPCHK(c, c->ring_sel.reserve((size_t)std::max<int64_t>(h.nring, 1))); HIPCHK(c, c->ring_plus.reserve((size_t)std::max<int64_t>(h.nring, 1)));
     HIPCHK(c, c->am_sel.reserve((size_t)std::max<int64_t>(h.namide, 1))); HIPCHK(c, c->am_plus.reserve((size_t)std::max<int64_t>(h.namide, 1)));
-    c->static_dirty = true;
-    c->lists_dirty = true;
-    c->lists_from_upload = false;
+    inputs_changed(c, IN_EVERYTHING);
     c->has_gid = c->has_home = c->has_group_owner = false;
     c->gid_max = -1;
     c->shard_resident = false;
-    batch_reset(c);
-    c->sel_made = false; c->sel_uploaded = false; c->nsel = -1; c->sel_all = false; c->whole_structure = false;
     c->sel_prefilled = true; c->sp_cnt_zeroed = zero_ints;      // (k_validate_blob's fills)
-    c->contacts_valid = false;
-    c->atom_grid.valid = false; c->all_grid_current = false;
     // a failed check also leaves the number of this upload in a word of its own (the error word goes back to zero when the verdict
     // is published): kernels enqueued ahead of the verdict look at it and leave (speculative static order, below)
     HIPCHK(c, c->upload_bad.reserve(1));
@@ -2581,30 +2614,26 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
     // its grid build (ARP_UPLOAD_ASIDE=0: behind the validation kernel on the main stream, where the static order of the first pass
     // then waits for them: 25 us of latency chains at 100 k atoms).  A structure that fails the validation has them thrown away
     // below: centres outside their box are clamped into it, nothing is written out of bounds.
-    // A failure behind the validation kernel (an allocation, a launch): its verdict is still on its way and kernels of the second
-    // stream may be reading the blob — wait for both streams, consume what was published, leave no structure resident.
+    // A failure behind the validation kernel (an allocation, a launch) or a failed verdict: the verdict may still be on its way
+    // and kernels of the second stream may be reading the blob — wait for both streams, consume what was published, leave no
+    // structure resident.
     auto abandon = [&](int rc) -> int {
         const std::string why = c->err;
         if (c->stream2) (void)hipStreamSynchronize(c->stream2);
         if (polled) (void)collect_counters(c); else (void)hipStreamSynchronize(c->stream);
         c->err = why;
         c->uplists_pending = false;
+        inputs_changed(c, IN_EVERYTHING);
         c->n = c->nres = c->nring = c->namide = 0;
         c->blob_bytes = 0;
-        c->static_dirty = true; c->sp_radius = 0;
-        c->lists_dirty = true; c->lists_from_upload = false;
-        c->ring_grid.valid = false; c->amide_grid.valid = false;
+        c->sp_radius = 0;
         c->sel_prefilled = false; c->sp_cnt_zeroed = 0;
         c->ctr_zero_ok = false;
         return rc;
     };
-    bool grids_made = false;
     if (with_upload) {
-        c->ring_grid.valid = false; c->amide_grid.valid = false;
-        c->lists_dirty = true;
-        batch_reset(c);
         if (on_second) {
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_upload, 0));
+            if (hipStreamWaitEvent(c->stream2, c->ev_upload, 0) != hipSuccess) { c->err = "hipStreamWaitEvent failed (upload lists)"; return abandon(ARP_E_HIP); }
             std::swap(c->stream, c->stream2);
         }
         int rc = ensure_center_grids(c);
@@ -2617,10 +2646,7 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
             }
         }
         if (rc != ARP_OK) return abandon(rc);
-        grids_made = true;
     }
-    const bool ring_grid_made = grids_made && c->ring_grid.valid, amide_grid_made = grids_made && c->amide_grid.valid;
-    const bool lists_made = grids_made && !c->lists_dirty;
     // The static columns of the structure and their spatial order — the first three launches of its first pass — go out NOW, for the
     // cell edge of the context's last pass: they run while the host waits for the verdict and turns round (13 us between the end of
     // the validation kernel and the first launch of the pass, at 100 k atoms), and leave at once when the check has failed
@@ -2634,25 +2660,18 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
     }
     int h_err[2] = {0, 0};
     if (polled) {
-        CHK(collect_counters(c));
+        const int rc = collect_counters(c);
+        if (rc != ARP_OK) return abandon(rc);
         h_err[0] = (int)(uint32_t)c->h_ctr[C_ERR];
     } else {
         HIPCHK(c, hipMemcpyAsync(&h_err[0], d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (also) HIPCHK(c, hipMemcpyAsync(&h_err[1], also, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    c->lists_dirty = !lists_made;
-    c->lists_from_upload = lists_made;
-    const bool verdict_ok = h_err[0] == 0 && h_err[1] == 0;
-    if (!verdict_ok) { c->static_dirty = true; c->sp_radius = 0; }      // (whatever was composed ahead of the verdict is void)
-    c->ring_grid.valid = verdict_ok && ring_grid_made; c->amide_grid.valid = verdict_ok && amide_grid_made;
-    c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
-    if (h_err[0] != 0 || h_err[1] != 0) {
-        c->n = c->nres = c->nring = c->namide = 0;   // nothing usable is resident
-        c->blob_bytes = 0;
+    if (h_err[0] != 0 || h_err[1] != 0) {      // (whatever was made ahead of the verdict is void)
         c->err = std::string(who) + ": the structure failed validation (non-finite value, point outside its box, index out of range, "
                                     "offsets that are not a CSR, or an item that occurs twice)";
-        return ARP_E_ARG;
+        return abandon(ARP_E_ARG);
     }
     c->ctr_zero_ok = polled ? true : counters_were_zero;      // (polled: the publishing block returned every counter to zero)
     return ARP_OK;
@@ -2925,7 +2944,7 @@ int arp_shard_assemble(arp_ctx* c, uint64_t dev_left, uint64_t bytes_left, uint6
     CHK(join_upload_lists(c));
     if (!c->has_rec_home) FAIL(c, ARP_E_ARG, "arp_shard_assemble: call arp_shard_set_home first");
     HIPCHK(c, hipSetDevice(c->device));
-    batch_reset(c);      // (a shard is one structure)
+    inputs_changed(c, IN_EVERYTHING);      // (the blob of the resident structure is overwritten below)
     arp_rec_header hd[3];
     hd[0] = c->rec_home_hdr;
     const uint8_t* base[3] = {c->rec_home.p, (const uint8_t*)(uintptr_t)dev_left, (const uint8_t*)(uintptr_t)dev_right};
@@ -3054,8 +3073,7 @@ int arp_shard_layout(arp_ctx* c, int32_t* global_id, int8_t* origin, uint8_t* se
 int arp_set_ownership(arp_ctx* c, const uint8_t* is_home, const int32_t* global_id) {
     if (!c) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    batch_reset(c);      // (the partition of a batch was declared for the arrays that were resident then: arp_set_batch again after this call)
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_OWNERSHIP);      // (M_HOME is part of the sorted records)
     if (is_home) { CHK(upload(c, c->home, is_home, (size_t)c->n)); c->has_home = true; }
     else c->has_home = false;
     if (global_id) {
@@ -3066,9 +3084,6 @@ int arp_set_ownership(arp_ctx* c, const uint8_t* is_home, const int32_t* global_
         c->has_gid = true;
         c->gid_max = c->n > 0 ? (int64_t)global_id[c->n - 1] : -1;
     } else { c->has_gid = false; c->gid_max = -1; }
-    c->atom_grid.valid = false;   // M_HOME is part of the sorted records
-    c->all_grid_current = false;
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
@@ -3076,8 +3091,7 @@ int arp_set_group_ownership(arp_ctx* c, const uint8_t* ring_home, const int32_t*
                             const int32_t* amide_gid) {
     if (!c) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    batch_reset(c);      // (a shard is one structure)
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_GROUP_OWNERSHIP);
     if (!ring_home && !ring_gid && !amide_home && !amide_gid) { c->has_group_owner = false; return ARP_OK; }
     if ((c->nring > 0 && (!ring_home || !ring_gid)) || (c->namide > 0 && (!amide_home || !amide_gid)))
         FAIL(c, ARP_E_ARG, "arp_set_group_ownership: all four arrays are required");
@@ -3094,12 +3108,11 @@ int arp_set_group_ownership(arp_ctx* c, const uint8_t* ring_home, const int32_t*
 int arp_set_single_bond_neighbour_coords(arp_ctx* c, const float* sb_xyz, const uint8_t* sb_present) {
     if (!c || (c->n > 0 && (!sb_xyz || !sb_present))) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_NEIGHBOURS);
     std::vector<float4> sb((size_t)c->n);
     for (int64_t i = 0; i < c->n; ++i)
         sb[i] = sb_present[i] ? make_float4(sb_xyz[3 * i], sb_xyz[3 * i + 1], sb_xyz[3 * i + 2], 1.0f) : make_float4(0, 0, 0, 0);
     CHK(upload(c, c->sb, sb.data(), (size_t)c->n));
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
@@ -3110,26 +3123,22 @@ int arp_set_selection_state(arp_ctx* c, const uint8_t* in_selection, const uint8
         (c->namide > 0 && (!amide_sel || !amide_plus)))
         FAIL(c, ARP_E_ARG, "arp_set_selection_state: null input");
     HIPCHK(c, hipSetDevice(c->device));
-    c->static_dirty = true; c->lists_from_upload = false;
+    inputs_changed(c, IN_SELECTION_STATE);
     CHK(upload(c, c->sel, in_selection, (size_t)c->n));
     CHK(upload(c, c->plus, in_plus, (size_t)c->n));
     c->sel_uploaded = true;
     c->nsel = -1;
     c->sel_all = false;   // the caller's masks are taken as they are
-    ++c->sel_epoch;
     CHK(upload(c, c->ring_sel, ring_sel, (size_t)c->nring)); CHK(upload(c, c->ring_plus, ring_plus, (size_t)c->nring));
     CHK(upload(c, c->am_sel, amide_sel, (size_t)c->namide)); CHK(upload(c, c->am_plus, amide_plus, (size_t)c->namide));
     c->sel_made = true;
-    c->atom_grid.valid = false;
-    c->all_grid_current = false;
-    c->contacts_valid = false;
-    c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     return ARP_OK;
 }
 
 int arp_set_selection(arp_ctx* c, const uint8_t* in_selection) {
     if (!c || (c->n > 0 && !in_selection)) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    inputs_changed(c, IN_SELECTION);      // (expansion pending)
     CHK(upload(c, c->sel, in_selection, (size_t)c->n));
     c->sel_uploaded = true;
     // how many atoms are selected decides how selection_plus is computed (arp_run_launch): everything -> nothing to do,
@@ -3144,10 +3153,6 @@ int arp_set_selection(arp_ctx* c, const uint8_t* in_selection) {
     c->nsel = nsel;
     c->sel_all = (nsel == c->n);
     if (nsel > 0 && nsel <= SMALL_SEL_MAX) CHK(upload(c, c->sel_list, list.data(), (size_t)nsel));
-    c->sel_made = false;  // expansion pending
-    ++c->sel_epoch;
-    c->all_grid_current = false;
-    c->contacts_valid = false;
     return ARP_OK;
 }
 
@@ -3973,9 +3978,7 @@ int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const in
     if (!c) return ARP_E_ARG;
     CHK(join_upload_lists(c));
     if (nstruct == 0) {   // back to one structure
-        batch_reset(c);
-        c->static_dirty = true; c->lists_from_upload = false; c->lists_dirty = true;
-        c->atom_grid.valid = false; c->all_grid_current = false; c->ring_grid.valid = false; c->amide_grid.valid = false;
+        inputs_changed(c, IN_BATCH);
         return ARP_OK;
     }
     if (nstruct < 0 || !atom_off || !ring_off || !amide_off || !boxes) FAIL(c, ARP_E_ARG, "arp_set_batch: bad input");
@@ -3995,7 +3998,7 @@ int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const in
         }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    batch_reset(c);
+    inputs_changed(c, IN_BATCH);
     c->batch_atom_off.assign(atom_off, atom_off + nstruct + 1);
     c->batch_ring_off.assign(ring_off, ring_off + nstruct + 1);
     c->batch_amide_off.assign(amide_off, amide_off + nstruct + 1);
@@ -4017,10 +4020,6 @@ int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const in
         CHK(check_launch(c, "k_fill_sid"));
     }
     c->batch_n = nstruct;
-    c->static_dirty = true; c->lists_from_upload = false; c->lists_dirty = true;
-    c->contacts_valid = false;
-    c->atom_grid.valid = false; c->all_grid_current = false; c->ring_grid.valid = false; c->amide_grid.valid = false;
-    c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     return ARP_OK;
 }
 
@@ -4214,9 +4213,8 @@ int arp_set_grid_reuse(arp_ctx* c, int enabled) {
 
 int arp_set_whole_structure(arp_ctx* c, int enabled) {
     if (!c) return ARP_E_ARG;
+    inputs_changed(c, IN_WHOLE_STRUCTURE);
     c->whole_structure = enabled != 0;
-    c->contacts_valid = false;
-    c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     return ARP_OK;
 }
 

@@ -334,7 +334,9 @@ int arp_plane_plane(arp_ctx* ctx, int64_t cap, int32_t* out_bgn, int32_t* out_en
                     double* out_theta_end, uint8_t* out_type1, uint8_t* out_type2,
                     uint8_t* out_ctype, int64_t* count);
 
-/* launch-only / fetch-only halves of the four calls in this section and the next */
+/* launch-only / fetch-only halves of the four calls in this section and the next.  A call that replaces an input (structure,
+ * selection, ownership, batch, whole-structure assertion; arp_set_blob and arp_shard_assemble included) voids the results of
+ * the last launch: these four fetches, arp_atom_contacts_fetch and arp_fetch_packed return ARP_E_ARG until the next launch. */
 int arp_atom_plane_launch(arp_ctx* ctx, int64_t* count);
 int arp_plane_plane_launch(arp_ctx* ctx, int64_t* count);
 int arp_group_group_launch(arp_ctx* ctx, int64_t* count);

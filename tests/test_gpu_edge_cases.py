@@ -732,3 +732,108 @@ def test_sift_blocks_dealt_by_index_give_the_same_contacts():
         assert r.returncode == 0, r.stderr[-2000:]
         res[mode] = json.loads(r.stdout.strip().splitlines()[-1])
     assert res['0'] == res['1'] and all(v[0]['atom_atom'] > 1000 for v in res['0'].values()), res
+
+
+def _input_change_structure():
+    """Two structures in one space (a batch can be declared over them: its grids keep them apart) with rings, amides, hydrogens,
+    bonds, single-bond neighbours and a chlorine xbond donor."""
+    from arpeggio_amd import batch, synth
+    prot = synth.proteinlike(n_res=60, n_waters=30, seed=41)
+    lo = prot.xyz.min(axis=0).astype(np.float64)
+    pcs = [prot, synth.make_synthetic(1500, seed=42, box=(40.0, 40.0, 40.0), origin=tuple(lo), n_rings=200, n_amides=200)]
+    return batch.concat_complexes(pcs)
+
+
+def _change_input(c, what, pc, off):
+    """Replace one input of context c by a value other than the one set_complex(pc) uploaded."""
+    import dataclasses
+    from arpeggio_amd import _capi, synth
+    from arpeggio_amd.core import config
+    p, L, h, n = _capi._p, c._L, c._h, pc.n_atoms
+    idx = np.arange(n)
+    if what == 'atoms':      # moved, and (no neighbours after this call) no xbond donor
+        xyz = (pc.xyz + np.where(idx % 3 == 0, 0.4, 0.0)[:, None]).astype(np.float32)
+        tm = (pc.type_mask & ~np.uint16(config.ATOM_TYPE_BIT['xbond donor'])).astype(np.uint16)
+        c._check(L.arp_set_atoms(h, n, p(xyz), p(pc.vdw), p(pc.cov), p(tm), p(pc.flags), p(pc.res_id)), 'arp_set_atoms')
+    elif what == 'residues':   # every third chain link broken
+        cut = np.arange(pc.n_residues) % 3 == 0
+        prev, nxt = np.where(cut, -1, pc.res_prev).astype(np.int32), np.where(cut, -1, pc.res_next).astype(np.int32)
+        c._check(L.arp_set_residues(h, pc.n_residues, p(pc.res_flags), p(prev), p(nxt)), 'arp_set_residues')
+    elif what == 'bonds':      # the first bond of every atom only
+        deg = np.minimum(np.diff(pc.bond_off), 1)
+        off = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+        bidx = np.ascontiguousarray(pc.bond_idx[pc.bond_off[:-1][deg > 0]], np.int32)
+        c._check(L.arp_set_bonds(h, p(off), p(bidx)), 'arp_set_bonds')
+    elif what == 'hydrogens':
+        hx = np.ascontiguousarray(pc.h_xyz + 0.25, np.float64)
+        c._check(L.arp_set_hydrogens(h, p(pc.h_off), p(hx)), 'arp_set_hydrogens')
+    elif what == 'single_bond_neighbours':
+        nb = np.where(pc.sb_nbr >= 0, (pc.sb_nbr + 1) % n, -1).astype(np.int32)
+        c._check(L.arp_set_single_bond_neighbours(h, p(nb)), 'arp_set_single_bond_neighbours')
+    elif what == 'single_bond_neighbour_coords':
+        has = pc.sb_nbr >= 0
+        c.set_single_bond_neighbour_coords(pc.xyz[np.maximum(pc.sb_nbr, 0)] + np.float32(0.5), has.astype(np.uint8))
+    elif what == 'rings':
+        m = dataclasses.replace(pc, ring_center=pc.ring_center[::-1].copy(), ring_normal=pc.ring_normal[::-1].copy(), ring_res=pc.ring_res[::-1].copy())
+        c._check(L.arp_set_rings(h, m.n_rings, p(m.ring_center), p(m.ring_normal), p(m.ring_res)), 'arp_set_rings')
+    elif what == 'amides':
+        ctr = (pc.amide_center + np.float32(0.75)).astype(np.float32)
+        c._check(L.arp_set_amides(h, pc.n_amides, p(ctr), p(pc.amide_normal), p(pc.amide_res)), 'arp_set_amides')
+    elif what == 'selection':
+        c.set_selection((pc.res_id % 3 == 0).astype(np.uint8))
+    elif what == 'selection_state':
+        sel = (pc.res_id % 3 == 0).astype(np.uint8)
+        c.set_selection_state(sel, sel | (pc.res_id % 3 == 1), (pc.ring_res % 2 == 0).astype(np.uint8), np.ones(pc.n_rings, np.uint8),
+                              (pc.amide_res % 2 == 0).astype(np.uint8), np.ones(pc.n_amides, np.uint8))
+    elif what == 'ownership':
+        c.set_ownership((idx % 4 != 0).astype(np.uint8), (2 * idx + 1).astype(np.int32))
+    elif what == 'group_ownership':
+        r, a = np.arange(pc.n_rings), np.arange(pc.n_amides)
+        c.set_group_ownership((r % 3 != 0).astype(np.uint8), (2 * r).astype(np.int32), (a % 3 != 0).astype(np.uint8), (2 * a).astype(np.int32))
+    elif what == 'batch':
+        c.declare_batch(off)
+    elif what == 'batch_0':
+        c._check(L.arp_set_batch(h, 0, None, None, None, None), 'arp_set_batch')
+    elif what == 'whole_structure':
+        c.set_whole_structure(True)
+    elif what == 'blob':
+        c.set_blob(_capi.pack_blob(synth.proteinlike(n_res=70, n_waters=20, seed=43)))
+    else:
+        raise AssertionError(what)
+
+
+_INPUTS = ('atoms', 'residues', 'bonds', 'hydrogens', 'single_bond_neighbours', 'rings', 'amides', 'selection', 'selection_state',
+           'ownership', 'group_ownership', 'single_bond_neighbour_coords', 'batch', 'batch_0', 'whole_structure', 'blob',
+           'atoms_after_batch')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('what', _INPUTS)
+def test_an_input_change_voids_the_last_results_and_stales_what_was_made_from_it(what):
+    """Every input setter of the C ABI: a pass after the change (context a: setup, pass, change, pass) gives the bags of a context
+    that never saw the old value (b: setup, change, pass), and between the change and the next launch every fetch refuses with
+    'no launch results'.  'batch_0' starts from a declared batch; 'atoms_after_batch' is a batch, a pass over it, then new atoms
+    alone (the centre grids of the batch layout must go)."""
+    from arpeggio_amd import _capi
+    pc, off = _input_change_structure()
+    setter = 'atoms' if what == 'atoms_after_batch' else what
+    a, b = _capi.Context(0), _capi.Context(0)
+    try:
+        for c in (a, b):
+            c.set_complex(pc)
+            if what == 'batch_0' or (what == 'atoms_after_batch' and c is a):      # (b never has the batch)
+                c.declare_batch(off)
+        first = a.run_launch(5.0, 0.1, False, 6.0)
+        assert first['atom_atom'] > 0 and first['plane_plane'] > 0
+        _change_input(a, setter, pc, off)
+        with pytest.raises(ValueError, match='no launch results'):
+            a.atom_contacts_fetch(first['atom_atom'], sort=False)
+        for bag in ('plane_plane', 'atom_plane', 'group_group', 'group_plane'):
+            with pytest.raises(ValueError, match='no launch results'):
+                a.fetch_bag(bag, sort=False)
+        _change_input(b, setter, pc, off)
+        ca, cb = a.run_launch(5.0, 0.1, False, 6.0), b.run_launch(5.0, 0.1, False, 6.0)
+        assert ca == cb, (what, ca, cb)
+        _same_bags(_five_bags(a, ca), _five_bags(b, cb), what)
+    finally:
+        a.close(); b.close()
