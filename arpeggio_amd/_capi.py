@@ -35,7 +35,7 @@ SYMBOLS = (
     'arp_write_contacts_json', 'arp_records_size', 'arp_records_layout', 'arp_records_fill', 'arp_shard_set_home', 'arp_shard_pack_face',
     'arp_shard_assemble', 'arp_shard_layout', 'arp_get_blob', 'arp_cif_open', 'arp_cif_close', 'arp_cif_rows', 'arp_cif_cols',
     'arp_cif_blocks', 'arp_cif_tag', 'arp_cif_text', 'arp_cif_column', 'arp_cif_column_f64', 'arp_cif_column_i64',
-    'arp_atom_contacts_sort', 'arp_fetch_packed',
+    'arp_atom_contacts_sort', 'arp_fetch_packed', 'arp_set_topology', 'arp_set_models', 'arp_models_planes',
 )
 
 _lib = None
@@ -173,6 +173,9 @@ def load():
     L.arp_set_packed_layout.argtypes = [vp, i32]
     L.arp_device_synchronize.argtypes = [vp]
     L.arp_set_batch.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.arp_set_topology.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+    L.arp_set_models.argtypes = [vp, i64, vp, vp]
+    L.arp_models_planes.argtypes = [vp, vp, vp, vp, vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -457,6 +460,43 @@ BAG_SORT_MAX = 8192       # ARP_BAG_SORT_MAX of include/arpeggio_hip.h
 KERNEL_SLOTS = ('bin', 'scan', 'scatter', 'unused', 'search', 'sift', 'mark_search', 'planes')
 
 
+# first-id column of every bag in its canonical order, and what its ids count (atoms / rings / amides)
+_MODEL_SPLIT = {'atom_atom': ('i', {'i': 'n', 'j': 'n'}), 'atom_plane': ('ring', {'ring': 'nring', 'atom': 'n'}),
+                'plane_plane': ('bgn', {'bgn': 'nring', 'end': 'nring'}), 'group_group': ('bgn', {'bgn': 'namide', 'end': 'namide'}),
+                'group_plane': ('amide', {'amide': 'namide', 'ring': 'nring'})}
+
+
+def split_models(bags, m):
+    """The five bags of one pass over F resident models (arp_set_models) -> one dict of five bags per model, ids local to the
+    model.  In each bag's canonical order the records of model f are ONE contiguous range — they follow those of model f - 1
+    — so the cut is a binary search on the first-id column (in the ROWS layout: row[f n]), not a sort.  ``m``: the counts
+    of one model (n, nring, namide) and F."""
+    F = m['F']
+    out = [dict() for _ in range(F)]
+    for name, (key, shifts) in _MODEL_SPLIT.items():
+        b = bags[name]
+        if name == 'atom_atom' and isinstance(b, RowsBag):
+            row = b['row']
+            bounds = row[np.arange(F + 1) * m['n']].astype(np.int64)
+            cols = {k: v for k, v in b.items() if k not in ('row', 'i')}
+            for f in range(F):
+                lo, hi = int(bounds[f]), int(bounds[f + 1])
+                d = {k: v[lo:hi] for k, v in cols.items()}
+                d['j'] = (d['j'] - f * m['n']).astype(np.int32)
+                seg = row[f * m['n']:(f + 1) * m['n'] + 1]
+                d['i'] = np.repeat(np.arange(m['n'], dtype=np.int32), np.diff(seg))
+                out[f][name] = d
+            continue
+        bounds = np.searchsorted(b[key], np.arange(F + 1, dtype=np.int64) * m[shifts[key]], side='left')
+        for f in range(F):
+            lo, hi = int(bounds[f]), int(bounds[f + 1])
+            d = {k: v[lo:hi] for k, v in b.items()}
+            for col, what in shifts.items():
+                d[col] = (d[col] - f * m[what]).astype(np.int32)
+            out[f][name] = d
+    return out
+
+
 class Context:
     """One arp_ctx: one GPU, one HIP stream, device-resident structure."""
 
@@ -470,6 +510,7 @@ class Context:
         self._h = h
         self.device = device
         self.n = self.n_rings = self.n_amides = 0
+        self._models = None          # counts of the resident models (set_models), None outside model mode
         # the five bag sizes of a pass land here (one context per host thread: no sharing); a ctypes array made once costs the
         # call nothing, a NumPy array + pointer per call cost ~2 us of a ~90 us pass
         self._counts = (C.c_int64 * 5)()
@@ -533,6 +574,7 @@ class Context:
         self._check(L.arp_set_rings(h, pc.n_rings, _p(pc.ring_center), _p(pc.ring_normal), _p(pc.ring_res)), 'arp_set_rings')
         self._check(L.arp_set_amides(h, pc.n_amides, _p(pc.amide_center), _p(pc.amide_normal), _p(pc.amide_res)), 'arp_set_amides')
         self.n, self.n_rings, self.n_amides = pc.n_atoms, pc.n_rings, pc.n_amides
+        self._models = None
 
     def set_batch(self, pcs, selections=None):
         """Several structures in one pass (arpeggio_amd.batch): uploads the concatenation of ``pcs`` and tells the library
@@ -553,6 +595,7 @@ class Context:
         a, r, m, bx = (np.ascontiguousarray(off[k]) for k in ('atom', 'ring', 'amide', 'boxes'))
         self._check(self._L.arp_set_batch(self._h, len(a) - 1, _p(a), _p(r), _p(m), _p(bx)), 'arp_set_batch')
         self._batch = off
+        self._models = None
 
     def run_batch(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, expand_radius=6.0, fetch=True):
         """run_arpeggio on every structure of the resident batch in ONE pass.  Returns a list of per-structure dicts
@@ -570,9 +613,67 @@ class Context:
                 per[s_][name] = d
         return per
 
+    # ---- one topology, several models (arp_set_topology / arp_set_models) ----
+    def set_topology(self, pc):
+        """Keep ``pc``'s topology on the device (its coordinates are model 1's; ring / amide centres are not read):
+        ``pc.ring_atoms`` in ring-path order and ``pc.amide_atoms`` (N, C, O, C-alpha) are what every model's planes are made
+        from.  The resident structure is not touched."""
+        blob = pack_blob(pc, pinned=False)
+        nr = pc.n_rings
+        if nr and len(pc.ring_atoms) != nr:
+            raise ValueError('set_topology: the pack needs the atoms of every ring (ring_atoms)')
+        off = np.zeros(nr + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in pc.ring_atoms]) if nr else []
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(a, np.int32) for a in pc.ring_atoms]) if nr else np.zeros(1, np.int32))
+        am = np.ascontiguousarray(pc.amide_atoms, np.int32).reshape(-1, 4)
+        self._check(self._L.arp_set_topology(self._h, _p(blob), int(blob.nbytes), _p(off), _p(idx), _p(am)), 'arp_set_topology')
+        self._topology = dict(n=pc.n_atoms, nres=pc.n_residues, nring=nr, namide=pc.n_amides, nh=int(pc.h_xyz.shape[0]))
+
+    def set_models(self, xyz, h_xyz):
+        """F models of the kept topology become the resident structure, one batch partition per model:
+        ``xyz`` float32 [F, n, 3], ``h_xyz`` float64 [F, nh, 3] (hydrogens in the topology's h_off order)."""
+        t = getattr(self, '_topology', None)
+        if t is None:
+            raise ValueError('set_models: no topology (set_topology first)')
+        x = np.ascontiguousarray(xyz, np.float32)
+        hx = np.ascontiguousarray(h_xyz, np.float64)
+        if x.ndim != 3 or x.shape[1:] != (t['n'], 3):
+            raise ValueError(f'set_models: xyz must be [F, {t["n"]}, 3]')
+        F = x.shape[0]
+        if hx.shape != (F, t['nh'], 3):
+            raise ValueError(f'set_models: h_xyz must be [{F}, {t["nh"]}, 3]')
+        self._models = None
+        self.n = self.n_rings = self.n_amides = 0      # (a failed call leaves nothing resident)
+        self._check(self._L.arp_set_models(self._h, F, _p(x), _p(hx)), 'arp_set_models')
+        self.n, self.n_rings, self.n_amides = F * t['n'], F * t['nring'], F * t['namide']
+        self._models = dict(t, F=F)
+
+    def models_planes(self):
+        """Per model: ring_center / ring_normal f64 [F, R, 3], ring_res i32 [F, R] (residues of the model, -1 = none),
+        amide_center / amide_normal f32 [F, A, 3] — what set_models computed on the device."""
+        m = self._models
+        if m is None:
+            raise ValueError('models_planes: no models resident (set_models)')
+        F, R, A = m['F'], m['nring'], m['namide']
+        rc, rn, rr = np.zeros((F, R, 3)), np.zeros((F, R, 3)), np.zeros((F, R), np.int32)
+        ac, an = np.zeros((F, A, 3), np.float32), np.zeros((F, A, 3), np.float32)
+        self._check(self._L.arp_models_planes(self._h, _p(rc), _p(rn), _p(rr), _p(ac), _p(an)), 'arp_models_planes')
+        return dict(ring_center=rc, ring_normal=rn, ring_res=rr, amide_center=ac, amide_normal=an)
+
+    def run_models(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, expand_radius=6.0):
+        """run_arpeggio on every resident model in ONE pass; one ``fetch_packed``, cut into the models by contiguous ranges
+        (``split_models``).  Returns a list of F dicts {atom_atom, atom_plane, plane_plane, group_group, group_plane} with
+        model-local ids."""
+        if self._models is None:
+            raise ValueError('run_models: no models resident (set_models)')
+        self.run_launch(cutoff, vdw_comp, include_sequence_adjacent, expand_radius)
+        bags, _ = self.fetch_packed()
+        return split_models(bags, self._models)
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
+        self._models = None
         self._check(self._L.arp_set_blob(self._h, _p(blob), int(blob.nbytes)), 'arp_set_blob')
         hdr = BlobHeader.from_buffer_copy(blob[:C.sizeof(BlobHeader)].tobytes())
         self.n, self.n_rings, self.n_amides = int(hdr.n), int(hdr.nring), int(hdr.namide)

@@ -546,3 +546,150 @@ def pack_from_reference_objects(ic, ob=None):
         serial=[a.serial_number for a in atoms], res_name=[r.resname for r in residues],
         res_seq=[r.id[1] for r in residues], res_icode=[r.id[2] for r in residues],
         res_chain=[r.get_parent().id for r in residues], component_types=dict(ic.component_types), id=ic.id)
+
+
+class EnsembleComplex:
+    """Every model of a multi-model structure (an NMR ensemble, the frames of a simulation) in ONE pass on the GPU, where the
+    reference keeps the first model only (P:67-69).  ``filename``: an mmCIF path (``protein_reader.read_mmcif_models``) or a
+    tuple ``(pc, xyz [F, n, 3], h_xyz [F, nh, 3])`` of a topology and its models' coordinates.  The other arguments are
+    InteractionComplex's.  The topology is kept on the device once; every model gets its own ring / amide geometry and
+    ring residues there (arp_set_models) and its own bags, bit-identical to an InteractionComplex run on that model alone.
+    ``model(k)`` hands out model k as an InteractionComplex with its results attached (get_contacts, write_json, the CSV
+    writers)."""
+
+    def __init__(self, filename, vdw_comp=0.1, interacting=5.0, ph=7.4, device=0, allow_incomplete=False):
+        self.allow_incomplete = bool(allow_incomplete)
+        if isinstance(filename, tuple):
+            pc, xyz, h_xyz = filename
+            self.id = pc.id
+            self.model_numbers = list(range(1, len(xyz) + 1))
+        elif isinstance(filename, (str, os.PathLike)) and str(filename).lower().endswith(('.cif', '.mmcif')):
+            from . import protein_reader
+            pc, xyz, h_xyz, self.model_numbers = protein_reader.read_mmcif_models(str(filename))
+            self.id = os.path.basename(str(filename)).split('.')[0]        # I:51
+        else:
+            raise NotImplementedError('EnsembleComplex reads mmCIF files (.cif) or (PackedComplex, xyz, h_xyz) tuples')
+        self.pc = pc
+        self.pc.ensure_labels()
+        self.component_types = self.pc.component_types
+        self.device = device
+        self._ctx = None
+        self.params = Parameters(vdw_comp_factor=vdw_comp, interacting_threshold=interacting,
+                                 has_hydrogens=bool(np.any(self.pc.flags & config.F_HYDROGEN)) or self.pc.h_xyz.shape[0] > 0, ph=ph)
+        self._set_arrays(xyz, h_xyz)
+        self._results = None
+
+    @property
+    def n_models(self):
+        return int(self.xyz.shape[0])
+
+    def _set_arrays(self, xyz, h_xyz):
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        h_xyz = np.ascontiguousarray(h_xyz, np.float64).reshape(len(xyz), -1, 3)
+        if xyz.ndim != 3 or xyz.shape[1:] != (self.pc.n_atoms, 3) or h_xyz.shape[1] != self.pc.h_xyz.shape[0] or len(xyz) < 1:
+            raise ValueError(f'EnsembleComplex: xyz must be [F >= 1, {self.pc.n_atoms}, 3] and h_xyz [F, {self.pc.h_xyz.shape[0]}, 3]')
+        self.xyz, self.h_xyz = xyz, h_xyz
+
+    def structure_checks(self):
+        """I:109-118 (serial numbers of the topology)."""
+        serials = self.pc.serial
+        if len(serials) > len(set(serials.tolist())):
+            raise AtomSerialError
+
+    def initialize(self):
+        """Keep the topology on the GPU and make the models resident, with each model's ring / amide geometry and ring
+        residues computed there."""
+        from .. import _capi
+        incomplete = getattr(self.pc, 'incomplete', ())
+        if 'added hydrogens' in incomplete and not self.params.has_hydrogens and self.pc.n_atoms:
+            InteractionComplex._incomplete(self, ['hydrogens (the file has none; the reference adds them with OpenBabel, I:99-105)'])
+        pc = self.pc
+        bad = pc.rings_not_in_path_order()
+        if bad:
+            raise ValueError(f'ring_atoms of ring(s) {bad[:8]} are not in ring-path order (consecutive atoms are not bonded)')
+        if pc.n_amides and (pc.amide_atoms >= 0).all():       # (as compute_plane_geometry: the residue of every amide, I:1554-1559)
+            pc.amide_res = amide_majority_residue(pc.res_id, pc.amide_atoms)
+        if self._ctx is None:
+            self._ctx = _capi.Context(self.device)
+            self._ctx.set_sort_after_pass(True)
+        self._ctx.set_topology(pc)
+        self._ctx.set_models(self.xyz, self.h_xyz)
+        self.planes = self._ctx.models_planes()
+        self._results = None
+
+    def _incomplete(self, needs):
+        InteractionComplex._incomplete(self, needs)
+
+    def set_coordinates(self, xyz, h_xyz):
+        """Replace the models (any number of them: the next chunk of a trajectory; numbered 1 ... F); only their coordinates
+        go to the GPU."""
+        self._set_arrays(xyz, h_xyz)
+        self.model_numbers = list(range(1, self.n_models + 1))
+        if self._ctx is None:
+            self.initialize()
+        else:
+            self._ctx.set_models(self.xyz, self.h_xyz)
+            self.planes = self._ctx.models_planes()
+        self._results = None
+
+    def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
+        """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx, F, n = self.pc, self._ctx, self.n_models, self.pc.n_atoms
+        if isinstance(user_selections, np.ndarray):
+            idx = np.unique(user_selections.astype(np.int64))
+        elif user_selections:
+            idx = utils.selection_parser(user_selections, pc)
+        else:
+            idx = np.arange(n, dtype=np.int64)
+        if idx.size == 0:                                                   # I:1399-1401
+            logging.error('Selection was empty.')
+            raise AttributeError('Selection must not be empty.')
+        mask = np.zeros(n, np.uint8)
+        mask[idx] = 1
+        ctx.set_selection(np.tile(mask, F))
+        per_model = ctx.run_models(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        masks = ctx.make_selection_masks()
+        R, A = pc.n_rings, pc.n_amides
+        self._results = []
+        for f in range(F):
+            plus = np.nonzero(masks['plus'][f * n:(f + 1) * n])[0]
+            self._results.append(dict(
+                bags=per_model[f], selection=idx, selection_plus=plus, selection_plus_residues=np.unique(pc.res_id[plus]),
+                selection_ring_ids=set(np.nonzero(masks['ring_sel'][f * R:(f + 1) * R])[0].tolist()),
+                selection_plus_ring_ids=set(np.nonzero(masks['ring_plus'][f * R:(f + 1) * R])[0].tolist()),
+                selection_amide_ids=set(np.nonzero(masks['amide_sel'][f * A:(f + 1) * A])[0].tolist()),
+                selection_plus_amide_ids=set(np.nonzero(masks['amide_plus'][f * A:(f + 1) * A])[0].tolist())))
+        for f in range(F):
+            self.model(f)._check_incomplete_after_run()
+        self.stats = ctx.stats()
+
+    def model_pack(self, k):
+        """Model k (0-based) as a PackedComplex: the topology with model k's coordinates and plane geometry."""
+        import copy
+        if self._ctx is None:
+            self.initialize()
+        q = copy.copy(self.pc)
+        q.xyz, q.h_xyz = self.xyz[k], self.h_xyz[k]
+        p = self.planes
+        q.ring_center, q.ring_normal, q.ring_res = p['ring_center'][k], p['ring_normal'][k], p['ring_res'][k]
+        q.amide_center, q.amide_normal = p['amide_center'][k], p['amide_normal'][k]
+        if len(q.amide_atoms) and (q.amide_atoms >= 0).all():
+            q.amide_res = amide_majority_residue(q.res_id, q.amide_atoms)
+        q.plane_geometry_pending = False
+        return q
+
+    def model(self, k):
+        """Model k (0-based) as an InteractionComplex with the results of the last run_arpeggio attached: get_contacts,
+        write_json and the CSV writers work on it unchanged (it holds no GPU context of its own)."""
+        ic = InteractionComplex(self.model_pack(k), self.params.vdw_comp_factor, self.params.interacting_threshold, self.params.ph,
+                                self.device, self.allow_incomplete)
+        ic.id = self.id if self.n_models == 1 else f'{self.id}_model{self.model_numbers[k]}'
+        if self._results is not None:
+            r = self._results[k]
+            ic._bags = r['bags']
+            for key in ('selection', 'selection_plus', 'selection_plus_residues', 'selection_ring_ids', 'selection_plus_ring_ids',
+                        'selection_amide_ids', 'selection_plus_amide_ids'):
+                setattr(ic, key, r[key])
+        return ic

@@ -275,15 +275,26 @@ def polypeptide_bookkeeping(polypeptides):
 # ---------------------------------------------------------------------------------------------------------------------
 # what gemmi does to the table before the reference reads it (recalled: gemmi is not in the image)
 # ---------------------------------------------------------------------------------------------------------------------
-def gemmi_normalised(atom_sites):
-    """The reference reads ``gemmi.read_structure(path, merge_chain_parts=True)`` -> first model -> ``make_mmcif_block``
-    (P:61-68, 272-277), not the file's own table.  Restated here on the columns: (1) rows of the first model only; (2) the
-    parts of a chain (polymer, ligands, waters: same auth_asym_id, apart in the file) follow each other — chains in the
-    order of their first row, rows of a chain in file order; (3) coordinates re-written with three decimals
-    (``%.3f``, then parsed again)."""
-    n = len(atom_sites['id'])
+def model_rows(atom_sites, model=None):
+    """Rows of ``_atom_site`` that belong to ``model`` (a ``pdbx_PDB_model_num`` value as it stands in the file; None:
+    the model of the first row, the one the reference keeps, P:67-69)."""
     models = atom_sites['pdbx_PDB_model_num']
-    keep = [i for i in range(n) if models[i] == models[0]]
+    want = models[0] if model is None else str(model)
+    return [i for i in range(len(atom_sites['id'])) if models[i] == want]
+
+
+def model_numbers(atom_sites):
+    """The ``pdbx_PDB_model_num`` values of a table, in the order of their first row."""
+    return list(dict.fromkeys(atom_sites['pdbx_PDB_model_num']))
+
+
+def gemmi_normalised(atom_sites, model=None):
+    """The reference reads ``gemmi.read_structure(path, merge_chain_parts=True)`` -> first model -> ``make_mmcif_block``
+    (P:61-68, 272-277), not the file's own table.  Restated here on the columns: (1) rows of the first model only
+    (``model``: of that model instead, see ``model_rows``); (2) the parts of a chain (polymer, ligands, waters: same
+    auth_asym_id, apart in the file) follow each other — chains in the order of their first row, rows of a chain in file
+    order; (3) coordinates re-written with three decimals (``%.3f``, then parsed again)."""
+    keep = model_rows(atom_sites, model)
     first = {}
     for i in keep:
         first.setdefault(atom_sites['auth_asym_id'][i], len(first))
@@ -491,18 +502,24 @@ def template_amides(residues, res_next, atom_index):
     return np.array(out, np.int32).reshape(-1, 4)
 
 
-def read_mmcif(path, use_ambiguities=False, normalise=True):
+def read_mmcif(path, use_ambiguities=False, normalise=True, model=None):
     """``initialize()``'s result for an mmCIF file as far as the file alone goes (see the module docstring and
     ``pc.incomplete``): atoms, residues, polypeptide links, table types and radii; bonds from ``_struct_conn``, the peptide
     bonds of the polypeptides and the X-H bonds of explicit hydrogens; the hydrogens' coordinates on their heavy atoms.
-    ``normalise``: apply what gemmi does to the table first (``gemmi_normalised``)."""
-    text = _read_text(path)
+    ``normalise``: apply what gemmi does to the table first (``gemmi_normalised``).  ``model``: read that model
+    (``pdbx_PDB_model_num`` value) instead of the first one, which is the reference's (P:67-69)."""
+    return _read_mmcif_text(_read_text(path), path, use_ambiguities, normalise, model)
+
+
+def _read_mmcif_text(text, path, use_ambiguities=False, normalise=True, model=None):
     cat = _category(text, '_atom_site.')
     if cat.rows == 0:
         raise ValueError('The cif file does not contain _atom_site record')           # P:285-287
     cols = cat.columns()
     if normalise:
-        cols = gemmi_normalised(cols)
+        cols = gemmi_normalised(cols, model)
+    elif model is not None:
+        cols = {k: [v[i] for i in model_rows(cols, model)] for k, v in cols.items()}
     chains = build_structure(structure_events(cols))
     links = polypeptide_bookkeeping(build_peptides(chains))
     residues = [r for _, rs in chains for r in rs]
@@ -630,3 +647,40 @@ def read_mmcif(path, use_ambiguities=False, normalise=True):
         logging.warning('read_mmcif(%s): %d explicit hydrogens have no heavy atom of their residue within 1.3 A and take no part in the '
                         'hydrogen-bond geometry (OpenBabel would attach them by its own bond perception)', os.path.basename(path), orphans)
     return pc
+
+
+# what must be the same in every model of a file for its models to share one topology (read_mmcif_models), in the order they
+# are compared
+_TOPOLOGY = ('atom_name', 'element', 'res_name', 'res_chain', 'res_seq', 'res_icode', 'res_het', 'res_id', 'bond_off', 'bond_idx',
+             'h_off', 'hydrogen_parent', 'res_flags', 'res_prev', 'res_next', 'sb_nbr', 'type_mask', 'ring_atoms', 'amide_atoms')
+
+
+def read_mmcif_models(path, use_ambiguities=False, normalise=True):
+    """Every model of an mmCIF file (an NMR ensemble, the frames of a simulation) for ``EnsembleComplex`` /
+    ``Context.set_models``, where the reference keeps the first one only (P:67-69).  Each model is read by ``read_mmcif``'s
+    own code (``model=``).  Returns ``(pc, xyz, h_xyz, model_numbers)``: ``pc`` = model 1 exactly as ``read_mmcif(path)``
+    gives it, ``xyz`` float32 [F, n, 3] and ``h_xyz`` float64 [F, nh, 3] = every model's atoms and hydrogens in ``pc``'s
+    order, ``model_numbers`` = the file's ``pdbx_PDB_model_num`` values in file order.  Every model must have model 1's
+    topology (atoms, residues, bonds, hydrogens, links, types, rings and amide groups); ``ValueError`` names the first model
+    and the first array that differ."""
+    text = _read_text(path)
+    cat = _category(text, '_atom_site.')
+    if cat.rows == 0:
+        raise ValueError('The cif file does not contain _atom_site record')           # P:285-287
+    numbers = model_numbers({'pdbx_PDB_model_num': cat.column('pdbx_PDB_model_num')})
+    cat.close()
+    pcs = [_read_mmcif_text(text, path, use_ambiguities, normalise, None if k == 0 else m) for k, m in enumerate(numbers)]
+    pc = pcs[0]
+    for m, q in zip(numbers[1:], pcs[1:]):
+        for name in _TOPOLOGY:
+            a, b = getattr(pc, name), getattr(q, name)
+            if name == 'ring_atoms':
+                same = len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+            else:
+                same = (len(a) == len(b)) and (np.array_equal(np.asarray(a), np.asarray(b)) if len(a) else True)
+            if not same:
+                raise ValueError(f'read_mmcif_models({os.path.basename(str(path))}): model {m} does not have the topology of model '
+                                 f'{numbers[0]}: {name} differs')
+    xyz = np.stack([q.xyz for q in pcs]).astype(np.float32)
+    h_xyz = np.stack([q.h_xyz.reshape(-1, 3) for q in pcs]).astype(np.float64)
+    return pc, xyz, h_xyz, numbers

@@ -21,6 +21,7 @@
 #include "arp_pairs.h"
 #include "arp_planes.h"
 #include "arp_prepare.h"
+#include "arp_models.h"
 #include "arp_json.h"
 #include "arp_shard.h"
 #include "arp_cif.h"
@@ -431,6 +432,15 @@ struct arp_ctx {
     DevBuf<int> sid_atom, sid_ring, sid_amide;
     DevBuf<long long> batch_off_dev;   // the three offset tables of arp_set_batch, one after the other
     struct BatchGrid { double radius = 0; bool valid = false; DevBuf<BatchPlace> place; GridDesc d{}; } batch_grid[4];
+    // ---- one topology, several models (arp_set_topology / arp_set_models): the kept topology blob and its ring / amide atoms,
+    // and the number of models the resident structure holds (0: no model mode; see inputs_changed)
+    DevBuf<uint8_t> topo_dev;
+    arp_blob_header topo_hdr{};
+    bool has_topo = false;
+    DevBuf<int> topo_ring_off, topo_ring_idx, topo_amide_atoms;
+    DevBuf<float> models_xyz;
+    DevBuf<double> models_box;
+    int64_t models_n = 0;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -622,20 +632,21 @@ enum : unsigned {
 
 // The one place that marks derived state stale because an input changed; whoever builds an artefact sets it valid again.
 //
-//   input                  static  lists  contact  all-atom  centre  batch  selection  default    results
-//                          columns        grid     grid      grids                     selection
-//   atoms                  x       x      x        x         (b)     x      x          x          x
-//   residues               x       x      x        x                        x                     x
-//   bonds, hydrogens       x       x                                                              x
-//   single-bond nbrs       x       x                                                              x
-//   rings / amides         x       x                         own(b)  x      x                     x
-//   ownership              x       x      x        x         (b)     x                            x
-//   group ownership        x       x                         (b)     x                            x
+//   input                  static  lists  contact  all-atom  centre  batch  selection  default    results  model
+//                          columns        grid     grid      grids                     selection           mode
+//   atoms                  x       x      x        x         (b)     x      x          x          x        x
+//   residues               x       x      x        x                        x                     x        x
+//   bonds, hydrogens       x       x                                                              x        x
+//   single-bond nbrs       x       x                                                              x        x
+//   rings / amides         x       x                         own(b)  x      x                     x        x
+//   ownership              x       x      x        x         (b)     x                            x        x
+//   group ownership        x       x                         (b)     x                            x        x
 //   selection                                      x                        x                     x
 //   selection state        x (s)   x      x        x                        x                     x
-//   batch                  x       x      x        x         x       x                            x
+//   batch                  x       x      x        x         x       x                            x        x
 //   whole structure                                                                               x
 //   batch grid tables      x (k)   x      x        x         x                                    (no input)
+//   models                 as a blob upload (everything), then as a batch; model mode begins after both      (m)
 //
 // static columns: k_prepare_static's records and their spatial order; the contact count of the last pass that sizes the sift
 //   launch goes with them.  The lists are made beside them (from the centre grids and the atoms as uploaded), so whatever
@@ -651,6 +662,11 @@ enum : unsigned {
 // selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.
+// model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
+//   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
+//   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
+//   nothing made so far reads: the all-atom grid it builds for them holds atoms and residue ids only.  The kept topology is
+//   no derived state: only arp_set_topology replaces it.
 void inputs_changed(arp_ctx* c, unsigned what) {
     const unsigned columns = IN_EVERYTHING & ~(IN_SELECTION | IN_WHOLE_STRUCTURE);
     const unsigned partition = IN_ATOMS | IN_RINGS | IN_AMIDES | IN_OWNERSHIP | IN_GROUP_OWNERSHIP | IN_BATCH;
@@ -674,6 +690,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->sel_uploaded = c->sel_prefilled = c->sel_all = c->whole_structure = false;
         c->nsel = -1;
     }
+    if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->models_n = 0;
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
@@ -2540,11 +2557,24 @@ void borrow_blob_views(arp_ctx* c, const arp_blob_header& h) {
     c->h_xyz.clear();
 }
 
+// No structure is resident any more (a failed upload: the arrays it overwrote are void).
+void drop_resident(arp_ctx* c) {
+    c->uplists_pending = false;
+    inputs_changed(c, IN_EVERYTHING);
+    c->n = c->nres = c->nring = c->namide = 0;
+    c->blob_bytes = 0;
+    c->sp_radius = 0;
+    c->sel_prefilled = false; c->sp_cnt_zeroed = 0;
+    c->ctr_zero_ok = false;
+}
+
 // Device-side validation of the resident blob (what arp_set_atoms ... check on the host) + the bookkeeping of a new
 // structure.  Waits for the stream.  `also` = further device error words OR-ed in (shard assembly), may be null.
-int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who, const int* also = nullptr, bool gather_sb = false, bool rad_from_table = false) {
+// batch_next: the caller declares a batch partition next (arp_set_models), so nothing is made ahead for ONE structure.
+int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who, const int* also = nullptr, bool gather_sb = false, bool rad_from_table = false,
+                           bool batch_next = false) {
     int* const d_err = (int*)(c->d_ctr + ctr_dev(C_ERR));
-    const bool after_batch = c->batch_n > 0;      // (before the bookkeeping below resets it)
+    const bool after_batch = c->batch_n > 0 || batch_next;      // (before the bookkeeping below resets it)
     // The verdict reaches the host the way the counters of a pass do: the last block of the kernel stores the counter block in
     // the pinned mirror and the host polls the completion word (pass_end) — no copy launch behind the kernel, no
     // hipStreamSynchronize (~15 us per structure).  That needs the whole block zero at the start (its tickets live there) and
@@ -2622,13 +2652,7 @@ int validate_resident_blob(arp_ctx* c, const arp_blob_header& h, const char* who
         if (c->stream2) (void)hipStreamSynchronize(c->stream2);
         if (polled) (void)collect_counters(c); else (void)hipStreamSynchronize(c->stream);
         c->err = why;
-        c->uplists_pending = false;
-        inputs_changed(c, IN_EVERYTHING);
-        c->n = c->nres = c->nring = c->namide = 0;
-        c->blob_bytes = 0;
-        c->sp_radius = 0;
-        c->sel_prefilled = false; c->sp_cnt_zeroed = 0;
-        c->ctr_zero_ok = false;
+        drop_resident(c);
         return rc;
     };
     if (with_upload) {
@@ -4020,6 +4044,186 @@ int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const in
         CHK(check_launch(c, "k_fill_sid"));
     }
     c->batch_n = nstruct;
+    return ARP_OK;
+}
+
+// ---- one topology, several models (arp_models.h) ----------------------------------------------------------------------
+int arp_set_topology(arp_ctx* c, const void* blob, uint64_t bytes, const int32_t* ring_off, const int32_t* ring_idx,
+                     const int32_t* amide_atoms) {
+    if (!c || !blob || bytes < sizeof(arp_blob_header)) return ARP_E_ARG;
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_set_topology: not for a shard of a distributed structure");
+    arp_blob_header h;
+    memcpy(&h, blob, sizeof(h));
+    CHK(check_blob_header(c, h, bytes));
+    const int64_t R = h.nring, A = h.namide;
+    if ((R > 0 && (!ring_off || !ring_idx)) || (A > 0 && !amide_atoms)) FAIL(c, ARP_E_ARG, "arp_set_topology: ring or amide atoms missing");
+    if (R > 0) {
+        if (!csr_ok(ring_off, R)) FAIL(c, ARP_E_ARG, "arp_set_topology: ring offsets must start at 0 and never decrease");
+        for (int64_t r = 0; r < R; ++r)
+            if (ring_off[r + 1] - ring_off[r] < 3) FAIL(c, ARP_E_ARG, "arp_set_topology: a ring needs at least three atoms");
+        for (int64_t k = 0; k < ring_off[R]; ++k)
+            if (ring_idx[k] < 0 || ring_idx[k] >= h.n) FAIL(c, ARP_E_ARG, "arp_set_topology: ring atom index out of range");
+    }
+    for (int64_t k = 0; k < 4 * A; ++k)
+        if ((k & 3) != 3 && (amide_atoms[k] < 0 || amide_atoms[k] >= h.n))   // N, C, O are read; the fourth atom is not
+            FAIL(c, ARP_E_ARG, "arp_set_topology: amide atom index out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    c->has_topo = false;
+    const int32_t zero = 0;
+    CHK(upload(c, c->topo_dev, (const uint8_t*)blob, (size_t)h.bytes));
+    CHK(upload(c, c->topo_ring_off, R > 0 ? ring_off : &zero, (size_t)R + 1));
+    CHK(upload(c, c->topo_ring_idx, ring_idx, R > 0 ? (size_t)ring_off[R] : 0));
+    CHK(upload(c, c->topo_amide_atoms, amide_atoms, (size_t)(4 * A)));
+    c->topo_hdr = h;
+    c->has_topo = true;
+    return ARP_OK;
+}
+
+int arp_set_models(arp_ctx* c, int64_t nmodel, const float* xyz, const double* h_xyz) {
+    if (!c) return ARP_E_ARG;
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_set_models: not for a shard of a distributed structure");
+    if (!c->has_topo) FAIL(c, ARP_E_ARG, "arp_set_models: no topology (arp_set_topology first)");
+    const arp_blob_header& t = c->topo_hdr;
+    if (nmodel < 1) FAIL(c, ARP_E_ARG, "arp_set_models: at least one model");
+    const int64_t lim = (int64_t)1 << 31;
+    auto reaches = [&](int64_t per) { return per > 0 && nmodel >= (lim + per - 1) / per; };     // nmodel * per >= 2^31
+    if (nmodel >= lim || reaches(t.n) || reaches(t.nbond) || reaches(3 * t.nh))
+        FAIL(c, ARP_E_ARG, "arp_set_models: F n, F nbond and 3 F nh must stay below 2^31");
+    if ((t.n > 0 && !xyz) || (t.nh > 0 && !h_xyz)) FAIL(c, ARP_E_ARG, "arp_set_models: coordinates missing");
+    const int64_t F = nmodel;
+    BlobSizes z;
+    if (!blob_sizes(F * t.n, F * t.nres, F * t.nbond, F * t.nh, F * t.nring, F * t.namide, z))
+        FAIL(c, ARP_E_ARG, "arp_set_models: counts out of range");
+    arp_blob_header h;
+    memset(&h, 0, sizeof(h));
+    h.magic = ARP_BLOB_MAGIC;
+    h.n = F * t.n; h.nres = F * t.nres; h.nbond = F * t.nbond; h.nh = F * t.nh; h.nring = F * t.nring; h.namide = F * t.namide;
+    h.n_rad = t.n_rad;
+    h.bytes = arp_blob_size(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide);
+    {
+        uint64_t off = align16(sizeof(arp_blob_header));
+        for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) {
+            h.off[k] = off;
+            off = align16(off + z.esize[k] * z.count[k]);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    // From here on the resident arrays are overwritten: a failure leaves no structure resident (the topology stays kept).
+    drop_resident(c);
+    auto fail = [&](int rc) -> int {
+        const std::string why = c->err;
+        (void)hipStreamSynchronize(c->stream);
+        c->err = why;
+        drop_resident(c);
+        return rc;
+    };
+    if (c->blob_dev.reserve((size_t)h.bytes) != hipSuccess || c->models_box.reserve((size_t)(18 * F)) != hipSuccess ||
+        c->models_xyz.reserve((size_t)std::max<int64_t>(3 * h.n, 1)) != hipSuccess) {
+        c->err = "arp_set_models: out of device memory";
+        return fail(ARP_E_NOMEM);
+    }
+    uint8_t* const d = c->blob_dev.p;
+    const uint8_t* const tp = c->topo_dev.p;
+    hipError_t e = hipSuccess;
+    if (h.n > 0) e = hipMemcpyAsync(c->models_xyz.p, xyz, (size_t)(3 * h.n) * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && h.nh > 0) e = hipMemcpyAsync(d + h.off[11], h_xyz, (size_t)(3 * h.nh) * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) { c->err = std::string("arp_set_models: copy of the coordinates: ") + hipGetErrorString(e); return fail(ARP_E_HIP); }
+    ModelsExpand E;
+    E.F = (int)F; E.n = (int)t.n; E.nres = (int)t.nres; E.nbond = (int)t.nbond; E.nh = (int)t.nh; E.nring = (int)t.nring; E.namide = (int)t.namide;
+    E.xyz_in = c->models_xyz.p;
+    E.t_rad = (const double2*)(tp + t.off[1]); E.t_tmask = (const uint16_t*)(tp + t.off[2]); E.t_flags = (const uint16_t*)(tp + t.off[3]);
+    E.t_res_id = (const int*)(tp + t.off[4]); E.t_res_flags = tp + t.off[5]; E.t_res_prev = (const int*)(tp + t.off[6]);
+    E.t_res_next = (const int*)(tp + t.off[7]); E.t_bond_off = (const int*)(tp + t.off[8]); E.t_bond_idx = (const int*)(tp + t.off[9]);
+    E.t_h_off = (const int*)(tp + t.off[10]); E.t_sb_nbr = (const int*)(tp + t.off[12]); E.t_am_res = (const int*)(tp + t.off[18]);
+    E.t_rad_idx = (const uint16_t*)(tp + t.off[19]); E.t_rad_tab = (const double2*)(tp + t.off[20]);
+    E.xyz4 = (float4*)(d + h.off[0]); E.rad = (double2*)(d + h.off[1]); E.tmask = (uint16_t*)(d + h.off[2]); E.flags = (uint16_t*)(d + h.off[3]);
+    E.res_id = (int*)(d + h.off[4]); E.res_flags = d + h.off[5]; E.res_prev = (int*)(d + h.off[6]); E.res_next = (int*)(d + h.off[7]);
+    E.bond_off = (int*)(d + h.off[8]); E.bond_idx = (int*)(d + h.off[9]); E.h_off = (int*)(d + h.off[10]); E.sb_nbr = (int*)(d + h.off[12]);
+    E.ring_res = (int*)(d + h.off[15]); E.am_res = (int*)(d + h.off[18]); E.rad_idx = (uint16_t*)(d + h.off[19]); E.rad_tab = (double2*)(d + h.off[20]);
+    const int64_t work = std::max({h.n + 1, h.nres, h.nbond, h.nring, h.namide, (int64_t)RAD_TABLE});
+    hipLaunchKernelGGL(k_models_expand, dim3(nblocks(work, 256), MODELS_EXPAND_SEGMENTS), dim3(256), 0, c->stream, E);
+    const float4* const xyz4 = E.xyz4;
+    double* const ring_c = (double*)(d + h.off[13]);
+    float* const am_c = (float*)(d + h.off[16]);
+    if (h.nring > 0)
+        hipLaunchKernelGGL(k_models_ring_geometry, dim3(nblocks(h.nring, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.nring,
+                           c->topo_ring_off.p, c->topo_ring_idx.p, xyz4, ring_c, (double*)(d + h.off[14]));
+    if (h.namide > 0)
+        hipLaunchKernelGGL(k_models_amide_geometry, dim3(nblocks(h.namide, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.namide,
+                           c->topo_amide_atoms.p, xyz4, am_c, (float*)(d + h.off[17]));
+    hipLaunchKernelGGL(k_models_boxes, dim3((unsigned)F), dim3(256), 0, c->stream, (int)t.n, (int)t.nring, (int)t.namide, xyz4, ring_c, am_c,
+                       c->models_box.p);
+    int rc = check_launch(c, "k_models_expand / geometry / boxes");
+    if (rc != ARP_OK) return fail(rc);
+    std::vector<double> box((size_t)(18 * F));
+    e = hipMemcpyAsync(box.data(), c->models_box.p, box.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("arp_set_models: boxes: ") + hipGetErrorString(e); return fail(ARP_E_HIP); }
+    // header boxes: the union over the models of atoms / ring centres / amide centres (0 for an empty set, as arp_blob_fill);
+    // partition boxes: everything a model holds (as batch.concat_complexes)
+    const int64_t cnt[3] = {t.n, t.nring, t.namide};
+    double* const hlo[3] = {h.lo, h.ring_lo, h.amide_lo};
+    double* const hhi[3] = {h.hi, h.ring_hi, h.amide_hi};
+    std::vector<double> pbox((size_t)(6 * F), 0.0);
+    bool finite = true;
+    for (int64_t f = 0; f < F; ++f) {
+        bool any = false;
+        for (int q = 0; q < 3; ++q) {
+            if (cnt[q] == 0) continue;
+            for (int k = 0; k < 3; ++k) {
+                const double lo = box[(size_t)(18 * f + 6 * q + k)], hi = box[(size_t)(18 * f + 6 * q + 3 + k)];
+                finite = finite && std::isfinite(lo) && std::isfinite(hi);
+                hlo[q][k] = f == 0 ? lo : std::min(hlo[q][k], lo);
+                hhi[q][k] = f == 0 ? hi : std::max(hhi[q][k], hi);
+                double& plo = pbox[(size_t)(6 * f + k)];
+                double& phi = pbox[(size_t)(6 * f + 3 + k)];
+                plo = any ? std::min(plo, lo) : lo;
+                phi = any ? std::max(phi, hi) : hi;
+            }
+            any = true;
+        }
+    }
+    if (!finite)   // a model with a non-finite coordinate: the validation below reports it (no atom lies in an empty box)
+        for (int q = 0; q < 3; ++q)
+            for (int k = 0; k < 3; ++k) hlo[q][k] = hhi[q][k] = 0.0;
+    borrow_blob_views(c, h);
+    rc = validate_resident_blob(c, h, "arp_set_models", nullptr, /*gather_sb=*/true, /*rad_from_table=*/false, /*batch_next=*/true);
+    if (rc != ARP_OK) return rc;      // (abandoned: nothing resident)
+    std::vector<int64_t> ao((size_t)F + 1), ro((size_t)F + 1), mo((size_t)F + 1);
+    for (int64_t f = 0; f <= F; ++f) { ao[(size_t)f] = f * t.n; ro[(size_t)f] = f * t.nring; mo[(size_t)f] = f * t.namide; }
+    rc = arp_set_batch(c, F, ao.data(), ro.data(), mo.data(), pbox.data());
+    if (rc != ARP_OK) return fail(rc);
+    if (h.nring > 0 && h.n > 0) {     // I:1453-1492 per model, on the all-atom grid of the partition (no atoms: every ring keeps -1)
+        rc = build_all_grid(c, 6.0);
+        if (rc == ARP_OK) {
+            hipLaunchKernelGGL(k_models_ring_residue, dim3(nblocks(h.nring * 64, 256, 4096)), dim3(256), 0, c->stream, c->all_grid.d,
+                               c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)h.nring, c->ring_c.p, c->ring_res.p);
+            rc = check_launch(c, "k_models_ring_residue");
+        }
+        if (rc != ARP_OK) return fail(rc);
+    }
+    c->models_n = F;
+    return ARP_OK;
+}
+
+int arp_models_planes(arp_ctx* c, double* ring_center, double* ring_normal, int32_t* ring_res, float* amide_center, float* amide_normal) {
+    if (!c) return ARP_E_ARG;
+    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, "arp_models_planes: no models resident (arp_set_models)");
+    const int64_t F = c->models_n, R = c->nring, A = c->namide;
+    if ((R > 0 && (!ring_center || !ring_normal || !ring_res)) || (A > 0 && (!amide_center || !amide_normal)))
+        FAIL(c, ARP_E_ARG, "arp_models_planes: output missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(download_async(c, ring_center, c->ring_c.p, (size_t)(3 * R)));
+    CHK(download_async(c, ring_normal, c->ring_n.p, (size_t)(3 * R)));
+    CHK(download_async(c, ring_res, c->ring_res.p, (size_t)R));
+    CHK(download_async(c, amide_center, c->am_c.p, (size_t)(3 * A)));
+    CHK(download_async(c, amide_normal, c->am_n.p, (size_t)(3 * A)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t per = R / F, nres = c->nres / F;     // residues of the resident partition -> of the model
+    for (int64_t k = 0; k < R; ++k)
+        if (ring_res[k] >= 0) ring_res[k] -= (int32_t)((k / per) * nres);
     return ARP_OK;
 }
 

@@ -663,3 +663,43 @@ def proteinlike(n_res: int = 480, seed: int = 2, n_waters: int = 300, id: str = 
         atom_name=[a['name'] for a in atoms], element=el, serial=np.arange(1, n + 1, dtype=np.int32),
         res_name=[r['name'] for r in residues], res_seq=[r['seq'] for r in residues], res_icode=[' '] * nres,
         res_chain=[r['chain'] for r in residues], component_types=comp, id=id)
+
+
+def models_of(pc: PackedComplex, n_models: int, seed: int = 0, jitter: float = 0.0):
+    """Coordinates of ``n_models`` models of ``pc``'s topology (an NMR ensemble / trajectory stand-in for arp_set_models):
+    ``(xyz float32 [F, n, 3], h_xyz float64 [F, nh, 3])``.  Model 0 is ``pc`` itself; every other model is ``pc`` turned
+    and shifted as a whole (a random rotation about the centroid, a shift of up to 5 A), and then every residue outside
+    the polypeptides — waters, ligands — is shifted once more as a rigid group (normal, sigma 1 A per axis).  Rigid moves
+    keep every bond length and every peptide link, so a file of such models reads back with model 1's topology.
+    ``jitter`` > 0 adds independent normal noise of that sigma to every atom and hydrogen: valid for arrays handed to
+    arp_set_models directly, not for files (the reader re-derives links and hydrogen parents from distances, and noise of
+    even 0.02 A moves some of them across its thresholds)."""
+    F, n, nh = int(n_models), pc.n_atoms, int(pc.h_xyz.shape[0])
+    xyz = np.empty((F, n, 3), np.float32)
+    h_xyz = np.empty((F, nh, 3), np.float64)
+    xyz[0], h_xyz[0] = pc.xyz, pc.h_xyz
+    x64 = pc.xyz.astype(np.float64)
+    centre = x64.mean(axis=0) if n else np.zeros(3)
+    h_owner = np.repeat(np.arange(n), np.diff(pc.h_off)) if nh else np.zeros(0, np.int64)
+    loose = (pc.res_flags & config.R_POLYPEPTIDE) == 0                  # residues moved on their own
+    if F > 1:
+        rot = _rotation_matrices(seed, 40, np.arange(1, F, dtype=np.uint64))
+        for f in range(1, F):
+            k = np.arange(3 * f, 3 * f + 3, dtype=np.uint64)
+            shift = 5.0 * (2.0 * u01(seed, 43, k) - 1.0)
+            # Box-Muller from two uniforms: one normal triple per residue
+            r_idx = np.arange(pc.n_residues, dtype=np.uint64) + np.uint64(f * (pc.n_residues + 1))
+            u1 = np.maximum(u01(seed, 44, 3 * r_idx[:, None] + np.arange(3, dtype=np.uint64)[None, :]), 1e-12)
+            u2 = u01(seed, 45, 3 * r_idx[:, None] + np.arange(3, dtype=np.uint64)[None, :])
+            grp = np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2) * loose[:, None]
+            R = rot[f - 1]
+            a = (x64 - centre) @ R.T + centre + shift + grp[pc.res_id]
+            h = (pc.h_xyz - centre) @ R.T + centre + shift + (grp[pc.res_id[h_owner]] if nh else 0.0)
+            if jitter > 0:
+                idx = np.arange(3 * (n + nh), dtype=np.uint64) + np.uint64(f * 3 * (n + nh + 1))
+                g1, g2 = np.maximum(u01(seed, 46, idx), 1e-12), u01(seed, 47, idx)
+                noise = jitter * np.sqrt(-2.0 * np.log(g1)) * np.cos(2.0 * np.pi * g2)
+                a = a + noise[:3 * n].reshape(n, 3)
+                h = h + noise[3 * n:].reshape(nh, 3)
+            xyz[f], h_xyz[f] = a.astype(np.float32), h
+    return xyz, h_xyz

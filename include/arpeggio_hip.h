@@ -507,6 +507,38 @@ int arp_shard_reduce_residue_sets(arp_ctx* ctx);
  * first id.  nstruct = 0 returns to one structure.  Not available on a shard (arp_set_ownership). */
 int arp_set_batch(arp_ctx* ctx, int64_t nstruct, const int64_t* atom_off, const int64_t* ring_off, const int64_t* amide_off,
                   const double* boxes);
+/* Every model of a multi-model structure (an NMR ensemble, the frames of a simulation) in ONE pass.  The reference keeps
+ * the first model only (P:67-69: del st[1:]); here the topology is kept on the device once and any number of coordinate
+ * sets for it become resident as a batch (arp_set_batch) with one structure per model.
+ *
+ * arp_set_topology: the topology as a blob (arp_blob_layout / arp_blob_fill; its coordinates are model 1's, its ring
+ * and amide centres, normals and ring residues are not read) plus what initialize() perceives on it: ring_off[nring + 1]
+ * / ring_idx = the atoms of every ring in ring-path order (at least 3 each), amide_atoms[4 * namide] = N, C, O,
+ * C-alpha of every amide group.  The resident structure is not touched.
+ *
+ * arp_set_models: F = nmodel >= 1 models of the kept topology: xyz = float[F][n][3], h_xyz = double[F][nh][3] (the
+ * hydrogens in the topology's h_off order).  Only these cross PCIe (12 bytes per atom and 24 per hydrogen of each
+ * model).  On the device the F copies of the topology are expanded (atom f n + i is atom i of model f; residues, bonds,
+ * hydrogens, rings and amides likewise), and each model gets the geometric part of initialize() with the arithmetic of
+ * arp_ring_geometry / arp_amide_geometry / arp_ring_residues: ring centres and normals (I:1697-1733), amide centres and
+ * normals (I:1531-1589) and the ring residues on the all-atom grid of its own model (I:1453-1492).  The expanded
+ * structure is validated as an arp_set_blob upload is; a failure (ARP_E_ARG: a non-finite coordinate, ...) leaves NO
+ * structure resident and keeps the topology, so a corrected call can follow.  A pass then evaluates every model; each
+ * model's bags are bit-identical to its own single-structure run, and in their canonical order the records of model f
+ * are contiguous and follow those of model f - 1 (ids of model f: atoms [f n, (f + 1) n), rings [f nring, ..), amides
+ * [f namide, ..)).  Selections: one mask over the F n atoms.  Call again with any F to stream further coordinate sets
+ * (trajectory chunks); a blob, a setter or arp_set_batch ends model mode.
+ * Both return ARP_E_ARG on a shard (arp_set_ownership, arp_shard_assemble); arp_set_models also without a topology, and
+ * when F n, F nbond or 3 F nh reach 2^31.
+ *
+ * arp_models_planes: what arp_set_models computed for the resident models, model after model: ring_center /
+ * ring_normal double[3 * F * nring], ring_res int32[F * nring] (residue of the MODEL, -1 = none), amide_center /
+ * amide_normal float[3 * F * namide].  ARP_E_ARG when no models are resident. */
+int arp_set_topology(arp_ctx* ctx, const void* blob, uint64_t bytes, const int32_t* ring_off, const int32_t* ring_idx,
+                     const int32_t* amide_atoms);
+int arp_set_models(arp_ctx* ctx, int64_t nmodel, const float* xyz, const double* h_xyz);
+int arp_models_planes(arp_ctx* ctx, double* ring_center, double* ring_normal, int32_t* ring_res, float* amide_center,
+                      float* amide_normal);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
