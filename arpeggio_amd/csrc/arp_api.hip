@@ -27,6 +27,7 @@
 #include "arp_cif.h"
 #include "arp_comm.h"
 #include "arp_sort.h"
+#include "arp_blob.h"
 
 namespace {
 
@@ -1188,23 +1189,24 @@ bool all_finite(const T* v, int64_t n) {
     return true;
 }
 
-void host_bbox(const float* xyz, int64_t n, double lo[3], double hi[3]) {
-    for (int k = 0; k < 3; ++k) { lo[k] = 0; hi[k] = 0; }
-    for (int64_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            double v = xyz[i * 3 + k];
-            if (i == 0 || v < lo[k]) lo[k] = v;
-            if (i == 0 || v > hi[k]) hi[k] = v;
-        }
+// The atom lists k_ring_geometry / k_amide_geometry read unchecked, against a structure of n_atoms atoms (`who` = the entry
+// point that was called).  Rings: CSR offsets, at least three atoms each, indices in range.
+int check_ring_atoms(arp_ctx* c, const char* who, int64_t nring, const int32_t* off, const int32_t* idx, int64_t n_atoms) {
+    const std::string w(who);
+    if (nring == 0) return ARP_OK;
+    if (!csr_ok(off, nring)) FAIL(c, ARP_E_ARG, w + ": ring offsets must start at 0 and never decrease");
+    if (off[nring] > 0 && !idx) FAIL(c, ARP_E_ARG, w + ": ring atom indices missing");
+    for (int64_t r = 0; r < nring; ++r)
+        if (off[r + 1] - off[r] < 3) FAIL(c, ARP_E_ARG, w + ": a ring needs at least three atoms");
+    for (int64_t k = 0; k < off[nring]; ++k)
+        if (idx[k] < 0 || idx[k] >= n_atoms) FAIL(c, ARP_E_ARG, w + ": ring atom index out of range");
+    return ARP_OK;
 }
-void host_bbox_d(const double* xyz, int64_t n, double lo[3], double hi[3]) {
-    for (int k = 0; k < 3; ++k) { lo[k] = 0; hi[k] = 0; }
-    for (int64_t i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) {
-            double v = xyz[i * 3 + k];
-            if (i == 0 || v < lo[k]) lo[k] = v;
-            if (i == 0 || v > hi[k]) hi[k] = v;
-        }
+// Amides: N, C, O of each group of four are read; the fourth atom is not.
+int check_amide_atoms(arp_ctx* c, const char* who, int64_t namide, const int32_t* atoms, int64_t n_atoms) {
+    for (int64_t k = 0; k < 4 * namide; ++k)
+        if ((k & 3) != 3 && (atoms[k] < 0 || atoms[k] >= n_atoms)) FAIL(c, ARP_E_ARG, std::string(who) + ": amide atom index out of range");
+    return ARP_OK;
 }
 
 int ensure_ring_grid(arp_ctx* c) {
@@ -2201,7 +2203,7 @@ int arp_set_atoms(arp_ctx* c, int64_t n, const float* xyz, const double* vdw, co
     inputs_changed(c, IN_ATOMS);
     c->n = n;
     c->h_xyz.assign(xyz, xyz + 3 * n);
-    host_bbox(xyz, n, c->lo, c->hi);
+    points_box(xyz, n, c->lo, c->hi);
     std::vector<float4> x4((size_t)n);
     std::vector<double2> r2((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
@@ -2321,7 +2323,7 @@ int arp_set_rings(arp_ctx* c, int64_t nring, const double* center, const double*
     HIPCHK(c, hipSetDevice(c->device));
     inputs_changed(c, IN_RINGS);
     c->nring = nring;
-    host_bbox_d(center, nring, c->ring_lo, c->ring_hi);
+    points_box(center, nring, c->ring_lo, c->ring_hi);
     CHK(upload(c, c->ring_c, center, (size_t)nring * 3));
     CHK(upload(c, c->ring_n, normal, (size_t)nring * 3));
     CHK(upload(c, c->ring_res, ring_res, (size_t)nring));
@@ -2344,7 +2346,7 @@ int arp_set_amides(arp_ctx* c, int64_t namide, const float* center, const float*
     HIPCHK(c, hipSetDevice(c->device));
     inputs_changed(c, IN_AMIDES);
     c->namide = namide;
-    host_bbox(center, namide, c->am_lo, c->am_hi);
+    points_box(center, namide, c->am_lo, c->am_hi);
     CHK(upload(c, c->am_c, center, (size_t)namide * 3));
     CHK(upload(c, c->am_n, normal, (size_t)namide * 3));
     CHK(upload(c, c->am_res, amide_res, (size_t)namide));
@@ -2354,169 +2356,15 @@ int arp_set_amides(arp_ctx* c, int64_t namide, const float* center, const float*
     return ARP_OK;
 }
 
-// ---- one-blob upload -----------------------------------------------------------------------------------------------
-namespace {
-struct BlobSizes { uint64_t esize[ARP_BLOB_ARRAYS]; uint64_t count[ARP_BLOB_ARRAYS]; };
-bool blob_sizes(int64_t n, int64_t nres, int64_t nbond, int64_t nh, int64_t nring, int64_t namide, BlobSizes& z) {
-    if (n < 0 || nres < 0 || nbond < 0 || nh < 0 || nring < 0 || namide < 0) return false;
-    if (n > 0x7FFFFFF0LL || nres > 0x7FFFFFF0LL || nbond > 0x7FFFFFF0LL || nh > 0x7FFFFFF0LL / 3 || nring > 0x7FFFFFF0LL / 3 ||
-        namide > 0x7FFFFFF0LL / 3)
-        return false;
-    const uint64_t N = (uint64_t)n, NR = (uint64_t)nres, R = (uint64_t)nring, A = (uint64_t)namide;
-    const uint64_t es[ARP_BLOB_ARRAYS] = {4, 8, 2, 2, 4, 1, 4, 4, 4, 4, 4, 8, 4, 8, 8, 4, 4, 4, 4, 2, 8};
-    const uint64_t ct[ARP_BLOB_ARRAYS] = {4 * N, 2 * N, N, N, N, NR, NR, NR, N + 1, (uint64_t)nbond, N + 1, 3 * (uint64_t)nh, N, 3 * R, 3 * R,
-                                          R, 3 * A, 3 * A, A, N, 2 * RAD_TABLE};
-    for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) { z.esize[k] = es[k]; z.count[k] = ct[k]; }
-    return true;
-}
-uint64_t align16(uint64_t v) { return (v + 15ull) & ~15ull; }
-}  // namespace
-
-uint64_t arp_blob_size(int64_t n, int64_t nres, int64_t nbond, int64_t nh, int64_t nring, int64_t namide) {
-    BlobSizes z;
-    if (!blob_sizes(n, nres, nbond, nh, nring, namide, z)) return 0;
-    uint64_t off = align16(sizeof(arp_blob_header));
-    for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) off = align16(off + z.esize[k] * z.count[k]);
-    return off;
-}
-
-int arp_blob_layout(void* blob, uint64_t bytes, int64_t n, int64_t nres, int64_t nbond, int64_t nh, int64_t nring, int64_t namide) {
-    const uint64_t need = arp_blob_size(n, nres, nbond, nh, nring, namide);
-    if (!blob || need == 0 || bytes < need) return ARP_E_ARG;
-    BlobSizes z;
-    blob_sizes(n, nres, nbond, nh, nring, namide, z);
-    arp_blob_header h;
-    memset(&h, 0, sizeof(h));
-    h.magic = ARP_BLOB_MAGIC;
-    h.bytes = need;
-    h.n = n; h.nres = nres; h.nbond = nbond; h.nh = nh; h.nring = nring; h.namide = namide;
-    uint64_t off = align16(sizeof(arp_blob_header));
-    for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) {
-        h.off[k] = off;
-        off = align16(off + z.esize[k] * z.count[k]);
-    }
-    memcpy(blob, &h, sizeof(h));
-    return ARP_OK;
-}
-
-int arp_blob_fill(void* blob, uint64_t bytes, const float* xyz, const double* vdw, const double* cov, const uint16_t* type_mask,
-                  const uint16_t* flags, const int32_t* res_id, const uint8_t* res_flags, const int32_t* res_prev,
-                  const int32_t* res_next, const int32_t* bond_off, const int32_t* bond_idx, const int32_t* h_off,
-                  const double* h_xyz, const int32_t* sb_nbr, const double* ring_center, const double* ring_normal,
-                  const int32_t* ring_res, const float* amide_center, const float* amide_normal, const int32_t* amide_res) {
-    if (!blob || bytes < sizeof(arp_blob_header)) return ARP_E_ARG;
-    arp_blob_header h;
-    memcpy(&h, blob, sizeof(h));
-    if (h.magic != ARP_BLOB_MAGIC || h.bytes > bytes || h.bytes != arp_blob_size(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide)) return ARP_E_ARG;
-    const int64_t n = h.n;
-    if ((n > 0 && (!xyz || !vdw || !cov || !type_mask || !flags || !res_id || !bond_off || !h_off || !sb_nbr)) ||
-        (h.nres > 0 && (!res_flags || !res_prev || !res_next)) || (h.nbond > 0 && !bond_idx) || (h.nh > 0 && !h_xyz) ||
-        (h.nring > 0 && (!ring_center || !ring_normal || !ring_res)) || (h.namide > 0 && (!amide_center || !amide_normal || !amide_res)))
-        return ARP_E_ARG;
-    uint8_t* const b = (uint8_t*)blob;
-    auto at = [&](int k) { return b + h.off[k]; };
-    float* x4 = (float*)at(0);
-    double* r2 = (double*)at(1);
-    for (int64_t i = 0; i < n; ++i) {
-        x4[4 * i] = xyz[3 * i]; x4[4 * i + 1] = xyz[3 * i + 1]; x4[4 * i + 2] = xyz[3 * i + 2]; x4[4 * i + 3] = 0.0f;
-        r2[2 * i] = vdw[i]; r2[2 * i + 1] = cov[i];
-    }
-    auto copy = [&](int k, const void* src, size_t nbytes) { if (nbytes) memcpy(at(k), src, nbytes); };
-    copy(2, type_mask, (size_t)n * 2); copy(3, flags, (size_t)n * 2); copy(4, res_id, (size_t)n * 4);
-    copy(5, res_flags, (size_t)h.nres); copy(6, res_prev, (size_t)h.nres * 4); copy(7, res_next, (size_t)h.nres * 4);
-    if (n > 0) { copy(8, bond_off, ((size_t)n + 1) * 4); copy(10, h_off, ((size_t)n + 1) * 4); }
-    else { const int32_t z = 0; copy(8, &z, 4); copy(10, &z, 4); }
-    copy(9, bond_idx, (size_t)h.nbond * 4); copy(11, h_xyz, (size_t)h.nh * 24); copy(12, sb_nbr, (size_t)n * 4);
-    copy(13, ring_center, (size_t)h.nring * 24); copy(14, ring_normal, (size_t)h.nring * 24); copy(15, ring_res, (size_t)h.nring * 4);
-    copy(16, amide_center, (size_t)h.namide * 12); copy(17, amide_normal, (size_t)h.namide * 12); copy(18, amide_res, (size_t)h.namide * 4);
-    // dictionary of the distinct {vdw, cov} pairs, compared bit for bit: a handful of element values in practice, so a
-    // small open-addressing table keyed by the 128 bits; entries are numbered in ascending (vdw bits, cov bits) order
-    uint16_t* ridx = (uint16_t*)at(19);
-    double* tab = (double*)at(20);
-    memset(tab, 0, sizeof(double) * 2 * RAD_TABLE);
-    struct Key { uint64_t a, b; int64_t count; int slot; };
-    std::vector<Key> keys;
-    std::vector<int> hash(4096, -1);
-    std::vector<int> key_of((size_t)n);
-    auto bits = [](double d) { uint64_t u; memcpy(&u, &d, 8); return u; };
-    for (int64_t i = 0; i < n; ++i) {
-        const uint64_t ka = bits(vdw[i]), kb = bits(cov[i]);
-        size_t hpos = (size_t)((ka * 0x9E3779B97F4A7C15ull) ^ (kb * 0xC2B2AE3D27D4EB4Full)) >> 20;
-        int found = -1;
-        for (;;) {
-            hpos &= hash.size() - 1;
-            const int k = hash[hpos];
-            if (k < 0) break;
-            if (keys[(size_t)k].a == ka && keys[(size_t)k].b == kb) { found = k; break; }
-            ++hpos;
-        }
-        if (found < 0) {
-            if (keys.size() * 2 >= hash.size()) {   // grow and re-insert
-                std::vector<int> bigger(hash.size() * 4, -1);
-                for (size_t k = 0; k < keys.size(); ++k) {
-                    size_t p = (size_t)((keys[k].a * 0x9E3779B97F4A7C15ull) ^ (keys[k].b * 0xC2B2AE3D27D4EB4Full)) >> 20;
-                    for (;; ++p) { p &= bigger.size() - 1; if (bigger[p] < 0) { bigger[p] = (int)k; break; } }
-                }
-                hash.swap(bigger);
-                hpos = (size_t)((ka * 0x9E3779B97F4A7C15ull) ^ (kb * 0xC2B2AE3D27D4EB4Full)) >> 20;
-                for (;; ++hpos) { hpos &= hash.size() - 1; if (hash[hpos] < 0) break; }
-            }
-            found = (int)keys.size();
-            keys.push_back(Key{ka, kb, 0, -1});
-            hash[hpos] = found;
-        }
-        ++keys[(size_t)found].count;
-        key_of[(size_t)i] = found;
-    }
-    std::vector<int> order(keys.size());
-    for (size_t k = 0; k < keys.size(); ++k) order[k] = (int)k;
-    std::sort(order.begin(), order.end(), [&](int p, int q) { return keys[(size_t)p].a != keys[(size_t)q].a ? keys[(size_t)p].a < keys[(size_t)q].a : keys[(size_t)p].b < keys[(size_t)q].b; });
-    if (keys.size() <= (size_t)RAD_TABLE) {
-        for (size_t r = 0; r < order.size(); ++r) keys[(size_t)order[r]].slot = (int)r;
-        h.n_rad = (int64_t)keys.size();
-    } else {   // the 256 most frequent pairs (ties: the smaller pair first), numbered by descending frequency
-        std::stable_sort(order.begin(), order.end(), [&](int p, int q) { return keys[(size_t)p].count > keys[(size_t)q].count; });
-        for (size_t r = 0; r < (size_t)RAD_TABLE; ++r) keys[(size_t)order[r]].slot = (int)r;
-        h.n_rad = RAD_TABLE;
-    }
-    for (const Key& k : keys)
-        if (k.slot >= 0) { memcpy(&tab[2 * k.slot], &k.a, 8); memcpy(&tab[2 * k.slot + 1], &k.b, 8); }
-    for (int64_t i = 0; i < n; ++i) {
-        const int slot = keys[(size_t)key_of[(size_t)i]].slot;
-        ridx[i] = slot >= 0 ? (uint16_t)slot : (uint16_t)RAD_NONE;
-    }
-    // bounding boxes (0 for an empty set)
-    auto box = [](auto* pts, int64_t cnt, double* lo, double* hi) {
-        for (int k = 0; k < 3; ++k) { lo[k] = hi[k] = cnt > 0 ? (double)pts[k] : 0.0; }
-        for (int64_t i = 1; i < cnt; ++i)
-            for (int k = 0; k < 3; ++k) {
-                const double v = (double)pts[3 * i + k];
-                lo[k] = std::min(lo[k], v);
-                hi[k] = std::max(hi[k], v);
-            }
-    };
-    box(xyz, n, h.lo, h.hi);
-    box(ring_center, h.nring, h.ring_lo, h.ring_hi);
-    box(amide_center, h.namide, h.amide_lo, h.amide_hi);
-    memcpy(blob, &h, sizeof(h));
-    return ARP_OK;
-}
-
+// ---- one-blob upload (layout, names of the arrays and the host packer: arp_blob.h) -------------------------------------------
 namespace {
 // header of a blob: counts, size and offsets as arp_blob_layout writes them, finite boxes
 int check_blob_header(arp_ctx* c, const arp_blob_header& h, uint64_t bytes) {
     if (h.magic != ARP_BLOB_MAGIC) FAIL(c, ARP_E_ARG, "arp_set_blob: bad magic");
-    BlobSizes z;
-    if (!blob_sizes(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide, z)) FAIL(c, ARP_E_ARG, "arp_set_blob: counts out of range");
-    if (h.bytes != arp_blob_size(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide) || h.bytes > bytes)
-        FAIL(c, ARP_E_ARG, "arp_set_blob: size does not match the counts");
-    {   // the offsets must be the ones arp_blob_layout writes
-        uint64_t off = align16(sizeof(arp_blob_header));
-        for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) {
-            if (h.off[k] != off) FAIL(c, ARP_E_ARG, "arp_set_blob: unexpected array offset");
-            off = align16(off + z.esize[k] * z.count[k]);
-        }
-    }
+    arp_blob_header want;
+    if (!blob_header(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide, want)) FAIL(c, ARP_E_ARG, "arp_set_blob: counts out of range");
+    if (h.bytes != want.bytes || h.bytes > bytes) FAIL(c, ARP_E_ARG, "arp_set_blob: size does not match the counts");
+    if (memcmp(h.off, want.off, sizeof(h.off)) != 0) FAIL(c, ARP_E_ARG, "arp_set_blob: unexpected array offset");
     if (h.n_rad < 0 || h.n_rad > RAD_TABLE) FAIL(c, ARP_E_ARG, "arp_set_blob: n_rad out of range");
     if (h.n > 0 && h.nres <= 0) FAIL(c, ARP_E_ARG, "arp_set_blob: atoms without a residue table");
     for (int k = 0; k < 3; ++k) {
@@ -2532,18 +2380,20 @@ int check_blob_header(arp_ctx* c, const arp_blob_header& h, uint64_t bytes) {
 void borrow_blob_views(arp_ctx* c, const arp_blob_header& h) {
     uint8_t* const d = c->blob_dev.p;
     const size_t n1 = (size_t)std::max<int64_t>(h.n, 1);
-    c->xyz.borrow(d + h.off[0], n1); c->rad.borrow(d + h.off[1], n1); c->tmask.borrow(d + h.off[2], n1);
-    c->flags.borrow(d + h.off[3], n1); c->res_id.borrow(d + h.off[4], n1);
-    c->res_flags.borrow(d + h.off[5], (size_t)std::max<int64_t>(h.nres, 1)); c->res_prev.borrow(d + h.off[6], (size_t)std::max<int64_t>(h.nres, 1));
-    c->res_next.borrow(d + h.off[7], (size_t)std::max<int64_t>(h.nres, 1));
-    c->bond_off.borrow(d + h.off[8], (size_t)h.n + 1); c->bond_idx.borrow(d + h.off[9], (size_t)std::max<int64_t>(h.nbond, 1));
-    c->h_off.borrow(d + h.off[10], (size_t)h.n + 1); c->h_xyz_d.borrow(d + h.off[11], (size_t)std::max<int64_t>(3 * h.nh, 3));
-    c->blob_sb_nbr.borrow(d + h.off[12], n1);
-    c->ring_c.borrow(d + h.off[13], (size_t)std::max<int64_t>(3 * h.nring, 1)); c->ring_n.borrow(d + h.off[14], (size_t)std::max<int64_t>(3 * h.nring, 1));
-    c->ring_res.borrow(d + h.off[15], (size_t)std::max<int64_t>(h.nring, 1));
-    c->am_c.borrow(d + h.off[16], (size_t)std::max<int64_t>(3 * h.namide, 1)); c->am_n.borrow(d + h.off[17], (size_t)std::max<int64_t>(3 * h.namide, 1));
-    c->am_res.borrow(d + h.off[18], (size_t)std::max<int64_t>(h.namide, 1));
-    c->rad_idx.borrow(d + h.off[19], n1); c->rad_tab.borrow(d + h.off[20], (size_t)RAD_TABLE);
+    auto at = [&](BlobArray a) { return d + h.off[a]; };
+    auto atleast1 = [](int64_t v) { return (size_t)std::max<int64_t>(v, 1); };
+    c->xyz.borrow(at(BLOB_XYZ), n1); c->rad.borrow(at(BLOB_RAD), n1); c->tmask.borrow(at(BLOB_TMASK), n1);
+    c->flags.borrow(at(BLOB_FLAGS), n1); c->res_id.borrow(at(BLOB_RES_ID), n1);
+    c->res_flags.borrow(at(BLOB_RES_FLAGS), atleast1(h.nres)); c->res_prev.borrow(at(BLOB_RES_PREV), atleast1(h.nres));
+    c->res_next.borrow(at(BLOB_RES_NEXT), atleast1(h.nres));
+    c->bond_off.borrow(at(BLOB_BOND_OFF), (size_t)h.n + 1); c->bond_idx.borrow(at(BLOB_BOND_IDX), atleast1(h.nbond));
+    c->h_off.borrow(at(BLOB_H_OFF), (size_t)h.n + 1); c->h_xyz_d.borrow(at(BLOB_H_XYZ), (size_t)std::max<int64_t>(3 * h.nh, 3));
+    c->blob_sb_nbr.borrow(at(BLOB_SB_NBR), n1);
+    c->ring_c.borrow(at(BLOB_RING_C), atleast1(3 * h.nring)); c->ring_n.borrow(at(BLOB_RING_N), atleast1(3 * h.nring));
+    c->ring_res.borrow(at(BLOB_RING_RES), atleast1(h.nring));
+    c->am_c.borrow(at(BLOB_AMIDE_C), atleast1(3 * h.namide)); c->am_n.borrow(at(BLOB_AMIDE_N), atleast1(3 * h.namide));
+    c->am_res.borrow(at(BLOB_AMIDE_RES), atleast1(h.namide));
+    c->rad_idx.borrow(at(BLOB_RAD_IDX), n1); c->rad_tab.borrow(at(BLOB_RAD_TAB), (size_t)RAD_TABLE);
     c->n = h.n; c->nres = h.nres; c->nring = h.nring; c->namide = h.namide;
     c->has_res = true;
     c->blob_nbond = h.nbond; c->blob_nh = h.nh; c->blob_nrad = h.n_rad;
@@ -2715,14 +2565,15 @@ int arp_set_blob(arp_ctx* c, const void* blob, uint64_t bytes) {
     // writes them on the device from the table.  (From 32 768 atoms on: below that the second copy costs more than the bytes.)
     bool rad_from_table = h.n >= 32768 && h.n_rad > 0 && h.n_rad <= RAD_TABLE;
     if (rad_from_table) {
-        const uint16_t* ridx = (const uint16_t*)((const uint8_t*)blob + h.off[19]);
+        const uint16_t* ridx = blob_at<uint16_t>((const uint8_t*)blob, h, BLOB_RAD_IDX);
         unsigned any_none = 0;
         for (int64_t i = 0; i < h.n; ++i) any_none |= (unsigned)(ridx[i] == RAD_NONE);
         rad_from_table = any_none == 0;
     }
     if (rad_from_table) {
-        HIPCHK(c, hipMemcpyAsync(c->blob_dev.p, blob, (size_t)h.off[1], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->blob_dev.p + h.off[2], (const uint8_t*)blob + h.off[2], (size_t)(h.bytes - h.off[2]), hipMemcpyHostToDevice, c->stream));
+        const uint64_t rad = h.off[BLOB_RAD], after = h.off[BLOB_RAD + 1];       // everything before the radii, everything behind them
+        HIPCHK(c, hipMemcpyAsync(c->blob_dev.p, blob, (size_t)rad, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->blob_dev.p + after, (const uint8_t*)blob + after, (size_t)(h.bytes - after), hipMemcpyHostToDevice, c->stream));
     } else {
         HIPCHK(c, hipMemcpyAsync(c->blob_dev.p, blob, (size_t)h.bytes, hipMemcpyHostToDevice, c->stream));
     }
@@ -2744,30 +2595,20 @@ int arp_get_blob(arp_ctx* c, void* host, uint64_t cap, uint64_t* bytes) {
 
 // ---- sharded structures assembled on the device ---------------------------------------------------------
 namespace {
-const uint64_t REC_ESIZE[5] = {sizeof(arp_rec_atom), 3 * sizeof(double), sizeof(int32_t), sizeof(arp_rec_ring), sizeof(arp_rec_amide)};
-bool rec_counts_ok(int64_t na, int64_t nh, int64_t nb, int64_t nring, int64_t namide) {
-    const int64_t lim = 0x7FFFFFF0LL / 3;
-    return na >= 0 && nh >= 0 && nb >= 0 && nring >= 0 && namide >= 0 && na <= lim && nh <= lim && nb <= 0x7FFFFFF0LL && nring <= lim &&
-           namide <= lim;
-}
 int check_rec_header(arp_ctx* c, const arp_rec_header& h, uint64_t bytes, const char* who) {
     const std::string w(who);
     if (h.magic != ARP_REC_MAGIC) FAIL(c, ARP_E_ARG, w + ": bad magic");
-    if (!rec_counts_ok(h.na, h.nh, h.nb, h.nring, h.namide)) FAIL(c, ARP_E_ARG, w + ": counts out of range");
-    if (h.bytes != arp_records_size(h.na, h.nh, h.nb, h.nring, h.namide) || h.bytes > bytes) FAIL(c, ARP_E_ARG, w + ": size does not match the counts");
-    const int64_t cnt[5] = {h.na, h.nh, h.nb, h.nring, h.namide};
-    uint64_t off = align16(sizeof(arp_rec_header));
-    for (int k = 0; k < 5; ++k) {
-        if (h.off[k] != off) FAIL(c, ARP_E_ARG, w + ": unexpected section offset");
-        off = align16(off + REC_ESIZE[k] * (uint64_t)cnt[k]);
-    }
+    arp_rec_header want;
+    if (!rec_header(h.na, h.nh, h.nb, h.nring, h.namide, want)) FAIL(c, ARP_E_ARG, w + ": counts out of range");
+    if (h.bytes != want.bytes || h.bytes > bytes) FAIL(c, ARP_E_ARG, w + ": size does not match the counts");
+    if (memcmp(h.off, want.off, sizeof(h.off)) != 0) FAIL(c, ARP_E_ARG, w + ": unexpected section offset");
     if (h.n_rad < 0 || h.n_rad > RAD_TABLE) FAIL(c, ARP_E_ARG, w + ": n_rad out of range");
     return ARP_OK;
 }
 RecList rec_list(const uint8_t* base, const arp_rec_header& h) {
     RecList l;
-    l.a = (const arp_rec_atom*)(base + h.off[0]); l.h = (const double*)(base + h.off[1]); l.b = (const int*)(base + h.off[2]);
-    l.r = (const arp_rec_ring*)(base + h.off[3]); l.m = (const arp_rec_amide*)(base + h.off[4]);
+    l.a = (const arp_rec_atom*)(base + h.off[REC_ATOMS]); l.h = (const double*)(base + h.off[REC_H_XYZ]); l.b = (const int*)(base + h.off[REC_BONDS]);
+    l.r = (const arp_rec_ring*)(base + h.off[REC_RINGS]); l.m = (const arp_rec_amide*)(base + h.off[REC_AMIDES]);
     l.na = (int)h.na; l.nh = (int)h.nh; l.nb = (int)h.nb; l.nr = (int)h.nring; l.nm = (int)h.namide;
     return l;
 }
@@ -2779,120 +2620,13 @@ RecList empty_rec_list() {
 }
 }  // namespace
 
-uint64_t arp_records_size(int64_t na, int64_t nh, int64_t nb, int64_t nring, int64_t namide) {
-    if (!rec_counts_ok(na, nh, nb, nring, namide)) return 0;
-    const int64_t cnt[5] = {na, nh, nb, nring, namide};
-    uint64_t off = align16(sizeof(arp_rec_header));
-    for (int k = 0; k < 5; ++k) off = align16(off + REC_ESIZE[k] * (uint64_t)cnt[k]);
-    return off;
-}
-
-int arp_records_layout(void* buf, uint64_t bytes, int64_t na, int64_t nh, int64_t nb, int64_t nring, int64_t namide) {
-    const uint64_t need = arp_records_size(na, nh, nb, nring, namide);
-    if (!buf || need == 0 || bytes < need) return ARP_E_ARG;
-    arp_rec_header h;
-    memset(&h, 0, sizeof(h));
-    h.magic = ARP_REC_MAGIC;
-    h.bytes = need;
-    h.na = na; h.nh = nh; h.nb = nb; h.nring = nring; h.namide = namide;
-    const int64_t cnt[5] = {na, nh, nb, nring, namide};
-    uint64_t off = align16(sizeof(arp_rec_header));
-    for (int k = 0; k < 5; ++k) {
-        h.off[k] = off;
-        off = align16(off + REC_ESIZE[k] * (uint64_t)cnt[k]);
-    }
-    memcpy(buf, &h, sizeof(h));
-    return ARP_OK;
-}
-
-int arp_records_fill(void* buf, uint64_t bytes, int64_t n_total, int64_t nres_total, int64_t nring_total, int64_t namide_total, const float* xyz, const double* vdw, const double* cov,
-                     const uint16_t* type_mask, const uint16_t* flags, const int32_t* res_id, const uint8_t* res_flags,
-                     const int32_t* res_prev, const int32_t* res_next, const int32_t* bond_off, const int32_t* bond_idx,
-                     const int32_t* h_off, const double* h_xyz, const int32_t* sb_nbr, const double* ring_center,
-                     const double* ring_normal, const int32_t* ring_res, const float* amide_center, const float* amide_normal,
-                     const int32_t* amide_res, const uint8_t* sel, const int64_t* atom_ids, const int64_t* ring_ids,
-                     const int64_t* amide_ids) {
-    if (!buf || bytes < sizeof(arp_rec_header)) return ARP_E_ARG;
-    arp_rec_header h;
-    memcpy(&h, buf, sizeof(h));
-    if (h.magic != ARP_REC_MAGIC || h.bytes > bytes || h.bytes != arp_records_size(h.na, h.nh, h.nb, h.nring, h.namide)) return ARP_E_ARG;
-    if ((h.na > 0 && (!atom_ids || !xyz || !vdw || !cov || !type_mask || !flags || !res_id || !res_flags || !res_prev || !res_next || !bond_off ||
-                      !h_off || !sb_nbr)) ||
-        (h.nring > 0 && (!ring_ids || !ring_center || !ring_normal || !ring_res)) ||
-        (h.namide > 0 && (!amide_ids || !amide_center || !amide_normal || !amide_res)))
-        return ARP_E_ARG;
-    uint8_t* const b = (uint8_t*)buf;
-    memset(b + sizeof(h), 0, (size_t)h.bytes - sizeof(h));
-    arp_rec_atom* A = (arp_rec_atom*)(b + h.off[0]);
-    double* H = (double*)(b + h.off[1]);
-    int32_t* B = (int32_t*)(b + h.off[2]);
-    arp_rec_ring* R = (arp_rec_ring*)(b + h.off[3]);
-    arp_rec_amide* M = (arp_rec_amide*)(b + h.off[4]);
-    int64_t hs = 0, bs = 0;
-    struct Pair { uint64_t a, b; };
-    std::vector<Pair> uniq;
-    auto bits = [](double d) { uint64_t u; memcpy(&u, &d, 8); return u; };
-    for (int64_t k = 0; k < h.na; ++k) {
-        const int64_t i = atom_ids[k];
-        if (i < 0 || i >= n_total || (k > 0 && atom_ids[k - 1] >= i)) return ARP_E_ARG;
-        arp_rec_atom& r = A[k];
-        r.x = xyz[3 * i]; r.y = xyz[3 * i + 1]; r.z = xyz[3 * i + 2]; r.gid = (int32_t)i;
-        r.vdw = vdw[i]; r.cov = cov[i];
-        const int32_t nb = sb_nbr[i];
-        if (nb < -1 || nb >= n_total) return ARP_E_ARG;
-        if (nb >= 0) { r.sb_x = xyz[3 * (int64_t)nb]; r.sb_y = xyz[3 * (int64_t)nb + 1]; r.sb_z = xyz[3 * (int64_t)nb + 2]; r.sb_has = 1; }
-        const int32_t res = res_id[i];
-        if (res < 0 || res >= nres_total) return ARP_E_ARG;
-        r.res_gid = res; r.res_prev = res_prev[res]; r.res_next = res_next[res]; r.res_flags = res_flags[res];
-        r.tmask = type_mask[i]; r.flags = flags[i];
-        r.sel = sel ? sel[i] : (uint8_t)1;
-        r.h_start = (int32_t)hs; r.h_cnt = h_off[i + 1] - h_off[i];
-        r.bond_start = (int32_t)bs; r.bond_cnt = bond_off[i + 1] - bond_off[i];
-        if (r.h_cnt < 0 || r.bond_cnt < 0 || hs + r.h_cnt > h.nh || bs + r.bond_cnt > h.nb) return ARP_E_ARG;
-        if (r.h_cnt) memcpy(H + 3 * hs, h_xyz + 3 * (int64_t)h_off[i], (size_t)r.h_cnt * 24);
-        if (r.bond_cnt) memcpy(B + bs, bond_idx + bond_off[i], (size_t)r.bond_cnt * 4);
-        hs += r.h_cnt; bs += r.bond_cnt;
-        const Pair key{bits(r.vdw), bits(r.cov)};
-        bool seen = false;
-        for (const Pair& u : uniq) if (u.a == key.a && u.b == key.b) { seen = true; break; }
-        if (!seen && uniq.size() < 4096) uniq.push_back(key);     // (a handful of element values in practice)
-    }
-    if (hs != h.nh || bs != h.nb) return ARP_E_ARG;
-    for (int64_t k = 0; k < h.nring; ++k) {
-        const int64_t i = ring_ids[k];
-        if (i < 0 || i >= nring_total || (k > 0 && ring_ids[k - 1] >= i) || ring_res[i] < -1 || ring_res[i] >= nres_total) return ARP_E_ARG;
-        for (int q = 0; q < 3; ++q) { R[k].c[q] = ring_center[3 * i + q]; R[k].n[q] = ring_normal[3 * i + q]; }
-        R[k].gid = (int32_t)i; R[k].res = ring_res[i];
-    }
-    for (int64_t k = 0; k < h.namide; ++k) {
-        const int64_t i = amide_ids[k];
-        if (i < 0 || i >= namide_total || (k > 0 && amide_ids[k - 1] >= i) || amide_res[i] < -1 || amide_res[i] >= nres_total) return ARP_E_ARG;
-        for (int q = 0; q < 3; ++q) { M[k].c[q] = amide_center[3 * i + q]; M[k].n[q] = amide_normal[3 * i + q]; }
-        M[k].gid = (int32_t)i; M[k].res = amide_res[i];
-    }
-    std::sort(uniq.begin(), uniq.end(), [](const Pair& p, const Pair& q) { return p.a != q.a ? p.a < q.a : p.b < q.b; });
-    h.n_rad = (int64_t)std::min<size_t>(uniq.size(), RAD_TABLE);
-    memset(h.rad_tab, 0, sizeof(h.rad_tab));
-    for (int64_t k = 0; k < h.n_rad; ++k) { memcpy(&h.rad_tab[2 * k], &uniq[(size_t)k].a, 8); memcpy(&h.rad_tab[2 * k + 1], &uniq[(size_t)k].b, 8); }
-    auto box = [](double* lo, double* hi, int64_t cnt, auto coord) {
-        for (int q = 0; q < 3; ++q) lo[q] = hi[q] = cnt > 0 ? coord(0, q) : 0.0;
-        for (int64_t k = 1; k < cnt; ++k)
-            for (int q = 0; q < 3; ++q) { const double v = coord(k, q); lo[q] = std::min(lo[q], v); hi[q] = std::max(hi[q], v); }
-    };
-    box(h.lo, h.hi, h.na, [&](int64_t k, int q) { return (double)(&A[k].x)[q]; });
-    box(h.ring_lo, h.ring_hi, h.nring, [&](int64_t k, int q) { return R[k].c[q]; });
-    box(h.amide_lo, h.amide_hi, h.namide, [&](int64_t k, int q) { return (double)M[k].c[q]; });
-    memcpy(buf, &h, sizeof(h));
-    return ARP_OK;
-}
-
 int arp_shard_set_home(arp_ctx* c, const void* records, uint64_t bytes) {
     if (!c || !records || bytes < sizeof(arp_rec_header)) return ARP_E_ARG;
     arp_rec_header h;
     memcpy(&h, records, sizeof(h));
     CHK(check_rec_header(c, h, bytes, "arp_shard_set_home"));
     {   // the CSR runs of the home records are read by the face kernels: check them here (the merge checks received buffers)
-        const arp_rec_atom* a = (const arp_rec_atom*)((const uint8_t*)records + h.off[0]);
+        const arp_rec_atom* a = (const arp_rec_atom*)((const uint8_t*)records + h.off[REC_ATOMS]);
         for (int64_t i = 0; i < h.na; ++i) {
             const bool ok = a[i].h_cnt >= 0 && a[i].bond_cnt >= 0 && a[i].h_start >= 0 && a[i].bond_start >= 0 &&
                             (int64_t)a[i].h_start + a[i].h_cnt <= h.nh && (int64_t)a[i].bond_start + a[i].bond_cnt <= h.nb &&
@@ -2930,12 +2664,9 @@ int arp_shard_pack_face(arp_ctx* c, int slot, double x_lo, double x_hi, uint64_t
     const int* last[5] = {fa + na, fh + na, fb + na, fr + nr, fm + nm};
     for (int k = 0; k < 5; ++k) HIPCHK(c, hipMemcpyAsync(&tot[k], last[k], sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t bytes = arp_records_size(tot[0], tot[1], tot[2], tot[3], tot[4]);
-    if (bytes == 0) FAIL(c, ARP_E_ARG, "arp_shard_pack_face: counts out of range");
-    std::vector<uint8_t> hb(sizeof(arp_rec_header));
-    arp_records_layout(hb.data(), bytes, tot[0], tot[1], tot[2], tot[3], tot[4]);
     arp_rec_header F;
-    memcpy(&F, hb.data(), sizeof(F));
+    if (!rec_header(tot[0], tot[1], tot[2], tot[3], tot[4], F)) FAIL(c, ARP_E_ARG, "arp_shard_pack_face: counts out of range");
+    const uint64_t bytes = F.bytes;
     // any box that contains the points will do: the home boxes, clipped to the x range that was asked for
     for (int k = 0; k < 3; ++k) {
         F.lo[k] = H.lo[k]; F.hi[k] = H.hi[k]; F.ring_lo[k] = H.ring_lo[k]; F.ring_hi[k] = H.ring_hi[k];
@@ -2953,8 +2684,8 @@ int arp_shard_pack_face(arp_ctx* c, int slot, double x_lo, double x_hi, uint64_t
     HIPCHK(c, hipMemsetAsync(out.p, 0, (size_t)bytes, c->stream));         // alignment gaps travel too: keep them defined
     HIPCHK(c, hipMemcpyAsync(out.p, &F, sizeof(F), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_face_write, dim3(nblocks((int64_t)std::max({na, nr, nm, (size_t)1}), 256)), dim3(256), 0, c->stream, home, fa, fh, fb, fr,
-                       fm, (arp_rec_atom*)(out.p + F.off[0]), (double*)(out.p + F.off[1]), (int*)(out.p + F.off[2]),
-                       (arp_rec_ring*)(out.p + F.off[3]), (arp_rec_amide*)(out.p + F.off[4]));
+                       fm, (arp_rec_atom*)(out.p + F.off[REC_ATOMS]), (double*)(out.p + F.off[REC_H_XYZ]), (int*)(out.p + F.off[REC_BONDS]),
+                       (arp_rec_ring*)(out.p + F.off[REC_RINGS]), (arp_rec_amide*)(out.p + F.off[REC_AMIDES]));
     CHK(check_launch(c, "k_face_write"));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // the caller hands the buffer to another stream (RCCL)
     *device_ptr = (uint64_t)(uintptr_t)out.p;
@@ -3013,34 +2744,23 @@ int arp_shard_assemble(arp_ctx* c, uint64_t dev_left, uint64_t bytes_left, uint6
         FAIL(c, ARP_E_ARG, "arp_shard_assemble: an atom occurs twice in home + halos, a list is not ascending, or a record's runs leave its sections");
     const int64_t nbond = tot[1];
     // the blob the merged structure lives in
-    const uint64_t bytes = arp_blob_size(n, nres_global, nbond, nh, nring, namide);
-    if (bytes == 0) FAIL(c, ARP_E_ARG, "arp_shard_assemble: merged counts out of range");
-    std::vector<uint8_t> hb(sizeof(arp_blob_header));
-    arp_blob_layout(hb.data(), bytes, n, nres_global, nbond, nh, nring, namide);
     arp_blob_header B;
-    memcpy(&B, hb.data(), sizeof(B));
-    auto merge_box = [&](double* lo, double* hi, int which) {
-        bool any = false;
+    if (!blob_header(n, nres_global, nbond, nh, nring, namide, B)) FAIL(c, ARP_E_ARG, "arp_shard_assemble: merged counts out of range");
+    const uint64_t bytes = B.bytes;
+    {   // boxes: the union over the parts that hold points of the kind (none: 0, as the header is)
+        bool any[3] = {false, false, false};
         for (int s = 0; s < 3; ++s) {
-            const int64_t cnt = which == 0 ? hd[s].na : (which == 1 ? hd[s].nring : hd[s].namide);
-            if (cnt == 0) continue;
-            const double* l = which == 0 ? hd[s].lo : (which == 1 ? hd[s].ring_lo : hd[s].amide_lo);
-            const double* u = which == 0 ? hd[s].hi : (which == 1 ? hd[s].ring_hi : hd[s].amide_hi);
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = any ? std::min(lo[k], l[k]) : l[k];
-                hi[k] = any ? std::max(hi[k], u[k]) : u[k];
-            }
-            any = true;
+            if (hd[s].na > 0) box_union(B.lo, B.hi, any[0], hd[s].lo, hd[s].hi);
+            if (hd[s].nring > 0) box_union(B.ring_lo, B.ring_hi, any[1], hd[s].ring_lo, hd[s].ring_hi);
+            if (hd[s].namide > 0) box_union(B.amide_lo, B.amide_hi, any[2], hd[s].amide_lo, hd[s].amide_hi);
         }
-        if (!any) for (int k = 0; k < 3; ++k) lo[k] = hi[k] = 0.0;
-    };
-    merge_box(B.lo, B.hi, 0); merge_box(B.ring_lo, B.ring_hi, 1); merge_box(B.amide_lo, B.amide_hi, 2);
+    }
     B.n_rad = hd[0].n_rad;
     CHK(check_blob_header(c, B, bytes));
     HIPCHK(c, c->blob_dev.reserve((size_t)bytes));
     HIPCHK(c, hipMemsetAsync(c->blob_dev.p, 0, (size_t)bytes, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->blob_dev.p, &B, sizeof(B), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->blob_dev.p + B.off[20], hd[0].rad_tab, sizeof(double) * 2 * RAD_TABLE, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->blob_dev.p + B.off[BLOB_RAD_TAB], hd[0].rad_tab, sizeof(double) * 2 * RAD_TABLE, hipMemcpyHostToDevice, c->stream));
     borrow_blob_views(c, B);
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), r1 = (size_t)std::max<int64_t>(nring, 1), m1 = (size_t)std::max<int64_t>(namide, 1);
     HIPCHK(c, c->sb.reserve(n1)); HIPCHK(c, c->gid.reserve(n1)); HIPCHK(c, c->home.reserve(n1)); HIPCHK(c, c->origin.reserve(n1));
@@ -3865,13 +3585,8 @@ int arp_ring_geometry(arp_ctx* c, int64_t nring, const int32_t* ring_off, const 
                       double* out_normal) {
     if (!c || nring < 0 || (nring > 0 && (!ring_off || !out_center || !out_normal))) return ARP_E_ARG;
     if (nring == 0) return ARP_OK;
-    if (!csr_ok(ring_off, nring)) FAIL(c, ARP_E_ARG, "arp_ring_geometry: offsets must start at 0 and never decrease");
+    CHK(check_ring_atoms(c, "arp_ring_geometry", nring, ring_off, ring_idx, c->n));
     const int64_t m = ring_off[nring];
-    if (m > 0 && !ring_idx) return ARP_E_ARG;
-    for (int64_t r = 0; r < nring; ++r)
-        if (ring_off[r + 1] - ring_off[r] < 3) FAIL(c, ARP_E_ARG, "arp_ring_geometry: a ring needs at least three atoms");
-    for (int64_t k = 0; k < m; ++k)
-        if (ring_idx[k] < 0 || ring_idx[k] >= c->n) FAIL(c, ARP_E_ARG, "arp_ring_geometry: atom index out of range");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<int> d_off, d_idx;
     DevBuf<double> d_c, d_n;
@@ -3880,8 +3595,8 @@ int arp_ring_geometry(arp_ctx* c, int64_t nring, const int32_t* ring_off, const 
     hipError_t e = d_c.reserve((size_t)nring * 3);
     if (e == hipSuccess) e = d_n.reserve((size_t)nring * 3);
     if (rc == ARP_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_ring_geometry, dim3(nblocks(nring, 256)), dim3(256), 0, c->stream, (int)nring, d_off.p, d_idx.p,
-                           c->xyz.p, d_c.p, d_n.p);
+        hipLaunchKernelGGL(k_ring_geometry, dim3(nblocks(nring, 256)), dim3(256), 0, c->stream, 1, (int)c->n, (int)nring, d_off.p,
+                           d_idx.p, c->xyz.p, d_c.p, d_n.p);
         rc = check_launch(c, "k_ring_geometry");
         if (rc == ARP_OK) rc = download(c, out_center, d_c.p, (size_t)nring * 3);
         if (rc == ARP_OK) rc = download(c, out_normal, d_n.p, (size_t)nring * 3);
@@ -3894,9 +3609,7 @@ int arp_ring_geometry(arp_ctx* c, int64_t nring, const int32_t* ring_off, const 
 int arp_amide_geometry(arp_ctx* c, int64_t namide, const int32_t* amide_atoms, float* out_center, float* out_normal) {
     if (!c || namide < 0 || (namide > 0 && (!amide_atoms || !out_center || !out_normal))) return ARP_E_ARG;
     if (namide == 0) return ARP_OK;
-    for (int64_t k = 0; k < 4 * namide; ++k)
-        if ((k & 3) != 3 && (amide_atoms[k] < 0 || amide_atoms[k] >= c->n))   // N, C, O are read; the fourth atom is not
-            FAIL(c, ARP_E_ARG, "arp_amide_geometry: atom index out of range");
+    CHK(check_amide_atoms(c, "arp_amide_geometry", namide, amide_atoms, c->n));
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<int> d_at;
     DevBuf<float> d_c, d_n;
@@ -3904,8 +3617,8 @@ int arp_amide_geometry(arp_ctx* c, int64_t namide, const int32_t* amide_atoms, f
     hipError_t e = d_c.reserve((size_t)namide * 3);
     if (e == hipSuccess) e = d_n.reserve((size_t)namide * 3);
     if (rc == ARP_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(k_amide_geometry, dim3(nblocks(namide, 256)), dim3(256), 0, c->stream, (int)namide, d_at.p, c->xyz.p,
-                           d_c.p, d_n.p);
+        hipLaunchKernelGGL(k_amide_geometry, dim3(nblocks(namide, 256)), dim3(256), 0, c->stream, 1, (int)c->n, (int)namide, d_at.p,
+                           c->xyz.p, d_c.p, d_n.p);
         rc = check_launch(c, "k_amide_geometry");
         if (rc == ARP_OK) rc = download(c, out_center, d_c.p, (size_t)namide * 3);
         if (rc == ARP_OK) rc = download(c, out_normal, d_n.p, (size_t)namide * 3);
@@ -3933,7 +3646,7 @@ int arp_ring_residues(arp_ctx* c, int64_t nring, const double* center, int32_t* 
     if (e == hipSuccess) e = d_d.reserve((size_t)nring);
     if (rc == ARP_OK && e == hipSuccess) {
         hipLaunchKernelGGL(k_ring_residue, dim3(nblocks(nring * 64, 256, 4096)), dim3(256), 0, c->stream, c->all_grid.d,
-                           c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)nring, d_c.p, d_r.p, d_d.p);
+                           c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)nring, d_c.p, (const int*)nullptr, d_r.p, d_d.p);
         rc = check_launch(c, "k_ring_residue");
         if (rc == ARP_OK) rc = download(c, out_ring_res, d_r.p, (size_t)nring);
         if (rc == ARP_OK && out_shortest) rc = download(c, out_shortest, d_d.p, (size_t)nring);
@@ -4057,16 +3770,8 @@ int arp_set_topology(arp_ctx* c, const void* blob, uint64_t bytes, const int32_t
     CHK(check_blob_header(c, h, bytes));
     const int64_t R = h.nring, A = h.namide;
     if ((R > 0 && (!ring_off || !ring_idx)) || (A > 0 && !amide_atoms)) FAIL(c, ARP_E_ARG, "arp_set_topology: ring or amide atoms missing");
-    if (R > 0) {
-        if (!csr_ok(ring_off, R)) FAIL(c, ARP_E_ARG, "arp_set_topology: ring offsets must start at 0 and never decrease");
-        for (int64_t r = 0; r < R; ++r)
-            if (ring_off[r + 1] - ring_off[r] < 3) FAIL(c, ARP_E_ARG, "arp_set_topology: a ring needs at least three atoms");
-        for (int64_t k = 0; k < ring_off[R]; ++k)
-            if (ring_idx[k] < 0 || ring_idx[k] >= h.n) FAIL(c, ARP_E_ARG, "arp_set_topology: ring atom index out of range");
-    }
-    for (int64_t k = 0; k < 4 * A; ++k)
-        if ((k & 3) != 3 && (amide_atoms[k] < 0 || amide_atoms[k] >= h.n))   // N, C, O are read; the fourth atom is not
-            FAIL(c, ARP_E_ARG, "arp_set_topology: amide atom index out of range");
+    CHK(check_ring_atoms(c, "arp_set_topology", R, ring_off, ring_idx, h.n));
+    CHK(check_amide_atoms(c, "arp_set_topology", A, amide_atoms, h.n));
     HIPCHK(c, hipSetDevice(c->device));
     CHK(join_upload_lists(c));
     c->has_topo = false;
@@ -4092,22 +3797,10 @@ int arp_set_models(arp_ctx* c, int64_t nmodel, const float* xyz, const double* h
         FAIL(c, ARP_E_ARG, "arp_set_models: F n, F nbond and 3 F nh must stay below 2^31");
     if ((t.n > 0 && !xyz) || (t.nh > 0 && !h_xyz)) FAIL(c, ARP_E_ARG, "arp_set_models: coordinates missing");
     const int64_t F = nmodel;
-    BlobSizes z;
-    if (!blob_sizes(F * t.n, F * t.nres, F * t.nbond, F * t.nh, F * t.nring, F * t.namide, z))
-        FAIL(c, ARP_E_ARG, "arp_set_models: counts out of range");
     arp_blob_header h;
-    memset(&h, 0, sizeof(h));
-    h.magic = ARP_BLOB_MAGIC;
-    h.n = F * t.n; h.nres = F * t.nres; h.nbond = F * t.nbond; h.nh = F * t.nh; h.nring = F * t.nring; h.namide = F * t.namide;
+    if (!blob_header(F * t.n, F * t.nres, F * t.nbond, F * t.nh, F * t.nring, F * t.namide, h))
+        FAIL(c, ARP_E_ARG, "arp_set_models: counts out of range");
     h.n_rad = t.n_rad;
-    h.bytes = arp_blob_size(h.n, h.nres, h.nbond, h.nh, h.nring, h.namide);
-    {
-        uint64_t off = align16(sizeof(arp_blob_header));
-        for (int k = 0; k < ARP_BLOB_ARRAYS; ++k) {
-            h.off[k] = off;
-            off = align16(off + z.esize[k] * z.count[k]);
-        }
-    }
     HIPCHK(c, hipSetDevice(c->device));
     CHK(join_upload_lists(c));
     // From here on the resident arrays are overwritten: a failure leaves no structure resident (the topology stays kept).
@@ -4128,31 +3821,38 @@ int arp_set_models(arp_ctx* c, int64_t nmodel, const float* xyz, const double* h
     const uint8_t* const tp = c->topo_dev.p;
     hipError_t e = hipSuccess;
     if (h.n > 0) e = hipMemcpyAsync(c->models_xyz.p, xyz, (size_t)(3 * h.n) * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && h.nh > 0) e = hipMemcpyAsync(d + h.off[11], h_xyz, (size_t)(3 * h.nh) * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && h.nh > 0)
+        e = hipMemcpyAsync(blob_at<double>(d, h, BLOB_H_XYZ), h_xyz, (size_t)(3 * h.nh) * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { c->err = std::string("arp_set_models: copy of the coordinates: ") + hipGetErrorString(e); return fail(ARP_E_HIP); }
     ModelsExpand E;
     E.F = (int)F; E.n = (int)t.n; E.nres = (int)t.nres; E.nbond = (int)t.nbond; E.nh = (int)t.nh; E.nring = (int)t.nring; E.namide = (int)t.namide;
-    E.xyz_in = c->models_xyz.p;
-    E.t_rad = (const double2*)(tp + t.off[1]); E.t_tmask = (const uint16_t*)(tp + t.off[2]); E.t_flags = (const uint16_t*)(tp + t.off[3]);
-    E.t_res_id = (const int*)(tp + t.off[4]); E.t_res_flags = tp + t.off[5]; E.t_res_prev = (const int*)(tp + t.off[6]);
-    E.t_res_next = (const int*)(tp + t.off[7]); E.t_bond_off = (const int*)(tp + t.off[8]); E.t_bond_idx = (const int*)(tp + t.off[9]);
-    E.t_h_off = (const int*)(tp + t.off[10]); E.t_sb_nbr = (const int*)(tp + t.off[12]); E.t_am_res = (const int*)(tp + t.off[18]);
-    E.t_rad_idx = (const uint16_t*)(tp + t.off[19]); E.t_rad_tab = (const double2*)(tp + t.off[20]);
-    E.xyz4 = (float4*)(d + h.off[0]); E.rad = (double2*)(d + h.off[1]); E.tmask = (uint16_t*)(d + h.off[2]); E.flags = (uint16_t*)(d + h.off[3]);
-    E.res_id = (int*)(d + h.off[4]); E.res_flags = d + h.off[5]; E.res_prev = (int*)(d + h.off[6]); E.res_next = (int*)(d + h.off[7]);
-    E.bond_off = (int*)(d + h.off[8]); E.bond_idx = (int*)(d + h.off[9]); E.h_off = (int*)(d + h.off[10]); E.sb_nbr = (int*)(d + h.off[12]);
-    E.ring_res = (int*)(d + h.off[15]); E.am_res = (int*)(d + h.off[18]); E.rad_idx = (uint16_t*)(d + h.off[19]); E.rad_tab = (double2*)(d + h.off[20]);
+    E.xyz_in = c->models_xyz.p;                             E.xyz4 = blob_at<float4>(d, h, BLOB_XYZ);
+    E.t_rad = blob_at<double2>(tp, t, BLOB_RAD);            E.rad = blob_at<double2>(d, h, BLOB_RAD);
+    E.t_tmask = blob_at<uint16_t>(tp, t, BLOB_TMASK);       E.tmask = blob_at<uint16_t>(d, h, BLOB_TMASK);
+    E.t_flags = blob_at<uint16_t>(tp, t, BLOB_FLAGS);       E.flags = blob_at<uint16_t>(d, h, BLOB_FLAGS);
+    E.t_rad_idx = blob_at<uint16_t>(tp, t, BLOB_RAD_IDX);   E.rad_idx = blob_at<uint16_t>(d, h, BLOB_RAD_IDX);
+    E.t_res_id = blob_at<int>(tp, t, BLOB_RES_ID);          E.res_id = blob_at<int>(d, h, BLOB_RES_ID);
+    E.t_res_flags = blob_at<uint8_t>(tp, t, BLOB_RES_FLAGS); E.res_flags = blob_at<uint8_t>(d, h, BLOB_RES_FLAGS);
+    E.t_res_prev = blob_at<int>(tp, t, BLOB_RES_PREV);      E.res_prev = blob_at<int>(d, h, BLOB_RES_PREV);
+    E.t_res_next = blob_at<int>(tp, t, BLOB_RES_NEXT);      E.res_next = blob_at<int>(d, h, BLOB_RES_NEXT);
+    E.t_bond_off = blob_at<int>(tp, t, BLOB_BOND_OFF);      E.bond_off = blob_at<int>(d, h, BLOB_BOND_OFF);
+    E.t_bond_idx = blob_at<int>(tp, t, BLOB_BOND_IDX);      E.bond_idx = blob_at<int>(d, h, BLOB_BOND_IDX);
+    E.t_h_off = blob_at<int>(tp, t, BLOB_H_OFF);            E.h_off = blob_at<int>(d, h, BLOB_H_OFF);
+    E.t_sb_nbr = blob_at<int>(tp, t, BLOB_SB_NBR);          E.sb_nbr = blob_at<int>(d, h, BLOB_SB_NBR);
+    E.t_am_res = blob_at<int>(tp, t, BLOB_AMIDE_RES);       E.am_res = blob_at<int>(d, h, BLOB_AMIDE_RES);
+    E.t_rad_tab = blob_at<double2>(tp, t, BLOB_RAD_TAB);    E.rad_tab = blob_at<double2>(d, h, BLOB_RAD_TAB);
+    E.ring_res = blob_at<int>(d, h, BLOB_RING_RES);         // (-1 until k_ring_residue below)
     const int64_t work = std::max({h.n + 1, h.nres, h.nbond, h.nring, h.namide, (int64_t)RAD_TABLE});
     hipLaunchKernelGGL(k_models_expand, dim3(nblocks(work, 256), MODELS_EXPAND_SEGMENTS), dim3(256), 0, c->stream, E);
     const float4* const xyz4 = E.xyz4;
-    double* const ring_c = (double*)(d + h.off[13]);
-    float* const am_c = (float*)(d + h.off[16]);
+    double* const ring_c = blob_at<double>(d, h, BLOB_RING_C);
+    float* const am_c = blob_at<float>(d, h, BLOB_AMIDE_C);
     if (h.nring > 0)
-        hipLaunchKernelGGL(k_models_ring_geometry, dim3(nblocks(h.nring, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.nring,
-                           c->topo_ring_off.p, c->topo_ring_idx.p, xyz4, ring_c, (double*)(d + h.off[14]));
+        hipLaunchKernelGGL(k_ring_geometry, dim3(nblocks(h.nring, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.nring,
+                           c->topo_ring_off.p, c->topo_ring_idx.p, xyz4, ring_c, blob_at<double>(d, h, BLOB_RING_N));
     if (h.namide > 0)
-        hipLaunchKernelGGL(k_models_amide_geometry, dim3(nblocks(h.namide, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.namide,
-                           c->topo_amide_atoms.p, xyz4, am_c, (float*)(d + h.off[17]));
+        hipLaunchKernelGGL(k_amide_geometry, dim3(nblocks(h.namide, 256)), dim3(256), 0, c->stream, (int)F, (int)t.n, (int)t.namide,
+                           c->topo_amide_atoms.p, xyz4, am_c, blob_at<float>(d, h, BLOB_AMIDE_N));
     hipLaunchKernelGGL(k_models_boxes, dim3((unsigned)F), dim3(256), 0, c->stream, (int)t.n, (int)t.nring, (int)t.namide, xyz4, ring_c, am_c,
                        c->models_box.p);
     int rc = check_launch(c, "k_models_expand / geometry / boxes");
@@ -4167,22 +3867,15 @@ int arp_set_models(arp_ctx* c, int64_t nmodel, const float* xyz, const double* h
     double* const hlo[3] = {h.lo, h.ring_lo, h.amide_lo};
     double* const hhi[3] = {h.hi, h.ring_hi, h.amide_hi};
     std::vector<double> pbox((size_t)(6 * F), 0.0);
-    bool finite = true;
+    bool finite = true, seen[3] = {false, false, false};
     for (int64_t f = 0; f < F; ++f) {
         bool any = false;
         for (int q = 0; q < 3; ++q) {
             if (cnt[q] == 0) continue;
-            for (int k = 0; k < 3; ++k) {
-                const double lo = box[(size_t)(18 * f + 6 * q + k)], hi = box[(size_t)(18 * f + 6 * q + 3 + k)];
-                finite = finite && std::isfinite(lo) && std::isfinite(hi);
-                hlo[q][k] = f == 0 ? lo : std::min(hlo[q][k], lo);
-                hhi[q][k] = f == 0 ? hi : std::max(hhi[q][k], hi);
-                double& plo = pbox[(size_t)(6 * f + k)];
-                double& phi = pbox[(size_t)(6 * f + 3 + k)];
-                plo = any ? std::min(plo, lo) : lo;
-                phi = any ? std::max(phi, hi) : hi;
-            }
-            any = true;
+            const double* b = &box[(size_t)(18 * f + 6 * q)];       // lo xyz, hi xyz
+            for (int k = 0; k < 6; ++k) finite = finite && std::isfinite(b[k]);
+            box_union(hlo[q], hhi[q], seen[q], b, b + 3);
+            box_union(&pbox[(size_t)(6 * f)], &pbox[(size_t)(6 * f + 3)], any, b, b + 3);
         }
     }
     if (!finite)   // a model with a non-finite coordinate: the validation below reports it (no atom lies in an empty box)
@@ -4198,9 +3891,10 @@ int arp_set_models(arp_ctx* c, int64_t nmodel, const float* xyz, const double* h
     if (h.nring > 0 && h.n > 0) {     // I:1453-1492 per model, on the all-atom grid of the partition (no atoms: every ring keeps -1)
         rc = build_all_grid(c, 6.0);
         if (rc == ARP_OK) {
-            hipLaunchKernelGGL(k_models_ring_residue, dim3(nblocks(h.nring * 64, 256, 4096)), dim3(256), 0, c->stream, c->all_grid.d,
-                               c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)h.nring, c->ring_c.p, c->ring_res.p);
-            rc = check_launch(c, "k_models_ring_residue");
+            hipLaunchKernelGGL(k_ring_residue, dim3(nblocks(h.nring * 64, 256, 4096)), dim3(256), 0, c->stream, c->all_grid.d,
+                               c->all_grid.start.p, c->a_xyzm.p, c->a_aux.p, (int)h.nring, c->ring_c.p, c->all_grid.d.sid_ring, c->ring_res.p,
+                               (double*)nullptr);
+            rc = check_launch(c, "k_ring_residue");
         }
         if (rc != ARP_OK) return fail(rc);
     }

@@ -1,11 +1,10 @@
 // arp_models.h — F models (coordinate sets) of ONE topology, resident as a batch partition with one structure per model
 // (arp_set_topology / arp_set_models).  The reference keeps the first model only (P:67-69: del st[1:]); here every model
 // is evaluated in one pass, each with exactly the arithmetic of its own single-structure run:
-//   k_models_expand          the F copies of the kept topology blob, indices shifted by the model's offsets
-//   k_models_ring_geometry   _perceive_rings per (model, ring)                   interactions.py:1697-1733
-//   k_models_amide_geometry  _perceive_amide_groups per (model, amide)          interactions.py:1531-1589
-//   k_models_boxes           bounding boxes per model (blob header, batch partition)
-//   k_models_ring_residue    _assign_aromatic_rings_to_residues per model      interactions.py:1453-1492
+//   k_models_expand   the F copies of the kept topology blob, indices shifted by the model's offsets
+//   k_models_boxes    bounding boxes per model (blob header, batch partition)
+// Ring and amide geometry per (model, ring / amide) and the ring residues per model are the kernels of arp_prepare.h, which take
+// the model count and the models' places; their arithmetic is written there only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,7 +53,7 @@ struct ModelsExpand {
 __device__ __forceinline__ int shift_index(int v, int by) { return v >= 0 ? v + by : v; }   // (-1 = none stays -1)
 
 // One grid-stride launch; blockIdx.y picks the segment: 0 per-atom arrays (F n items), 1 per-residue (F nres), 2 bonds
-// (F nbond), 3 rings (F nring: residue -1 until k_models_ring_residue), 4 amides (F namide), 5 the radius table.  The
+// (F nbond), 3 rings (F nring: residue -1 until k_ring_residue), 4 amides (F namide), 5 the radius table.  The
 // coordinates go out as one 16-byte float4 per atom (w = 0, as arp_blob_fill writes them) and the radius pairs as one
 // 16-byte double2; the narrower per-atom columns start at model offsets f n that are not multiples of four, so they move
 // element by element.  The models' hydrogen coordinates are no part of this: they are copied into the blob as they came.
@@ -103,74 +102,6 @@ __global__ __launch_bounds__(256) void k_models_expand(ModelsExpand E) {
         }
     } else {
         for (int k = t0; k < RAD_TABLE; k += stride) E.rad_tab[k] = E.t_rad_tab[k];
-    }
-}
-
-// The bodies of k_ring_geometry and k_amide_geometry (arp_prepare.h: see there for the reference's arithmetic), restated for
-// one item.  They are copies, not shared: with the bodies moved into functions both kernels call, the code of the two
-// existing kernels changes, and their code is part of what a change here must leave alone.
-__device__ __forceinline__ void model_ring_geometry(int a0, int na, const int* __restrict__ idx, const float4* __restrict__ xyz,
-                                                    double* __restrict__ center, double* __restrict__ normal, size_t r) {
-    double cx = 0, cy = 0, cz = 0;
-    for (int j = 0; j < na; ++j) {
-        const float4 v = xyz[idx[a0 + j]];
-        cx += (double)v.x; cy += (double)v.y; cz += (double)v.z;
-    }
-    const double inv_n = 1.0 / (double)na;
-    cx *= inv_n; cy *= inv_n; cz *= inv_n;
-    double nx = 0, ny = 0, nz = 0;
-    for (int j = 0; j < na; ++j) {
-        const float4 p = xyz[idx[a0 + j]], q = xyz[idx[a0 + ((j + 1 == na) ? 0 : j + 1)]];
-        const double ax = (double)p.x - cx, ay = (double)p.y - cy, az = (double)p.z - cz;
-        const double bx = (double)q.x - cx, by = (double)q.y - cy, bz = (double)q.z - cz;
-        nx += ay * bz - az * by;
-        ny += az * bx - ax * bz;
-        nz += ax * by - ay * bx;
-    }
-    nx *= inv_n; ny *= inv_n; nz *= inv_n;
-    const double l = sqrt(nx * nx + ny * ny + nz * nz);
-    if (!(fabs(l) < 2e-6)) {
-        const double inv_l = 1.0 / l;
-        nx *= inv_l; ny *= inv_l; nz *= inv_l;
-    }
-    center[3 * r] = cx; center[3 * r + 1] = cy; center[3 * r + 2] = cz;
-    normal[3 * r] = nx; normal[3 * r + 1] = ny; normal[3 * r + 2] = nz;
-}
-__device__ __forceinline__ void model_amide_geometry(int iN, int iC, int iO, const float4* __restrict__ xyz, float* __restrict__ center,
-                                                     float* __restrict__ normal, size_t a) {
-    const float4 N = xyz[iN], Cc = xyz[iC], O = xyz[iO];
-    center[3 * a] = (Cc.x + N.x) / 2.0f;
-    center[3 * a + 1] = (Cc.y + N.y) / 2.0f;
-    center[3 * a + 2] = (Cc.z + N.z) / 2.0f;
-    const double mx = ((double)Cc.x + O.x + N.x) / 3.0, my = ((double)Cc.y + O.y + N.y) / 3.0, mz = ((double)Cc.z + O.z + N.z) / 3.0;
-    const double ux = Cc.x - mx, uy = Cc.y - my, uz = Cc.z - mz;
-    const double vx = O.x - mx, vy = O.y - my, vz = O.z - mz;
-    double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
-    const double l = sqrt(nx * nx + ny * ny + nz * nz);
-    if (l > 0) { nx /= l; ny /= l; nz /= l; }
-    normal[3 * a] = (float)nx; normal[3 * a + 1] = (float)ny; normal[3 * a + 2] = (float)nz;
-}
-
-// Ring (model f, ring r) = item f nring + r: the topology's ring path over model f's atoms [f n, (f + 1) n).
-__global__ __launch_bounds__(256) void k_models_ring_geometry(int F, int n, int nring, const int* __restrict__ off,
-                                                              const int* __restrict__ idx, const float4* __restrict__ xyz,
-                                                              double* __restrict__ center, double* __restrict__ normal) {
-    const int total = F * nring;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
-        const int f = k / nring, r = k - f * nring;
-        model_ring_geometry(off[r], off[r + 1] - off[r], idx, xyz + (size_t)f * n, center, normal, (size_t)k);
-    }
-}
-
-// Amide (model f, amide a) = item f namide + a: atoms N, C, O of the topology in model f.
-__global__ __launch_bounds__(256) void k_models_amide_geometry(int F, int n, int namide, const int* __restrict__ atoms,
-                                                               const float4* __restrict__ xyz, float* __restrict__ center,
-                                                               float* __restrict__ normal) {
-    const int total = F * namide;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
-        const int f = k / namide, a = k - f * namide;
-        const int base = f * n;
-        model_amide_geometry(base + atoms[4 * a], base + atoms[4 * a + 1], base + atoms[4 * a + 2], xyz, center, normal, (size_t)k);
     }
 }
 
@@ -223,42 +154,5 @@ __global__ __launch_bounds__(256) void k_models_boxes(int n, int nring, int nami
         double r = s_v[0][q];
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = (q % 6) < 3 ? lo_keep_nan(r, s_v[w][q]) : hi_keep_nan(r, s_v[w][q]);
         out[18 * (size_t)f + q] = r;
-    }
-}
-
-// k_ring_residue over a grid that holds the F models apart (the all-atom 6 A grid built under the model partition): the
-// centre's cells are looked up in its own model's place (sid_ring, as the ring loops do, arp_planes.h), so only that model's
-// atoms are candidates.  The atoms' local ids and residues are the resident (model-shifted) ones; within a model they keep
-// the topology's order, so the lowest id still wins a tie.
-__global__ __launch_bounds__(256) void k_models_ring_residue(GridDesc g, const int* __restrict__ start, const float4* __restrict__ s_xyzm,
-                                                             const int4* __restrict__ s_aux, int nring, const double* __restrict__ ring_c,
-                                                             int* __restrict__ ring_res) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwave = (gridDim.x * blockDim.x) >> 6;
-    for (int r = wave; r < nring; r += nwave) {
-        const num::d3 ctr_ = ld3(ring_c, r);
-        const Stencil st = stencil_load(g, start, cell_box(g, ctr_, g.place ? g.sid_ring[r] : 0), lane);
-        double best = 1e300;
-        int best_lid = 0x7FFFFFFF, best_res = -1;
-        for (int kb = 0; kb < st.pre[9]; kb += 64) {
-            const int k = kb + lane;
-            if (k < st.pre[9]) {
-                const int j = stencil_pos(st, k);
-                const float4 v = s_xyzm[j];
-                const num::d3 x = {(double)v.x, (double)v.y, (double)v.z};
-                if (num::dist2_kd(ctr_, x) <= 9.0) {
-                    const double d = num::norm(num::sub(x, ctr_));
-                    const int4 a = s_aux[j];
-                    if (d < best || (d == best && a.x < best_lid)) { best = d; best_lid = a.x; best_res = a.y; }
-                }
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const double od = __shfl_xor(best, o);
-            const int ol = __shfl_xor(best_lid, o), orr = __shfl_xor(best_res, o);
-            if (od < best || (od == best && ol < best_lid)) { best = od; best_lid = ol; best_res = orr; }
-        }
-        if (lane == 0) ring_res[r] = best_res;
     }
 }

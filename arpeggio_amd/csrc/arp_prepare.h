@@ -15,10 +15,15 @@
 // source): centre = mean of the ring atoms' vectors; normal = sum over consecutive atoms of (v_j - centre) x
 // (v_j+1 - centre), divided by the ring size, then normalised (left alone when its length is ~0).  All float64 on the
 // float32 atom coordinates (OpenBabel holds its own float64 copy parsed from the same file text).
-__global__ __launch_bounds__(256) void k_ring_geometry(int nring, const int* __restrict__ off, const int* __restrict__ idx,
-                                                       const float4* __restrict__ xyz, double* __restrict__ center,
+// F models of n atoms each share the topology's nring ring paths (off / idx): item k = f nring + r is ring r over model f's
+// atoms [f n, (f + 1) n).  One structure is F = 1.
+__global__ __launch_bounds__(256) void k_ring_geometry(int F, int n, int nring, const int* __restrict__ off, const int* __restrict__ idx,
+                                                       const float4* __restrict__ xyz_all, double* __restrict__ center,
                                                        double* __restrict__ normal) {
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < nring; r += gridDim.x * blockDim.x) {
+    const int total = F * nring;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
+        const int f = k / nring, r = k - f * nring;
+        const float4* __restrict__ xyz = xyz_all + (size_t)f * n;
         const int a0 = off[r], na = off[r + 1] - a0;
         double cx = 0, cy = 0, cz = 0;
         for (int j = 0; j < na; ++j) {
@@ -42,8 +47,8 @@ __global__ __launch_bounds__(256) void k_ring_geometry(int nring, const int* __r
             const double inv_l = 1.0 / l;
             nx *= inv_l; ny *= inv_l; nz *= inv_l;
         }
-        center[3 * (size_t)r] = cx; center[3 * (size_t)r + 1] = cy; center[3 * (size_t)r + 2] = cz;
-        normal[3 * (size_t)r] = nx; normal[3 * (size_t)r + 1] = ny; normal[3 * (size_t)r + 2] = nz;
+        center[3 * (size_t)k] = cx; center[3 * (size_t)k + 1] = cy; center[3 * (size_t)k + 2] = cz;
+        normal[3 * (size_t)k] = nx; normal[3 * (size_t)k + 1] = ny; normal[3 * (size_t)k + 2] = nz;
     }
 }
 
@@ -52,13 +57,18 @@ __global__ __launch_bounds__(256) void k_ring_geometry(int nring, const int* __r
 // always lie in a plane: that vector is the unit normal of the plane, i.e. the normalised cross product of two
 // centred rows; the sign LAPACK happens to return is not reproduced (every consumer folds the angle, U:656-660), and
 // the last bits differ from an SVD's (agreement ~1e-6 in the components, tested against numpy).
-__global__ __launch_bounds__(256) void k_amide_geometry(int namide, const int* __restrict__ atoms, const float4* __restrict__ xyz,
-                                                        float* __restrict__ center, float* __restrict__ normal) {
-    for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < namide; a += gridDim.x * blockDim.x) {
+// Models as in k_ring_geometry: item k = f namide + a is amide a of the topology over model f's atoms.
+__global__ __launch_bounds__(256) void k_amide_geometry(int F, int n, int namide, const int* __restrict__ atoms,
+                                                        const float4* __restrict__ xyz_all, float* __restrict__ center,
+                                                        float* __restrict__ normal) {
+    const int total = F * namide;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < total; k += gridDim.x * blockDim.x) {
+        const int f = k / namide, a = k - f * namide;
+        const float4* __restrict__ xyz = xyz_all + (size_t)f * n;
         const float4 N = xyz[atoms[4 * a]], Cc = xyz[atoms[4 * a + 1]], O = xyz[atoms[4 * a + 2]];
-        center[3 * (size_t)a] = (Cc.x + N.x) / 2.0f;
-        center[3 * (size_t)a + 1] = (Cc.y + N.y) / 2.0f;
-        center[3 * (size_t)a + 2] = (Cc.z + N.z) / 2.0f;
+        center[3 * (size_t)k] = (Cc.x + N.x) / 2.0f;
+        center[3 * (size_t)k + 1] = (Cc.y + N.y) / 2.0f;
+        center[3 * (size_t)k + 2] = (Cc.z + N.z) / 2.0f;
         // centred rows (amide centroid = mean of C, O, N, I:1568) in float64 for a well-conditioned cross product
         const double mx = ((double)Cc.x + O.x + N.x) / 3.0, my = ((double)Cc.y + O.y + N.y) / 3.0, mz = ((double)Cc.z + O.z + N.z) / 3.0;
         const double ux = Cc.x - mx, uy = Cc.y - my, uz = Cc.z - mz;
@@ -66,7 +76,7 @@ __global__ __launch_bounds__(256) void k_amide_geometry(int namide, const int* _
         double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
         const double l = sqrt(nx * nx + ny * ny + nz * nz);
         if (l > 0) { nx /= l; ny /= l; nz /= l; }
-        normal[3 * (size_t)a] = (float)nx; normal[3 * (size_t)a + 1] = (float)ny; normal[3 * (size_t)a + 2] = (float)nz;
+        normal[3 * (size_t)k] = (float)nx; normal[3 * (size_t)k + 1] = (float)ny; normal[3 * (size_t)k + 2] = (float)nz;
     }
 }
 
@@ -75,15 +85,20 @@ __global__ __launch_bounds__(256) void k_amide_geometry(int namide, const int* _
 // np.linalg.norm(atom.coord - centre) (float64, I:1471); strict '<' keeps the first of equal distances, which in the
 // reference is the KD-tree's delivery order — here the lowest packed atom index.  ring_res = residue of that atom,
 // -1 when no atom is that close (I:1476-1479).
+// sid = the structure of each centre when the grid holds a batch partition (the F models of arp_set_models: g.sid_ring): the
+// centre's cells are looked up in its own structure's place, as the ring loops do (arp_planes.h), so only that structure's atoms
+// are candidates; their local ids keep the order they have within it, so the lowest id still wins a tie.  Null (centres given by
+// the caller, arp_ring_residues): the cells of the whole grid, no structure's place.  ring_dist may be null.
 __global__ __launch_bounds__(256) void k_ring_residue(GridDesc g, const int* __restrict__ start, const float4* __restrict__ s_xyzm,
                                                       const int4* __restrict__ s_aux, int nring, const double* __restrict__ ring_c,
-                                                      int* __restrict__ ring_res, double* __restrict__ ring_dist) {
+                                                      const int* __restrict__ sid, int* __restrict__ ring_res,
+                                                      double* __restrict__ ring_dist) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwave = (gridDim.x * blockDim.x) >> 6;
     for (int r = wave; r < nring; r += nwave) {
         const num::d3 ctr_ = ld3(ring_c, r);
-        const Stencil st = stencil_load(g, start, cell_box(g, ctr_), lane);
+        const Stencil st = stencil_load(g, start, (sid && g.place) ? cell_box(g, ctr_, sid[r]) : cell_box(g, ctr_), lane);
         double best = 1e300;
         int best_lid = 0x7FFFFFFF, best_res = -1;
         for (int kb = 0; kb < st.pre[9]; kb += 64) {

@@ -174,6 +174,7 @@ int arp_set_amides(arp_ctx* ctx, int64_t namide, const float* center,
  *   8 bond_off  int32[n+1]  CSR (I:750)                            19 rad_idx   uint16[n]  index into rad_tab, 0xFFFF = not in it
  *   9 bond_idx  int32[nbond]                                       20 rad_tab   double[2 * 256]  distinct {vdw, cov} pairs
  *  10 h_off     int32[n+1]  CSR (I:1513-1529)
+ * (inside the library the arrays go by name: enum BlobArray, csrc/arp_blob.h, in this order, with their sizes in one table)
  * lo/hi, ring_lo/hi, amide_lo/hi = bounding boxes of the atom coordinates / ring centres / amide centres (the grids are
  * sized from them; arp_set_blob verifies that every point lies inside).  n_rad = entries of rad_tab in use.
  * rad[i] MUST equal rad_tab[rad_idx[i]] bit for bit wherever rad_idx[i] != 0xFFFF (arp_blob_fill writes them so): from
