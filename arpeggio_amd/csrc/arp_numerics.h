@@ -92,6 +92,37 @@ __device__ __forceinline__ double get_angle_mixed(f3 a, f3 b, d3 c) {
     return ang;
 }
 
+// The cosines get_angle / get_angle_mixed hand to acos: the same operation sequences, without the acos.
+// A DECISION at a threshold angle must not hang on the last bit of an acos implementation (the device library's differs from
+// glibc's and NumPy's there: one weak hydrogen bond in 2 688 seam cases of tests/test_sift_edges.py), so inside the bands the
+// reference's cosine is compared with the last double whose arccosine still passes — constants found by bisection on glibc's
+// acos and NumPy's arccos, which agree on all four (tests/test_sift_edges.py pins them against both).
+__device__ __forceinline__ double cos_angle(d3 a, d3 b, d3 c) {
+    d3 v1 = sub(a, b), v2 = sub(c, b);
+    double m1 = sqrt(v1.x * v1.x + v1.y * v1.y + v1.z * v1.z);
+    d3 n1 = {v1.x / m1, v1.y / m1, v1.z / m1};
+    double m2 = sqrt(v2.x * v2.x + v2.y * v2.y + v2.z * v2.z);
+    d3 n2 = {v2.x / m2, v2.y / m2, v2.z / m2};
+    return n1.x * n2.x + n1.y * n2.y + n1.z * n2.z;
+}
+__device__ __forceinline__ double cos_angle_mixed(f3 a, f3 b, d3 c) {
+    f3 v1 = sub(a, b);
+    d3 v2 = sub(c, to_d3(b));
+    float m1 = sqrtf(v1.x * v1.x + v1.y * v1.y + v1.z * v1.z);
+    f3 n1 = {v1.x / m1, v1.y / m1, v1.z / m1};
+    double m2 = sqrt(v2.x * v2.x + v2.y * v2.y + v2.z * v2.z);
+    d3 n2 = {v2.x / m2, v2.y / m2, v2.z / m2};
+    return (double)n1.x * n2.x + (double)n1.y * n2.y + (double)n1.z * n2.z;
+}
+#define ARP_COS_LAST_GE_1_57 0x1.a181296fadffap-11      // the largest double c with acos(c) >= 1.57
+#define ARP_COS_LAST_GE_2_27 (-0x1.49870aeb9c1fep-1)    //                                    >= 2.27
+#define ARP_COS_LAST_GE_0_52 0x1.bc52cba71d363p-1       //                                    >= 0.52
+#define ARP_COS_FIRST_LE_2_62 (-0x1.bbeaed2abc536p-1)   // the smallest double c with acos(c) <= 2.62
+// acos(res) >= a_min as the reference decides it, NaN -> pi included (|res| > 1 or NaN passes); cos_last = the constant of a_min
+__device__ __forceinline__ bool angle_ge_exact(double res, double cos_last) { return !(res > cos_last && res <= 1.0); }
+// 0.52 <= acos(res) <= 2.62 (NaN -> pi fails the upper bound)
+__device__ __forceinline__ bool angle_in_exact(double res) { return res <= ARP_COS_LAST_GE_0_52 && res >= ARP_COS_FIRST_LE_2_62; }
+
 // ---- decision shortcuts ---------------------------------------------------------------------------
 // The reference decides "angle >= a_min" via normalise / dot / acos (2 sqrt, 6 divisions and an acos
 // per hydrogen).  cosA = (v1.v2) / sqrt(|v1|^2 |v2|^2) is the same quantity up to ~1e-15 (1e-7 when one

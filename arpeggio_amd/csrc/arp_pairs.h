@@ -1400,9 +1400,10 @@ __device__ __forceinline__ num::f3 xyz_of(float4 v) { return {v.x, v.y, v.z}; }
 
 // utils.is_hbond (utils.py:73-93, angle_min 1.57) / is_weak_hbond (utils.py:96-116, 2.27).
 // cos_min = cos(angle_min).  Decisions away from a threshold use the squared-quantity shortcuts of
-// arp_numerics.h; inside the safety margins the reference's exact operation sequence decides.
+// arp_numerics.h; inside the safety margins the reference's exact operation sequence makes the cosine, which is
+// compared with cos_last, the last double whose arccosine is still >= angle_min (no acos on the device).
 __device__ __forceinline__ bool hbond_like(num::f3 donor, const double* __restrict__ hx, int h0, int h1, num::f3 acc,
-                                           double acc_vdw, double comp, double angle_min, double cos_min) {
+                                           double acc_vdw, double comp, double cos_min, double cos_last) {
     const num::d3 d = num::to_d3(donor), a = num::to_d3(acc);
     const double thr = 1.2 + acc_vdw + comp;  // config.VDW_RADII['H'] + vdw + comp
     const double thr2 = thr * thr;
@@ -1414,7 +1415,7 @@ __device__ __forceinline__ bool hbond_like(num::f3 donor, const double* __restri
         if (near < 0) near = (sqrt(s) <= thr) ? 1 : 0;         // h_dist <= thr, exact
         if (!near) continue;
         int ok = num::angle_ge_fast(d, h, a, cos_min, 1e-12);
-        if (ok < 0) ok = (num::get_angle(d, h, a) >= angle_min) ? 1 : 0;
+        if (ok < 0) ok = num::angle_ge_exact(num::cos_angle(d, h, a), cos_last) ? 1 : 0;
         if (ok) return true;
     }
     return false;
@@ -1437,10 +1438,7 @@ __device__ __forceinline__ bool halogen_weak(num::f3 hal, float4 sbh, double hal
         if (!near) continue;
         // the reference normalises (nbr - hal) in float32 (utils.py:151): 1e-5 covers that rounding
         int ok = num::angle_in_fast(num::to_d3(nbr), hd, h, ARP_COS_0_52, ARP_COS_2_62, 1e-5);
-        if (ok < 0) {
-            const double ang = num::get_angle_mixed(nbr, hal, h);
-            ok = (0.52 <= ang && ang <= 2.62) ? 1 : 0;
-        }
+        if (ok < 0) ok = num::angle_in_exact(num::cos_angle_mixed(nbr, hal, h)) ? 1 : 0;
         if (ok) return true;
     }
     return false;
@@ -1539,10 +1537,10 @@ __device__ __forceinline__ uint32_t sift_geometry(const GeoAtom& B, const GeoAto
         bool r;
         if (kind < 4) {
             const bool donor_b = (kind == 0) || (kind == 3);
-            const double amin = (kind < 2) ? 1.57 : 2.27;
+            const double clast = (kind < 2) ? ARP_COS_LAST_GE_1_57 : ARP_COS_LAST_GE_2_27;
             const double cmin = (kind < 2) ? ARP_COS_1_57 : ARP_COS_2_27;
             r = hbond_like(donor_b ? xb : xe, h_xyz, donor_b ? hb0 : he0, donor_b ? hb1 : he1, donor_b ? xe : xb,
-                           donor_b ? ve : vb, comp, amin, cmin);
+                           donor_b ? ve : vb, comp, cmin, clast);
         } else {
             const bool hal_b = kind == 4;
             const float4 sbh = sd.sb[hal_b ? B.lid : E.lid];   // w = 1 when the halogen has a single-bond neighbour
