@@ -36,7 +36,16 @@ SYMBOLS = (
     'arp_shard_assemble', 'arp_shard_layout', 'arp_get_blob', 'arp_cif_open', 'arp_cif_close', 'arp_cif_rows', 'arp_cif_cols',
     'arp_cif_blocks', 'arp_cif_tag', 'arp_cif_text', 'arp_cif_column', 'arp_cif_column_f64', 'arp_cif_column_i64',
     'arp_atom_contacts_sort', 'arp_fetch_packed', 'arp_set_topology', 'arp_set_models', 'arp_models_planes',
+    'arp_models_persistence_launch', 'arp_models_persistence_fetch',
 )
+
+# the persistence table (arp_models_persistence_*): its columns, the SIFt bits counted per row, and ARP_PERSIST_STAGE_MAX
+PERSIST_BITS = 15
+PERSIST_STAGE_MAX = 0
+PERSIST_COLUMNS = (('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                   ('dist_min', np.float32), ('dist_max', np.float32), ('dist_sum', np.float64), ('bit_count', np.uint16),
+                   ('ctype_mask', np.uint8))
+_PERSIST_FETCH_ORDER = tuple(k for k, _ in PERSIST_COLUMNS)
 
 _lib = None
 
@@ -176,6 +185,8 @@ def load():
     L.arp_set_topology.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
     L.arp_set_models.argtypes = [vp, i64, vp, vp]
     L.arp_models_planes.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.arp_models_persistence_launch.argtypes = [vp, C.POINTER(i64)]
+    L.arp_models_persistence_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -669,6 +680,19 @@ class Context:
         self.run_launch(cutoff, vdw_comp, include_sequence_adjacent, expand_radius)
         bags, _ = self.fetch_packed()
         return split_models(bags, self._models)
+
+    def models_persistence(self):
+        """Contact persistence over the resident models of the last pass, reduced on the device (arp_models_persistence_*):
+        one row per distinct topology pair (a, b) in ascending (a, b).  Returns a dict of the ten columns ``PERSIST_COLUMNS``
+        (``bit_count`` as [U, 15]; see ``arpeggio_amd.persistence``).  Only the table is copied to the host; the bags of the
+        pass stay fetchable as before."""
+        n = C.c_int64(0)
+        self._check(self._L.arp_models_persistence_launch(self._h, C.byref(n)), 'arp_models_persistence_launch')
+        U = int(n.value)
+        t = {k: np.empty((U, PERSIST_BITS) if k == 'bit_count' else U, dt) for k, dt in PERSIST_COLUMNS}
+        self._check(self._L.arp_models_persistence_fetch(self._h, U, *(_p(t[k]) for k in _PERSIST_FETCH_ORDER), C.byref(n)),
+                    'arp_models_persistence_fetch')
+        return t
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

@@ -578,6 +578,8 @@ class EnsembleComplex:
                                  has_hydrogens=bool(np.any(self.pc.flags & config.F_HYDROGEN)) or self.pc.h_xyz.shape[0] > 0, ph=ph)
         self._set_arrays(xyz, h_xyz)
         self._results = None
+        self.persistence = None          # the table of run_persistence and the models it covers
+        self.persistence_models = 0
 
     @property
     def n_models(self):
@@ -632,11 +634,9 @@ class EnsembleComplex:
             self.planes = self._ctx.models_planes()
         self._results = None
 
-    def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
-        """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""
-        if self._ctx is None:
-            self.initialize()
-        pc, ctx, F, n = self.pc, self._ctx, self.n_models, self.pc.n_atoms
+    def _upload_selection(self, user_selections):
+        """The selectors, parsed once on the topology, select the same atoms in each model; returns their indices."""
+        pc, F, n = self.pc, self.n_models, self.pc.n_atoms
         if isinstance(user_selections, np.ndarray):
             idx = np.unique(user_selections.astype(np.int64))
         elif user_selections:
@@ -648,7 +648,37 @@ class EnsembleComplex:
             raise AttributeError('Selection must not be empty.')
         mask = np.zeros(n, np.uint8)
         mask[idx] = 1
-        ctx.set_selection(np.tile(mask, F))
+        self._ctx.set_selection(np.tile(mask, F))
+        return idx
+
+    def run_persistence(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, accumulate=False):
+        """Contact persistence over the models: the selection handling and the pass of ``run_arpeggio``, then the atom-atom
+        records of all models reduced ON THE DEVICE to one row per topology pair (``arpeggio_amd.persistence`` describes the
+        table) — and only that table fetched, into ``self.persistence`` (also returned).  No bag is copied to the host:
+        ``model(k)`` has no results after this call (``run_arpeggio`` gives those).  ``accumulate=True`` merges the table
+        into that of the calls before it, this call's models following theirs (``self.persistence_models`` counts them): a
+        trajectory streams through ``set_coordinates`` + ``run_persistence(..., accumulate=True)`` chunk by chunk."""
+        from .. import persistence as _persistence
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        t = self._ctx.models_persistence()
+        self._results = None
+        if accumulate and self.persistence is not None:
+            self.persistence = _persistence.merge(self.persistence, t, self.persistence_models)
+            self.persistence_models += self.n_models
+        else:
+            self.persistence, self.persistence_models = t, self.n_models
+        self.stats = self._ctx.stats()
+        return self.persistence
+
+    def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
+        """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx, F, n = self.pc, self._ctx, self.n_models, self.pc.n_atoms
+        idx = self._upload_selection(user_selections)
         per_model = ctx.run_models(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
         masks = ctx.make_selection_masks()
         R, A = pc.n_rings, pc.n_amides

@@ -27,6 +27,7 @@
 #include "arp_cif.h"
 #include "arp_comm.h"
 #include "arp_sort.h"
+#include "arp_persist.h"
 #include "arp_blob.h"
 
 namespace {
@@ -442,6 +443,15 @@ struct arp_ctx {
     DevBuf<float> models_xyz;
     DevBuf<double> models_box;
     int64_t models_n = 0;
+    // ---- contact persistence over the resident models (arp_persist.h; arp_models_persistence_launch / _fetch)
+    SortScratch sort_persist;             // the re-keyed records, double-buffered, and the digit tables of their sort
+    DevBuf<int> persist_tiles, persist_rows;
+    DevBuf<long long> persist_total;
+    DevBuf<uint8_t> persist_slab;         // the table's ten columns in one piece (persist_layout)
+    uint8_t* persist_stage = nullptr;     // page-locked host side of the one copy (its first word also receives U)
+    size_t persist_stage_cap = 0;
+    int64_t persist_count = 0;            // rows of the table
+    bool persist_valid = false;           // persist_slab holds the table of the last launch's results
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -662,7 +672,8 @@ enum : unsigned {
 //   tables go with it.  arp_set_batch records the new partition after this call.
 // selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
 //   with everything selected (I:1395) and no whole-structure assertion.
-// results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.
+// results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
+//   persistence table of the resident models (arp_models_persistence_launch) is made from the atom-atom bag and goes with it.
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -694,6 +705,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->models_n = 0;
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
+        c->persist_valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1822,6 +1834,7 @@ bool finish_contacts(arp_ctx* c) {
     c->contacts_expected = (int64_t)np;
     c->contacts_valid = true;
     c->contacts_sorted = false;
+    c->persist_valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2158,6 +2171,8 @@ void arp_destroy(arp_ctx* c) {
     c->bag_ap.release(); c->bag_pp.release(); c->bag_gg.release(); c->bag_gp.release();
     c->bag_pack.release(); c->bag_perm.release();
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
+    c->sort_persist.release(); c->persist_tiles.release(); c->persist_rows.release(); c->persist_total.release(); c->persist_slab.release();
+    if (c->persist_stage) (void)hipHostFree(c->persist_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
     c->rec_home.release(); c->rec_face[0].release(); c->rec_face[1].release(); c->sh_scan.release(); c->sh_src.release();
@@ -3918,6 +3933,135 @@ int arp_models_planes(arp_ctx* c, double* ring_center, double* ring_normal, int3
     const int64_t per = R / F, nres = c->nres / F;     // residues of the resident partition -> of the model
     for (int64_t k = 0; k < R; ++k)
         if (ring_res[k] >= 0) ring_res[k] -= (int32_t)((k / per) * nres);
+    return ARP_OK;
+}
+
+// ---- contact persistence over the resident models (arp_persist.h) ----------------------------------------------
+namespace {
+// Layout of the table's slab: the ten columns one after the other, each on a 256-byte boundary (the float64 column first).
+enum { PT_DSUM = 0, PT_A, PT_B, PT_FIRST, PT_LAST, PT_DMIN, PT_DMAX, PT_NMODELS, PT_BITS, PT_CTYPE, PT_COLS };
+void persist_layout(size_t U, size_t off[PT_COLS], size_t* bytes) {
+    static const size_t es[PT_COLS] = {8, 4, 4, 4, 4, 4, 4, 2, 2 * PERSIST_BITS, 1};
+    size_t at = 0;
+    for (int q = 0; q < PT_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
+    *bytes = at;
+}
+int persist_stage_reserve(arp_ctx* c, size_t bytes) {
+    if (c->persist_stage && c->persist_stage_cap >= bytes) return ARP_OK;
+    if (c->persist_stage) (void)hipHostFree(c->persist_stage);
+    c->persist_stage = nullptr;
+    c->persist_stage_cap = 0;
+    const size_t want = std::max(bytes + bytes / 4, (size_t)4096);
+    HIPCHK(c, hipHostMalloc((void**)&c->persist_stage, want, hipHostMallocDefault));
+    c->persist_stage_cap = want;
+    return ARP_OK;
+}
+}  // namespace
+
+int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: not for a shard of a distributed structure");
+    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: no models resident (arp_set_models)");
+    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: no results of a pass over the resident models (launch one first)");
+    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: more than 65 535 models (the table counts models in uint16)");
+    if (c->persist_valid) { *count = c->persist_count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)c->n_contacts;
+    const int64_t F = c->models_n, n = c->topo_hdr.n;
+    c->persist_count = 0;
+    if (k == 0 || n <= 0) { c->persist_valid = true; *count = 0; return ARP_OK; }
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: 2^31 records or more");
+    PersistArgs A{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k;
+    A.n = (uint32_t)n;
+    const int abits = id_bits(std::max<int64_t>(n - 1, 1));
+    A.bbits = abits;
+    A.fbits = id_bits(std::max<int64_t>(F - 1, 1));
+    const int keybits = abits + A.bbits + A.fbits;
+    if (keybits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: (atom, atom, model) does not fit a 63-bit key");
+    // ---- scratch: sized from the capacity of the bag's columns, so that it is allocated once per structure size
+    SortScratch& s = c->sort_persist;
+    const size_t cap = std::max(k, c->out_i.cap);
+    for (int q = 0; q < 2; ++q) { HIPCHK(c, s.key[q].reserve(cap)); HIPCHK(c, s.val[q].reserve(cap)); }
+    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
+    const int tstride = (int)((tiles + 3) & ~3ll);
+    HIPCHK(c, s.table.reserve((size_t)SORT_BINS * (size_t)tstride));
+    HIPCHK(c, s.total.reserve(SORT_BINS));
+    A.T = (int)(((long long)k + PERSIST_TILE - 1) / PERSIST_TILE);
+    HIPCHK(c, c->persist_tiles.reserve((size_t)A.T));
+    HIPCHK(c, c->persist_total.reserve(1));
+    CHK(persist_stage_reserve(c, 4096));
+    A.tile_rows = c->persist_tiles.p;
+    A.total = c->persist_total.p;
+    // ---- (a, b, f) keys, sorted by every bit: least significant digit first
+    A.key = s.key[0].p; A.val = s.val[0].p;
+    hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, A);
+    const int passes = (keybits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
+    SortArgs S{};
+    S.n = (long long)k; S.T = (int)tiles; S.tstride = tstride; S.table = s.table.p; S.total = s.total.p;
+    S.first = 0; S.last = 0; S.jbits = 0;
+    int shift = 0;
+    for (int ps = 0; ps < passes; ++ps) {
+        S.shift = shift;
+        S.bits = keybits / passes + (ps < keybits % passes ? 1 : 0);
+        shift += S.bits;
+        S.key_in = s.key[ps & 1].p; S.val_in = s.val[ps & 1].p;
+        S.key_out = s.key[(ps + 1) & 1].p; S.val_out = s.val[(ps + 1) & 1].p;
+        hipLaunchKernelGGL(k_sort_hist, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
+        hipLaunchKernelGGL(k_sort_scan, dim3(1 << S.bits), dim3(SORT_THREADS), 0, c->stream, S);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
+    }
+    A.key = s.key[passes & 1].p; A.val = s.val[passes & 1].p;
+    // ---- rows: count, scan; the host learns U (the one wait)
+    hipLaunchKernelGGL(k_persist_count, dim3(A.T), dim3(PERSIST_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_persist_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, "arp_models_persistence_launch: sort / count"));
+    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    long long U = 0;
+    memcpy(&U, c->persist_stage, sizeof(U));
+    if (U < 1 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_models_persistence_launch: row count out of range");
+    // ---- the table: row starts, one wave per row
+    size_t off[PT_COLS], bytes;
+    persist_layout((size_t)U, off, &bytes);
+    HIPCHK(c, c->persist_rows.reserve((size_t)U + 1));
+    HIPCHK(c, c->persist_slab.reserve(bytes));
+    uint8_t* const slab = c->persist_slab.p;
+    A.U = U;
+    A.row_start = c->persist_rows.p;
+    A.t_dsum = (double*)(slab + off[PT_DSUM]); A.t_a = (int*)(slab + off[PT_A]); A.t_b = (int*)(slab + off[PT_B]);
+    A.t_first = (int*)(slab + off[PT_FIRST]); A.t_last = (int*)(slab + off[PT_LAST]);
+    A.t_dmin = (float*)(slab + off[PT_DMIN]); A.t_dmax = (float*)(slab + off[PT_DMAX]);
+    A.t_nmodels = (uint16_t*)(slab + off[PT_NMODELS]); A.t_bits = (uint16_t*)(slab + off[PT_BITS]); A.t_ctype = slab + off[PT_CTYPE];
+    hipLaunchKernelGGL(k_persist_starts, dim3(A.T), dim3(PERSIST_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+    CHK(check_launch(c, "arp_models_persistence_launch: reduce"));
+    c->persist_count = U;
+    c->persist_valid = true;
+    *count = U;
+    return ARP_OK;
+}
+
+int arp_models_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
+                                 float* dist_min, float* dist_max, double* dist_sum, uint16_t* bit_count, uint8_t* ctype_mask, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (!c->contacts_valid || !c->persist_valid) FAIL(c, ARP_E_ARG, "arp_models_persistence_fetch: no table (arp_models_persistence_launch after a pass)");
+    *count = c->persist_count;
+    if (c->persist_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_fetch: output buffers too small");
+    const size_t U = (size_t)c->persist_count;
+    if (U == 0) return ARP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t off[PT_COLS], bytes;
+    persist_layout(U, off, &bytes);
+    CHK(persist_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint8_t* const h = c->persist_stage;
+    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
+    put(dist_sum, PT_DSUM, 8); put(a, PT_A, 4); put(b, PT_B, 4); put(first, PT_FIRST, 4); put(last, PT_LAST, 4);
+    put(dist_min, PT_DMIN, 4); put(dist_max, PT_DMAX, 4); put(n_models, PT_NMODELS, 2); put(bit_count, PT_BITS, 2 * PERSIST_BITS);
+    put(ctype_mask, PT_CTYPE, 1);
     return ARP_OK;
 }
 

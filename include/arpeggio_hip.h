@@ -540,6 +540,36 @@ int arp_set_topology(arp_ctx* ctx, const void* blob, uint64_t bytes, const int32
 int arp_set_models(arp_ctx* ctx, int64_t nmodel, const float* xyz, const double* h_xyz);
 int arp_models_planes(arp_ctx* ctx, double* ring_center, double* ring_normal, int32_t* ring_res, float* amide_center,
                       float* amide_normal);
+/* Contact persistence over the resident models: ONE table over the topology instead of F bags.  After a pass over F
+ * models (arp_set_models, then any launch that fills the atom-atom bag) the records of all models are regrouped on the
+ * device into one row per distinct topology pair (a, b), a < b, rows in ascending (a, b):
+ *   a, b                int32     topology atom ids
+ *   n_models            uint16    models in which the pair has a record
+ *   first, last         int32     lowest / highest 0-based model index with a record
+ *   dist_min, dist_max  float32   over those models, the records' own float32 distances
+ *   dist_sum            float64   those distances widened to float64 and added one by one in ascending model order,
+ *                                 starting from 0.0 (defined to the bit; the mean is dist_sum / n_models)
+ *   bit_count           uint16[ARP_PERSIST_BITS]  for SIFt bit k (ARP_S_CLASH ... ARP_S_WEAK_POLAR): models whose record has it
+ *   ctype_mask          uint8     OR of 1 << ARP_CT_* over the models
+ * Only the table crosses PCIe; the per-model bags stay what they were (arp_fetch_packed / arp_atom_contacts_fetch return
+ * the same before, after and without these calls, in either layout, with arp_set_sort_after_pass on or off).
+ *
+ * arp_models_persistence_launch: enqueues the reduction on the context's stream and waits once, for *count = rows.  The
+ * table is a result of the last launch and is voided with it (a new structure, models, selection or launch).  A second
+ * call on the same results does nothing and returns the same count.  ARP_E_ARG: no models resident, no results of a
+ * pass, more than 65 535 models (the uint16 columns), a shard.
+ *
+ * arp_models_persistence_fetch: the table with one device-to-host copy; any column pointer may be NULL; bit_count =
+ * uint16[cap][ARP_PERSIST_BITS].  ARP_E_CAPACITY with *count = rows when cap is too small; ARP_E_ARG without a launch.
+ *
+ * ARP_PERSIST_STAGE_MAX: records of one bgn atom (over all models) that the reduction can stage on chip before it takes
+ * a general path; 0 = the implementation has no such stage and no such limit (every atom takes the one path). */
+#define ARP_PERSIST_BITS 15
+#define ARP_PERSIST_STAGE_MAX 0
+int arp_models_persistence_launch(arp_ctx* ctx, int64_t* count);
+int arp_models_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first,
+                                 int32_t* last, float* dist_min, float* dist_max, double* dist_sum,
+                                 uint16_t* bit_count /* [cap][15] */, uint8_t* ctype_mask, int64_t* count);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
