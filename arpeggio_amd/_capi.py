@@ -36,7 +36,7 @@ SYMBOLS = (
     'arp_shard_assemble', 'arp_shard_layout', 'arp_get_blob', 'arp_cif_open', 'arp_cif_close', 'arp_cif_rows', 'arp_cif_cols',
     'arp_cif_blocks', 'arp_cif_tag', 'arp_cif_text', 'arp_cif_column', 'arp_cif_column_f64', 'arp_cif_column_i64',
     'arp_atom_contacts_sort', 'arp_fetch_packed', 'arp_set_topology', 'arp_set_models', 'arp_models_planes',
-    'arp_models_persistence_launch', 'arp_models_persistence_fetch',
+    'arp_models_persistence_launch', 'arp_models_persistence_fetch', 'arp_set_compact_lookback',
 )
 
 # the persistence table (arp_models_persistence_*): its columns, the SIFt bits counted per row, and ARP_PERSIST_STAGE_MAX
@@ -178,6 +178,7 @@ def load():
     L.arp_get_host_times.argtypes = [vp, vp, vp, i32]
     L.arp_set_whole_structure.argtypes = [vp, i32]
     L.arp_set_grid_reuse.argtypes = [vp, i32]
+    L.arp_set_compact_lookback.argtypes = [vp, i32]
     L.arp_set_sort_after_pass.argtypes = [vp, i32]
     L.arp_set_packed_layout.argtypes = [vp, i32]
     L.arp_device_synchronize.argtypes = [vp]
@@ -536,6 +537,11 @@ class Context:
         """Whole-structure passes keep their contact grid (default); ``False``: every pass builds it (measurements)."""
         self._check(self._L.arp_set_grid_reuse(self._h, int(bool(on))), 'arp_set_grid_reuse')
 
+    def set_compact_lookback(self, on=True):
+        """Every grid build finds its blocks' bases by look-back, also where the table made with the spatial order would serve
+        (whole-structure passes); for tests that hold the two against each other."""
+        self._check(self._L.arp_set_compact_lookback(self._h, int(bool(on))), 'arp_set_compact_lookback')
+
     def set_sort_after_pass(self, on=True):
         """``run_launch`` / ``run_wait`` enqueue the canonical sort of the atom-atom bag before they return (for callers that
         fetch the sorted bag next: ``fetch_packed``)."""
@@ -808,7 +814,7 @@ class Context:
         a = [np.ascontiguousarray(x, np.uint8) for x in (sel, plus, ring_sel, ring_plus, amide_sel, amide_plus)]
         self._check(self._L.arp_set_selection_state(self._h, *[_p(x) for x in a]), 'arp_set_selection_state')
 
-    BUF_PLUS, BUF_RES_SETS = 0, 1
+    BUF_PLUS, BUF_RES_SETS, BUF_GRID_START, BUF_KEEP_BASE = 0, 1, 2, 3
 
     def device_buffer(self, which):
         """(device pointer, bytes) of a context buffer, for torch tensors that alias it (sharded runs)."""

@@ -311,6 +311,18 @@ struct arp_ctx {
     GridDesc sp_grid{};           // the grid the spatial order was made for
     double sp_radius = 0;         // ... and its cell edge (0: no order yet)
     DevBuf<unsigned long long> compact_chain;   // k_compact_atoms: one word per block
+    // sp_keep_base: kept rows (no hydrogens) before every block of a whole-structure k_compact_atoms over the spatial order, made
+    // from the order by the second such build over it (make_keep_bases).  Layout: [ticket, 3 words of padding | count per block | base per block, the total last]
+    DevBuf<int> sp_keep;
+    int sp_keep_rows = 0, sp_keep_blocks = 0;   // rows per block the table was made for, and its blocks
+    uint64_t sp_keep_epoch = 0;                 // static_epoch of the order it describes (0: none)
+    uint64_t sp_keep_seen = 0;                  // static_epoch of the last order a whole-structure grid was built over without it
+#ifdef ARP_COMPACT_LOOKBACK                     // (developer builds: the look-back everywhere, for A/B runs of one source)
+    bool compact_lookback = true;
+#else
+    bool compact_lookback = false;              // arp_set_compact_lookback: tests compare the two ways of finding a block's base
+#endif
+    bool compact_used_table = false;            // the last grid build read the table
     DevBuf<int> s_cell;                         // cell of every row of the contact grid (k_search: blocks split by atoms)
     bool s_cell_valid = false;                  // ... written by the build of the grid that is in place
     DevBuf<int> sb_tile;                        // k_search's runs of tiles with equal numbers of atoms (k_balance_blocks): a hint from the pass before
@@ -660,7 +672,8 @@ enum : unsigned {
 //   models                 as a blob upload (everything), then as a batch; model mode begins after both      (m)
 //
 // static columns: k_prepare_static's records and their spatial order; the contact count of the last pass that sizes the sift
-//   launch goes with them.  The lists are made beside them (from the centre grids and the atoms as uploaded), so whatever
+//   launch goes with them, and so does sp_keep_base, the kept rows before every block of a whole-structure grid build
+//   (k_keep_bases: hydrogen flags and the order, no selection; a new order for resident columns voids it as well: its epoch).  The lists are made beside them (from the centre grids and the atoms as uploaded), so whatever
 //   stales the columns stales the lists at the same moment.
 // (s) the static columns read no selection; a staged shard pass recomposes them all the same (a change of that is a change of
 //   the kernels the staged path launches).  (k) the same structure in new grid tables keeps its contact count.
@@ -683,7 +696,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     const unsigned columns = IN_EVERYTHING & ~(IN_SELECTION | IN_WHOLE_STRUCTURE);
     const unsigned partition = IN_ATOMS | IN_RINGS | IN_AMIDES | IN_OWNERSHIP | IN_GROUP_OWNERSHIP | IN_BATCH;
     const unsigned layout = IN_BATCH | IN_BATCH_GRIDS;
-    if (what & (columns | IN_BATCH_GRIDS)) c->static_dirty = c->lists_dirty = true;
+    if (what & (columns | IN_BATCH_GRIDS)) { c->static_dirty = c->lists_dirty = true; c->sp_keep_epoch = 0; }
     if (what & columns) c->contacts_expected = 0;
     if (what & (IN_ATOMS | IN_RESIDUES | IN_OWNERSHIP | IN_SELECTION_STATE | layout)) c->atom_grid.valid = false;
     if (what & (IN_ATOMS | IN_RESIDUES | IN_OWNERSHIP | IN_SELECTION | IN_SELECTION_STATE | layout)) c->all_grid_current = false;
@@ -882,6 +895,7 @@ int join_upload_lists(arp_ctx* c, bool must = false) {
 // Selection-independent part of every atom record (rebuilt only when an input changed) and its SPATIAL ORDER: the rows sorted
 // by cell of the grid with cell edge `radius` (counting sort, x fastest), which a pass with that cell edge compacts into its
 // contact grid in one launch (k_compact_atoms).  radius = 0: any order will do (the one that exists, 6 A when there is none).
+inline int compact_rows(int n) { return n <= sw().compact_512_max_rows ? 512 : 1024; }      // rows per block of k_compact_atoms
 int ensure_static(arp_ctx* c, double radius = 0.0) {
     if (radius <= 0) radius = c->sp_radius > 0 ? c->sp_radius : 6.0;
     const bool columns = c->static_dirty;
@@ -950,6 +964,24 @@ int ensure_static(arp_ctx* c, double radius = 0.0) {
     c->sp_radius = radius;
     c->static_dirty = false;
     ++c->static_epoch;      // (whatever was derived from the old columns or their order is stale)
+    return ARP_OK;
+}
+// sp_keep_base of the spatial order in place (k_keep_bases: one launch on the main stream, once per order).  Not made with the
+// order itself: there it was 2.8 us of every structure's first pass (0.1034 -> 0.1062 ms at 100 k atoms), and a structure that is
+// evaluated once, or whose passes keep their grid, never reads it.  The second whole-structure grid build over an order makes it
+// (enqueue_contacts), as the search's hint is worked out by the second pass over a grid.
+int make_keep_bases(arp_ctx* c) {
+    const int n = (int)c->n;
+    const int rows = compact_rows(n), nb = (n + rows - 1) / rows;
+    bool fresh = false;
+    HIPCHK(c, c->sp_keep.reserve(4 + 2 * (size_t)nb + 1, &fresh));
+    if (fresh) HIPCHK(c, hipMemsetAsync(c->sp_keep.p, 0, 4 * sizeof(int), c->stream));      // (the ticket: every launch leaves it zero)
+    int* const cnt = c->sp_keep.p + 4;
+    if (rows == 512) hipLaunchKernelGGL(k_keep_bases<512>, dim3(nb), dim3(256), 0, c->stream, n, c->sp_xyzm.p, cnt, cnt + nb, (unsigned int*)c->sp_keep.p);
+    else hipLaunchKernelGGL(k_keep_bases<1024>, dim3(nb), dim3(256), 0, c->stream, n, c->sp_xyzm.p, cnt, cnt + nb, (unsigned int*)c->sp_keep.p);
+    CHK(check_launch(c, "k_keep_bases"));
+    c->sp_keep_rows = rows; c->sp_keep_blocks = nb;
+    c->sp_keep_epoch = c->static_epoch;
     return ARP_OK;
 }
 
@@ -1061,7 +1093,9 @@ int build_contact_grid(arp_ctx* c, double radius, uint32_t req, uint32_t forb, c
     return build_atom_grid(c, c->atom_grid, c->s_xyzm, c->s_aux, &c->s_qa, radius, req, forb, active, total_out, nullptr, nullptr, rm, gm);
 }
 // The contact grid of a pass as an ordered compaction of the static columns (k_compact_atoms): ONE launch.
-int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t forb, u64* total_out, uint8_t* plus_init, ResMarks rm) {
+// use_table: the caller has seen that sp_keep_base describes this pass (enqueue_contacts): no chain, no look-back.
+int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t forb, u64* total_out, uint8_t* plus_init, ResMarks rm,
+                               bool use_table = false) {
     Grid& G = c->atom_grid;
     const int n = (int)c->n;
     CHK(grid_desc_for(c, G.d, c->lo, c->hi, radius));
@@ -1076,15 +1110,20 @@ int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t
     CHK(ensure_static(c, radius));
     if (n > 0) {
         Prof p(c, SLOT_BIN);
-        const int rows_per_block = n <= sw().compact_512_max_rows ? 512 : 1024;
+        const int rows_per_block = compact_rows(n);
         const int nb = (n + rows_per_block - 1) / rows_per_block;
-        bool fresh = false;
-        HIPCHK(c, c->compact_chain.reserve((size_t)nb, &fresh));
-        if (fresh || c->compact_epoch >= (1u << 30) - 1u) {   // new buffer, or the 30-bit launch number wraps: no stale word may match
-            HIPCHK(c, hipMemsetAsync(c->compact_chain.p, 0, c->compact_chain.cap * sizeof(unsigned long long), c->stream));
-            c->compact_epoch = 0;
+        // (the caller's look at the table was before this function's ensure_static: a new order since then, and the look-back it is)
+        use_table = use_table && c->sp_keep_epoch == c->static_epoch && c->sp_keep_rows == rows_per_block && c->sp_keep_blocks == nb;
+        if (!use_table) {
+            bool fresh = false;
+            HIPCHK(c, c->compact_chain.reserve((size_t)nb, &fresh));
+            if (fresh || c->compact_epoch >= (1u << 30) - 1u) {   // new buffer, or the 30-bit launch number wraps: no stale word may match
+                HIPCHK(c, hipMemsetAsync(c->compact_chain.p, 0, c->compact_chain.cap * sizeof(unsigned long long), c->stream));
+                c->compact_epoch = 0;
+            }
+            ++c->compact_epoch;
         }
-        ++c->compact_epoch;
+        c->compact_used_table = use_table;
         CompactArgs A;
         A.r = static_atoms(c);
         A.sp_cell = c->sp_cell.p; A.n = n; A.ncell = ncell; A.req = req; A.forb = forb;
@@ -1093,11 +1132,17 @@ int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t
         A.s_cell = c->s_cell.p;
         A.start = G.start.p; A.chain = c->compact_chain.p; A.epoch = c->compact_epoch; A.total_out = total_out;
         A.plus_init = plus_init; A.rm = rm; A.err = (int*)(c->d_ctr + ctr_dev(C_ERR));
-        if (rows_per_block == 512) hipLaunchKernelGGL(k_compact_atoms<512>, dim3(nb), dim3(512), 0, c->stream, A);
+        A.keep_base = use_table ? c->sp_keep.p + 4 + nb : nullptr;
+        if (use_table) {
+            if (rows_per_block == 512) hipLaunchKernelGGL((k_compact_atoms<512, true>), dim3(nb), dim3(512), 0, c->stream, A);
+            else hipLaunchKernelGGL((k_compact_atoms<1024, true>), dim3(nb), dim3(1024), 0, c->stream, A);
+        }
+        else if (rows_per_block == 512) hipLaunchKernelGGL(k_compact_atoms<512>, dim3(nb), dim3(512), 0, c->stream, A);
         else hipLaunchKernelGGL(k_compact_atoms<1024>, dim3(nb), dim3(1024), 0, c->stream, A);
         CHK(check_launch(c, "k_compact_atoms"));
         c->s_cell_valid = true;
     } else {
+        c->compact_used_table = false;
         HIPCHK(c, hipMemsetAsync(G.start.p, 0, ((size_t)ncell + 1) * sizeof(int), c->stream));
         if (total_out) HIPCHK(c, hipMemsetAsync(total_out, 0, sizeof(u64), c->stream));
     }
@@ -1597,7 +1642,18 @@ int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
     }
     if (!reuse_grid) {
         c->cg_valid = false;
-        CHK(build_contact_grid_compact(c, cutoff, M_PLUS, M_HYDROGEN, c->d_ctr + ctr_dev(C_BINNED), c->init_plus_in_bin ? c->plus.p : nullptr, rm));
+        // A whole-structure pass keeps every row of the spatial order that is no hydrogen, whatever else the pass is: where its
+        // blocks' records begin follows from the order alone (sp_keep_base), and k_compact_atoms reads it instead of looking back.
+        // Any other selection or predicate, a table of another order or of other blocks, an order's first build: the look-back.
+        const uint32_t req = M_PLUS, forb = M_HYDROGEN;
+        CHK(ensure_static(c, cutoff));      // (the order of this pass: what the table has to describe)
+        const bool whole_pass = c->sel_made && c->sel_all && req == M_PLUS && forb == M_HYDROGEN && c->n > 0 && !c->compact_lookback;
+        if (whole_pass && (c->sp_keep_epoch != c->static_epoch || c->sp_keep_rows != compact_rows((int)c->n))) {
+            if (c->sp_keep_seen == c->static_epoch) CHK(make_keep_bases(c));      // the second such build over this order
+            else c->sp_keep_seen = c->static_epoch;                               // the first one looks back
+        }
+        const bool use_table = whole_pass && c->sp_keep_epoch == c->static_epoch && c->sp_keep_rows == compact_rows((int)c->n);
+        CHK(build_contact_grid_compact(c, cutoff, req, forb, c->d_ctr + ctr_dev(C_BINNED), c->init_plus_in_bin ? c->plus.p : nullptr, rm, use_table));
         if (whole) {      // what this grid was built from; its atom count arrives with the counters of the pass (finish_contacts)
             c->cg_valid = true; c->cg_pending = true;
             c->cg_key = grid_key();      // (after the build: ensure_static may have made a new spatial order)
@@ -3511,6 +3567,14 @@ int arp_device_buffer(arp_ctx* c, int which, uint64_t* device_ptr, int64_t* byte
         if (!c->res_sel.p) FAIL(c, ARP_E_ARG, "arp_device_buffer: residue sets do not exist yet (run stage 1 first)");
         *device_ptr = (uint64_t)(uintptr_t)c->res_sel.p;
         *bytes = 2 * std::max<int64_t>(c->nres, 1);
+    } else if (which == ARP_BUF_GRID_START) {
+        if (!c->atom_grid.valid || !c->atom_grid.start.p) FAIL(c, ARP_E_ARG, "arp_device_buffer: no contact grid is in place");
+        *device_ptr = (uint64_t)(uintptr_t)c->atom_grid.start.p;
+        *bytes = ((int64_t)c->atom_grid.d.ncell + 1) * (int64_t)sizeof(int);
+    } else if (which == ARP_BUF_KEEP_BASE) {
+        if (!c->compact_used_table) FAIL(c, ARP_E_ARG, "arp_device_buffer: the last grid build did not read the table of block bases");
+        *device_ptr = (uint64_t)(uintptr_t)(c->sp_keep.p + 4 + c->sp_keep_blocks);
+        *bytes = ((int64_t)c->sp_keep_blocks + 1) * (int64_t)sizeof(int);
     } else FAIL(c, ARP_E_ARG, "arp_device_buffer: unknown buffer");
     return ARP_OK;
 }
@@ -4250,6 +4314,13 @@ int arp_set_grid_reuse(arp_ctx* c, int enabled) {
     if (!c) return ARP_E_ARG;
     c->grid_reuse = enabled != 0;
     c->cg_valid = false;
+    return ARP_OK;
+}
+
+int arp_set_compact_lookback(arp_ctx* c, int enabled) {
+    if (!c) return ARP_E_ARG;
+    c->compact_lookback = enabled != 0;
+    c->cg_valid = false;      // (the next pass builds its grid)
     return ARP_OK;
 }
 

@@ -311,6 +311,57 @@ __global__ __launch_bounds__(256) void k_static_permute(int n, const int2* __res
         sp_cell[pos] = c.x;
     }
 }
+// Once per spatial order that whole-structure passes build their grid over more than once: base[b] = rows before row b * ROWS of the order that are no hydrogens, b = 0 ...
+// blocks (the last entry: all of them).  A whole-structure pass keeps exactly those rows, so its k_compact_atoms<ROWS, true> block
+// b reads where its records begin instead of looking back over its predecessors.  One launch: every block counts its ROWS rows and
+// takes a ticket, the last one to arrive scans the counts.  Counts and ticket travel as in pass_end (relaxed device-scope words,
+// vmcnt(0) between count and ticket: nothing else is published through them); the ticket goes back to zero for the next order.
+template <int ROWS>
+__global__ __launch_bounds__(256) void k_keep_bases(int n, const float4* __restrict__ sp_xyzm, int* __restrict__ cnt, int* __restrict__ base,
+                                                    unsigned int* __restrict__ ticket) {
+    __shared__ int s_w[4];
+    __shared__ int s_last;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nb = (int)gridDim.x;
+    int k = 0;
+#pragma unroll
+    for (int q = 0; q < ROWS / 256; ++q) {
+        const int i = blockIdx.x * ROWS + q * 256 + threadIdx.x;
+        if (i < n && !(__float_as_uint(sp_xyzm[i].w) & M_HYDROGEN)) ++k;
+    }
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o);
+    if (lane == 0) s_w[wv] = k;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(cnt + blockIdx.x, s_w[0] + s_w[1] + s_w[2] + s_w[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        s_last = atomicAdd(ticket, 1u) == (unsigned)nb - 1u;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    int carry = 0;
+    for (int c0 = 0; c0 < nb; c0 += 256) {      // (256 counts at a time with a running carry: 2 M rows are 1954 blocks)
+        const int b = c0 + (int)threadIdx.x;
+        const int v = b < nb ? __hip_atomic_load(cnt + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        int incl = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int u = __shfl_up(incl, off);
+            if (lane >= off) incl += u;
+        }
+        __syncthreads();      // (s_w: read above / in the round before)
+        if (lane == 63) s_w[wv] = incl;
+        __syncthreads();
+        int before = carry;
+        for (int w = 0; w < wv; ++w) before += s_w[w];
+        if (b < nb) base[b] = before + incl - v;
+        carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    }
+    if (threadIdx.x == 0) {
+        base[nb] = carry;
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
 
 // Residue / ring / amide sets of _make_selection (I:1413-1437) ride along with the contact grid build: the binning
 // kernel, which reads every atom's selection bits anyway, tags the residues (ResMarks; tag = pass number mod 255 + 1, so
@@ -528,6 +579,7 @@ struct CompactArgs {
     uint8_t* plus_init;        // not null: selection_plus = selection (I:1407), by local id
     ResMarks rm;
     int* err;
+    const int* keep_base;      // BASES: kept rows before every block, the total last (k_keep_bases)
 };
 #define CHAIN_AGG 1ull
 #define CHAIN_PFX 2ull
@@ -536,10 +588,23 @@ __device__ __forceinline__ unsigned long long chain_word(unsigned int epoch, uns
 }
 // (rows per block: 512 up to 150 000 rows — more blocks reading at once: 13.0 against 14.0 us at 100 k atoms; 250 k: 19.9 against 17.4 —,
 // 1024 beyond, where the shorter look-back wins: 61 against 68 us at 1 M)
-template <int COMPACT_THREADS>
+// (with the bases read from the table the rule stays: 2 M rows 82.9 us with 1024 rows per block, 93.8 with 512)
+// BASES: a whole-structure pass (every row that is no hydrogen is kept) over an order whose table of block bases is in place:
+// the block reads its base, publishes nothing and looks back at nobody; the last block holds its end against the table's total.
+template <int COMPACT_THREADS, bool BASES = false>
 __global__ __launch_bounds__(COMPACT_THREADS) void k_compact_atoms(CompactArgs A) {
     __shared__ int s_wtot[16], s_woff[16];
     __shared__ int s_base;
+    int known_base = 0, known_total = 0;
+    if constexpr (BASES) {      // (block-uniform loads, in flight beside the columns)
+        known_base = A.keep_base[blockIdx.x];
+        if (blockIdx.x == gridDim.x - 1) known_total = A.keep_base[gridDim.x];
+        // (whatever the table holds, no record is written outside the arrays: at most every row before this block was kept)
+        if ((unsigned)known_base > blockIdx.x * (unsigned)COMPACT_THREADS) {
+            if (threadIdx.x == 0) atomicExch(A.err, -2 /* ARP_E_HIP */);
+            known_base = 0;
+        }
+    }
     constexpr int NW = COMPACT_THREADS / 64;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #ifdef ARP_COMPACT_TRACE
@@ -586,6 +651,16 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compact_atoms(CompactArgs A
         if (lane < NW) s_woff[lane] = incl - t;
         const int total = __shfl(incl, NW - 1);
         const int b = (int)blockIdx.x;
+        if constexpr (BASES) {
+            if (lane == 0) {
+                s_base = known_base;
+                if (b == (int)gridDim.x - 1) {
+                    // (a table that is not this order's: an error of the pass, never a grid that is quietly wrong)
+                    if (known_base + total != known_total) atomicExch(A.err, -2 /* ARP_E_HIP */);
+                    if (A.total_out) *A.total_out = (unsigned long long)(known_base + total);
+                }
+            }
+        } else {      // (the look-back, its lines where they were)
         // (relaxed device-scope atomics: a word carries everything its readers need — no other memory is published through it,
         // so none of the L2 write-back / invalidate of a release / acquire pair is wanted: that pair cost 44 us in round 1)
         if (lane == 0)
@@ -619,6 +694,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compact_atoms(CompactArgs A
             if (b > 0) __hip_atomic_store(A.chain + b, chain_word(A.epoch, CHAIN_PFX, (unsigned)(base + total)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (b == (int)gridDim.x - 1 && A.total_out) *A.total_out = (unsigned long long)(base + total);
         }
+        }      // (!BASES)
     }
     __syncthreads();
     COMPACT_T(2);

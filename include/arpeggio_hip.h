@@ -400,6 +400,10 @@ int arp_set_selection_state(arp_ctx* ctx, const uint8_t* in_selection, const uin
  * Each stage returns after the context's streams have drained. */
 #define ARP_BUF_PLUS      0   /* u8[n]        selection_plus                                            */
 #define ARP_BUF_RES_SETS  1   /* u8[2 * nres] [0,nres) selection residues, [nres,2nres) selection_plus  */
+/* For tests of the grid build (read-only, valid until the next call that changes the context): */
+#define ARP_BUF_GRID_START 2  /* i32[cells + 1] first record of every cell of the contact grid in place     */
+#define ARP_BUF_KEEP_BASE  3  /* i32[blocks + 1] kept rows before every block of the last grid build, which  */
+                              /*                read them from this table (ARP_E_ARG if it looked back)      */
 int arp_device_buffer(arp_ctx* ctx, int which, uint64_t* device_ptr, int64_t* bytes);
 int arp_run_stage(arp_ctx* ctx, int stage, double cutoff, double vdw_comp, int include_sequence_adjacent,
                   double expand_radius, int64_t counts[5]);
@@ -443,6 +447,10 @@ int arp_host_free(void* p);
  * selection_plus into a new grid every time, as the reference rebuilds NeighborSearch(selection_plus) (interactions.py:1442).
  * enabled = 0 makes every pass build its grid (measurements); default 1. */
 int  arp_set_grid_reuse(arp_ctx* ctx, int enabled);
+/* The grid build of a whole-structure pass reads where each of its blocks' records begin from a table made from the structure's
+ * spatial order; every other pass finds them by a look-back over the blocks before.  enabled = 1 makes every pass look back
+ * (tests hold the two against each other; results are the same either way); default 0. */
+int  arp_set_compact_lookback(arp_ctx* ctx, int enabled);
 /* enabled = 1: arp_run_launch / arp_run_wait enqueue the canonical sort of the atom-atom bag (arp_atom_contacts_sort) as soon as
  * the pass has reported its record count, before they return — for callers that fetch the sorted bag next (arp_fetch_packed,
  * arp_atom_contacts_fetch after a sort; I:183-190 exports every record): the sort then starts a host round trip earlier and runs
