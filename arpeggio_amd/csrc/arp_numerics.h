@@ -178,33 +178,45 @@ __device__ __forceinline__ float fold_deg(float rad) {
     return fabsf(t / (float)ARP_PI);
 }
 
-// abs(group_angle(group, point, True, True)), utils.py:638-660
-__device__ __forceinline__ double group_angle(d3 normal, d3 point) {
-    double c = dot(normal, point) / (norm(normal) * norm(point));
-    return fold_deg(acos(c));
-}
-__device__ __forceinline__ float group_angle(f3 normal, f3 point) {
-    float c = dot(normal, point) / (norm(normal) * norm(point));
-    return fold_deg(acosf(c));
-}
+// The cosine utils.group_angle / group_group_angle hand to arccos (utils.py:646, 677): dot / (norm * norm), the operand types as in
+// the reference.  The REPORTED angle of a ring / amide record is fold_deg(acos(c)) by the device library; every DECISION on a folded
+// angle is taken on c itself (fold_le below), for the reason given at cos_angle above: at the cosine 0x1p-1 glibc folds acos to
+// 60.00000000000001 and the device library to 59.99999999999999, and the float32 acosf differs about 30 degrees
+// (tests/test_plane_edges.py, profiles/plane_edges.md).
+__device__ __forceinline__ double group_cos(d3 normal, d3 point) { return dot(normal, point) / (norm(normal) * norm(point)); }
+__device__ __forceinline__ float group_cos(f3 normal, f3 point) { return dot(normal, point) / (norm(normal) * norm(point)); }
 // float32 normal against a float64 vector: the dot promotes, norm(normal) stays float32
-__device__ __forceinline__ double group_angle(f3 normal, d3 other) {
-    double c = dot(to_d3(normal), other) / ((double)norm(normal) * norm(other));
-    return fold_deg(acos(c));
-}
+__device__ __forceinline__ double group_cos(f3 normal, d3 other) { return dot(to_d3(normal), other) / ((double)norm(normal) * norm(other)); }
 
-// interactions.py:1127-1148 (9 = '' when an angle is NaN)
-__device__ __forceinline__ int pp_class(double dihedral, double theta) {
-    if (dihedral <= 30.0 && theta <= 30.0) return 0;
-    else if (dihedral <= 30.0 && theta <= 60.0) return 1;
-    else if (dihedral <= 30.0 && theta <= 90.0) return 2;
-    else if (30.0 < dihedral && dihedral <= 60.0 && theta <= 30.0) return 3;
-    else if (30.0 < dihedral && dihedral <= 60.0 && theta <= 60.0) return 4;
-    else if (30.0 < dihedral && dihedral <= 60.0 && theta <= 90.0) return 5;
-    else if (60.0 < dihedral && dihedral <= 90.0 && theta <= 30.0) return 6;
-    else if (60.0 < dihedral && dihedral <= 90.0 && theta <= 60.0) return 7;
-    else if (60.0 < dihedral && dihedral <= 90.0 && theta <= 90.0) return 8;
-    return 9;
+// Per cut the two cosines that bound `abs(folded degrees of arccos(c)) <= cut` as glibc's acos / acosf decide it: the smallest c that
+// still passes without the fold (rad <= pi / 2) and the largest that still passes through it (rad - pi).  Found by bisection and pinned
+// by tests/test_plane_edges.py::test_fold_cosines_are_the_last_that_pass, monotonic for 10 000 values either side.
+#define ARP_FOLD_COS_30_POS 0x1.bb67ae8584cabp-1
+#define ARP_FOLD_COS_30_NEG (-0x1.bb67ae8584caap-1)
+#define ARP_FOLD_COS_60_POS 0x1.0000000000001p-1
+#define ARP_FOLD_COS_60_NEG (-0x1.0000000000000p-1)
+#define ARP_FOLD_COSF_30_POS 0x1.bb67aep-1f
+#define ARP_FOLD_COSF_30_NEG (-0x1.bb67b2p-1f)
+// folded angle of c <= cut; NaN and |c| > 1 (arccos NaN) fail, as every comparison with NaN does in the reference
+__device__ __forceinline__ bool fold_le(double c, double c_pos, double c_neg) { return (c >= c_pos && c <= 1.0) || (c <= c_neg && c >= -1.0); }
+__device__ __forceinline__ bool fold_le(float c, float c_pos, float c_neg) { return (c >= c_pos && c <= 1.0f) || (c <= c_neg && c >= -1.0f); }
+// the angle is a number (a folded angle never exceeds 90, so this is also `<= 90`)
+__device__ __forceinline__ bool fold_num(double c) { return c >= -1.0 && c <= 1.0; }
+__device__ __forceinline__ bool fold_num(float c) { return c >= -1.0f && c <= 1.0f; }
+// folded angle of c > 30 (false for NaN): the test of the amide loops, I:1282 / I:1363
+__device__ __forceinline__ bool fold_gt_30(double c) { return fold_num(c) && !fold_le(c, ARP_FOLD_COS_30_POS, ARP_FOLD_COS_30_NEG); }
+__device__ __forceinline__ bool fold_gt_30(float c) { return fold_num(c) && !fold_le(c, ARP_FOLD_COSF_30_POS, ARP_FOLD_COSF_30_NEG); }
+
+// interactions.py:1127-1148 on the cosines of the dihedral and of theta (9 = '' when an angle is NaN)
+__device__ __forceinline__ int pp_class(double cos_dihedral, double cos_theta) {
+    const bool dn = fold_num(cos_dihedral), tn = fold_num(cos_theta);
+    const bool d_lo = fold_le(cos_dihedral, ARP_FOLD_COS_30_POS, ARP_FOLD_COS_30_NEG);
+    const bool d_mid = fold_le(cos_dihedral, ARP_FOLD_COS_60_POS, ARP_FOLD_COS_60_NEG);
+    const bool t_lo = fold_le(cos_theta, ARP_FOLD_COS_30_POS, ARP_FOLD_COS_30_NEG);
+    const bool t_mid = fold_le(cos_theta, ARP_FOLD_COS_60_POS, ARP_FOLD_COS_60_NEG);
+    if (!dn || !tn) return 9;
+    const int row = d_lo ? 0 : d_mid ? 3 : 6;
+    return row + (t_lo ? 0 : t_mid ? 1 : 2);
 }
 
 }  // namespace num

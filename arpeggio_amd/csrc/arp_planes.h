@@ -299,9 +299,10 @@ __device__ __forceinline__ void ap_eval(const AtomPlaneArgs& A, bool live, int r
         const uint32_t m = __float_as_uint(v.w);
         const double dist = num::norm(num::sub(x, ctr_));                        // I:972
         const int ct = plane_ctype(A.ring_sel[r], m & M_SEL, true, true);         // I:985-997
-        const double theta = num::group_angle(nrm, num::sub(ctr_, x));           // I:1005
+        const double cost = num::group_cos(nrm, num::sub(ctr_, x));              // I:1005
+        const double theta = num::fold_deg(acos(cost));
         uint32_t mask = 0;
-        if (dist <= 4.5 && theta <= 30.0) {                                      // I:1007
+        if (dist <= 4.5 && num::fold_le(cost, ARP_FOLD_COS_30_POS, ARP_FOLD_COS_30_NEG)) {   // I:1007, theta <= 30 decided on its cosine
             if ((m & M_ELEM_C) && (m & ARP_T_WEAK_HBOND_DONOR)) mask |= ARP_AP_CARBONPI;
             if (m & ARP_T_POS_IONISABLE) mask |= ARP_AP_CATIONPI;
             if (m & ARP_T_HBOND_DONOR) mask |= ARP_AP_DONORPI;
@@ -342,9 +343,10 @@ __device__ __forceinline__ void pp_eval(const PlanePlaneArgs& A, bool live, int 
             const int ct = plane_ctype(A.ring_sel[a], A.ring_sel[b], true, true);
             const double cosd = num::dot(na, nb) / (num::norm(na) * num::norm(nb));
             const double dih = num::fold_deg(acos(cosd));                       // I:1122
-            const double t_ab = num::group_angle(na, pab);                      // I:1123, visit (a,b)
-            const double t_ba = num::group_angle(nb, num::sub(cbv, ca));        // visit (b,a)
-            const int y_ab = num::pp_class(dih, t_ab), y_ba = num::pp_class(dih, t_ba);
+            const double c_ab = num::group_cos(na, pab);                        // I:1123, visit (a,b)
+            const double c_ba = num::group_cos(nb, num::sub(cbv, ca));          // visit (b,a)
+            const double t_ab = num::fold_deg(acos(c_ab)), t_ba = num::fold_deg(acos(c_ba));
+            const int y_ab = num::pp_class(cosd, c_ab), y_ba = num::pp_class(cosd, c_ba);   // classes decided on the cosines
             const bool skip_ab = intra && y_ab == ARP_PP_EE;  // I:1154
             const bool skip_ba = intra && y_ba == ARP_PP_EE;
             emit = !(skip_ab && skip_ba);
@@ -388,8 +390,9 @@ __device__ __forceinline__ void gg_eval(const GroupGroupArgs& A, bool live, int 
         if (!(dist > (float)6.0)) {                        // I:1270
             const float cosd = num::dot(na, nb) / (num::norm(na) * num::norm(nb));
             const float dih = num::fold_deg(acosf(cosd));  // I:1278
-            const float theta = num::group_angle(na, pab); // I:1279
-            emit = !(dih > 30.0f || theta > 30.0f);        // I:1282
+            const float cost = num::group_cos(na, pab);    // I:1279
+            const float theta = num::fold_deg(acosf(cost));
+            emit = !(num::fold_gt_30(cosd) || num::fold_gt_30(cost));   // I:1282, decided on the cosines
             rec.i0 = A.am_gid ? A.am_gid[a] : a; rec.i1 = A.am_gid ? A.am_gid[b] : b;
             rec.d0 = (double)dist; rec.d1 = (double)dih; rec.d2 = (double)theta;
             rec.u = (unsigned)plane_ctype(A.am_sel[a], A.am_sel[b], true, true);
@@ -420,8 +423,9 @@ __device__ __forceinline__ void gp_eval(const GroupPlaneArgs& A, bool live, int 
         if (!(dist > 6.0)) {                        // I:1351
             const double cosd = num::dot(num::to_d3(na), nr) / ((double)num::norm(na) * num::norm(nr));
             const double dih = num::fold_deg(acos(cosd));    // I:1359
-            const double theta = num::group_angle(na, par);  // I:1360
-            emit = !(dih > 30.0 || theta > 30.0);            // I:1363
+            const double cost = num::group_cos(na, par);     // I:1360
+            const double theta = num::fold_deg(acos(cost));
+            emit = !(num::fold_gt_30(cosd) || num::fold_gt_30(cost));   // I:1363, decided on the cosines
             rec.i0 = A.am_gid ? A.am_gid[a] : a; rec.i1 = A.ring_gid ? A.ring_gid[r] : r;
             rec.d0 = dist; rec.d1 = dih; rec.d2 = theta;
             rec.u = (unsigned)plane_ctype(A.am_sel[a], A.ring_sel[r], true, true);

@@ -6,7 +6,9 @@ Purpose: (1) cross-check oracle/ref_c.c, whose arithmetic is an explicit model o
 float64 accumulation, FMA-chained float64 dot, NEP-50 comparisons); (2) the interpreter-bound "B1" baseline of
 BASELINE.md.  Only small inputs: it is as slow as the reference.
 
-Follows arpeggio/core/interactions.py:693-936 and arpeggio/core/utils.py:73-179, 696-745 on a PackedComplex.
+Follows arpeggio/core/interactions.py:693-936 and arpeggio/core/utils.py:73-179, 696-745 on a PackedComplex; the four
+ring / amide loops (interactions.py:947-1382 with utils.py:638-693) are the methods atom_plane, plane_plane, group_group
+and group_plane of RefPy.
 """
 from __future__ import annotations
 
@@ -33,12 +35,66 @@ def get_angle(pa, pb, pc):
     return np.pi if np.isnan(ang) else ang
 
 
+def group_angle(normal, point):
+    """utils.py:638-660 and 663-693 (the two are one expression) with degrees=True, signed=True: the dtype follows the operands
+    (float32 scalars against the Python floats np.pi, 180: NEP 50 keeps float32)."""
+    with np.errstate(all='ignore'):
+        cosangle = np.dot(normal, point) / (np.linalg.norm(normal) * np.linalg.norm(point))
+        rad = np.arccos(cosangle)
+    rad = rad - np.pi if rad > np.pi / 2 else rad
+    return rad * 180 / np.pi
+
+
+def plane_contact_type(a_sel, b_sel, a_plus, b_plus):
+    """The chain of four ifs of interactions.py:985-997, 1095-1108, 1252-1265, 1333-1346."""
+    ct = None
+    if not a_sel and not b_sel:
+        ct = 'INTRA_NON_SELECTION'
+    if a_plus and b_plus:
+        ct = 'INTRA_BINDING_SITE'
+    if a_sel and b_sel:
+        ct = 'INTRA_SELECTION'
+    if (a_sel and not b_sel) or (b_sel and not a_sel):
+        ct = 'INTER'
+    return CT[ct]
+
+
+def plane_plane_class(dihedral, theta):
+    """interactions.py:1127-1148; '' when no branch applies (an angle is NaN)."""
+    int_type = ''
+    if dihedral <= 30.0 and theta <= 30.0:
+        int_type = 'FF'
+    elif dihedral <= 30.0 and theta <= 60.0:
+        int_type = 'OF'
+    elif dihedral <= 30.0 and theta <= 90.0:
+        int_type = 'EE'
+    elif 30.0 < dihedral <= 60.0 and theta <= 30.0:
+        int_type = 'FT'
+    elif 30.0 < dihedral <= 60.0 and theta <= 60.0:
+        int_type = 'OT'
+    elif 30.0 < dihedral <= 60.0 and theta <= 90.0:
+        int_type = 'ET'
+    elif 60.0 < dihedral <= 90.0 and theta <= 30.0:
+        int_type = 'FE'
+    elif 60.0 < dihedral <= 90.0 and theta <= 60.0:
+        int_type = 'OE'
+    elif 60.0 < dihedral <= 90.0 and theta <= 90.0:
+        int_type = 'EF'
+    return int_type
+
+
 class RefPy:
     def __init__(self, pc, in_sel=None, in_plus=None):
         self.pc = pc
         n = pc.n_atoms
         self.sel = np.ones(n, bool) if in_sel is None else np.asarray(in_sel, bool)
         self.plus = np.ones(n, bool) if in_plus is None else np.asarray(in_plus, bool)
+        # interactions.py:1413-1437: a ring / amide belongs to the selection (selection_plus) when its residue does
+        res_sel, res_plus = set(pc.res_id[self.sel].tolist()), set(pc.res_id[self.plus].tolist())
+        self.ring_sel = [int(r) in res_sel for r in pc.ring_res]
+        self.ring_plus = [int(r) in res_plus for r in pc.ring_res]
+        self.amide_sel = [int(r) in res_sel for r in pc.amide_res]
+        self.amide_plus = [int(r) in res_plus for r in pc.amide_res]
         self.h = [pc.h_xyz[pc.h_off[i]:pc.h_off[i + 1]] for i in range(n)]                  # float64 rows
         self.bonded = [set(pc.bond_idx[pc.bond_off[i]:pc.bond_off[i + 1]].tolist()) for i in range(n)]
 
@@ -197,6 +253,147 @@ class RefPy:
         return dict(i=np.array([t[0] for t in out], np.int32), j=np.array([t[1] for t in out], np.int32),
                     dist=np.array([t[2] for t in out], np.float32), sift=np.array([t[3] for t in out], np.uint16),
                     ctype=np.array([t[4] for t in out], np.uint8))
+
+    # ---- the ring / amide loops ------------------------------------------------------------------------------------
+    @staticmethod
+    def _near(centres, c, reach=7.0):
+        """Items whose centre is within `reach` of c, ascending: a vectorised superset of the loops' own 6.0 A tests (which
+        still run, in the reference's arithmetic, on every item it lets through) so that the double loops stay affordable."""
+        d = np.asarray(centres, np.float64) - np.asarray(c, np.float64)
+        return np.nonzero((d * d).sum(axis=1) <= reach * reach)[0].tolist()
+
+    # interactions.py:947-1062
+    def atom_plane(self):
+        pc = self.pc
+        AP = {name: 1 << k for k, name in enumerate(config.ATOM_PLANE_NAMES)}
+        x64 = pc.xyz.astype(np.float64)
+        out = []
+        for r in range(pc.n_rings):
+            if not self.ring_plus[r]:
+                continue
+            center, normal = pc.ring_center[r], pc.ring_normal[r]
+            # NeighborSearch.search(center, 6.0) on the tree of selection_plus: float64 sum of squares, inclusive
+            d = center - x64
+            d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+            d2 = d2 + d[:, 2] * d[:, 2]
+            for a in np.nonzero((d2 <= 6.0 * 6.0) & self.plus)[0].tolist():
+                fl, tm = int(pc.flags[a]), int(pc.type_mask[a])
+                if fl & config.F_HYDROGEN:
+                    continue
+                distance = np.linalg.norm(pc.xyz[a] - center)
+                if tm & T['aromatic']:
+                    continue
+                ct = plane_contact_type(self.ring_sel[r], self.sel[a], self.ring_plus[r], self.plus[a])
+                theta = abs(group_angle(normal, center - pc.xyz[a]))
+                m = 0
+                if distance <= TH['aromatic']['atom_aromatic_distance'] and theta <= 30.0:
+                    if fl & config.F_ELEM_C and tm & T['weak hbond donor']:
+                        m |= AP['CARBONPI']
+                    if tm & T['pos ionisable']:
+                        m |= AP['CATIONPI']
+                    if tm & T['hbond donor']:
+                        m |= AP['DONORPI']
+                    if tm & T['xbond donor']:
+                        m |= AP['HALOGENPI']
+                if distance <= TH['aromatic']['met_sulphur_aromatic_distance']:
+                    if fl & config.F_RES_MET and fl & config.F_ELEM_S:
+                        m |= AP['METSULPHURPI']
+                if not m:
+                    continue
+                out.append((r, a, distance, theta, m, ct))
+        out.sort(key=lambda t: (t[0], t[1]))
+        return dict(atom=np.array([t[1] for t in out], np.int32), ring=np.array([t[0] for t in out], np.int32),
+                    dist=np.array([t[2] for t in out], np.float64), theta=np.array([t[3] for t in out], np.float64),
+                    mask=np.array([t[4] for t in out], np.uint8), ctype=np.array([t[5] for t in out], np.uint8))
+
+    # interactions.py:1064-1194: the ordered double loop and its dedupe, records in creation order
+    def plane_plane(self):
+        pc = self.pc
+        names = {n: k for k, n in enumerate(config.PLANE_PLANE_NAMES)}
+        contacts, index = [], {}
+        for r1 in range(pc.n_rings):
+            for r2 in self._near(pc.ring_center, pc.ring_center[r1]):
+                if not self.ring_plus[r1] or not self.ring_plus[r2]:
+                    continue
+                if r1 == r2:
+                    continue
+                intra_residue = pc.ring_res[r1] == pc.ring_res[r2]
+                ct = plane_contact_type(self.ring_sel[r1], self.ring_sel[r2], self.ring_plus[r1], self.ring_plus[r2])
+                distance = np.linalg.norm(pc.ring_center[r1] - pc.ring_center[r2])
+                if distance > TH['aromatic']['centroid_distance']:
+                    continue
+                theta_point = pc.ring_center[r1] - pc.ring_center[r2]
+                dihedral = abs(group_angle(pc.ring_normal[r1], pc.ring_normal[r2]))
+                theta = abs(group_angle(pc.ring_normal[r1], theta_point))
+                int_type = plane_plane_class(dihedral, theta)
+                if intra_residue and int_type == 'EE':
+                    continue
+                identity = index.get((r1, r2), index.get((r2, r1)))
+                if identity is not None:
+                    if int_type not in identity['types']:
+                        identity['types'].append(int_type)
+                    identity['seen'], identity['theta_end'] = True, theta
+                else:
+                    index[(r1, r2)] = dict(bgn=r1, end=r2, dist=distance, dihedral=dihedral, theta_bgn=theta, theta_end=np.nan,
+                                           types=[int_type], seen=False, ctype=ct)
+                    contacts.append(index[(r1, r2)])
+        type2 = [names[c['types'][1]] if len(c['types']) > 1 else (config.PP_SAME if c['seen'] else config.PP_SKIPPED) for c in contacts]
+        return dict(bgn=np.array([c['bgn'] for c in contacts], np.int32), end=np.array([c['end'] for c in contacts], np.int32),
+                    dist=np.array([c['dist'] for c in contacts], np.float64), dihedral=np.array([c['dihedral'] for c in contacts], np.float64),
+                    theta_bgn=np.array([c['theta_bgn'] for c in contacts], np.float64),
+                    theta_end=np.array([c['theta_end'] for c in contacts], np.float64),
+                    type1=np.array([names[c['types'][0]] for c in contacts], np.uint8), type2=np.array(type2, np.uint8),
+                    ctype=np.array([c['ctype'] for c in contacts], np.uint8))
+
+    # interactions.py:1217-1300, float32 throughout
+    def group_group(self):
+        pc = self.pc
+        out = []
+        for a1 in range(pc.n_amides):
+            if not self.amide_plus[a1]:
+                continue
+            for a2 in self._near(pc.amide_center, pc.amide_center[a1]):
+                if a1 == a2:
+                    continue
+                if not self.amide_plus[a2]:
+                    continue
+                ct = plane_contact_type(self.amide_sel[a1], self.amide_sel[a2], self.amide_plus[a1], self.amide_plus[a2])
+                distance = np.linalg.norm(pc.amide_center[a1] - pc.amide_center[a2])
+                if distance > TH['amide']['centroid_distance']:
+                    continue
+                theta_point = pc.amide_center[a1] - pc.amide_center[a2]
+                dihedral = abs(group_angle(pc.amide_normal[a1], pc.amide_normal[a2]))
+                theta = abs(group_angle(pc.amide_normal[a1], theta_point))
+                if dihedral > 30.0 or theta > 30.0:
+                    continue
+                out.append((a1, a2, distance, dihedral, theta, ct))
+        return dict(bgn=np.array([t[0] for t in out], np.int32), end=np.array([t[1] for t in out], np.int32),
+                    dist=np.array([t[2] for t in out], np.float32), dihedral=np.array([t[3] for t in out], np.float32),
+                    theta=np.array([t[4] for t in out], np.float32), ctype=np.array([t[5] for t in out], np.uint8))
+
+    # interactions.py:1302-1382: float32 amide against float64 ring
+    def group_plane(self):
+        pc = self.pc
+        out = []
+        for a in range(pc.n_amides):
+            if not self.amide_plus[a]:
+                continue
+            for r in self._near(pc.ring_center, pc.amide_center[a]):
+                if not self.ring_plus[r]:
+                    continue
+                ct = plane_contact_type(self.amide_sel[a], self.ring_sel[r], self.amide_plus[a], self.ring_plus[r])
+                distance = np.linalg.norm(pc.amide_center[a] - pc.ring_center[r])
+                if distance > TH['amide']['centroid_distance']:
+                    continue
+                theta_point = pc.amide_center[a] - pc.ring_center[r]
+                dihedral = abs(group_angle(pc.amide_normal[a], pc.ring_normal[r]))
+                theta = abs(group_angle(pc.amide_normal[a], theta_point))
+                if dihedral > 30.0 or theta > 30.0:
+                    continue
+                out.append((a, r, distance, dihedral, theta, ct))
+        return dict(amide=np.array([t[0] for t in out], np.int32), ring=np.array([t[1] for t in out], np.int32),
+                    dist=np.array([t[2] for t in out], np.float64), dihedral=np.array([t[3] for t in out], np.float64),
+                    theta=np.array([t[4] for t in out], np.float64), ctype=np.array([t[5] for t in out], np.uint8))
 
 
 # ---- geometric part of initialize() (SURVEY 8f row f2) -----------------------------------------------------------

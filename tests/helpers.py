@@ -187,6 +187,33 @@ def random_dense_pack(seed, n=400, box=14.0):
     return pc
 
 
+def random_ring_and_amide_sets(n=40, seed=99):
+    """(case, pack, selection or None) of n random ring / amide sets on random soups: coincident centres, zero normals (NaN angles ->
+    class ''), rings without a residue, whole and partial selections (one generator state over the cases)."""
+    rng = np.random.default_rng(seed)
+    for case in range(n):
+        nr, na = int(rng.integers(1, 300)), int(rng.integers(1, 300))
+        box = float(rng.choice([4.0, 9.0, 20.0, 45.0]))
+        pc = random_dense_pack(9000 + case, n=int(rng.integers(50, 600)), box=box)
+        rc, rn = rng.random((nr, 3)) * box, rng.standard_normal((nr, 3))
+        ac, an = (rng.random((na, 3)) * box).astype(np.float32), rng.standard_normal((na, 3)).astype(np.float32)
+        if case % 4 == 1:
+            rc[rng.integers(0, nr, max(1, nr // 5))] = rc[rng.integers(0, nr, max(1, nr // 5))]
+            rn[rng.integers(0, nr, max(1, nr // 8))] = 0.0
+        if case % 4 == 2:
+            an[rng.integers(0, na, max(1, na // 8))] = 0.0
+        pc.ring_center, pc.ring_normal = rc, rn
+        pc.ring_res = rng.integers(-1, pc.n_residues, nr).astype(np.int32)
+        pc.ring_atoms = []
+        pc.amide_center, pc.amide_normal = ac, an
+        pc.amide_res = rng.integers(-1, pc.n_residues, na).astype(np.int32)
+        pc.amide_atoms = np.full((na, 4), -1, np.int32)
+        sel = None if case % 3 == 0 else (rng.random(pc.n_atoms) < 0.3).astype(np.uint8)
+        if sel is not None and sel.sum() == 0:
+            sel[0] = 1
+        yield case, pc, sel
+
+
 def boundary_sensitive_pairs(pc, contacts, comp=0.1):
     """how many emitted contacts sit within one float32 ulp of a threshold the per-pair code compares the
     float32 distance with (sum of covalent radii, sum of vdW radii, vdW sum + comp, 2.8, 3.5, 3.6, 4.0, 4.5: I:760-920;

@@ -327,8 +327,7 @@ def test_random_ring_and_amide_sets(ctx):
     without a residue, whole and partial selections — through arp_run_launch: ids, classes, masks and contact types
     exactly, distances and angles within 1e-4 degrees / Angstrom, the north-star bound (acos differs by an ulp between the two libms)."""
     import oracle
-    from helpers import random_dense_pack
-    rng = np.random.default_rng(99)
+    from helpers import random_ring_and_amide_sets
 
     def close(a, b, tol=1e-4):
         a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
@@ -339,26 +338,7 @@ def test_random_ring_and_amide_sets(ctx):
             ('group_group', ('bgn', 'end'), ('bgn', 'end', 'ctype'), ('dist', 'dihedral', 'theta')),
             ('group_plane', ('amide', 'ring'), ('amide', 'ring', 'ctype'), ('dist', 'dihedral', 'theta')))
     records = 0
-    for case in range(40):
-        nr, na = int(rng.integers(1, 300)), int(rng.integers(1, 300))
-        box = float(rng.choice([4.0, 9.0, 20.0, 45.0]))
-        pc = random_dense_pack(9000 + case, n=int(rng.integers(50, 600)), box=box)
-        rc, rn = rng.random((nr, 3)) * box, rng.standard_normal((nr, 3))
-        ac, an = (rng.random((na, 3)) * box).astype(np.float32), rng.standard_normal((na, 3)).astype(np.float32)
-        if case % 4 == 1:
-            rc[rng.integers(0, nr, max(1, nr // 5))] = rc[rng.integers(0, nr, max(1, nr // 5))]
-            rn[rng.integers(0, nr, max(1, nr // 8))] = 0.0
-        if case % 4 == 2:
-            an[rng.integers(0, na, max(1, na // 8))] = 0.0
-        pc.ring_center, pc.ring_normal = rc, rn
-        pc.ring_res = rng.integers(-1, pc.n_residues, nr).astype(np.int32)
-        pc.ring_atoms = []
-        pc.amide_center, pc.amide_normal = ac, an
-        pc.amide_res = rng.integers(-1, pc.n_residues, na).astype(np.int32)
-        pc.amide_atoms = np.full((na, 4), -1, np.int32)
-        sel = None if case % 3 == 0 else (rng.random(pc.n_atoms) < 0.3).astype(np.uint8)
-        if sel is not None and sel.sum() == 0:
-            sel[0] = 1
+    for case, pc, sel in random_ring_and_amide_sets():
         ctx.set_complex(pc)
         if sel is not None:
             ctx.set_selection(sel)
