@@ -37,6 +37,7 @@ SYMBOLS = (
     'arp_cif_blocks', 'arp_cif_tag', 'arp_cif_text', 'arp_cif_column', 'arp_cif_column_f64', 'arp_cif_column_i64',
     'arp_atom_contacts_sort', 'arp_fetch_packed', 'arp_set_topology', 'arp_set_models', 'arp_models_planes',
     'arp_models_persistence_launch', 'arp_models_persistence_fetch', 'arp_set_compact_lookback',
+    'arp_residue_pairs_launch', 'arp_residue_pairs_fetch',
 )
 
 # the persistence table (arp_models_persistence_*): its columns, the SIFt bits counted per row, and ARP_PERSIST_STAGE_MAX
@@ -46,6 +47,11 @@ PERSIST_COLUMNS = (('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('
                    ('dist_min', np.float32), ('dist_max', np.float32), ('dist_sum', np.float64), ('bit_count', np.uint16),
                    ('ctype_mask', np.uint8))
 _PERSIST_FETCH_ORDER = tuple(k for k, _ in PERSIST_COLUMNS)
+# the residue-pair table (arp_residue_pairs_*): its columns in the order of arp_residue_pairs_fetch's arguments
+RESPAIR_BITS = 15
+RESPAIR_COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_contacts', np.uint32), ('dist_min', np.float32),
+                   ('bit_count', np.uint32), ('ctype_mask', np.uint8), ('plane_count', np.uint32))
+_RESPAIR_WIDTH = {'bit_count': RESPAIR_BITS, 'plane_count': 4}
 
 _lib = None
 
@@ -188,6 +194,8 @@ def load():
     L.arp_models_planes.argtypes = [vp, vp, vp, vp, vp, vp]
     L.arp_models_persistence_launch.argtypes = [vp, C.POINTER(i64)]
     L.arp_models_persistence_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.arp_residue_pairs_launch.argtypes = [vp, C.POINTER(i64)]
+    L.arp_residue_pairs_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -698,6 +706,20 @@ class Context:
         t = {k: np.empty((U, PERSIST_BITS) if k == 'bit_count' else U, dt) for k, dt in PERSIST_COLUMNS}
         self._check(self._L.arp_models_persistence_fetch(self._h, U, *(_p(t[k]) for k in _PERSIST_FETCH_ORDER), C.byref(n)),
                     'arp_models_persistence_fetch')
+        return t
+
+    def residue_pairs(self):
+        """The residue-residue contact table of the last complete pass, reduced on the device (arp_residue_pairs_*): one row
+        per unordered residue pair with a record in any of the five bags, rows in ascending (res_a, res_b).  Returns a dict
+        of the seven columns ``RESPAIR_COLUMNS`` (``bit_count`` as [U, 15], ``plane_count`` as [U, 4]; see
+        ``arpeggio_amd.residue_pairs``).  Only the table is copied to the host; the bags of the pass stay fetchable as
+        before.  With a batch or models resident the ids are those of the concatenation (``residue_pairs.split``)."""
+        n = C.c_int64(0)
+        self._check(self._L.arp_residue_pairs_launch(self._h, C.byref(n)), 'arp_residue_pairs_launch')
+        U = int(n.value)
+        t = {k: np.empty((U, _RESPAIR_WIDTH[k]) if k in _RESPAIR_WIDTH else U, dt) for k, dt in RESPAIR_COLUMNS}
+        self._check(self._L.arp_residue_pairs_fetch(self._h, U, *(_p(t[k]) for k, _ in RESPAIR_COLUMNS), C.byref(n)),
+                    'arp_residue_pairs_fetch')
         return t
 
     def set_blob(self, blob, counts=None):

@@ -333,6 +333,20 @@ class InteractionComplex:
         bits = self.atom_sifts()
         return export.residue_sift_table(self.pc, bits, self.atom_integer_sifts(), self.residue_plane_sifts())
 
+    def residue_contacts(self):
+        """The residue-residue contact table of the last run (``arpeggio_amd.residue_pairs`` describes the seven columns): the
+        records of all five bags folded by residue on the GPU, from the results ``run_arpeggio`` left resident there — only
+        the table is copied."""
+        self._need_results()
+        if self._ctx is None:
+            raise AttributeError('no results on a GPU context: call run_arpeggio() on this complex first')
+        return self._ctx.residue_pairs()
+
+    def write_residue_contacts(self, wd):
+        """'<id>.rescontacts': ``residue_contacts()`` as CSV, one row per residue pair (``residue_pairs.write_csv``)."""
+        from .. import residue_pairs
+        return residue_pairs.write_residue_contacts(wd, self.id, self.residue_contacts(), self.pc, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""
@@ -672,6 +686,21 @@ class EnsembleComplex:
             self.persistence, self.persistence_models = t, self.n_models
         self.stats = self._ctx.stats()
         return self.persistence
+
+    def run_residue_contacts(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
+        """The residue-residue contact table of every model: the selection handling and the pass of ``run_arpeggio``, then the
+        records of all models folded by residue ON THE DEVICE (``arpeggio_amd.residue_pairs`` describes the table) and only
+        that table fetched and cut: a list of F tables with model-local residue ids.  No bag is copied to the host:
+        ``model(k)`` has no results after this call (``run_arpeggio`` gives those)."""
+        from .. import residue_pairs
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        t = self._ctx.residue_pairs()
+        self._results = None
+        self.stats = self._ctx.stats()
+        return residue_pairs.split(t, np.arange(self.n_models + 1, dtype=np.int64) * self.pc.n_residues)
 
     def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
         """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""

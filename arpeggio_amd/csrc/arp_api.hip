@@ -28,6 +28,7 @@
 #include "arp_comm.h"
 #include "arp_sort.h"
 #include "arp_persist.h"
+#include "arp_respair.h"
 #include "arp_blob.h"
 
 namespace {
@@ -464,6 +465,11 @@ struct arp_ctx {
     size_t persist_stage_cap = 0;
     int64_t persist_count = 0;            // rows of the table
     bool persist_valid = false;           // persist_slab holds the table of the last launch's results
+    // ---- residue-pair table of the last pass (arp_respair.h; arp_residue_pairs_launch / _fetch): its scratch is the persistence
+    // table's (sort_persist, persist_tiles / _rows / _total, persist_stage) — both tables are results and are voided together
+    DevBuf<uint8_t> respair_slab;         // the table's seven columns in one piece (respair_layout)
+    int64_t respair_count = 0;            // rows of the table
+    bool respair_valid = false;           // respair_slab holds the table of the last pass's results
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -686,7 +692,9 @@ enum : unsigned {
 // selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
-//   persistence table of the resident models (arp_models_persistence_launch) is made from the atom-atom bag and goes with it.
+//   persistence table of the resident models (arp_models_persistence_launch) is made from the atom-atom bag and goes with it;
+//   the residue-pair table (arp_residue_pairs_launch) is made from all five and goes with any of them (finish_contacts,
+//   finish_bag: the next launch that refills a bag).
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -719,6 +727,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
         c->persist_valid = false;
+        c->respair_valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1891,6 +1900,7 @@ bool finish_contacts(arp_ctx* c) {
     c->contacts_valid = true;
     c->contacts_sorted = false;
     c->persist_valid = false;
+    c->respair_valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2023,6 +2033,7 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     b.count = (int64_t)k;
     b.valid = true;
     ++b.version;
+    c->respair_valid = false;
     return false;
 }
 int grow_pairs(arp_ctx* c) {
@@ -2228,6 +2239,7 @@ void arp_destroy(arp_ctx* c) {
     c->bag_pack.release(); c->bag_perm.release();
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
     c->sort_persist.release(); c->persist_tiles.release(); c->persist_rows.release(); c->persist_total.release(); c->persist_slab.release();
+    c->respair_slab.release();
     if (c->persist_stage) (void)hipHostFree(c->persist_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4020,6 +4032,60 @@ int persist_stage_reserve(arp_ctx* c, size_t bytes) {
     c->persist_stage_cap = want;
     return ARP_OK;
 }
+// k re-keyed records in s.key[0] / s.val[0], sorted by the low keybits bits of the key — every bit of it: least significant
+// digit first, up to SORT_MAX_BITS a pass, stable.  *sorted = the buffer (0 / 1) the last pass wrote.  reserve_key_sort sizes the
+// scratch (cap >= k records) before the caller fills buffer 0.
+int reserve_key_sort(arp_ctx* c, SortScratch& s, size_t k, size_t cap) {
+    for (int q = 0; q < 2; ++q) { HIPCHK(c, s.key[q].reserve(cap)); HIPCHK(c, s.val[q].reserve(cap)); }
+    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
+    HIPCHK(c, s.table.reserve((size_t)SORT_BINS * (size_t)((tiles + 3) & ~3ll)));
+    HIPCHK(c, s.total.reserve(SORT_BINS));
+    return ARP_OK;
+}
+void enqueue_key_sort(arp_ctx* c, SortScratch& s, size_t k, int keybits, int* sorted) {
+    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
+    const int passes = (keybits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
+    SortArgs S{};
+    S.n = (long long)k; S.T = (int)tiles; S.tstride = (int)((tiles + 3) & ~3ll); S.table = s.table.p; S.total = s.total.p;
+    S.first = 0; S.last = 0; S.jbits = 0;
+    int shift = 0;
+    for (int ps = 0; ps < passes; ++ps) {
+        S.shift = shift;
+        S.bits = keybits / passes + (ps < keybits % passes ? 1 : 0);
+        shift += S.bits;
+        S.key_in = s.key[ps & 1].p; S.val_in = s.val[ps & 1].p;
+        S.key_out = s.key[(ps + 1) & 1].p; S.val_out = s.val[(ps + 1) & 1].p;
+        hipLaunchKernelGGL(k_sort_hist, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
+        hipLaunchKernelGGL(k_sort_scan, dim3(1 << S.bits), dim3(SORT_THREADS), 0, c->stream, S);
+        hipLaunchKernelGGL(k_sort_scatter, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
+    }
+    *sorted = passes & 1;
+}
+// The runs of equal key >> R.shift among the sorted keys: counted per tile and scanned on the stream, then the one wait of a
+// table's launch — *U = runs = rows of the table.  R.key, R.k and R.shift are the caller's.
+int count_runs(arp_ctx* c, RunArgs& R, long long* U, const char* what) {
+    R.T = (int)((R.k + PERSIST_TILE - 1) / PERSIST_TILE);
+    HIPCHK(c, c->persist_tiles.reserve((size_t)R.T));
+    HIPCHK(c, c->persist_total.reserve(1));
+    CHK(persist_stage_reserve(c, 4096));
+    R.tile_rows = c->persist_tiles.p;
+    R.total = c->persist_total.p;
+    hipLaunchKernelGGL(k_persist_count, dim3(R.T), dim3(PERSIST_THREADS), 0, c->stream, R);
+    hipLaunchKernelGGL(k_persist_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+    CHK(check_launch(c, what));
+    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(U, c->persist_stage, sizeof(*U));
+    return ARP_OK;
+}
+// ... and where each of the U runs begins (row_start[U] = k), for the reduction that follows on the stream
+int enqueue_run_starts(arp_ctx* c, RunArgs& R, long long U) {
+    HIPCHK(c, c->persist_rows.reserve((size_t)U + 1));
+    R.U = U;
+    R.row_start = c->persist_rows.p;
+    hipLaunchKernelGGL(k_persist_starts, dim3(R.T), dim3(PERSIST_THREADS), 0, c->stream, R);
+    return ARP_OK;
+}
 }  // namespace
 
 int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
@@ -4046,59 +4112,31 @@ int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
     if (keybits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: (atom, atom, model) does not fit a 63-bit key");
     // ---- scratch: sized from the capacity of the bag's columns, so that it is allocated once per structure size
     SortScratch& s = c->sort_persist;
-    const size_t cap = std::max(k, c->out_i.cap);
-    for (int q = 0; q < 2; ++q) { HIPCHK(c, s.key[q].reserve(cap)); HIPCHK(c, s.val[q].reserve(cap)); }
-    const long long tiles = ((long long)k + SORT_TILE - 1) / SORT_TILE;
-    const int tstride = (int)((tiles + 3) & ~3ll);
-    HIPCHK(c, s.table.reserve((size_t)SORT_BINS * (size_t)tstride));
-    HIPCHK(c, s.total.reserve(SORT_BINS));
-    A.T = (int)(((long long)k + PERSIST_TILE - 1) / PERSIST_TILE);
-    HIPCHK(c, c->persist_tiles.reserve((size_t)A.T));
-    HIPCHK(c, c->persist_total.reserve(1));
-    CHK(persist_stage_reserve(c, 4096));
-    A.tile_rows = c->persist_tiles.p;
-    A.total = c->persist_total.p;
+    CHK(reserve_key_sort(c, s, k, std::max(k, c->out_i.cap)));
     // ---- (a, b, f) keys, sorted by every bit: least significant digit first
     A.key = s.key[0].p; A.val = s.val[0].p;
     hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, A);
-    const int passes = (keybits + SORT_MAX_BITS - 1) / SORT_MAX_BITS;
-    SortArgs S{};
-    S.n = (long long)k; S.T = (int)tiles; S.tstride = tstride; S.table = s.table.p; S.total = s.total.p;
-    S.first = 0; S.last = 0; S.jbits = 0;
-    int shift = 0;
-    for (int ps = 0; ps < passes; ++ps) {
-        S.shift = shift;
-        S.bits = keybits / passes + (ps < keybits % passes ? 1 : 0);
-        shift += S.bits;
-        S.key_in = s.key[ps & 1].p; S.val_in = s.val[ps & 1].p;
-        S.key_out = s.key[(ps + 1) & 1].p; S.val_out = s.val[(ps + 1) & 1].p;
-        hipLaunchKernelGGL(k_sort_hist, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
-        hipLaunchKernelGGL(k_sort_scan, dim3(1 << S.bits), dim3(SORT_THREADS), 0, c->stream, S);
-        hipLaunchKernelGGL(k_sort_scatter, dim3(S.T), dim3(SORT_THREADS), 0, c->stream, S);
-    }
-    A.key = s.key[passes & 1].p; A.val = s.val[passes & 1].p;
+    int sorted = 0;
+    enqueue_key_sort(c, s, k, keybits, &sorted);
+    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
     // ---- rows: count, scan; the host learns U (the one wait)
-    hipLaunchKernelGGL(k_persist_count, dim3(A.T), dim3(PERSIST_THREADS), 0, c->stream, A);
-    hipLaunchKernelGGL(k_persist_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, A);
-    CHK(check_launch(c, "arp_models_persistence_launch: sort / count"));
-    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    RunArgs R{};
+    R.key = A.key; R.k = A.k; R.shift = A.fbits;
     long long U = 0;
-    memcpy(&U, c->persist_stage, sizeof(U));
+    CHK(count_runs(c, R, &U, "arp_models_persistence_launch: sort / count"));
     if (U < 1 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_models_persistence_launch: row count out of range");
     // ---- the table: row starts, one wave per row
     size_t off[PT_COLS], bytes;
     persist_layout((size_t)U, off, &bytes);
-    HIPCHK(c, c->persist_rows.reserve((size_t)U + 1));
     HIPCHK(c, c->persist_slab.reserve(bytes));
     uint8_t* const slab = c->persist_slab.p;
+    CHK(enqueue_run_starts(c, R, U));
     A.U = U;
-    A.row_start = c->persist_rows.p;
+    A.row_start = R.row_start;
     A.t_dsum = (double*)(slab + off[PT_DSUM]); A.t_a = (int*)(slab + off[PT_A]); A.t_b = (int*)(slab + off[PT_B]);
     A.t_first = (int*)(slab + off[PT_FIRST]); A.t_last = (int*)(slab + off[PT_LAST]);
     A.t_dmin = (float*)(slab + off[PT_DMIN]); A.t_dmax = (float*)(slab + off[PT_DMAX]);
     A.t_nmodels = (uint16_t*)(slab + off[PT_NMODELS]); A.t_bits = (uint16_t*)(slab + off[PT_BITS]); A.t_ctype = slab + off[PT_CTYPE];
-    hipLaunchKernelGGL(k_persist_starts, dim3(A.T), dim3(PERSIST_THREADS), 0, c->stream, A);
     hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
     CHK(check_launch(c, "arp_models_persistence_launch: reduce"));
     c->persist_count = U;
@@ -4126,6 +4164,116 @@ int arp_models_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b
     put(dist_sum, PT_DSUM, 8); put(a, PT_A, 4); put(b, PT_B, 4); put(first, PT_FIRST, 4); put(last, PT_LAST, 4);
     put(dist_min, PT_DMIN, 4); put(dist_max, PT_DMAX, 4); put(n_models, PT_NMODELS, 2); put(bit_count, PT_BITS, 2 * PERSIST_BITS);
     put(ctype_mask, PT_CTYPE, 1);
+    return ARP_OK;
+}
+
+// ---- residue-residue contact table of the last pass (arp_respair.h) ---------------------------------------------------
+namespace {
+// Layout of the table's slab: the seven columns one after the other, each on a 256-byte boundary.
+enum { RT_A = 0, RT_B, RT_N, RT_DMIN, RT_BITS, RT_PLANES, RT_CTYPE, RT_COLS };
+void respair_layout(size_t U, size_t off[RT_COLS], size_t* bytes) {
+    static const size_t es[RT_COLS] = {4, 4, 4, 4, 4 * RESPAIR_BITS, 4 * RESPAIR_PLANE_BAGS, 1};
+    size_t at = 0;
+    for (int q = 0; q < RT_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
+    *bytes = at;
+}
+// Bits of the key the sort covers: res_a << rbits | res_b, and one bit more where the all-ones key of a left-out record
+// would otherwise tie with a pair in the sorted bits — the pair (nres - 1, nres - 1) of a ring / amide bag when nres - 1 is
+// all ones itself (bit 2 rbits is set in ~0 and in no pair: the left-out records then sort last by it).
+int respair_key_bits(int64_t nres, int rbits, bool planes) {
+    const bool tie = planes && nres - 1 == ((int64_t)1 << rbits) - 1;
+    return 2 * rbits + (tie ? 1 : 0);
+}
+}  // namespace
+
+int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: not for a shard of a distributed structure");
+    Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};      // classes 1 ... 4
+    bool complete = !c->pass_pending && c->contacts_valid;
+    for (const Bag* b : bags) complete = complete && b->valid;
+    if (!complete) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: no results of a complete pass (arp_run_launch first)");
+    if (c->respair_valid) { *count = c->respair_count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    RespairArgs A{};
+    A.k_aa = (long long)c->n_contacts;
+    size_t k = (size_t)c->n_contacts, planes = 0;
+    const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
+                                                      {c->am_res.p, c->am_res.p}, {c->am_res.p, c->ring_res.p}};
+    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) {
+        const Bag& b = *bags[m];
+        A.bag[m] = RespairBag{b.a.p, b.b.p, res_of[m][0], res_of[m][1], (long long)b.count, (long long)k};
+        k += (size_t)b.count;
+        planes += (size_t)b.count;
+    }
+    c->respair_count = 0;
+    if (k == 0) { c->respair_valid = true; *count = 0; return ARP_OK; }
+    // (a left-out record keeps its slot up to the reduction, so every record of the five bags counts here, kept or not)
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_residue_pairs_launch: 2^31 records or more");
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.res_id = c->res_id.p;
+    A.rbits = id_bits(std::max<int64_t>(c->nres - 1, 1));
+    const int keybits = respair_key_bits(c->nres, A.rbits, planes > 0);
+    // ---- scratch: sized from the capacities of the bags' columns, so that it is allocated once per structure size
+    SortScratch& s = c->sort_persist;
+    size_t cap = std::max((size_t)c->n_contacts, c->out_i.cap);
+    for (const Bag* b : bags) cap += std::max((size_t)b->count, b->cap);
+    CHK(reserve_key_sort(c, s, k, cap));
+    // ---- (res_a, res_b) keys of all five bags, sorted by every bit
+    A.key = s.key[0].p; A.val = s.val[0].p;
+    if (A.k_aa > 0) hipLaunchKernelGGL(k_respair_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
+    if (planes > 0) {
+        int64_t largest = 0;
+        for (const Bag* b : bags) largest = std::max(largest, b->count);
+        hipLaunchKernelGGL(k_respair_rekey_planes, dim3(nblocks(largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
+    }
+    int sorted = 0;
+    enqueue_key_sort(c, s, k, keybits, &sorted);
+    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
+    // ---- rows: count, scan; the host learns U (the one wait)
+    RunArgs R{};
+    R.key = A.key; R.k = (long long)k; R.shift = 0;
+    long long U = 0;
+    CHK(count_runs(c, R, &U, "arp_residue_pairs_launch: sort / count"));
+    if (U < 0 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_residue_pairs_launch: row count out of range");
+    if (U > 0) {      // (0: every record was left out)
+        size_t off[RT_COLS], bytes;
+        respair_layout((size_t)U, off, &bytes);
+        HIPCHK(c, c->respair_slab.reserve(bytes));
+        uint8_t* const slab = c->respair_slab.p;
+        CHK(enqueue_run_starts(c, R, U));
+        A.U = U;
+        A.row_start = R.row_start;
+        A.t_a = (int*)(slab + off[RT_A]); A.t_b = (int*)(slab + off[RT_B]); A.t_n = (uint32_t*)(slab + off[RT_N]);
+        A.t_dmin = (float*)(slab + off[RT_DMIN]); A.t_bits = (uint32_t*)(slab + off[RT_BITS]);
+        A.t_planes = (uint32_t*)(slab + off[RT_PLANES]); A.t_ctype = slab + off[RT_CTYPE];
+        hipLaunchKernelGGL(k_respair_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        CHK(check_launch(c, "arp_residue_pairs_launch: reduce"));
+    }
+    c->respair_count = U;
+    c->respair_valid = true;
+    *count = U;
+    return ARP_OK;
+}
+
+int arp_residue_pairs_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* res_b, uint32_t* n_contacts, float* dist_min,
+                            uint32_t* bit_count, uint8_t* ctype_mask, uint32_t* plane_count, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (!c->contacts_valid || !c->respair_valid) FAIL(c, ARP_E_ARG, "arp_residue_pairs_fetch: no table (arp_residue_pairs_launch after a pass)");
+    *count = c->respair_count;
+    if (c->respair_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_residue_pairs_fetch: output buffers too small");
+    const size_t U = (size_t)c->respair_count;
+    if (U == 0) return ARP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t off[RT_COLS], bytes;
+    respair_layout(U, off, &bytes);
+    CHK(persist_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->respair_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint8_t* const h = c->persist_stage;
+    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
+    put(res_a, RT_A, 4); put(res_b, RT_B, 4); put(n_contacts, RT_N, 4); put(dist_min, RT_DMIN, 4);
+    put(bit_count, RT_BITS, 4 * RESPAIR_BITS); put(plane_count, RT_PLANES, 4 * RESPAIR_PLANE_BAGS); put(ctype_mask, RT_CTYPE, 1);
     return ARP_OK;
 }
 

@@ -14,6 +14,8 @@
 //   k_persist_rekey   record p -> key a << (bbits + fbits) | b << fbits | f, payload distance | SIFt << 32 | type << 48
 //   (radix passes over the abits + bbits + fbits bits of the key, up to 9 bits a pass)
 //   k_persist_count   block t: the runs that BEGIN in tile t (a record whose (a, b) differs from its predecessor's)
+//   (k_persist_count / _scan / _starts take a RunArgs — sorted keys, a shift, the tile counts and the row starts — and nothing
+//   of this table: the residue-pair table of arp_respair.h finds its runs with them as well)
 //   k_persist_scan    one block: exclusive prefix of those counts over the tiles; their sum U = rows of the table
 //   (the host reads U — the one wait — and sizes the table)
 //   k_persist_starts  block t: row_start[prefix[t] + rank in the tile] = position of the run's first record
@@ -35,6 +37,20 @@
 #define PERSIST_TILE (PERSIST_THREADS * PERSIST_ITEMS)
 #define PERSIST_BITS 15          // SIFt bits with a column of their own (ARP_S_CLASH ... ARP_S_WEAK_POLAR)
 
+// What finding the runs of a sorted key array needs: a run = consecutive records with equal key >> shift.  A record whose
+// key >> shift is all ones (~0ull >> shift) never BEGINS a run: no key of the persistence table has 64 bits, and the
+// residue-pair table marks the records it leaves out that way (they sort last and trail the last run uncounted).
+struct RunArgs {
+    const unsigned long long* key;   // sorted
+    long long k;             // records
+    int shift;
+    int T;                   // tiles of PERSIST_TILE records
+    int* tile_rows;          // [T]: runs beginning in tile t, then their exclusive prefix
+    long long* total;        // [1]: U
+    int* row_start;          // [U + 1]: first record of row r; row_start[U] = k
+    long long U;
+};
+
 struct PersistArgs {
     // the bag of the last pass, in the order the pass left it
     const int* ci;
@@ -48,10 +64,7 @@ struct PersistArgs {
     // re-keyed records: written by k_persist_rekey, read (sorted) by everything after the radix passes
     unsigned long long* key;
     unsigned long long* val;
-    int T;                   // tiles of PERSIST_TILE records
-    int* tile_rows;          // [T]: runs beginning in tile t, then their exclusive prefix
-    long long* total;        // [1]: U
-    int* row_start;          // [U + 1]: first record of row r; row_start[U] = k
+    const int* row_start;    // [U + 1]: first record of row r; row_start[U] = k (RunArgs)
     long long U;
     // the table, one column after the other (persist_layout)
     int* t_a;
@@ -77,21 +90,22 @@ __global__ __launch_bounds__(256) void k_persist_rekey(PersistArgs A) {
 }
 
 // bit r of the result: record lo + r of the thread's PERSIST_ITEMS consecutive records begins a run
-__device__ __forceinline__ uint32_t persist_heads(const PersistArgs& A, long long lo) {
+__device__ __forceinline__ uint32_t persist_heads(const RunArgs& A, long long lo) {
     if (lo >= A.k) return 0u;
-    unsigned long long prev = lo > 0 ? (A.key[lo - 1] >> A.fbits) : ~0ull;      // (no pair has this id: a key has at most 63 bits)
+    const unsigned long long none = ~0ull >> A.shift;
+    unsigned long long prev = lo > 0 ? (A.key[lo - 1] >> A.shift) : none;
     uint32_t m = 0;
 #pragma unroll
     for (int r = 0; r < PERSIST_ITEMS; ++r) {
         if (lo + r >= A.k) break;
-        const unsigned long long cur = A.key[lo + r] >> A.fbits;
-        m |= (cur != prev ? 1u : 0u) << r;
+        const unsigned long long cur = A.key[lo + r] >> A.shift;
+        m |= (cur != prev && cur != none ? 1u : 0u) << r;
         prev = cur;
     }
     return m;
 }
 
-__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_count(PersistArgs A) {
+__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_count(RunArgs A) {
     __shared__ int s_w[PERSIST_THREADS / 64];
     int c = __popc(persist_heads(A, (long long)blockIdx.x * PERSIST_TILE + (long long)threadIdx.x * PERSIST_ITEMS));
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
@@ -105,7 +119,7 @@ __global__ __launch_bounds__(PERSIST_THREADS) void k_persist_count(PersistArgs A
 }
 
 // one block (SORT_THREADS threads: sort_block_scan)
-__global__ __launch_bounds__(SORT_THREADS) void k_persist_scan(PersistArgs A) {
+__global__ __launch_bounds__(SORT_THREADS) void k_persist_scan(RunArgs A) {
     __shared__ long long s_w[SORT_WAVES];
     long long run = 0;
     for (int t0 = 0; t0 < A.T; t0 += SORT_THREADS) {      // (block-uniform trip count)
@@ -119,7 +133,7 @@ __global__ __launch_bounds__(SORT_THREADS) void k_persist_scan(PersistArgs A) {
     if (threadIdx.x == 0) A.total[0] = run;
 }
 
-__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_starts(PersistArgs A) {
+__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_starts(RunArgs A) {
     __shared__ long long s_w[SORT_WAVES];
     static_assert(PERSIST_THREADS == SORT_THREADS, "sort_block_scan scans SORT_THREADS values");
     const long long lo = (long long)blockIdx.x * PERSIST_TILE + (long long)threadIdx.x * PERSIST_ITEMS;

@@ -578,6 +578,44 @@ int arp_models_persistence_launch(arp_ctx* ctx, int64_t* count);
 int arp_models_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first,
                                  int32_t* last, float* dist_min, float* dist_max, double* dist_sum,
                                  uint16_t* bit_count /* [cap][15] */, uint8_t* ctype_mask, int64_t* count);
+/* Residue-residue contact table of the last pass: the records of all five bags folded by residue ON THE DEVICE, so that only
+ * the table crosses PCIe.  It is made after a COMPLETE pass (arp_run_launch, arp_run_wait or the last arp_run_stage: all
+ * five bags valid; the five launched one by one since the last input change count as one) from the bags as the pass left them.  Each record contributes the residues of its two partners:
+ *   atom-atom (i, j)            res_id[i],        res_id[j]
+ *   atom-plane (atom, ring)     res_id[atom],     ring_res[ring]
+ *   plane-plane (bgn, end)      ring_res[bgn],    ring_res[end]
+ *   group-group (bgn, end)      amide_res[bgn],   amide_res[end]
+ *   group-plane (amide, ring)   amide_res[amide], ring_res[ring]
+ * as the unordered pair res_a = min, res_b = max (bgn < end of a record says nothing about the order of the residues).  A
+ * record with a residue of -1 (a ring or amide without one) is left out.  Atom-atom records never have res_a == res_b (the
+ * reference skips intra-residue pairs, I:729); records of the other four bags can.  One row per distinct (res_a, res_b) with
+ * at least one record, rows in ascending (res_a, res_b):
+ *   res_a, res_b   int32      resident residue indices, res_a <= res_b (several structures or models resident: the indices of
+ *                             the concatenation, so the table of each is a contiguous range of rows by res_a)
+ *   n_contacts     uint32     atom-atom records of the pair
+ *   dist_min       float32    smallest atom-atom distance of the pair, the bag's own float32; +inf when n_contacts == 0
+ *   bit_count      uint32[ARP_RESPAIR_BITS]  atom-atom records with SIFt bit k (ARP_S_CLASH ... ARP_S_WEAK_POLAR)
+ *   ctype_mask     uint8      OR of 1 << ARP_CT_* over the atom-atom records
+ *   plane_count    uint32[4]  records of the atom-plane, plane-plane, group-group and group-plane bags, in that order
+ * Every column is a count, a minimum or an OR: the table is a function of the bags as sets of records, whatever order the pass
+ * wrote them in.  The bags stay what they were: arp_fetch_packed and the *_fetch calls return the same before, after and
+ * without these calls, in either layout (arp_set_packed_layout), sorted or not (arp_set_sort_after_pass,
+ * arp_atom_contacts_sort).
+ *
+ * arp_residue_pairs_launch: enqueues the reduction on the context's stream and waits once, for *count = rows.  The table is
+ * a result of the last pass and is voided with it: by every input change and by the next launch that fills any bag.  A second
+ * call on the same results launches nothing and returns the same count.  No record at all: 0 rows, ARP_OK.  ARP_E_ARG without
+ * the results of a complete pass (arp_atom_contacts_launch alone is none) and on a shard of a distributed structure;
+ * ARP_E_CAPACITY when the five bags together hold 2^31 records or more.
+ *
+ * arp_residue_pairs_fetch: the table with one device-to-host copy of one piece (its columns on 256-byte boundaries, through a
+ * page-locked stage); any column pointer may be NULL; bit_count = uint32[cap][ARP_RESPAIR_BITS], plane_count =
+ * uint32[cap][4].  ARP_E_CAPACITY with *count = rows when cap is too small; ARP_E_ARG without a launch. */
+#define ARP_RESPAIR_BITS 15
+int arp_residue_pairs_launch(arp_ctx* ctx, int64_t* count);
+int arp_residue_pairs_fetch(arp_ctx* ctx, int64_t cap, int32_t* res_a, int32_t* res_b, uint32_t* n_contacts,
+                            float* dist_min, uint32_t* bit_count /* [cap][15] */, uint8_t* ctype_mask,
+                            uint32_t* plane_count /* [cap][4] */, int64_t* count);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
