@@ -38,6 +38,7 @@ SYMBOLS = (
     'arp_atom_contacts_sort', 'arp_fetch_packed', 'arp_set_topology', 'arp_set_models', 'arp_models_planes',
     'arp_models_persistence_launch', 'arp_models_persistence_fetch', 'arp_set_compact_lookback',
     'arp_residue_pairs_launch', 'arp_residue_pairs_fetch',
+    'arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch',
 )
 
 # the persistence table (arp_models_persistence_*): its columns, the SIFt bits counted per row, and ARP_PERSIST_STAGE_MAX
@@ -52,6 +53,12 @@ RESPAIR_BITS = 15
 RESPAIR_COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_contacts', np.uint32), ('dist_min', np.float32),
                    ('bit_count', np.uint32), ('ctype_mask', np.uint8), ('plane_count', np.uint32))
 _RESPAIR_WIDTH = {'bit_count': RESPAIR_BITS, 'plane_count': 4}
+# the residue persistence table (arp_models_residue_persistence_*): its columns in the order of the fetch's arguments
+RESPERSIST_BITS = 15
+RESPERSIST_COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                      ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
+                      ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8))
+_RESPERSIST_WIDTH = {'class_models': 5, 'bit_models': RESPERSIST_BITS}
 
 _lib = None
 
@@ -196,6 +203,8 @@ def load():
     L.arp_models_persistence_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.arp_residue_pairs_launch.argtypes = [vp, C.POINTER(i64)]
     L.arp_residue_pairs_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    L.arp_models_residue_persistence_launch.argtypes = [vp, C.POINTER(i64)]
+    L.arp_models_residue_persistence_fetch.argtypes = [vp, i64] + [vp] * 12 + [C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -720,6 +729,20 @@ class Context:
         t = {k: np.empty((U, _RESPAIR_WIDTH[k]) if k in _RESPAIR_WIDTH else U, dt) for k, dt in RESPAIR_COLUMNS}
         self._check(self._L.arp_residue_pairs_fetch(self._h, U, *(_p(t[k]) for k, _ in RESPAIR_COLUMNS), C.byref(n)),
                     'arp_residue_pairs_fetch')
+        return t
+
+    def models_residue_persistence(self):
+        """Residue contact persistence over the resident models of the last complete pass, reduced on the device
+        (arp_models_residue_persistence_*): one row per pair of topology residues with a record in any bag of any model,
+        rows in ascending (res_a, res_b).  Returns a dict of the twelve columns ``RESPERSIST_COLUMNS`` (``class_models`` as
+        [U, 5], ``bit_models`` as [U, 15]; see ``arpeggio_amd.residue_persistence``).  Only the table is copied to the host;
+        the bags of the pass and the two other tables stay fetchable as before."""
+        n = C.c_int64(0)
+        self._check(self._L.arp_models_residue_persistence_launch(self._h, C.byref(n)), 'arp_models_residue_persistence_launch')
+        U = int(n.value)
+        t = {k: np.empty((U, _RESPERSIST_WIDTH[k]) if k in _RESPERSIST_WIDTH else U, dt) for k, dt in RESPERSIST_COLUMNS}
+        self._check(self._L.arp_models_residue_persistence_fetch(self._h, U, *(_p(t[k]) for k, _ in RESPERSIST_COLUMNS), C.byref(n)),
+                    'arp_models_residue_persistence_fetch')
         return t
 
     def set_blob(self, blob, counts=None):

@@ -594,6 +594,8 @@ class EnsembleComplex:
         self._results = None
         self.persistence = None          # the table of run_persistence and the models it covers
         self.persistence_models = 0
+        self.residue_persistence = None  # the table of run_residue_persistence and the models it covers
+        self.residue_persistence_models = 0
 
     @property
     def n_models(self):
@@ -701,6 +703,29 @@ class EnsembleComplex:
         self._results = None
         self.stats = self._ctx.stats()
         return residue_pairs.split(t, np.arange(self.n_models + 1, dtype=np.int64) * self.pc.n_residues)
+
+    def run_residue_persistence(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, accumulate=False):
+        """Residue contact persistence over the models — a residue contact-frequency map: the selection handling and the pass
+        of ``run_persistence``, then the records of all five bags of all models reduced ON THE DEVICE to one row per pair of
+        topology residues (``arpeggio_amd.residue_persistence`` describes the table) — and only that table fetched, into
+        ``self.residue_persistence`` (also returned).  No bag is copied to the host: ``model(k)`` has no results after this
+        call (``run_arpeggio`` gives those).  ``accumulate=True`` merges the table into that of the calls before it, this
+        call's models following theirs (``self.residue_persistence_models`` counts them), as ``run_persistence`` does for the
+        atom table."""
+        from .. import residue_persistence as _respersist
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        t = self._ctx.models_residue_persistence()
+        self._results = None
+        if accumulate and self.residue_persistence is not None:
+            self.residue_persistence = _respersist.merge(self.residue_persistence, t, self.residue_persistence_models)
+            self.residue_persistence_models += self.n_models
+        else:
+            self.residue_persistence, self.residue_persistence_models = t, self.n_models
+        self.stats = self._ctx.stats()
+        return self.residue_persistence
 
     def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
         """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""

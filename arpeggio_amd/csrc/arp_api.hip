@@ -29,6 +29,7 @@
 #include "arp_sort.h"
 #include "arp_persist.h"
 #include "arp_respair.h"
+#include "arp_respersist.h"
 #include "arp_blob.h"
 
 namespace {
@@ -470,6 +471,11 @@ struct arp_ctx {
     DevBuf<uint8_t> respair_slab;         // the table's seven columns in one piece (respair_layout)
     int64_t respair_count = 0;            // rows of the table
     bool respair_valid = false;           // respair_slab holds the table of the last pass's results
+    // ---- residue persistence table of the resident models (arp_respersist.h; arp_models_residue_persistence_launch / _fetch):
+    // the same scratch again, and voided wherever the residue-pair table is — it is made from the same five bags
+    DevBuf<uint8_t> respersist_slab;      // the table's twelve columns in one piece (respersist_layout)
+    int64_t respersist_count = 0;         // rows of the table
+    bool respersist_valid = false;        // respersist_slab holds the table of the last pass's results
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -693,8 +699,9 @@ enum : unsigned {
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
 //   persistence table of the resident models (arp_models_persistence_launch) is made from the atom-atom bag and goes with it;
-//   the residue-pair table (arp_residue_pairs_launch) is made from all five and goes with any of them (finish_contacts,
-//   finish_bag: the next launch that refills a bag).
+//   the residue-pair table (arp_residue_pairs_launch) and the residue persistence table
+//   (arp_models_residue_persistence_launch) are made from all five and go with any of them (finish_contacts, finish_bag: the
+//   next launch that refills a bag).
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -728,6 +735,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->contacts_valid = false;
         c->persist_valid = false;
         c->respair_valid = false;
+        c->respersist_valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1901,6 +1909,7 @@ bool finish_contacts(arp_ctx* c) {
     c->contacts_sorted = false;
     c->persist_valid = false;
     c->respair_valid = false;
+    c->respersist_valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2034,6 +2043,7 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     b.valid = true;
     ++b.version;
     c->respair_valid = false;
+    c->respersist_valid = false;
     return false;
 }
 int grow_pairs(arp_ctx* c) {
@@ -2240,6 +2250,7 @@ void arp_destroy(arp_ctx* c) {
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
     c->sort_persist.release(); c->persist_tiles.release(); c->persist_rows.release(); c->persist_total.release(); c->persist_slab.release();
     c->respair_slab.release();
+    c->respersist_slab.release();
     if (c->persist_stage) (void)hipHostFree(c->persist_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4184,28 +4195,48 @@ int respair_key_bits(int64_t nres, int rbits, bool planes) {
     const bool tie = planes && nres - 1 == ((int64_t)1 << rbits) - 1;
     return 2 * rbits + (tie ? 1 : 0);
 }
+// What a residue table (this one and arp_respersist.h's) reads of a complete pass besides the atom-atom bag: the four ring /
+// amide bags as the re-key kernels walk them, placed behind the atom-atom records; the records of all five bags (k), of the four
+// (planes) and of the largest of the four; and the capacity the sort scratch is sized from — the capacities of the bags'
+// columns, so that it is allocated once per structure size.
+struct FiveBags {
+    RespairBag bag[RESPAIR_PLANE_BAGS];      // classes 1 ... 4
+    size_t k, planes, cap;
+    int64_t largest;
+};
+bool five_bags_complete(const arp_ctx* c) {
+    return !c->pass_pending && c->contacts_valid && c->bag_ap.valid && c->bag_pp.valid && c->bag_gg.valid && c->bag_gp.valid;
+}
+FiveBags five_bags(const arp_ctx* c) {
+    const Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};
+    const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
+                                                      {c->am_res.p, c->am_res.p}, {c->am_res.p, c->ring_res.p}};
+    FiveBags B{};
+    B.k = (size_t)c->n_contacts;
+    B.cap = std::max((size_t)c->n_contacts, c->out_i.cap);
+    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) {
+        const Bag& b = *bags[m];
+        B.bag[m] = RespairBag{b.a.p, b.b.p, res_of[m][0], res_of[m][1], (long long)b.count, (long long)B.k};
+        B.k += (size_t)b.count;
+        B.planes += (size_t)b.count;
+        B.cap += std::max((size_t)b.count, b.cap);
+        B.largest = std::max(B.largest, b.count);
+    }
+    return B;
+}
 }  // namespace
 
 int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
     if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: not for a shard of a distributed structure");
-    Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};      // classes 1 ... 4
-    bool complete = !c->pass_pending && c->contacts_valid;
-    for (const Bag* b : bags) complete = complete && b->valid;
-    if (!complete) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: no results of a complete pass (arp_run_launch first)");
+    if (!five_bags_complete(c)) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: no results of a complete pass (arp_run_launch first)");
     if (c->respair_valid) { *count = c->respair_count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     RespairArgs A{};
     A.k_aa = (long long)c->n_contacts;
-    size_t k = (size_t)c->n_contacts, planes = 0;
-    const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
-                                                      {c->am_res.p, c->am_res.p}, {c->am_res.p, c->ring_res.p}};
-    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) {
-        const Bag& b = *bags[m];
-        A.bag[m] = RespairBag{b.a.p, b.b.p, res_of[m][0], res_of[m][1], (long long)b.count, (long long)k};
-        k += (size_t)b.count;
-        planes += (size_t)b.count;
-    }
+    const FiveBags B = five_bags(c);
+    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
+    const size_t k = B.k, planes = B.planes;
     c->respair_count = 0;
     if (k == 0) { c->respair_valid = true; *count = 0; return ARP_OK; }
     // (a left-out record keeps its slot up to the reduction, so every record of the five bags counts here, kept or not)
@@ -4214,19 +4245,13 @@ int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
     A.res_id = c->res_id.p;
     A.rbits = id_bits(std::max<int64_t>(c->nres - 1, 1));
     const int keybits = respair_key_bits(c->nres, A.rbits, planes > 0);
-    // ---- scratch: sized from the capacities of the bags' columns, so that it is allocated once per structure size
+    // ---- scratch
     SortScratch& s = c->sort_persist;
-    size_t cap = std::max((size_t)c->n_contacts, c->out_i.cap);
-    for (const Bag* b : bags) cap += std::max((size_t)b->count, b->cap);
-    CHK(reserve_key_sort(c, s, k, cap));
+    CHK(reserve_key_sort(c, s, k, B.cap));
     // ---- (res_a, res_b) keys of all five bags, sorted by every bit
     A.key = s.key[0].p; A.val = s.val[0].p;
     if (A.k_aa > 0) hipLaunchKernelGGL(k_respair_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
-    if (planes > 0) {
-        int64_t largest = 0;
-        for (const Bag* b : bags) largest = std::max(largest, b->count);
-        hipLaunchKernelGGL(k_respair_rekey_planes, dim3(nblocks(largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
-    }
+    if (planes > 0) hipLaunchKernelGGL(k_respair_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
     int sorted = 0;
     enqueue_key_sort(c, s, k, keybits, &sorted);
     A.key = s.key[sorted].p; A.val = s.val[sorted].p;
@@ -4274,6 +4299,112 @@ int arp_residue_pairs_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* re
     auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
     put(res_a, RT_A, 4); put(res_b, RT_B, 4); put(n_contacts, RT_N, 4); put(dist_min, RT_DMIN, 4);
     put(bit_count, RT_BITS, 4 * RESPAIR_BITS); put(plane_count, RT_PLANES, 4 * RESPAIR_PLANE_BAGS); put(ctype_mask, RT_CTYPE, 1);
+    return ARP_OK;
+}
+
+// ---- residue contact persistence over the resident models (arp_respersist.h) ------------------------------------------
+namespace {
+// Layout of the table's slab: the twelve columns one after the other, each on a 256-byte boundary (the float64 column first).
+enum { ST_DSUM = 0, ST_A, ST_B, ST_FIRST, ST_LAST, ST_N, ST_DMIN, ST_DMAX, ST_NMODELS, ST_CLS, ST_BITS, ST_CTYPE, ST_COLS };
+void respersist_layout(size_t U, size_t off[ST_COLS], size_t* bytes) {
+    static const size_t es[ST_COLS] = {8, 4, 4, 4, 4, 4, 4, 4, 2, 2 * RESPERSIST_CLASSES, 2 * RESPERSIST_BITS, 1};
+    size_t at = 0;
+    for (int q = 0; q < ST_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
+    *bytes = at;
+}
+// Bits of the key the sort covers: res_a << (rbits + fbits) | res_b << fbits | f, and one bit more where the all-ones key of a
+// left-out record would otherwise tie with a real record in the sorted bits — the pair (nres_t - 1, nres_t - 1) of a ring /
+// amide bag in model F - 1, when nres_t - 1 and F - 1 are all ones themselves (bit 2 rbits + fbits is set in ~0 and in no
+// record: the left-out records then sort last by it).
+int respersist_key_bits(int64_t nres_t, int64_t F, int rbits, int fbits, bool planes) {
+    const bool tie = planes && nres_t - 1 == ((int64_t)1 << rbits) - 1 && F - 1 == ((int64_t)1 << fbits) - 1;
+    return 2 * rbits + fbits + (tie ? 1 : 0);
+}
+}  // namespace
+
+int arp_models_residue_persistence_launch(arp_ctx* c, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: not for a shard of a distributed structure");
+    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: no models resident (arp_set_models)");
+    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: more than 65 535 models (the table counts models in uint16)");
+    if (!five_bags_complete(c)) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: no results of a complete pass over the resident models (arp_run_launch first)");
+    if (c->respersist_valid) { *count = c->respersist_count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    RespersistArgs A{};
+    A.k_aa = (long long)c->n_contacts;
+    const FiveBags B = five_bags(c);
+    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
+    const size_t k = B.k, planes = B.planes;
+    const int64_t F = c->models_n, nres_t = c->nres / F;
+    c->respersist_count = 0;
+    if (k == 0 || nres_t <= 0) { c->respersist_valid = true; *count = 0; return ARP_OK; }
+    // (a left-out record keeps its slot up to the reduction, so every record of the five bags counts here, kept or not)
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: 2^31 records or more");
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.res_id = c->res_id.p;
+    A.nres_t = (uint32_t)nres_t;
+    A.rbits = id_bits(std::max<int64_t>(nres_t - 1, 1));
+    A.fbits = id_bits(std::max<int64_t>(F - 1, 1));
+    if (2 * A.rbits + A.fbits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: (residue, residue, model) does not fit a 63-bit key");
+    const int keybits = respersist_key_bits(nres_t, F, A.rbits, A.fbits, planes > 0);
+    // ---- scratch
+    SortScratch& s = c->sort_persist;
+    CHK(reserve_key_sort(c, s, k, B.cap));
+    // ---- (res_a, res_b, f) keys of all five bags, sorted by every bit
+    A.key = s.key[0].p; A.val = s.val[0].p;
+    if (A.k_aa > 0) hipLaunchKernelGGL(k_respersist_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
+    if (planes > 0) hipLaunchKernelGGL(k_respersist_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
+    int sorted = 0;
+    enqueue_key_sort(c, s, k, keybits, &sorted);
+    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
+    // ---- rows: a run is one residue pair over its models; count, scan; the host learns U (the one wait)
+    RunArgs R{};
+    R.key = A.key; R.k = (long long)k; R.shift = A.fbits;
+    long long U = 0;
+    CHK(count_runs(c, R, &U, "arp_models_residue_persistence_launch: sort / count"));
+    if (U < 0 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_models_residue_persistence_launch: row count out of range");
+    if (U > 0) {      // (0: every record was left out)
+        size_t off[ST_COLS], bytes;
+        respersist_layout((size_t)U, off, &bytes);
+        HIPCHK(c, c->respersist_slab.reserve(bytes));
+        uint8_t* const slab = c->respersist_slab.p;
+        CHK(enqueue_run_starts(c, R, U));
+        A.U = U;
+        A.row_start = R.row_start;
+        A.t_dsum = (double*)(slab + off[ST_DSUM]); A.t_a = (int*)(slab + off[ST_A]); A.t_b = (int*)(slab + off[ST_B]);
+        A.t_first = (int*)(slab + off[ST_FIRST]); A.t_last = (int*)(slab + off[ST_LAST]); A.t_n = (uint32_t*)(slab + off[ST_N]);
+        A.t_dmin = (float*)(slab + off[ST_DMIN]); A.t_dmax = (float*)(slab + off[ST_DMAX]);
+        A.t_nmodels = (uint16_t*)(slab + off[ST_NMODELS]); A.t_cls = (uint16_t*)(slab + off[ST_CLS]);
+        A.t_bits = (uint16_t*)(slab + off[ST_BITS]); A.t_ctype = slab + off[ST_CTYPE];
+        hipLaunchKernelGGL(k_respersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        CHK(check_launch(c, "arp_models_residue_persistence_launch: reduce"));
+    }
+    c->respersist_count = U;
+    c->respersist_valid = true;
+    *count = U;
+    return ARP_OK;
+}
+
+int arp_models_residue_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* res_b, uint16_t* n_models, int32_t* first,
+                                         int32_t* last, uint32_t* n_contacts, uint16_t* class_models, uint16_t* bit_models,
+                                         float* dist_min, float* dist_max, double* dist_sum, uint8_t* ctype_mask, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    if (!c->contacts_valid || !c->respersist_valid) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_fetch: no table (arp_models_residue_persistence_launch after a pass)");
+    *count = c->respersist_count;
+    if (c->respersist_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_fetch: output buffers too small");
+    const size_t U = (size_t)c->respersist_count;
+    if (U == 0) return ARP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t off[ST_COLS], bytes;
+    respersist_layout(U, off, &bytes);
+    CHK(persist_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->respersist_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint8_t* const h = c->persist_stage;
+    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
+    put(dist_sum, ST_DSUM, 8); put(res_a, ST_A, 4); put(res_b, ST_B, 4); put(first, ST_FIRST, 4); put(last, ST_LAST, 4);
+    put(n_contacts, ST_N, 4); put(dist_min, ST_DMIN, 4); put(dist_max, ST_DMAX, 4); put(n_models, ST_NMODELS, 2);
+    put(class_models, ST_CLS, 2 * RESPERSIST_CLASSES); put(bit_models, ST_BITS, 2 * RESPERSIST_BITS); put(ctype_mask, ST_CTYPE, 1);
     return ARP_OK;
 }
 

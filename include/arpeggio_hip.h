@@ -616,6 +616,53 @@ int arp_residue_pairs_launch(arp_ctx* ctx, int64_t* count);
 int arp_residue_pairs_fetch(arp_ctx* ctx, int64_t cap, int32_t* res_a, int32_t* res_b, uint32_t* n_contacts,
                             float* dist_min, uint32_t* bit_count /* [cap][15] */, uint8_t* ctype_mask,
                             uint32_t* plane_count /* [cap][4] */, int64_t* count);
+/* Residue contact persistence over the resident models: the product of the two tables above — per pair of TOPOLOGY residues, in
+ * how many models they touch, through which record classes, and how closely.  It is made after a COMPLETE pass over F
+ * resident models (arp_set_models; all five bags valid, the condition of arp_residue_pairs_launch) from the bags as the pass
+ * left them, never from the sorted slab.  A record contributes the residues of its two partners exactly as above (res_id of
+ * an atom, ring_res of a ring, amide_res of an amide): resident indices.  With nres_t = nres / F the record's model is
+ * f = res / nres_t (both partners lie in the same model), and the topology pair is res_a = min - f nres_t,
+ * res_b = max - f nres_t.  A record with a residue of -1 is left out.  One row per distinct (res_a, res_b) with at least one
+ * kept record in at least one model, rows in ascending (res_a, res_b):
+ *   res_a, res_b   int32      topology residue indices, res_a <= res_b (equal only through ring / amide records)
+ *   n_models       uint16     models with at least one kept record of the pair, in any bag
+ *   first, last    int32      lowest / highest 0-based model index among those
+ *   n_contacts     uint32     atom-atom records of the pair over all models
+ *   class_models   uint16[5]  models with at least one record of class m: 0 atom-atom, 1 atom-plane, 2 plane-plane,
+ *                             3 group-group, 4 group-plane
+ *   bit_models     uint16[ARP_RESPERSIST_BITS]  for SIFt bit k (ARP_S_CLASH ... ARP_S_WEAK_POLAR): models in which at least
+ *                             one atom-atom record of the pair has it
+ *   dist_min       float32    smallest atom-atom distance over all models, the bag's own float32; +inf when
+ *                             class_models[0] == 0
+ *   dist_max       float32    largest of the PER-MODEL smallest atom-atom distances; -inf when class_models[0] == 0
+ *   dist_sum       float64    the per-model smallest distances (models with an atom-atom record only) widened to float64 and
+ *                             added one by one in ascending model order, starting from 0.0 (defined to the bit; the mean
+ *                             closest approach is dist_sum / class_models[0])
+ *   ctype_mask     uint8      OR of 1 << ARP_CT_* over the atom-atom records
+ * Every per-model quantity is an OR, a minimum or a presence, so the order in which the pass wrote a model's records cannot
+ * show; the one ordered operation is the sum over the models, and its order is fixed.  The bags, the persistence table and the
+ * residue-pair table stay what they were: each returns the same before, after and without these calls, in either layout
+ * (arp_set_packed_layout), with arp_set_sort_after_pass on or off.  The three tables share their scratch and none needs it
+ * once made: making one voids no other.
+ *
+ * arp_models_residue_persistence_launch: enqueues the reduction on the context's stream and waits once, for *count = rows.
+ * The table is a result of the last pass and is voided with it, wherever the residue-pair table is: by every input change
+ * and by the next launch that fills any bag.  A second call on the same results launches nothing and returns the same
+ * count.  No record at all: 0 rows, ARP_OK.  ARP_E_ARG: no models resident, no results of a complete pass, more than 65 535
+ * models (the uint16 columns), a shard.  ARP_E_CAPACITY: the five bags together hold 2^31 records or more, or
+ * (residue, residue, model) does not fit a 63-bit key.
+ *
+ * arp_models_residue_persistence_fetch: the table with one device-to-host copy of one piece (its columns on 256-byte
+ * boundaries, the float64 column first, through a page-locked stage); any column pointer may be NULL; class_models =
+ * uint16[cap][5], bit_models = uint16[cap][ARP_RESPERSIST_BITS].  ARP_E_CAPACITY with *count = rows when cap is too small;
+ * ARP_E_ARG without a launch. */
+#define ARP_RESPERSIST_BITS 15
+int arp_models_residue_persistence_launch(arp_ctx* ctx, int64_t* count);
+int arp_models_residue_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* res_a, int32_t* res_b, uint16_t* n_models,
+                                         int32_t* first, int32_t* last, uint32_t* n_contacts,
+                                         uint16_t* class_models /* [cap][5] */, uint16_t* bit_models /* [cap][15] */,
+                                         float* dist_min, float* dist_max, double* dist_sum, uint8_t* ctype_mask,
+                                         int64_t* count);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
