@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from . import tables
 from .core.exceptions import NativeLibraryError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,24 +42,10 @@ SYMBOLS = (
     'arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch',
 )
 
-# the persistence table (arp_models_persistence_*): its columns, the SIFt bits counted per row, and ARP_PERSIST_STAGE_MAX
-PERSIST_BITS = 15
+# the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
+PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = tables.N_BITS
 PERSIST_STAGE_MAX = 0
-PERSIST_COLUMNS = (('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
-                   ('dist_min', np.float32), ('dist_max', np.float32), ('dist_sum', np.float64), ('bit_count', np.uint16),
-                   ('ctype_mask', np.uint8))
-_PERSIST_FETCH_ORDER = tuple(k for k, _ in PERSIST_COLUMNS)
-# the residue-pair table (arp_residue_pairs_*): its columns in the order of arp_residue_pairs_fetch's arguments
-RESPAIR_BITS = 15
-RESPAIR_COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_contacts', np.uint32), ('dist_min', np.float32),
-                   ('bit_count', np.uint32), ('ctype_mask', np.uint8), ('plane_count', np.uint32))
-_RESPAIR_WIDTH = {'bit_count': RESPAIR_BITS, 'plane_count': 4}
-# the residue persistence table (arp_models_residue_persistence_*): its columns in the order of the fetch's arguments
-RESPERSIST_BITS = 15
-RESPERSIST_COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
-                      ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
-                      ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8))
-_RESPERSIST_WIDTH = {'class_models': 5, 'bit_models': RESPERSIST_BITS}
+PERSIST_COLUMNS, RESPAIR_COLUMNS, RESPERSIST_COLUMNS = tables.PERSIST.columns, tables.RESPAIR.columns, tables.RESPERSIST.columns
 
 _lib = None
 
@@ -704,18 +691,21 @@ class Context:
         bags, _ = self.fetch_packed()
         return split_models(bags, self._models)
 
+    def _table(self, launch, fetch, spec):
+        """One device-reduced table: launch (the row count), then one fetch of every column of ``spec``."""
+        n = C.c_int64(0)
+        self._check(getattr(self._L, launch)(self._h, C.byref(n)), launch)
+        U = int(n.value)
+        t = tables.alloc(spec, U)
+        self._check(getattr(self._L, fetch)(self._h, U, *(_p(t[k]) for k, _ in spec.columns), C.byref(n)), fetch)
+        return t
+
     def models_persistence(self):
         """Contact persistence over the resident models of the last pass, reduced on the device (arp_models_persistence_*):
         one row per distinct topology pair (a, b) in ascending (a, b).  Returns a dict of the ten columns ``PERSIST_COLUMNS``
         (``bit_count`` as [U, 15]; see ``arpeggio_amd.persistence``).  Only the table is copied to the host; the bags of the
         pass stay fetchable as before."""
-        n = C.c_int64(0)
-        self._check(self._L.arp_models_persistence_launch(self._h, C.byref(n)), 'arp_models_persistence_launch')
-        U = int(n.value)
-        t = {k: np.empty((U, PERSIST_BITS) if k == 'bit_count' else U, dt) for k, dt in PERSIST_COLUMNS}
-        self._check(self._L.arp_models_persistence_fetch(self._h, U, *(_p(t[k]) for k in _PERSIST_FETCH_ORDER), C.byref(n)),
-                    'arp_models_persistence_fetch')
-        return t
+        return self._table('arp_models_persistence_launch', 'arp_models_persistence_fetch', tables.PERSIST)
 
     def residue_pairs(self):
         """The residue-residue contact table of the last complete pass, reduced on the device (arp_residue_pairs_*): one row
@@ -723,13 +713,7 @@ class Context:
         of the seven columns ``RESPAIR_COLUMNS`` (``bit_count`` as [U, 15], ``plane_count`` as [U, 4]; see
         ``arpeggio_amd.residue_pairs``).  Only the table is copied to the host; the bags of the pass stay fetchable as
         before.  With a batch or models resident the ids are those of the concatenation (``residue_pairs.split``)."""
-        n = C.c_int64(0)
-        self._check(self._L.arp_residue_pairs_launch(self._h, C.byref(n)), 'arp_residue_pairs_launch')
-        U = int(n.value)
-        t = {k: np.empty((U, _RESPAIR_WIDTH[k]) if k in _RESPAIR_WIDTH else U, dt) for k, dt in RESPAIR_COLUMNS}
-        self._check(self._L.arp_residue_pairs_fetch(self._h, U, *(_p(t[k]) for k, _ in RESPAIR_COLUMNS), C.byref(n)),
-                    'arp_residue_pairs_fetch')
-        return t
+        return self._table('arp_residue_pairs_launch', 'arp_residue_pairs_fetch', tables.RESPAIR)
 
     def models_residue_persistence(self):
         """Residue contact persistence over the resident models of the last complete pass, reduced on the device
@@ -737,13 +721,7 @@ class Context:
         rows in ascending (res_a, res_b).  Returns a dict of the twelve columns ``RESPERSIST_COLUMNS`` (``class_models`` as
         [U, 5], ``bit_models`` as [U, 15]; see ``arpeggio_amd.residue_persistence``).  Only the table is copied to the host;
         the bags of the pass and the two other tables stay fetchable as before."""
-        n = C.c_int64(0)
-        self._check(self._L.arp_models_residue_persistence_launch(self._h, C.byref(n)), 'arp_models_residue_persistence_launch')
-        U = int(n.value)
-        t = {k: np.empty((U, _RESPERSIST_WIDTH[k]) if k in _RESPERSIST_WIDTH else U, dt) for k, dt in RESPERSIST_COLUMNS}
-        self._check(self._L.arp_models_residue_persistence_fetch(self._h, U, *(_p(t[k]) for k, _ in RESPERSIST_COLUMNS), C.byref(n)),
-                    'arp_models_residue_persistence_fetch')
-        return t
+        return self._table('arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch', tables.RESPERSIST)
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

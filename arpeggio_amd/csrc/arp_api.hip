@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -243,6 +244,13 @@ struct HintKey {
 
 }  // namespace
 
+// a table reduced on the device: its columns in one piece (table_layout), its rows, and whether it is that of the last results
+struct ResultTable {
+    DevBuf<uint8_t> slab;
+    int64_t count = 0;
+    bool valid = false;
+};
+
 struct arp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless arp_use_stream)
@@ -457,25 +465,15 @@ struct arp_ctx {
     DevBuf<float> models_xyz;
     DevBuf<double> models_box;
     int64_t models_n = 0;
-    // ---- contact persistence over the resident models (arp_persist.h; arp_models_persistence_launch / _fetch)
-    SortScratch sort_persist;             // the re-keyed records, double-buffered, and the digit tables of their sort
-    DevBuf<int> persist_tiles, persist_rows;
-    DevBuf<long long> persist_total;
-    DevBuf<uint8_t> persist_slab;         // the table's ten columns in one piece (persist_layout)
-    uint8_t* persist_stage = nullptr;     // page-locked host side of the one copy (its first word also receives U)
-    size_t persist_stage_cap = 0;
-    int64_t persist_count = 0;            // rows of the table
-    bool persist_valid = false;           // persist_slab holds the table of the last launch's results
-    // ---- residue-pair table of the last pass (arp_respair.h; arp_residue_pairs_launch / _fetch): its scratch is the persistence
-    // table's (sort_persist, persist_tiles / _rows / _total, persist_stage) — both tables are results and are voided together
-    DevBuf<uint8_t> respair_slab;         // the table's seven columns in one piece (respair_layout)
-    int64_t respair_count = 0;            // rows of the table
-    bool respair_valid = false;           // respair_slab holds the table of the last pass's results
-    // ---- residue persistence table of the resident models (arp_respersist.h; arp_models_residue_persistence_launch / _fetch):
-    // the same scratch again, and voided wherever the residue-pair table is — it is made from the same five bags
-    DevBuf<uint8_t> respersist_slab;      // the table's twelve columns in one piece (respersist_layout)
-    int64_t respersist_count = 0;         // rows of the table
-    bool respersist_valid = false;        // respersist_slab holds the table of the last pass's results
+    // ---- the tables reduced on the device from the results of a pass (make_table / table_fetch): contact persistence over the
+    // resident models (arp_persist.h), the residue-pair table (arp_respair.h), residue persistence (arp_respersist.h).  They share
+    // the scratch — none needs it once it is made — and are results: voided with the bags they are made from
+    SortScratch table_sort;               // the re-keyed records, double-buffered, and the digit tables of their sort
+    DevBuf<int> table_tiles, table_rows;  // run detection (arp_runs.h)
+    DevBuf<long long> table_total;
+    uint8_t* table_stage = nullptr;       // page-locked host side of a fetch's one copy (its first word also receives U)
+    size_t table_stage_cap = 0;
+    ResultTable persist, respair, respersist;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -733,9 +731,9 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->models_n = 0;
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
-        c->persist_valid = false;
-        c->respair_valid = false;
-        c->respersist_valid = false;
+        c->persist.valid = false;
+        c->respair.valid = false;
+        c->respersist.valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1907,9 +1905,9 @@ bool finish_contacts(arp_ctx* c) {
     c->contacts_expected = (int64_t)np;
     c->contacts_valid = true;
     c->contacts_sorted = false;
-    c->persist_valid = false;
-    c->respair_valid = false;
-    c->respersist_valid = false;
+    c->persist.valid = false;
+    c->respair.valid = false;
+    c->respersist.valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2042,8 +2040,8 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     b.count = (int64_t)k;
     b.valid = true;
     ++b.version;
-    c->respair_valid = false;
-    c->respersist_valid = false;
+    c->respair.valid = false;
+    c->respersist.valid = false;
     return false;
 }
 int grow_pairs(arp_ctx* c) {
@@ -2248,10 +2246,9 @@ void arp_destroy(arp_ctx* c) {
     c->bag_ap.release(); c->bag_pp.release(); c->bag_gg.release(); c->bag_gp.release();
     c->bag_pack.release(); c->bag_perm.release();
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
-    c->sort_persist.release(); c->persist_tiles.release(); c->persist_rows.release(); c->persist_total.release(); c->persist_slab.release();
-    c->respair_slab.release();
-    c->respersist_slab.release();
-    if (c->persist_stage) (void)hipHostFree(c->persist_stage);
+    c->table_sort.release(); c->table_tiles.release(); c->table_rows.release(); c->table_total.release();
+    c->persist.slab.release(); c->respair.slab.release(); c->respersist.slab.release();
+    if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
     c->rec_home.release(); c->rec_face[0].release(); c->rec_face[1].release(); c->sh_scan.release(); c->sh_src.release();
@@ -4023,24 +4020,50 @@ int arp_models_planes(arp_ctx* c, double* ring_center, double* ring_normal, int3
     return ARP_OK;
 }
 
-// ---- contact persistence over the resident models (arp_persist.h) ----------------------------------------------
+// ---- the tables reduced on the device from the results of a pass -------------------------------
+// Contact persistence over the resident models (arp_persist.h), the residue-pair table (arp_respair.h) and residue persistence
+// over the resident models (arp_respersist.h) are one shape: refuse, return a table that is already made, re-key the records,
+// sort them by the whole key, count the runs (the one wait: U rows), size the slab, reduce one wave per row (make_table);
+// and one copy of the slab through the page-locked stage (table_fetch).  A table brings a TableSpec and its two own steps.
 namespace {
-// Layout of the table's slab: the ten columns one after the other, each on a 256-byte boundary (the float64 column first).
-enum { PT_DSUM = 0, PT_A, PT_B, PT_FIRST, PT_LAST, PT_DMIN, PT_DMAX, PT_NMODELS, PT_BITS, PT_CTYPE, PT_COLS };
-void persist_layout(size_t U, size_t off[PT_COLS], size_t* bytes) {
-    static const size_t es[PT_COLS] = {8, 4, 4, 4, 4, 4, 4, 2, 2 * PERSIST_BITS, 1};
+enum { TABLE_MAX_COLS = 12 };
+struct TableSpec {
+    const char* name;                // "<name>_launch" / "<name>_fetch" in messages
+    ResultTable arp_ctx::* table;
+    int cols;
+    size_t es[TABLE_MAX_COLS];       // bytes per row of every column, in the order of the fetch's arguments (= of the slab)
+    bool models;                     // made over the resident models (arp_set_models)
+    bool five_bags;                  // made from all five bags of a complete pass; else from the atom-atom bag alone
+    const char* no_pass;             // the refusal when those results are missing
+    long long min_rows;              // fewest rows that records can give: 0 where a table leaves records out (all of them, then)
+};
+// the columns of every table in the order of its fetch's arguments
+enum { PT_A = 0, PT_B, PT_NMODELS, PT_FIRST, PT_LAST, PT_DMIN, PT_DMAX, PT_DSUM, PT_BITS, PT_CTYPE, PT_COLS };
+enum { RT_A = 0, RT_B, RT_N, RT_DMIN, RT_BITS, RT_CTYPE, RT_PLANES, RT_COLS };
+enum { ST_A = 0, ST_B, ST_NMODELS, ST_FIRST, ST_LAST, ST_N, ST_CLS, ST_BITS, ST_DMIN, ST_DMAX, ST_DSUM, ST_CTYPE, ST_COLS };
+const TableSpec PERSIST_TABLE = {"arp_models_persistence", &arp_ctx::persist, PT_COLS, {4, 4, 2, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 1},
+                                 true, false, "no results of a pass over the resident models (launch one first)", 1};
+const TableSpec RESPAIR_TABLE = {"arp_residue_pairs", &arp_ctx::respair, RT_COLS, {4, 4, 4, 4, 4 * TABLE_SIFT_BITS, 1, 4 * RESPAIR_PLANE_BAGS},
+                                 false, true, "no results of a complete pass (arp_run_launch first)", 0};
+const TableSpec RESPERSIST_TABLE = {"arp_models_residue_persistence", &arp_ctx::respersist, ST_COLS,
+                                    {4, 4, 2, 4, 4, 4, 2 * RESPERSIST_CLASSES, 2 * TABLE_SIFT_BITS, 4, 4, 8, 1},
+                                    true, true, "no results of a complete pass over the resident models (arp_run_launch first)", 0};
+static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+
+// Layout of a table's slab: its columns one after the other, each on a 256-byte boundary (so their order is free).
+void table_layout(const TableSpec& spec, size_t U, size_t off[TABLE_MAX_COLS], size_t* bytes) {
     size_t at = 0;
-    for (int q = 0; q < PT_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
+    for (int q = 0; q < spec.cols; ++q) { off[q] = at; at += al256(U * spec.es[q]); }
     *bytes = at;
 }
-int persist_stage_reserve(arp_ctx* c, size_t bytes) {
-    if (c->persist_stage && c->persist_stage_cap >= bytes) return ARP_OK;
-    if (c->persist_stage) (void)hipHostFree(c->persist_stage);
-    c->persist_stage = nullptr;
-    c->persist_stage_cap = 0;
+int table_stage_reserve(arp_ctx* c, size_t bytes) {
+    if (c->table_stage && c->table_stage_cap >= bytes) return ARP_OK;
+    if (c->table_stage) (void)hipHostFree(c->table_stage);
+    c->table_stage = nullptr;
+    c->table_stage_cap = 0;
     const size_t want = std::max(bytes + bytes / 4, (size_t)4096);
-    HIPCHK(c, hipHostMalloc((void**)&c->persist_stage, want, hipHostMallocDefault));
-    c->persist_stage_cap = want;
+    HIPCHK(c, hipHostMalloc((void**)&c->table_stage, want, hipHostMallocDefault));
+    c->table_stage_cap = want;
     return ARP_OK;
 }
 // k re-keyed records in s.key[0] / s.val[0], sorted by the low keybits bits of the key — every bit of it: least significant
@@ -4074,131 +4097,33 @@ void enqueue_key_sort(arp_ctx* c, SortScratch& s, size_t k, int keybits, int* so
 }
 // The runs of equal key >> R.shift among the sorted keys: counted per tile and scanned on the stream, then the one wait of a
 // table's launch — *U = runs = rows of the table.  R.key, R.k and R.shift are the caller's.
-int count_runs(arp_ctx* c, RunArgs& R, long long* U, const char* what) {
-    R.T = (int)((R.k + PERSIST_TILE - 1) / PERSIST_TILE);
-    HIPCHK(c, c->persist_tiles.reserve((size_t)R.T));
-    HIPCHK(c, c->persist_total.reserve(1));
-    CHK(persist_stage_reserve(c, 4096));
-    R.tile_rows = c->persist_tiles.p;
-    R.total = c->persist_total.p;
-    hipLaunchKernelGGL(k_persist_count, dim3(R.T), dim3(PERSIST_THREADS), 0, c->stream, R);
-    hipLaunchKernelGGL(k_persist_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
-    CHK(check_launch(c, what));
-    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+int count_runs(arp_ctx* c, RunArgs& R, long long* U, const std::string& what) {
+    R.T = (int)((R.k + RUNS_TILE - 1) / RUNS_TILE);
+    HIPCHK(c, c->table_tiles.reserve((size_t)R.T));
+    HIPCHK(c, c->table_total.reserve(1));
+    CHK(table_stage_reserve(c, 4096));
+    R.tile_rows = c->table_tiles.p;
+    R.total = c->table_total.p;
+    hipLaunchKernelGGL(k_runs_count, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
+    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+    CHK(check_launch(c, what.c_str()));
+    HIPCHK(c, hipMemcpyAsync(c->table_stage, c->table_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(U, c->persist_stage, sizeof(*U));
+    memcpy(U, c->table_stage, sizeof(*U));
     return ARP_OK;
 }
 // ... and where each of the U runs begins (row_start[U] = k), for the reduction that follows on the stream
 int enqueue_run_starts(arp_ctx* c, RunArgs& R, long long U) {
-    HIPCHK(c, c->persist_rows.reserve((size_t)U + 1));
+    HIPCHK(c, c->table_rows.reserve((size_t)U + 1));
     R.U = U;
-    R.row_start = c->persist_rows.p;
-    hipLaunchKernelGGL(k_persist_starts, dim3(R.T), dim3(PERSIST_THREADS), 0, c->stream, R);
+    R.row_start = c->table_rows.p;
+    hipLaunchKernelGGL(k_runs_starts, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
     return ARP_OK;
 }
-}  // namespace
-
-int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
-    if (!c || !count) return ARP_E_ARG;
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: not for a shard of a distributed structure");
-    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: no models resident (arp_set_models)");
-    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: no results of a pass over the resident models (launch one first)");
-    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, "arp_models_persistence_launch: more than 65 535 models (the table counts models in uint16)");
-    if (c->persist_valid) { *count = c->persist_count; return ARP_OK; }
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)c->n_contacts;
-    const int64_t F = c->models_n, n = c->topo_hdr.n;
-    c->persist_count = 0;
-    if (k == 0 || n <= 0) { c->persist_valid = true; *count = 0; return ARP_OK; }
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: 2^31 records or more");
-    PersistArgs A{};
-    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
-    A.k = (long long)k;
-    A.n = (uint32_t)n;
-    const int abits = id_bits(std::max<int64_t>(n - 1, 1));
-    A.bbits = abits;
-    A.fbits = id_bits(std::max<int64_t>(F - 1, 1));
-    const int keybits = abits + A.bbits + A.fbits;
-    if (keybits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: (atom, atom, model) does not fit a 63-bit key");
-    // ---- scratch: sized from the capacity of the bag's columns, so that it is allocated once per structure size
-    SortScratch& s = c->sort_persist;
-    CHK(reserve_key_sort(c, s, k, std::max(k, c->out_i.cap)));
-    // ---- (a, b, f) keys, sorted by every bit: least significant digit first
-    A.key = s.key[0].p; A.val = s.val[0].p;
-    hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, A);
-    int sorted = 0;
-    enqueue_key_sort(c, s, k, keybits, &sorted);
-    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
-    // ---- rows: count, scan; the host learns U (the one wait)
-    RunArgs R{};
-    R.key = A.key; R.k = A.k; R.shift = A.fbits;
-    long long U = 0;
-    CHK(count_runs(c, R, &U, "arp_models_persistence_launch: sort / count"));
-    if (U < 1 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_models_persistence_launch: row count out of range");
-    // ---- the table: row starts, one wave per row
-    size_t off[PT_COLS], bytes;
-    persist_layout((size_t)U, off, &bytes);
-    HIPCHK(c, c->persist_slab.reserve(bytes));
-    uint8_t* const slab = c->persist_slab.p;
-    CHK(enqueue_run_starts(c, R, U));
-    A.U = U;
-    A.row_start = R.row_start;
-    A.t_dsum = (double*)(slab + off[PT_DSUM]); A.t_a = (int*)(slab + off[PT_A]); A.t_b = (int*)(slab + off[PT_B]);
-    A.t_first = (int*)(slab + off[PT_FIRST]); A.t_last = (int*)(slab + off[PT_LAST]);
-    A.t_dmin = (float*)(slab + off[PT_DMIN]); A.t_dmax = (float*)(slab + off[PT_DMAX]);
-    A.t_nmodels = (uint16_t*)(slab + off[PT_NMODELS]); A.t_bits = (uint16_t*)(slab + off[PT_BITS]); A.t_ctype = slab + off[PT_CTYPE];
-    hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
-    CHK(check_launch(c, "arp_models_persistence_launch: reduce"));
-    c->persist_count = U;
-    c->persist_valid = true;
-    *count = U;
-    return ARP_OK;
-}
-
-int arp_models_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
-                                 float* dist_min, float* dist_max, double* dist_sum, uint16_t* bit_count, uint8_t* ctype_mask, int64_t* count) {
-    if (!c || !count) return ARP_E_ARG;
-    if (!c->contacts_valid || !c->persist_valid) FAIL(c, ARP_E_ARG, "arp_models_persistence_fetch: no table (arp_models_persistence_launch after a pass)");
-    *count = c->persist_count;
-    if (c->persist_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_fetch: output buffers too small");
-    const size_t U = (size_t)c->persist_count;
-    if (U == 0) return ARP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    size_t off[PT_COLS], bytes;
-    persist_layout(U, off, &bytes);
-    CHK(persist_stage_reserve(c, bytes));
-    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->persist_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint8_t* const h = c->persist_stage;
-    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
-    put(dist_sum, PT_DSUM, 8); put(a, PT_A, 4); put(b, PT_B, 4); put(first, PT_FIRST, 4); put(last, PT_LAST, 4);
-    put(dist_min, PT_DMIN, 4); put(dist_max, PT_DMAX, 4); put(n_models, PT_NMODELS, 2); put(bit_count, PT_BITS, 2 * PERSIST_BITS);
-    put(ctype_mask, PT_CTYPE, 1);
-    return ARP_OK;
-}
-
-// ---- residue-residue contact table of the last pass (arp_respair.h) ---------------------------------------------------
-namespace {
-// Layout of the table's slab: the seven columns one after the other, each on a 256-byte boundary.
-enum { RT_A = 0, RT_B, RT_N, RT_DMIN, RT_BITS, RT_PLANES, RT_CTYPE, RT_COLS };
-void respair_layout(size_t U, size_t off[RT_COLS], size_t* bytes) {
-    static const size_t es[RT_COLS] = {4, 4, 4, 4, 4 * RESPAIR_BITS, 4 * RESPAIR_PLANE_BAGS, 1};
-    size_t at = 0;
-    for (int q = 0; q < RT_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
-    *bytes = at;
-}
-// Bits of the key the sort covers: res_a << rbits | res_b, and one bit more where the all-ones key of a left-out record
-// would otherwise tie with a pair in the sorted bits — the pair (nres - 1, nres - 1) of a ring / amide bag when nres - 1 is
-// all ones itself (bit 2 rbits is set in ~0 and in no pair: the left-out records then sort last by it).
-int respair_key_bits(int64_t nres, int rbits, bool planes) {
-    const bool tie = planes && nres - 1 == ((int64_t)1 << rbits) - 1;
-    return 2 * rbits + (tie ? 1 : 0);
-}
-// What a residue table (this one and arp_respersist.h's) reads of a complete pass besides the atom-atom bag: the four ring /
-// amide bags as the re-key kernels walk them, placed behind the atom-atom records; the records of all five bags (k), of the four
-// (planes) and of the largest of the four; and the capacity the sort scratch is sized from — the capacities of the bags'
-// columns, so that it is allocated once per structure size.
+// What a table reads of a pass: the atom-atom bag and — planes: a residue table — the four ring / amide bags as the re-key
+// kernels walk them, placed behind the atom-atom records; the records of all those bags (k), of the four (planes) and of the
+// largest of the four; and the capacity the sort scratch is sized from — the capacities of the bags' columns, so that it is
+// allocated once per structure size.
 struct FiveBags {
     RespairBag bag[RESPAIR_PLANE_BAGS];      // classes 1 ... 4
     size_t k, planes, cap;
@@ -4207,14 +4132,14 @@ struct FiveBags {
 bool five_bags_complete(const arp_ctx* c) {
     return !c->pass_pending && c->contacts_valid && c->bag_ap.valid && c->bag_pp.valid && c->bag_gg.valid && c->bag_gp.valid;
 }
-FiveBags five_bags(const arp_ctx* c) {
+FiveBags five_bags(const arp_ctx* c, bool planes) {
     const Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};
     const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
                                                       {c->am_res.p, c->am_res.p}, {c->am_res.p, c->ring_res.p}};
     FiveBags B{};
     B.k = (size_t)c->n_contacts;
     B.cap = std::max((size_t)c->n_contacts, c->out_i.cap);
-    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) {
+    for (int m = 0; planes && m < RESPAIR_PLANE_BAGS; ++m) {
         const Bag& b = *bags[m];
         B.bag[m] = RespairBag{b.a.p, b.b.p, res_of[m][0], res_of[m][1], (long long)b.count, (long long)B.k};
         B.k += (size_t)b.count;
@@ -4224,188 +4149,186 @@ FiveBags five_bags(const arp_ctx* c) {
     }
     return B;
 }
-}  // namespace
-
-int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
+// What a table's re-key step tells the sequence: the bits of the key the sort covers, and a run = equal key >> shift.
+struct TableKey {
+    int bits, shift;
+};
+// The sequence of a table's launch.  rekey(B, key, val, &K) enqueues the table's keys and payloads for the B.k records into
+// key / val and fills K; reduce(key, val, row_start, U, col) enqueues the table's reduction of the sorted records into the U
+// rows of the columns col[0 ... spec.cols).
+using RekeyStep = std::function<int(const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K)>;
+using ReduceStep = std::function<void(const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col)>;
+int make_table(arp_ctx* c, const TableSpec& spec, int64_t* count, const RekeyStep& rekey, const ReduceStep& reduce) {
     if (!c || !count) return ARP_E_ARG;
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: not for a shard of a distributed structure");
-    if (!five_bags_complete(c)) FAIL(c, ARP_E_ARG, "arp_residue_pairs_launch: no results of a complete pass (arp_run_launch first)");
-    if (c->respair_valid) { *count = c->respair_count; return ARP_OK; }
+    const std::string fn = std::string(spec.name) + "_launch: ";
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (spec.models && c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
+    if (spec.models && c->models_n > 65535) FAIL(c, ARP_E_ARG, fn + "more than 65 535 models (the table counts models in uint16)");
+    if (spec.five_bags ? !five_bags_complete(c) : (c->pass_pending || !c->contacts_valid)) FAIL(c, ARP_E_ARG, fn + spec.no_pass);
+    ResultTable& T = c->*spec.table;
+    if (T.valid) { *count = T.count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
-    RespairArgs A{};
-    A.k_aa = (long long)c->n_contacts;
-    const FiveBags B = five_bags(c);
-    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
-    const size_t k = B.k, planes = B.planes;
-    c->respair_count = 0;
-    if (k == 0) { c->respair_valid = true; *count = 0; return ARP_OK; }
-    // (a left-out record keeps its slot up to the reduction, so every record of the five bags counts here, kept or not)
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_residue_pairs_launch: 2^31 records or more");
-    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
-    A.res_id = c->res_id.p;
-    A.rbits = id_bits(std::max<int64_t>(c->nres - 1, 1));
-    const int keybits = respair_key_bits(c->nres, A.rbits, planes > 0);
-    // ---- scratch
-    SortScratch& s = c->sort_persist;
+    const FiveBags B = five_bags(c, spec.five_bags);
+    const size_t k = B.k;
+    T.count = 0;
+    if (k == 0) { T.valid = true; *count = 0; return ARP_OK; }
+    // (a left-out record keeps its slot up to the reduction, so every record of the bags counts here, kept or not)
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
+    // ---- the table's keys, sorted by every bit: least significant digit first
+    SortScratch& s = c->table_sort;
     CHK(reserve_key_sort(c, s, k, B.cap));
-    // ---- (res_a, res_b) keys of all five bags, sorted by every bit
-    A.key = s.key[0].p; A.val = s.val[0].p;
-    if (A.k_aa > 0) hipLaunchKernelGGL(k_respair_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
-    if (planes > 0) hipLaunchKernelGGL(k_respair_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
+    TableKey K{};
+    CHK(rekey(B, s.key[0].p, s.val[0].p, &K));
     int sorted = 0;
-    enqueue_key_sort(c, s, k, keybits, &sorted);
-    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
+    enqueue_key_sort(c, s, k, K.bits, &sorted);
     // ---- rows: count, scan; the host learns U (the one wait)
     RunArgs R{};
-    R.key = A.key; R.k = (long long)k; R.shift = 0;
+    R.key = s.key[sorted].p; R.k = (long long)k; R.shift = K.shift;
     long long U = 0;
-    CHK(count_runs(c, R, &U, "arp_residue_pairs_launch: sort / count"));
-    if (U < 0 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_residue_pairs_launch: row count out of range");
-    if (U > 0) {      // (0: every record was left out)
-        size_t off[RT_COLS], bytes;
-        respair_layout((size_t)U, off, &bytes);
-        HIPCHK(c, c->respair_slab.reserve(bytes));
-        uint8_t* const slab = c->respair_slab.p;
+    CHK(count_runs(c, R, &U, fn + "sort / count"));
+    if (U < spec.min_rows || U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    if (U > 0) {
+        // ---- the table: row starts, one wave per row
+        size_t off[TABLE_MAX_COLS], bytes;
+        table_layout(spec, (size_t)U, off, &bytes);
+        HIPCHK(c, T.slab.reserve(bytes));
         CHK(enqueue_run_starts(c, R, U));
-        A.U = U;
-        A.row_start = R.row_start;
-        A.t_a = (int*)(slab + off[RT_A]); A.t_b = (int*)(slab + off[RT_B]); A.t_n = (uint32_t*)(slab + off[RT_N]);
-        A.t_dmin = (float*)(slab + off[RT_DMIN]); A.t_bits = (uint32_t*)(slab + off[RT_BITS]);
-        A.t_planes = (uint32_t*)(slab + off[RT_PLANES]); A.t_ctype = slab + off[RT_CTYPE];
-        hipLaunchKernelGGL(k_respair_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
-        CHK(check_launch(c, "arp_residue_pairs_launch: reduce"));
+        uint8_t* col[TABLE_MAX_COLS];
+        for (int q = 0; q < spec.cols; ++q) col[q] = T.slab.p + off[q];
+        reduce(R.key, s.val[sorted].p, R.row_start, U, col);
+        CHK(check_launch(c, (fn + "reduce").c_str()));
     }
-    c->respair_count = U;
-    c->respair_valid = true;
+    T.count = U;
+    T.valid = true;
     *count = U;
     return ARP_OK;
 }
-
-int arp_residue_pairs_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* res_b, uint32_t* n_contacts, float* dist_min,
-                            uint32_t* bit_count, uint8_t* ctype_mask, uint32_t* plane_count, int64_t* count) {
+// One copy of the slab into the page-locked stage; column q goes to dst[q] unless that is NULL.
+int table_fetch(arp_ctx* c, const TableSpec& spec, int64_t cap, void* const dst[], int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
-    if (!c->contacts_valid || !c->respair_valid) FAIL(c, ARP_E_ARG, "arp_residue_pairs_fetch: no table (arp_residue_pairs_launch after a pass)");
-    *count = c->respair_count;
-    if (c->respair_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_residue_pairs_fetch: output buffers too small");
-    const size_t U = (size_t)c->respair_count;
+    const std::string name = spec.name;
+    const ResultTable& T = c->*spec.table;
+    if (!c->contacts_valid || !T.valid) FAIL(c, ARP_E_ARG, name + "_fetch: no table (" + name + "_launch after a pass)");
+    *count = T.count;
+    if (T.count > cap) FAIL(c, ARP_E_CAPACITY, name + "_fetch: output buffers too small");
+    const size_t U = (size_t)T.count;
     if (U == 0) return ARP_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    size_t off[RT_COLS], bytes;
-    respair_layout(U, off, &bytes);
-    CHK(persist_stage_reserve(c, bytes));
-    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->respair_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    size_t off[TABLE_MAX_COLS], bytes;
+    table_layout(spec, U, off, &bytes);
+    CHK(table_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->table_stage, T.slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint8_t* const h = c->persist_stage;
-    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
-    put(res_a, RT_A, 4); put(res_b, RT_B, 4); put(n_contacts, RT_N, 4); put(dist_min, RT_DMIN, 4);
-    put(bit_count, RT_BITS, 4 * RESPAIR_BITS); put(plane_count, RT_PLANES, 4 * RESPAIR_PLANE_BAGS); put(ctype_mask, RT_CTYPE, 1);
+    for (int q = 0; q < spec.cols; ++q)
+        if (dst[q]) memcpy(dst[q], c->table_stage + off[q], U * spec.es[q]);
     return ARP_OK;
 }
-
-// ---- residue contact persistence over the resident models (arp_respersist.h) ------------------------------------------
-namespace {
-// Layout of the table's slab: the twelve columns one after the other, each on a 256-byte boundary (the float64 column first).
-enum { ST_DSUM = 0, ST_A, ST_B, ST_FIRST, ST_LAST, ST_N, ST_DMIN, ST_DMAX, ST_NMODELS, ST_CLS, ST_BITS, ST_CTYPE, ST_COLS };
-void respersist_layout(size_t U, size_t off[ST_COLS], size_t* bytes) {
-    static const size_t es[ST_COLS] = {8, 4, 4, 4, 4, 4, 4, 4, 2, 2 * RESPERSIST_CLASSES, 2 * RESPERSIST_BITS, 1};
-    size_t at = 0;
-    for (int q = 0; q < ST_COLS; ++q) { off[q] = at; at += al256(U * es[q]); }
-    *bytes = at;
-}
-// Bits of the key the sort covers: res_a << (rbits + fbits) | res_b << fbits | f, and one bit more where the all-ones key of a
-// left-out record would otherwise tie with a real record in the sorted bits — the pair (nres_t - 1, nres_t - 1) of a ring /
-// amide bag in model F - 1, when nres_t - 1 and F - 1 are all ones themselves (bit 2 rbits + fbits is set in ~0 and in no
-// record: the left-out records then sort last by it).
+// Bits of the key of a residue table that the sort covers: res_a << (rbits + fbits) | res_b << fbits | f, and one bit more
+// where the all-ones key of a left-out record would otherwise tie with a real record in the sorted bits — the pair
+// (nres_t - 1, nres_t - 1) of a ring / amide bag in model F - 1, when nres_t - 1 and F - 1 are all ones themselves (bit
+// 2 rbits + fbits is set in ~0 and in no record: the left-out records then sort last by it).  The residue-pair table has no
+// model in its key: fbits = 0, F = 1.
 int respersist_key_bits(int64_t nres_t, int64_t F, int rbits, int fbits, bool planes) {
     const bool tie = planes && nres_t - 1 == ((int64_t)1 << rbits) - 1 && F - 1 == ((int64_t)1 << fbits) - 1;
     return 2 * rbits + fbits + (tie ? 1 : 0);
 }
-}  // namespace
-
-int arp_models_residue_persistence_launch(arp_ctx* c, int64_t* count) {
-    if (!c || !count) return ARP_E_ARG;
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: not for a shard of a distributed structure");
-    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: no models resident (arp_set_models)");
-    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: more than 65 535 models (the table counts models in uint16)");
-    if (!five_bags_complete(c)) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_launch: no results of a complete pass over the resident models (arp_run_launch first)");
-    if (c->respersist_valid) { *count = c->respersist_count; return ARP_OK; }
-    HIPCHK(c, hipSetDevice(c->device));
-    RespersistArgs A{};
-    A.k_aa = (long long)c->n_contacts;
-    const FiveBags B = five_bags(c);
-    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
-    const size_t k = B.k, planes = B.planes;
-    const int64_t F = c->models_n, nres_t = c->nres / F;
-    c->respersist_count = 0;
-    if (k == 0 || nres_t <= 0) { c->respersist_valid = true; *count = 0; return ARP_OK; }
-    // (a left-out record keeps its slot up to the reduction, so every record of the five bags counts here, kept or not)
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: 2^31 records or more");
+// The re-key step of both residue tables: the five bags keyed by topology residue pair and model (nres_t residues a model).
+void enqueue_residue_rekey(arp_ctx* c, const FiveBags& B, int64_t nres_t, int rbits, int fbits, unsigned long long* key, unsigned long long* val) {
+    RekeyArgs A{};
     A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
     A.res_id = c->res_id.p;
-    A.nres_t = (uint32_t)nres_t;
-    A.rbits = id_bits(std::max<int64_t>(nres_t - 1, 1));
-    A.fbits = id_bits(std::max<int64_t>(F - 1, 1));
-    if (2 * A.rbits + A.fbits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: (residue, residue, model) does not fit a 63-bit key");
-    const int keybits = respersist_key_bits(nres_t, F, A.rbits, A.fbits, planes > 0);
-    // ---- scratch
-    SortScratch& s = c->sort_persist;
-    CHK(reserve_key_sort(c, s, k, B.cap));
-    // ---- (res_a, res_b, f) keys of all five bags, sorted by every bit
-    A.key = s.key[0].p; A.val = s.val[0].p;
-    if (A.k_aa > 0) hipLaunchKernelGGL(k_respersist_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
-    if (planes > 0) hipLaunchKernelGGL(k_respersist_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
-    int sorted = 0;
-    enqueue_key_sort(c, s, k, keybits, &sorted);
-    A.key = s.key[sorted].p; A.val = s.val[sorted].p;
-    // ---- rows: a run is one residue pair over its models; count, scan; the host learns U (the one wait)
-    RunArgs R{};
-    R.key = A.key; R.k = (long long)k; R.shift = A.fbits;
-    long long U = 0;
-    CHK(count_runs(c, R, &U, "arp_models_residue_persistence_launch: sort / count"));
-    if (U < 0 || U > (long long)k) FAIL(c, ARP_E_HIP, "arp_models_residue_persistence_launch: row count out of range");
-    if (U > 0) {      // (0: every record was left out)
-        size_t off[ST_COLS], bytes;
-        respersist_layout((size_t)U, off, &bytes);
-        HIPCHK(c, c->respersist_slab.reserve(bytes));
-        uint8_t* const slab = c->respersist_slab.p;
-        CHK(enqueue_run_starts(c, R, U));
-        A.U = U;
-        A.row_start = R.row_start;
-        A.t_dsum = (double*)(slab + off[ST_DSUM]); A.t_a = (int*)(slab + off[ST_A]); A.t_b = (int*)(slab + off[ST_B]);
-        A.t_first = (int*)(slab + off[ST_FIRST]); A.t_last = (int*)(slab + off[ST_LAST]); A.t_n = (uint32_t*)(slab + off[ST_N]);
-        A.t_dmin = (float*)(slab + off[ST_DMIN]); A.t_dmax = (float*)(slab + off[ST_DMAX]);
-        A.t_nmodels = (uint16_t*)(slab + off[ST_NMODELS]); A.t_cls = (uint16_t*)(slab + off[ST_CLS]);
-        A.t_bits = (uint16_t*)(slab + off[ST_BITS]); A.t_ctype = slab + off[ST_CTYPE];
-        hipLaunchKernelGGL(k_respersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
-        CHK(check_launch(c, "arp_models_residue_persistence_launch: reduce"));
-    }
-    c->respersist_count = U;
-    c->respersist_valid = true;
-    *count = U;
-    return ARP_OK;
+    A.k_aa = (long long)c->n_contacts;
+    for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
+    A.nres_t = (uint32_t)nres_t; A.rbits = rbits; A.fbits = fbits;
+    A.key = key; A.val = val;
+    if (A.k_aa > 0) hipLaunchKernelGGL(k_residue_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
+    if (B.planes > 0) hipLaunchKernelGGL(k_residue_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
+}
+}  // namespace
+
+// ---- contact persistence over the resident models (arp_persist.h)
+int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
+    PersistArgs A{};
+    return make_table(c, PERSIST_TABLE, count,
+        [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+            A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+            A.k = (long long)B.k;
+            A.n = (uint32_t)c->topo_hdr.n;      // (> 0: the bag has records)
+            A.bbits = id_bits(std::max<int64_t>(c->topo_hdr.n - 1, 1));
+            A.fbits = id_bits(std::max<int64_t>(c->models_n - 1, 1));
+            *K = TableKey{2 * A.bbits + A.fbits, A.fbits};
+            if (K->bits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: (atom, atom, model) does not fit a 63-bit key");
+            A.key = key; A.val = val;
+            hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)B.k, 256, 2048)), dim3(256), 0, c->stream, A);
+            return ARP_OK;
+        },
+        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
+            A.key = (unsigned long long*)key; A.val = (unsigned long long*)val; A.row_start = row_start; A.U = U;
+            A.t_a = (int*)col[PT_A]; A.t_b = (int*)col[PT_B]; A.t_nmodels = (uint16_t*)col[PT_NMODELS];
+            A.t_first = (int*)col[PT_FIRST]; A.t_last = (int*)col[PT_LAST]; A.t_dmin = (float*)col[PT_DMIN]; A.t_dmax = (float*)col[PT_DMAX];
+            A.t_dsum = (double*)col[PT_DSUM]; A.t_bits = (uint16_t*)col[PT_BITS]; A.t_ctype = col[PT_CTYPE];
+            hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        });
+}
+
+int arp_models_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
+                                 float* dist_min, float* dist_max, double* dist_sum, uint16_t* bit_count, uint8_t* ctype_mask, int64_t* count) {
+    void* const dst[PT_COLS] = {a, b, n_models, first, last, dist_min, dist_max, dist_sum, bit_count, ctype_mask};
+    return table_fetch(c, PERSIST_TABLE, cap, dst, count);
+}
+
+// ---- residue-residue contact table of the last pass (arp_respair.h): no model in the key, every resident residue one "model"
+int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
+    int rbits = 0;
+    return make_table(c, RESPAIR_TABLE, count,
+        [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+            rbits = id_bits(std::max<int64_t>(c->nres - 1, 1));
+            *K = TableKey{respersist_key_bits(c->nres, 1, rbits, 0, B.planes > 0), 0};
+            enqueue_residue_rekey(c, B, std::max<int64_t>(c->nres, 1), rbits, 0, key, val);
+            return ARP_OK;
+        },
+        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
+            const RespairArgs A{rbits, key, val, row_start, U, (int*)col[RT_A], (int*)col[RT_B], (uint32_t*)col[RT_N], (float*)col[RT_DMIN],
+                                (uint32_t*)col[RT_BITS], col[RT_CTYPE], (uint32_t*)col[RT_PLANES]};
+            hipLaunchKernelGGL(k_respair_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        });
+}
+
+int arp_residue_pairs_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* res_b, uint32_t* n_contacts, float* dist_min,
+                            uint32_t* bit_count, uint8_t* ctype_mask, uint32_t* plane_count, int64_t* count) {
+    void* const dst[RT_COLS] = {res_a, res_b, n_contacts, dist_min, bit_count, ctype_mask, plane_count};
+    return table_fetch(c, RESPAIR_TABLE, cap, dst, count);
+}
+
+// ---- residue contact persistence over the resident models (arp_respersist.h)
+int arp_models_residue_persistence_launch(arp_ctx* c, int64_t* count) {
+    int rbits = 0, fbits = 0;
+    return make_table(c, RESPERSIST_TABLE, count,
+        [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+            const int64_t F = c->models_n, nres_t = std::max<int64_t>(c->nres / F, 1);      // (no residue at all: every record is left out)
+            rbits = id_bits(std::max<int64_t>(nres_t - 1, 1));
+            fbits = id_bits(std::max<int64_t>(F - 1, 1));
+            if (2 * rbits + fbits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: (residue, residue, model) does not fit a 63-bit key");
+            *K = TableKey{respersist_key_bits(nres_t, F, rbits, fbits, B.planes > 0), fbits};
+            enqueue_residue_rekey(c, B, nres_t, rbits, fbits, key, val);
+            return ARP_OK;
+        },
+        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
+            RespersistArgs A{};
+            A.rbits = rbits; A.fbits = fbits; A.key = key; A.val = val; A.row_start = row_start; A.U = U;
+            A.t_a = (int*)col[ST_A]; A.t_b = (int*)col[ST_B]; A.t_nmodels = (uint16_t*)col[ST_NMODELS];
+            A.t_first = (int*)col[ST_FIRST]; A.t_last = (int*)col[ST_LAST]; A.t_n = (uint32_t*)col[ST_N];
+            A.t_cls = (uint16_t*)col[ST_CLS]; A.t_bits = (uint16_t*)col[ST_BITS]; A.t_dmin = (float*)col[ST_DMIN];
+            A.t_dmax = (float*)col[ST_DMAX]; A.t_dsum = (double*)col[ST_DSUM]; A.t_ctype = col[ST_CTYPE];
+            hipLaunchKernelGGL(k_respersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        });
 }
 
 int arp_models_residue_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* res_b, uint16_t* n_models, int32_t* first,
                                          int32_t* last, uint32_t* n_contacts, uint16_t* class_models, uint16_t* bit_models,
                                          float* dist_min, float* dist_max, double* dist_sum, uint8_t* ctype_mask, int64_t* count) {
-    if (!c || !count) return ARP_E_ARG;
-    if (!c->contacts_valid || !c->respersist_valid) FAIL(c, ARP_E_ARG, "arp_models_residue_persistence_fetch: no table (arp_models_residue_persistence_launch after a pass)");
-    *count = c->respersist_count;
-    if (c->respersist_count > cap) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_fetch: output buffers too small");
-    const size_t U = (size_t)c->respersist_count;
-    if (U == 0) return ARP_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    size_t off[ST_COLS], bytes;
-    respersist_layout(U, off, &bytes);
-    CHK(persist_stage_reserve(c, bytes));
-    HIPCHK(c, hipMemcpyAsync(c->persist_stage, c->respersist_slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint8_t* const h = c->persist_stage;
-    auto put = [&](void* dst, int col, size_t es) { if (dst) memcpy(dst, h + off[col], U * es); };
-    put(dist_sum, ST_DSUM, 8); put(res_a, ST_A, 4); put(res_b, ST_B, 4); put(first, ST_FIRST, 4); put(last, ST_LAST, 4);
-    put(n_contacts, ST_N, 4); put(dist_min, ST_DMIN, 4); put(dist_max, ST_DMAX, 4); put(n_models, ST_NMODELS, 2);
-    put(class_models, ST_CLS, 2 * RESPERSIST_CLASSES); put(bit_models, ST_BITS, 2 * RESPERSIST_BITS); put(ctype_mask, ST_CTYPE, 1);
-    return ARP_OK;
+    void* const dst[ST_COLS] = {res_a, res_b, n_models, first, last, n_contacts, class_models, bit_models, dist_min, dist_max, dist_sum, ctype_mask};
+    return table_fetch(c, RESPERSIST_TABLE, cap, dst, count);
 }
 
 // ---- exchange between the shards of a distributed structure (RCCL behind the C ABI) -----------------------------------

@@ -11,14 +11,10 @@
 // not.  Sorting every bit of the key needs no tie-break and no per-atom stage in LDS: an atom with 10^4 records (they
 // grow with F) is sorted like any other, so there is no capacity and no second path (ARP_PERSIST_STAGE_MAX = 0).
 // After the sort the records of a pair are one run in ascending f:
-//   k_persist_rekey   record p -> key a << (bbits + fbits) | b << fbits | f, payload distance | SIFt << 32 | type << 48
+//   k_persist_rekey   record p -> key a << (bbits + fbits) | b << fbits | f, payload table_payload (arp_runs.h), class 0
 //   (radix passes over the abits + bbits + fbits bits of the key, up to 9 bits a pass)
-//   k_persist_count   block t: the runs that BEGIN in tile t (a record whose (a, b) differs from its predecessor's)
-//   (k_persist_count / _scan / _starts take a RunArgs — sorted keys, a shift, the tile counts and the row starts — and nothing
-//   of this table: the residue-pair table of arp_respair.h finds its runs with them as well)
-//   k_persist_scan    one block: exclusive prefix of those counts over the tiles; their sum U = rows of the table
-//   (the host reads U — the one wait — and sizes the table)
-//   k_persist_starts  block t: row_start[prefix[t] + rank in the tile] = position of the run's first record
+//   k_runs_count / k_runs_scan / k_runs_starts (arp_runs.h, shift fbits): a run = a record whose (a, b) differs from its
+//   predecessor's; the host reads their number U — the one wait — and sizes the table
 //   k_persist_reduce  one wave per row: 64 records of the run per step, consecutive lanes on consecutive records;
 //                     counts by ballots, min / max / type mask by a butterfly over the lanes, and dist_sum by adding the 64
 //                     distances of a step ONE BY ONE in lane order (= ascending model) to the running float64 sum — the
@@ -30,26 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "arp_sort.h"
-
-#define PERSIST_THREADS 256
-#define PERSIST_ITEMS 8          // consecutive records per thread of k_persist_count / k_persist_starts
-#define PERSIST_TILE (PERSIST_THREADS * PERSIST_ITEMS)
-#define PERSIST_BITS 15          // SIFt bits with a column of their own (ARP_S_CLASH ... ARP_S_WEAK_POLAR)
-
-// What finding the runs of a sorted key array needs: a run = consecutive records with equal key >> shift.  A record whose
-// key >> shift is all ones (~0ull >> shift) never BEGINS a run: no key of the persistence table has 64 bits, and the
-// residue-pair table marks the records it leaves out that way (they sort last and trail the last run uncounted).
-struct RunArgs {
-    const unsigned long long* key;   // sorted
-    long long k;             // records
-    int shift;
-    int T;                   // tiles of PERSIST_TILE records
-    int* tile_rows;          // [T]: runs beginning in tile t, then their exclusive prefix
-    long long* total;        // [1]: U
-    int* row_start;          // [U + 1]: first record of row r; row_start[U] = k
-    long long U;
-};
+#include "arp_runs.h"
 
 struct PersistArgs {
     // the bag of the last pass, in the order the pass left it
@@ -66,7 +43,7 @@ struct PersistArgs {
     unsigned long long* val;
     const int* row_start;    // [U + 1]: first record of row r; row_start[U] = k (RunArgs)
     long long U;
-    // the table, one column after the other (persist_layout)
+    // the table, one column after the other (PERSIST_TABLE)
     int* t_a;
     int* t_b;
     uint16_t* t_nmodels;
@@ -75,7 +52,7 @@ struct PersistArgs {
     float* t_dmin;
     float* t_dmax;
     double* t_dsum;
-    uint16_t* t_bits;        // [U][PERSIST_BITS]
+    uint16_t* t_bits;        // [U][TABLE_SIFT_BITS]
     uint8_t* t_ctype;
 };
 
@@ -85,67 +62,8 @@ __global__ __launch_bounds__(256) void k_persist_rekey(PersistArgs A) {
         const uint32_t f = i / A.n;                  // (a pair never crosses models: j lies in the same model)
         const uint32_t base = f * A.n;
         A.key[p] = ((unsigned long long)(i - base) << (A.bbits + A.fbits)) | ((unsigned long long)(j - base) << A.fbits) | (unsigned long long)f;
-        A.val[p] = (unsigned long long)__float_as_uint(A.d_in[p]) | ((unsigned long long)A.s_in[p] << 32) | ((unsigned long long)A.ct_in[p] << 48);
+        A.val[p] = table_payload(A.d_in[p], A.s_in[p], A.ct_in[p], 0ull);
     }
-}
-
-// bit r of the result: record lo + r of the thread's PERSIST_ITEMS consecutive records begins a run
-__device__ __forceinline__ uint32_t persist_heads(const RunArgs& A, long long lo) {
-    if (lo >= A.k) return 0u;
-    const unsigned long long none = ~0ull >> A.shift;
-    unsigned long long prev = lo > 0 ? (A.key[lo - 1] >> A.shift) : none;
-    uint32_t m = 0;
-#pragma unroll
-    for (int r = 0; r < PERSIST_ITEMS; ++r) {
-        if (lo + r >= A.k) break;
-        const unsigned long long cur = A.key[lo + r] >> A.shift;
-        m |= (cur != prev && cur != none ? 1u : 0u) << r;
-        prev = cur;
-    }
-    return m;
-}
-
-__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_count(RunArgs A) {
-    __shared__ int s_w[PERSIST_THREADS / 64];
-    int c = __popc(persist_heads(A, (long long)blockIdx.x * PERSIST_TILE + (long long)threadIdx.x * PERSIST_ITEMS));
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < PERSIST_THREADS / 64; ++w) t += s_w[w];
-        A.tile_rows[blockIdx.x] = t;
-    }
-}
-
-// one block (SORT_THREADS threads: sort_block_scan)
-__global__ __launch_bounds__(SORT_THREADS) void k_persist_scan(RunArgs A) {
-    __shared__ long long s_w[SORT_WAVES];
-    long long run = 0;
-    for (int t0 = 0; t0 < A.T; t0 += SORT_THREADS) {      // (block-uniform trip count)
-        const int t = t0 + threadIdx.x;
-        const int v = t < A.T ? A.tile_rows[t] : 0;
-        long long sum;
-        const long long e = sort_block_scan((long long)v, s_w, &sum);
-        if (t < A.T) A.tile_rows[t] = (int)(run + e);      // (rows <= records < 2^31)
-        run += sum;
-    }
-    if (threadIdx.x == 0) A.total[0] = run;
-}
-
-__global__ __launch_bounds__(PERSIST_THREADS) void k_persist_starts(RunArgs A) {
-    __shared__ long long s_w[SORT_WAVES];
-    static_assert(PERSIST_THREADS == SORT_THREADS, "sort_block_scan scans SORT_THREADS values");
-    const long long lo = (long long)blockIdx.x * PERSIST_TILE + (long long)threadIdx.x * PERSIST_ITEMS;
-    const uint32_t m = persist_heads(A, lo);
-    long long row = (long long)A.tile_rows[blockIdx.x] + sort_block_scan((long long)__popc(m), s_w, nullptr);
-#pragma unroll
-    for (int r = 0; r < PERSIST_ITEMS; ++r)
-        if ((m >> r) & 1u) {
-            if (row < A.U) A.row_start[row] = (int)(lo + r);      // (row < U always: U is the sum of the same counts)
-            ++row;
-        }
-    if (blockIdx.x == 0 && threadIdx.x == 0) A.row_start[A.U] = (int)A.k;
 }
 
 __global__ __launch_bounds__(256) void k_persist_reduce(PersistArgs A) {
@@ -158,21 +76,21 @@ __global__ __launch_bounds__(256) void k_persist_reduce(PersistArgs A) {
         float dmin = 0.f, dmax = 0.f;
         bool seen = false;
         uint32_t types = 0;
-        int cnt = 0;              // lane b < PERSIST_BITS: records of the run with SIFt bit b
+        int cnt = 0;              // lane b < TABLE_SIFT_BITS: records of the run with SIFt bit b
         double sum = 0.0;
         for (long long q = s; q < e; q += 64) {      // (wave-uniform trip count)
             const bool valid = q + lane < e;
             const unsigned long long v = valid ? A.val[q + lane] : 0ull;
-            const float d = __uint_as_float((uint32_t)v);
-            const uint32_t sf = (uint32_t)(v >> 32) & 0xFFFFu;
+            const float d = payload_distance(v);
+            const uint32_t sf = payload_sift(v);
             if (valid) {
                 dmin = seen ? (d < dmin ? d : dmin) : d;
                 dmax = seen ? (d > dmax ? d : dmax) : d;
                 seen = true;
-                types |= 1u << ((uint32_t)(v >> 48) & 7u);
+                types |= 1u << payload_type(v);
             }
 #pragma unroll
-            for (int b = 0; b < PERSIST_BITS; ++b) {
+            for (int b = 0; b < TABLE_SIFT_BITS; ++b) {
                 const int c = __popcll(__ballot(valid && ((sf >> b) & 1u)));
                 if (lane == b) cnt += c;
             }
@@ -191,7 +109,7 @@ __global__ __launch_bounds__(256) void k_persist_reduce(PersistArgs A) {
                 seen = true;
             }
         }
-        if (lane < PERSIST_BITS) A.t_bits[row * PERSIST_BITS + lane] = (uint16_t)cnt;
+        if (lane < TABLE_SIFT_BITS) A.t_bits[row * TABLE_SIFT_BITS + lane] = (uint16_t)cnt;
         if (lane == 0) {
             A.t_a[row] = (int)(k0 >> (A.bbits + A.fbits));
             A.t_b[row] = (int)((k0 >> A.fbits) & bmask);

@@ -5,13 +5,12 @@
 // classes, with which SIFt bits, and how closely.  Its size does not depend on F, so only the table crosses PCIe.
 //
 // Shape (that of both neighbours):
-//   k_respersist_rekey         atom-atom record p -> key res_a << (rbits + fbits) | res_b << fbits | f, the payload of arp_respair.h
-//                              (distance | SIFt << 32 | type << 47 | class << 50), class 0
-//   k_respersist_rekey_planes  the records of the four ring / amide bags behind them, class 1 ... 4
+//   k_residue_rekey / k_residue_rekey_planes (arp_respair.h): the records of the five bags -> key res_a << (rbits + fbits) |
+//                              res_b << fbits | f (respersist_key), payload table_payload (arp_runs.h), class 0 ... 4
 //   (radix passes of arp_sort.h over every bit of the key)
-//   k_persist_count / k_persist_scan / k_persist_starts (arp_persist.h, shift fbits): a run = one residue pair; U = rows
+//   k_runs_count / k_runs_scan / k_runs_starts (arp_runs.h, shift fbits): a run = one residue pair; U = rows
 //   k_respersist_reduce        one wave per row, 64 consecutive sorted records per step
-// Records that are left out (a residue of -1) keep their slot with an all-ones key and class RESPAIR_LEFT_OUT, as in
+// Records that are left out (a residue of -1) keep their slot with an all-ones key and class TABLE_LEFT_OUT, as in
 // arp_respair.h and for its reason: they trail the last run, no run begins on them, and the host needs no second wait.
 //
 // What neither neighbour needed: after the sort a run holds SEVERAL records per model (every atom pair of the two residues,
@@ -25,30 +24,19 @@
 
 #include "arp_respair.h"
 
-#define RESPERSIST_BITS 15       // SIFt bits with a column of their own (ARP_S_CLASH ... ARP_S_WEAK_POLAR)
 #define RESPERSIST_CLASSES 5     // atom-atom, atom-plane, plane-plane, group-group, group-plane
 // lanes of k_respersist_reduce that keep a count: b < 15 SIFt bit b, 15 + m class m, then the models and the atom-atom records
-#define RESPERSIST_LANE_MODELS (RESPERSIST_BITS + RESPERSIST_CLASSES)
+#define RESPERSIST_LANE_MODELS (TABLE_SIFT_BITS + RESPERSIST_CLASSES)
 #define RESPERSIST_LANE_CONTACTS (RESPERSIST_LANE_MODELS + 1)
 
 struct RespersistArgs {
-    // the atom-atom bag of the last pass, in the order the pass left it
-    const int* ci;
-    const int* cj;
-    const float* d_in;
-    const uint16_t* s_in;
-    const uint8_t* ct_in;
-    const int* res_id;
-    long long k_aa;          // its records
-    RespairBag bag[RESPAIR_PLANE_BAGS];
-    uint32_t nres_t;         // residues of the topology (resident residues of model f: [f nres_t, (f + 1) nres_t))
     int rbits, fbits;        // key = res_a << (rbits + fbits) | res_b << fbits | f
-    // re-keyed records: written by the two rekey kernels, read (sorted) by everything after the radix passes
-    unsigned long long* key;
-    unsigned long long* val;
+    // the re-keyed records, sorted
+    const unsigned long long* key;
+    const unsigned long long* val;
     const int* row_start;    // [U + 1] (RunArgs)
     long long U;
-    // the table, one column after the other (respersist_layout)
+    // the table, one column after the other (RESPERSIST_TABLE)
     double* t_dsum;
     int* t_a;
     int* t_b;
@@ -59,42 +47,9 @@ struct RespersistArgs {
     float* t_dmax;
     uint16_t* t_nmodels;
     uint16_t* t_cls;         // [U][RESPERSIST_CLASSES]
-    uint16_t* t_bits;        // [U][RESPERSIST_BITS]
+    uint16_t* t_bits;        // [U][TABLE_SIFT_BITS]
     uint8_t* t_ctype;
 };
-
-// the unordered topology pair and the model as a key; a negative residue leaves the record out.  Both residues lie in the
-// same model, so the model of either is the record's.
-__device__ __forceinline__ bool respersist_key(int ra, int rb, const RespersistArgs& A, unsigned long long* key) {
-    if ((ra | rb) < 0) { *key = ~0ull; return false; }
-    const uint32_t f = (uint32_t)ra / A.nres_t;
-    const uint32_t base = f * A.nres_t;
-    const uint32_t lo = (uint32_t)min(ra, rb) - base, hi = (uint32_t)max(ra, rb) - base;
-    *key = ((unsigned long long)lo << (A.rbits + A.fbits)) | ((unsigned long long)hi << A.fbits) | (unsigned long long)f;
-    return true;
-}
-
-__global__ __launch_bounds__(256) void k_respersist_rekey(RespersistArgs A) {
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < A.k_aa; p += (long long)gridDim.x * blockDim.x) {
-        unsigned long long key;
-        const bool kept = respersist_key(A.res_id[A.ci[p]], A.res_id[A.cj[p]], A, &key);
-        A.key[p] = key;
-        A.val[p] = kept ? (unsigned long long)__float_as_uint(A.d_in[p]) | ((unsigned long long)(A.s_in[p] & 0x7FFFu) << 32) |
-                              ((unsigned long long)(A.ct_in[p] & 7u) << 47)
-                        : RESPAIR_LEFT_OUT << RESPAIR_CLASS_SHIFT;
-    }
-}
-
-// grid (x, RESPAIR_PLANE_BAGS): row y of the grid walks bag y
-__global__ __launch_bounds__(256) void k_respersist_rekey_planes(RespersistArgs A) {
-    const RespairBag g = A.bag[blockIdx.y];
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < g.count; p += (long long)gridDim.x * blockDim.x) {
-        unsigned long long key;
-        const bool kept = respersist_key(g.res_of_a[g.a[p]], g.res_of_b[g.b[p]], A, &key);
-        A.key[g.out + p] = key;
-        A.val[g.out + p] = (kept ? (unsigned long long)(blockIdx.y + 1) : RESPAIR_LEFT_OUT) << RESPAIR_CLASS_SHIFT;
-    }
-}
 
 // What a closed model adds to the row, on every lane alike: its SIFt bits and classes to the counts (lane b keeps count b),
 // and — when it has an atom-atom record — its smallest distance to dist_min / dist_max / dist_sum.
@@ -126,23 +81,23 @@ __global__ __launch_bounds__(256) void k_respersist_reduce(RespersistArgs A) {
         float c_min = inf;
         for (long long q = s; q < e; q += 64) {      // (wave-uniform trip count)
             const bool in = q + lane < e;
-            const unsigned long long v = in ? A.val[q + lane] : RESPAIR_LEFT_OUT << RESPAIR_CLASS_SHIFT;
-            const uint32_t cls = (uint32_t)(v >> RESPAIR_CLASS_SHIFT) & 7u;
+            const unsigned long long v = in ? A.val[q + lane] : TABLE_LEFT_OUT << TABLE_CLASS_SHIFT;
+            const uint32_t cls = payload_class(v);
             const bool valid = cls < (uint32_t)RESPERSIST_CLASSES;      // (valid lanes are a prefix: the left-out records sort last)
             const int nv = __popcll(__ballot(valid));
             if (nv == 0) break;
             const uint32_t f = valid ? (uint32_t)(A.key[q + lane] & fmask) : 0u;
             const bool aa = cls == 0u;
-            const uint32_t sf = aa ? (uint32_t)(v >> 32) & 0x7FFFu : 0u;
-            if (aa) types |= 1u << ((uint32_t)(v >> 47) & 7u);
+            const uint32_t sf = aa ? payload_sift(v) : 0u;
+            if (aa) types |= 1u << payload_type(v);
             // ---- segments: a lane is a head when its f differs from the lane before (lane 0: from the open model)
             const uint32_t fp = __shfl_up(f, 1);
             const bool head = valid && (lane == 0 ? (!open || f != c_f) : f != fp);
             const unsigned long long hb = __ballot(head);
             const bool cont = open && !(hb & 1ull);          // the open model goes on in this step's first segment
             if (open && !cont) {                             // ... or it is closed before this step's models
-                if (lane < RESPERSIST_BITS) r.cnt += (c_sf >> lane) & 1u;
-                else if (lane < RESPERSIST_LANE_MODELS) r.cnt += (c_cls >> (lane - RESPERSIST_BITS)) & 1u;
+                if (lane < TABLE_SIFT_BITS) r.cnt += (c_sf >> lane) & 1u;
+                else if (lane < RESPERSIST_LANE_MODELS) r.cnt += (c_cls >> (lane - TABLE_SIFT_BITS)) & 1u;
                 else if (lane == RESPERSIST_LANE_MODELS) r.cnt += 1u;
                 if (c_cls & 1u) respersist_close_distance(r, c_min);
             }
@@ -157,7 +112,7 @@ __global__ __launch_bounds__(256) void k_respersist_reduce(RespersistArgs A) {
             // ---- per-model presence: each ballot of the step restricted to the lane's own segment, and counted where a model ends
             uint32_t m_sf = carried ? c_sf : 0u, m_cls = carried ? c_cls : 0u;
 #pragma unroll
-            for (int b = 0; b < RESPERSIST_BITS; ++b) {
+            for (int b = 0; b < TABLE_SIFT_BITS; ++b) {
                 m_sf |= (__ballot((sf >> b) & 1u) & seg) ? 1u << b : 0u;
                 const uint32_t c = (uint32_t)__popcll(__ballot(closing && ((m_sf >> b) & 1u)));
                 if (lane == b) r.cnt += c;
@@ -166,7 +121,7 @@ __global__ __launch_bounds__(256) void k_respersist_reduce(RespersistArgs A) {
             for (int m = 0; m < RESPERSIST_CLASSES; ++m) {
                 m_cls |= (__ballot(cls == (uint32_t)m) & seg) ? 1u << m : 0u;
                 const uint32_t c = (uint32_t)__popcll(__ballot(closing && ((m_cls >> m) & 1u)));
-                if (lane == RESPERSIST_BITS + m) r.cnt += c;
+                if (lane == TABLE_SIFT_BITS + m) r.cnt += c;
             }
             {
                 const uint32_t c = (uint32_t)__popcll(__ballot(closing)), n = (uint32_t)__popcll(__ballot(aa));
@@ -174,7 +129,7 @@ __global__ __launch_bounds__(256) void k_respersist_reduce(RespersistArgs A) {
                 if (lane == RESPERSIST_LANE_CONTACTS) r.cnt += n;
             }
             // ---- per-model minimum: an inclusive scan that stops at segment heads; the segment's last lane holds the minimum
-            float d = aa ? __uint_as_float((uint32_t)v) : inf;
+            float d = aa ? payload_distance(v) : inf;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
                 const float t = __shfl_up(d, o);
@@ -193,14 +148,14 @@ __global__ __launch_bounds__(256) void k_respersist_reduce(RespersistArgs A) {
         }
         // the run ends: its last model closes (a run begins on a kept record, so there is one)
         if (open) {
-            if (lane < RESPERSIST_BITS) r.cnt += (c_sf >> lane) & 1u;
-            else if (lane < RESPERSIST_LANE_MODELS) r.cnt += (c_cls >> (lane - RESPERSIST_BITS)) & 1u;
+            if (lane < TABLE_SIFT_BITS) r.cnt += (c_sf >> lane) & 1u;
+            else if (lane < RESPERSIST_LANE_MODELS) r.cnt += (c_cls >> (lane - TABLE_SIFT_BITS)) & 1u;
             else if (lane == RESPERSIST_LANE_MODELS) r.cnt += 1u;
             if (c_cls & 1u) respersist_close_distance(r, c_min);
         }
         for (int o = 32; o > 0; o >>= 1) types |= __shfl_xor(types, o);
-        if (lane < RESPERSIST_BITS) A.t_bits[row * RESPERSIST_BITS + lane] = (uint16_t)r.cnt;
-        else if (lane < RESPERSIST_LANE_MODELS) A.t_cls[row * RESPERSIST_CLASSES + (lane - RESPERSIST_BITS)] = (uint16_t)r.cnt;
+        if (lane < TABLE_SIFT_BITS) A.t_bits[row * TABLE_SIFT_BITS + lane] = (uint16_t)r.cnt;
+        else if (lane < RESPERSIST_LANE_MODELS) A.t_cls[row * RESPERSIST_CLASSES + (lane - TABLE_SIFT_BITS)] = (uint16_t)r.cnt;
         else if (lane == RESPERSIST_LANE_MODELS) A.t_nmodels[row] = (uint16_t)r.cnt;
         else if (lane == RESPERSIST_LANE_CONTACTS) A.t_n[row] = r.cnt;
         if (lane == 0) {

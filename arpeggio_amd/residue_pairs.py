@@ -18,18 +18,17 @@ import os
 
 import numpy as np
 
+from . import tables
 from .core import config
 
-COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_contacts', np.uint32), ('dist_min', np.float32),
-           ('bit_count', np.uint32), ('ctype_mask', np.uint8), ('plane_count', np.uint32))
-N_BITS = 15
-PLANE_BAGS = ('atom_plane', 'plane_plane', 'group_group', 'group_plane')
-_WIDTH = {'bit_count': N_BITS, 'plane_count': len(PLANE_BAGS)}
+COLUMNS = tables.RESPAIR.columns
+N_BITS = tables.N_BITS
+PLANE_BAGS = tables.PLANE_BAGS
 
 
 def empty():
     """A table without rows."""
-    return {k: np.zeros((0, _WIDTH[k]) if k in _WIDTH else 0, dt) for k, dt in COLUMNS}
+    return tables.empty(tables.RESPAIR)
 
 
 def split(table, res_offsets):
@@ -66,18 +65,15 @@ def to_records(table, pc, component_types=None):
     types met, and 'distance_min' is None for a pair without atom-atom records."""
     from .core import export
     lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
-    names, ctn = config.SIFT_NAMES, config.CONTACT_TYPE_NAMES
     out = []
     for r in range(len(table['res_a'])):
         n = int(table['n_contacts'][r])
-        bc = table['bit_count'][r].tolist()
         pl = table['plane_count'][r].tolist()
-        cm = int(table['ctype_mask'][r])
         out.append({'bgn': _residue_dict(lab, int(table['res_a'][r])), 'end': _residue_dict(lab, int(table['res_b'][r])),
                     'type': 'residue-residue', 'n_contacts': n, 'distance_min': float(table['dist_min'][r]) if n else None,
-                    'contact': {names[k]: bc[k] for k in range(N_BITS) if bc[k]},
+                    'contact': tables.sift_counts(table['bit_count'][r].tolist()),
                     'planes': {PLANE_BAGS[k]: pl[k] for k in range(len(PLANE_BAGS)) if pl[k]},
-                    'interacting_entities': [ctn[k] for k in range(len(ctn)) if (cm >> k) & 1]})
+                    'interacting_entities': tables.contact_types(int(table['ctype_mask'][r]))})
     return out
 
 
@@ -91,16 +87,14 @@ def write_csv(path, table, pc, component_types=None):
     types met, joined with '|'."""
     from .core import export
     lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
-    ctn = config.CONTACT_TYPE_NAMES
     with open(path, 'w', newline='') as fh:
         w = csv.writer(fh, delimiter=',', quotechar='"', quoting=csv.QUOTE_MINIMAL)
         w.writerow(CSV_HEADER)
         for r in range(len(table['res_a'])):
             n = int(table['n_contacts'][r])
-            cm = int(table['ctype_mask'][r])
             w.writerow([lab.res_macro[int(table['res_a'][r])], lab.res_macro[int(table['res_b'][r])], n,
                         str(table['dist_min'][r]) if n else ''] + table['bit_count'][r].tolist() + table['plane_count'][r].tolist() +
-                       ['|'.join(ctn[k] for k in range(len(ctn)) if (cm >> k) & 1)])
+                       ['|'.join(tables.contact_types(int(table['ctype_mask'][r])))])
 
 
 def write_residue_contacts(wd, sid, table, pc, component_types=None):

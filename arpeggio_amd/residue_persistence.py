@@ -23,22 +23,18 @@ import os
 
 import numpy as np
 
+from . import tables
 from .core import config
-from .residue_pairs import PLANE_BAGS, _residue_dict
+from .residue_pairs import _residue_dict
 
-COLUMNS = (('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
-           ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
-           ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8))
-N_BITS = 15
-CLASSES = ('atom_atom',) + PLANE_BAGS
-_WIDTH = {'class_models': len(CLASSES), 'bit_models': N_BITS}
-_U16_MAX = 65535
-_U32_MAX = 0xFFFFFFFF
+COLUMNS = tables.RESPERSIST.columns
+N_BITS = tables.N_BITS
+CLASSES = tables.CLASSES
 
 
 def empty():
     """A table without rows."""
-    return {k: np.zeros((0, _WIDTH[k]) if k in _WIDTH else 0, dt) for k, dt in COLUMNS}
+    return tables.empty(tables.RESPERSIST)
 
 
 def merge(t1, t2, model_offset):
@@ -47,47 +43,9 @@ def merge(t1, t2, model_offset):
     ``dist_sum = t1.dist_sum + t2.dist_sum`` in that order, as ``persistence.merge`` defines it — so a table accumulated
     chunk by chunk is defined to the bit by the chunking, and differs from the one-pass table of all the models at most in
     the rounding of ``dist_sum``.  Rows in (res_a, res_b) order.  ``OverflowError`` when a count would leave its type."""
-    model_offset = int(model_offset)
-    if model_offset < 0:
-        raise ValueError('merge: model_offset must not be negative')
-    a = np.concatenate([t1['res_a'], t2['res_a']]).astype(np.int64)
-    b = np.concatenate([t1['res_b'], t2['res_b']]).astype(np.int64)
-    n1 = len(t1['res_a'])
-    stride = int(b.max()) + 1 if len(b) else 1
-    key, inv = np.unique(a * stride + b, return_inverse=True)
-    inv = inv.reshape(-1)
-    U = len(key)
-    r1, r2 = inv[:n1], inv[n1:]      # (a table's pairs are distinct: each of r1, r2 hits a row at most once)
-    out = {'res_a': (key // stride).astype(np.int32), 'res_b': (key % stride).astype(np.int32)}
-    for k, width, top in (('n_models', None, _U16_MAX), ('n_contacts', None, _U32_MAX), ('class_models', len(CLASSES), _U16_MAX),
-                          ('bit_models', N_BITS, _U16_MAX)):
-        acc = np.zeros(U if width is None else (U, width), np.int64)
-        acc[r1] += t1[k]
-        acc[r2] += t2[k]
-        if acc.size and acc.max() > top:
-            raise OverflowError(f'merge: {k} leaves its type (a pair counted in more than 65535 models, or 2^32 records)')
-        out[k] = acc.astype(dict(COLUMNS)[k])
-    first, last = np.zeros(U, np.int32), np.zeros(U, np.int32)
-    first[r2] = t2['first'] + model_offset      # (every model of t2 comes after every model of t1 ...)
-    first[r1] = t1['first']                     # ... so t1's first wins where both have the pair,
-    last[r1] = t1['last']
-    last[r2] = t2['last'] + model_offset        # and t2's last
-    out['first'], out['last'] = first, last
-    # (a pair without atom-atom records on one side brings +inf / -inf / 0.0 there: the identities of min / max / +)
-    dmin, dmax = np.full(U, np.inf, np.float32), np.full(U, -np.inf, np.float32)
-    dmin[r1], dmax[r1] = t1['dist_min'], t1['dist_max']
-    dmin[r2] = np.minimum(dmin[r2], t2['dist_min'])
-    dmax[r2] = np.maximum(dmax[r2], t2['dist_max'])
-    out['dist_min'], out['dist_max'] = dmin, dmax
-    s1, s2 = np.zeros(U, np.float64), np.zeros(U, np.float64)
-    s1[r1] = t1['dist_sum']
-    s2[r2] = t2['dist_sum']
-    out['dist_sum'] = s1 + s2
-    ct = np.zeros(U, np.uint8)
-    ct[r1] |= t1['ctype_mask']
-    ct[r2] |= t2['ctype_mask']
-    out['ctype_mask'] = ct
-    return {k: out[k] for k, _ in COLUMNS}
+    return tables.merge(tables.RESPERSIST, t1, t2, model_offset, ('res_a', 'res_b'),
+                        {'n_models': 65535, 'n_contacts': 0xFFFFFFFF, 'class_models': 65535, 'bit_models': 65535},
+                        'merge: {k} leaves its type (a pair counted in more than 65535 models, or 2^32 records)')
 
 
 def frequency(t, n_models):
@@ -107,12 +65,9 @@ def to_records(t, pc, component_types=None):
     None for a pair without atom-atom records."""
     from .core import export
     lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
-    names, ctn = config.SIFT_NAMES, config.CONTACT_TYPE_NAMES
     out = []
     for r in range(len(t['res_a'])):
-        bm = t['bit_models'][r].tolist()
         cl = t['class_models'][r].tolist()
-        cm = int(t['ctype_mask'][r])
         s = float(t['dist_sum'][r])
         aa = cl[0]
         out.append({'bgn': _residue_dict(lab, int(t['res_a'][r])), 'end': _residue_dict(lab, int(t['res_b'][r])),
@@ -120,9 +75,9 @@ def to_records(t, pc, component_types=None):
                     'last_model': int(t['last'][r]), 'n_contacts': int(t['n_contacts'][r]),
                     'distance_min': float(t['dist_min'][r]) if aa else None, 'distance_max': float(t['dist_max'][r]) if aa else None,
                     'distance_sum': s if aa else None, 'distance_mean': s / aa if aa else None,
-                    'contact': {names[k]: bm[k] for k in range(N_BITS) if bm[k]},
+                    'contact': tables.sift_counts(t['bit_models'][r].tolist()),
                     'classes': {CLASSES[k]: cl[k] for k in range(len(CLASSES)) if cl[k]},
-                    'interacting_entities': [ctn[k] for k in range(len(ctn)) if (cm >> k) & 1]})
+                    'interacting_entities': tables.contact_types(int(t['ctype_mask'][r]))})
     return out
 
 
@@ -136,17 +91,15 @@ def write_csv(path, t, pc, component_types=None):
     counts and the contact types met, joined with '|'."""
     from .core import export
     lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
-    ctn = config.CONTACT_TYPE_NAMES
     with open(path, 'w', newline='') as fh:
         w = csv.writer(fh, delimiter=',', quotechar='"', quoting=csv.QUOTE_MINIMAL)
         w.writerow(CSV_HEADER)
         for r in range(len(t['res_a'])):
             aa = int(t['class_models'][r][0])
-            cm = int(t['ctype_mask'][r])
             dist = [str(t['dist_min'][r]), str(t['dist_max'][r]), repr(float(t['dist_sum'][r]))] if aa else ['', '', '']
             w.writerow([lab.res_macro[int(t['res_a'][r])], lab.res_macro[int(t['res_b'][r])], int(t['n_models'][r]), int(t['first'][r]),
                         int(t['last'][r]), int(t['n_contacts'][r])] + dist + t['class_models'][r].tolist() + t['bit_models'][r].tolist() +
-                       ['|'.join(ctn[k] for k in range(len(ctn)) if (cm >> k) & 1)])
+                       ['|'.join(tables.contact_types(int(t['ctype_mask'][r])))])
 
 
 def write_residue_persistence(wd, sid, t, pc, component_types=None):

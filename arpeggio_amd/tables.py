@@ -1,0 +1,98 @@
+"""What the three device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
+(``residue_pairs``) and residue persistence (``residue_persistence``).
+
+A table is a dict of NumPy columns with one row per pair.  A ``Spec`` names the columns in the order of the C fetch's
+arguments (include/arpeggio_hip.h) with their types, and the width of those that hold several values a row.  Everything here
+is NumPy on the host.
+"""
+from typing import NamedTuple
+
+import numpy as np
+
+from .core import config
+
+N_BITS = 15       # SIFt bits with a count of their own (ARP_*_BITS): config.SIFT_NAMES[:15]
+PLANE_BAGS = ('atom_plane', 'plane_plane', 'group_group', 'group_plane')
+CLASSES = ('atom_atom',) + PLANE_BAGS
+
+
+class Spec(NamedTuple):
+    columns: tuple      # ((name, dtype), ...)
+    width: dict         # name -> values per row, for the columns that are [U, width]
+
+
+PERSIST = Spec((('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                ('dist_min', np.float32), ('dist_max', np.float32), ('dist_sum', np.float64), ('bit_count', np.uint16),
+                ('ctype_mask', np.uint8)), {'bit_count': N_BITS})
+RESPAIR = Spec((('res_a', np.int32), ('res_b', np.int32), ('n_contacts', np.uint32), ('dist_min', np.float32),
+                ('bit_count', np.uint32), ('ctype_mask', np.uint8), ('plane_count', np.uint32)),
+               {'bit_count': N_BITS, 'plane_count': len(PLANE_BAGS)})
+RESPERSIST = Spec((('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                   ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
+                   ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8)),
+                  {'class_models': len(CLASSES), 'bit_models': N_BITS})
+
+
+def alloc(spec, U, make=np.empty):
+    """The columns of ``spec`` for ``U`` rows, each made by ``make(shape, dtype)``."""
+    return {k: make((U, spec.width[k]) if k in spec.width else U, dt) for k, dt in spec.columns}
+
+
+def empty(spec):
+    """A table without rows."""
+    return alloc(spec, 0, np.zeros)
+
+
+def merge(spec, t1, t2, model_offset, keys, additive, overflow, mins=('dist_min',), maxs=('dist_max',), ors=('ctype_mask',)):
+    """The table of two chunks of one trajectory: ``t1`` over models [0, model_offset), ``t2`` over the models that follow.
+    Rows are joined on the two ``keys`` columns and come back in their order.  ``additive`` maps each count column to the
+    largest value its type holds (``OverflowError(overflow.format(k=column))`` beyond it); ``mins`` / ``maxs`` / ``ors`` name
+    the columns combined by min / max / OR; 'first' / 'last' are model indices (those of ``t2`` shifted by ``model_offset``);
+    and ``dist_sum = t1.dist_sum + t2.dist_sum`` in that order.  A row that one side lacks brings +inf / -inf / 0 / 0.0 there:
+    the identities of min / max / OR / +."""
+    model_offset = int(model_offset)
+    if model_offset < 0:
+        raise ValueError('merge: model_offset must not be negative')
+    ka, kb = keys
+    a = np.concatenate([t1[ka], t2[ka]]).astype(np.int64)
+    b = np.concatenate([t1[kb], t2[kb]]).astype(np.int64)
+    n1 = len(t1[ka])
+    stride = int(b.max()) + 1 if len(b) else 1
+    key, inv = np.unique(a * stride + b, return_inverse=True)
+    inv = inv.reshape(-1)
+    U = len(key)
+    r1, r2 = inv[:n1], inv[n1:]      # (a table's pairs are distinct: each of r1, r2 hits a row at most once)
+    out = alloc(spec, U, np.zeros)
+    out[ka], out[kb] = (key // stride).astype(np.int32), (key % stride).astype(np.int32)
+    for k, top in additive.items():
+        acc = np.zeros(out[k].shape, np.int64)
+        acc[r1] += t1[k]
+        acc[r2] += t2[k]
+        if acc.size and acc.max() > top:
+            raise OverflowError(overflow.format(k=k))
+        out[k] = acc.astype(out[k].dtype)
+    out['first'][r2] = t2['first'] + model_offset      # (every model of t2 comes after every model of t1 ...)
+    out['first'][r1] = t1['first']                     # ... so t1's first wins where both have the pair,
+    out['last'][r1] = t1['last']
+    out['last'][r2] = t2['last'] + model_offset        # and t2's last
+    for names, identity, fold in ((mins, np.inf, np.minimum), (maxs, -np.inf, np.maximum), (ors, 0, np.bitwise_or)):
+        for k in names:
+            out[k][:] = identity
+            out[k][r1] = t1[k]
+            out[k][r2] = fold(out[k][r2], t2[k])
+    s1, s2 = np.zeros(U, np.float64), np.zeros(U, np.float64)
+    s1[r1] = t1['dist_sum']
+    s2[r2] = t2['dist_sum']
+    out['dist_sum'] = s1 + s2        # (a pair of one table alone: x + 0.0, which is x — a sum of distances is never -0.0)
+    return out
+
+
+def sift_counts(counts):
+    """{SIFt name: count} for the counts of a row that are not zero."""
+    return {config.SIFT_NAMES[k]: counts[k] for k in range(N_BITS) if counts[k]}
+
+
+def contact_types(mask):
+    """The names of the contact types in a ``ctype_mask``."""
+    ctn = config.CONTACT_TYPE_NAMES
+    return [ctn[k] for k in range(len(ctn)) if (mask >> k) & 1]

@@ -653,7 +653,7 @@ int arp_residue_pairs_fetch(arp_ctx* ctx, int64_t cap, int32_t* res_a, int32_t* 
  * (residue, residue, model) does not fit a 63-bit key.
  *
  * arp_models_residue_persistence_fetch: the table with one device-to-host copy of one piece (its columns on 256-byte
- * boundaries, the float64 column first, through a page-locked stage); any column pointer may be NULL; class_models =
+ * boundaries, in the order of the arguments, through a page-locked stage); any column pointer may be NULL; class_models =
  * uint16[cap][5], bit_models = uint16[cap][ARP_RESPERSIST_BITS].  ARP_E_CAPACITY with *count = rows when cap is too small;
  * ARP_E_ARG without a launch. */
 #define ARP_RESPERSIST_BITS 15

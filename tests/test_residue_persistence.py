@@ -433,6 +433,33 @@ def test_segment_seams():
 
 
 @pytest.mark.gpu
+def test_a_fetch_of_one_column_returns_the_bytes_of_the_full_fetch():
+    """Seam structure a (16 atoms, two residues, F = 3), each of the three device-reduced tables, every column: a fetch with
+    only that column non-NULL gives the bytes the full fetch gives for it.  The slab of a table is laid out in the order of its
+    fetch's arguments; a column copied from another column's place would show here."""
+    _, n, F, away = SEAMS[0]
+    pc = seam_two_residues(n)
+    xyz, h_xyz = _translated(pc, F, away)
+    ctx = _ctx_with_models(pc, xyz, h_xyz)
+    ctx.run_launch(*PARAMS[0])
+    for table, fetch, columns in ((ctx.models_persistence, 'arp_models_persistence_fetch', _capi.PERSIST_COLUMNS),
+                                  (ctx.residue_pairs, 'arp_residue_pairs_fetch', _capi.RESPAIR_COLUMNS),
+                                  (ctx.models_residue_persistence, 'arp_models_residue_persistence_fetch', _capi.RESPERSIST_COLUMNS)):
+        full = table()
+        U = len(full[columns[0][0]])
+        assert U > 0 and list(full) == [k for k, _ in columns], fetch
+        for q, (k, dt) in enumerate(columns):
+            one = np.empty(full[k].shape, dt)
+            one.view(np.uint8)[...] = 0xA5
+            args = [None] * len(columns)
+            args[q] = _capi._p(one)
+            cnt = C.c_int64(-1)
+            assert getattr(ctx._L, fetch)(ctx._h, U, *args, C.byref(cnt)) == _capi.ARP_OK and cnt.value == U, (fetch, k)
+            assert one.tobytes() == full[k].tobytes(), (fetch, k)
+    ctx.close()
+
+
+@pytest.mark.gpu
 def test_left_out_records_do_not_split_the_row_they_tie_with():
     """seam_sentinel_tie in four models with an installed selection state and the five bags launched one by one (all five
     valid: a complete pass): the group-group records of the amide without a residue are left out, and (3, 3) is ONE row with

@@ -71,7 +71,7 @@ def kernel_stats(path):
     for p in glob.glob(os.path.join(path, '**', '*kernel_stats.csv'), recursive=True):
         for row in csv.DictReader(open(p)):
             name = row.get('Name', '')
-            if 'k_persist' in name or 'k_sort_' in name:
+            if 'k_persist' in name or 'k_runs_' in name or 'k_sort_' in name:
                 short = name.split('(')[0].split(' ')[-1]
                 out[short] = dict(calls=int(row['Calls']), total_us=float(row['TotalDurationNs']) / 1e3, average_us=float(row['AverageNs']) / 1e3)
     return out
