@@ -40,6 +40,7 @@ SYMBOLS = (
     'arp_models_persistence_launch', 'arp_models_persistence_fetch', 'arp_set_compact_lookback',
     'arp_residue_pairs_launch', 'arp_residue_pairs_fetch',
     'arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch',
+    'arp_contacts_filter_launch', 'arp_fetch_packed_filtered',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -192,6 +193,8 @@ def load():
     L.arp_residue_pairs_fetch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.arp_models_residue_persistence_launch.argtypes = [vp, C.POINTER(i64)]
     L.arp_models_residue_persistence_fetch.argtypes = [vp, i64] + [vp] * 12 + [C.POINTER(i64)]
+    L.arp_contacts_filter_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.arp_fetch_packed_filtered.argtypes = L.arp_fetch_packed.argtypes
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -681,14 +684,15 @@ class Context:
         self._check(self._L.arp_models_planes(self._h, _p(rc), _p(rn), _p(rr), _p(ac), _p(an)), 'arp_models_planes')
         return dict(ring_center=rc, ring_normal=rn, ring_res=rr, amide_center=ac, amide_normal=an)
 
-    def run_models(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, expand_radius=6.0):
+    def run_models(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, expand_radius=6.0, contact_filter=None):
         """run_arpeggio on every resident model in ONE pass; one ``fetch_packed``, cut into the models by contiguous ranges
         (``split_models``).  Returns a list of F dicts {atom_atom, atom_plane, plane_plane, group_group, group_plane} with
-        model-local ids."""
+        model-local ids.  ``contact_filter``: (sift_any, ctype_mask) — the fetch is ``fetch_packed_filtered``, every model's
+        atom-atom bag its kept records."""
         if self._models is None:
             raise ValueError('run_models: no models resident (set_models)')
         self.run_launch(cutoff, vdw_comp, include_sequence_adjacent, expand_radius)
-        bags, _ = self.fetch_packed()
+        bags, _ = self.fetch_packed() if contact_filter is None else self.fetch_packed_filtered(*contact_filter)
         return split_models(bags, self._models)
 
     def _table(self, launch, fetch, spec):
@@ -1017,7 +1021,10 @@ class Context:
                 bags[name] = self.fetch_bag(name, sort=sort_bags)
             return bags, buf
         self._check(rc, 'arp_fetch_packed')
+        return self._packed_views(buf, counts, offs), buf
 
+    def _packed_views(self, buf, counts, offs):
+        """The five bags of a packed fetch as views into ``buf`` (arp_fetch_packed's counts and offsets)."""
         def view(off, dtype, n):
             return np.frombuffer(buf, dtype, n, int(off)) if n else np.empty(0, dtype)
         k = int(counts[0])
@@ -1033,6 +1040,36 @@ class Context:
             # (every bag arrives in its canonical order, made on the device: one block's bitonic network for a bag of up to
             # BAG_SORT_MAX records, the radix passes of the atom-atom bag beyond that)
             bags[name] = res
+        return bags
+
+    def contacts_filter(self, sift_any=0x7FFF, ctype_mask=0x7F):
+        """Filter the resident atom-atom bag of the last pass on the device (arp_contacts_filter_launch): a record is kept when
+        ``(sift & sift_any) != 0`` and bit ``ctype`` of ``ctype_mask`` is set (``arpeggio_amd.contact_filter`` names the bits).
+        The kept records are sorted into the canonical order there, in the layout ``set_packed_layout`` names; returns their
+        number.  A second call with the same masks on the same results does no work."""
+        kept = C.c_int64(0)
+        self._check(self._L.arp_contacts_filter_launch(self._h, int(sift_any), int(ctype_mask), C.byref(kept)), 'arp_contacts_filter_launch')
+        return int(kept.value)
+
+    def fetch_packed_filtered(self, sift_any, ctype_mask=0x7F, buf=None):
+        """``fetch_packed`` with the atom-atom bag filtered ON THE DEVICE first (``contacts_filter``, then
+        arp_fetch_packed_filtered): only the kept records are sorted and cross PCIe, in canonical order — byte for byte the
+        columns of ``fetch_packed`` masked with the predicate —, the four ring / amide bags complete behind them.  ``buf`` as
+        in ``fetch_packed`` (grown when too small).  Returns ``(bags, buf)``; ``bags['atom_atom']`` is a ``RowsBag`` under the
+        rows layout, ``bags['atom_atom_total']`` the unfiltered count."""
+        self.contacts_filter(sift_any, ctype_mask)
+        counts = (C.c_int64 * 5)()
+        offs = (C.c_uint64 * 53)()
+        used = C.c_uint64(0)
+        if buf is None:
+            buf = pinned_empty(1 << 20, np.uint8)
+        rc = self._L.arp_fetch_packed_filtered(self._h, _p(buf), buf.nbytes, counts, offs, C.byref(used))
+        if rc == ARP_E_CAPACITY and int(used.value) > buf.nbytes:
+            buf = pinned_empty(int(used.value) + int(used.value) // 4 + 4096, np.uint8)
+            rc = self._L.arp_fetch_packed_filtered(self._h, _p(buf), buf.nbytes, counts, offs, C.byref(used))
+        self._check(rc, 'arp_fetch_packed_filtered')
+        bags = self._packed_views(buf, counts, offs)
+        bags['atom_atom_total'] = self.stats()['emitted']      # (arp_get_stats: the records the pass emitted)
         return bags, buf
 
     def atom_contacts(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, sort=True):

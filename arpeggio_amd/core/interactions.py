@@ -97,6 +97,7 @@ class InteractionComplex:
         self.selection_plus_amide_ids = []
         # result bags (I:84-88)
         self._bags = {}
+        self._contact_filter = None      # (sift_any, ctype_mask) of set_contact_filter
         self.params = Parameters(vdw_comp_factor=vdw_comp, interacting_threshold=interacting,
                                  has_hydrogens=bool(np.any(self.pc.flags & config.F_HYDROGEN)) or self.pc.h_xyz.shape[0] > 0,
                                  ph=ph)                                    # I:90-94
@@ -144,10 +145,24 @@ class InteractionComplex:
             raise IncompleteStructureError(needs)
         logging.warning('Structure read without OpenBabel, going on as asked (allow_incomplete); missing: %s', '; '.join(needs))
 
+    def set_contact_filter(self, contacts=None, interacting_entities=None):
+        """Extension beside the mirror (not in the reference): the next ``run_arpeggio`` fetches only the atom-atom records
+        with at least one of the named ``contacts`` (``config.SIFT_NAMES``) between entities of one of the named
+        ``interacting_entities`` kinds (``config.CONTACT_TYPE_NAMES``); ``None`` means all of that kind, and no arguments at
+        all clear the filter.  The records are picked on the GPU before they are sorted and copied
+        (``arpeggio_amd.contact_filter``, ``Context.fetch_packed_filtered``), so ``atom_contacts``, ``get_contacts``,
+        ``write_json`` and ``write_contacts`` show the kept records only, the ring / amide bags whole.  What is made from the
+        bag resident on the GPU does not change: ``atom_sifts``, ``atom_integer_sifts``, ``residue_sifts``,
+        ``residue_contacts`` and the selection sets are those of the unfiltered run.  The check for what an incompletely read
+        structure would have needed (``allow_incomplete``) looks at the records fetched, that is the kept ones."""
+        from .. import contact_filter
+        self._contact_filter = None if contacts is None and interacting_entities is None else contact_filter.masks(contacts, interacting_entities)
+
     def _check_incomplete_after_run(self):
         """What of ``pc.incomplete`` the run that has just finished would have needed: atom types, rings and amide groups of the
         non-standard residues inside selection_plus (OpenBabel's SMARTS and ring perception, I:1697-1733, 1531-1589, 1966-1983),
-        and the single-bond neighbour of a halogen that takes part in a contact (U:139-141, 173)."""
+        and the single-bond neighbour of a halogen that takes part in a contact (U:139-141, 173).  It looks at the atom-atom
+        records that were fetched: with ``set_contact_filter`` in force, the kept ones."""
         pc = self.pc
         incomplete = getattr(pc, 'incomplete', ())
         untyped = getattr(pc, 'untyped_atoms', None)
@@ -225,7 +240,10 @@ class InteractionComplex:
         self.selection_plus_amide_ids = set(np.nonzero(masks['amide_plus'])[0].tolist())
         # all five bags with one copy; the atom-atom bag arrives in the canonical (i, j) order, made on the device
         # (the arrays are views into a page-locked buffer of their own: the next run allocates another one)
-        self._bags, _ = ctx.fetch_packed()
+        if self._contact_filter is None:
+            self._bags, _ = ctx.fetch_packed()
+        else:      # (set_contact_filter: the kept atom-atom records only, picked on the device)
+            self._bags, _ = ctx.fetch_packed_filtered(*self._contact_filter)
         self._check_incomplete_after_run()
         self.stats = ctx.stats()
 
@@ -592,6 +610,7 @@ class EnsembleComplex:
                                  has_hydrogens=bool(np.any(self.pc.flags & config.F_HYDROGEN)) or self.pc.h_xyz.shape[0] > 0, ph=ph)
         self._set_arrays(xyz, h_xyz)
         self._results = None
+        self._contact_filter = None      # (sift_any, ctype_mask) of set_contact_filter
         self.persistence = None          # the table of run_persistence and the models it covers
         self.persistence_models = 0
         self.residue_persistence = None  # the table of run_residue_persistence and the models it covers
@@ -637,6 +656,12 @@ class EnsembleComplex:
 
     def _incomplete(self, needs):
         InteractionComplex._incomplete(self, needs)
+
+    def set_contact_filter(self, contacts=None, interacting_entities=None):
+        """``InteractionComplex.set_contact_filter`` for every model: the next ``run_arpeggio`` fetches the kept atom-atom
+        records of all models in one piece and cuts it into the models as it cuts the whole bag (a model's kept records are one
+        contiguous range).  The device-reduced tables (``run_persistence`` ...) read the resident bag and do not change."""
+        InteractionComplex.set_contact_filter(self, contacts, interacting_entities)
 
     def set_coordinates(self, xyz, h_xyz):
         """Replace the models (any number of them: the next chunk of a trajectory; numbered 1 ... F); only their coordinates
@@ -733,7 +758,8 @@ class EnsembleComplex:
             self.initialize()
         pc, ctx, F, n = self.pc, self._ctx, self.n_models, self.pc.n_atoms
         idx = self._upload_selection(user_selections)
-        per_model = ctx.run_models(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        per_model = ctx.run_models(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS,
+                                   contact_filter=self._contact_filter)
         masks = ctx.make_selection_masks()
         R, A = pc.n_rings, pc.n_amides
         self._results = []
@@ -770,6 +796,7 @@ class EnsembleComplex:
         ic = InteractionComplex(self.model_pack(k), self.params.vdw_comp_factor, self.params.interacting_threshold, self.params.ph,
                                 self.device, self.allow_incomplete)
         ic.id = self.id if self.n_models == 1 else f'{self.id}_model{self.model_numbers[k]}'
+        ic._contact_filter = self._contact_filter
         if self._results is not None:
             r = self._results[k]
             ic._bags = r['bags']

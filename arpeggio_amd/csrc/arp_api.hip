@@ -31,6 +31,7 @@
 #include "arp_persist.h"
 #include "arp_respair.h"
 #include "arp_respersist.h"
+#include "arp_filter.h"
 #include "arp_blob.h"
 
 namespace {
@@ -248,6 +249,16 @@ struct HintKey {
 struct ResultTable {
     DevBuf<uint8_t> slab;
     int64_t count = 0;
+    bool valid = false;
+};
+
+// the atom-atom records a caller asked for (arp_contacts_filter_launch): the kept records as the filter left them, and their
+// canonical order in a slab of their own, laid out as sorted_slab is — with room for the ring / amide bags behind the columns
+struct FilteredBag {
+    DevBuf<uint8_t> cols, slab;
+    int64_t count = 0;
+    uint32_t sift_any = 0, ctype_mask = 0;
+    bool csr = false;                   // the slab's first column is N + 1 row offsets
     bool valid = false;
 };
 
@@ -474,6 +485,7 @@ struct arp_ctx {
     uint8_t* table_stage = nullptr;       // page-locked host side of a fetch's one copy (its first word also receives U)
     size_t table_stage_cap = 0;
     ResultTable persist, respair, respersist;
+    FilteredBag filtered;                 // arp_contacts_filter_launch: tile counts and total in table_tiles / table_total
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -734,6 +746,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->persist.valid = false;
         c->respair.valid = false;
         c->respersist.valid = false;
+        c->filtered.valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1908,6 +1921,7 @@ bool finish_contacts(arp_ctx* c) {
     c->persist.valid = false;
     c->respair.valid = false;
     c->respersist.valid = false;
+    c->filtered.valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2042,6 +2056,7 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     ++b.version;
     c->respair.valid = false;
     c->respersist.valid = false;
+    c->filtered.valid = false;      // (the bags packed behind the kept records are sized when it is made)
     return false;
 }
 int grow_pairs(arp_ctx* c) {
@@ -2248,6 +2263,7 @@ void arp_destroy(arp_ctx* c) {
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
     c->table_sort.release(); c->table_tiles.release(); c->table_rows.release(); c->table_total.release();
     c->persist.slab.release(); c->respair.slab.release(); c->respersist.slab.release();
+    c->filtered.cols.release(); c->filtered.slab.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -3138,47 +3154,70 @@ int bag_order_large(arp_ctx* c, const int* first, const int* second, size_t k, i
 
 // Every result of the last pass with ONE copy: the atom-atom bag in canonical order (sorted on the device if it is not yet)
 // and the used prefixes of the four ring / amide bags behind it, gathered in HBM (k_pack_segments) and copied in one piece.
-int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used) {
-    if (!c || !counts || !offsets || !bytes_used) return ARP_E_ARG;
-    if (!c->contacts_valid) FAIL(c, ARP_E_ARG, "arp_fetch_packed: no launch results");
-    HIPCHK(c, hipSetDevice(c->device));
-    Bag* bags[4] = {&c->bag_pp, &c->bag_ap, &c->bag_gg, &c->bag_gp};      // (the order of get_contacts, I:183-210)
-    static const size_t es[12] = {4, 4, 8, 8, 8, 8, 4, 4, 4, 1, 1, 1};
-    size_t off[5], cbytes;
-    const bool csr = c->packed_csr && !c->has_gid;
-    if (c->packed_csr && c->has_gid) FAIL(c, ARP_E_ARG, "arp_fetch_packed: the row-offset layout needs packed atom ids (this context holds a shard with global ids)");
-    sorted_layout((size_t)c->n_contacts, off, &cbytes, csr ? (size_t)std::max<int64_t>(c->n, 0) + 1 : (size_t)c->n_contacts);
-    size_t total = cbytes;
+// arp_fetch_packed and arp_fetch_packed_filtered differ in which atom-atom columns lead the piece, in which slab (PackedAtomBag);
+// everything behind that is fetch_packed_from.
+namespace {
+struct PackedAtomBag {
+    const char* who;             // the entry point, for messages
+    int64_t k;                   // records of the atom-atom bag it delivers
+    bool csr;                    // first column: N + 1 row offsets
+    FilteredBag* filtered;       // the kept records, sorted in their own slab already; NULL: the whole bag in sorted_slab (sorted on the way)
+};
+// Where every array of every bag goes in the one piece: the five atom-atom columns (sorted_layout), then the arrays of the
+// ring / amide bags (the order of get_contacts, I:183-210), each on a 16-byte boundary
+struct PackedPlan {
+    size_t off[5], cbytes, total;
     PackTable t;
+    int seg_of[4][12];
+    Bag* bags[4];
+};
+int packed_plan(arp_ctx* c, const PackedAtomBag& S, PackedPlan& P, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS]) {
+    const std::string who = S.who;
+    static const size_t es[12] = {4, 4, 8, 8, 8, 8, 4, 4, 4, 1, 1, 1};
+    Bag* const bags[4] = {&c->bag_pp, &c->bag_ap, &c->bag_gg, &c->bag_gp};
+    sorted_layout((size_t)S.k, P.off, &P.cbytes, S.csr ? (size_t)std::max<int64_t>(c->n, 0) + 1 : (size_t)S.k);
+    size_t total = P.cbytes;
+    PackTable& t = P.t;
     t.n = 0;
     for (int q = 0; q < ARP_PACKED_OFFSETS; ++q) offsets[q] = 0;
-    for (int q = 0; q < 5; ++q) offsets[q] = off[q];
-    counts[0] = c->n_contacts;
-    // Sizes first: where every array of every bag goes in the one piece, and whether it fits — before anything is launched (a
-    // caller with too small a buffer, or a result beyond what one piece can address, leaves with bytes_used and no work done)
-    *bytes_used = 0;
-    int seg_of[4][12];
+    for (int q = 0; q < 5; ++q) offsets[q] = P.off[q];
+    counts[0] = S.k;
     for (int b = 0; b < 4; ++b) {
         Bag& g = *bags[b];
+        P.bags[b] = bags[b];
         counts[1 + b] = g.valid ? g.count : 0;
-        for (int q = 0; q < 12; ++q) seg_of[b][q] = -1;
+        for (int q = 0; q < 12; ++q) P.seg_of[b][q] = -1;
         if (!g.valid || g.count == 0) continue;
-        if ((uint64_t)g.count >= ((uint64_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, "arp_fetch_packed: a ring / amide bag of 2^31 records or more (fetch the bags one by one)");
+        if ((uint64_t)g.count >= ((uint64_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, who + ": a ring / amide bag of 2^31 records or more (fetch the bags one by one)");
         const uint8_t* ptr[12] = {(const uint8_t*)g.a.p, (const uint8_t*)g.b.p, (const uint8_t*)g.d0.p, (const uint8_t*)g.d1.p,
                                   (const uint8_t*)g.d2.p, (const uint8_t*)g.d3.p, (const uint8_t*)g.f0.p, (const uint8_t*)g.f1.p,
                                   (const uint8_t*)g.f2.p, g.u0.p, g.u1.p, g.u2.p};
         for (int q = 0; q < 12; ++q) {
             if (!ptr[q]) continue;
             const size_t bytes = (size_t)g.count * es[q];
-            if (t.n >= 48 || bytes >= ((size_t)1 << 32) || total >= ((size_t)1 << 32)) FAIL(c, ARP_E_CAPACITY, "arp_fetch_packed: ring / amide bags too large for one piece (fetch them one by one)");
+            if (t.n >= 48 || bytes >= ((size_t)1 << 32) || total >= ((size_t)1 << 32)) FAIL(c, ARP_E_CAPACITY, who + ": ring / amide bags too large for one piece (fetch them one by one)");
             offsets[5 + 12 * b + q] = total;
-            seg_of[b][q] = t.n;
+            P.seg_of[b][q] = t.n;
             t.s[t.n++] = PackSeg{ptr[q], (uint32_t)total, (uint32_t)bytes, nullptr, (uint32_t)es[q]};
             total = (total + bytes + 15) & ~(size_t)15;
         }
     }
+    P.total = total;
+    return ARP_OK;
+}
+int fetch_packed_from(arp_ctx* c, const PackedAtomBag& S, void* host, uint64_t host_bytes, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used) {
+    const std::string who = S.who;
+    // Sizes first: where every array of every bag goes in the one piece, and whether it fits — before anything is launched (a
+    // caller with too small a buffer, or a result beyond what one piece can address, leaves with bytes_used and no work done)
+    *bytes_used = 0;
+    PackedPlan P;
+    CHK(packed_plan(c, S, P, counts, offsets));
+    Bag* const* bags = P.bags;
+    PackTable& t = P.t;
+    const size_t total = P.total, cbytes = P.cbytes;
     *bytes_used = total;
-    if (!host || host_bytes < total) FAIL(c, ARP_E_CAPACITY, "arp_fetch_packed: host buffer too small (bytes_used holds the size needed)");
+    if (!host || host_bytes < total) FAIL(c, ARP_E_CAPACITY, who + ": host buffer too small (bytes_used holds the size needed)");
+    if (S.filtered && S.filtered->slab.cap < total) FAIL(c, ARP_E_HIP, who + ": the filtered slab has no room for the ring / amide bags");      // (sized by the launch; finish_bag voids it)
     // canonical order of the small bags, made on the device: plane-plane, group-group, group-plane by (first id, second id),
     // atom-plane by (ring, atom) — the order the reference's loops create them in
     BagOrderArgs bo{};
@@ -3205,15 +3244,16 @@ int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts
     const bool order_aside = any_order && c->stream2 && !c->external_stream;      // (beside the sort, which may be under way already: arp_set_sort_after_pass)
     for (int b = 0; b < 4; ++b)
         for (int q = 0; q < 12; ++q)
-            if (seg_of[b][q] >= 0) t.s[seg_of[b][q]].perm = bo.n[b] > 0 ? bo.perm[b] : big_perm[b];
-    c->contacts_sorted = c->contacts_sorted && c->sorted_slab.cap >= total && c->sorted_is_csr == csr;
+            if (P.seg_of[b][q] >= 0) t.s[P.seg_of[b][q]].perm = bo.n[b] > 0 ? bo.perm[b] : big_perm[b];
+    if (!S.filtered) c->contacts_sorted = c->contacts_sorted && c->sorted_slab.cap >= total && c->sorted_is_csr == S.csr;
     // (aside: the sort's launches go out first — they are the critical path, the host needs ~5 us per launch —, the one block per
     // small bag on the second stream behind them)
     if (any_order && !order_aside) {
         hipLaunchKernelGGL(k_bag_order, dim3(4), dim3(1024), 0, c->stream, bo);
         CHK(check_launch(c, "k_bag_order"));
     }
-    CHK(sort_contacts(c, total - cbytes));
+    if (!S.filtered) CHK(sort_contacts(c, total - cbytes));
+    DevBuf<uint8_t>& slab = S.filtered ? S.filtered->slab : c->sorted_slab;
     if (any_order && order_aside) {
         hipLaunchKernelGGL(k_bag_order, dim3(4), dim3(1024), 0, c->stream2, bo);
         CHK(check_launch(c, "k_bag_order"));
@@ -3221,7 +3261,7 @@ int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts
     }
     if (order_aside) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_planes, 0));
     if (t.n > 0) {
-        hipLaunchKernelGGL(k_pack_segments, pack_grid(t), dim3(256), 0, c->stream, t, c->sorted_slab.p);
+        hipLaunchKernelGGL(k_pack_segments, pack_grid(t), dim3(256), 0, c->stream, t, slab.p);
         CHK(check_launch(c, "k_pack_segments"));
     }
     if (total) {
@@ -3229,21 +3269,30 @@ int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts
         // the copy engine needs ~10 us to get going, which is as long as such a copy takes (stand-in end to end 0.155 -> see
         // profiles/README.md).  Anything larger, or a pageable buffer: the copy engine.
         void* host_dev = nullptr;
-        if (total <= sw().fetch_direct_max && host_bytes >= ((total + 15) & ~(uint64_t)15) && c->sorted_slab.cap >= ((total + 15) & ~(size_t)15)) {      // (whole quads on both sides)
+        if (total <= sw().fetch_direct_max && host_bytes >= ((total + 15) & ~(uint64_t)15) && slab.cap >= ((total + 15) & ~(size_t)15)) {      // (whole quads on both sides)
             hipPointerAttribute_t at{};
             if (hipPointerGetAttributes(&at, host) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) host_dev = at.devicePointer;
             else (void)hipGetLastError();
         }
         if (host_dev && ((uintptr_t)host_dev & 15) == 0) {
             const unsigned nq = (unsigned)((total + 15) / 16);
-            hipLaunchKernelGGL(k_copy_quads, dim3(nblocks(nq, 256, 1024)), dim3(256), 0, c->stream, (const int4*)c->sorted_slab.p, (int4*)host_dev, nq);
+            hipLaunchKernelGGL(k_copy_quads, dim3(nblocks(nq, 256, 1024)), dim3(256), 0, c->stream, (const int4*)slab.p, (int4*)host_dev, nq);
             CHK(check_launch(c, "k_copy_quads"));
         } else {
-            HIPCHK(c, hipMemcpyAsync(host, c->sorted_slab.p, total, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(host, slab.p, total, hipMemcpyDeviceToHost, c->stream));
         }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ARP_OK;
+}
+}  // namespace
+
+int arp_fetch_packed(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used) {
+    if (!c || !counts || !offsets || !bytes_used) return ARP_E_ARG;
+    if (!c->contacts_valid) FAIL(c, ARP_E_ARG, "arp_fetch_packed: no launch results");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->packed_csr && c->has_gid) FAIL(c, ARP_E_ARG, "arp_fetch_packed: the row-offset layout needs packed atom ids (this context holds a shard with global ids)");
+    return fetch_packed_from(c, PackedAtomBag{"arp_fetch_packed", c->n_contacts, c->packed_csr && !c->has_gid, nullptr}, host, host_bytes, counts, offsets, bytes_used);
 }
 
 int arp_atom_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_sequence_adjacent, int64_t cap, int32_t* out_i,
@@ -4331,6 +4380,93 @@ int arp_models_residue_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* res_a
     return table_fetch(c, RESPERSIST_TABLE, cap, dst, count);
 }
 
+// ---- the atom-atom records a caller asks for (arp_filter.h): filter the bag of the pass, sort the kept records alone
+// The host shape of the tables: count per tile and scan on the stream, ONE wait for k', size, enqueue the rest — the kept
+// records into columns of their own, their canonical order (radix_sort, as sort_contacts runs it) into the filtered slab.
+// sorted_slab, contacts_sorted and sorted_is_csr are not touched: an unfiltered fetch returns what it returned.
+int arp_contacts_filter_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mask, int64_t* kept) {
+    if (!c || !kept) return ARP_E_ARG;
+    const char* const fn = "arp_contacts_filter_launch: ";
+    if ((sift_any & ~ARP_FILTER_SIFT_ALL) || (ctype_mask & ~ARP_FILTER_CTYPE_ALL)) FAIL(c, ARP_E_ARG, std::string(fn) + "a mask has bits beyond the 15 SIFt bits / the 7 contact types");
+    if (!sift_any || !ctype_mask) FAIL(c, ARP_E_ARG, std::string(fn) + "a mask of 0 keeps nothing");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, std::string(fn) + "not for a shard of a distributed structure");
+    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, std::string(fn) + "no atom-contact results (call a launch first)");
+    FilteredBag& F = c->filtered;
+    const bool csr = c->packed_csr;
+    if (F.valid && F.sift_any == sift_any && F.ctype_mask == ctype_mask && F.csr == csr) { *kept = F.count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    F.valid = false;
+    const size_t k = (size_t)c->n_contacts;
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, std::string(fn) + "2^31 records or more (the digit table's prefixes are 32-bit)");
+    const size_t rows = (size_t)std::max<int64_t>(c->n, 0);
+    // ---- kept records per tile, scanned; the host learns k' (the one wait)
+    FilterArgs A{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k; A.sift_any = sift_any; A.ctype_mask = ctype_mask;
+    const int T = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
+    long long kp = 0;
+    if (k > 0) {
+        HIPCHK(c, c->table_tiles.reserve((size_t)T));
+        HIPCHK(c, c->table_total.reserve(1));
+        CHK(table_stage_reserve(c, 4096));
+        A.tile_keep = c->table_tiles.p;
+        RunArgs R{};
+        R.T = T; R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
+        hipLaunchKernelGGL(k_filter_count, dim3(T), dim3(FILTER_THREADS), 0, c->stream, A);
+        hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+        CHK(check_launch(c, "arp_contacts_filter_launch: count / scan"));
+        HIPCHK(c, hipMemcpyAsync(c->table_stage, c->table_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        memcpy(&kp, c->table_stage, sizeof(kp));
+        if (kp < 0 || kp > (long long)k) FAIL(c, ARP_E_HIP, std::string(fn) + "kept count out of range");
+    }
+    // ---- the slab of the sorted result, with room for the ring / amide bags arp_fetch_packed_filtered packs behind it
+    const PackedAtomBag S{"arp_contacts_filter_launch", (int64_t)kp, csr, &F};
+    PackedPlan P;
+    int64_t counts[5];
+    uint64_t offsets[ARP_PACKED_OFFSETS];
+    CHK(packed_plan(c, S, P, counts, offsets));
+    HIPCHK(c, F.slab.reserve(std::max(P.total, (size_t)16)));
+    F.count = kp; F.sift_any = sift_any; F.ctype_mask = ctype_mask; F.csr = csr;
+    if (kp == 0) {      // (0 records, no launch: the row column is all zeros, as sort_contacts leaves it for k = 0)
+        if (csr) HIPCHK(c, hipMemsetAsync(F.slab.p + P.off[0], 0, (rows + 1) * sizeof(int32_t), c->stream));
+        F.valid = true;
+        *kept = 0;
+        return ARP_OK;
+    }
+    // ---- the kept records, in the order the bag holds them: five columns sized for exactly k'
+    size_t coff[5], cbytes;
+    sorted_layout((size_t)kp, coff, &cbytes, (size_t)kp);
+    HIPCHK(c, F.cols.reserve(cbytes));
+    A.i_out = (int*)(F.cols.p + coff[0]); A.j_out = (int*)(F.cols.p + coff[1]); A.d_out = (float*)(F.cols.p + coff[2]);
+    A.s_out = (uint16_t*)(F.cols.p + coff[3]); A.ct_out = F.cols.p + coff[4];
+    A.kept = kp;
+    hipLaunchKernelGGL(k_filter_write, dim3(T), dim3(FILTER_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, "k_filter_write"));
+    // ---- their canonical order (the sort of sort_contacts, over k' records)
+    const int64_t idmax = std::max<int64_t>(c->n - 1, 1);
+    SortArgs Q{};
+    Q.ci = A.i_out; Q.cj = A.j_out; Q.d_in = A.d_out; Q.s_in = A.s_out; Q.ct_in = A.ct_out;
+    uint8_t* slab = F.slab.p;
+    Q.i_out = (int*)(slab + P.off[0]); Q.j_out = (int*)(slab + P.off[1]); Q.d_out = (float*)(slab + P.off[2]);
+    Q.s_out = (uint16_t*)(slab + P.off[3]); Q.ct_out = slab + P.off[4];
+    Q.row_out = csr ? Q.i_out : nullptr;
+    Q.nrows = (int)rows;
+    const bool small = sw().sort_small && (size_t)kp <= (size_t)SORT_SMALL_MAX_RECORDS && idmax + 1 <= (int64_t)SORT_SMALL_MAX_BINS;
+    CHK(radix_sort(c, c->sort_aa, Q, (size_t)kp, std::max(k, c->out_i.cap), id_bits(idmax), small ? (int)idmax + 1 : 0, "arp_contacts_filter_launch"));
+    F.valid = true;
+    *kept = kp;
+    return ARP_OK;
+}
+
+int arp_fetch_packed_filtered(arp_ctx* c, void* host, uint64_t host_bytes, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used) {
+    if (!c || !counts || !offsets || !bytes_used) return ARP_E_ARG;
+    FilteredBag& F = c->filtered;
+    if (!c->contacts_valid || !F.valid || F.csr != c->packed_csr) FAIL(c, ARP_E_ARG, "arp_fetch_packed_filtered: no filtered result (arp_contacts_filter_launch after a pass)");
+    HIPCHK(c, hipSetDevice(c->device));
+    return fetch_packed_from(c, PackedAtomBag{"arp_fetch_packed_filtered", F.count, F.csr, &F}, host, host_bytes, counts, offsets, bytes_used);
+}
+
 // ---- exchange between the shards of a distributed structure (RCCL behind the C ABI) -----------------------------------
 #define NCCLCHK(ctx, expr)                                                                              \
     do {                                                                                                \
@@ -4508,6 +4644,7 @@ int arp_set_sort_after_pass(arp_ctx* c, int enabled) {
 
 int arp_set_packed_layout(arp_ctx* c, int layout) {
     if (!c || (layout != ARP_LAYOUT_RECORDS && layout != ARP_LAYOUT_ROWS)) return ARP_E_ARG;
+    if (c->packed_csr != (layout == ARP_LAYOUT_ROWS)) c->filtered.valid = false;
     c->packed_csr = layout == ARP_LAYOUT_ROWS;
     return ARP_OK;
 }

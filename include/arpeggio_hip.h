@@ -663,6 +663,36 @@ int arp_models_residue_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* res
                                          uint16_t* class_models /* [cap][5] */, uint16_t* bit_models /* [cap][15] */,
                                          float* dist_min, float* dist_max, double* dist_sum, uint8_t* ctype_mask,
                                          int64_t* count);
+/* ---- only the atom-atom records a caller asks for: the bag filtered on the device, then sorted and fetched ------------------
+ * A record is kept when (sift & sift_any) != 0 && ((1u << ctype) & ctype_mask) != 0: at least one of the named SIFt bits
+ * (ARP_S_*) and a contact type among the named ones (bit ARP_CT_* of ctype_mask).  Only the low 15 bits of sift_any and the
+ * low 7 bits of ctype_mask may be set, and neither mask may be 0 (it would keep nothing): ARP_E_ARG otherwise.  There is no
+ * distance term (a smaller cutoff is another pass) and no "none of these bits" term; the five ladder bits (clash, covalent,
+ * vdw_clash, vdw, proximal) exclude each other, so "not bare proximity" is sift_any = ARP_FILTER_SIFT_ALL & ~ARP_S_PROXIMAL.
+ *
+ * arp_contacts_filter_launch: filters the bag of the last launch as the pass left it (never the sorted slab), waits once for
+ * *kept = k', the kept records, and enqueues their canonical sort — over k' records only — into a slab of the filtered
+ * result's own, in the layout arp_set_packed_layout names at this moment.  The result is byte for byte what masking the
+ * columns of arp_fetch_packed with the predicate gives (the (i, j) key of a record is unique: the sort alone fixes the
+ * order); in the ROWS layout row[] are the N + 1 offsets into the kept records (all zeros when none is kept).  It needs
+ * atom-atom results (ARP_E_ARG without), is refused on a shard (ARP_E_ARG, like the device-reduced tables), and returns
+ * ARP_E_CAPACITY for a bag of 2^31 records or more.  No record in the bag, or none kept: *kept = 0, nothing is launched.
+ * A second call with the same masks and layout on the same results returns the stored count without work; other masks
+ * re-make the result.  It is voided by every input change, by the next launch that fills the atom-atom bag or any ring /
+ * amide bag (the bags packed behind it are sized here), and by a change of arp_set_packed_layout.  The unfiltered results
+ * are neither read nor written: arp_fetch_packed, arp_atom_contacts_fetch, arp_atom_contacts_sort and the tables return the
+ * same before, after and without these calls, with arp_set_sort_after_pass on or off.  With a batch or models resident the
+ * ids are those of the concatenation and a structure's kept records stay one contiguous range in canonical order.
+ *
+ * arp_fetch_packed_filtered: arp_fetch_packed's contract in every respect — one copy, the meaning of counts and offsets, the
+ * four ring / amide bags complete and in canonical order behind the atom-atom columns, ARP_E_CAPACITY with bytes_used set
+ * before anything is launched — except that the atom-atom bag is the kept records: counts[0] = k'.  ARP_E_ARG without a
+ * valid filtered result. */
+#define ARP_FILTER_SIFT_ALL  0x7FFFu
+#define ARP_FILTER_CTYPE_ALL 0x7Fu
+int arp_contacts_filter_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t ctype_mask, int64_t* kept);
+int arp_fetch_packed_filtered(arp_ctx* ctx, void* host, uint64_t host_bytes, int64_t counts[5],
+                              uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
