@@ -41,6 +41,7 @@ SYMBOLS = (
     'arp_residue_pairs_launch', 'arp_residue_pairs_fetch',
     'arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch',
     'arp_contacts_filter_launch', 'arp_fetch_packed_filtered',
+    'arp_water_bridges_launch', 'arp_water_bridges_fetch',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -195,6 +196,8 @@ def load():
     L.arp_models_residue_persistence_fetch.argtypes = [vp, i64] + [vp] * 12 + [C.POINTER(i64)]
     L.arp_contacts_filter_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
     L.arp_fetch_packed_filtered.argtypes = L.arp_fetch_packed.argtypes
+    L.arp_water_bridges_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.arp_water_bridges_fetch.argtypes = [vp, i64] + [vp] * 9 + [C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -726,6 +729,21 @@ class Context:
         [U, 5], ``bit_models`` as [U, 15]; see ``arpeggio_amd.residue_persistence``).  Only the table is copied to the host;
         the bags of the pass and the two other tables stay fetchable as before."""
         return self._table('arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch', tables.RESPERSIST)
+
+    def water_bridges(self, sift_any, flags=0):
+        """The water-mediated contacts of the last pass, joined on the device (arp_water_bridges_*): one row per water and
+        unordered pair of its partners, rows in ascending (water, a, b).  A leg is a record with exactly one water atom and
+        ``(sift & sift_any) != 0``; ``flags``: ``water_bridges.SAME_RESIDUE`` keeps the pairs of one residue.  Returns a dict of
+        the nine columns ``water_bridges.COLUMNS`` (see ``arpeggio_amd.water_bridges``).  Only the table is copied to the host;
+        the bags of the pass, the filtered bag and the three tables stay fetchable as before.  With a batch or models resident
+        the ids are those of the concatenation (``water_bridges.split_structures`` / ``split_models``)."""
+        from . import water_bridges as wb
+        n = C.c_int64(0)
+        self._check(self._L.arp_water_bridges_launch(self._h, int(sift_any), int(flags), C.byref(n)), 'arp_water_bridges_launch')
+        U = int(n.value)
+        t = {k: np.empty(U, dt) for k, dt in wb.COLUMNS}
+        self._check(self._L.arp_water_bridges_fetch(self._h, U, *(_p(t[k]) for k, _ in wb.COLUMNS), C.byref(n)), 'arp_water_bridges_fetch')
+        return t
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

@@ -365,6 +365,25 @@ class InteractionComplex:
         from .. import residue_pairs
         return residue_pairs.write_residue_contacts(wd, self.id, self.residue_contacts(), self.pc, self.component_types)
 
+    def water_bridges(self, contacts=('hbond', 'polar'), same_residue=False):
+        """Extension beside the mirror (not in the reference, which marks water contacts — I:643-691, 821-852 — but never says
+        what a water sits between): the water-mediated contacts of the last run, one row per water and unordered pair of the
+        atoms it touches through a record with one of the named ``contacts`` (``config.SIFT_NAMES``; ``None``: any); pairs of
+        one residue only with ``same_residue``.  ``arpeggio_amd.water_bridges`` describes the nine columns.  The atom-atom bag
+        that ``run_arpeggio`` left resident on the GPU is joined with itself there — only the table is copied — whatever
+        ``set_contact_filter`` made of the fetched records."""
+        from .. import water_bridges as wb
+        self._need_results()
+        if self._ctx is None:
+            raise AttributeError('no results on a GPU context: call run_arpeggio() on this complex first')
+        return self._ctx.water_bridges(wb.mask(contacts), wb.SAME_RESIDUE if same_residue else 0)
+
+    def write_water_bridges(self, wd, contacts=('hbond', 'polar'), same_residue=False):
+        """'<id>.waterbridges': ``water_bridges()`` as CSV, one row per bridge with the atom labels of the other CSV writers
+        (``water_bridges.write_csv``)."""
+        from .. import water_bridges as wb
+        return wb.write_water_bridges(wd, self.id, self.water_bridges(contacts, same_residue), self.pc, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""
@@ -728,6 +747,29 @@ class EnsembleComplex:
         self._results = None
         self.stats = self._ctx.stats()
         return residue_pairs.split(t, np.arange(self.n_models + 1, dtype=np.int64) * self.pc.n_residues)
+
+    def run_water_bridges(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, contacts=('hbond', 'polar'),
+                          same_residue=False):
+        """Extension beside the mirror: the water-mediated contacts of every model (``InteractionComplex.water_bridges``): the
+        selection handling and the pass of ``run_arpeggio``, then ONE join on the device over the records of all models and
+        ONE fetch of the table.  A water only meets atoms of its own model, so the rows of a model are one contiguous range:
+        the table comes back with topology atom ids and a ``model`` column (0-based, int32), rows ascending by (model, water,
+        a, b).  No bag is copied to the host: ``model(k)`` has no results after this call (``run_arpeggio`` gives those).
+        Persistence of bridges over the models is not reduced on the device: fold the rows of each model with
+        ``water_bridges.by_residue`` on the host."""
+        from .. import water_bridges as wb
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        t = self._ctx.water_bridges(wb.mask(contacts), wb.SAME_RESIDUE if same_residue else 0)
+        self._results = None
+        self.stats = self._ctx.stats()
+        n = self.pc.n_atoms
+        model = (t['water'] // n).astype(np.int32)
+        out = {k: ((t[k] - model * n).astype(np.int32) if k in ('water', 'a', 'b') else t[k]) for k, _ in wb.COLUMNS}
+        out['model'] = model
+        return out
 
     def run_residue_persistence(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, accumulate=False):
         """Residue contact persistence over the models — a residue contact-frequency map: the selection handling and the pass

@@ -32,6 +32,7 @@
 #include "arp_respair.h"
 #include "arp_respersist.h"
 #include "arp_filter.h"
+#include "arp_bridge.h"
 #include "arp_blob.h"
 
 namespace {
@@ -486,6 +487,12 @@ struct arp_ctx {
     size_t table_stage_cap = 0;
     ResultTable persist, respair, respersist;
     FilteredBag filtered;                 // arp_contacts_filter_launch: tile counts and total in table_tiles / table_total
+    // water-mediated contacts (arp_water_bridges_launch, arp_bridge.h): the table and what it was made for; the legs are sorted in
+    // table_sort and their runs found in table_tiles / table_rows / table_total, like a table's records
+    ResultTable bridges;
+    uint32_t bridges_sift_any = 0, bridges_flags = 0;
+    DevBuf<long long> bridge_off;         // [L + 1] kept pairs per water run, then their exclusive prefix; [L] = rows
+    DevBuf<int> bridge_res;               // [L] residue of every sorted leg's partner
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -708,7 +715,8 @@ enum : unsigned {
 // selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
-//   persistence table of the resident models (arp_models_persistence_launch) is made from the atom-atom bag and goes with it;
+//   persistence table of the resident models (arp_models_persistence_launch) and the water bridges
+//   (arp_water_bridges_launch) are made from the atom-atom bag and go with it;
 //   the residue-pair table (arp_residue_pairs_launch) and the residue persistence table
 //   (arp_models_residue_persistence_launch) are made from all five and go with any of them (finish_contacts, finish_bag: the
 //   next launch that refills a bag).
@@ -747,6 +755,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->respair.valid = false;
         c->respersist.valid = false;
         c->filtered.valid = false;
+        c->bridges.valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1922,6 +1931,7 @@ bool finish_contacts(arp_ctx* c) {
     c->respair.valid = false;
     c->respersist.valid = false;
     c->filtered.valid = false;
+    c->bridges.valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2264,6 +2274,7 @@ void arp_destroy(arp_ctx* c) {
     c->table_sort.release(); c->table_tiles.release(); c->table_rows.release(); c->table_total.release();
     c->persist.slab.release(); c->respair.slab.release(); c->respersist.slab.release();
     c->filtered.cols.release(); c->filtered.slab.release();
+    c->bridges.slab.release(); c->bridge_off.release(); c->bridge_res.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4465,6 +4476,121 @@ int arp_fetch_packed_filtered(arp_ctx* c, void* host, uint64_t host_bytes, int64
     if (!c->contacts_valid || !F.valid || F.csr != c->packed_csr) FAIL(c, ARP_E_ARG, "arp_fetch_packed_filtered: no filtered result (arp_contacts_filter_launch after a pass)");
     HIPCHK(c, hipSetDevice(c->device));
     return fetch_packed_from(c, PackedAtomBag{"arp_fetch_packed_filtered", F.count, F.csr, &F}, host, host_bytes, counts, offsets, bytes_used);
+}
+
+// ---- water-mediated contacts (arp_bridge.h): the atom-atom bag joined with itself on its water atoms
+// Two waits — L legs, then B rows — and arguments, so the sequence is its own and not make_table's; the steps are the tables':
+// reserve_key_sort / enqueue_key_sort, the run kernels, enqueue_run_starts, table_layout, and table_fetch for the fetch.  U,
+// the waters with a leg, is never read by the host: row_start is made for L runs (the most there can be) and the kernels take
+// U from table_total.  The bags, sorted_slab, contacts_sorted, sorted_is_csr, the filtered bag and the three tables are
+// neither read nor written.
+namespace {
+enum { WB_WATER = 0, WB_A, WB_B, WB_DIST_A, WB_DIST_B, WB_SIFT_A, WB_SIFT_B, WB_CTYPE_A, WB_CTYPE_B, WB_COLS };
+const TableSpec BRIDGE_TABLE = {"arp_water_bridges", &arp_ctx::bridges, WB_COLS, {4, 4, 4, 4, 4, 2, 2, 1, 1},
+                                false, false, "no atom-contact results (call a launch first)", 0};
+static_assert(WB_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+static_assert(BRIDGE_F_WATER == ARP_F_WATER && BRIDGE_SAME_RESIDUE == ARP_WB_SAME_RESIDUE, "arp_bridge.h names the header's bits");
+// one 64-bit word from the device through the page-locked stage: a wait
+int read_word(arp_ctx* c, const long long* dev, long long* v) {
+    CHK(table_stage_reserve(c, 4096));
+    HIPCHK(c, hipMemcpyAsync(c->table_stage, dev, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(v, c->table_stage, sizeof(*v));
+    return ARP_OK;
+}
+}  // namespace
+
+int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const std::string fn = "arp_water_bridges_launch: ";
+    if (sift_any & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_any has bits beyond the 15 SIFt bits");
+    if (!sift_any) FAIL(c, ARP_E_ARG, fn + "a sift_any of 0 makes no record a leg");
+    if (flags & ~ARP_WB_SAME_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, fn + BRIDGE_TABLE.no_pass);
+    ResultTable& T = c->bridges;
+    if (T.valid && c->bridges_sift_any == sift_any && c->bridges_flags == flags) { *count = T.count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    T.valid = false;
+    T.count = 0;
+    const size_t k = (size_t)c->n_contacts;
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
+    const auto done = [&](long long rows) {
+        T.count = rows; T.valid = true;
+        c->bridges_sift_any = sift_any; c->bridges_flags = flags;
+        *count = rows;
+        return ARP_OK;
+    };
+    if (k == 0) return done(0);
+    // ---- legs per tile, scanned; the host learns L (wait 1)
+    BridgeLegArgs A{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k; A.flags = c->flags.p; A.sift_any = sift_any;
+    A.pbits = id_bits(std::max<int64_t>(c->n - 1, 1));      // (key = w << pbits | partner: at most 62 bits)
+    const int tiles = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
+    HIPCHK(c, c->table_tiles.reserve((size_t)tiles));
+    HIPCHK(c, c->table_total.reserve(1));
+    A.tile_keep = c->table_tiles.p;
+    RunArgs R{};
+    R.T = tiles; R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
+    hipLaunchKernelGGL(k_bridge_legs_count, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+    CHK(check_launch(c, (fn + "legs count / scan").c_str()));
+    long long L = 0;
+    CHK(read_word(c, c->table_total.p, &L));
+    if (L < 0 || L > (long long)k) FAIL(c, ARP_E_HIP, fn + "leg count out of range");
+    if (L == 0) return done(0);
+    // ---- the legs keyed by (water, partner), sorted by every bit: a water's legs become one run, partners ascending
+    SortScratch& s = c->table_sort;
+    CHK(reserve_key_sort(c, s, (size_t)L, (size_t)L));
+    A.key = s.key[0].p; A.val = s.val[0].p; A.legs = L;
+    hipLaunchKernelGGL(k_bridge_legs_write, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    int sorted = 0;
+    enqueue_key_sort(c, s, (size_t)L, 2 * A.pbits, &sorted);
+    // ---- the runs: at most L of them, so their starts are made for L and U stays on the device (no wait of its own)
+    R = RunArgs{};
+    R.key = s.key[sorted].p; R.k = L; R.shift = A.pbits;
+    R.T = (int)((L + RUNS_TILE - 1) / RUNS_TILE);      // (<= tiles: table_tiles is large enough, and the legs' prefixes are consumed in stream order)
+    R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
+    hipLaunchKernelGGL(k_runs_count, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
+    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+    CHK(enqueue_run_starts(c, R, L));
+    // ---- kept pairs per run, scanned in 64 bits; the host learns B (wait 2)
+    HIPCHK(c, c->bridge_off.reserve((size_t)L + 1));
+    HIPCHK(c, c->bridge_res.reserve((size_t)L));
+    BridgePairArgs P{};
+    P.key = R.key; P.val = s.val[sorted].p; P.legs = L; P.pbits = A.pbits;
+    P.row_start = R.row_start; P.runs = c->table_total.p; P.res_id = c->res_id.p; P.leg_res = c->bridge_res.p;
+    P.flags = flags; P.row_off = c->bridge_off.p;
+    const int pair_blocks = nblocks(L, 4, 16384);       // (one wave per run; U <= L)
+    if (!(flags & ARP_WB_SAME_RESIDUE)) hipLaunchKernelGGL(k_bridge_leg_res, dim3(nblocks(L, 256, 2048)), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(k_bridge_pairs<false>, dim3(pair_blocks), dim3(256), 0, c->stream, P);
+    hipLaunchKernelGGL(k_bridge_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, P);
+    CHK(check_launch(c, (fn + "sort / pairs count").c_str()));
+    long long B = 0;
+    CHK(read_word(c, c->bridge_off.p + L, &B));
+    if (B < 0) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    if (B >= (1ll << 31)) { *count = B; FAIL(c, ARP_E_CAPACITY, fn + "2^31 rows or more"); }
+    if (B == 0) return done(0);
+    // ---- the rows, each at its rank
+    size_t off[TABLE_MAX_COLS], bytes;
+    table_layout(BRIDGE_TABLE, (size_t)B, off, &bytes);
+    HIPCHK(c, T.slab.reserve(bytes));
+    uint8_t* const slab = T.slab.p;
+    P.rows = B;
+    P.t_w = (int*)(slab + off[WB_WATER]); P.t_a = (int*)(slab + off[WB_A]); P.t_b = (int*)(slab + off[WB_B]);
+    P.t_da = (float*)(slab + off[WB_DIST_A]); P.t_db = (float*)(slab + off[WB_DIST_B]);
+    P.t_sa = (uint16_t*)(slab + off[WB_SIFT_A]); P.t_sb = (uint16_t*)(slab + off[WB_SIFT_B]);
+    P.t_ca = slab + off[WB_CTYPE_A]; P.t_cb = slab + off[WB_CTYPE_B];
+    hipLaunchKernelGGL(k_bridge_pairs<true>, dim3(pair_blocks), dim3(256), 0, c->stream, P);
+    CHK(check_launch(c, (fn + "pairs write").c_str()));
+    return done(B);
+}
+
+int arp_water_bridges_fetch(arp_ctx* c, int64_t cap, int32_t* water, int32_t* a, int32_t* b, float* dist_a, float* dist_b,
+                            uint16_t* sift_a, uint16_t* sift_b, uint8_t* ctype_a, uint8_t* ctype_b, int64_t* count) {
+    void* const dst[WB_COLS] = {water, a, b, dist_a, dist_b, sift_a, sift_b, ctype_a, ctype_b};
+    return table_fetch(c, BRIDGE_TABLE, cap, dst, count);
 }
 
 // ---- exchange between the shards of a distributed structure (RCCL behind the C ABI) -----------------------------------

@@ -693,6 +693,43 @@ int arp_models_residue_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* res
 int arp_contacts_filter_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t ctype_mask, int64_t* kept);
 int arp_fetch_packed_filtered(arp_ctx* ctx, void* host, uint64_t host_bytes, int64_t counts[5],
                               uint64_t offsets[ARP_PACKED_OFFSETS], uint64_t* bytes_used);
+/* ---- water-mediated contacts: the atom-atom bag joined with itself on its water atoms, on the device ---------------------
+ * The reference marks water contacts — the water branches of __get_contact_type (I:643-691: SELECTION_WATER,
+ * NON_SELECTION_WATER, WATER_WATER) and the *_water_only hbond / polar counters per atom (I:821-852) — but never says what a
+ * water sits BETWEEN.  This table does: which two atoms share a water.  It is an extension beside the mirror.
+ *
+ * Inputs: the atom-atom bag of the last pass as the pass left it, the per-atom flags (ARP_F_WATER) and res_id.
+ *   leg      a record (i, j) with exactly one of i, j flagged ARP_F_WATER and (sift & sift_any) != 0.  The water atom is w, the
+ *            other atom the partner.  Water-water records and records without a water are no legs: first-order bridges only.
+ *   bridge   for every water w and every unordered pair a < b (resident atom ids) of its partners one row (w, a, b) — dropped
+ *            when res_id[a] == res_id[b], unless flags has ARP_WB_SAME_RESIDUE.
+ * Columns, in the order of the fetch's arguments:
+ *   water, a, b        int32    resident atom ids
+ *   dist_a, dist_b     float32  the bits of the distances of the records (w, a) and (w, b)
+ *   sift_a, sift_b     uint16   the whole SIFt of each leg, not masked with sift_any
+ *   ctype_a, ctype_b   uint8    each leg's ARP_CT_* code
+ * A ligand-water-protein bridge is a row with one ARP_CT_SELECTION_WATER leg and one ARP_CT_NON_SELECTION_WATER leg.
+ * Rows ascend by (water, a, b).  The (i, j) key of a record is unique, so a water's partners are distinct: the rows are
+ * unique and the order is total.  Only the low 15 bits of sift_any may be set and it may not be 0; flags may hold
+ * ARP_WB_SAME_RESIDUE only (ARP_E_ARG otherwise).  With a batch or models resident nothing changes: ids are resident ids, a
+ * water only meets atoms of its own structure or model, and the rows of one structure or model are one contiguous range.
+ *
+ * arp_water_bridges_launch: makes the table on the context's stream from the bag as the pass left it (never the sorted slab)
+ * and waits twice: for the number of legs, and for *count = rows.  It needs atom-atom results of a finished pass (ARP_E_ARG
+ * without) and is refused on a shard of a distributed structure (ARP_E_ARG).  ARP_E_CAPACITY for a bag of 2^31 records or
+ * more and for 2^31 rows or more (*count = rows).  No record or no leg: *count = 0 and nothing more is launched.  A second
+ * call with the same sift_any and flags on the same results returns the stored count without work; other arguments remake
+ * the table.  It is voided by every input change and by the next launch that fills the atom-atom bag.  The bags, their sorted
+ * slab, the filtered bag and the three tables above are neither read nor written: every fetch returns the same before,
+ * after and without these calls.
+ *
+ * arp_water_bridges_fetch: the table with one device-to-host copy of one piece (its columns on 256-byte boundaries, through
+ * a page-locked stage); any column pointer may be NULL and is skipped.  ARP_E_CAPACITY with *count = rows when cap is too
+ * small; ARP_E_ARG without a launch.  A table of 0 rows copies nothing. */
+#define ARP_WB_SAME_RESIDUE (1u << 0)   /* keep the pairs of partners that share a residue */
+int arp_water_bridges_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t flags, int64_t* count);
+int arp_water_bridges_fetch(arp_ctx* ctx, int64_t cap, int32_t* water, int32_t* a, int32_t* b, float* dist_a, float* dist_b,
+                            uint16_t* sift_a, uint16_t* sift_b, uint8_t* ctype_a, uint8_t* ctype_b, int64_t* count);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
