@@ -42,10 +42,12 @@ SYMBOLS = (
     'arp_models_residue_persistence_launch', 'arp_models_residue_persistence_fetch',
     'arp_contacts_filter_launch', 'arp_fetch_packed_filtered',
     'arp_water_bridges_launch', 'arp_water_bridges_fetch',
+    'arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
-PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = tables.N_BITS
+PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
+WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 PERSIST_COLUMNS, RESPAIR_COLUMNS, RESPERSIST_COLUMNS = tables.PERSIST.columns, tables.RESPAIR.columns, tables.RESPERSIST.columns
 
@@ -198,6 +200,8 @@ def load():
     L.arp_fetch_packed_filtered.argtypes = L.arp_fetch_packed.argtypes
     L.arp_water_bridges_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
     L.arp_water_bridges_fetch.argtypes = [vp, i64] + [vp] * 9 + [C.POINTER(i64)]
+    L.arp_models_water_bridge_persistence_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.arp_models_water_bridge_persistence_fetch.argtypes = [vp, i64] + [vp] * 14 + [C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -743,6 +747,23 @@ class Context:
         U = int(n.value)
         t = {k: np.empty(U, dt) for k, dt in wb.COLUMNS}
         self._check(self._L.arp_water_bridges_fetch(self._h, U, *(_p(t[k]) for k, _ in wb.COLUMNS), C.byref(n)), 'arp_water_bridges_fetch')
+        return t
+
+    def models_water_bridge_persistence(self, sift_any, flags=0):
+        """Water-bridge persistence over the resident models of the last pass, reduced on the device
+        (arp_models_water_bridge_persistence_*): the bridge table of ``water_bridges(sift_any, flags & SAME_RESIDUE)`` folded
+        per pair of topology atoms — or, with ``WBP_BY_RESIDUE`` in ``flags``, of topology residues —, rows ascending by the
+        pair.  Returns a dict of the fourteen columns ``tables.BRIDGEPERSIST_ATOM`` / ``BRIDGEPERSIST_RESIDUE``
+        (``bit_models_a`` / ``bit_models_b`` as [U, 15]; see ``arpeggio_amd.bridge_persistence``).  Only the table is copied to
+        the host; the bridge table stays resident and fetchable, and every other result stays what it was."""
+        spec = tables.BRIDGEPERSIST_RESIDUE if int(flags) & WBP_BY_RESIDUE else tables.BRIDGEPERSIST_ATOM
+        n = C.c_int64(0)
+        self._check(self._L.arp_models_water_bridge_persistence_launch(self._h, int(sift_any), int(flags), C.byref(n)),
+                    'arp_models_water_bridge_persistence_launch')
+        U = int(n.value)
+        t = tables.alloc(spec, U)
+        self._check(self._L.arp_models_water_bridge_persistence_fetch(self._h, U, *(_p(t[k]) for k, _ in spec.columns), C.byref(n)),
+                    'arp_models_water_bridge_persistence_fetch')
         return t
 
     def set_blob(self, blob, counts=None):

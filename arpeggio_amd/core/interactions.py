@@ -634,6 +634,9 @@ class EnsembleComplex:
         self.persistence_models = 0
         self.residue_persistence = None  # the table of run_residue_persistence and the models it covers
         self.residue_persistence_models = 0
+        self.bridge_persistence = None   # the table of run_water_bridge_persistence, the models it covers and what it was made with
+        self.bridge_persistence_models = 0
+        self._bridge_persistence_key = None
 
     @property
     def n_models(self):
@@ -755,8 +758,7 @@ class EnsembleComplex:
         ONE fetch of the table.  A water only meets atoms of its own model, so the rows of a model are one contiguous range:
         the table comes back with topology atom ids and a ``model`` column (0-based, int32), rows ascending by (model, water,
         a, b).  No bag is copied to the host: ``model(k)`` has no results after this call (``run_arpeggio`` gives those).
-        Persistence of bridges over the models is not reduced on the device: fold the rows of each model with
-        ``water_bridges.by_residue`` on the host."""
+        Persistence of bridges over the models is ``run_water_bridge_persistence``."""
         from .. import water_bridges as wb
         if self._ctx is None:
             self.initialize()
@@ -793,6 +795,47 @@ class EnsembleComplex:
             self.residue_persistence, self.residue_persistence_models = t, self.n_models
         self.stats = self._ctx.stats()
         return self.residue_persistence
+
+    def run_water_bridge_persistence(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent,
+                                     contacts=('hbond', 'polar'), same_residue=False, level='atom', accumulate=False):
+        """Extension beside the mirror: water-bridge persistence over the models — in what fraction of the models a water
+        bridges two atoms (``level='atom'``) or two residues (``level='residue'``), through how many waters and how tightly:
+        the selection handling and the pass of ``run_water_bridges``, then the bridges of all models joined and folded ON THE
+        DEVICE to one row per topology pair (``arpeggio_amd.bridge_persistence`` describes the table) — and only that table
+        fetched, into ``self.bridge_persistence`` (also returned).  ``contacts`` and ``same_residue`` are those of
+        ``run_water_bridges``.  No bag is copied to the host: ``model(k)`` has no results after this call.
+        ``accumulate=True`` merges the table into that of the calls before it, this call's models following theirs
+        (``self.bridge_persistence_models`` counts them), as ``run_residue_persistence`` does; ``ValueError`` when the
+        contacts, ``same_residue`` or the level differ from those of the accumulated table."""
+        from .. import _capi, bridge_persistence as _bp, water_bridges as wb
+        if level not in _bp.LEVELS:
+            raise ValueError(f"run_water_bridge_persistence: level must be 'atom' or 'residue', not {level!r}")
+        key = (wb.mask(contacts), bool(same_residue), level)
+        merging = accumulate and self.bridge_persistence is not None
+        if merging and key != self._bridge_persistence_key:
+            raise ValueError('run_water_bridge_persistence: accumulate=True with other contacts, same_residue or level than the '
+                             'accumulated table was made with')
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        flags = (wb.SAME_RESIDUE if same_residue else 0) | (_capi.WBP_BY_RESIDUE if level == 'residue' else 0)
+        t = self._ctx.models_water_bridge_persistence(key[0], flags)
+        self._results = None
+        if merging:
+            self.bridge_persistence = _bp.merge(self.bridge_persistence, t, self.bridge_persistence_models)
+            self.bridge_persistence_models += self.n_models
+        else:
+            self.bridge_persistence, self.bridge_persistence_models, self._bridge_persistence_key = t, self.n_models, key
+        self.stats = self._ctx.stats()
+        return self.bridge_persistence
+
+    def write_bridge_persistence(self, wd):
+        """'<id>.bridgepersist' in ``wd``: the table of ``run_water_bridge_persistence`` as CSV."""
+        from .. import bridge_persistence as _bp
+        if self.bridge_persistence is None:
+            raise AttributeError('write_bridge_persistence: run_water_bridge_persistence first')
+        return _bp.write_bridge_persistence(wd, self.id, self.bridge_persistence, self.pc, self.component_types)
 
     def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
         """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""

@@ -33,6 +33,7 @@
 #include "arp_respersist.h"
 #include "arp_filter.h"
 #include "arp_bridge.h"
+#include "arp_bridgepersist.h"
 #include "arp_blob.h"
 
 namespace {
@@ -493,6 +494,10 @@ struct arp_ctx {
     uint32_t bridges_sift_any = 0, bridges_flags = 0;
     DevBuf<long long> bridge_off;         // [L + 1] kept pairs per water run, then their exclusive prefix; [L] = rows
     DevBuf<int> bridge_res;               // [L] residue of every sorted leg's partner
+    // water-bridge persistence over the resident models (arp_models_water_bridge_persistence_launch, arp_bridgepersist.h): made
+    // from the bridge table above — with bridges_sift_any / bridges_flags — and void whenever that is void or remade
+    ResultTable bridgepersist;
+    uint32_t bridgepersist_flags = 0;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -716,7 +721,8 @@ enum : unsigned {
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
 //   persistence table of the resident models (arp_models_persistence_launch) and the water bridges
-//   (arp_water_bridges_launch) are made from the atom-atom bag and go with it;
+//   (arp_water_bridges_launch) are made from the atom-atom bag and go with it, and so does the water-bridge persistence
+//   table (arp_models_water_bridge_persistence_launch), which is made from the water bridges;
 //   the residue-pair table (arp_residue_pairs_launch) and the residue persistence table
 //   (arp_models_residue_persistence_launch) are made from all five and go with any of them (finish_contacts, finish_bag: the
 //   next launch that refills a bag).
@@ -756,6 +762,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->respersist.valid = false;
         c->filtered.valid = false;
         c->bridges.valid = false;
+        c->bridgepersist.valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1932,6 +1939,7 @@ bool finish_contacts(arp_ctx* c) {
     c->respersist.valid = false;
     c->filtered.valid = false;
     c->bridges.valid = false;
+    c->bridgepersist.valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2275,6 +2283,7 @@ void arp_destroy(arp_ctx* c) {
     c->persist.slab.release(); c->respair.slab.release(); c->respersist.slab.release();
     c->filtered.cols.release(); c->filtered.slab.release();
     c->bridges.slab.release(); c->bridge_off.release(); c->bridge_res.release();
+    c->bridgepersist.slab.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4086,7 +4095,7 @@ int arp_models_planes(arp_ctx* c, double* ring_center, double* ring_normal, int3
 // sort them by the whole key, count the runs (the one wait: U rows), size the slab, reduce one wave per row (make_table);
 // and one copy of the slab through the page-locked stage (table_fetch).  A table brings a TableSpec and its two own steps.
 namespace {
-enum { TABLE_MAX_COLS = 12 };
+enum { TABLE_MAX_COLS = 14 };
 struct TableSpec {
     const char* name;                // "<name>_launch" / "<name>_fetch" in messages
     ResultTable arp_ctx::* table;
@@ -4513,6 +4522,7 @@ int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int6
     HIPCHK(c, hipSetDevice(c->device));
     T.valid = false;
     T.count = 0;
+    c->bridgepersist.valid = false;      // (made from the table that is remade here)
     const size_t k = (size_t)c->n_contacts;
     if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
     const auto done = [&](long long rows) {
@@ -4591,6 +4601,104 @@ int arp_water_bridges_fetch(arp_ctx* c, int64_t cap, int32_t* water, int32_t* a,
                             uint16_t* sift_a, uint16_t* sift_b, uint8_t* ctype_a, uint8_t* ctype_b, int64_t* count) {
     void* const dst[WB_COLS] = {water, a, b, dist_a, dist_b, sift_a, sift_b, ctype_a, ctype_b};
     return table_fetch(c, BRIDGE_TABLE, cap, dst, count);
+}
+
+// ---- water-bridge persistence over the resident models (arp_bridgepersist.h): the bridge table folded per pair
+// The records are the rows of the bridge table, not the bags of make_table, and the launch has arguments: the sequence is
+// written out as arp_water_bridges_launch writes its own, from the tables' steps.  Three waits: the bridge launch's two (none
+// when that table is resident) and U.  Only the bridge table is read; nothing but this table and the shared scratch is written.
+namespace {
+enum { WP_A = 0, WP_B, WP_NMODELS, WP_FIRST, WP_LAST, WP_NWATERS, WP_NBRIDGES, WP_DMIN, WP_DMAX, WP_DSUM, WP_BITS_A, WP_BITS_B,
+       WP_CTYPE_A, WP_CTYPE_B, WP_COLS };
+const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &arp_ctx::bridgepersist, WP_COLS,
+                                       {4, 4, 2, 4, 4, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 2 * TABLE_SIFT_BITS, 1, 1},
+                                       true, false, "no atom-contact results of a pass over the resident models (call a launch first)", 0};
+static_assert(WP_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+static_assert(BRIDGEPERSIST_BY_RESIDUE == ARP_WBP_BY_RESIDUE && TABLE_SIFT_BITS == ARP_WBP_BITS, "arp_bridgepersist.h names the header's bits");
+}  // namespace
+
+int arp_models_water_bridge_persistence_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const std::string fn = "arp_models_water_bridge_persistence_launch: ";
+    if (sift_any & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_any has bits beyond the 15 SIFt bits");
+    if (!sift_any) FAIL(c, ARP_E_ARG, fn + "a sift_any of 0 makes no record a leg");
+    if (flags & ~(ARP_WB_SAME_RESIDUE | ARP_WBP_BY_RESIDUE)) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
+    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, fn + "more than 65 535 models (the table counts models in uint16)");
+    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, fn + BRIDGEPERSIST_TABLE.no_pass);
+    const uint32_t wb_flags = flags & ARP_WB_SAME_RESIDUE;
+    ResultTable& T = c->bridgepersist;
+    if (T.valid && c->bridges.valid && c->bridges_sift_any == sift_any && c->bridges_flags == wb_flags && c->bridgepersist_flags == flags) {
+        *count = T.count;
+        return ARP_OK;
+    }
+    const bool by_res = (flags & ARP_WBP_BY_RESIDUE) != 0;
+    const int64_t F = c->models_n, n = c->topo_hdr.n, nres_t = std::max<int64_t>(c->nres / F, 1);
+    const int bits = id_bits(std::max<int64_t>((by_res ? nres_t : n) - 1, 1)), fbits = id_bits(std::max<int64_t>(F - 1, 1));
+    if (2 * bits + fbits > 63) FAIL(c, ARP_E_CAPACITY, fn + "(pair, model) does not fit a 63-bit key");
+    // ---- the bridge table: made here unless the same one is resident; its own refusals and errors pass through
+    T.valid = false;
+    T.count = 0;
+    int64_t B = 0;
+    const int rc = arp_water_bridges_launch(c, sift_any, wb_flags, &B);
+    if (rc != ARP_OK) { *count = B; return rc; }
+    const auto done = [&](long long rows) {
+        T.count = rows; T.valid = true;
+        c->bridgepersist_flags = flags;
+        *count = rows;
+        return ARP_OK;
+    };
+    if (B == 0 || n <= 0) return done(0);
+    HIPCHK(c, hipSetDevice(c->device));
+    // ---- its rows keyed by (pair, model), sorted by every bit: least significant digit first, stable
+    size_t boff[TABLE_MAX_COLS], bbytes;
+    table_layout(BRIDGE_TABLE, (size_t)B, boff, &bbytes);
+    const uint8_t* const bs = c->bridges.slab.p;
+    SortScratch& s = c->table_sort;
+    CHK(reserve_key_sort(c, s, (size_t)B, (size_t)B));
+    BridgepersistArgs A{};
+    A.bits = bits; A.fbits = fbits; A.n = (uint32_t)n; A.nres_t = (uint32_t)nres_t; A.flags = flags;
+    A.b_w = (const int*)(bs + boff[WB_WATER]); A.b_a = (const int*)(bs + boff[WB_A]); A.b_b = (const int*)(bs + boff[WB_B]);
+    A.b_da = (const float*)(bs + boff[WB_DIST_A]); A.b_db = (const float*)(bs + boff[WB_DIST_B]);
+    A.b_sa = (const uint16_t*)(bs + boff[WB_SIFT_A]); A.b_sb = (const uint16_t*)(bs + boff[WB_SIFT_B]);
+    A.b_ca = bs + boff[WB_CTYPE_A]; A.b_cb = bs + boff[WB_CTYPE_B];
+    A.rows = B; A.res_id = c->res_id.p;
+    A.key = s.key[0].p; A.val = s.val[0].p;
+    hipLaunchKernelGGL(k_bridgepersist_rekey, dim3(nblocks(B, 256, 2048)), dim3(256), 0, c->stream, A);
+    int sorted = 0;
+    enqueue_key_sort(c, s, (size_t)B, 2 * bits + fbits, &sorted);
+    // ---- rows: count, scan; the host learns U (the wait of this table)
+    RunArgs R{};
+    R.key = s.key[sorted].p; R.k = B; R.shift = fbits;
+    long long U = 0;
+    CHK(count_runs(c, R, &U, fn + "sort / count"));
+    if (U < 1 || U > B) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    // ---- the table: row starts, one wave per row
+    size_t off[TABLE_MAX_COLS], bytes;
+    table_layout(BRIDGEPERSIST_TABLE, (size_t)U, off, &bytes);
+    HIPCHK(c, T.slab.reserve(bytes));
+    CHK(enqueue_run_starts(c, R, U));
+    uint8_t* const slab = T.slab.p;
+    A.key = s.key[sorted].p; A.val = s.val[sorted].p; A.row_start = R.row_start; A.U = U;
+    A.t_a = (int*)(slab + off[WP_A]); A.t_b = (int*)(slab + off[WP_B]); A.t_nmodels = (uint16_t*)(slab + off[WP_NMODELS]);
+    A.t_first = (int*)(slab + off[WP_FIRST]); A.t_last = (int*)(slab + off[WP_LAST]);
+    A.t_nwaters = (uint32_t*)(slab + off[WP_NWATERS]); A.t_nbridges = (uint32_t*)(slab + off[WP_NBRIDGES]);
+    A.t_dmin = (float*)(slab + off[WP_DMIN]); A.t_dmax = (float*)(slab + off[WP_DMAX]); A.t_dsum = (double*)(slab + off[WP_DSUM]);
+    A.t_bits_a = (uint16_t*)(slab + off[WP_BITS_A]); A.t_bits_b = (uint16_t*)(slab + off[WP_BITS_B]);
+    A.t_ctype_a = slab + off[WP_CTYPE_A]; A.t_ctype_b = slab + off[WP_CTYPE_B];
+    hipLaunchKernelGGL(k_bridgepersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "reduce").c_str()));
+    return done(U);
+}
+
+int arp_models_water_bridge_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
+                                              uint32_t* n_waters, uint32_t* n_bridges, float* dist_min, float* dist_max, double* dist_sum,
+                                              uint16_t* bit_models_a, uint16_t* bit_models_b, uint8_t* ctype_mask_a, uint8_t* ctype_mask_b,
+                                              int64_t* count) {
+    void* const dst[WP_COLS] = {a, b, n_models, first, last, n_waters, n_bridges, dist_min, dist_max, dist_sum,
+                                bit_models_a, bit_models_b, ctype_mask_a, ctype_mask_b};
+    return table_fetch(c, BRIDGEPERSIST_TABLE, cap, dst, count);
 }
 
 // ---- exchange between the shards of a distributed structure (RCCL behind the C ABI) -----------------------------------

@@ -1,6 +1,7 @@
 // arp_runs.h — the runs of a sorted key array, found on the device, and the payload the device-reduced tables sort beside
 // their keys.  Nothing here belongs to one table: arp_persist.h, arp_respair.h and arp_respersist.h all find
-// their rows with these kernels and pack their records with table_payload.
+// their rows with these kernels and pack their records with table_payload; arp_bridge.h and arp_bridgepersist.h find their
+// runs with them too.
 //   k_runs_count   block t: the runs that BEGIN in tile t (a record whose key >> shift differs from its predecessor's)
 //   k_runs_scan    one block: exclusive prefix of those counts over the tiles; their sum U = rows of the table
 //   (the host reads U — the one wait — and sizes the table)

@@ -1,5 +1,5 @@
-"""What the three device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
-(``residue_pairs``) and residue persistence (``residue_persistence``).
+"""What the device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
+(``residue_pairs``), residue persistence (``residue_persistence``) and water-bridge persistence (``bridge_persistence``).
 
 A table is a dict of NumPy columns with one row per pair.  A ``Spec`` names the columns in the order of the C fetch's
 arguments (include/arpeggio_hip.h) with their types, and the width of those that hold several values a row.  Everything here
@@ -31,6 +31,17 @@ RESPERSIST = Spec((('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uin
                    ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
                    ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8)),
                   {'class_models': len(CLASSES), 'bit_models': N_BITS})
+
+
+def _bridgepersist(ka, kb):
+    return Spec(((ka, np.int32), (kb, np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                 ('n_waters', np.uint32), ('n_bridges', np.uint32), ('dist_min', np.float32), ('dist_max', np.float32),
+                 ('dist_sum', np.float64), ('bit_models_a', np.uint16), ('bit_models_b', np.uint16), ('ctype_mask_a', np.uint8),
+                 ('ctype_mask_b', np.uint8)), {'bit_models_a': N_BITS, 'bit_models_b': N_BITS})
+
+
+BRIDGEPERSIST_ATOM = _bridgepersist('a', 'b')
+BRIDGEPERSIST_RESIDUE = _bridgepersist('res_a', 'res_b')
 
 
 def alloc(spec, U, make=np.empty):

@@ -13,7 +13,7 @@ A table is a dict of nine NumPy columns, one row per water ``w`` and unordered p
 
 A ligand-water-protein bridge is a row with one SELECTION_WATER leg and one NON_SELECTION_WATER leg (``ligand_bridges``).
 There is no angle criterion at the water and no second-order (water-water-) bridge.  Persistence of bridges over the models of
-an ensemble is not reduced on the device: fold the per-model tables with ``by_residue`` here.
+an ensemble is ``arpeggio_amd.bridge_persistence`` (reduced on the device: ``Context.models_water_bridge_persistence``).
 
 Everything here is NumPy on the host: no GPU, no native library.  ``join`` makes the table from a fetched atom-atom bag — the
 only route before the device made it, and the fallback where the whole bag is on the host anyway.

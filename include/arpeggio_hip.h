@@ -730,6 +730,60 @@ int arp_fetch_packed_filtered(arp_ctx* ctx, void* host, uint64_t host_bytes, int
 int arp_water_bridges_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t flags, int64_t* count);
 int arp_water_bridges_fetch(arp_ctx* ctx, int64_t cap, int32_t* water, int32_t* a, int32_t* b, float* dist_a, float* dist_b,
                             uint16_t* sift_a, uint16_t* sift_b, uint8_t* ctype_a, uint8_t* ctype_b, int64_t* count);
+/* Water-bridge persistence over the resident models: the bridge table above folded over the F resident models
+ * (arp_set_models) — per pair of TOPOLOGY atoms, or of topology residues with ARP_WBP_BY_RESIDUE, that share a water in at
+ * least one model: in how many models, through how many waters, with which SIFt bits on either leg, and how tight the bridge
+ * is.  It is an extension beside the mirror, and its size does not depend on F.
+ *
+ * Input: the bridge table of arp_water_bridges_launch(ctx, sift_any, flags & ARP_WB_SAME_RESIDUE).  The launch makes that
+ * table itself through that entry point (no work when the same table is resident), and afterwards it is resident and
+ * fetchable exactly as if the caller had launched it.  flags may hold ARP_WB_SAME_RESIDUE and ARP_WBP_BY_RESIDUE only.
+ *
+ * What a bridge row (w, a, b) with resident ids contributes, with n topology atoms and nres_t = nres / F: its model is
+ * f = w / n (a and b lie in the same model).  At atom level the pair is (a - f n, b - f n), already ascending, and leg "a" is
+ * the row's leg a.  At residue level the pair is res_a = min, res_b = max of the two partners' topology residues
+ * res_id[.] - f nres_t (as arp_models_residue_persistence defines them); leg "a" is the leg whose partner lies in res_a, and
+ * the row's own leg a when the residues are equal (possible under ARP_WB_SAME_RESIDUE only).  The row's path is
+ * dist_a + dist_b as ONE float32 addition (it commutes: the leg order cannot show).
+ *
+ * One row per distinct pair, rows ascending by the pair.  Columns, in the order of the fetch's arguments:
+ *   a, b           int32      topology atom ids, a < b — or, at residue level, topology residue ids res_a <= res_b
+ *   n_models       uint16     models with at least one bridge row of the pair
+ *   first, last    int32      lowest / highest 0-based model index among those
+ *   n_waters       uint32     sum over the models of the DISTINCT waters that bridge the pair in that model
+ *   n_bridges      uint32     bridge rows of the pair over all models (atom level: equals n_waters)
+ *   dist_min       float32    smallest path over all rows
+ *   dist_max       float32    largest of the PER-MODEL smallest paths
+ *   dist_sum       float64    the per-model smallest paths widened to float64 and added one by one in ascending model order,
+ *                             starting from 0.0 (defined to the bit; the mean is dist_sum / n_models)
+ *   bit_models_a, bit_models_b  uint16[ARP_WBP_BITS] each  for SIFt bit k (ARP_S_CLASH ... ARP_S_WEAK_POLAR): models in which
+ *                             at least one row's leg a (b) has it — the whole SIFt of the leg, not masked with sift_any
+ *   ctype_mask_a, ctype_mask_b  uint8 each  OR of 1 << ARP_CT_* of leg a (b) over all rows
+ * Every per-model quantity is a presence, a count of distinct waters, a minimum or an OR; the one ordered operation is the sum
+ * over the models, and its order is fixed: the table is a function of the bridge table as a set of rows.
+ *
+ * arp_models_water_bridge_persistence_launch: enqueues the fold on the context's stream and waits for *count = rows, after
+ * the two waits of the bridge launch where that runs.  ARP_E_ARG: no models resident, more than 65 535 models (the uint16
+ * columns), a shard, no atom-atom results of a finished pass, a sift_any of 0 or with bits beyond the low 15, an unknown
+ * flag.  ARP_E_CAPACITY: (pair, model) does not fit a 63-bit key.  Whatever arp_water_bridges_launch returns passes through
+ * unchanged.  No bridge row: *count = 0, ARP_OK, and nothing more is launched.  A second call with the same arguments on the
+ * same results returns the stored count without work; other arguments remake the table.  It is voided wherever the bridge
+ * table is — by every input change and by the next launch that fills the atom-atom bag — and when the bridge table is
+ * remade with other arguments.  It reads the bridge table alone and writes no bag, no sorted slab, no filtered bag and no
+ * other table: every other fetch returns the same before, after and without these calls.
+ *
+ * arp_models_water_bridge_persistence_fetch: the table with one device-to-host copy of one piece (its columns on 256-byte
+ * boundaries, in the order of the arguments, through a page-locked stage); any column pointer may be NULL and is skipped;
+ * bit_models_a / bit_models_b = uint16[cap][ARP_WBP_BITS].  ARP_E_CAPACITY with *count = rows when cap is too small;
+ * ARP_E_ARG without a launch.  A table of 0 rows copies nothing. */
+#define ARP_WBP_BY_RESIDUE (1u << 1)   /* key the rows by topology residue pair instead of topology atom pair */
+#define ARP_WBP_BITS 15
+int arp_models_water_bridge_persistence_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t flags, int64_t* count);
+int arp_models_water_bridge_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models,
+                                              int32_t* first, int32_t* last, uint32_t* n_waters, uint32_t* n_bridges,
+                                              float* dist_min, float* dist_max, double* dist_sum,
+                                              uint16_t* bit_models_a /* [cap][15] */, uint16_t* bit_models_b /* [cap][15] */,
+                                              uint8_t* ctype_mask_a, uint8_t* ctype_mask_b, int64_t* count);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
