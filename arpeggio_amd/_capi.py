@@ -43,6 +43,7 @@ SYMBOLS = (
     'arp_contacts_filter_launch', 'arp_fetch_packed_filtered',
     'arp_water_bridges_launch', 'arp_water_bridges_fetch',
     'arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch',
+    'arp_batch_layout',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -60,8 +61,10 @@ def device_count():
 
 
 def _declare_host_entry_points(L):
-    """argtypes of the host-only entry points (mmCIF reader, JSON writer): the same in both libraries."""
+    """argtypes of the host-only entry points (mmCIF reader, JSON writer, batch layout): the same in both libraries."""
     vp, i64, dbl, i32 = C.c_void_p, C.c_int64, C.c_double, C.c_int
+    L.arp_batch_layout.argtypes = [i64, vp, dbl, vp, vp, C.POINTER(dbl)]
+    L.arp_batch_layout.restype = C.c_int
     L.arp_cif_open.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_uint64]
     L.arp_cif_close.argtypes = [vp]
     L.arp_cif_close.restype = None
@@ -81,7 +84,7 @@ def _declare_host_entry_points(L):
 
 HOST_LIB_PATH = os.path.join(_HERE, 'csrc', 'libarpeggio_host.so')
 HOST_SYMBOLS = ('arp_cif_open', 'arp_cif_close', 'arp_cif_rows', 'arp_cif_cols', 'arp_cif_blocks', 'arp_cif_tag', 'arp_cif_text', 'arp_cif_column',
-                'arp_cif_column_f64', 'arp_cif_column_i64', 'arp_write_contacts_json')
+                'arp_cif_column_f64', 'arp_cif_column_i64', 'arp_write_contacts_json', 'arp_batch_layout')
 _host_lib = None
 
 
@@ -229,6 +232,21 @@ def load():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def batch_layout(boxes, radius):
+    """Where arp_set_batch's grids put every structure at cell edge ``radius`` (arp_batch_layout: host arithmetic, no GPU;
+    served by the host library where the HIP library has not been built).  ``boxes``: float64 [B, 6] = lo xyz, hi xyz.
+    Returns ``dict(cell=int32 [B, 3] offsets, n=int32 [B, 3] cell counts, dims=(NX, NY, NZ), edge=float)``."""
+    bx = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6)
+    B = bx.shape[0]
+    places = np.zeros((max(B, 1), 6), np.int32)
+    dims = np.zeros(3, np.int32)
+    edge = C.c_double(0.0)
+    rc = load_host().arp_batch_layout(B, _p(bx), float(radius), _p(places), _p(dims), C.byref(edge))
+    if rc != ARP_OK:
+        raise ValueError('arp_batch_layout: a box is not finite, has hi < lo or an infinite extent, or the radius is NaN')
+    return dict(cell=places[:B, :3].copy(), n=places[:B, 3:].copy(), dims=tuple(int(v) for v in dims), edge=float(edge.value))
 
 
 def pinned_empty(n, dtype):
@@ -1232,7 +1250,7 @@ class Context:
         s = np.zeros(8, np.int64)
         self._check(self._L.arp_get_stats(self._h, _p(s)), 'arp_get_stats')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
-                    expand_candidates=int(s[5]), expand_hits=int(s[6]))
+                    expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]))
 
     def set_profiling(self, on=True):
         self._check(self._L.arp_set_profiling(self._h, int(on)), 'arp_set_profiling')

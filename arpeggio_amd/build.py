@@ -48,11 +48,11 @@ def build(force=False, verbose=False):
 
 
 HOST_LIB = os.path.join(CSRC, 'libarpeggio_host.so')
-HOST_DEPS = ['arp_host.cpp', 'arp_cif.h', 'arp_cif_api.h', 'arp_json.h']
+HOST_DEPS = ['arp_host.cpp', 'arp_cif.h', 'arp_cif_api.h', 'arp_json.h', 'arp_batchgrid.h']
 
 
 def build_host(force=False):
-    """libarpeggio_host.so: the host-only entry points (mmCIF reader, JSON writer) with g++ — no hipcc, no GPU.  What
+    """libarpeggio_host.so: the host-only entry points (mmCIF reader, JSON writer, batch layout) with g++ — no hipcc, no GPU.  What
     tests/golden/make_golden*.py and the file reader need on a machine where the HIP library cannot be built."""
     deps = [os.path.join(CSRC, f) for f in HOST_DEPS] + [os.path.join(HERE, '..', 'include', 'arpeggio_hip.h')]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps):

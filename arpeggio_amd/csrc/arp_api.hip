@@ -468,7 +468,11 @@ struct arp_ctx {
     std::vector<double> batch_box;       // 6 per structure: lo xyz, hi xyz
     DevBuf<int> sid_atom, sid_ring, sid_amide;
     DevBuf<long long> batch_off_dev;   // the three offset tables of arp_set_batch, one after the other
-    struct BatchGrid { double radius = 0; bool valid = false; DevBuf<BatchPlace> place; GridDesc d{}; } batch_grid[4];
+    // live: a table was uploaded into `place` since the partition was declared — kernels in flight and grids of the running
+    // pass may read it, so a refill takes a fresh buffer and the old one is retired (batch_grid_desc)
+    struct BatchGrid { double radius = 0; bool valid = false, live = false; DevBuf<BatchPlace> place; GridDesc d{}; } batch_grid[4];
+    std::vector<DevBuf<BatchPlace>> batch_retired;   // tables replaced since the last start-over: intact until the next one
+    int64_t batch_restarts = 0;        // how often the tables were started over since arp_set_batch (arp_get_stats, stats[7])
     // ---- one topology, several models (arp_set_topology / arp_set_models): the kept topology blob and its ring / amide atoms,
     // and the number of models the resident structure holds (0: no model mode; see inputs_changed)
     DevBuf<uint8_t> topo_dev;
@@ -676,8 +680,8 @@ void make_grid_desc(GridDesc& d, const double lo[3], const double hi[3], double 
     d.place = nullptr; d.sid_atom = nullptr; d.sid_ring = nullptr; d.sid_amide = nullptr;
 }
 
-// What a caller can replace, for inputs_changed.  IN_BATCH_GRIDS is no input: batch_grid_desc replaced the grid tables of the
-// batch (every slot held another radius).
+// What a caller can replace, for inputs_changed.  IN_BATCH_GRIDS is no input: batch_grid_desc started the grid tables of the
+// batch over (every slot held another radius; arp_get_stats counts it in stats[7]).
 enum : unsigned {
     IN_ATOMS = 1u << 0, IN_RESIDUES = 1u << 1, IN_BONDS = 1u << 2, IN_HYDROGENS = 1u << 3,
     IN_NEIGHBOURS = 1u << 4,        // single-bond neighbours: indices or coordinates
@@ -711,6 +715,13 @@ enum : unsigned {
 //   stales the columns stales the lists at the same moment.
 // (s) the static columns read no selection; a staged shard pass recomposes them all the same (a change of that is a change of
 //   the kernels the staged path launches).  (k) the same structure in new grid tables keeps its contact count.
+// batch grid tables: a start-over can come in the MIDDLE of a pass — at any of its up to three radii: the order of the static
+//   columns (cutoff), the all-atom grid of the expansion, the centre grids (6 A), the last also on the second stream — behind
+//   kernels of that pass which read a table and in front of launches that use a grid built from one.  That is safe because no
+//   table is overwritten: the old ones are retired intact (batch_grid_desc), so what was built earlier in the pass stays
+//   usable to its end, and the marks set here only make the NEXT user rebuild (the columns again inside the same pass, when
+//   the expansion's grid build asks ensure_static: the same layout from a new table, the same records).  A placement is a
+//   pure function of the boxes and the radius (arp_batchgrid.h), so a rebuilt table equals the retired one.
 // contact grid: what atom_grid was built from; the whole-structure reuse also checks its GridKey.  all-atom grid: M_SEL is in
 //   its records.
 // centre grids: a ring / amide upload voids its own grid; (b) both, when a batch partition was in force: they were built in
@@ -767,61 +778,54 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     }
 }
 
-// Several structures in one grid (arp_set_batch): every structure gets the cells its own box needs at this cell edge and a
-// place in a common grid — shelves along x, rows along y, layers along z, one empty cell between neighbours in every
-// direction, the whole as near to a cube as the largest structure allows.  Cached per radius.
+// Several structures in one grid (arp_set_batch): the placement of arp_batchgrid.h (batch_layout), cached per radius in four
+// slots; this function keeps the cache and uploads the table.
+//
+// Nothing is ever copied into a table that something may still read.  A pass asks for up to three radii (cutoff, expansion,
+// 6 A for the centre grids) and enqueues kernels that read a table through GridDesc::place before it asks for the next one,
+// and the context's streams do not wait for a blocking copy; so a slot whose buffer has held a table since the partition was
+// declared (live) is refilled into a FRESH buffer and the old one is retired, intact.  When every slot holds another radius
+// the tables start over: all slots become free and whatever was built in the old tables is marked stale
+// (inputs_changed(IN_BATCH_GRIDS)) — for the NEXT user: a grid or an order built earlier in the running pass keeps reading
+// its retired table to the end of that pass.  The buffers a start-over retired are freed by the next start-over, after both
+// streams have drained, or by arp_set_batch, which has waited for the stream.
+void release_batch_tables(arp_ctx* c) {      // (the caller knows that nothing in flight reads them)
+    for (auto& b : c->batch_retired) b.release();
+    c->batch_retired.clear();
+    for (auto& g : c->batch_grid) g.live = false;      // (their buffers are reused in place)
+}
 int batch_grid_desc(arp_ctx* c, GridDesc& d, double radius) {
     arp_ctx::BatchGrid* slot = nullptr;
     for (auto& g : c->batch_grid)
         if (g.valid && g.radius == radius) { d = g.d; return ARP_OK; }
     for (auto& g : c->batch_grid)
         if (!g.valid) { slot = &g; break; }
-    if (!slot) {   // every slot holds another radius: start over (grids built with the old tables are rebuilt)
+    if (!slot) {   // every slot holds another radius: start over (grids built with the old tables are rebuilt by their next user)
+        if (!c->batch_retired.empty()) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+            for (auto& b : c->batch_retired) b.release();
+            c->batch_retired.clear();
+        }
         for (auto& g : c->batch_grid) g.valid = false;
         slot = &c->batch_grid[0];
+        ++c->batch_restarts;
         inputs_changed(c, IN_BATCH_GRIDS);
     }
     const int64_t B = c->batch_n;
-    double edge = radius * (1.0 + 1e-6);
-    if (!(edge > 0)) edge = 1.0;
     std::vector<BatchPlace> pl((size_t)B);
-    int NX = 1, NY = 1, NZ = 1;
-    for (;;) {
-        double vol = 0;
-        int mx = 1, my = 1, mz = 1;
-        bool too_big = false;
-        for (int64_t s_ = 0; s_ < B; ++s_) {
-            const double* lo = &c->batch_box[(size_t)s_ * 6];
-            const double* hi = lo + 3;
-            const double nx = std::floor((hi[0] - lo[0]) / edge) + 1, ny = std::floor((hi[1] - lo[1]) / edge) + 1, nz = std::floor((hi[2] - lo[2]) / edge) + 1;
-            if (!(nx < 4096 && ny < 4096 && nz < 4096)) { too_big = true; break; }
-            pl[(size_t)s_] = BatchPlace{lo[0], lo[1], lo[2], 0, 0, 0, (int)nx, (int)ny, (int)nz};
-            vol += (nx + 1) * (ny + 1) * (nz + 1);
-            mx = std::max(mx, (int)nx); my = std::max(my, (int)ny); mz = std::max(mz, (int)nz);
-        }
-        if (!too_big) {
-            const int side = (int)std::ceil(std::cbrt(vol));
-            const int LX = std::max(side, mx), LY = std::max(side, my);
-            int x = 0, y = 0, z = 0, row_h = 0, layer_h = 0;
-            NX = NY = NZ = 1;
-            for (int64_t s_ = 0; s_ < B; ++s_) {
-                BatchPlace& b = pl[(size_t)s_];
-                if (x > 0 && x + b.nx > LX) { x = 0; y += row_h + 1; row_h = 0; }
-                if (y > 0 && y + b.ny > LY) { x = 0; y = 0; z += layer_h + 1; layer_h = 0; row_h = 0; }
-                b.cx = x; b.cy = y; b.cz = z;
-                NX = std::max(NX, x + b.nx); NY = std::max(NY, y + b.ny); NZ = std::max(NZ, z + b.nz);
-                x += b.nx + 1;
-                row_h = std::max(row_h, b.ny);
-                layer_h = std::max(layer_h, b.nz);
-            }
-            if ((double)NX * NY * NZ <= (double)(1 << 26)) break;
-        }
-        edge *= 1.26;
+    int dims[3] = {1, 1, 1};
+    const double edge = batch_layout(B, c->batch_box.data(), radius, pl.data(), dims);
+    if (slot->live) {
+        c->batch_retired.push_back(slot->place);
+        slot->place = DevBuf<BatchPlace>{};
+        slot->live = false;
     }
     HIPCHK(c, slot->place.reserve((size_t)B));
-    HIPCHK(c, hipMemcpy(slot->place.p, pl.data(), (size_t)B * sizeof(BatchPlace), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(slot->place.p, pl.data(), (size_t)B * sizeof(BatchPlace), hipMemcpyHostToDevice));   // (a buffer nothing reads)
+    slot->live = true;
     GridDesc g{};
-    g.nx = NX; g.ny = NY; g.nz = NZ; g.ncell = NX * NY * NZ;
+    g.nx = dims[0]; g.ny = dims[1]; g.nz = dims[2]; g.ncell = dims[0] * dims[1] * dims[2];
     g.ox = c->lo[0]; g.oy = c->lo[1]; g.oz = c->lo[2];   // (not used for binning: every structure has its own origin)
     g.inv = 1.0 / edge;
     g.place = slot->place.p; g.sid_atom = c->sid_atom.p; g.sid_ring = c->sid_ring.p; g.sid_amide = c->sid_amide.p;
@@ -1057,10 +1061,12 @@ auto launch_scan_scatter(int steps, dim3 grid, hipStream_t st, Args... args) {
 // sift records directly).
 int build_atom_grid(arp_ctx* c, Grid& G, DevBuf<float4>& sx, DevBuf<int4>& sa, DevBuf<int4>* srec, double radius,
                     uint32_t req, uint32_t forb, const uint8_t* active, u64* total_out = nullptr, uint8_t* plus_init = nullptr,
-                    hipStream_t st = nullptr, ResMarks rm = ResMarks{nullptr, nullptr, 0}, GroupMasks gm = GroupMasks{}) {
+                    hipStream_t st = nullptr, ResMarks rm = ResMarks{nullptr, nullptr, 0}, GroupMasks gm = GroupMasks{}, bool world = false) {
     if (!st) st = c->stream;
     const int n = (int)c->n;
-    CHK(grid_desc_for(c, G.d, c->lo, c->hi, radius));
+    // world: one grid over the box of ALL resident atoms in their own coordinates, whatever the partition (build_world_grid)
+    if (world) make_grid_desc(G.d, c->lo, c->hi, radius);
+    else CHK(grid_desc_for(c, G.d, c->lo, c->hi, radius));
     G.radius = radius;
     G.n_points = n;
     const int ncell = G.d.ncell;
@@ -1198,6 +1204,17 @@ int build_contact_grid_compact(arp_ctx* c, double radius, uint32_t req, uint32_t
 int build_all_grid(arp_ctx* c, double radius, uint8_t* plus_init = nullptr, hipStream_t st = nullptr) {
     CHK(build_atom_grid(c, c->all_grid, c->a_xyzm, c->a_aux, nullptr, radius, 0, 0, nullptr, nullptr, plus_init, st));
     c->all_grid_current = true;
+    return ARP_OK;
+}
+
+// The all-atom grid of the queries with caller-given centres (arp_search, arp_ring_residues): a centre belongs to no structure
+// of a batch and to no model, so these answer over all resident atoms in world coordinates — with a partition in force the
+// grid is built over the box of everything resident instead of the batch layout (whose cells a centre cannot be located in),
+// and the pass, which needs the layout, builds its own again.
+int build_world_grid(arp_ctx* c, double radius) {
+    CHK(build_atom_grid(c, c->all_grid, c->a_xyzm, c->a_aux, nullptr, radius, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                        ResMarks{nullptr, nullptr, 0}, GroupMasks{}, /*world=*/true));
+    c->all_grid_current = false;
     return ARP_OK;
 }
 
@@ -2289,6 +2306,9 @@ void arp_destroy(arp_ctx* c) {
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
     c->rec_home.release(); c->rec_face[0].release(); c->rec_face[1].release(); c->sh_scan.release(); c->sh_src.release();
     c->origin.release(); c->ring_origin.release(); c->am_origin.release(); c->sh_sel.release();
+    release_batch_tables(c);
+    for (auto& g : c->batch_grid) g.place.release();
+    c->sid_atom.release(); c->sid_ring.release(); c->sid_amide.release(); c->batch_off_dev.release();
     for (auto& l : c->plist) l.release();
     c->plist_count.release();   // (views into the blob were released above: no-ops)
     c->ring_home.release(); c->am_home.release(); c->ring_gid.release(); c->am_gid.release();
@@ -3732,6 +3752,7 @@ int arp_run_stage(arp_ctx* c, int stage, double cutoff, double vdw_comp, int inc
 int arp_get_stats(arp_ctx* c, int64_t stats[8]) {
     if (!c || !stats) return ARP_E_ARG;
     for (int k = 0; k < 8; ++k) stats[k] = c->stats[k];
+    stats[7] = c->batch_restarts;
     return ARP_OK;
 }
 
@@ -3806,7 +3827,9 @@ int arp_ring_residues(arp_ctx* c, int64_t nring, const double* center, int32_t* 
         return ARP_OK;
     }
     // the all-atom grid (hydrogens included, I:1455); its cells (>= 6 A) cover the 3 A query with the 27-cell stencil
-    if (!(c->all_grid_current && c->all_grid.valid && c->all_grid.radius == 6.0)) CHK(build_all_grid(c, 6.0));
+    // (with a batch or models resident: over all of them, in world coordinates — build_world_grid)
+    if (c->batch_n > 0) CHK(build_world_grid(c, 6.0));
+    else if (!(c->all_grid_current && c->all_grid.valid && c->all_grid.radius == 6.0)) CHK(build_all_grid(c, 6.0));
     DevBuf<double> d_c, d_d;
     DevBuf<int> d_r;
     int rc = upload(c, d_c, center, (size_t)nring * 3);
@@ -3832,7 +3855,8 @@ int arp_search(arp_ctx* c, double radius, int64_t ncenters, const double* center
     if (ncenters > 0x7FFFFFF0LL) FAIL(c, ARP_E_ARG, "arp_search: too many centres");
     if (!all_finite(centers, 3 * ncenters)) FAIL(c, ARP_E_ARG, "arp_search: non-finite centre");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!(c->all_grid_current && c->all_grid.valid && c->all_grid.radius >= radius)) CHK(build_all_grid(c, std::max(radius, 6.0)));
+    if (c->batch_n > 0) CHK(build_world_grid(c, std::max(radius, 6.0)));      // (all resident atoms, world coordinates)
+    else if (!(c->all_grid_current && c->all_grid.valid && c->all_grid.radius >= radius)) CHK(build_all_grid(c, std::max(radius, 6.0)));
     DevBuf<double> d_c;
     DevBuf<int2> d_out;
     DevBuf<u64> d_n;
@@ -3878,6 +3902,10 @@ int arp_host_free(void* p) {
     return hipHostFree(p) == hipSuccess ? ARP_OK : ARP_E_HIP;
 }
 
+int arp_batch_layout(int64_t nstruct, const double* boxes, double radius, int32_t* places_out, int32_t dims_out[3], double* edge_out) {
+    return batch_layout_c(nstruct, boxes, radius, places_out, dims_out, edge_out) == 0 ? ARP_OK : ARP_E_ARG;
+}
+
 int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const int64_t* ring_off, const int64_t* amide_off,
                   const double* boxes) {
     if (!c) return ARP_E_ARG;
@@ -3899,11 +3927,14 @@ int arp_set_batch(arp_ctx* c, int64_t nstruct, const int64_t* atom_off, const in
     for (int64_t k = 0; k < nstruct; ++k)
         for (int a = 0; a < 3; ++a) {
             const double lo = boxes[6 * k + a], hi = boxes[6 * k + 3 + a];
-            if (!std::isfinite(lo) || !std::isfinite(hi) || hi < lo) FAIL(c, ARP_E_ARG, "arp_set_batch: a box is not finite or has hi < lo");
+            if (!std::isfinite(lo) || !std::isfinite(hi) || hi < lo || !std::isfinite(hi - lo))
+                FAIL(c, ARP_E_ARG, "arp_set_batch: a box is not finite or has hi < lo");
         }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     inputs_changed(c, IN_BATCH);
+    release_batch_tables(c);      // (the stream has drained, and with it whatever the second stream did for a pass)
+    c->batch_restarts = 0;
     c->batch_atom_off.assign(atom_off, atom_off + nstruct + 1);
     c->batch_ring_off.assign(ring_off, ring_off + nstruct + 1);
     c->batch_amide_off.assign(amide_off, amide_off + nstruct + 1);

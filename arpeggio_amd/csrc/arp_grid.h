@@ -12,16 +12,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "arp_batchgrid.h"
 #include "arp_numerics.h"
 
 // Several structures in one grid (arp_set_batch): every structure keeps its own coordinates and its own box; its cells sit
 // at an integer offset inside a common grid, with at least one empty cell between two structures, so that no stencil ever
 // reaches from one structure into another.  place[s] = origin of structure s's box, its cell offset and its cell counts;
-// sid_* = structure of every atom (by local id), ring and amide.
-struct BatchPlace {
-    double ox, oy, oz;
-    int cx, cy, cz, nx, ny, nz;
-};
+// sid_* = structure of every atom (by local id), ring and amide.  (BatchPlace and the placement itself: arp_batchgrid.h)
 struct GridDesc {
     double ox, oy, oz, inv;
     int nx, ny, nz, ncell;

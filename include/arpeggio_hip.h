@@ -221,7 +221,10 @@ int arp_search_all(arp_ctx* ctx, double radius, const uint8_t* active,
 /* NeighborSearch(atoms).search(center, radius) (I:960, 1463) for ncenters centres at once: every (centre, atom) with
  * float64 d^2 <= radius^2 over ALL atoms of the structure (hydrogens included, as the tree of I:1394 / 1455 holds them).
  * centers = double[3 * ncenters].  Output sorted by (centre, atom index).  ARP_E_CAPACITY with the required count in
- * *count when cap is too small. */
+ * *count when cap is too small.
+ * With a batch (arp_set_batch) or models (arp_set_models) resident a centre belongs to no structure: the answer is over
+ * ALL resident atoms in their own (world) coordinates, atom index = index in the concatenation — also where the
+ * coordinates of two structures overlap. */
 int arp_search(arp_ctx* ctx, double radius, int64_t ncenters, const double* centers, int64_t cap, int32_t* out_center,
                int32_t* out_atom, int64_t* count);
 
@@ -412,7 +415,10 @@ int arp_run_stage(arp_ctx* ctx, int stage, double cutoff, double vdw_comp, int i
 /* stats[0]=candidate pairs tested by the last atom-contact search,
  * stats[1]=pairs with d<=cutoff, stats[2]=pairs passing the residue filters
  * (= emitted contacts), stats[3]=atoms binned, stats[4]=grid cells,
- * stats[5]/[6]=candidates / hits of the last selection-expansion search. */
+ * stats[5]/[6]=candidates / hits of the last selection-expansion search,
+ * stats[7]=how often the grid tables of the resident batch were started over since arp_set_batch: the placement of a
+ * batch is cached for four radii (cutoff, expansion radius, 6 A of the ring / amide grids, arp_search_all's); a fifth
+ * one starts the cache over and the next pass rebuilds what it had built in the old tables (results do not change). */
 int arp_get_stats(arp_ctx* ctx, int64_t stats[8]);
 /* When enabled, every kernel of arp_atom_contacts_launch is bracketed by
  * hipEvents on the context stream.  ms[k], launches[k] accumulate per kernel
@@ -435,7 +441,9 @@ int arp_ring_geometry(arp_ctx* ctx, int64_t nring, const int32_t* ring_off, cons
 int arp_amide_geometry(arp_ctx* ctx, int64_t namide, const int32_t* amide_atoms, float* out_center, float* out_normal);
 /* _assign_aromatic_rings_to_residues (I:1453-1492): residue of the atom nearest to each ring centre among ALL atoms
  * within 3.0 A (float64, inclusive), -1 when there is none; out_shortest (may be NULL) = that distance
- * ('residue_shortest_distance', I:1485), -1 when there is none.  Needs arp_set_atoms (and the residue ids given there). */
+ * ('residue_shortest_distance', I:1485), -1 when there is none.  Needs arp_set_atoms (and the residue ids given there).
+ * With a batch or models resident: over all resident atoms in world coordinates, like arp_search (residue ids of the
+ * concatenation; among atoms at the same distance the lowest resident index). */
 int arp_ring_residues(arp_ctx* ctx, int64_t nring, const double* center, int32_t* out_ring_res, double* out_shortest);
 /* Page-locked (pinned) host memory.  Result buffers allocated here make the *_fetch calls DMA transfers at PCIe speed
  * (a 1.25 M-contact list: 0.5 ms instead of 2.5 ms into pageable memory); any host pointer is accepted by every call. */
@@ -513,9 +521,19 @@ int arp_shard_reduce_residue_sets(arp_ctx* ctx);
  * ever pairs items of different structures, while every distance is computed from the same coordinates as in a
  * single-structure run: each structure's five bags are bit-identical to its own run.  Selections: one mask over the
  * concatenated atoms (arp_set_selection).  Results carry the concatenated ids; a record belongs to the structure of its
- * first id.  nstruct = 0 returns to one structure.  Not available on a shard (arp_set_ownership). */
+ * first id.  nstruct = 0 returns to one structure.  Not available on a shard (arp_set_ownership).
+ * Items outside their structure's declared box count as its border cells (results do not change; a box much smaller
+ * than its contents only makes those cells crowded).  A box needs finite corners, hi >= lo and a finite extent. */
 int arp_set_batch(arp_ctx* ctx, int64_t nstruct, const int64_t* atom_off, const int64_t* ring_off, const int64_t* amide_off,
                   const double* boxes);
+/* The placement arp_set_batch's grids use at cell edge `radius`, as a pure host function (no context, no GPU; also in
+ * libarpeggio_host.so): structure s occupies cells [cx, cx + nx) x [cy, cy + ny) x [cz, cz + nz) of a common grid of
+ * dims_out = NX, NY, NZ cells, n = floor((hi - lo) / edge) + 1 per axis; places_out = int32[6 * nstruct] = cx, cy, cz,
+ * nx, ny, nz per structure.  *edge_out = the cell edge: radius (1 + 1e-6), grown by 1.26 until every n < 4096 and
+ * NX NY NZ <= 2^26.  Any two structures are at least one empty cell apart in some direction.  ARP_E_ARG for boxes
+ * arp_set_batch would refuse or a NaN radius. */
+int arp_batch_layout(int64_t nstruct, const double* boxes, double radius, int32_t* places_out, int32_t dims_out[3],
+                     double* edge_out);
 /* Every model of a multi-model structure (an NMR ensemble, the frames of a simulation) in ONE pass.  The reference keeps
  * the first model only (P:67-69: del st[1:]); here the topology is kept on the device once and any number of coordinate
  * sets for it become resident as a batch (arp_set_batch) with one structure per model.

@@ -132,7 +132,8 @@ def test_product_fails_loudly_without_gpu():
 
 def test_host_only_library_has_the_reader_and_the_writer_and_nothing_that_computes(tmp_path):
     """libarpeggio_host.so (g++, arpeggio_amd.build.build_host): the mmCIF reader and the JSON writer of include/arpeggio_hip.h —
-    what the fixture generators need on a machine without hipcc — and no compute entry point."""
+    what the fixture generators need on a machine without hipcc —, the placement arithmetic of a batch (arp_batch_layout, no
+    device code) and no compute entry point."""
     import ctypes as C
     import subprocess
     from arpeggio_amd import _capi, build
