@@ -44,12 +44,15 @@ SYMBOLS = (
     'arp_water_bridges_launch', 'arp_water_bridges_fetch',
     'arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch',
     'arp_batch_layout',
+    'arp_models_similarity_launch', 'arp_models_similarity_fetch', 'arp_models_similarity_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
 PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
+SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
+CTYPE_ALL = 0x7F                 # ARP_FILTER_CTYPE_ALL
 PERSIST_COLUMNS, RESPAIR_COLUMNS, RESPERSIST_COLUMNS = tables.PERSIST.columns, tables.RESPAIR.columns, tables.RESPERSIST.columns
 
 _lib = None
@@ -205,6 +208,9 @@ def load():
     L.arp_water_bridges_fetch.argtypes = [vp, i64] + [vp] * 9 + [C.POINTER(i64)]
     L.arp_models_water_bridge_persistence_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(i64)]
     L.arp_models_water_bridge_persistence_fetch.argtypes = [vp, i64] + [vp] * 14 + [C.POINTER(i64)]
+    L.arp_models_similarity_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64), C.POINTER(i64)]
+    L.arp_models_similarity_fetch.argtypes = [vp, i64, vp, C.POINTER(i64)]
+    L.arp_models_similarity_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -784,6 +790,23 @@ class Context:
                     'arp_models_water_bridge_persistence_fetch')
         return t
 
+    def models_similarity(self, planes, ctype_mask=CTYPE_ALL, by_residue=False):
+        """The model-by-model matrix of shared interaction features of the last pass, made on the device
+        (arp_models_similarity_*): ``inter`` uint32 [F, F], ``inter[f, g]`` = features (row, plane) present in model f and in
+        model g — rows the topology atom pairs of ``models_persistence`` or, with ``by_residue``, the topology residue pairs of
+        ``models_residue_persistence`` (a complete pass); ``planes`` as ``similarity.planes`` builds it; an atom-atom record
+        takes part when bit ``ctype`` of ``ctype_mask`` is set (see ``arpeggio_amd.similarity``).  Only the matrix is copied to
+        the host; the bags of the pass and every table stay fetchable as before.  The row count and what the launch did are in
+        ``stats()`` (``sim_rows``, ``sim_words``, ``sim_slices``, ``sim_launches``)."""
+        F, U = C.c_int64(0), C.c_int64(0)
+        flags = SIM_BY_RESIDUE if by_residue else 0
+        self._check(self._L.arp_models_similarity_launch(self._h, int(planes), int(ctype_mask), flags, C.byref(F), C.byref(U)),
+                    'arp_models_similarity_launch')
+        n = int(F.value)
+        inter = np.empty((n, n), np.uint32)
+        self._check(self._L.arp_models_similarity_fetch(self._h, n, _p(inter), C.byref(F)), 'arp_models_similarity_fetch')
+        return inter
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
@@ -1249,8 +1272,11 @@ class Context:
     def stats(self):
         s = np.zeros(8, np.int64)
         self._check(self._L.arp_get_stats(self._h, _p(s)), 'arp_get_stats')
+        m = np.zeros(4, np.int64)
+        self._check(self._L.arp_models_similarity_info(self._h, _p(m)), 'arp_models_similarity_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
-                    expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]))
+                    expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
+                    sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]))
 
     def set_profiling(self, on=True):
         self._check(self._L.arp_set_profiling(self._h, int(on)), 'arp_set_profiling')

@@ -637,6 +637,8 @@ class EnsembleComplex:
         self.bridge_persistence = None   # the table of run_water_bridge_persistence, the models it covers and what it was made with
         self.bridge_persistence_models = 0
         self._bridge_persistence_key = None
+        self.similarity = None           # the matrix of run_similarity (uint32 [F, F]) and the rows it was made over
+        self.similarity_rows = 0
 
     @property
     def n_models(self):
@@ -836,6 +838,44 @@ class EnsembleComplex:
         if self.bridge_persistence is None:
             raise AttributeError('write_bridge_persistence: run_water_bridge_persistence first')
         return _bp.write_bridge_persistence(wd, self.id, self.bridge_persistence, self.pc, self.component_types)
+
+    def run_similarity(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, contacts=None, classes=(),
+                       interacting_entities=None, level='atom'):
+        """Extension beside the mirror: interaction-fingerprint similarity between the models — which models share their
+        contacts: the selection handling and the pass of ``run_persistence``, then the records of all models turned ON THE
+        DEVICE into one bit per (model, row, plane) and multiplied there to ``inter`` uint32 [F, F], the features two models
+        share (``arpeggio_amd.similarity`` describes it and derives Tanimoto, distance and medoid) — and only that matrix
+        fetched, into ``self.similarity`` (also returned).  A row is a topology atom pair (``level='atom'``) or a topology
+        residue pair over all five bags (``level='residue'``).  ``contacts`` / ``classes`` name the planes
+        (``similarity.planes``: ``None`` = every contact but bare proximity; the ring / amide classes exist at residue level
+        only); ``interacting_entities`` names the kinds of entities whose atom-atom records take part
+        (``contact_filter.masks``; ``None`` = all).  No bag is copied to the host: ``model(k)`` has no results after this
+        call.  There is no ``accumulate``: the block of the matrix between two chunks of a trajectory needs the records of
+        both chunks resident, so a streamed trajectory is out of scope — make the models of interest resident together (up
+        to ``similarity.MAX_MODELS``)."""
+        from .. import contact_filter, similarity as _sim
+        if level not in ('atom', 'residue'):
+            raise ValueError(f"run_similarity: level must be 'atom' or 'residue', not {level!r}")
+        mask = _sim.planes(contacts, classes)
+        if level == 'atom' and mask & ~_sim.ATOM_PLANES:
+            raise ValueError("run_similarity: the ring / amide classes are planes of level='residue' only")
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        self.similarity = self._ctx.models_similarity(mask, ctype_mask, by_residue=level == 'residue')
+        self._results = None
+        self.stats = self._ctx.stats()
+        self.similarity_rows = self.stats['sim_rows']
+        return self.similarity
+
+    def write_similarity(self, wd):
+        """'<id>.modelsim' in ``wd``: the matrix of ``run_similarity`` as CSV, one line per pair of models (0-based)."""
+        from .. import similarity as _sim
+        if self.similarity is None:
+            raise AttributeError('write_similarity: run_similarity first')
+        return _sim.write_similarity(wd, self.id, self.similarity)
 
     def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
         """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""

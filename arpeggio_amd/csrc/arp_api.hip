@@ -34,6 +34,7 @@
 #include "arp_filter.h"
 #include "arp_bridge.h"
 #include "arp_bridgepersist.h"
+#include "arp_similarity.h"
 #include "arp_blob.h"
 
 namespace {
@@ -261,6 +262,16 @@ struct FilteredBag {
     int64_t count = 0;
     uint32_t sift_any = 0, ctype_mask = 0;
     bool csr = false;                   // the slab's first column is N + 1 row offsets
+    bool valid = false;
+};
+
+// the model-by-model matrix of shared features (arp_models_similarity_launch): the bit matrix it is multiplied from, the
+// matrix, and what it was made for; rows / words / slices / launches answer arp_models_similarity_info
+struct SimilarityResult {
+    DevBuf<unsigned long long> bits;
+    DevBuf<uint32_t> inter;
+    int64_t F = 0, rows = 0, words = 0, slices = 0, launches = 0;
+    uint32_t planes = 0, ctype_mask = 0, flags = 0;
     bool valid = false;
 };
 
@@ -502,6 +513,9 @@ struct arp_ctx {
     // from the bridge table above — with bridges_sift_any / bridges_flags — and void whenever that is void or remade
     ResultTable bridgepersist;
     uint32_t bridgepersist_flags = 0;
+    // fingerprint similarity between the resident models (arp_models_similarity_launch, arp_similarity.h): made from the records
+    // of the persistence table (atom level) or of the residue persistence table (residue level), and void wherever that is
+    SimilarityResult similarity;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -733,7 +747,8 @@ enum : unsigned {
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
 //   persistence table of the resident models (arp_models_persistence_launch) and the water bridges
 //   (arp_water_bridges_launch) are made from the atom-atom bag and go with it, and so does the water-bridge persistence
-//   table (arp_models_water_bridge_persistence_launch), which is made from the water bridges;
+//   table (arp_models_water_bridge_persistence_launch), which is made from the water bridges; the similarity matrix of the
+//   resident models (arp_models_similarity_launch) goes with the bag(s) its level reads, as the persistence table of that level;
 //   the residue-pair table (arp_residue_pairs_launch) and the residue persistence table
 //   (arp_models_residue_persistence_launch) are made from all five and go with any of them (finish_contacts, finish_bag: the
 //   next launch that refills a bag).
@@ -774,6 +789,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->filtered.valid = false;
         c->bridges.valid = false;
         c->bridgepersist.valid = false;
+        c->similarity.valid = false;
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1957,6 +1973,7 @@ bool finish_contacts(arp_ctx* c) {
     c->filtered.valid = false;
     c->bridges.valid = false;
     c->bridgepersist.valid = false;
+    c->similarity.valid = false;
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -2091,6 +2108,7 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     ++b.version;
     c->respair.valid = false;
     c->respersist.valid = false;
+    if (c->similarity.flags & SIM_BY_RESIDUE) c->similarity.valid = false;      // (at atom level it reads the atom-atom bag alone)
     c->filtered.valid = false;      // (the bags packed behind the kept records are sized when it is made)
     return false;
 }
@@ -2301,6 +2319,7 @@ void arp_destroy(arp_ctx* c) {
     c->filtered.cols.release(); c->filtered.slab.release();
     c->bridges.slab.release(); c->bridge_off.release(); c->bridge_res.release();
     c->bridgepersist.slab.release();
+    c->similarity.bits.release(); c->similarity.inter.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4730,6 +4749,128 @@ int arp_models_water_bridge_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* 
     void* const dst[WP_COLS] = {a, b, n_models, first, last, n_waters, n_bridges, dist_min, dist_max, dist_sum,
                                 bit_models_a, bit_models_b, ctype_mask_a, ctype_mask_b};
     return table_fetch(c, BRIDGEPERSIST_TABLE, cap, dst, count);
+}
+
+// ---- fingerprint similarity between the resident models (arp_similarity.h): inter = B B^T of a bit matrix
+// The result is F x F, not U rows of columns, and the launch has arguments: the sequence is written out from the tables'
+// steps, as arp_water_bridges_launch writes its own.  One wait (U).  The rows are those of the persistence table (atom level:
+// k_persist_rekey) or of the residue persistence table (residue level: enqueue_residue_rekey), found by the same sort and run
+// kernels.  Only the bags are read; nothing but the matrix, its bit matrix and the shared scratch is written.
+static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESIDUE && SIM_PLANES == TABLE_SIFT_BITS + RESPERSIST_CLASSES,
+              "arp_similarity.h names the header's planes");
+
+int arp_models_similarity_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t* n_models, int64_t* n_rows) {
+    if (!c || !n_models || !n_rows) return ARP_E_ARG;
+    const std::string fn = "arp_models_similarity_launch: ";
+    const bool by_res = (flags & ARP_SIM_BY_RESIDUE) != 0;
+    if (flags & ~ARP_SIM_BY_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    if (planes & ~((1u << ARP_SIM_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 20 planes");
+    if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
+    if (!by_res && (planes >> (TABLE_SIFT_BITS + 1))) FAIL(c, ARP_E_ARG, fn + "planes 16 ... 19 (the ring / amide classes) exist at residue level only");
+    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
+    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no atom-atom record");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
+    const int64_t F = c->models_n;
+    *n_models = F;
+    if (F > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "more than 4096 models (the matrix and its page-locked stage would pass 64 MiB)");
+    if (by_res ? !five_bags_complete(c) : (c->pass_pending || !c->contacts_valid))
+        FAIL(c, ARP_E_ARG, fn + (by_res ? RESPERSIST_TABLE.no_pass : PERSIST_TABLE.no_pass));
+    SimilarityResult& S = c->similarity;
+    if (S.valid && S.F == F && S.planes == planes && S.ctype_mask == ctype_mask && S.flags == flags) { *n_rows = S.rows; return ARP_OK; }
+    S.valid = false;
+    const FiveBags B = five_bags(c, by_res);
+    const size_t k = B.k;
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
+    const int64_t n = c->topo_hdr.n, nres_t = std::max<int64_t>(c->nres / F, 1);
+    const int bits = id_bits(std::max<int64_t>((by_res ? nres_t : n) - 1, 1)), fbits = id_bits(std::max<int64_t>(F - 1, 1));
+    if (2 * bits + fbits > 63) FAIL(c, ARP_E_CAPACITY, fn + "(pair, model) does not fit a 63-bit key");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, S.inter.reserve((size_t)(F * F)));
+    const auto done = [&](long long rows, long long words, long long slices) {
+        S.F = F; S.rows = rows; S.words = words; S.slices = slices;
+        S.planes = planes; S.ctype_mask = ctype_mask; S.flags = flags;
+        S.valid = true;
+        ++S.launches;
+        *n_rows = rows;
+        return ARP_OK;
+    };
+    long long U = 0;
+    SortScratch& s = c->table_sort;
+    RunArgs R{};
+    int sorted = 0;
+    if (k > 0) {
+        // ---- the records keyed by (pair, model), sorted by every bit: least significant digit first
+        CHK(reserve_key_sort(c, s, k, B.cap));
+        int keybits = 2 * bits + fbits;
+        if (by_res) {
+            keybits = respersist_key_bits(nres_t, F, bits, fbits, B.planes > 0);
+            enqueue_residue_rekey(c, B, nres_t, bits, fbits, s.key[0].p, s.val[0].p);
+        } else {
+            PersistArgs P{};
+            P.ci = c->out_i.p; P.cj = c->out_j.p; P.d_in = c->out_d.p; P.s_in = c->out_s.p; P.ct_in = c->out_ct.p;
+            P.k = (long long)k; P.n = (uint32_t)n; P.bbits = bits; P.fbits = fbits;
+            P.key = s.key[0].p; P.val = s.val[0].p;
+            hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, P);
+        }
+        enqueue_key_sort(c, s, k, keybits, &sorted);
+        // ---- rows: count, scan; the host learns U (the one wait)
+        R.key = s.key[sorted].p; R.k = (long long)k; R.shift = fbits;
+        CHK(count_runs(c, R, &U, fn + "sort / count"));
+        if (U < (by_res ? 0 : 1) || U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    }
+    if (U == 0) {      // no record with a row: no feature in any model
+        HIPCHK(c, hipMemsetAsync(S.inter.p, 0, (size_t)(F * F) * sizeof(uint32_t), c->stream));
+        return done(0, 0, 0);
+    }
+    // ---- the bit matrix: popcount(planes) planes of ceil(U / 64) words a model
+    const long long NP = __builtin_popcount(planes), wpp = (U + 63) / 64, W = NP * wpp;
+    if (NP * U >= (1ll << 32)) FAIL(c, ARP_E_CAPACITY, fn + "2^32 features or more (a count would not fit uint32)");
+    if (F * W >= (1ll << 29)) FAIL(c, ARP_E_CAPACITY, fn + "a bit matrix of 4 GiB or more");
+    HIPCHK(c, S.bits.reserve((size_t)(F * W)));
+    HIPCHK(c, hipMemsetAsync(S.bits.p, 0, (size_t)(F * W) * sizeof(unsigned long long), c->stream));
+    CHK(enqueue_run_starts(c, R, U));
+    SimArgs A{};
+    A.key = R.key; A.val = s.val[sorted].p; A.row_start = R.row_start; A.U = U;
+    A.fbits = fbits; A.planes = planes; A.ctype_mask = ctype_mask; A.F = (uint32_t)F;
+    A.bits = S.bits.p; A.wpp = wpp; A.W = W;
+    hipLaunchKernelGGL(k_sim_bits, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+    // ---- inter = B B^T: the tile pairs of the upper triangle times as many word slices as fill the device (F = 8 is one
+    // tile: the words supply the parallelism), a slice no shorter than one staged panel
+    const long long tiles = (F + SIM_TILE - 1) / SIM_TILE, pairs = tiles * (tiles + 1) / 2, chunks = (W + SIM_KC - 1) / SIM_KC;
+    const long long want = std::max<long long>(1, std::min<long long>(chunks, (2ll * c->num_cu + pairs - 1) / pairs));
+    const long long per = (chunks + want - 1) / want * SIM_KC, slices = (W + per - 1) / per;
+    A.per = per; A.slices = (int)slices; A.tiles = (int)tiles; A.inter = S.inter.p;
+    if (slices > 1) HIPCHK(c, hipMemsetAsync(S.inter.p, 0, (size_t)(F * F) * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_sim_gram, dim3((unsigned)pairs, (unsigned)slices), dim3(256), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "bits / gram").c_str()));
+    return done(U, W, slices);
+}
+
+int arp_models_similarity_fetch(arp_ctx* c, int64_t cap_models, uint32_t* inter, int64_t* n_models) {
+    if (!c || !n_models) return ARP_E_ARG;
+    const SimilarityResult& S = c->similarity;
+    if (!c->contacts_valid || !S.valid) FAIL(c, ARP_E_ARG, "arp_models_similarity_fetch: no matrix (arp_models_similarity_launch after a pass)");
+    *n_models = S.F;
+    if (S.F > cap_models) FAIL(c, ARP_E_CAPACITY, "arp_models_similarity_fetch: output buffer too small");
+    if (!inter) FAIL(c, ARP_E_ARG, "arp_models_similarity_fetch: output missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)(S.F * S.F) * sizeof(uint32_t);
+    CHK(table_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->table_stage, S.inter.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(inter, c->table_stage, bytes);
+    return ARP_OK;
+}
+
+int arp_models_similarity_info(arp_ctx* c, int64_t info[4]) {
+    if (!c || !info) return ARP_E_ARG;
+    const SimilarityResult& S = c->similarity;
+    info[0] = S.valid ? S.rows : 0;
+    info[1] = S.valid ? S.words : 0;
+    info[2] = S.valid ? S.slices : 0;
+    info[3] = S.launches;
+    return ARP_OK;
 }
 
 // ---- exchange between the shards of a distributed structure (RCCL behind the C ABI) -----------------------------------

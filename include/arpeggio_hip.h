@@ -802,6 +802,50 @@ int arp_models_water_bridge_persistence_fetch(arp_ctx* ctx, int64_t cap, int32_t
                                               float* dist_min, float* dist_max, double* dist_sum,
                                               uint16_t* bit_models_a /* [cap][15] */, uint16_t* bit_models_b /* [cap][15] */,
                                               uint8_t* ctype_mask_a, uint8_t* ctype_mask_b, int64_t* count);
+/* Interaction-fingerprint similarity between the resident models: which of the F models (arp_set_models) share their
+ * contacts.  The persistence tables above count, per row, the models that have it; this counts, per PAIR of models, the
+ * features both have — the intersection matrix from which the Tanimoto similarity, a clustering or a medoid follow on the
+ * host.  It is an extension beside the mirror; the result is F x F integers whatever the structure size.
+ *
+ * Rows.  At atom level a row is a distinct topology atom pair (a, b) of the atom-atom bag: exactly the rows of
+ *   arp_models_persistence.  With ARP_SIM_BY_RESIDUE a row is a distinct topology residue pair over the five bags: exactly
+ *   the rows of arp_models_residue_persistence — a record with a residue of -1 is left out, and a complete pass is needed.
+ * Planes.  ARP_SIM_PLANES = 20.  Plane q < 15: "an atom-atom record with SIFt bit q" (ARP_S_CLASH ... ARP_S_WEAK_POLAR).
+ *   Plane 15 + m: "a record of class m" — 0 atom-atom, 1 atom-plane, 2 plane-plane, 3 group-group, 4 group-plane.  At atom
+ *   level only the planes 0 ... 15 exist.
+ * Participation.  An atom-atom record takes part only when bit `ctype` of ctype_mask is set (the contact-type half of
+ *   arp_contacts_filter_launch's predicate); ring and amide records always take part.
+ * Features.  Feature (row r, plane q) is present in model f when q is in `planes` and at least one participating record of
+ *   row r in model f has plane q.
+ * Result.  inter[f][g], uint32: the features present in both f and g.  The matrix is symmetric, inter[f][f] is the feature
+ *   count of model f, and a model without records has a zero row and column.  Everything is a presence and a count: no float
+ *   exists on the device, and the order of the records cannot show.
+ *
+ * arp_models_similarity_launch: enqueues the work on the context's stream and waits once, for *n_rows = rows (U);
+ * *n_models = F.  ARP_E_ARG: a shard, no models resident, no results of a finished pass (atom level) or of a complete pass
+ * (residue level), planes == 0 or with bits beyond the 20, bits 16 ... 19 at atom level, a ctype_mask of 0 or beyond
+ * ARP_FILTER_CTYPE_ALL, an unknown flag.  ARP_E_CAPACITY: F > ARP_SIM_MAX_MODELS, (pair, model) does not fit a 63-bit key,
+ * 2^31 records or more, popcount(planes) x U >= 2^32 (a count would not fit uint32), a bit matrix of 4 GiB or more
+ * (F x popcount(planes) x ceil(U / 64) x 8 B).  No record at all: an all-zero matrix and ARP_OK.  A second call with the
+ * same arguments on the same results returns without work; other arguments remake the matrix.  It is voided wherever the
+ * persistence table (atom level) or the residue persistence table (residue level) is: by every input change and by the next
+ * launch that refills a bag it reads.  It reads the bags as the pass left them and writes no bag, no sorted slab, no filtered
+ * bag and no table: every other fetch returns the same before, after and without these calls, and no other call voids it.
+ *
+ * arp_models_similarity_fetch: the matrix with one device-to-host copy through the page-locked stage.  ARP_E_CAPACITY with
+ * *n_models = F when cap_models < F; ARP_E_ARG without a launch.
+ *
+ * arp_models_similarity_info: what the last launch did — info[0] = rows U, info[1] = 64-bit words of the bit matrix per
+ * model, info[2] = word slices of the product's grid (more than one: partial sums met by integer atomic adds), info[3] =
+ * launches of this context that did work (one that returned a resident matrix does not count).  [0 ... 2] are 0 while no
+ * matrix is resident. */
+#define ARP_SIM_PLANES 20
+#define ARP_SIM_MAX_MODELS 4096          /* F*F*4 B = 64 MiB result and page-locked stage */
+#define ARP_SIM_BY_RESIDUE 1u
+int arp_models_similarity_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags,
+                                 int64_t* n_models, int64_t* n_rows);
+int arp_models_similarity_fetch(arp_ctx* ctx, int64_t cap_models, uint32_t* inter /* [F][F] */, int64_t* n_models);
+int arp_models_similarity_info(arp_ctx* ctx, int64_t info[4]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
