@@ -726,10 +726,11 @@ class Context:
         bags, _ = self.fetch_packed() if contact_filter is None else self.fetch_packed_filtered(*contact_filter)
         return split_models(bags, self._models)
 
-    def _table(self, launch, fetch, spec):
-        """One device-reduced table: launch (the row count), then one fetch of every column of ``spec``."""
+    def _table(self, launch, fetch, spec, *args):
+        """One device-reduced table: launch with its arguments ``args`` (the row count), then one fetch of every column of
+        ``spec``."""
         n = C.c_int64(0)
-        self._check(getattr(self._L, launch)(self._h, C.byref(n)), launch)
+        self._check(getattr(self._L, launch)(self._h, *args, C.byref(n)), launch)
         U = int(n.value)
         t = tables.alloc(spec, U)
         self._check(getattr(self._L, fetch)(self._h, U, *(_p(t[k]) for k, _ in spec.columns), C.byref(n)), fetch)
@@ -765,13 +766,7 @@ class Context:
         the nine columns ``water_bridges.COLUMNS`` (see ``arpeggio_amd.water_bridges``).  Only the table is copied to the host;
         the bags of the pass, the filtered bag and the three tables stay fetchable as before.  With a batch or models resident
         the ids are those of the concatenation (``water_bridges.split_structures`` / ``split_models``)."""
-        from . import water_bridges as wb
-        n = C.c_int64(0)
-        self._check(self._L.arp_water_bridges_launch(self._h, int(sift_any), int(flags), C.byref(n)), 'arp_water_bridges_launch')
-        U = int(n.value)
-        t = {k: np.empty(U, dt) for k, dt in wb.COLUMNS}
-        self._check(self._L.arp_water_bridges_fetch(self._h, U, *(_p(t[k]) for k, _ in wb.COLUMNS), C.byref(n)), 'arp_water_bridges_fetch')
-        return t
+        return self._table('arp_water_bridges_launch', 'arp_water_bridges_fetch', tables.BRIDGES, int(sift_any), int(flags))
 
     def models_water_bridge_persistence(self, sift_any, flags=0):
         """Water-bridge persistence over the resident models of the last pass, reduced on the device
@@ -781,14 +776,8 @@ class Context:
         (``bit_models_a`` / ``bit_models_b`` as [U, 15]; see ``arpeggio_amd.bridge_persistence``).  Only the table is copied to
         the host; the bridge table stays resident and fetchable, and every other result stays what it was."""
         spec = tables.BRIDGEPERSIST_RESIDUE if int(flags) & WBP_BY_RESIDUE else tables.BRIDGEPERSIST_ATOM
-        n = C.c_int64(0)
-        self._check(self._L.arp_models_water_bridge_persistence_launch(self._h, int(sift_any), int(flags), C.byref(n)),
-                    'arp_models_water_bridge_persistence_launch')
-        U = int(n.value)
-        t = tables.alloc(spec, U)
-        self._check(self._L.arp_models_water_bridge_persistence_fetch(self._h, U, *(_p(t[k]) for k, _ in spec.columns), C.byref(n)),
-                    'arp_models_water_bridge_persistence_fetch')
-        return t
+        return self._table('arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch', spec,
+                           int(sift_any), int(flags))
 
     def models_similarity(self, planes, ctype_mask=CTYPE_ALL, by_residue=False):
         """The model-by-model matrix of shared interaction features of the last pass, made on the device

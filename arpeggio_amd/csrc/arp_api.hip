@@ -248,11 +248,14 @@ struct HintKey {
 
 }  // namespace
 
-// a table reduced on the device: its columns in one piece (table_layout), its rows, and whether it is that of the last results
+// a table reduced on the device: its columns in one piece (table_layout), its rows, whether it is that of the last results, and
+// the arguments of the launch that made it (0 for a launch without)
 struct ResultTable {
     DevBuf<uint8_t> slab;
     int64_t count = 0;
+    uint32_t arg[2] = {0, 0};
     bool valid = false;
+    bool made_with(uint32_t arg0, uint32_t arg1) const { return valid && arg[0] == arg0 && arg[1] == arg1; }
 };
 
 // the atom-atom records a caller asked for (arp_contacts_filter_launch): the kept records as the filter left them, and their
@@ -493,9 +496,8 @@ struct arp_ctx {
     DevBuf<float> models_xyz;
     DevBuf<double> models_box;
     int64_t models_n = 0;
-    // ---- the tables reduced on the device from the results of a pass (make_table / table_fetch): contact persistence over the
-    // resident models (arp_persist.h), the residue-pair table (arp_respair.h), residue persistence (arp_respersist.h).  They share
-    // the scratch — none needs it once it is made — and are results: voided with the bags they are made from
+    // ---- the results made on the device from the bags of a pass (DESIGN.md 5e ... 5k).  They share the scratch — none needs it
+    // once it is made — and are voided with what they read (void_results)
     SortScratch table_sort;               // the re-keyed records, double-buffered, and the digit tables of their sort
     DevBuf<int> table_tiles, table_rows;  // run detection (arp_runs.h)
     DevBuf<long long> table_total;
@@ -503,19 +505,10 @@ struct arp_ctx {
     size_t table_stage_cap = 0;
     ResultTable persist, respair, respersist;
     FilteredBag filtered;                 // arp_contacts_filter_launch: tile counts and total in table_tiles / table_total
-    // water-mediated contacts (arp_water_bridges_launch, arp_bridge.h): the table and what it was made for; the legs are sorted in
-    // table_sort and their runs found in table_tiles / table_rows / table_total, like a table's records
-    ResultTable bridges;
-    uint32_t bridges_sift_any = 0, bridges_flags = 0;
+    ResultTable bridges, bridgepersist;   // arp_water_bridges_launch, and arp_models_water_bridge_persistence_launch from its rows
     DevBuf<long long> bridge_off;         // [L + 1] kept pairs per water run, then their exclusive prefix; [L] = rows
     DevBuf<int> bridge_res;               // [L] residue of every sorted leg's partner
-    // water-bridge persistence over the resident models (arp_models_water_bridge_persistence_launch, arp_bridgepersist.h): made
-    // from the bridge table above — with bridges_sift_any / bridges_flags — and void whenever that is void or remade
-    ResultTable bridgepersist;
-    uint32_t bridgepersist_flags = 0;
-    // fingerprint similarity between the resident models (arp_models_similarity_launch, arp_similarity.h): made from the records
-    // of the persistence table (atom level) or of the residue persistence table (residue level), and void wherever that is
-    SimilarityResult similarity;
+    SimilarityResult similarity;          // arp_models_similarity_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -694,6 +687,25 @@ void make_grid_desc(GridDesc& d, const double lo[3], const double hi[3], double 
     d.place = nullptr; d.sid_atom = nullptr; d.sid_ring = nullptr; d.sid_amide = nullptr;
 }
 
+// The one rule that voids the results made on the device from the bags of a pass (DESIGN.md 5e ... 5k).  `lost` names what was
+// refilled, lost or remade: the atom-atom bag, the ring / amide bags, the bridge table, the packed layout.  A result goes when it
+// reads any of that, and what is made from it goes with it (it stands behind its source in the list below, which is the one
+// statement of what each result reads).  A launch sets its own result valid again.
+enum : unsigned { RES_AA = 1u << 0, RES_PLANES = 1u << 1, RES_BRIDGES = 1u << 2, RES_LAYOUT = 1u << 3 };
+void void_results(arp_ctx* c, unsigned lost) {
+    const unsigned bags = RES_AA | RES_PLANES;
+    const struct { bool* valid; unsigned reads, makes; } results[] = {
+        {&c->persist.valid, RES_AA, 0},
+        {&c->bridges.valid, RES_AA, RES_BRIDGES},
+        {&c->bridgepersist.valid, RES_BRIDGES, 0},
+        {&c->respair.valid, bags, 0},
+        {&c->respersist.valid, bags, 0},
+        {&c->filtered.valid, bags | RES_LAYOUT, 0},      // (its slab is sized for the four bags packed behind the kept records)
+        {&c->similarity.valid, (c->similarity.flags & SIM_BY_RESIDUE) ? bags : RES_AA, 0}};      // (the bags of its level)
+    for (const auto& r : results)
+        if (r.reads & lost) { *r.valid = false; lost |= r.makes; }
+}
+
 // What a caller can replace, for inputs_changed.  IN_BATCH_GRIDS is no input: batch_grid_desc started the grid tables of the
 // batch over (every slot held another radius; arp_get_stats counts it in stats[7]).
 enum : unsigned {
@@ -744,14 +756,8 @@ enum : unsigned {
 //   tables go with it.  arp_set_batch records the new partition after this call.
 // selection: selection_plus and the sets are made again (sel_made, sel_epoch).  default selection: a new structure starts
 //   with everything selected (I:1395) and no whole-structure assertion.
-// results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  The
-//   persistence table of the resident models (arp_models_persistence_launch) and the water bridges
-//   (arp_water_bridges_launch) are made from the atom-atom bag and go with it, and so does the water-bridge persistence
-//   table (arp_models_water_bridge_persistence_launch), which is made from the water bridges; the similarity matrix of the
-//   resident models (arp_models_similarity_launch) goes with the bag(s) its level reads, as the persistence table of that level;
-//   the residue-pair table (arp_residue_pairs_launch) and the residue persistence table
-//   (arp_models_residue_persistence_launch) are made from all five and go with any of them (finish_contacts, finish_bag: the
-//   next launch that refills a bag).
+// results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  What
+//   is made from them on the device goes with them by the one rule of void_results.
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -783,13 +789,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->models_n = 0;
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
-        c->persist.valid = false;
-        c->respair.valid = false;
-        c->respersist.valid = false;
-        c->filtered.valid = false;
-        c->bridges.valid = false;
-        c->bridgepersist.valid = false;
-        c->similarity.valid = false;
+        void_results(c, RES_AA | RES_PLANES);
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
     }
 }
@@ -1967,13 +1967,7 @@ bool finish_contacts(arp_ctx* c) {
     c->contacts_expected = (int64_t)np;
     c->contacts_valid = true;
     c->contacts_sorted = false;
-    c->persist.valid = false;
-    c->respair.valid = false;
-    c->respersist.valid = false;
-    c->filtered.valid = false;
-    c->bridges.valid = false;
-    c->bridgepersist.valid = false;
-    c->similarity.valid = false;
+    void_results(c, RES_AA);
     c->stats[0] = (int64_t)c->h_ctr[C_CAND];
     c->stats[1] = (int64_t)c->h_ctr[C_ACC];
     c->stats[2] = (int64_t)np;
@@ -1996,6 +1990,17 @@ void sorted_layout(size_t k, size_t off[5], size_t* bytes, size_t first_col_entr
     off[4] = off[3] + al256(k * sizeof(uint16_t));
     *bytes = off[4] + al256(k * sizeof(uint8_t));
 }
+// A slab bound to the offsets of its columns — sorted_layout's or a table's (table_layout) —: col[q] is column q as whatever
+// pointer it is assigned to.
+struct Column {
+    uint8_t* p;
+    template <class T> operator T*() const { return (T*)p; }
+};
+struct Columns {
+    uint8_t* slab;
+    const size_t* off;
+    Column operator[](int q) const { return Column{slab + off[q]}; }
+};
 // Canonical order of a bag by the radix sort of arp_sort.h: keys {first id << idbits | second id}, the other columns riding in
 // the payload.  Radix passes over the bits of the first id — or, small_nbin > 0, ONE launch that groups the records by first id
 // (k_sort_small, small_nbin ids) —, then the runs of equal first id ordered by the second in one launch (k_sort_runs).  A holds
@@ -2106,10 +2111,7 @@ bool finish_bag(arp_ctx* c, Bag& b) {
     b.count = (int64_t)k;
     b.valid = true;
     ++b.version;
-    c->respair.valid = false;
-    c->respersist.valid = false;
-    if (c->similarity.flags & SIM_BY_RESIDUE) c->similarity.valid = false;      // (at atom level it reads the atom-atom bag alone)
-    c->filtered.valid = false;      // (the bags packed behind the kept records are sized when it is made)
+    void_results(c, RES_PLANES);
     return false;
 }
 int grow_pairs(arp_ctx* c) {
@@ -4139,41 +4141,109 @@ int arp_models_planes(arp_ctx* c, double* ring_center, double* ring_normal, int3
     return ARP_OK;
 }
 
-// ---- the tables reduced on the device from the results of a pass -------------------------------
-// Contact persistence over the resident models (arp_persist.h), the residue-pair table (arp_respair.h) and residue persistence
-// over the resident models (arp_respersist.h) are one shape: refuse, return a table that is already made, re-key the records,
-// sort them by the whole key, count the runs (the one wait: U rows), size the slab, reduce one wave per row (make_table);
-// and one copy of the slab through the page-locked stage (table_fetch).  A table brings a TableSpec and its two own steps.
+// ---- the results made on the device from the bags of a pass (DESIGN.md 5e ... 5k) -------------------------------------
+// Every launch refuses (check_masks, launch_refusals), returns a result that is already made for its arguments, enqueues, waits
+// for a count (wait_count) and enqueues the rest.  A result of sorted records is two parts around that wait: sort_to_runs
+// (reserve, re-key, sort by every bit, count the runs, learn U) and reduce_to_rows (layout, slab, run starts, one wave per
+// row); table_fetch is one copy of the slab through the page-locked stage.  A table brings a TableSpec and its two own steps.
 namespace {
 enum { TABLE_MAX_COLS = 14 };
+// what a launch needs of the context; refused in this order before a launch looks for its result (launch_refusals)
+enum : unsigned { NEED_WHOLE = 1u << 0, NEED_MODELS = 1u << 1, NEED_MODELS_U16 = 1u << 2, NEED_AA_BAG = 1u << 3, NEED_FIVE_BAGS = 1u << 4 };
 struct TableSpec {
     const char* name;                // "<name>_launch" / "<name>_fetch" in messages
     ResultTable arp_ctx::* table;
     int cols;
     size_t es[TABLE_MAX_COLS];       // bytes per row of every column, in the order of the fetch's arguments (= of the slab)
-    bool models;                     // made over the resident models (arp_set_models)
-    bool five_bags;                  // made from all five bags of a complete pass; else from the atom-atom bag alone
+    unsigned needs;                  // NEED_*: FIVE_BAGS = made from all five bags of a complete pass; else from the atom-atom bag alone
     const char* no_pass;             // the refusal when those results are missing
     long long min_rows;              // fewest rows that records can give: 0 where a table leaves records out (all of them, then)
+    std::string launch() const { return std::string(name) + "_launch: "; }
 };
+const char* const NO_AA_PASS = "no atom-contact results (call a launch first)";
 // the columns of every table in the order of its fetch's arguments
 enum { PT_A = 0, PT_B, PT_NMODELS, PT_FIRST, PT_LAST, PT_DMIN, PT_DMAX, PT_DSUM, PT_BITS, PT_CTYPE, PT_COLS };
 enum { RT_A = 0, RT_B, RT_N, RT_DMIN, RT_BITS, RT_CTYPE, RT_PLANES, RT_COLS };
 enum { ST_A = 0, ST_B, ST_NMODELS, ST_FIRST, ST_LAST, ST_N, ST_CLS, ST_BITS, ST_DMIN, ST_DMAX, ST_DSUM, ST_CTYPE, ST_COLS };
+enum { WB_WATER = 0, WB_A, WB_B, WB_DIST_A, WB_DIST_B, WB_SIFT_A, WB_SIFT_B, WB_CTYPE_A, WB_CTYPE_B, WB_COLS };
+enum { WP_A = 0, WP_B, WP_NMODELS, WP_FIRST, WP_LAST, WP_NWATERS, WP_NBRIDGES, WP_DMIN, WP_DMAX, WP_DSUM, WP_BITS_A, WP_BITS_B,
+       WP_CTYPE_A, WP_CTYPE_B, WP_COLS };
+const unsigned OVER_MODELS = NEED_WHOLE | NEED_MODELS | NEED_MODELS_U16;
 const TableSpec PERSIST_TABLE = {"arp_models_persistence", &arp_ctx::persist, PT_COLS, {4, 4, 2, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 1},
-                                 true, false, "no results of a pass over the resident models (launch one first)", 1};
+                                 OVER_MODELS | NEED_AA_BAG, "no results of a pass over the resident models (launch one first)", 1};
 const TableSpec RESPAIR_TABLE = {"arp_residue_pairs", &arp_ctx::respair, RT_COLS, {4, 4, 4, 4, 4 * TABLE_SIFT_BITS, 1, 4 * RESPAIR_PLANE_BAGS},
-                                 false, true, "no results of a complete pass (arp_run_launch first)", 0};
+                                 NEED_WHOLE | NEED_FIVE_BAGS, "no results of a complete pass (arp_run_launch first)", 0};
 const TableSpec RESPERSIST_TABLE = {"arp_models_residue_persistence", &arp_ctx::respersist, ST_COLS,
                                     {4, 4, 2, 4, 4, 4, 2 * RESPERSIST_CLASSES, 2 * TABLE_SIFT_BITS, 4, 4, 8, 1},
-                                    true, true, "no results of a complete pass over the resident models (arp_run_launch first)", 0};
-static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+                                    OVER_MODELS | NEED_FIVE_BAGS, "no results of a complete pass over the resident models (arp_run_launch first)", 0};
+const TableSpec BRIDGE_TABLE = {"arp_water_bridges", &arp_ctx::bridges, WB_COLS, {4, 4, 4, 4, 4, 2, 2, 1, 1}, NEED_WHOLE | NEED_AA_BAG, NO_AA_PASS, 0};
+const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &arp_ctx::bridgepersist, WP_COLS,
+                                       {4, 4, 2, 4, 4, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 2 * TABLE_SIFT_BITS, 1, 1}, OVER_MODELS | NEED_AA_BAG,
+                                       "no atom-contact results of a pass over the resident models (call a launch first)", 1};
+static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS && WB_COLS <= TABLE_MAX_COLS &&
+              WP_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+static_assert(BRIDGE_F_WATER == ARP_F_WATER && BRIDGE_SAME_RESIDUE == ARP_WB_SAME_RESIDUE, "arp_bridge.h names the header's bits");
+static_assert(BRIDGEPERSIST_BY_RESIDUE == ARP_WBP_BY_RESIDUE && TABLE_SIFT_BITS == ARP_WBP_BITS, "arp_bridgepersist.h names the header's bits");
+static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESIDUE && SIM_PLANES == TABLE_SIFT_BITS + RESPERSIST_CLASSES,
+              "arp_similarity.h names the header's planes");
 
+// ---- what a launch refuses
+bool five_bags_complete(const arp_ctx* c) {
+    return !c->pass_pending && c->contacts_valid && c->bag_ap.valid && c->bag_pp.valid && c->bag_gg.valid && c->bag_gp.valid;
+}
+int launch_refusals(arp_ctx* c, const std::string& fn, unsigned needs, const char* no_pass) {
+    if ((needs & NEED_WHOLE) && (c->has_home || c->has_gid || c->shard_resident)) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if ((needs & NEED_MODELS) && c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
+    if ((needs & NEED_MODELS_U16) && c->models_n > 65535) FAIL(c, ARP_E_ARG, fn + "more than 65 535 models (the table counts models in uint16)");
+    if ((needs & NEED_FIVE_BAGS) ? !five_bags_complete(c) : (needs & NEED_AA_BAG) && (c->pass_pending || !c->contacts_valid)) FAIL(c, ARP_E_ARG, fn + no_pass);
+    return ARP_OK;
+}
+// (a left-out record keeps its slot up to the reduction, so every record of the bags counts here, kept or not)
+int records_fit(arp_ctx* c, const std::string& fn, size_t k, const char* why = "") {
+    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more" + why);
+    return ARP_OK;
+}
+// masks {value, every bit there is}: none reaches beyond its bits, then none is 0
+int check_masks(arp_ctx* c, const std::string& fn, std::initializer_list<std::pair<uint32_t, uint32_t>> masks, const char* beyond, const char* zero) {
+    for (const auto& m : masks) if (m.first & ~m.second) FAIL(c, ARP_E_ARG, fn + beyond);
+    for (const auto& m : masks) if (!m.first) FAIL(c, ARP_E_ARG, fn + zero);
+    return ARP_OK;
+}
+int check_leg_mask(arp_ctx* c, const std::string& fn, uint32_t sift_any) {
+    return check_masks(c, fn, {{sift_any, ARP_FILTER_SIFT_ALL}}, "sift_any has bits beyond the 15 SIFt bits", "a sift_any of 0 makes no record a leg");
+}
+// A table is made: its rows, and the arguments of the launch for made_with.
+int table_done(ResultTable& T, uint32_t arg0, uint32_t arg1, long long rows, int64_t* count) {
+    T.count = rows; T.arg[0] = arg0; T.arg[1] = arg1; T.valid = true;
+    *count = rows;
+    return ARP_OK;
+}
+
+// ---- keys
+int index_bits(int64_t count) { return id_bits(std::max<int64_t>(count - 1, 1)); }      // of the ids 0 ... count - 1
+// The key of (pair, model): id_a << (bits + fbits) | id_b << fbits | model, the ids atoms of the topology (n of them) or
+// residues of a model (nres_t; no residue at all: 1, and every record is left out).
+struct PairModelKey {
+    int64_t F, n, nres_t;
+    int bits, fbits;
+    int total() const { return 2 * bits + fbits; }
+};
+int pair_model_key(arp_ctx* c, const std::string& fn, bool by_residue, const char* what, PairModelKey* G) {
+    G->F = c->models_n; G->n = c->topo_hdr.n; G->nres_t = std::max<int64_t>(c->nres / G->F, 1);
+    G->bits = index_bits(by_residue ? G->nres_t : G->n); G->fbits = index_bits(G->F);
+    if (G->total() > 63) FAIL(c, ARP_E_CAPACITY, fn + what + " does not fit a 63-bit key");
+    return ARP_OK;
+}
+
+// ---- slabs
 // Layout of a table's slab: its columns one after the other, each on a 256-byte boundary (so their order is free).
-void table_layout(const TableSpec& spec, size_t U, size_t off[TABLE_MAX_COLS], size_t* bytes) {
-    size_t at = 0;
-    for (int q = 0; q < spec.cols; ++q) { off[q] = at; at += al256(U * spec.es[q]); }
-    *bytes = at;
+struct TableLayout {
+    size_t off[TABLE_MAX_COLS], bytes;
+};
+TableLayout table_layout(const TableSpec& spec, size_t U) {
+    TableLayout L{};
+    for (int q = 0; q < spec.cols; ++q) { L.off[q] = L.bytes; L.bytes += al256(U * spec.es[q]); }
+    return L;
 }
 int table_stage_reserve(arp_ctx* c, size_t bytes) {
     if (c->table_stage && c->table_stage_cap >= bytes) return ARP_OK;
@@ -4185,6 +4255,39 @@ int table_stage_reserve(arp_ctx* c, size_t bytes) {
     c->table_stage_cap = want;
     return ARP_OK;
 }
+// One copy of `bytes` from the device into the page-locked stage, waited for: a fetch's, and the word of wait_count.
+int stage_copy(arp_ctx* c, const void* dev, size_t bytes) {
+    CHK(table_stage_reserve(c, bytes));
+    HIPCHK(c, hipMemcpyAsync(c->table_stage, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ARP_OK;
+}
+
+// ---- the wait for one count
+// Counts per tile go to table_tiles (reserve_tile_counts, then the caller's kernel), k_runs_scan makes their exclusive prefix
+// and their sum in table_total (enqueue_tile_scan), and the host reads one 64-bit word through the stage (wait_count).
+int reserve_tile_counts(arp_ctx* c, int T) {
+    HIPCHK(c, c->table_tiles.reserve((size_t)T));
+    HIPCHK(c, c->table_total.reserve(1));
+    return table_stage_reserve(c, 4096);
+}
+void enqueue_tile_scan(arp_ctx* c, int T) {
+    RunArgs R{};
+    R.T = T; R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
+    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+}
+int wait_count(arp_ctx* c, const long long* dev, long long* v, const std::string& what) {
+    CHK(check_launch(c, what.c_str()));
+    CHK(stage_copy(c, dev, sizeof(long long)));
+    memcpy(v, c->table_stage, sizeof(*v));
+    return ARP_OK;
+}
+int wait_tile_total(arp_ctx* c, int T, long long* v, const std::string& what) {
+    enqueue_tile_scan(c, T);
+    return wait_count(c, c->table_total.p, v, what);
+}
+
+// ---- sorted records and their runs
 // k re-keyed records in s.key[0] / s.val[0], sorted by the low keybits bits of the key — every bit of it: least significant
 // digit first, up to SORT_MAX_BITS a pass, stable.  *sorted = the buffer (0 / 1) the last pass wrote.  reserve_key_sort sizes the
 // scratch (cap >= k records) before the caller fills buffer 0.
@@ -4214,22 +4317,14 @@ void enqueue_key_sort(arp_ctx* c, SortScratch& s, size_t k, int keybits, int* so
     }
     *sorted = passes & 1;
 }
-// The runs of equal key >> R.shift among the sorted keys: counted per tile and scanned on the stream, then the one wait of a
-// table's launch — *U = runs = rows of the table.  R.key, R.k and R.shift are the caller's.
-int count_runs(arp_ctx* c, RunArgs& R, long long* U, const std::string& what) {
+// The runs of equal key >> R.shift among the sorted keys, counted per tile and scanned on the stream: their number stays in
+// table_total.  R.key, R.k and R.shift are the caller's, and so is the room for R.T tile counts (reserve_tile_counts).
+void enqueue_run_count(arp_ctx* c, RunArgs& R) {
     R.T = (int)((R.k + RUNS_TILE - 1) / RUNS_TILE);
-    HIPCHK(c, c->table_tiles.reserve((size_t)R.T));
-    HIPCHK(c, c->table_total.reserve(1));
-    CHK(table_stage_reserve(c, 4096));
     R.tile_rows = c->table_tiles.p;
     R.total = c->table_total.p;
     hipLaunchKernelGGL(k_runs_count, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
-    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
-    CHK(check_launch(c, what.c_str()));
-    HIPCHK(c, hipMemcpyAsync(c->table_stage, c->table_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(U, c->table_stage, sizeof(*U));
-    return ARP_OK;
+    enqueue_tile_scan(c, R.T);
 }
 // ... and where each of the U runs begins (row_start[U] = k), for the reduction that follows on the stream
 int enqueue_run_starts(arp_ctx* c, RunArgs& R, long long U) {
@@ -4239,6 +4334,57 @@ int enqueue_run_starts(arp_ctx* c, RunArgs& R, long long U) {
     hipLaunchKernelGGL(k_runs_starts, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
     return ARP_OK;
 }
+// What a re-key step tells the sequence: the bits of the key the sort covers, and a run = equal key >> shift.
+struct TableKey {
+    int bits, shift;
+};
+// Records sorted by their key and the U runs among them: what sort_to_runs leaves for the step that reduces them.
+struct SortedRuns {
+    const unsigned long long *key, *val;
+    RunArgs R;
+    long long U;
+};
+// rekey(key, val, &K) enqueues the keys and payloads of the k records into key / val and fills K; reduce(S, col) enqueues the
+// reduction of the sorted records S into the S.U rows of the columns col[0 ... spec.cols).
+using RekeyStep = std::function<int(unsigned long long* key, unsigned long long* val, TableKey* K)>;
+using ReduceStep = std::function<void(const SortedRuns& S, const Columns& col)>;
+// The first part: k > 0 records (the scratch sized for cap >= k) re-keyed, sorted by every bit of the key, their runs counted;
+// the host learns U (the one wait), which lies in [min_rows, k].
+int sort_to_runs(arp_ctx* c, const std::string& fn, size_t k, size_t cap, long long min_rows, const RekeyStep& rekey, SortedRuns* S) {
+    SortScratch& s = c->table_sort;
+    CHK(reserve_key_sort(c, s, k, cap));
+    TableKey K{};
+    CHK(rekey(s.key[0].p, s.val[0].p, &K));
+    int sorted = 0;
+    enqueue_key_sort(c, s, k, K.bits, &sorted);
+    *S = SortedRuns{s.key[sorted].p, s.val[sorted].p, RunArgs{}, 0};
+    RunArgs& R = S->R;
+    R.key = S->key; R.k = (long long)k; R.shift = K.shift;
+    CHK(reserve_tile_counts(c, (int)((R.k + RUNS_TILE - 1) / RUNS_TILE)));
+    enqueue_run_count(c, R);
+    CHK(wait_count(c, c->table_total.p, &S->U, fn + "sort / count"));
+    if (S->U < min_rows || S->U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    return ARP_OK;
+}
+// The second part: the slab of S.U > 0 rows, where each run begins, and the table's reduction, one wave per row.
+int reduce_to_rows(arp_ctx* c, const TableSpec& spec, SortedRuns& S, const ReduceStep& reduce) {
+    ResultTable& T = c->*spec.table;
+    const TableLayout L = table_layout(spec, (size_t)S.U);
+    HIPCHK(c, T.slab.reserve(L.bytes));
+    CHK(enqueue_run_starts(c, S.R, S.U));
+    reduce(S, Columns{T.slab.p, L.off});
+    return check_launch(c, (spec.launch() + "reduce").c_str());
+}
+// Both parts: the table of k > 0 records, made with (arg0, arg1).
+int table_from_records(arp_ctx* c, const TableSpec& spec, uint32_t arg0, uint32_t arg1, size_t k, size_t cap, int64_t* count,
+                       const RekeyStep& rekey, const ReduceStep& reduce) {
+    SortedRuns S{};
+    CHK(sort_to_runs(c, spec.launch(), k, cap, spec.min_rows, rekey, &S));
+    if (S.U > 0) CHK(reduce_to_rows(c, spec, S, reduce));
+    return table_done(c->*spec.table, arg0, arg1, S.U, count);
+}
+
+// ---- the bags as records
 // What a table reads of a pass: the atom-atom bag and — planes: a residue table — the four ring / amide bags as the re-key
 // kernels walk them, placed behind the atom-atom records; the records of all those bags (k), of the four (planes) and of the
 // largest of the four; and the capacity the sort scratch is sized from — the capacities of the bags' columns, so that it is
@@ -4248,9 +4394,6 @@ struct FiveBags {
     size_t k, planes, cap;
     int64_t largest;
 };
-bool five_bags_complete(const arp_ctx* c) {
-    return !c->pass_pending && c->contacts_valid && c->bag_ap.valid && c->bag_pp.valid && c->bag_gg.valid && c->bag_gp.valid;
-}
 FiveBags five_bags(const arp_ctx* c, bool planes) {
     const Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};
     const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
@@ -4268,59 +4411,22 @@ FiveBags five_bags(const arp_ctx* c, bool planes) {
     }
     return B;
 }
-// What a table's re-key step tells the sequence: the bits of the key the sort covers, and a run = equal key >> shift.
-struct TableKey {
-    int bits, shift;
-};
-// The sequence of a table's launch.  rekey(B, key, val, &K) enqueues the table's keys and payloads for the B.k records into
-// key / val and fills K; reduce(key, val, row_start, U, col) enqueues the table's reduction of the sorted records into the U
-// rows of the columns col[0 ... spec.cols).
-using RekeyStep = std::function<int(const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K)>;
-using ReduceStep = std::function<void(const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col)>;
-int make_table(arp_ctx* c, const TableSpec& spec, int64_t* count, const RekeyStep& rekey, const ReduceStep& reduce) {
+// A table without launch arguments, made from the bags: refuse, return the table that is made, then table_from_records with
+// rekey(B, ...) over the bags B the spec names.
+using BagsRekeyStep = std::function<int(const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K)>;
+int make_table(arp_ctx* c, const TableSpec& spec, int64_t* count, const BagsRekeyStep& rekey, const ReduceStep& reduce) {
     if (!c || !count) return ARP_E_ARG;
-    const std::string fn = std::string(spec.name) + "_launch: ";
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (spec.models && c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
-    if (spec.models && c->models_n > 65535) FAIL(c, ARP_E_ARG, fn + "more than 65 535 models (the table counts models in uint16)");
-    if (spec.five_bags ? !five_bags_complete(c) : (c->pass_pending || !c->contacts_valid)) FAIL(c, ARP_E_ARG, fn + spec.no_pass);
+    const std::string fn = spec.launch();
+    CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
     ResultTable& T = c->*spec.table;
-    if (T.valid) { *count = T.count; return ARP_OK; }
+    if (T.made_with(0, 0)) { *count = T.count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
-    const FiveBags B = five_bags(c, spec.five_bags);
-    const size_t k = B.k;
+    const FiveBags B = five_bags(c, (spec.needs & NEED_FIVE_BAGS) != 0);
     T.count = 0;
-    if (k == 0) { T.valid = true; *count = 0; return ARP_OK; }
-    // (a left-out record keeps its slot up to the reduction, so every record of the bags counts here, kept or not)
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
-    // ---- the table's keys, sorted by every bit: least significant digit first
-    SortScratch& s = c->table_sort;
-    CHK(reserve_key_sort(c, s, k, B.cap));
-    TableKey K{};
-    CHK(rekey(B, s.key[0].p, s.val[0].p, &K));
-    int sorted = 0;
-    enqueue_key_sort(c, s, k, K.bits, &sorted);
-    // ---- rows: count, scan; the host learns U (the one wait)
-    RunArgs R{};
-    R.key = s.key[sorted].p; R.k = (long long)k; R.shift = K.shift;
-    long long U = 0;
-    CHK(count_runs(c, R, &U, fn + "sort / count"));
-    if (U < spec.min_rows || U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
-    if (U > 0) {
-        // ---- the table: row starts, one wave per row
-        size_t off[TABLE_MAX_COLS], bytes;
-        table_layout(spec, (size_t)U, off, &bytes);
-        HIPCHK(c, T.slab.reserve(bytes));
-        CHK(enqueue_run_starts(c, R, U));
-        uint8_t* col[TABLE_MAX_COLS];
-        for (int q = 0; q < spec.cols; ++q) col[q] = T.slab.p + off[q];
-        reduce(R.key, s.val[sorted].p, R.row_start, U, col);
-        CHK(check_launch(c, (fn + "reduce").c_str()));
-    }
-    T.count = U;
-    T.valid = true;
-    *count = U;
-    return ARP_OK;
+    if (B.k == 0) return table_done(T, 0, 0, 0, count);
+    CHK(records_fit(c, fn, B.k));
+    return table_from_records(c, spec, 0, 0, B.k, B.cap, count,
+                              [&](unsigned long long* key, unsigned long long* val, TableKey* K) { return rekey(B, key, val, K); }, reduce);
 }
 // One copy of the slab into the page-locked stage; column q goes to dst[q] unless that is NULL.
 int table_fetch(arp_ctx* c, const TableSpec& spec, int64_t cap, void* const dst[], int64_t* count) {
@@ -4333,32 +4439,41 @@ int table_fetch(arp_ctx* c, const TableSpec& spec, int64_t cap, void* const dst[
     const size_t U = (size_t)T.count;
     if (U == 0) return ARP_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    size_t off[TABLE_MAX_COLS], bytes;
-    table_layout(spec, U, off, &bytes);
-    CHK(table_stage_reserve(c, bytes));
-    HIPCHK(c, hipMemcpyAsync(c->table_stage, T.slab.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const TableLayout L = table_layout(spec, U);
+    CHK(stage_copy(c, T.slab.p, L.bytes));
     for (int q = 0; q < spec.cols; ++q)
-        if (dst[q]) memcpy(dst[q], c->table_stage + off[q], U * spec.es[q]);
+        if (dst[q]) memcpy(dst[q], c->table_stage + L.off[q], U * spec.es[q]);
     return ARP_OK;
 }
-// Bits of the key of a residue table that the sort covers: res_a << (rbits + fbits) | res_b << fbits | f, and one bit more
-// where the all-ones key of a left-out record would otherwise tie with a real record in the sorted bits — the pair
-// (nres_t - 1, nres_t - 1) of a ring / amide bag in model F - 1, when nres_t - 1 and F - 1 are all ones themselves (bit
-// 2 rbits + fbits is set in ~0 and in no record: the left-out records then sort last by it).  The residue-pair table has no
-// model in its key: fbits = 0, F = 1.
-int respersist_key_bits(int64_t nres_t, int64_t F, int rbits, int fbits, bool planes) {
-    const bool tie = planes && nres_t - 1 == ((int64_t)1 << rbits) - 1 && F - 1 == ((int64_t)1 << fbits) - 1;
-    return 2 * rbits + fbits + (tie ? 1 : 0);
+
+// ---- the re-key steps
+// The atom-atom bag keyed by topology atom pair and model (the persistence table's rows); returns what it launched with, for
+// the reduction of that table.
+PersistArgs enqueue_persist_rekey(arp_ctx* c, const PairModelKey& G, size_t k, unsigned long long* key, unsigned long long* val, TableKey* K) {
+    PersistArgs A{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k;
+    A.n = (uint32_t)G.n;      // (> 0: the bag has records)
+    A.bbits = G.bits; A.fbits = G.fbits;
+    A.key = key; A.val = val;
+    *K = TableKey{G.total(), G.fbits};
+    hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, A);
+    return A;
 }
-// The re-key step of both residue tables: the five bags keyed by topology residue pair and model (nres_t residues a model).
-void enqueue_residue_rekey(arp_ctx* c, const FiveBags& B, int64_t nres_t, int rbits, int fbits, unsigned long long* key, unsigned long long* val) {
+// The five bags keyed by topology residue pair and model (the rows of both residue tables; the residue-pair table has no model
+// in its key: G.fbits = 0, G.F = 1).  The sort covers res_a << (bits + fbits) | res_b << fbits | f, and one bit more where the
+// all-ones key of a left-out record would otherwise tie with a real record in the sorted bits — the pair (nres_t - 1,
+// nres_t - 1) of a ring / amide bag in model F - 1, when nres_t - 1 and F - 1 are all ones themselves (bit 2 bits + fbits is
+// set in ~0 and in no record: the left-out records then sort last by it).
+void enqueue_residue_rekey(arp_ctx* c, const FiveBags& B, const PairModelKey& G, unsigned long long* key, unsigned long long* val, TableKey* K) {
+    const bool tie = B.planes > 0 && G.nres_t - 1 == ((int64_t)1 << G.bits) - 1 && G.F - 1 == ((int64_t)1 << G.fbits) - 1;
+    *K = TableKey{G.total() + (tie ? 1 : 0), G.fbits};
     RekeyArgs A{};
     A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
     A.res_id = c->res_id.p;
     A.k_aa = (long long)c->n_contacts;
     for (int m = 0; m < RESPAIR_PLANE_BAGS; ++m) A.bag[m] = B.bag[m];
-    A.nres_t = (uint32_t)nres_t; A.rbits = rbits; A.fbits = fbits;
+    A.nres_t = (uint32_t)G.nres_t; A.rbits = G.bits; A.fbits = G.fbits;
     A.key = key; A.val = val;
     if (A.k_aa > 0) hipLaunchKernelGGL(k_residue_rekey, dim3(nblocks((int64_t)A.k_aa, 256, 2048)), dim3(256), 0, c->stream, A);
     if (B.planes > 0) hipLaunchKernelGGL(k_residue_rekey_planes, dim3(nblocks(B.largest, 256, 512), RESPAIR_PLANE_BAGS), dim3(256), 0, c->stream, A);
@@ -4370,23 +4485,16 @@ int arp_models_persistence_launch(arp_ctx* c, int64_t* count) {
     PersistArgs A{};
     return make_table(c, PERSIST_TABLE, count,
         [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
-            A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
-            A.k = (long long)B.k;
-            A.n = (uint32_t)c->topo_hdr.n;      // (> 0: the bag has records)
-            A.bbits = id_bits(std::max<int64_t>(c->topo_hdr.n - 1, 1));
-            A.fbits = id_bits(std::max<int64_t>(c->models_n - 1, 1));
-            *K = TableKey{2 * A.bbits + A.fbits, A.fbits};
-            if (K->bits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_persistence_launch: (atom, atom, model) does not fit a 63-bit key");
-            A.key = key; A.val = val;
-            hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)B.k, 256, 2048)), dim3(256), 0, c->stream, A);
+            PairModelKey G{};
+            CHK(pair_model_key(c, PERSIST_TABLE.launch(), false, "(atom, atom, model)", &G));
+            A = enqueue_persist_rekey(c, G, B.k, key, val, K);
             return ARP_OK;
         },
-        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
-            A.key = (unsigned long long*)key; A.val = (unsigned long long*)val; A.row_start = row_start; A.U = U;
-            A.t_a = (int*)col[PT_A]; A.t_b = (int*)col[PT_B]; A.t_nmodels = (uint16_t*)col[PT_NMODELS];
-            A.t_first = (int*)col[PT_FIRST]; A.t_last = (int*)col[PT_LAST]; A.t_dmin = (float*)col[PT_DMIN]; A.t_dmax = (float*)col[PT_DMAX];
-            A.t_dsum = (double*)col[PT_DSUM]; A.t_bits = (uint16_t*)col[PT_BITS]; A.t_ctype = col[PT_CTYPE];
-            hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        [&](const SortedRuns& S, const Columns& col) {
+            A.key = (unsigned long long*)S.key; A.val = (unsigned long long*)S.val; A.row_start = S.R.row_start; A.U = S.U;
+            A.t_a = col[PT_A]; A.t_b = col[PT_B]; A.t_nmodels = col[PT_NMODELS]; A.t_first = col[PT_FIRST]; A.t_last = col[PT_LAST];
+            A.t_dmin = col[PT_DMIN]; A.t_dmax = col[PT_DMAX]; A.t_dsum = col[PT_DSUM]; A.t_bits = col[PT_BITS]; A.t_ctype = col[PT_CTYPE];
+            hipLaunchKernelGGL(k_persist_reduce, dim3(nblocks(S.U, 4, 16384)), dim3(256), 0, c->stream, A);
         });
 }
 
@@ -4398,18 +4506,17 @@ int arp_models_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b
 
 // ---- residue-residue contact table of the last pass (arp_respair.h): no model in the key, every resident residue one "model"
 int arp_residue_pairs_launch(arp_ctx* c, int64_t* count) {
-    int rbits = 0;
+    PairModelKey G{};
     return make_table(c, RESPAIR_TABLE, count,
         [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
-            rbits = id_bits(std::max<int64_t>(c->nres - 1, 1));
-            *K = TableKey{respersist_key_bits(c->nres, 1, rbits, 0, B.planes > 0), 0};
-            enqueue_residue_rekey(c, B, std::max<int64_t>(c->nres, 1), rbits, 0, key, val);
+            G = PairModelKey{1, c->n, std::max<int64_t>(c->nres, 1), index_bits(c->nres), 0};
+            enqueue_residue_rekey(c, B, G, key, val, K);
             return ARP_OK;
         },
-        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
-            const RespairArgs A{rbits, key, val, row_start, U, (int*)col[RT_A], (int*)col[RT_B], (uint32_t*)col[RT_N], (float*)col[RT_DMIN],
-                                (uint32_t*)col[RT_BITS], col[RT_CTYPE], (uint32_t*)col[RT_PLANES]};
-            hipLaunchKernelGGL(k_respair_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+        [&](const SortedRuns& S, const Columns& col) {
+            const RespairArgs A{G.bits, S.key, S.val, S.R.row_start, S.U, col[RT_A], col[RT_B], col[RT_N], col[RT_DMIN],
+                                col[RT_BITS], col[RT_CTYPE], col[RT_PLANES]};
+            hipLaunchKernelGGL(k_respair_reduce, dim3(nblocks(S.U, 4, 16384)), dim3(256), 0, c->stream, A);
         });
 }
 
@@ -4421,25 +4528,20 @@ int arp_residue_pairs_fetch(arp_ctx* c, int64_t cap, int32_t* res_a, int32_t* re
 
 // ---- residue contact persistence over the resident models (arp_respersist.h)
 int arp_models_residue_persistence_launch(arp_ctx* c, int64_t* count) {
-    int rbits = 0, fbits = 0;
+    PairModelKey G{};
     return make_table(c, RESPERSIST_TABLE, count,
         [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
-            const int64_t F = c->models_n, nres_t = std::max<int64_t>(c->nres / F, 1);      // (no residue at all: every record is left out)
-            rbits = id_bits(std::max<int64_t>(nres_t - 1, 1));
-            fbits = id_bits(std::max<int64_t>(F - 1, 1));
-            if (2 * rbits + fbits > 63) FAIL(c, ARP_E_CAPACITY, "arp_models_residue_persistence_launch: (residue, residue, model) does not fit a 63-bit key");
-            *K = TableKey{respersist_key_bits(nres_t, F, rbits, fbits, B.planes > 0), fbits};
-            enqueue_residue_rekey(c, B, nres_t, rbits, fbits, key, val);
+            CHK(pair_model_key(c, RESPERSIST_TABLE.launch(), true, "(residue, residue, model)", &G));
+            enqueue_residue_rekey(c, B, G, key, val, K);
             return ARP_OK;
         },
-        [&](const unsigned long long* key, const unsigned long long* val, const int* row_start, long long U, uint8_t* const* col) {
+        [&](const SortedRuns& S, const Columns& col) {
             RespersistArgs A{};
-            A.rbits = rbits; A.fbits = fbits; A.key = key; A.val = val; A.row_start = row_start; A.U = U;
-            A.t_a = (int*)col[ST_A]; A.t_b = (int*)col[ST_B]; A.t_nmodels = (uint16_t*)col[ST_NMODELS];
-            A.t_first = (int*)col[ST_FIRST]; A.t_last = (int*)col[ST_LAST]; A.t_n = (uint32_t*)col[ST_N];
-            A.t_cls = (uint16_t*)col[ST_CLS]; A.t_bits = (uint16_t*)col[ST_BITS]; A.t_dmin = (float*)col[ST_DMIN];
-            A.t_dmax = (float*)col[ST_DMAX]; A.t_dsum = (double*)col[ST_DSUM]; A.t_ctype = col[ST_CTYPE];
-            hipLaunchKernelGGL(k_respersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+            A.rbits = G.bits; A.fbits = G.fbits; A.key = S.key; A.val = S.val; A.row_start = S.R.row_start; A.U = S.U;
+            A.t_a = col[ST_A]; A.t_b = col[ST_B]; A.t_nmodels = col[ST_NMODELS]; A.t_first = col[ST_FIRST]; A.t_last = col[ST_LAST];
+            A.t_n = col[ST_N]; A.t_cls = col[ST_CLS]; A.t_bits = col[ST_BITS]; A.t_dmin = col[ST_DMIN]; A.t_dmax = col[ST_DMAX];
+            A.t_dsum = col[ST_DSUM]; A.t_ctype = col[ST_CTYPE];
+            hipLaunchKernelGGL(k_respersist_reduce, dim3(nblocks(S.U, 4, 16384)), dim3(256), 0, c->stream, A);
         });
 }
 
@@ -4451,23 +4553,22 @@ int arp_models_residue_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* res_a
 }
 
 // ---- the atom-atom records a caller asks for (arp_filter.h): filter the bag of the pass, sort the kept records alone
-// The host shape of the tables: count per tile and scan on the stream, ONE wait for k', size, enqueue the rest — the kept
-// records into columns of their own, their canonical order (radix_sort, as sort_contacts runs it) into the filtered slab.
-// sorted_slab, contacts_sorted and sorted_is_csr are not touched: an unfiltered fetch returns what it returned.
+// Kept records per tile, ONE wait for k', then the kept records into columns of their own and their canonical order
+// (radix_sort, as sort_contacts runs it) into the filtered slab.  sorted_slab, contacts_sorted and sorted_is_csr are not
+// touched: an unfiltered fetch returns what it returned.
 int arp_contacts_filter_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mask, int64_t* kept) {
     if (!c || !kept) return ARP_E_ARG;
-    const char* const fn = "arp_contacts_filter_launch: ";
-    if ((sift_any & ~ARP_FILTER_SIFT_ALL) || (ctype_mask & ~ARP_FILTER_CTYPE_ALL)) FAIL(c, ARP_E_ARG, std::string(fn) + "a mask has bits beyond the 15 SIFt bits / the 7 contact types");
-    if (!sift_any || !ctype_mask) FAIL(c, ARP_E_ARG, std::string(fn) + "a mask of 0 keeps nothing");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, std::string(fn) + "not for a shard of a distributed structure");
-    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, std::string(fn) + "no atom-contact results (call a launch first)");
+    const std::string fn = "arp_contacts_filter_launch: ";
+    CHK(check_masks(c, fn, {{sift_any, ARP_FILTER_SIFT_ALL}, {ctype_mask, ARP_FILTER_CTYPE_ALL}},
+                    "a mask has bits beyond the 15 SIFt bits / the 7 contact types", "a mask of 0 keeps nothing"));
+    CHK(launch_refusals(c, fn, NEED_WHOLE | NEED_AA_BAG, NO_AA_PASS));
     FilteredBag& F = c->filtered;
     const bool csr = c->packed_csr;
     if (F.valid && F.sift_any == sift_any && F.ctype_mask == ctype_mask && F.csr == csr) { *kept = F.count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     F.valid = false;
     const size_t k = (size_t)c->n_contacts;
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, std::string(fn) + "2^31 records or more (the digit table's prefixes are 32-bit)");
+    CHK(records_fit(c, fn, k, " (the digit table's prefixes are 32-bit)"));
     const size_t rows = (size_t)std::max<int64_t>(c->n, 0);
     // ---- kept records per tile, scanned; the host learns k' (the one wait)
     FilterArgs A{};
@@ -4476,19 +4577,11 @@ int arp_contacts_filter_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mas
     const int T = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
     long long kp = 0;
     if (k > 0) {
-        HIPCHK(c, c->table_tiles.reserve((size_t)T));
-        HIPCHK(c, c->table_total.reserve(1));
-        CHK(table_stage_reserve(c, 4096));
+        CHK(reserve_tile_counts(c, T));
         A.tile_keep = c->table_tiles.p;
-        RunArgs R{};
-        R.T = T; R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
         hipLaunchKernelGGL(k_filter_count, dim3(T), dim3(FILTER_THREADS), 0, c->stream, A);
-        hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
-        CHK(check_launch(c, "arp_contacts_filter_launch: count / scan"));
-        HIPCHK(c, hipMemcpyAsync(c->table_stage, c->table_total.p, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(&kp, c->table_stage, sizeof(kp));
-        if (kp < 0 || kp > (long long)k) FAIL(c, ARP_E_HIP, std::string(fn) + "kept count out of range");
+        CHK(wait_tile_total(c, T, &kp, fn + "count / scan"));
+        if (kp < 0 || kp > (long long)k) FAIL(c, ARP_E_HIP, fn + "kept count out of range");
     }
     // ---- the slab of the sorted result, with room for the ring / amide bags arp_fetch_packed_filtered packs behind it
     const PackedAtomBag S{"arp_contacts_filter_launch", (int64_t)kp, csr, &F};
@@ -4508,8 +4601,8 @@ int arp_contacts_filter_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mas
     size_t coff[5], cbytes;
     sorted_layout((size_t)kp, coff, &cbytes, (size_t)kp);
     HIPCHK(c, F.cols.reserve(cbytes));
-    A.i_out = (int*)(F.cols.p + coff[0]); A.j_out = (int*)(F.cols.p + coff[1]); A.d_out = (float*)(F.cols.p + coff[2]);
-    A.s_out = (uint16_t*)(F.cols.p + coff[3]); A.ct_out = F.cols.p + coff[4];
+    const Columns in{F.cols.p, coff}, out{F.slab.p, P.off};
+    A.i_out = in[0]; A.j_out = in[1]; A.d_out = in[2]; A.s_out = in[3]; A.ct_out = in[4];
     A.kept = kp;
     hipLaunchKernelGGL(k_filter_write, dim3(T), dim3(FILTER_THREADS), 0, c->stream, A);
     CHK(check_launch(c, "k_filter_write"));
@@ -4517,9 +4610,7 @@ int arp_contacts_filter_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mas
     const int64_t idmax = std::max<int64_t>(c->n - 1, 1);
     SortArgs Q{};
     Q.ci = A.i_out; Q.cj = A.j_out; Q.d_in = A.d_out; Q.s_in = A.s_out; Q.ct_in = A.ct_out;
-    uint8_t* slab = F.slab.p;
-    Q.i_out = (int*)(slab + P.off[0]); Q.j_out = (int*)(slab + P.off[1]); Q.d_out = (float*)(slab + P.off[2]);
-    Q.s_out = (uint16_t*)(slab + P.off[3]); Q.ct_out = slab + P.off[4];
+    Q.i_out = out[0]; Q.j_out = out[1]; Q.d_out = out[2]; Q.s_out = out[3]; Q.ct_out = out[4];
     Q.row_out = csr ? Q.i_out : nullptr;
     Q.nrows = (int)rows;
     const bool small = sw().sort_small && (size_t)kp <= (size_t)SORT_SMALL_MAX_RECORDS && idmax + 1 <= (int64_t)SORT_SMALL_MAX_BINS;
@@ -4538,66 +4629,37 @@ int arp_fetch_packed_filtered(arp_ctx* c, void* host, uint64_t host_bytes, int64
 }
 
 // ---- water-mediated contacts (arp_bridge.h): the atom-atom bag joined with itself on its water atoms
-// Two waits — L legs, then B rows — and arguments, so the sequence is its own and not make_table's; the steps are the tables':
-// reserve_key_sort / enqueue_key_sort, the run kernels, enqueue_run_starts, table_layout, and table_fetch for the fetch.  U,
-// the waters with a leg, is never read by the host: row_start is made for L runs (the most there can be) and the kernels take
-// U from table_total.  The bags, sorted_slab, contacts_sorted, sorted_is_csr, the filtered bag and the three tables are
-// neither read nor written.
-namespace {
-enum { WB_WATER = 0, WB_A, WB_B, WB_DIST_A, WB_DIST_B, WB_SIFT_A, WB_SIFT_B, WB_CTYPE_A, WB_CTYPE_B, WB_COLS };
-const TableSpec BRIDGE_TABLE = {"arp_water_bridges", &arp_ctx::bridges, WB_COLS, {4, 4, 4, 4, 4, 2, 2, 1, 1},
-                                false, false, "no atom-contact results (call a launch first)", 0};
-static_assert(WB_COLS <= TABLE_MAX_COLS, "TableSpec::es");
-static_assert(BRIDGE_F_WATER == ARP_F_WATER && BRIDGE_SAME_RESIDUE == ARP_WB_SAME_RESIDUE, "arp_bridge.h names the header's bits");
-// one 64-bit word from the device through the page-locked stage: a wait
-int read_word(arp_ctx* c, const long long* dev, long long* v) {
-    CHK(table_stage_reserve(c, 4096));
-    HIPCHK(c, hipMemcpyAsync(c->table_stage, dev, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    memcpy(v, c->table_stage, sizeof(*v));
-    return ARP_OK;
-}
-}  // namespace
-
+// Two waits — L legs, then B rows —: a shape of its own, from the shared steps.  U, the waters with a leg, is never read by the
+// host: row_start is made for L runs (the most there can be) and the kernels take U from table_total.  Of the results only the
+// atom-atom bag is read, and this table alone is written; remaking it voids what is made from it (void_results).
 int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
-    const std::string fn = "arp_water_bridges_launch: ";
-    if (sift_any & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_any has bits beyond the 15 SIFt bits");
-    if (!sift_any) FAIL(c, ARP_E_ARG, fn + "a sift_any of 0 makes no record a leg");
+    const TableSpec& spec = BRIDGE_TABLE;
+    const std::string fn = spec.launch();
+    CHK(check_leg_mask(c, fn, sift_any));
     if (flags & ~ARP_WB_SAME_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, fn + BRIDGE_TABLE.no_pass);
+    CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
     ResultTable& T = c->bridges;
-    if (T.valid && c->bridges_sift_any == sift_any && c->bridges_flags == flags) { *count = T.count; return ARP_OK; }
+    if (T.made_with(sift_any, flags)) { *count = T.count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     T.valid = false;
     T.count = 0;
-    c->bridgepersist.valid = false;      // (made from the table that is remade here)
+    void_results(c, RES_BRIDGES);
     const size_t k = (size_t)c->n_contacts;
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
-    const auto done = [&](long long rows) {
-        T.count = rows; T.valid = true;
-        c->bridges_sift_any = sift_any; c->bridges_flags = flags;
-        *count = rows;
-        return ARP_OK;
-    };
+    CHK(records_fit(c, fn, k));
+    const auto done = [&](long long rows) { return table_done(T, sift_any, flags, rows, count); };
     if (k == 0) return done(0);
     // ---- legs per tile, scanned; the host learns L (wait 1)
     BridgeLegArgs A{};
     A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
     A.k = (long long)k; A.flags = c->flags.p; A.sift_any = sift_any;
-    A.pbits = id_bits(std::max<int64_t>(c->n - 1, 1));      // (key = w << pbits | partner: at most 62 bits)
+    A.pbits = index_bits(c->n);      // (key = w << pbits | partner: at most 62 bits)
     const int tiles = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
-    HIPCHK(c, c->table_tiles.reserve((size_t)tiles));
-    HIPCHK(c, c->table_total.reserve(1));
+    CHK(reserve_tile_counts(c, tiles));
     A.tile_keep = c->table_tiles.p;
-    RunArgs R{};
-    R.T = tiles; R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
     hipLaunchKernelGGL(k_bridge_legs_count, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
-    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
-    CHK(check_launch(c, (fn + "legs count / scan").c_str()));
     long long L = 0;
-    CHK(read_word(c, c->table_total.p, &L));
+    CHK(wait_tile_total(c, tiles, &L, fn + "legs count / scan"));
     if (L < 0 || L > (long long)k) FAIL(c, ARP_E_HIP, fn + "leg count out of range");
     if (L == 0) return done(0);
     // ---- the legs keyed by (water, partner), sorted by every bit: a water's legs become one run, partners ascending
@@ -4608,12 +4670,9 @@ int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int6
     int sorted = 0;
     enqueue_key_sort(c, s, (size_t)L, 2 * A.pbits, &sorted);
     // ---- the runs: at most L of them, so their starts are made for L and U stays on the device (no wait of its own)
-    R = RunArgs{};
+    RunArgs R{};
     R.key = s.key[sorted].p; R.k = L; R.shift = A.pbits;
-    R.T = (int)((L + RUNS_TILE - 1) / RUNS_TILE);      // (<= tiles: table_tiles is large enough, and the legs' prefixes are consumed in stream order)
-    R.tile_rows = c->table_tiles.p; R.total = c->table_total.p;
-    hipLaunchKernelGGL(k_runs_count, dim3(R.T), dim3(RUNS_THREADS), 0, c->stream, R);
-    hipLaunchKernelGGL(k_runs_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, R);
+    enqueue_run_count(c, R);      // (R.T <= tiles: table_tiles is large enough, and the legs' prefixes are consumed in stream order)
     CHK(enqueue_run_starts(c, R, L));
     // ---- kept pairs per run, scanned in 64 bits; the host learns B (wait 2)
     HIPCHK(c, c->bridge_off.reserve((size_t)L + 1));
@@ -4626,22 +4685,18 @@ int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int6
     if (!(flags & ARP_WB_SAME_RESIDUE)) hipLaunchKernelGGL(k_bridge_leg_res, dim3(nblocks(L, 256, 2048)), dim3(256), 0, c->stream, P);
     hipLaunchKernelGGL(k_bridge_pairs<false>, dim3(pair_blocks), dim3(256), 0, c->stream, P);
     hipLaunchKernelGGL(k_bridge_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, P);
-    CHK(check_launch(c, (fn + "sort / pairs count").c_str()));
     long long B = 0;
-    CHK(read_word(c, c->bridge_off.p + L, &B));
+    CHK(wait_count(c, c->bridge_off.p + L, &B, fn + "sort / pairs count"));
     if (B < 0) FAIL(c, ARP_E_HIP, fn + "row count out of range");
     if (B >= (1ll << 31)) { *count = B; FAIL(c, ARP_E_CAPACITY, fn + "2^31 rows or more"); }
     if (B == 0) return done(0);
     // ---- the rows, each at its rank
-    size_t off[TABLE_MAX_COLS], bytes;
-    table_layout(BRIDGE_TABLE, (size_t)B, off, &bytes);
-    HIPCHK(c, T.slab.reserve(bytes));
-    uint8_t* const slab = T.slab.p;
+    const TableLayout lay = table_layout(spec, (size_t)B);
+    HIPCHK(c, T.slab.reserve(lay.bytes));
+    const Columns col{T.slab.p, lay.off};
     P.rows = B;
-    P.t_w = (int*)(slab + off[WB_WATER]); P.t_a = (int*)(slab + off[WB_A]); P.t_b = (int*)(slab + off[WB_B]);
-    P.t_da = (float*)(slab + off[WB_DIST_A]); P.t_db = (float*)(slab + off[WB_DIST_B]);
-    P.t_sa = (uint16_t*)(slab + off[WB_SIFT_A]); P.t_sb = (uint16_t*)(slab + off[WB_SIFT_B]);
-    P.t_ca = slab + off[WB_CTYPE_A]; P.t_cb = slab + off[WB_CTYPE_B];
+    P.t_w = col[WB_WATER]; P.t_a = col[WB_A]; P.t_b = col[WB_B]; P.t_da = col[WB_DIST_A]; P.t_db = col[WB_DIST_B];
+    P.t_sa = col[WB_SIFT_A]; P.t_sb = col[WB_SIFT_B]; P.t_ca = col[WB_CTYPE_A]; P.t_cb = col[WB_CTYPE_B];
     hipLaunchKernelGGL(k_bridge_pairs<true>, dim3(pair_blocks), dim3(256), 0, c->stream, P);
     CHK(check_launch(c, (fn + "pairs write").c_str()));
     return done(B);
@@ -4654,92 +4709,50 @@ int arp_water_bridges_fetch(arp_ctx* c, int64_t cap, int32_t* water, int32_t* a,
 }
 
 // ---- water-bridge persistence over the resident models (arp_bridgepersist.h): the bridge table folded per pair
-// The records are the rows of the bridge table, not the bags of make_table, and the launch has arguments: the sequence is
-// written out as arp_water_bridges_launch writes its own, from the tables' steps.  Three waits: the bridge launch's two (none
-// when that table is resident) and U.  Only the bridge table is read; nothing but this table and the shared scratch is written.
-namespace {
-enum { WP_A = 0, WP_B, WP_NMODELS, WP_FIRST, WP_LAST, WP_NWATERS, WP_NBRIDGES, WP_DMIN, WP_DMAX, WP_DSUM, WP_BITS_A, WP_BITS_B,
-       WP_CTYPE_A, WP_CTYPE_B, WP_COLS };
-const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &arp_ctx::bridgepersist, WP_COLS,
-                                       {4, 4, 2, 4, 4, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 2 * TABLE_SIFT_BITS, 1, 1},
-                                       true, false, "no atom-contact results of a pass over the resident models (call a launch first)", 0};
-static_assert(WP_COLS <= TABLE_MAX_COLS, "TableSpec::es");
-static_assert(BRIDGEPERSIST_BY_RESIDUE == ARP_WBP_BY_RESIDUE && TABLE_SIFT_BITS == ARP_WBP_BITS, "arp_bridgepersist.h names the header's bits");
-}  // namespace
-
+// A table whose records are the rows of the bridge table: the bridge launch's waits (none when that table is resident) and
+// U.  Only the bridge table is read; nothing but this table and the shared scratch is written.
 int arp_models_water_bridge_persistence_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
-    const std::string fn = "arp_models_water_bridge_persistence_launch: ";
-    if (sift_any & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_any has bits beyond the 15 SIFt bits");
-    if (!sift_any) FAIL(c, ARP_E_ARG, fn + "a sift_any of 0 makes no record a leg");
+    const TableSpec& spec = BRIDGEPERSIST_TABLE;
+    const std::string fn = spec.launch();
+    CHK(check_leg_mask(c, fn, sift_any));
     if (flags & ~(ARP_WB_SAME_RESIDUE | ARP_WBP_BY_RESIDUE)) FAIL(c, ARP_E_ARG, fn + "unknown flag");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
-    if (c->models_n > 65535) FAIL(c, ARP_E_ARG, fn + "more than 65 535 models (the table counts models in uint16)");
-    if (c->pass_pending || !c->contacts_valid) FAIL(c, ARP_E_ARG, fn + BRIDGEPERSIST_TABLE.no_pass);
+    CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
     const uint32_t wb_flags = flags & ARP_WB_SAME_RESIDUE;
     ResultTable& T = c->bridgepersist;
-    if (T.valid && c->bridges.valid && c->bridges_sift_any == sift_any && c->bridges_flags == wb_flags && c->bridgepersist_flags == flags) {
-        *count = T.count;
-        return ARP_OK;
-    }
-    const bool by_res = (flags & ARP_WBP_BY_RESIDUE) != 0;
-    const int64_t F = c->models_n, n = c->topo_hdr.n, nres_t = std::max<int64_t>(c->nres / F, 1);
-    const int bits = id_bits(std::max<int64_t>((by_res ? nres_t : n) - 1, 1)), fbits = id_bits(std::max<int64_t>(F - 1, 1));
-    if (2 * bits + fbits > 63) FAIL(c, ARP_E_CAPACITY, fn + "(pair, model) does not fit a 63-bit key");
+    if (T.made_with(sift_any, flags) && c->bridges.made_with(sift_any, wb_flags)) { *count = T.count; return ARP_OK; }
+    PairModelKey G{};
+    CHK(pair_model_key(c, fn, (flags & ARP_WBP_BY_RESIDUE) != 0, "(pair, model)", &G));
     // ---- the bridge table: made here unless the same one is resident; its own refusals and errors pass through
     T.valid = false;
     T.count = 0;
     int64_t B = 0;
     const int rc = arp_water_bridges_launch(c, sift_any, wb_flags, &B);
     if (rc != ARP_OK) { *count = B; return rc; }
-    const auto done = [&](long long rows) {
-        T.count = rows; T.valid = true;
-        c->bridgepersist_flags = flags;
-        *count = rows;
-        return ARP_OK;
-    };
-    if (B == 0 || n <= 0) return done(0);
+    if (B == 0 || G.n <= 0) return table_done(T, sift_any, flags, 0, count);
     HIPCHK(c, hipSetDevice(c->device));
-    // ---- its rows keyed by (pair, model), sorted by every bit: least significant digit first, stable
-    size_t boff[TABLE_MAX_COLS], bbytes;
-    table_layout(BRIDGE_TABLE, (size_t)B, boff, &bbytes);
-    const uint8_t* const bs = c->bridges.slab.p;
-    SortScratch& s = c->table_sort;
-    CHK(reserve_key_sort(c, s, (size_t)B, (size_t)B));
     BridgepersistArgs A{};
-    A.bits = bits; A.fbits = fbits; A.n = (uint32_t)n; A.nres_t = (uint32_t)nres_t; A.flags = flags;
-    A.b_w = (const int*)(bs + boff[WB_WATER]); A.b_a = (const int*)(bs + boff[WB_A]); A.b_b = (const int*)(bs + boff[WB_B]);
-    A.b_da = (const float*)(bs + boff[WB_DIST_A]); A.b_db = (const float*)(bs + boff[WB_DIST_B]);
-    A.b_sa = (const uint16_t*)(bs + boff[WB_SIFT_A]); A.b_sb = (const uint16_t*)(bs + boff[WB_SIFT_B]);
-    A.b_ca = bs + boff[WB_CTYPE_A]; A.b_cb = bs + boff[WB_CTYPE_B];
-    A.rows = B; A.res_id = c->res_id.p;
-    A.key = s.key[0].p; A.val = s.val[0].p;
-    hipLaunchKernelGGL(k_bridgepersist_rekey, dim3(nblocks(B, 256, 2048)), dim3(256), 0, c->stream, A);
-    int sorted = 0;
-    enqueue_key_sort(c, s, (size_t)B, 2 * bits + fbits, &sorted);
-    // ---- rows: count, scan; the host learns U (the wait of this table)
-    RunArgs R{};
-    R.key = s.key[sorted].p; R.k = B; R.shift = fbits;
-    long long U = 0;
-    CHK(count_runs(c, R, &U, fn + "sort / count"));
-    if (U < 1 || U > B) FAIL(c, ARP_E_HIP, fn + "row count out of range");
-    // ---- the table: row starts, one wave per row
-    size_t off[TABLE_MAX_COLS], bytes;
-    table_layout(BRIDGEPERSIST_TABLE, (size_t)U, off, &bytes);
-    HIPCHK(c, T.slab.reserve(bytes));
-    CHK(enqueue_run_starts(c, R, U));
-    uint8_t* const slab = T.slab.p;
-    A.key = s.key[sorted].p; A.val = s.val[sorted].p; A.row_start = R.row_start; A.U = U;
-    A.t_a = (int*)(slab + off[WP_A]); A.t_b = (int*)(slab + off[WP_B]); A.t_nmodels = (uint16_t*)(slab + off[WP_NMODELS]);
-    A.t_first = (int*)(slab + off[WP_FIRST]); A.t_last = (int*)(slab + off[WP_LAST]);
-    A.t_nwaters = (uint32_t*)(slab + off[WP_NWATERS]); A.t_nbridges = (uint32_t*)(slab + off[WP_NBRIDGES]);
-    A.t_dmin = (float*)(slab + off[WP_DMIN]); A.t_dmax = (float*)(slab + off[WP_DMAX]); A.t_dsum = (double*)(slab + off[WP_DSUM]);
-    A.t_bits_a = (uint16_t*)(slab + off[WP_BITS_A]); A.t_bits_b = (uint16_t*)(slab + off[WP_BITS_B]);
-    A.t_ctype_a = slab + off[WP_CTYPE_A]; A.t_ctype_b = slab + off[WP_CTYPE_B];
-    hipLaunchKernelGGL(k_bridgepersist_reduce, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
-    CHK(check_launch(c, (fn + "reduce").c_str()));
-    return done(U);
+    return table_from_records(c, spec, sift_any, flags, (size_t)B, (size_t)B, count,
+        [&](unsigned long long* key, unsigned long long* val, TableKey* K) -> int {      // its rows keyed by (pair, model)
+            const TableLayout lay = table_layout(BRIDGE_TABLE, (size_t)B);
+            const Columns b{c->bridges.slab.p, lay.off};
+            A.bits = G.bits; A.fbits = G.fbits; A.n = (uint32_t)G.n; A.nres_t = (uint32_t)G.nres_t; A.flags = flags;
+            A.b_w = b[WB_WATER]; A.b_a = b[WB_A]; A.b_b = b[WB_B]; A.b_da = b[WB_DIST_A]; A.b_db = b[WB_DIST_B];
+            A.b_sa = b[WB_SIFT_A]; A.b_sb = b[WB_SIFT_B]; A.b_ca = b[WB_CTYPE_A]; A.b_cb = b[WB_CTYPE_B];
+            A.rows = B; A.res_id = c->res_id.p;
+            A.key = key; A.val = val;
+            *K = TableKey{G.total(), G.fbits};
+            hipLaunchKernelGGL(k_bridgepersist_rekey, dim3(nblocks(B, 256, 2048)), dim3(256), 0, c->stream, A);
+            return ARP_OK;
+        },
+        [&](const SortedRuns& S, const Columns& col) {
+            A.key = (unsigned long long*)S.key; A.val = (unsigned long long*)S.val; A.row_start = S.R.row_start; A.U = S.U;
+            A.t_a = col[WP_A]; A.t_b = col[WP_B]; A.t_nmodels = col[WP_NMODELS]; A.t_first = col[WP_FIRST]; A.t_last = col[WP_LAST];
+            A.t_nwaters = col[WP_NWATERS]; A.t_nbridges = col[WP_NBRIDGES]; A.t_dmin = col[WP_DMIN]; A.t_dmax = col[WP_DMAX];
+            A.t_dsum = col[WP_DSUM]; A.t_bits_a = col[WP_BITS_A]; A.t_bits_b = col[WP_BITS_B]; A.t_ctype_a = col[WP_CTYPE_A];
+            A.t_ctype_b = col[WP_CTYPE_B];
+            hipLaunchKernelGGL(k_bridgepersist_reduce, dim3(nblocks(S.U, 4, 16384)), dim3(256), 0, c->stream, A);
+        });
 }
 
 int arp_models_water_bridge_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
@@ -4752,13 +4765,10 @@ int arp_models_water_bridge_persistence_fetch(arp_ctx* c, int64_t cap, int32_t* 
 }
 
 // ---- fingerprint similarity between the resident models (arp_similarity.h): inter = B B^T of a bit matrix
-// The result is F x F, not U rows of columns, and the launch has arguments: the sequence is written out from the tables'
-// steps, as arp_water_bridges_launch writes its own.  One wait (U).  The rows are those of the persistence table (atom level:
-// k_persist_rekey) or of the residue persistence table (residue level: enqueue_residue_rekey), found by the same sort and run
-// kernels.  Only the bags are read; nothing but the matrix, its bit matrix and the shared scratch is written.
-static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESIDUE && SIM_PLANES == TABLE_SIFT_BITS + RESPERSIST_CLASSES,
-              "arp_similarity.h names the header's planes");
-
+// The result is F x F, not U rows of columns: sort_to_runs finds the rows — those of the persistence table (atom level) or of
+// the residue persistence table (residue level), by their re-key steps —, and the bit matrix, the slicing and the product are
+// this launch's own.  One wait (U).  Only the bags are read; nothing but the matrix, its bit matrix and the shared scratch is
+// written.
 int arp_models_similarity_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t* n_models, int64_t* n_rows) {
     if (!c || !n_models || !n_rows) return ARP_E_ARG;
     const std::string fn = "arp_models_similarity_launch: ";
@@ -4769,22 +4779,19 @@ int arp_models_similarity_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mas
     if (!by_res && (planes >> (TABLE_SIFT_BITS + 1))) FAIL(c, ARP_E_ARG, fn + "planes 16 ... 19 (the ring / amide classes) exist at residue level only");
     if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
     if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no atom-atom record");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (c->models_n <= 0) FAIL(c, ARP_E_ARG, fn + "no models resident (arp_set_models)");
+    CHK(launch_refusals(c, fn, NEED_WHOLE | NEED_MODELS, nullptr));
     const int64_t F = c->models_n;
     *n_models = F;
     if (F > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "more than 4096 models (the matrix and its page-locked stage would pass 64 MiB)");
-    if (by_res ? !five_bags_complete(c) : (c->pass_pending || !c->contacts_valid))
-        FAIL(c, ARP_E_ARG, fn + (by_res ? RESPERSIST_TABLE.no_pass : PERSIST_TABLE.no_pass));
+    CHK(launch_refusals(c, fn, by_res ? NEED_FIVE_BAGS : NEED_AA_BAG, (by_res ? RESPERSIST_TABLE : PERSIST_TABLE).no_pass));
     SimilarityResult& S = c->similarity;
     if (S.valid && S.F == F && S.planes == planes && S.ctype_mask == ctype_mask && S.flags == flags) { *n_rows = S.rows; return ARP_OK; }
     S.valid = false;
     const FiveBags B = five_bags(c, by_res);
     const size_t k = B.k;
-    if (k >= ((size_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more");
-    const int64_t n = c->topo_hdr.n, nres_t = std::max<int64_t>(c->nres / F, 1);
-    const int bits = id_bits(std::max<int64_t>((by_res ? nres_t : n) - 1, 1)), fbits = id_bits(std::max<int64_t>(F - 1, 1));
-    if (2 * bits + fbits > 63) FAIL(c, ARP_E_CAPACITY, fn + "(pair, model) does not fit a 63-bit key");
+    CHK(records_fit(c, fn, k));
+    PairModelKey G{};
+    CHK(pair_model_key(c, fn, by_res, "(pair, model)", &G));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, S.inter.reserve((size_t)(F * F)));
     const auto done = [&](long long rows, long long words, long long slices) {
@@ -4795,30 +4802,15 @@ int arp_models_similarity_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mas
         *n_rows = rows;
         return ARP_OK;
     };
-    long long U = 0;
-    SortScratch& s = c->table_sort;
-    RunArgs R{};
-    int sorted = 0;
-    if (k > 0) {
-        // ---- the records keyed by (pair, model), sorted by every bit: least significant digit first
-        CHK(reserve_key_sort(c, s, k, B.cap));
-        int keybits = 2 * bits + fbits;
-        if (by_res) {
-            keybits = respersist_key_bits(nres_t, F, bits, fbits, B.planes > 0);
-            enqueue_residue_rekey(c, B, nres_t, bits, fbits, s.key[0].p, s.val[0].p);
-        } else {
-            PersistArgs P{};
-            P.ci = c->out_i.p; P.cj = c->out_j.p; P.d_in = c->out_d.p; P.s_in = c->out_s.p; P.ct_in = c->out_ct.p;
-            P.k = (long long)k; P.n = (uint32_t)n; P.bbits = bits; P.fbits = fbits;
-            P.key = s.key[0].p; P.val = s.val[0].p;
-            hipLaunchKernelGGL(k_persist_rekey, dim3(nblocks((int64_t)k, 256, 2048)), dim3(256), 0, c->stream, P);
-        }
-        enqueue_key_sort(c, s, k, keybits, &sorted);
-        // ---- rows: count, scan; the host learns U (the one wait)
-        R.key = s.key[sorted].p; R.k = (long long)k; R.shift = fbits;
-        CHK(count_runs(c, R, &U, fn + "sort / count"));
-        if (U < (by_res ? 0 : 1) || U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
-    }
+    // ---- the records keyed by (pair, model), sorted by every bit; the host learns U (the one wait)
+    SortedRuns Q{};
+    if (k > 0)
+        CHK(sort_to_runs(c, fn, k, B.cap, by_res ? 0 : 1, [&](unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+            if (by_res) enqueue_residue_rekey(c, B, G, key, val, K);
+            else (void)enqueue_persist_rekey(c, G, k, key, val, K);
+            return ARP_OK;
+        }, &Q));
+    const long long U = Q.U;
     if (U == 0) {      // no record with a row: no feature in any model
         HIPCHK(c, hipMemsetAsync(S.inter.p, 0, (size_t)(F * F) * sizeof(uint32_t), c->stream));
         return done(0, 0, 0);
@@ -4829,10 +4821,10 @@ int arp_models_similarity_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mas
     if (F * W >= (1ll << 29)) FAIL(c, ARP_E_CAPACITY, fn + "a bit matrix of 4 GiB or more");
     HIPCHK(c, S.bits.reserve((size_t)(F * W)));
     HIPCHK(c, hipMemsetAsync(S.bits.p, 0, (size_t)(F * W) * sizeof(unsigned long long), c->stream));
-    CHK(enqueue_run_starts(c, R, U));
+    CHK(enqueue_run_starts(c, Q.R, U));
     SimArgs A{};
-    A.key = R.key; A.val = s.val[sorted].p; A.row_start = R.row_start; A.U = U;
-    A.fbits = fbits; A.planes = planes; A.ctype_mask = ctype_mask; A.F = (uint32_t)F;
+    A.key = Q.key; A.val = Q.val; A.row_start = Q.R.row_start; A.U = U;
+    A.fbits = G.fbits; A.planes = planes; A.ctype_mask = ctype_mask; A.F = (uint32_t)F;
     A.bits = S.bits.p; A.wpp = wpp; A.W = W;
     hipLaunchKernelGGL(k_sim_bits, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
     // ---- inter = B B^T: the tile pairs of the upper triangle times as many word slices as fill the device (F = 8 is one
@@ -4856,9 +4848,7 @@ int arp_models_similarity_fetch(arp_ctx* c, int64_t cap_models, uint32_t* inter,
     if (!inter) FAIL(c, ARP_E_ARG, "arp_models_similarity_fetch: output missing");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)(S.F * S.F) * sizeof(uint32_t);
-    CHK(table_stage_reserve(c, bytes));
-    HIPCHK(c, hipMemcpyAsync(c->table_stage, S.inter.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(stage_copy(c, S.inter.p, bytes));
     memcpy(inter, c->table_stage, bytes);
     return ARP_OK;
 }
@@ -5050,7 +5040,7 @@ int arp_set_sort_after_pass(arp_ctx* c, int enabled) {
 
 int arp_set_packed_layout(arp_ctx* c, int layout) {
     if (!c || (layout != ARP_LAYOUT_RECORDS && layout != ARP_LAYOUT_ROWS)) return ARP_E_ARG;
-    if (c->packed_csr != (layout == ARP_LAYOUT_ROWS)) c->filtered.valid = false;
+    if (c->packed_csr != (layout == ARP_LAYOUT_ROWS)) void_results(c, RES_LAYOUT);
     c->packed_csr = layout == ARP_LAYOUT_ROWS;
     return ARP_OK;
 }

@@ -1,5 +1,6 @@
 """What the device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
-(``residue_pairs``), residue persistence (``residue_persistence``) and water-bridge persistence (``bridge_persistence``).
+(``residue_pairs``), residue persistence (``residue_persistence``), the water bridges (``water_bridges``) and water-bridge
+persistence (``bridge_persistence``).
 
 A table is a dict of NumPy columns with one row per pair.  A ``Spec`` names the columns in the order of the C fetch's
 arguments (include/arpeggio_hip.h) with their types, and the width of those that hold several values a row.  Everything here
@@ -31,6 +32,8 @@ RESPERSIST = Spec((('res_a', np.int32), ('res_b', np.int32), ('n_models', np.uin
                    ('n_contacts', np.uint32), ('class_models', np.uint16), ('bit_models', np.uint16), ('dist_min', np.float32),
                    ('dist_max', np.float32), ('dist_sum', np.float64), ('ctype_mask', np.uint8)),
                   {'class_models': len(CLASSES), 'bit_models': N_BITS})
+BRIDGES = Spec((('water', np.int32), ('a', np.int32), ('b', np.int32), ('dist_a', np.float32), ('dist_b', np.float32),
+                ('sift_a', np.uint16), ('sift_b', np.uint16), ('ctype_a', np.uint8), ('ctype_b', np.uint8)), {})
 
 
 def _bridgepersist(ka, kb):

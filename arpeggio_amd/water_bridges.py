@@ -23,10 +23,10 @@ import os
 
 import numpy as np
 
+from . import tables
 from .core import config
 
-COLUMNS = (('water', np.int32), ('a', np.int32), ('b', np.int32), ('dist_a', np.float32), ('dist_b', np.float32),
-           ('sift_a', np.uint16), ('sift_b', np.uint16), ('ctype_a', np.uint8), ('ctype_b', np.uint8))
+COLUMNS = tables.BRIDGES.columns
 SIFT_ALL = (1 << len(config.SIFT_NAMES)) - 1
 SAME_RESIDUE = 1                     # ARP_WB_SAME_RESIDUE
 DEFAULT_CONTACTS = ('hbond', 'polar')
