@@ -45,6 +45,7 @@ SYMBOLS = (
     'arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch',
     'arp_batch_layout',
     'arp_models_similarity_launch', 'arp_models_similarity_fetch', 'arp_models_similarity_info',
+    'arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', 'arp_models_lifetimes_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -53,6 +54,7 @@ WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
 CTYPE_ALL = 0x7F                 # ARP_FILTER_CTYPE_ALL
+LIFETIMES_MAX_GAP = 65534        # ARP_LIFETIMES_MAX_GAP
 PERSIST_COLUMNS, RESPAIR_COLUMNS, RESPERSIST_COLUMNS = tables.PERSIST.columns, tables.RESPAIR.columns, tables.RESPERSIST.columns
 
 _lib = None
@@ -211,6 +213,9 @@ def load():
     L.arp_models_similarity_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64), C.POINTER(i64)]
     L.arp_models_similarity_fetch.argtypes = [vp, i64, vp, C.POINTER(i64)]
     L.arp_models_similarity_info.argtypes = [vp, vp]
+    L.arp_models_lifetimes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.arp_models_lifetimes_fetch.argtypes = [vp, i64] + [vp] * 11 + [C.POINTER(i64)]
+    L.arp_models_lifetimes_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -796,6 +801,17 @@ class Context:
         self._check(self._L.arp_models_similarity_fetch(self._h, n, _p(inter), C.byref(F)), 'arp_models_similarity_fetch')
         return inter
 
+    def models_lifetimes(self, gap=0, sift_any=0x7FFF, ctype_mask=CTYPE_ALL):
+        """Contact lifetimes over the resident models of the last pass, reduced on the device (arp_models_lifetimes_*): per
+        topology pair (a, b) with a participating record — ``(sift & sift_any) != 0`` and bit ``ctype`` of ``ctype_mask`` set —
+        the intervals of its presence along the model axis, ``gap`` models of absence tolerated inside one; rows in ascending
+        (a, b).  Returns a dict of the eleven columns ``tables.LIFETIMES`` (see ``arpeggio_amd.lifetimes``).  Only the table is
+        copied to the host; the bags of the pass and every other result stay fetchable as before.  A repeated call with the
+        same arguments on the same results fetches the resident table (``stats()['lifetimes_launches']`` counts the launches
+        that made one)."""
+        return self._table('arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', tables.LIFETIMES, int(gap), int(sift_any),
+                           int(ctype_mask))
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
@@ -1263,9 +1279,12 @@ class Context:
         self._check(self._L.arp_get_stats(self._h, _p(s)), 'arp_get_stats')
         m = np.zeros(4, np.int64)
         self._check(self._L.arp_models_similarity_info(self._h, _p(m)), 'arp_models_similarity_info')
+        lt = np.zeros(2, np.int64)
+        self._check(self._L.arp_models_lifetimes_info(self._h, _p(lt)), 'arp_models_lifetimes_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
-                    sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]))
+                    sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
+                    lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]))
 
     def set_profiling(self, on=True):
         self._check(self._L.arp_set_profiling(self._h, int(on)), 'arp_set_profiling')

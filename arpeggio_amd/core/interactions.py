@@ -639,6 +639,9 @@ class EnsembleComplex:
         self._bridge_persistence_key = None
         self.similarity = None           # the matrix of run_similarity (uint32 [F, F]) and the rows it was made over
         self.similarity_rows = 0
+        self.lifetimes = None            # the table of run_lifetimes, the models it covers and (gap, sift_any, ctype_mask)
+        self.lifetimes_models = 0
+        self._lifetimes_key = None
 
     @property
     def n_models(self):
@@ -876,6 +879,44 @@ class EnsembleComplex:
         if self.similarity is None:
             raise AttributeError('write_similarity: run_similarity first')
         return _sim.write_similarity(wd, self.id, self.similarity)
+
+    def run_lifetimes(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, gap=0, contacts=None,
+                      interacting_entities=None, accumulate=False):
+        """Extension beside the mirror: contact lifetimes over the models — how long a contact lasts along the ordered axis of
+        the models (for a trajectory streamed through ``set_coordinates``, model f is time) and how often it forms and breaks:
+        the selection handling and the pass of ``run_persistence``, then the atom-atom records of all models reduced ON THE
+        DEVICE to one row per topology pair with its intervals of presence (``arpeggio_amd.lifetimes`` describes the table) —
+        and only that table fetched, into ``self.lifetimes`` (also returned).  ``gap``: models of absence tolerated inside an
+        interval; ``contacts`` / ``interacting_entities`` name the records that take part (``contact_filter.masks``; ``None``
+        = all).  No bag is copied to the host: ``model(k)`` has no results after this call.  ``accumulate=True`` merges the
+        table EXACTLY into that of the calls before it, this call's models following theirs (``self.lifetimes_models`` counts
+        them); ``ValueError`` when ``gap`` or the masks differ from those of the accumulated table."""
+        from .. import contact_filter, lifetimes as _lt
+        key = (_lt.check_gap(gap),) + contact_filter.masks(contacts, interacting_entities)
+        merging = accumulate and self.lifetimes is not None
+        if merging and key != self._lifetimes_key:
+            raise ValueError('run_lifetimes: accumulate=True with another gap, other contacts or interacting entities than the '
+                             'accumulated table was made with')
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        t = self._ctx.models_lifetimes(*key)
+        self._results = None
+        if merging:
+            self.lifetimes = _lt.merge(self.lifetimes, t, self.lifetimes_models, key[0])
+            self.lifetimes_models += self.n_models
+        else:
+            self.lifetimes, self.lifetimes_models, self._lifetimes_key = t, self.n_models, key
+        self.stats = self._ctx.stats()
+        return self.lifetimes
+
+    def write_lifetimes(self, wd):
+        """'<id>.lifetimes' in ``wd``: the table of ``run_lifetimes`` as CSV."""
+        from .. import lifetimes as _lt
+        if self.lifetimes is None:
+            raise AttributeError('write_lifetimes: run_lifetimes first')
+        return _lt.write_lifetimes(wd, self.id, self.lifetimes, self.pc, self.lifetimes_models, self.component_types)
 
     def run_arpeggio(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent):
         """I:329-347 on every model: the selectors are parsed once on the topology and select the same atoms in each model."""

@@ -35,6 +35,7 @@
 #include "arp_bridge.h"
 #include "arp_bridgepersist.h"
 #include "arp_similarity.h"
+#include "arp_lifetimes.h"
 #include "arp_blob.h"
 
 namespace {
@@ -249,10 +250,10 @@ struct HintKey {
 }  // namespace
 
 // a table reduced on the device: its columns in one piece (table_layout), its rows, whether it is that of the last results, and
-// the arguments of the launch that made it (0 for a launch without)
+// the arguments of the launch that made it (0 for a launch without); launches counts the launches that made it anew
 struct ResultTable {
     DevBuf<uint8_t> slab;
-    int64_t count = 0;
+    int64_t count = 0, launches = 0;
     uint32_t arg[2] = {0, 0};
     bool valid = false;
     bool made_with(uint32_t arg0, uint32_t arg1) const { return valid && arg[0] == arg0 && arg[1] == arg1; }
@@ -509,6 +510,7 @@ struct arp_ctx {
     DevBuf<long long> bridge_off;         // [L + 1] kept pairs per water run, then their exclusive prefix; [L] = rows
     DevBuf<int> bridge_res;               // [L] residue of every sorted leg's partner
     SimilarityResult similarity;          // arp_models_similarity_launch
+    ResultTable lifetimes;                // arp_models_lifetimes_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -696,6 +698,7 @@ void void_results(arp_ctx* c, unsigned lost) {
     const unsigned bags = RES_AA | RES_PLANES;
     const struct { bool* valid; unsigned reads, makes; } results[] = {
         {&c->persist.valid, RES_AA, 0},
+        {&c->lifetimes.valid, RES_AA, 0},
         {&c->bridges.valid, RES_AA, RES_BRIDGES},
         {&c->bridgepersist.valid, RES_BRIDGES, 0},
         {&c->respair.valid, bags, 0},
@@ -4168,6 +4171,7 @@ enum { ST_A = 0, ST_B, ST_NMODELS, ST_FIRST, ST_LAST, ST_N, ST_CLS, ST_BITS, ST_
 enum { WB_WATER = 0, WB_A, WB_B, WB_DIST_A, WB_DIST_B, WB_SIFT_A, WB_SIFT_B, WB_CTYPE_A, WB_CTYPE_B, WB_COLS };
 enum { WP_A = 0, WP_B, WP_NMODELS, WP_FIRST, WP_LAST, WP_NWATERS, WP_NBRIDGES, WP_DMIN, WP_DMAX, WP_DSUM, WP_BITS_A, WP_BITS_B,
        WP_CTYPE_A, WP_CTYPE_B, WP_COLS };
+enum { LT_A = 0, LT_B, LT_NMODELS, LT_FIRST, LT_LAST, LT_NINTERVALS, LT_LONGEST, LT_LONGEST_START, LT_HEAD, LT_TAIL, LT_SPAN_SUM, LT_COLS };
 const unsigned OVER_MODELS = NEED_WHOLE | NEED_MODELS | NEED_MODELS_U16;
 const TableSpec PERSIST_TABLE = {"arp_models_persistence", &arp_ctx::persist, PT_COLS, {4, 4, 2, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 1},
                                  OVER_MODELS | NEED_AA_BAG, "no results of a pass over the resident models (launch one first)", 1};
@@ -4180,8 +4184,12 @@ const TableSpec BRIDGE_TABLE = {"arp_water_bridges", &arp_ctx::bridges, WB_COLS,
 const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &arp_ctx::bridgepersist, WP_COLS,
                                        {4, 4, 2, 4, 4, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 2 * TABLE_SIFT_BITS, 1, 1}, OVER_MODELS | NEED_AA_BAG,
                                        "no atom-contact results of a pass over the resident models (call a launch first)", 1};
+// (fewest rows 0: the masks of a launch may leave every record out)
+const TableSpec LIFETIMES_TABLE = {"arp_models_lifetimes", &arp_ctx::lifetimes, LT_COLS, {4, 4, 2, 4, 4, 2, 2, 4, 2, 2, 4},
+                                   OVER_MODELS | NEED_AA_BAG, PERSIST_TABLE.no_pass, 0};
 static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS && WB_COLS <= TABLE_MAX_COLS &&
-              WP_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+              WP_COLS <= TABLE_MAX_COLS && LT_COLS <= TABLE_MAX_COLS, "TableSpec::es");
+static_assert(ARP_LIFETIMES_MAX_GAP + 1u <= 0xFFFFu, "gap + 1 is compared with differences of models counted in uint16");
 static_assert(BRIDGE_F_WATER == ARP_F_WATER && BRIDGE_SAME_RESIDUE == ARP_WB_SAME_RESIDUE, "arp_bridge.h names the header's bits");
 static_assert(BRIDGEPERSIST_BY_RESIDUE == ARP_WBP_BY_RESIDUE && TABLE_SIFT_BITS == ARP_WBP_BITS, "arp_bridgepersist.h names the header's bits");
 static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESIDUE && SIM_PLANES == TABLE_SIFT_BITS + RESPERSIST_CLASSES,
@@ -4215,6 +4223,7 @@ int check_leg_mask(arp_ctx* c, const std::string& fn, uint32_t sift_any) {
 // A table is made: its rows, and the arguments of the launch for made_with.
 int table_done(ResultTable& T, uint32_t arg0, uint32_t arg1, long long rows, int64_t* count) {
     T.count = rows; T.arg[0] = arg0; T.arg[1] = arg1; T.valid = true;
+    ++T.launches;
     *count = rows;
     return ARP_OK;
 }
@@ -4411,21 +4420,23 @@ FiveBags five_bags(const arp_ctx* c, bool planes) {
     }
     return B;
 }
-// A table without launch arguments, made from the bags: refuse, return the table that is made, then table_from_records with
-// rekey(B, ...) over the bags B the spec names.
+// A table made from the bags: refuse, return the table that is made for the same launch arguments (arg0, arg1: 0 for a launch
+// without), then table_from_records with rekey(B, ...) over the bags B the spec names.
 using BagsRekeyStep = std::function<int(const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K)>;
-int make_table(arp_ctx* c, const TableSpec& spec, int64_t* count, const BagsRekeyStep& rekey, const ReduceStep& reduce) {
+int make_table(arp_ctx* c, const TableSpec& spec, int64_t* count, const BagsRekeyStep& rekey, const ReduceStep& reduce,
+               uint32_t arg0 = 0, uint32_t arg1 = 0) {
     if (!c || !count) return ARP_E_ARG;
     const std::string fn = spec.launch();
     CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
     ResultTable& T = c->*spec.table;
-    if (T.made_with(0, 0)) { *count = T.count; return ARP_OK; }
+    if (T.made_with(arg0, arg1)) { *count = T.count; return ARP_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     const FiveBags B = five_bags(c, (spec.needs & NEED_FIVE_BAGS) != 0);
+    T.valid = false;
     T.count = 0;
-    if (B.k == 0) return table_done(T, 0, 0, 0, count);
+    if (B.k == 0) return table_done(T, arg0, arg1, 0, count);
     CHK(records_fit(c, fn, B.k));
-    return table_from_records(c, spec, 0, 0, B.k, B.cap, count,
+    return table_from_records(c, spec, arg0, arg1, B.k, B.cap, count,
                               [&](unsigned long long* key, unsigned long long* val, TableKey* K) { return rekey(B, key, val, K); }, reduce);
 }
 // One copy of the slab into the page-locked stage; column q goes to dst[q] unless that is NULL.
@@ -4860,6 +4871,57 @@ int arp_models_similarity_info(arp_ctx* c, int64_t info[4]) {
     info[1] = S.valid ? S.words : 0;
     info[2] = S.valid ? S.slices : 0;
     info[3] = S.launches;
+    return ARP_OK;
+}
+
+// ---- contact lifetimes over the resident models (arp_lifetimes.h): the persistence table's rows, intervals for counts
+// made_with keeps two words: gap << 16 | sift_any (16 + 15 bits) and ctype_mask.
+int arp_models_lifetimes_launch(arp_ctx* c, uint32_t gap, uint32_t sift_any, uint32_t ctype_mask, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const std::string fn = LIFETIMES_TABLE.launch();
+    CHK(check_masks(c, fn, {{sift_any, ARP_FILTER_SIFT_ALL}, {ctype_mask, ARP_FILTER_CTYPE_ALL}},
+                    "a mask has bits beyond the 15 SIFt bits / the 7 contact types", "a mask of 0 lets no record take part"));
+    if (gap > ARP_LIFETIMES_MAX_GAP) FAIL(c, ARP_E_ARG, fn + "gap beyond 65 534 models");
+    LifetimesArgs A{};
+    return make_table(c, LIFETIMES_TABLE, count,
+        [&](const FiveBags& B, unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+            PairModelKey G{};
+            CHK(pair_model_key(c, fn, false, "(atom, atom, model)", &G));
+            // a < b <= n - 1 < 2^bits: the a field of a record's key is never all ones, so the all-ones key of a record that is
+            // left out is no record's in the sorted bits (no tie bit, unlike enqueue_residue_rekey)
+            if (G.n > ((int64_t)1 << G.bits)) FAIL(c, ARP_E_HIP, fn + "atom ids beyond their key bits");
+            A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+            A.k = (long long)B.k;
+            A.n = (uint32_t)G.n;      // (> 0: the bag has records)
+            A.bbits = G.bits; A.fbits = G.fbits;
+            A.sift_any = sift_any; A.ctype_mask = ctype_mask; A.gap = gap;
+            A.key = key; A.val = val;
+            *K = TableKey{G.total(), G.fbits};
+            hipLaunchKernelGGL(k_lifetimes_rekey, dim3(nblocks((int64_t)B.k, 256, 2048)), dim3(256), 0, c->stream, A);
+            return ARP_OK;
+        },
+        [&](const SortedRuns& S, const Columns& col) {
+            A.key = (unsigned long long*)S.key; A.val = (unsigned long long*)S.val; A.row_start = S.R.row_start; A.U = S.U;
+            A.t_a = col[LT_A]; A.t_b = col[LT_B]; A.t_nmodels = col[LT_NMODELS]; A.t_first = col[LT_FIRST]; A.t_last = col[LT_LAST];
+            A.t_nintervals = col[LT_NINTERVALS]; A.t_longest = col[LT_LONGEST]; A.t_longest_start = col[LT_LONGEST_START];
+            A.t_head = col[LT_HEAD]; A.t_tail = col[LT_TAIL]; A.t_span_sum = col[LT_SPAN_SUM];
+            hipLaunchKernelGGL(k_lifetimes_reduce, dim3(nblocks(S.U, 4, 16384)), dim3(256), 0, c->stream, A);
+        },
+        gap << 16 | sift_any, ctype_mask);
+}
+
+int arp_models_lifetimes_fetch(arp_ctx* c, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first, int32_t* last,
+                               uint16_t* n_intervals, uint16_t* longest, int32_t* longest_start, uint16_t* head, uint16_t* tail,
+                               uint32_t* span_sum, int64_t* count) {
+    void* const dst[LT_COLS] = {a, b, n_models, first, last, n_intervals, longest, longest_start, head, tail, span_sum};
+    return table_fetch(c, LIFETIMES_TABLE, cap, dst, count);
+}
+
+int arp_models_lifetimes_info(arp_ctx* c, int64_t info[2]) {
+    if (!c || !info) return ARP_E_ARG;
+    const ResultTable& T = c->lifetimes;
+    info[0] = T.valid ? T.count : 0;
+    info[1] = T.launches;
     return ARP_OK;
 }
 

@@ -1,6 +1,6 @@
 """What the device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
-(``residue_pairs``), residue persistence (``residue_persistence``), the water bridges (``water_bridges``) and water-bridge
-persistence (``bridge_persistence``).
+(``residue_pairs``), residue persistence (``residue_persistence``), the water bridges (``water_bridges``), water-bridge
+persistence (``bridge_persistence``) and contact lifetimes (``lifetimes``).
 
 A table is a dict of NumPy columns with one row per pair.  A ``Spec`` names the columns in the order of the C fetch's
 arguments (include/arpeggio_hip.h) with their types, and the width of those that hold several values a row.  Everything here
@@ -43,6 +43,9 @@ def _bridgepersist(ka, kb):
                  ('ctype_mask_b', np.uint8)), {'bit_models_a': N_BITS, 'bit_models_b': N_BITS})
 
 
+LIFETIMES = Spec((('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('first', np.int32), ('last', np.int32),
+                  ('n_intervals', np.uint16), ('longest', np.uint16), ('longest_start', np.int32), ('head', np.uint16),
+                  ('tail', np.uint16), ('span_sum', np.uint32)), {})
 BRIDGEPERSIST_ATOM = _bridgepersist('a', 'b')
 BRIDGEPERSIST_RESIDUE = _bridgepersist('res_a', 'res_b')
 

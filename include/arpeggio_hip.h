@@ -846,6 +846,46 @@ int arp_models_similarity_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_m
                                  int64_t* n_models, int64_t* n_rows);
 int arp_models_similarity_fetch(arp_ctx* ctx, int64_t cap_models, uint32_t* inter /* [F][F] */, int64_t* n_models);
 int arp_models_similarity_info(arp_ctx* ctx, int64_t info[4]);
+/* Contact lifetimes over the resident models: how LONG a contact lasts and how often it forms and breaks, where the
+ * persistence table gives the fraction of models that have it.  The models are an ordered axis (for a trajectory streamed
+ * through arp_set_models, model f is time).  It is an extension beside the mirror; every column is an integer.
+ *
+ * Participation.  A record of the atom-atom bag takes part when (sift & sift_any) != 0 and bit `ctype` of ctype_mask is set
+ *   (arp_contacts_filter_launch's predicate).  With ARP_FILTER_SIFT_ALL and ARP_FILTER_CTYPE_ALL every record takes part.
+ * Rows.  One row per topology pair (a, b), a < b, with at least one participating record, rows in ascending (a, b).
+ * Intervals.  Let a pair's participating models be f1 < f2 < ... < fm.  An interval is a maximal stretch in which
+ *   consecutive present models differ by at most gap + 1 (gap = models of absence tolerated inside an interval); its span is
+ *   f_end - f_start + 1, so bridged holes count.
+ *   a, b            int32    topology atom ids
+ *   n_models        uint16   m
+ *   first, last     int32    f1, fm
+ *   n_intervals     uint16   number of intervals
+ *   longest         uint16   the largest span
+ *   longest_start   int32    first model of the interval with the largest span; on a tie, the earliest
+ *   head, tail      uint16   span of the first and of the last interval (equal when n_intervals == 1): with them two chunk
+ *                            tables of one trajectory merge exactly
+ *   span_sum        uint32   sum of all spans (mean lifetime = span_sum / n_intervals)
+ * With the all-records masks a, b, n_models, first and last are byte-equal to those columns of arp_models_persistence.
+ *
+ * arp_models_lifetimes_launch: enqueues the reduction on the context's stream and waits once, for *count = rows.
+ * ARP_E_ARG: a shard, no models resident, more than 65 535 models, no results of a pass, a mask of 0 or with bits beyond
+ * ARP_FILTER_SIFT_ALL / ARP_FILTER_CTYPE_ALL, gap > ARP_LIFETIMES_MAX_GAP.  ARP_E_CAPACITY: 2^31 records or more, (atom,
+ * atom, model) does not fit a 63-bit key.  No participating record: 0 rows and ARP_OK.  A second call with the same three
+ * arguments on the same results returns without work; other arguments remake the table.  It is voided wherever the
+ * persistence table is (it reads the atom-atom bag alone); it writes no bag, no sorted slab, no filtered bag and no other
+ * table, and no other derived result voids it.
+ *
+ * arp_models_lifetimes_fetch: the table with one device-to-host copy; any column pointer may be NULL.  ARP_E_CAPACITY with
+ * *count = rows when cap is too small; ARP_E_ARG without a launch.
+ *
+ * arp_models_lifetimes_info: info[0] = rows of the resident table (0 while none is), info[1] = launches of this context that
+ * did work (one that returned a resident table does not count). */
+#define ARP_LIFETIMES_MAX_GAP 65534u
+int arp_models_lifetimes_launch(arp_ctx* ctx, uint32_t gap, uint32_t sift_any, uint32_t ctype_mask, int64_t* count);
+int arp_models_lifetimes_fetch(arp_ctx* ctx, int64_t cap, int32_t* a, int32_t* b, uint16_t* n_models, int32_t* first,
+                               int32_t* last, uint16_t* n_intervals, uint16_t* longest, int32_t* longest_start,
+                               uint16_t* head, uint16_t* tail, uint32_t* span_sum, int64_t* count);
+int arp_models_lifetimes_info(arp_ctx* ctx, int64_t info[2]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
