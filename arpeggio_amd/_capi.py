@@ -46,6 +46,7 @@ SYMBOLS = (
     'arp_batch_layout',
     'arp_models_similarity_launch', 'arp_models_similarity_fetch', 'arp_models_similarity_info',
     'arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', 'arp_models_lifetimes_info',
+    'arp_networks_launch', 'arp_networks_fetch', 'arp_networks_labels_fetch', 'arp_networks_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -55,6 +56,7 @@ PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
 CTYPE_ALL = 0x7F                 # ARP_FILTER_CTYPE_ALL
 LIFETIMES_MAX_GAP = 65534        # ARP_LIFETIMES_MAX_GAP
+NET_BY_RESIDUE = 1               # ARP_NET_BY_RESIDUE
 PERSIST_COLUMNS, RESPAIR_COLUMNS, RESPERSIST_COLUMNS = tables.PERSIST.columns, tables.RESPAIR.columns, tables.RESPERSIST.columns
 
 _lib = None
@@ -216,6 +218,10 @@ def load():
     L.arp_models_lifetimes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64)]
     L.arp_models_lifetimes_fetch.argtypes = [vp, i64] + [vp] * 11 + [C.POINTER(i64)]
     L.arp_models_lifetimes_info.argtypes = [vp, vp]
+    L.arp_networks_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64)]
+    L.arp_networks_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64)]
+    L.arp_networks_labels_fetch.argtypes = [vp, i64, vp, C.POINTER(i64)]
+    L.arp_networks_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -812,6 +818,25 @@ class Context:
         return self._table('arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', tables.LIFETIMES, int(gap), int(sift_any),
                            int(ctype_mask))
 
+    def networks(self, sift_any=0x7FFF, ctype_mask=CTYPE_ALL, by_residue=False):
+        """Interaction networks of the last pass: the connected components of the contact graph, labelled on the device
+        (arp_networks_*).  Nodes are the resident atoms or, ``by_residue``, the resident residues; an atom-atom record is an edge
+        when ``(sift & sift_any) != 0`` and bit ``ctype`` of ``ctype_mask`` is set.  Returns ``(label, table)``: ``label`` int32
+        [N], the smallest node id of each node's component or -1 for a node without a participating record, and a dict of
+        the five columns ``tables.NETWORKS``, one row per component in ascending ``root`` (see ``arpeggio_amd.networks``).
+        Only the labels and the table are copied to the host; the bags of the pass and every other result stay fetchable as
+        before.  With a batch or models resident the ids are those of the concatenation (``networks.split_structures`` /
+        ``split_models``).  A repeated call with the same arguments on the same results fetches the resident result
+        (``stats()['networks_launches']`` counts the launches that made one)."""
+        table = self._table('arp_networks_launch', 'arp_networks_fetch', tables.NETWORKS, int(sift_any), int(ctype_mask),
+                            NET_BY_RESIDUE if by_residue else 0)
+        info = np.zeros(3, np.int64)
+        self._check(self._L.arp_networks_info(self._h, _p(info)), 'arp_networks_info')
+        N = C.c_int64(0)
+        label = np.empty(int(info[1]), np.int32)
+        self._check(self._L.arp_networks_labels_fetch(self._h, len(label), _p(label), C.byref(N)), 'arp_networks_labels_fetch')
+        return label, table
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
@@ -1281,10 +1306,13 @@ class Context:
         self._check(self._L.arp_models_similarity_info(self._h, _p(m)), 'arp_models_similarity_info')
         lt = np.zeros(2, np.int64)
         self._check(self._L.arp_models_lifetimes_info(self._h, _p(lt)), 'arp_models_lifetimes_info')
+        nw = np.zeros(3, np.int64)
+        self._check(self._L.arp_networks_info(self._h, _p(nw)), 'arp_networks_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
                     sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
-                    lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]))
+                    lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]),
+                    networks_rows=int(nw[0]), networks_nodes=int(nw[1]), networks_launches=int(nw[2]))
 
     def set_profiling(self, on=True):
         self._check(self._L.arp_set_profiling(self._h, int(on)), 'arp_set_profiling')

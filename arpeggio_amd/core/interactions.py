@@ -384,6 +384,30 @@ class InteractionComplex:
         from .. import water_bridges as wb
         return wb.write_water_bridges(wd, self.id, self.water_bridges(contacts, same_residue), self.pc, self.component_types)
 
+    def networks(self, contacts=None, interacting_entities=None, level='atom'):
+        """Extension beside the mirror (the reference has no graph view of its contacts): the interaction networks of the last
+        run — the connected components of the graph whose nodes are the atoms (``level='atom'``) or the residues
+        (``'residue'``) and whose edges are the atom-atom records with one of the named ``contacts`` between the named
+        ``interacting_entities`` (``contact_filter.masks``; ``None``: all).  Returns ``(label, table)``: per node the smallest
+        node id of its component or -1 without such a record, and one row per component (``arpeggio_amd.networks`` describes
+        both).  The ring and amide bags take no part.  The atom-atom bag that ``run_arpeggio`` left resident on the GPU is
+        read there — only the labels and the table are copied — whatever ``set_contact_filter`` made of the fetched records."""
+        from .. import contact_filter
+        if level not in ('atom', 'residue'):
+            raise ValueError("networks: level must be 'atom' or 'residue'")
+        sift_any, ctype_mask = contact_filter.masks(contacts, interacting_entities)
+        self._need_results()
+        if self._ctx is None:
+            raise AttributeError('no results on a GPU context: call run_arpeggio() on this complex first')
+        return self._ctx.networks(sift_any, ctype_mask, level == 'residue')
+
+    def write_networks(self, wd, contacts=None, interacting_entities=None, level='atom'):
+        """'<id>.networks': ``networks()`` as CSV, one row per component with its members in the atom / residue labels of the
+        other CSV writers (``networks.write_csv``)."""
+        from .. import networks as nw
+        label, table = self.networks(contacts, interacting_entities, level)
+        return nw.write_networks(wd, self.id, label, table, self.pc, level, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""
@@ -777,6 +801,34 @@ class EnsembleComplex:
         out = {k: ((t[k] - model * n).astype(np.int32) if k in ('water', 'a', 'b') else t[k]) for k, _ in wb.COLUMNS}
         out['model'] = model
         return out
+
+    def run_networks(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, contacts=None,
+                     interacting_entities=None, level='atom'):
+        """Extension beside the mirror: the interaction networks of every model (``InteractionComplex.networks``): the
+        selection handling and the pass of ``run_arpeggio``, then ONE launch on the device over the records of all models and
+        ONE fetch each of the labels and of the table.  No record joins two models, so no component spans them: ``label``
+        comes back as int32 [F, n] (``level='residue'``: [F, residues of the topology]) in topology ids, -1 kept, and the table
+        with topology ids in ``root`` and a ``model`` column (0-based, int32), rows ascending by (model, root).  No bag is
+        copied to the host: ``model(k)`` has no results after this call (``run_arpeggio`` gives those)."""
+        from .. import contact_filter
+        if level not in ('atom', 'residue'):
+            raise ValueError("run_networks: level must be 'atom' or 'residue'")
+        sift_any, ctype_mask = contact_filter.masks(contacts, interacting_entities)
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        label, t = self._ctx.networks(sift_any, ctype_mask, level == 'residue')
+        self._results = None
+        self.stats = self._ctx.stats()
+        F = self.n_models
+        n = len(label) // F
+        label = label.reshape(F, n)
+        label = np.where(label >= 0, label - (np.arange(F, dtype=np.int32) * n)[:, None], -1).astype(np.int32)
+        model = (t['root'] // max(n, 1)).astype(np.int32)
+        out = dict(t, root=(t['root'] - model * n).astype(np.int32))
+        out['model'] = model
+        return label, out
 
     def run_residue_persistence(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, accumulate=False):
         """Residue contact persistence over the models — a residue contact-frequency map: the selection handling and the pass

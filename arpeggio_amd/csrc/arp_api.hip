@@ -36,6 +36,7 @@
 #include "arp_bridgepersist.h"
 #include "arp_similarity.h"
 #include "arp_lifetimes.h"
+#include "arp_networks.h"
 #include "arp_blob.h"
 
 namespace {
@@ -511,6 +512,9 @@ struct arp_ctx {
     DevBuf<int> bridge_res;               // [L] residue of every sorted leg's partner
     SimilarityResult similarity;          // arp_models_similarity_launch
     ResultTable lifetimes;                // arp_models_lifetimes_launch
+    ResultTable networks;                 // arp_networks_launch: the component table ...
+    DevBuf<int> net_label, net_scratch;   // ... the label of each of its net_nodes nodes, and the per-node scratch (arp_networks.h)
+    int64_t net_nodes = 0;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -699,6 +703,7 @@ void void_results(arp_ctx* c, unsigned lost) {
     const struct { bool* valid; unsigned reads, makes; } results[] = {
         {&c->persist.valid, RES_AA, 0},
         {&c->lifetimes.valid, RES_AA, 0},
+        {&c->networks.valid, RES_AA, 0},
         {&c->bridges.valid, RES_AA, RES_BRIDGES},
         {&c->bridgepersist.valid, RES_BRIDGES, 0},
         {&c->respair.valid, bags, 0},
@@ -2324,6 +2329,8 @@ void arp_destroy(arp_ctx* c) {
     c->filtered.cols.release(); c->filtered.slab.release();
     c->bridges.slab.release(); c->bridge_off.release(); c->bridge_res.release();
     c->bridgepersist.slab.release();
+    c->lifetimes.slab.release();
+    c->networks.slab.release(); c->net_label.release(); c->net_scratch.release();
     c->similarity.bits.release(); c->similarity.inter.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
@@ -4172,6 +4179,7 @@ enum { WB_WATER = 0, WB_A, WB_B, WB_DIST_A, WB_DIST_B, WB_SIFT_A, WB_SIFT_B, WB_
 enum { WP_A = 0, WP_B, WP_NMODELS, WP_FIRST, WP_LAST, WP_NWATERS, WP_NBRIDGES, WP_DMIN, WP_DMAX, WP_DSUM, WP_BITS_A, WP_BITS_B,
        WP_CTYPE_A, WP_CTYPE_B, WP_COLS };
 enum { LT_A = 0, LT_B, LT_NMODELS, LT_FIRST, LT_LAST, LT_NINTERVALS, LT_LONGEST, LT_LONGEST_START, LT_HEAD, LT_TAIL, LT_SPAN_SUM, LT_COLS };
+enum { NW_ROOT = 0, NW_NNODES, NW_NEDGES, NW_SIFT, NW_CTYPE, NW_COLS };
 const unsigned OVER_MODELS = NEED_WHOLE | NEED_MODELS | NEED_MODELS_U16;
 const TableSpec PERSIST_TABLE = {"arp_models_persistence", &arp_ctx::persist, PT_COLS, {4, 4, 2, 4, 4, 4, 4, 8, 2 * TABLE_SIFT_BITS, 1},
                                  OVER_MODELS | NEED_AA_BAG, "no results of a pass over the resident models (launch one first)", 1};
@@ -4187,9 +4195,11 @@ const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &a
 // (fewest rows 0: the masks of a launch may leave every record out)
 const TableSpec LIFETIMES_TABLE = {"arp_models_lifetimes", &arp_ctx::lifetimes, LT_COLS, {4, 4, 2, 4, 4, 2, 2, 4, 2, 2, 4},
                                    OVER_MODELS | NEED_AA_BAG, PERSIST_TABLE.no_pass, 0};
+const TableSpec NETWORKS_TABLE = {"arp_networks", &arp_ctx::networks, NW_COLS, {4, 4, 4, 2, 1}, NEED_WHOLE | NEED_AA_BAG, NO_AA_PASS, 0};
 static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS && WB_COLS <= TABLE_MAX_COLS &&
               WP_COLS <= TABLE_MAX_COLS && LT_COLS <= TABLE_MAX_COLS, "TableSpec::es");
 static_assert(ARP_LIFETIMES_MAX_GAP + 1u <= 0xFFFFu, "gap + 1 is compared with differences of models counted in uint16");
+static_assert(NET_BY_RESIDUE == ARP_NET_BY_RESIDUE, "arp_networks.h names the header's bit");
 static_assert(BRIDGE_F_WATER == ARP_F_WATER && BRIDGE_SAME_RESIDUE == ARP_WB_SAME_RESIDUE, "arp_bridge.h names the header's bits");
 static_assert(BRIDGEPERSIST_BY_RESIDUE == ARP_WBP_BY_RESIDUE && TABLE_SIFT_BITS == ARP_WBP_BITS, "arp_bridgepersist.h names the header's bits");
 static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESIDUE && SIM_PLANES == TABLE_SIFT_BITS + RESPERSIST_CLASSES,
@@ -4922,6 +4932,102 @@ int arp_models_lifetimes_info(arp_ctx* c, int64_t info[2]) {
     const ResultTable& T = c->lifetimes;
     info[0] = T.valid ? T.count : 0;
     info[1] = T.launches;
+    return ARP_OK;
+}
+
+// ---- interaction networks (arp_networks.h): the components of the contact graph, by lock-free union-find
+// Nothing is sorted: a sequence of its own from the shared steps, with ONE wait — U, the components.  Of the results only the
+// atom-atom bag (and res_id) is read; this table, its labels and its scratch alone are written.
+// made_with keeps two words: flags << 15 | sift_any and ctype_mask.
+int arp_networks_launch(arp_ctx* c, uint32_t sift_any, uint32_t ctype_mask, uint32_t flags, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const TableSpec& spec = NETWORKS_TABLE;
+    const std::string fn = spec.launch();
+    CHK(check_masks(c, fn, {{sift_any, ARP_FILTER_SIFT_ALL}, {ctype_mask, ARP_FILTER_CTYPE_ALL}},
+                    "a mask has bits beyond the 15 SIFt bits / the 7 contact types", "a mask of 0 lets no record take part"));
+    if (flags & ~ARP_NET_BY_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
+    ResultTable& T = c->networks;
+    const uint32_t arg0 = flags << 15 | sift_any;
+    if (T.made_with(arg0, ctype_mask)) { *count = T.count; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    T.valid = false;
+    T.count = 0;
+    const size_t k = (size_t)c->n_contacts;
+    CHK(records_fit(c, fn, k));
+    const bool by_res = (flags & ARP_NET_BY_RESIDUE) != 0;
+    const int64_t N = by_res ? c->nres : c->n;
+    if (N >= ((int64_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, fn + "2^31 nodes or more");
+    c->net_nodes = N;
+    const auto done = [&](long long rows) { return table_done(T, arg0, ctype_mask, rows, count); };
+    if (N == 0) return done(0);
+    HIPCHK(c, c->net_label.reserve((size_t)N));
+    if (k == 0) {      // (no record: every node alone and untouched)
+        HIPCHK(c, hipMemsetAsync(c->net_label.p, 0xFF, (size_t)N * sizeof(int), c->stream));
+        return done(0);
+    }
+    // ---- union-find over the records, labels, counts per root
+    HIPCHK(c, c->net_scratch.reserve(5 * (size_t)N + 1));
+    const int tiles = (int)((N + NET_TILE - 1) / NET_TILE);
+    CHK(reserve_tile_counts(c, tiles));
+    NetArgs A{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k; A.res_id = c->res_id.p;
+    A.sift_any = sift_any; A.ctype_mask = ctype_mask; A.flags = flags;
+    A.N = (int)N;
+    int* const s = c->net_scratch.p;
+    A.parent = s; A.n_nodes = s + N; A.n_edges = s + 2 * N; A.bits = (uint32_t*)(s + 3 * N); A.touched = s + 4 * N; A.err = s + 5 * N;
+    A.label = c->net_label.p;
+    A.tile_rows = c->table_tiles.p;
+    const dim3 per_node(nblocks(N, NET_THREADS, 2048)), per_record(nblocks((int64_t)k, NET_THREADS, 2048));
+    hipLaunchKernelGGL(k_net_init, per_node, dim3(NET_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_net_hook, per_record, dim3(NET_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_net_label, per_node, dim3(NET_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_net_edges, per_record, dim3(NET_THREADS), 0, c->stream, A);
+    // ---- roots per tile, scanned; the host learns U (the one wait; negative when a kernel met one of its bounds)
+    hipLaunchKernelGGL(k_net_roots, dim3(tiles), dim3(NET_THREADS), 0, c->stream, A);
+    long long U = 0;
+    CHK(wait_tile_total(c, tiles, &U, fn + "union / label / count"));
+    if (U < 0 || U > (long long)N || U > (long long)k) FAIL(c, ARP_E_HIP, fn + "row count out of range");
+    if (U == 0) return done(0);
+    // ---- the rows, each at its rank
+    const TableLayout lay = table_layout(spec, (size_t)U);
+    HIPCHK(c, T.slab.reserve(lay.bytes));
+    const Columns col{T.slab.p, lay.off};
+    A.U = U;
+    A.t_root = col[NW_ROOT]; A.t_nnodes = col[NW_NNODES]; A.t_nedges = col[NW_NEDGES]; A.t_sift = col[NW_SIFT]; A.t_ctype = col[NW_CTYPE];
+    hipLaunchKernelGGL(k_net_rows, dim3(tiles), dim3(NET_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "rows").c_str()));
+    return done(U);
+}
+
+int arp_networks_fetch(arp_ctx* c, int64_t cap, int32_t* root, int32_t* n_nodes, int32_t* n_edges, uint16_t* sift_or, uint8_t* ctype_or,
+                       int64_t* count) {
+    void* const dst[NW_COLS] = {root, n_nodes, n_edges, sift_or, ctype_or};
+    return table_fetch(c, NETWORKS_TABLE, cap, dst, count);
+}
+
+int arp_networks_labels_fetch(arp_ctx* c, int64_t cap, int32_t* label, int64_t* nodes) {
+    if (!c || !nodes) return ARP_E_ARG;
+    const ResultTable& T = c->networks;
+    if (!c->contacts_valid || !T.valid) FAIL(c, ARP_E_ARG, "arp_networks_labels_fetch: no labels (arp_networks_launch after a pass)");
+    *nodes = c->net_nodes;
+    if (c->net_nodes > cap) FAIL(c, ARP_E_CAPACITY, "arp_networks_labels_fetch: output buffer too small");
+    if (c->net_nodes == 0) return ARP_OK;
+    if (!label) FAIL(c, ARP_E_ARG, "arp_networks_labels_fetch: output missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->net_nodes * sizeof(int32_t);
+    CHK(stage_copy(c, c->net_label.p, bytes));
+    memcpy(label, c->table_stage, bytes);
+    return ARP_OK;
+}
+
+int arp_networks_info(arp_ctx* c, int64_t info[3]) {
+    if (!c || !info) return ARP_E_ARG;
+    const ResultTable& T = c->networks;
+    info[0] = T.valid ? T.count : 0;
+    info[1] = T.valid ? c->net_nodes : 0;
+    info[2] = T.launches;
     return ARP_OK;
 }
 

@@ -886,6 +886,50 @@ int arp_models_lifetimes_fetch(arp_ctx* ctx, int64_t cap, int32_t* a, int32_t* b
                                int32_t* last, uint16_t* n_intervals, uint16_t* longest, int32_t* longest_start,
                                uint16_t* head, uint16_t* tail, uint32_t* span_sum, int64_t* count);
 int arp_models_lifetimes_info(arp_ctx* ctx, int64_t info[2]);
+/* Interaction networks: the connected components of the contact graph, labelled on the device by a lock-free union-find
+ * (csrc/arp_networks.h).  Which atoms form one hydrogen-bond network, waters included; how large the hydrophobic cluster is
+ * that a ligand sits in; whether a salt bridge is isolated or part of an ionic cluster.  It is an extension beside the mirror.
+ *
+ * Inputs.  The atom-atom bag of the last pass with whatever is resident: one structure, a batch, or models.  sift_any: of the
+ *   15 SIFt bits, not 0.  ctype_mask: of the 7 contact types, not 0.  flags: ARP_NET_BY_RESIDUE or 0.
+ * Nodes.  The N = n resident atoms; with ARP_NET_BY_RESIDUE the N = nres resident residues, a record's nodes then being
+ *   res_id[i], res_id[j].  The ring and amide bags take no part at either level.
+ * Edges.  A record takes part when (sift & sift_any) != 0 and bit `ctype` of ctype_mask is set (arp_contacts_filter_launch's
+ *   predicate).  A participating record is an edge between its two nodes.  A record with a negative node (a residue of -1) is
+ *   left out.  A record whose two nodes are equal counts as an edge of that node and joins nothing (a pass produces none:
+ *   no record joins two atoms of one residue).  No record joins two structures of a batch or two models, so no component spans them.
+ * Results.
+ *   label  int32 [N]   the smallest node id of the node's component, or -1 for a node without a participating record
+ *   the component table, one row per component in ascending root:
+ *   root      int32    the component's smallest node id
+ *   n_nodes   int32    its nodes
+ *   n_edges   int32    its participating records, multi-edges counted
+ *   sift_or   uint16   OR of the whole SIFt of those records
+ *   ctype_or  uint8    OR of 1 << ctype of those records
+ * Everything is an integer, a minimum, a count or an OR: the result does not depend on the order of the records.
+ *
+ * arp_networks_launch: enqueues the union, the labels and the counts on the context's stream and waits once, for *count =
+ * components.  ARP_E_ARG: a mask of 0 or with bits beyond ARP_FILTER_SIFT_ALL / ARP_FILTER_CTYPE_ALL, an unknown flag, a
+ * shard, no atom-contact results of a pass.  ARP_E_CAPACITY: 2^31 records or more.  ARP_E_HIP "row count out of range": a
+ * kernel met one of the bounds its loops cannot reach (arp_networks.h).  An empty bag or masks that no record meets: 0 rows,
+ * every label -1, ARP_OK.  A second call with the same three arguments on the same results returns without work; other
+ * arguments remake the result.  It is voided wherever the atom-atom bag is refilled or lost; it writes no bag, no sorted
+ * slab, no filtered bag and no other table, and no other derived result voids it.
+ *
+ * arp_networks_fetch: the table with one device-to-host copy; any column pointer may be NULL.  ARP_E_CAPACITY with *count =
+ * rows when cap is too small; ARP_E_ARG without a launch.
+ *
+ * arp_networks_labels_fetch: label[0 ... N) with one device-to-host copy, *nodes = N.  ARP_E_CAPACITY with *nodes = N when
+ * cap < N; ARP_E_ARG without a launch.
+ *
+ * arp_networks_info: info[0] = rows of the resident table and info[1] = its nodes N (0 while none is resident), info[2] =
+ * launches of this context that did work (one that returned a resident result does not count). */
+#define ARP_NET_BY_RESIDUE 1u
+int arp_networks_launch(arp_ctx* ctx, uint32_t sift_any, uint32_t ctype_mask, uint32_t flags, int64_t* count);
+int arp_networks_fetch(arp_ctx* ctx, int64_t cap, int32_t* root, int32_t* n_nodes, int32_t* n_edges, uint16_t* sift_or,
+                       uint8_t* ctype_or, int64_t* count);
+int arp_networks_labels_fetch(arp_ctx* ctx, int64_t cap, int32_t* label, int64_t* nodes);
+int arp_networks_info(arp_ctx* ctx, int64_t info[3]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
