@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from arpeggio_amd import sharding, synth
+from shard_cases import expected_rad_idx
 
 pytestmark = pytest.mark.gpu
 
@@ -74,9 +75,7 @@ def test_device_assembled_shard_equals_host_assembled(capi, world):
                             ('amide_res', pc.amide_res)):
                 assert np.array_equal(got[k], want), (name, r, k)
             assert np.all(got['sb_nbr'] == -1)
-            idx = got['rad_idx']
-            known = idx != 0xFFFF
-            assert known.mean() > 0.99 and np.array_equal(got['rad_tab'][idx[known]], got['rad'][known])
+            assert np.array_equal(got['rad_idx'], expected_rad_idx(got)), (name, r)      # the first matching table entry, 0xFFFF: none
             hdr = got['header']
             assert all(hdr.lo[k] <= pc.xyz[:, k].min() and hdr.hi[k] >= pc.xyz[:, k].max() for k in range(3))
             # and what the pass makes of it
