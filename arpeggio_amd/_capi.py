@@ -45,6 +45,7 @@ SYMBOLS = (
     'arp_models_water_bridge_persistence_launch', 'arp_models_water_bridge_persistence_fetch',
     'arp_batch_layout',
     'arp_models_similarity_launch', 'arp_models_similarity_fetch', 'arp_models_similarity_info',
+    'arp_models_coupling_launch', 'arp_models_coupling_fetch', 'arp_models_coupling_info',
     'arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', 'arp_models_lifetimes_info',
     'arp_networks_launch', 'arp_networks_fetch', 'arp_networks_labels_fetch', 'arp_networks_info',
 )
@@ -54,6 +55,7 @@ PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
+COUPLE_BY_RESIDUE, COUPLE_MAX_FEATURES = 1, 65536              # ARP_COUPLE_BY_RESIDUE, ARP_COUPLE_MAX_FEATURES
 CTYPE_ALL = 0x7F                 # ARP_FILTER_CTYPE_ALL
 LIFETIMES_MAX_GAP = 65534        # ARP_LIFETIMES_MAX_GAP
 NET_BY_RESIDUE = 1               # ARP_NET_BY_RESIDUE
@@ -215,6 +217,9 @@ def load():
     L.arp_models_similarity_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64), C.POINTER(i64)]
     L.arp_models_similarity_fetch.argtypes = [vp, i64, vp, C.POINTER(i64)]
     L.arp_models_similarity_info.argtypes = [vp, vp]
+    L.arp_models_coupling_launch.argtypes = [vp] + [C.c_uint32] * 6 + [i64, C.POINTER(i64), C.POINTER(i64)]
+    L.arp_models_coupling_fetch.argtypes = [vp, i64, i64] + [vp] * 6 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_models_coupling_info.argtypes = [vp, vp]
     L.arp_models_lifetimes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(i64)]
     L.arp_models_lifetimes_fetch.argtypes = [vp, i64] + [vp] * 11 + [C.POINTER(i64)]
     L.arp_models_lifetimes_info.argtypes = [vp, vp]
@@ -807,6 +812,35 @@ class Context:
         self._check(self._L.arp_models_similarity_fetch(self._h, n, _p(inter), C.byref(F)), 'arp_models_similarity_fetch')
         return inter
 
+    def models_coupling(self, planes, ctype_mask=CTYPE_ALL, by_residue=False, min_count=1, max_count=None, phi2_q=512, max_pairs=1 << 20):
+        """Contact coupling over the resident models of the last pass, correlated on the device (arp_models_coupling_*): which
+        contacts form and break together.  A row — a topology atom pair of ``models_persistence`` or, ``by_residue``, a topology
+        residue pair of ``models_residue_persistence`` (a complete pass) — is present in a model when a participating record of
+        it has a plane of ``planes`` (``similarity.planes``; bit ``ctype`` of ``ctype_mask`` decides participation).  The rows
+        present in ``min_count`` ... ``max_count`` models (``None``: F - 1) are the features; a pair of features is kept when
+        phi^2 >= ``phi2_q`` / 1024 (``coupling.phi2_q``).  Returns ``(features, pairs)``, dicts of the columns
+        ``tables.COUPLING_FEATURES`` (a, b, count) and ``tables.COUPLING_PAIRS`` (u, v, n11), in ascending (a, b) and (u, v); see
+        ``arpeggio_amd.coupling``.  More kept pairs than ``max_pairs``: ``NativeLibraryError`` with ``code`` ARP_E_CAPACITY and
+        the exact number in ``n_pairs``.  Only the two tables are copied to the host; the bags of the pass and every other
+        result stay fetchable as before.  What the launch did is in ``stats()`` (``couple_rows``, ``couple_features``,
+        ``couple_tile_pairs``, ``couple_launches``)."""
+        if self._models is None:
+            raise ValueError('models_coupling: no models resident (set_models)')
+        K, P = C.c_int64(0), C.c_int64(0)
+        top = self._models['F'] - 1 if max_count is None else int(max_count)
+        rc = self._L.arp_models_coupling_launch(self._h, int(planes), int(ctype_mask), COUPLE_BY_RESIDUE if by_residue else 0, int(min_count),
+                                                max(top, 0), int(phi2_q), int(max_pairs), C.byref(K), C.byref(P))
+        try:
+            self._check(rc, 'arp_models_coupling_launch')
+        except NativeLibraryError as e:
+            e.n_features, e.n_pairs = int(K.value), int(P.value)
+            raise
+        f, t = tables.alloc(tables.COUPLING_FEATURES, int(K.value)), tables.alloc(tables.COUPLING_PAIRS, int(P.value))
+        self._check(self._L.arp_models_coupling_fetch(self._h, int(K.value), int(P.value), *(_p(f[k]) for k, _ in tables.COUPLING_FEATURES.columns),
+                                                      *(_p(t[k]) for k, _ in tables.COUPLING_PAIRS.columns), C.byref(K), C.byref(P)),
+                    'arp_models_coupling_fetch')
+        return f, t
+
     def models_lifetimes(self, gap=0, sift_any=0x7FFF, ctype_mask=CTYPE_ALL):
         """Contact lifetimes over the resident models of the last pass, reduced on the device (arp_models_lifetimes_*): per
         topology pair (a, b) with a participating record — ``(sift & sift_any) != 0`` and bit ``ctype`` of ``ctype_mask`` set —
@@ -1308,10 +1342,13 @@ class Context:
         self._check(self._L.arp_models_lifetimes_info(self._h, _p(lt)), 'arp_models_lifetimes_info')
         nw = np.zeros(3, np.int64)
         self._check(self._L.arp_networks_info(self._h, _p(nw)), 'arp_networks_info')
+        cp = np.zeros(4, np.int64)
+        self._check(self._L.arp_models_coupling_info(self._h, _p(cp)), 'arp_models_coupling_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
                     sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
                     lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]),
+                    couple_rows=int(cp[0]), couple_features=int(cp[1]), couple_tile_pairs=int(cp[2]), couple_launches=int(cp[3]),
                     networks_rows=int(nw[0]), networks_nodes=int(nw[1]), networks_launches=int(nw[2]))
 
     def set_profiling(self, on=True):

@@ -663,6 +663,9 @@ class EnsembleComplex:
         self._bridge_persistence_key = None
         self.similarity = None           # the matrix of run_similarity (uint32 [F, F]) and the rows it was made over
         self.similarity_rows = 0
+        self.coupling = None             # (features, pairs) of run_coupling, its level and the effective threshold on |phi|
+        self.coupling_level = 'atom'
+        self.coupling_threshold = None
         self.lifetimes = None            # the table of run_lifetimes, the models it covers and (gap, sift_any, ctype_mask)
         self.lifetimes_models = 0
         self._lifetimes_key = None
@@ -931,6 +934,51 @@ class EnsembleComplex:
         if self.similarity is None:
             raise AttributeError('write_similarity: run_similarity first')
         return _sim.write_similarity(wd, self.id, self.similarity)
+
+    def run_coupling(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, contacts=None, classes=(),
+                     interacting_entities=None, level='atom', min_occupancy=0.05, max_occupancy=0.95, min_abs_phi=0.7,
+                     max_pairs=1 << 20):
+        """Extension beside the mirror: contact coupling over the models — which contacts form and break together: the
+        selection handling and the pass of ``run_persistence``, then the records of all models turned ON THE DEVICE into one
+        bit per (contact, model), the contacts whose occupancy lies in ``min_occupancy`` ... ``max_occupancy`` correlated
+        pairwise there, and only the pairs with \\|phi\\| >= ``min_abs_phi`` fetched (``arpeggio_amd.coupling`` describes the
+        two tables and derives phi, the Jaccard index and the groups of contacts that switch together), into
+        ``self.coupling`` = ``(features, pairs)`` (also returned).  A contact is a topology atom pair (``level='atom'``) or a
+        topology residue pair over all five bags (``level='residue'``); ``contacts`` / ``classes`` /
+        ``interacting_entities`` are those of ``run_similarity``.  The occupancies become counts of models by ceil and floor,
+        clipped to 1 ... F - 1 (``coupling.counts``); the threshold becomes ``coupling.phi2_q(min_abs_phi)``, whose effective
+        value is kept in ``self.coupling_threshold``.  More kept pairs than ``max_pairs``: ``NativeLibraryError`` whose
+        ``n_pairs`` is their exact number.  No bag is copied to the host: ``model(k)`` has no results after this call.
+        There is no ``accumulate``: the threshold is not additive over the chunks of a trajectory."""
+        from .. import contact_filter, coupling as _cp, similarity as _sim
+        if level not in _cp.LEVELS:
+            raise ValueError(f"run_coupling: level must be 'atom' or 'residue', not {level!r}")
+        mask = _sim.planes(contacts, classes)
+        if level == 'atom' and mask & ~_sim.ATOM_PLANES:
+            raise ValueError("run_coupling: the ring / amide classes are planes of level='residue' only")
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        lo, hi = _cp.counts(min_occupancy, max_occupancy, self.n_models)
+        if lo > hi:
+            raise ValueError('run_coupling: no count of models lies between min_occupancy and max_occupancy')
+        q, effective = _cp.phi2_q(min_abs_phi)
+        if self._ctx is None:
+            self.initialize()
+        self._upload_selection(user_selections)
+        self._ctx.run_launch(interacting_cutoff, vdw_comp, include_sequence_adjacent, config.SELECTION_EXPANSION_RADIUS)
+        self.coupling = self._ctx.models_coupling(mask, ctype_mask, by_residue=level == 'residue', min_count=lo, max_count=hi, phi2_q=q,
+                                                  max_pairs=max_pairs)
+        self.coupling_level, self.coupling_threshold = level, effective
+        self._results = None
+        self.stats = self._ctx.stats()
+        return self.coupling
+
+    def write_coupling(self, wd):
+        """'<id>.coupling' in ``wd``: the kept pairs of ``run_coupling`` as CSV."""
+        from .. import coupling as _cp
+        if self.coupling is None:
+            raise AttributeError('write_coupling: run_coupling first')
+        return _cp.write_coupling(wd, self.id, self.coupling[0], self.coupling[1], self.pc, self.n_models, self.coupling_level,
+                                  self.component_types)
 
     def run_lifetimes(self, user_selections, interacting_cutoff, vdw_comp, include_sequence_adjacent, gap=0, contacts=None,
                       interacting_entities=None, accumulate=False):

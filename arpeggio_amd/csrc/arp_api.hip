@@ -35,6 +35,7 @@
 #include "arp_bridge.h"
 #include "arp_bridgepersist.h"
 #include "arp_similarity.h"
+#include "arp_coupling.h"
 #include "arp_lifetimes.h"
 #include "arp_networks.h"
 #include "arp_blob.h"
@@ -251,13 +252,14 @@ struct HintKey {
 }  // namespace
 
 // a table reduced on the device: its columns in one piece (table_layout), its rows, whether it is that of the last results, and
-// the arguments of the launch that made it (0 for a launch without); launches counts the launches that made it anew
+// the arguments of the launch that made it (0 for a launch without; a launch with more than two packs them into the two
+// words); launches counts the launches that made it anew
 struct ResultTable {
     DevBuf<uint8_t> slab;
     int64_t count = 0, launches = 0;
-    uint32_t arg[2] = {0, 0};
+    uint64_t arg[2] = {0, 0};
     bool valid = false;
-    bool made_with(uint32_t arg0, uint32_t arg1) const { return valid && arg[0] == arg0 && arg[1] == arg1; }
+    bool made_with(uint64_t arg0, uint64_t arg1) const { return valid && arg[0] == arg0 && arg[1] == arg1; }
 };
 
 // the atom-atom records a caller asked for (arp_contacts_filter_launch): the kept records as the filter left them, and their
@@ -278,6 +280,15 @@ struct SimilarityResult {
     int64_t F = 0, rows = 0, words = 0, slices = 0, launches = 0;
     uint32_t planes = 0, ctype_mask = 0, flags = 0;
     bool valid = false;
+};
+
+// what the coupling tables (arp_models_coupling_launch) keep beside their slab: the model bits of all U rows and of the K
+// features with their counts, and what arp_models_coupling_info answers
+struct CouplingScratch {
+    DevBuf<unsigned long long> rowbits, bits;
+    DevBuf<uint32_t> n_row, n;
+    int64_t rows = 0, features = 0, tile_pairs = 0;
+    uint32_t flags = 0;
 };
 
 struct arp_ctx {
@@ -515,6 +526,8 @@ struct arp_ctx {
     ResultTable networks;                 // arp_networks_launch: the component table ...
     DevBuf<int> net_label, net_scratch;   // ... the label of each of its net_nodes nodes, and the per-node scratch (arp_networks.h)
     int64_t net_nodes = 0;
+    ResultTable coupling;                 // arp_models_coupling_launch: features and pairs in one slab; count = kept pairs
+    CouplingScratch couple;
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -709,7 +722,8 @@ void void_results(arp_ctx* c, unsigned lost) {
         {&c->respair.valid, bags, 0},
         {&c->respersist.valid, bags, 0},
         {&c->filtered.valid, bags | RES_LAYOUT, 0},      // (its slab is sized for the four bags packed behind the kept records)
-        {&c->similarity.valid, (c->similarity.flags & SIM_BY_RESIDUE) ? bags : RES_AA, 0}};      // (the bags of its level)
+        {&c->similarity.valid, (c->similarity.flags & SIM_BY_RESIDUE) ? bags : RES_AA, 0},      // (the bags of its level)
+        {&c->coupling.valid, (c->couple.flags & COUPLE_BY_RESIDUE) ? bags : RES_AA, 0}};       // (the same rule)
     for (const auto& r : results)
         if (r.reads & lost) { *r.valid = false; lost |= r.makes; }
 }
@@ -2332,6 +2346,7 @@ void arp_destroy(arp_ctx* c) {
     c->lifetimes.slab.release();
     c->networks.slab.release(); c->net_label.release(); c->net_scratch.release();
     c->similarity.bits.release(); c->similarity.inter.release();
+    c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
     c->res_tag.release(); c->blob_sb_nbr.release(); c->blob_dev.release(); c->longest_bond.release();
@@ -4196,6 +4211,12 @@ const TableSpec BRIDGEPERSIST_TABLE = {"arp_models_water_bridge_persistence", &a
 const TableSpec LIFETIMES_TABLE = {"arp_models_lifetimes", &arp_ctx::lifetimes, LT_COLS, {4, 4, 2, 4, 4, 2, 2, 4, 2, 2, 4},
                                    OVER_MODELS | NEED_AA_BAG, PERSIST_TABLE.no_pass, 0};
 const TableSpec NETWORKS_TABLE = {"arp_networks", &arp_ctx::networks, NW_COLS, {4, 4, 4, 2, 1}, NEED_WHOLE | NEED_AA_BAG, NO_AA_PASS, 0};
+// (two tables in one slab: the three columns of the K features, then the three of the P kept pairs — couple_layout; it needs
+// the bags of its level, which its launch refuses as similarity does)
+enum { CP_A = 0, CP_B, CP_COUNT, CP_U, CP_V, CP_N11, CP_COLS, CP_FEATURE_COLS = CP_U };
+const TableSpec COUPLING_TABLE = {"arp_models_coupling", &arp_ctx::coupling, CP_COLS, {4, 4, 4, 4, 4, 4}, NEED_WHOLE | NEED_MODELS, nullptr, 0};
+static_assert(COUPLE_BY_RESIDUE == ARP_COUPLE_BY_RESIDUE && COUPLE_MAX_FEATURES == ARP_COUPLE_MAX_FEATURES &&
+              COUPLE_MAX_WORDS * 64 == ARP_SIM_MAX_MODELS, "arp_coupling.h names the header's limits");
 static_assert(PT_COLS <= TABLE_MAX_COLS && RT_COLS <= TABLE_MAX_COLS && ST_COLS <= TABLE_MAX_COLS && WB_COLS <= TABLE_MAX_COLS &&
               WP_COLS <= TABLE_MAX_COLS && LT_COLS <= TABLE_MAX_COLS, "TableSpec::es");
 static_assert(ARP_LIFETIMES_MAX_GAP + 1u <= 0xFFFFu, "gap + 1 is compared with differences of models counted in uint16");
@@ -4231,7 +4252,7 @@ int check_leg_mask(arp_ctx* c, const std::string& fn, uint32_t sift_any) {
     return check_masks(c, fn, {{sift_any, ARP_FILTER_SIFT_ALL}}, "sift_any has bits beyond the 15 SIFt bits", "a sift_any of 0 makes no record a leg");
 }
 // A table is made: its rows, and the arguments of the launch for made_with.
-int table_done(ResultTable& T, uint32_t arg0, uint32_t arg1, long long rows, int64_t* count) {
+int table_done(ResultTable& T, uint64_t arg0, uint64_t arg1, long long rows, int64_t* count) {
     T.count = rows; T.arg[0] = arg0; T.arg[1] = arg1; T.valid = true;
     ++T.launches;
     *count = rows;
@@ -5028,6 +5049,167 @@ int arp_networks_info(arp_ctx* c, int64_t info[3]) {
     info[0] = T.valid ? T.count : 0;
     info[1] = T.valid ? c->net_nodes : 0;
     info[2] = T.launches;
+    return ARP_OK;
+}
+
+// ---- contact coupling over the resident models (arp_coupling.h): n11 = B^T B of a feature-major bit matrix
+// The rows are similarity's (sort_to_runs with the re-key step of the level); the bits, the band, the product and the
+// emission are this launch's own.  Three waits: U rows, K features, P kept pairs.  Only the bags are read; nothing but the
+// two tables, their bit matrices and the shared scratch is written.
+// made_with keeps two words: planes | ctype_mask << 20 | flags << 27 | phi2_q << 28 | min_count << 39 | max_count << 51
+// (20 + 7 + 1 + 11 + 12 + 12 bits) and max_pairs.
+namespace {
+// the slab of both tables: the feature columns for K rows, then the pair columns for P rows (the former do not move with P)
+TableLayout couple_layout(size_t K, size_t P) {
+    TableLayout L{};
+    for (int q = 0; q < CP_COLS; ++q) { L.off[q] = L.bytes; L.bytes += al256((q < CP_FEATURE_COLS ? K : P) * COUPLING_TABLE.es[q]); }
+    return L;
+}
+}  // namespace
+
+int arp_models_coupling_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, uint32_t min_count, uint32_t max_count,
+                               uint32_t phi2_q, int64_t max_pairs, int64_t* n_features, int64_t* n_pairs) {
+    if (!c || !n_features || !n_pairs) return ARP_E_ARG;
+    const TableSpec& spec = COUPLING_TABLE;
+    const std::string fn = spec.launch();
+    *n_features = 0;
+    *n_pairs = 0;
+    const bool by_res = (flags & ARP_COUPLE_BY_RESIDUE) != 0;
+    CHK(check_masks(c, fn, {{planes, (1u << ARP_SIM_PLANES) - 1u}, {ctype_mask, ARP_FILTER_CTYPE_ALL}},
+                    "a mask has bits beyond the 20 planes / the 7 contact types", "a mask of 0 lets no record take part"));
+    if (flags & ~ARP_COUPLE_BY_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    if (!by_res && (planes >> (TABLE_SIFT_BITS + 1))) FAIL(c, ARP_E_ARG, fn + "planes 16 ... 19 (the ring / amide classes) exist at residue level only");
+    if (phi2_q < 1u || phi2_q > 1024u) FAIL(c, ARP_E_ARG, fn + "phi2_q must lie in 1 ... 1024");
+    if (max_pairs < 0) FAIL(c, ARP_E_ARG, fn + "max_pairs must not be negative");
+    CHK(launch_refusals(c, fn, spec.needs, spec.no_pass));
+    const int64_t F = c->models_n;
+    if (F > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "more than 4096 models (the criterion's integers would pass 64 bits)");
+    if (!(1u <= min_count && min_count <= max_count && (int64_t)max_count <= F - 1))
+        FAIL(c, ARP_E_ARG, fn + "1 <= min_count <= max_count <= F - 1 is required (a row present in no model or in every model is no feature; F >= 2)");
+    CHK(launch_refusals(c, fn, by_res ? NEED_FIVE_BAGS : NEED_AA_BAG, (by_res ? RESPERSIST_TABLE : PERSIST_TABLE).no_pass));
+    ResultTable& T = c->coupling;
+    CouplingScratch& X = c->couple;
+    const uint64_t arg0 = (uint64_t)planes | (uint64_t)ctype_mask << 20 | (uint64_t)flags << 27 | (uint64_t)phi2_q << 28 |
+                          (uint64_t)min_count << 39 | (uint64_t)max_count << 51;
+    const uint64_t arg1 = (uint64_t)max_pairs;
+    if (T.made_with(arg0, arg1)) { *n_features = X.features; *n_pairs = T.count; return ARP_OK; }
+    T.valid = false;
+    T.count = 0;
+    const FiveBags B = five_bags(c, by_res);
+    const size_t k = B.k;
+    CHK(records_fit(c, fn, k));
+    PairModelKey G{};
+    CHK(pair_model_key(c, fn, by_res, "(pair, model)", &G));
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto done = [&](long long U, long long K, long long tile_pairs, long long P) {
+        X.rows = U; X.features = K; X.tile_pairs = tile_pairs; X.flags = flags;
+        *n_features = K;
+        return table_done(T, arg0, arg1, P, n_pairs);
+    };
+    if (k == 0) return done(0, 0, 0, 0);
+    // ---- the records keyed by (pair, model), sorted by every bit; the host learns U (wait 1).  The tile counts are sized for
+    // the rows there can be at most, so that nothing the enqueued kernels read moves afterwards
+    CHK(reserve_tile_counts(c, (int)std::max((k + RUNS_TILE - 1) / RUNS_TILE, (k + COUPLE_TILE_ROWS - 1) / COUPLE_TILE_ROWS)));
+    SortedRuns Q{};
+    CHK(sort_to_runs(c, fn, k, B.cap, by_res ? 0 : 1, [&](unsigned long long* key, unsigned long long* val, TableKey* K) -> int {
+        if (by_res) enqueue_residue_rekey(c, B, G, key, val, K);
+        else (void)enqueue_persist_rekey(c, G, k, key, val, K);
+        return ARP_OK;
+    }, &Q));
+    const long long U = Q.U;
+    if (U == 0) return done(0, 0, 0, 0);      // no record with a row
+    // ---- the model bits of every row and their count
+    const long long fw = (F + 63) / 64;
+    if (U * fw >= (1ll << 29)) FAIL(c, ARP_E_CAPACITY, fn + "a bit matrix of 4 GiB or more");
+    HIPCHK(c, X.rowbits.reserve((size_t)(U * fw)));
+    HIPCHK(c, X.n_row.reserve((size_t)U));
+    CHK(enqueue_run_starts(c, Q.R, U));
+    CoupleArgs A{};
+    A.key = Q.key; A.val = Q.val; A.row_start = Q.R.row_start; A.U = U;
+    A.fbits = G.fbits; A.bbits = G.bits; A.planes = planes; A.ctype_mask = ctype_mask; A.F = (uint32_t)F; A.fw = (int)fw;
+    A.rowbits = X.rowbits.p; A.n_row = X.n_row.p;
+    hipLaunchKernelGGL(k_couple_bits, dim3(nblocks(U, 4, 16384)), dim3(256), 0, c->stream, A);
+    // ---- the rows in the band per tile, scanned; the host learns K (wait 2)
+    A.min_count = min_count; A.max_count = max_count;
+    const int row_tiles = (int)((U + COUPLE_TILE_ROWS - 1) / COUPLE_TILE_ROWS);
+    A.tile_keep = c->table_tiles.p;
+    hipLaunchKernelGGL(k_couple_keep, dim3(row_tiles), dim3(COUPLE_TILE_ROWS), 0, c->stream, A);
+    long long K = 0;
+    CHK(wait_tile_total(c, row_tiles, &K, fn + "bits / band count"));
+    if (K < 0 || K > U) FAIL(c, ARP_E_HIP, fn + "feature count out of range");
+    *n_features = K;
+    if (K > ARP_COUPLE_MAX_FEATURES) FAIL(c, ARP_E_CAPACITY, fn + "more than 65 536 features (narrow the occupancy band)");
+    if (K == 0) return done(U, 0, 0, 0);
+    // ---- the features at their rank: bits, counts and the feature table.  The slab has room for as many pairs as may be kept
+    const long long all_pairs = K * (K - 1) / 2;
+    const long long cap = std::min<long long>({(long long)max_pairs, all_pairs, (1ll << 31) - 1});
+    HIPCHK(c, X.bits.reserve((size_t)(K * fw)));
+    HIPCHK(c, X.n.reserve((size_t)K));
+    const TableLayout room = couple_layout((size_t)K, (size_t)cap);
+    HIPCHK(c, T.slab.reserve(room.bytes));
+    const Columns fcol{T.slab.p, room.off};
+    A.K = K; A.bits = X.bits.p; A.n = X.n.p;
+    A.t_a = fcol[CP_A]; A.t_b = fcol[CP_B]; A.t_count = fcol[CP_COUNT];
+    hipLaunchKernelGGL(k_couple_compact, dim3(row_tiles), dim3(COUPLE_TILE_ROWS), 0, c->stream, A);
+    if (K == 1) {
+        CHK(check_launch(c, (fn + "compact").c_str()));
+        return done(U, 1, 0, 0);
+    }
+    // ---- n11 = B^T B over the tile pairs of the upper triangle, the criterion, the append; the host learns P (wait 3).  The
+    // sorted records are read for the last time by k_couple_compact: their buffers now take the pairs (a buffer that has to
+    // grow is freed once the device is idle: hipFree waits)
+    const long long tiles = (K + SIM_TILE - 1) / SIM_TILE, tile_pairs = tiles * (tiles + 1) / 2;
+    SortScratch& s = c->table_sort;
+    if (cap > 0) CHK(reserve_key_sort(c, s, (size_t)cap, (size_t)cap));
+    HIPCHK(c, hipMemsetAsync(c->table_total.p, 0, sizeof(long long), c->stream));
+    A.tiles = (int)tiles; A.q = phi2_q; A.vbits = index_bits(K);
+    A.total = (unsigned long long*)c->table_total.p; A.pair_key = s.key[0].p; A.pair_val = s.val[0].p; A.cap = cap;
+    hipLaunchKernelGGL(k_couple_gram, dim3((unsigned)tile_pairs), dim3(256), 0, c->stream, A);
+    long long P = 0;
+    CHK(wait_count(c, c->table_total.p, &P, fn + "compact / gram"));
+    if (P < 0 || P > all_pairs) FAIL(c, ARP_E_HIP, fn + "pair count out of range");
+    *n_pairs = P;
+    if (P > cap) FAIL(c, ARP_E_CAPACITY, fn + (P > (long long)max_pairs ? "more kept pairs than max_pairs (raise phi2_q, narrow the band, or come back with *n_pairs)"
+                                                                        : "2^31 kept pairs or more"));
+    if (P == 0) return done(U, K, tile_pairs, 0);
+    // ---- their canonical order: ascending u << vbits | v, then the columns
+    int sorted = 0;
+    enqueue_key_sort(c, s, (size_t)P, 2 * A.vbits, &sorted);
+    const TableLayout lay = couple_layout((size_t)K, (size_t)P);
+    const Columns pcol{T.slab.p, lay.off};
+    A.pair_key = s.key[sorted].p; A.pair_val = s.val[sorted].p; A.P = P;
+    A.t_u = pcol[CP_U]; A.t_v = pcol[CP_V]; A.t_n11 = pcol[CP_N11];
+    hipLaunchKernelGGL(k_couple_rows, dim3(nblocks(P, 256, 2048)), dim3(256), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "sort / rows").c_str()));
+    return done(U, K, tile_pairs, P);
+}
+
+int arp_models_coupling_fetch(arp_ctx* c, int64_t cap_features, int64_t cap_pairs, int32_t* a, int32_t* b, uint32_t* count, uint32_t* u,
+                              uint32_t* v, uint32_t* n11, int64_t* n_features, int64_t* n_pairs) {
+    if (!c || !n_features || !n_pairs) return ARP_E_ARG;
+    const ResultTable& T = c->coupling;
+    if (!c->contacts_valid || !T.valid) FAIL(c, ARP_E_ARG, "arp_models_coupling_fetch: no table (arp_models_coupling_launch after a pass)");
+    const size_t K = (size_t)c->couple.features, P = (size_t)T.count;
+    *n_features = (int64_t)K;
+    *n_pairs = (int64_t)P;
+    if ((int64_t)K > cap_features || (int64_t)P > cap_pairs) FAIL(c, ARP_E_CAPACITY, "arp_models_coupling_fetch: output buffers too small");
+    if (K == 0) return ARP_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const TableLayout L = couple_layout(K, P);
+    CHK(stage_copy(c, T.slab.p, L.bytes));
+    void* const dst[CP_COLS] = {a, b, count, u, v, n11};
+    for (int q = 0; q < CP_COLS; ++q)
+        if (dst[q]) memcpy(dst[q], c->table_stage + L.off[q], (q < CP_FEATURE_COLS ? K : P) * COUPLING_TABLE.es[q]);
+    return ARP_OK;
+}
+
+int arp_models_coupling_info(arp_ctx* c, int64_t info[4]) {
+    if (!c || !info) return ARP_E_ARG;
+    const ResultTable& T = c->coupling;
+    info[0] = T.valid ? c->couple.rows : 0;
+    info[1] = T.valid ? c->couple.features : 0;
+    info[2] = T.valid ? c->couple.tile_pairs : 0;
+    info[3] = T.launches;
     return ARP_OK;
 }
 

@@ -1,6 +1,7 @@
 """What the device-reduced tables share on the host: contact persistence (``persistence``), the residue-pair table
 (``residue_pairs``), residue persistence (``residue_persistence``), the water bridges (``water_bridges``), water-bridge
-persistence (``bridge_persistence``), contact lifetimes (``lifetimes``) and the interaction networks (``networks``).
+persistence (``bridge_persistence``), contact lifetimes (``lifetimes``), the interaction networks (``networks``) and the two
+tables of contact coupling (``coupling``).
 
 A table is a dict of NumPy columns with one row per pair (``NETWORKS``: per component).  A ``Spec`` names the columns in the order of the C fetch's
 arguments (include/arpeggio_hip.h) with their types, and the width of those that hold several values a row.  Everything here
@@ -47,6 +48,8 @@ LIFETIMES = Spec((('a', np.int32), ('b', np.int32), ('n_models', np.uint16), ('f
                   ('n_intervals', np.uint16), ('longest', np.uint16), ('longest_start', np.int32), ('head', np.uint16),
                   ('tail', np.uint16), ('span_sum', np.uint32)), {})
 NETWORKS = Spec((('root', np.int32), ('n_nodes', np.int32), ('n_edges', np.int32), ('sift_or', np.uint16), ('ctype_or', np.uint8)), {})
+COUPLING_FEATURES = Spec((('a', np.int32), ('b', np.int32), ('count', np.uint32)), {})
+COUPLING_PAIRS = Spec((('u', np.uint32), ('v', np.uint32), ('n11', np.uint32)), {})
 BRIDGEPERSIST_ATOM = _bridgepersist('a', 'b')
 BRIDGEPERSIST_RESIDUE = _bridgepersist('res_a', 'res_b')
 

@@ -846,6 +846,63 @@ int arp_models_similarity_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_m
                                  int64_t* n_models, int64_t* n_rows);
 int arp_models_similarity_fetch(arp_ctx* ctx, int64_t cap_models, uint32_t* inter /* [F][F] */, int64_t* n_models);
 int arp_models_similarity_info(arp_ctx* ctx, int64_t info[4]);
+/* Contact coupling over the resident models: which contacts form and break TOGETHER — the salt bridge that opens whenever a
+ * hydrogen bond across the pocket closes, the group of contacts that switches as one when a loop moves.  Similarity above is
+ * B B^T over the models; this is B^T B over the contacts, and only the pairs of contacts that pass a threshold on their phi
+ * coefficient leave the device.  It is an extension beside the mirror; every number is an integer.
+ *
+ * Rows.  Those of similarity: at atom level the distinct topology atom pairs (a, b) of the atom-atom bag (the rows of
+ *   arp_models_persistence); with ARP_COUPLE_BY_RESIDUE the distinct topology residue pairs over the five bags (the rows of
+ *   arp_models_residue_persistence) — a record with a residue of -1 is left out, and a complete pass is needed.
+ * Presence.  Row r is present in model f when a participating record of r in f has a plane in `planes`, the 20-bit mask of
+ *   similarity (at atom level only the planes 0 ... 15 exist); an atom-atom record takes part when bit `ctype` of ctype_mask
+ *   is set, ring and amide records always.  The planes are not kept apart: a row is one contact, present or absent.
+ *   n_r = the models with r present.
+ * Features.  The rows with min_count <= n_r <= max_count, numbered 0 ... K - 1 in ascending row order, which is ascending
+ *   (a, b).  The call requires 1 <= min_count <= max_count <= F - 1: a row of constant presence is never a feature, and the
+ *   variance of a feature is never 0.
+ * Pairs.  For features u < v let n11 = the models with both present and d = F n11 - n_u n_v (signed, 64 bits).  The pair
+ *   is kept when
+ *       1024 d^2 >= q n_u (F - n_u) n_v (F - n_v),    q = phi2_q in 1 ... 1024,
+ *   that is when phi^2 >= q / 1024.  It is a comparison of integers — with F <= ARP_SIM_MAX_MODELS = 4096 both sides stay
+ *   below 2^58 —, equality is kept, and an anti-correlated pair (d < 0) is kept like a correlated one.
+ * Result.  Two tables:
+ *   features   a, b int32 (topology atom ids, or residue ids), count uint32 (n_r)          K rows, ascending (a, b)
+ *   pairs      u, v uint32 (feature numbers, u < v), n11 uint32                            P rows, ascending (u, v)
+ *   The host derives phi, its sign and the Jaccard index from these integers.  Everything is exact and does not depend on
+ *   the order of the records.
+ * Capacity.  max_pairs is the most pairs the caller takes.  With more kept pairs the launch returns ARP_E_CAPACITY, writes
+ *   the exact number into *n_pairs and leaves no result: raise phi2_q, narrow the band, or come back with that capacity.
+ *   Zero kept pairs and K = 0 are valid, empty results.
+ * Out of scope: the chunks of a trajectory streamed through arp_set_models cannot be merged — the threshold is not additive
+ *   over chunks (a pair below it in every chunk may pass it over the whole) —, so one launch covers the resident models only.
+ *
+ * arp_models_coupling_launch: enqueues the work on the context's stream and waits three times, for the rows, for
+ * *n_features = K and for *n_pairs = P.  ARP_E_ARG: a mask of 0 or with bits beyond its bits, an unknown flag, planes
+ * 16 ... 19 at atom level, phi2_q outside 1 ... 1024, max_pairs < 0, a shard, no models resident, a band outside
+ * 1 <= min_count <= max_count <= F - 1 (so F = 1 always), no results of a finished pass (atom level) or of a complete pass
+ * (residue level).  ARP_E_CAPACITY: F > ARP_SIM_MAX_MODELS, (pair, model) does not fit a 63-bit key, 2^31 records or more, a
+ * bit matrix of 4 GiB or more (U x ceil(F / 64) x 8 B), K > ARP_COUPLE_MAX_FEATURES (*n_features = K), more kept pairs than
+ * max_pairs or 2^31 of them (*n_pairs = their number).  A second call with the same eight arguments on the same results
+ * returns without work; other arguments remake the result.  It is voided wherever similarity of its level is: by every input
+ * change and by the next launch that refills a bag it reads — the atom-atom bag, at residue level also the ring and amide
+ * bags.  It reads the bags as the pass left them and writes no bag, no sorted slab, no filtered bag and no other result:
+ * every other fetch returns the same before, after and without these calls, and no other derived result voids it.
+ *
+ * arp_models_coupling_fetch: both tables with one device-to-host copy through the page-locked stage; any column pointer may
+ * be NULL.  ARP_E_CAPACITY with *n_features = K and *n_pairs = P when a cap is too small; ARP_E_ARG without a launch (or
+ * after one that returned ARP_E_CAPACITY).  Empty tables copy nothing.
+ *
+ * arp_models_coupling_info: info[0] = rows U, info[1] = features K, info[2] = tile pairs of the product's grid (64 x 64
+ * features a tile, upper triangle), info[3] = launches of this context that did work (one that returned a resident result
+ * does not count).  [0 ... 2] are 0 while no result is resident. */
+#define ARP_COUPLE_BY_RESIDUE 1u
+#define ARP_COUPLE_MAX_FEATURES 65536    /* 1024 tiles a side: 524 800 tile pairs; feature numbers fit 16 + 16 key bits */
+int arp_models_coupling_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, uint32_t min_count,
+                               uint32_t max_count, uint32_t phi2_q, int64_t max_pairs, int64_t* n_features, int64_t* n_pairs);
+int arp_models_coupling_fetch(arp_ctx* ctx, int64_t cap_features, int64_t cap_pairs, int32_t* a, int32_t* b, uint32_t* count,
+                              uint32_t* u, uint32_t* v, uint32_t* n11, int64_t* n_features, int64_t* n_pairs);
+int arp_models_coupling_info(arp_ctx* ctx, int64_t info[4]);
 /* Contact lifetimes over the resident models: how LONG a contact lasts and how often it forms and breaks, where the
  * persistence table gives the fraction of models that have it.  The models are an ordered axis (for a trajectory streamed
  * through arp_set_models, model f is time).  It is an extension beside the mirror; every column is an integer.
