@@ -48,10 +48,13 @@ SYMBOLS = (
     'arp_models_coupling_launch', 'arp_models_coupling_fetch', 'arp_models_coupling_info',
     'arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', 'arp_models_lifetimes_info',
     'arp_networks_launch', 'arp_networks_fetch', 'arp_networks_labels_fetch', 'arp_networks_info',
+    'arp_poses_contacts_launch', 'arp_poses_contacts_fetch', 'arp_poses_contacts_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
 PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
+# ligand poses on the resident receptor (ARP_POSES_*)
+POSES_MAX_ATOMS, POSES_MAX_POSES, POSES_MAX_CUTOFF, POSES_SUMMARY = 1024, 1 << 20, 6.0, 16
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -227,6 +230,9 @@ def load():
     L.arp_networks_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64)]
     L.arp_networks_labels_fetch.argtypes = [vp, i64, vp, C.POINTER(i64)]
     L.arp_networks_info.argtypes = [vp, vp]
+    L.arp_poses_contacts_launch.argtypes = [vp, i64, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(i64)]
+    L.arp_poses_contacts_fetch.argtypes = [vp, i64] + [vp] * 7 + [C.POINTER(i64)]
+    L.arp_poses_contacts_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -646,6 +652,7 @@ class Context:
         self._check(L.arp_set_amides(h, pc.n_amides, _p(pc.amide_center), _p(pc.amide_normal), _p(pc.amide_res)), 'arp_set_amides')
         self.n, self.n_rings, self.n_amides = pc.n_atoms, pc.n_rings, pc.n_amides
         self._models = None
+        self._sel = None             # (a new structure starts with everything selected)
 
     def set_batch(self, pcs, selections=None):
         """Several structures in one pass (arpeggio_amd.batch): uploads the concatenation of ``pcs`` and tells the library
@@ -714,6 +721,7 @@ class Context:
         if hx.shape != (F, t['nh'], 3):
             raise ValueError(f'set_models: h_xyz must be [{F}, {t["nh"]}, 3]')
         self._models = None
+        self._sel = None
         self.n = self.n_rings = self.n_amides = 0      # (a failed call leaves nothing resident)
         self._check(self._L.arp_set_models(self._h, F, _p(x), _p(hx)), 'arp_set_models')
         self.n, self.n_rings, self.n_amides = F * t['n'], F * t['nring'], F * t['namide']
@@ -871,10 +879,77 @@ class Context:
         self._check(self._L.arp_networks_labels_fetch(self._h, len(label), _p(label), C.byref(N)), 'arp_networks_labels_fetch')
         return label, table
 
+    def _poses_launch(self, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent):
+        """Shapes checked against the uploaded selection, then arp_poses_contacts_launch; returns (P, records, movable ids)."""
+        sel = getattr(self, '_sel', None)
+        if sel is None or len(sel) != self.n:
+            raise ValueError('poses_contacts: no uploaded selection (set_selection names the movable set)')
+        atoms = np.nonzero(sel)[0].astype(np.int32)
+        S = len(atoms)
+        x = np.ascontiguousarray(xyz, np.float32)
+        if x.ndim != 3 or x.shape[1:] != (S, 3) or x.shape[0] < 1:
+            raise ValueError(f'poses_contacts: xyz must be [P >= 1, {S}, 3] (the selected atoms in ascending order)')
+        P = x.shape[0]
+        hx = np.zeros((P, 0, 3)) if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64)
+        # (the library reads P * SH rows: the shape is checked here, where the hydrogen offsets of the resident structure are known)
+        keep = getattr(self, '_keep', None)
+        h_off = getattr(keep, 'h_off', None)
+        if h_off is None and isinstance(keep, np.ndarray):
+            h_off = unpack_blob(keep)['h_off']
+        if h_off is None or len(h_off) != self.n + 1:
+            raise ValueError('poses_contacts: the hydrogen offsets of the resident structure are not known to this context')
+        SH = int(np.diff(np.asarray(h_off, np.int64))[atoms].sum()) if S else 0
+        if hx.shape != (P, SH, 3):
+            raise ValueError(f'poses_contacts: h_xyz must be [{P}, {SH}, 3] (the hydrogen rows of the selected atoms, h_off order)')
+        n = C.c_int64(0)
+        rc = self._L.arp_poses_contacts_launch(self._h, P, _p(x), _p(hx) if SH else None, float(cutoff), float(vdw_comp),
+                                               int(bool(include_sequence_adjacent)), C.byref(n))
+        try:
+            self._check(rc, 'arp_poses_contacts_launch')
+        except NativeLibraryError as e:
+            e.n_records = int(n.value)
+            raise
+        return P, int(n.value), atoms
+
+    def poses_contacts(self, xyz, h_xyz, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False):
+        """Every pose's ligand - receptor contacts in one launch (arp_poses_contacts_*; ``arpeggio_amd.poses``).  The uploaded
+        selection is the movable set; ``xyz`` float32 [P, S, 3] its atoms' coordinates per pose (ascending packed order),
+        ``h_xyz`` float64 [P, SH, 3] the hydrogen rows of those atoms (``poses.movable`` gives both index lists).  Returns a dict:
+        ``i, j, dist, sift, ctype`` — per pose exactly the atom-atom records with one selected and one unselected atom of a pass
+        over the structure with the pose scattered in, in ascending (pose, i, j) —, ``pose_off`` uint64 [P + 1], ``summary``
+        uint32 [P, 16] (records per SIFt bit, slot 15 the total) and ``movable`` (the selected atom ids).  At most
+        ``POSES_MAX_POSES`` poses a call (``poses.concat`` joins chunks); ``cutoff`` <= 6.0.  The bags of the last pass and
+        every table made from them stay as they are."""
+        P, k, atoms = self._poses_launch(xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
+        t = dict(i=np.empty(k, np.int32), j=np.empty(k, np.int32), dist=np.empty(k, np.float32), sift=np.empty(k, np.uint16),
+                 ctype=np.empty(k, np.uint8), pose_off=np.empty(P + 1, np.uint64), summary=np.empty((P, POSES_SUMMARY), np.uint32))
+        n = C.c_int64(0)
+        self._check(self._L.arp_poses_contacts_fetch(self._h, k, _p(t['pose_off']), _p(t['i']), _p(t['j']), _p(t['dist']), _p(t['sift']),
+                                                     _p(t['ctype']), _p(t['summary']), C.byref(n)), 'arp_poses_contacts_fetch')
+        t['movable'] = atoms
+        return t
+
+    def poses_summary(self, xyz, h_xyz, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False):
+        """``poses_contacts`` with only the per-pose summary copied to the host: uint32 [P, 16], records per SIFt bit and, in
+        slot 15, all records of the pose — for ranking many poses without copying a record."""
+        P, _, _ = self._poses_launch(xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
+        s = np.empty((P, POSES_SUMMARY), np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.arp_poses_contacts_fetch(self._h, 0, None, None, None, None, None, None, _p(s), C.byref(n)),
+                    'arp_poses_contacts_fetch')
+        return s
+
+    def poses_info(self):
+        """(P, S, SH, records) of the resident poses result, zeros while there is none (arp_poses_contacts_info)."""
+        info = np.zeros(4, np.int64)
+        self._check(self._L.arp_poses_contacts_info(self._h, _p(info)), 'arp_poses_contacts_info')
+        return dict(poses=int(info[0]), atoms=int(info[1]), hydrogens=int(info[2]), records=int(info[3]))
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
         self._models = None
+        self._sel = None
         self._check(self._L.arp_set_blob(self._h, _p(blob), int(blob.nbytes)), 'arp_set_blob')
         hdr = BlobHeader.from_buffer_copy(blob[:C.sizeof(BlobHeader)].tobytes())
         self.n, self.n_rings, self.n_amides = int(hdr.n), int(hdr.nring), int(hdr.namide)
@@ -984,6 +1059,7 @@ class Context:
     def set_selection_state(self, sel, plus, ring_sel, ring_plus, amide_sel, amide_plus):
         a = [np.ascontiguousarray(x, np.uint8) for x in (sel, plus, ring_sel, ring_plus, amide_sel, amide_plus)]
         self._check(self._L.arp_set_selection_state(self._h, *[_p(x) for x in a]), 'arp_set_selection_state')
+        self._sel = None
 
     BUF_PLUS, BUF_RES_SETS, BUF_GRID_START, BUF_KEEP_BASE = 0, 1, 2, 3
 
@@ -1042,6 +1118,7 @@ class Context:
         if sel.shape != (self.n,):
             raise ValueError('in_selection must have one entry per atom')
         self._check(self._L.arp_set_selection(self._h, _p(sel)), 'arp_set_selection')
+        self._sel = sel.copy()       # (the movable set of poses_contacts)
 
     def run_enqueue(self, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False, expand_radius=6.0):
         """First half of ``run_launch``: the pass is enqueued, the call returns.  Pair with ``run_wait``."""

@@ -408,6 +408,46 @@ class InteractionComplex:
         label, table = self.networks(contacts, interacting_entities, level)
         return nw.write_networks(wd, self.id, label, table, self.pc, level, self.component_types)
 
+    def run_poses(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None):
+        """Extension beside the mirror (the reference evaluates one placement per run): the contacts of many poses of a ligand
+        against this structure as the fixed receptor.  ``user_selections`` names the ligand, the MOVABLE SET (selectors, or
+        an integer array of packed atom ids); ``xyz`` float32 [P, S, 3] are its atoms' coordinates per pose in ascending packed
+        order and ``h_xyz`` float64 [P, SH, 3] the hydrogen rows of those atoms (``arpeggio_amd.poses.movable`` lists both).
+        Per pose the result holds exactly the atom-atom records between the ligand and the rest that ``run_arpeggio`` would
+        find on the structure with the pose scattered in — computed on the GPU against the resident receptor, only the poses
+        uploaded.  Returns the table ``arpeggio_amd.poses`` describes (also kept in ``self.poses``); the poses go to the device
+        ``chunk`` at a time (default: all at once, at most ``_capi.POSES_MAX_POSES``).  ``interacting_cutoff`` <= 6.0.  The
+        results of the last ``run_arpeggio`` stay as they are, but the selection on the device is the ligand from here on."""
+        from .. import _capi, poses as _poses
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx = self.pc, self._ctx
+        if isinstance(user_selections, np.ndarray):
+            idx = np.unique(user_selections.astype(np.int64))
+        else:
+            idx = utils.selection_parser(user_selections, pc) if user_selections else np.zeros(0, np.int64)
+        if idx.size == 0:
+            raise AttributeError('Selection must not be empty.')
+        mask = np.zeros(pc.n_atoms, np.uint8)
+        mask[idx] = 1
+        ctx.set_selection(mask)
+        x = np.ascontiguousarray(xyz, np.float32)
+        h = None if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64)
+        step = int(chunk) if chunk else min(max(len(x), 1), _capi.POSES_MAX_POSES)
+        parts = [ctx.poses_contacts(x[a:a + step], None if h is None else h[a:a + step], interacting_cutoff, vdw_comp, include_sequence_adjacent)
+                 for a in range(0, len(x), step)]
+        if not parts:
+            raise ValueError('run_poses: no pose given')
+        self.poses = parts[0] if len(parts) == 1 else _poses.concat(parts)
+        return self.poses
+
+    def write_poses(self, wd):
+        """'<id>.poses': the table of the last ``run_poses`` as CSV, one row per record (``poses.write_csv``)."""
+        from .. import poses as _poses
+        if getattr(self, 'poses', None) is None:
+            raise AttributeError('no poses yet: call run_poses() first')
+        return _poses.write_poses(wd, self.id, self.poses, self.pc, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""

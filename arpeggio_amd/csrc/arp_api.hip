@@ -38,6 +38,7 @@
 #include "arp_coupling.h"
 #include "arp_lifetimes.h"
 #include "arp_networks.h"
+#include "arp_poses.h"
 #include "arp_blob.h"
 
 namespace {
@@ -291,6 +292,23 @@ struct CouplingScratch {
     uint32_t flags = 0;
 };
 
+// the contacts of ligand poses on the resident receptor (arp_poses_contacts_launch): the movable set's tables (made once per
+// structure and selection), the uploaded poses, the appended records and their sort, the result's columns in one slab
+struct PosesResult {
+    DevBuf<int> sel_h, pos_of;
+    uint64_t movable_static = 0, movable_sel = 0;       // static_epoch / sel_epoch the tables were made for (0: none)
+    DevBuf<float> xyz;
+    DevBuf<double> hx;
+    DevBuf<unsigned long long> ctr;                     // [0] records appended, [1] device error
+    DevBuf<uint32_t> summary;
+    DevBuf<unsigned long long> pose_off;
+    SortScratch sort;
+    DevBuf<uint8_t> slab;
+    size_t off[5] = {0, 0, 0, 0, 0};
+    int64_t P = 0, S = 0, SH = 0, count = 0;
+    bool valid = false;
+};
+
 struct arp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless arp_use_stream)
@@ -319,6 +337,8 @@ struct arp_ctx {
     DevBuf<int> bond_off, bond_idx, h_off;
     DevBuf<double> h_xyz_d;
     DevBuf<float4> sb;           // single-bond neighbour xyz, w = 1 if present
+    DevBuf<int> sb_idx;          // ... and which atom it is, as arp_set_single_bond_neighbours uploaded it
+    int sb_index_src = 0;        // where the resident neighbour INDEX is: 0 nowhere (coordinates only), 1 sb_idx, 2 blob_sb_nbr
     DevBuf<int> gid;
     DevBuf<uint8_t> home, sel, plus, res_sel, res_plus;
     bool has_res = false, has_gid = false, has_home = false;
@@ -528,6 +548,7 @@ struct arp_ctx {
     int64_t net_nodes = 0;
     ResultTable coupling;                 // arp_models_coupling_launch: features and pairs in one slab; count = kept pairs
     CouplingScratch couple;
+    PosesResult poses;                    // arp_poses_contacts_launch: reads no bag, voided with the inputs (inputs_changed)
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -813,6 +834,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->contacts_valid = false;
         void_results(c, RES_AA | RES_PLANES);
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
+        c->poses.valid = false;      // (made from the inputs alone, the selection among them: no row in void_results)
     }
 }
 
@@ -2346,6 +2368,8 @@ void arp_destroy(arp_ctx* c) {
     c->lifetimes.slab.release();
     c->networks.slab.release(); c->net_label.release(); c->net_scratch.release();
     c->similarity.bits.release(); c->similarity.inter.release();
+    c->poses.sel_h.release(); c->poses.pos_of.release(); c->poses.xyz.release(); c->poses.hx.release(); c->poses.ctr.release();
+    c->poses.summary.release(); c->poses.pose_off.release(); c->poses.sort.release(); c->poses.slab.release(); c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
@@ -2394,6 +2418,7 @@ int arp_set_atoms(arp_ctx* c, int64_t n, const float* xyz, const double* vdw, co
     // uploads below are enqueued together; whatever the exit path, they are complete before the staging vectors die
     struct SyncOnExit { arp_ctx* c; ~SyncOnExit() { (void)hipStreamSynchronize(c->stream); } } sync_on_exit{c};
     inputs_changed(c, IN_ATOMS);
+    c->sb_index_src = 0;         // (of the atoms before: arp_set_single_bond_neighbours follows)
     c->n = n;
     c->h_xyz.assign(xyz, xyz + 3 * n);
     points_box(xyz, n, c->lo, c->hi);
@@ -2493,10 +2518,12 @@ int arp_set_single_bond_neighbours(arp_ctx* c, const int32_t* sb_nbr) {
     for (int64_t i = 0; i < c->n; ++i)
         if (sb_nbr[i] < -1 || sb_nbr[i] >= c->n) FAIL(c, ARP_E_ARG, "arp_set_single_bond_neighbours: index out of range");
     // the neighbour's coordinates are gathered on the device from the uploaded atoms (x, y, z, 1) / (0, 0, 0, 0)
-    CHK(upload(c, c->tmp_i32, sb_nbr, (size_t)c->n));
+    // (the index stays resident: a pose that moves the neighbour moves these coordinates with it, arp_poses.h)
+    CHK(upload(c, c->sb_idx, sb_nbr, (size_t)c->n));
+    c->sb_index_src = 1;
     HIPCHK(c, c->sb.reserve((size_t)std::max<int64_t>(c->n, 1)));
     if (c->n > 0) {
-        hipLaunchKernelGGL(k_gather_neighbours, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, (int)c->n, c->tmp_i32.p, c->xyz.p, c->sb.p);
+        hipLaunchKernelGGL(k_gather_neighbours, dim3(nblocks(c->n, 256)), dim3(256), 0, c->stream, (int)c->n, c->sb_idx.p, c->xyz.p, c->sb.p);
         CHK(check_launch(c, "k_gather_neighbours"));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -2582,6 +2609,7 @@ void borrow_blob_views(arp_ctx* c, const arp_blob_header& h) {
     c->bond_off.borrow(at(BLOB_BOND_OFF), (size_t)h.n + 1); c->bond_idx.borrow(at(BLOB_BOND_IDX), atleast1(h.nbond));
     c->h_off.borrow(at(BLOB_H_OFF), (size_t)h.n + 1); c->h_xyz_d.borrow(at(BLOB_H_XYZ), (size_t)std::max<int64_t>(3 * h.nh, 3));
     c->blob_sb_nbr.borrow(at(BLOB_SB_NBR), n1);
+    c->sb_index_src = 2;
     c->ring_c.borrow(at(BLOB_RING_C), atleast1(3 * h.nring)); c->ring_n.borrow(at(BLOB_RING_N), atleast1(3 * h.nring));
     c->ring_res.borrow(at(BLOB_RING_RES), atleast1(h.nring));
     c->am_c.borrow(at(BLOB_AMIDE_C), atleast1(3 * h.namide)); c->am_n.borrow(at(BLOB_AMIDE_N), atleast1(3 * h.namide));
@@ -3046,6 +3074,7 @@ int arp_set_single_bond_neighbour_coords(arp_ctx* c, const float* sb_xyz, const 
     if (!c || (c->n > 0 && (!sb_xyz || !sb_present))) return ARP_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     inputs_changed(c, IN_NEIGHBOURS);
+    c->sb_index_src = 0;
     std::vector<float4> sb((size_t)c->n);
     for (int64_t i = 0; i < c->n; ++i)
         sb[i] = sb_present[i] ? make_float4(sb_xyz[3 * i], sb_xyz[3 * i + 1], sb_xyz[3 * i + 2], 1.0f) : make_float4(0, 0, 0, 0);
@@ -5210,6 +5239,153 @@ int arp_models_coupling_info(arp_ctx* c, int64_t info[4]) {
     info[1] = T.valid ? c->couple.features : 0;
     info[2] = T.valid ? c->couple.tile_pairs : 0;
     info[3] = T.launches;
+    return ARP_OK;
+}
+
+// ---- ligand poses on the resident receptor (arp_poses.h): every pose's ligand - receptor records in one launch
+// No bag is read and none is written: the receptor is the static columns in the cell order of ensure_static(cutoff), the poses
+// are uploaded, the records are appended as (key, payload), sorted by every bit of the key (enqueue_key_sort over the result's
+// own scratch) and unpacked into a slab laid out as the sorted atom-atom bag is.  Two waits: SH when the movable set is new, and
+// the record count (with the device's error word).  A record buffer that was too small is grown to the exact count and the
+// launch repeated: nothing is truncated.
+static_assert(POSES_MAX_ATOMS == ARP_POSES_MAX_ATOMS && POSES_MAX_ATOMS == SMALL_SEL_MAX && POSES_MAX_POSES == ARP_POSES_MAX_POSES &&
+              POSES_SUMMARY == ARP_POSES_SUMMARY, "arp_poses.h names the header's limits; sel_list holds up to SMALL_SEL_MAX atoms");
+int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, const double* h_xyz, double cutoff, double vdw_comp,
+                              int include_sequence_adjacent, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const std::string fn = "arp_poses_contacts_launch: ";
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
+    if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
+    if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
+    if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
+    if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
+    if (n_poses < 1 || n_poses > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    if (c->n >= POSES_MAX_N) FAIL(c, ARP_E_ARG, fn + "2^21 atoms or more (the sort key holds 21 bits per atom id)");
+    if (!(cutoff > 0) || !(cutoff <= ARP_POSES_MAX_CUTOFF)) FAIL(c, ARP_E_ARG, fn + "cutoff must be in (0, 6.0] (beyond 6.0 selection_plus would depend on the pose)");
+    if (!std::isfinite(vdw_comp)) FAIL(c, ARP_E_ARG, fn + "vdw_comp is not finite");
+    if (c->sb_index_src == 0) FAIL(c, ARP_E_ARG, fn + "single-bond neighbours were given as coordinates only (arp_set_single_bond_neighbour_coords): which atom moves with a pose is not known");
+    if (!xyz) FAIL(c, ARP_E_ARG, fn + "xyz missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    CHK(ensure_static(c, cutoff));
+    PosesResult& R = c->poses;
+    const int n = (int)c->n, S = (int)c->nsel;
+    const int64_t P = n_poses;
+    // ---- the movable set's tables, once per structure and selection (the first wait: SH)
+    if (R.movable_static != c->static_epoch || R.movable_sel != c->sel_epoch) {
+        R.movable_static = R.movable_sel = 0;
+        HIPCHK(c, R.sel_h.reserve((size_t)S + 1));
+        HIPCHK(c, R.pos_of.reserve((size_t)n));
+        HIPCHK(c, hipMemsetAsync(R.pos_of.p, 0xFF, (size_t)n * sizeof(int), c->stream));
+        hipLaunchKernelGGL(k_poses_movable, dim3(1), dim3(1024), 0, c->stream, S, c->sel_list.p, c->h_off.p, R.sel_h.p, R.pos_of.p);
+        CHK(check_launch(c, "k_poses_movable"));
+        CHK(stage_copy(c, R.sel_h.p + S, sizeof(int)));
+        int sh = 0;
+        memcpy(&sh, c->table_stage, sizeof(sh));
+        if (sh < 0) FAIL(c, ARP_E_HIP, fn + "hydrogen count of the movable set out of range");
+        R.SH = sh;
+        R.S = S;
+        R.movable_static = c->static_epoch; R.movable_sel = c->sel_epoch;
+    }
+    const int64_t SH = R.SH;
+    if (SH > 0 && !h_xyz) FAIL(c, ARP_E_ARG, fn + "h_xyz missing (the movable set has hydrogens)");
+    // ---- from here on the previous result is gone
+    R.valid = false;
+    R.count = 0;
+    HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
+    HIPCHK(c, R.hx.reserve(std::max<size_t>((size_t)P * (size_t)SH * 3, 1)));
+    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)P * S * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (SH > 0) HIPCHK(c, hipMemcpyAsync(R.hx.p, h_xyz, (size_t)P * (size_t)SH * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, R.ctr.reserve(2));
+    HIPCHK(c, R.summary.reserve((size_t)P * POSES_SUMMARY));
+    HIPCHK(c, R.pose_off.reserve((size_t)P + 1));
+    PoseArgs A{};
+    A.n = n; A.S = S; A.P = (int)P; A.SH = SH;
+    A.sel_list = c->sel_list.p; A.sel_h = R.sel_h.p; A.pos_of = R.pos_of.p; A.sel = c->sel.p;
+    A.pxyz = R.xyz.p; A.phx = R.hx.p;
+    A.st_xyzm = c->st_xyzm.p; A.st_aux = c->st_aux.p; A.st_qa = c->st_qa.p; A.h_off = c->h_off.p; A.rad = c->rad.p; A.sb = c->sb.p;
+    A.sb_nbr = c->sb_index_src == 1 ? c->sb_idx.p : c->blob_sb_nbr.p;
+    A.bond_off = c->bond_off.p; A.bond_idx = c->bond_idx.p; A.h_xyz = c->h_xyz_d.p;
+    A.sp_xyzm = c->sp_xyzm.p; A.sp_aux = c->sp_aux.p; A.sp_qa = c->sp_qa.p; A.sp_h = c->sp_h.p;
+    A.start = c->sp_cnt.p + 4; A.g = c->sp_grid;
+    A.r2 = cutoff * cutoff; A.comp = vdw_comp; A.include_seq_adj = include_sequence_adjacent ? 1 : 0;
+    A.idbits = index_bits(c->n);
+    A.count = R.ctr.p; A.err = (int*)(R.ctr.p + 1);
+    A.summary = R.summary.p;
+    const int keybits = 2 * A.idbits + index_bits(P);
+    const size_t limit = ((size_t)1 << 31) - 1;
+    size_t cap = std::min(limit, std::max<size_t>((size_t)1 << 16, (size_t)P * (size_t)S * 32));
+    unsigned long long h[2] = {0, 0};
+    for (int attempt = 0;; ++attempt) {
+        CHK(reserve_key_sort(c, R.sort, cap, cap));
+        A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
+        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_poses_contacts, dim3((unsigned)P), dim3(POSES_THREADS), 0, c->stream, A);
+        CHK(check_launch(c, "k_poses_contacts"));
+        CHK(stage_copy(c, R.ctr.p, sizeof(h)));
+        memcpy(h, c->table_stage, sizeof(h));
+        const int dev = (int)(uint32_t)h[1];
+        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
+        if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
+        if (dev != 0) FAIL(c, ARP_E_HIP, fn + "device error");
+        if (h[0] <= cap) break;
+        *count = (int64_t)h[0];
+        if (h[0] > limit) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more (fewer poses a launch)");
+        if (attempt == 2) FAIL(c, ARP_E_CAPACITY, fn + "record buffer could not be sized");
+        cap = (size_t)h[0];
+    }
+    const size_t k = (size_t)h[0];
+    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)P, R.summary.p, R.pose_off.p);
+    if (k > 0) {
+        int sorted = 0;
+        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
+        size_t bytes = 0;
+        sorted_layout(k, R.off, &bytes, k);
+        HIPCHK(c, R.slab.reserve(bytes));
+        const Columns col{R.slab.p, R.off};
+        hipLaunchKernelGGL(k_poses_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, A.idbits,
+                           R.sort.key[sorted].p, R.sort.val[sorted].p, (int*)col[0], (int*)col[1], (float*)col[2], (uint16_t*)col[3], (uint8_t*)col[4]);
+    }
+    CHK(check_launch(c, "k_poses_offsets / sort / k_poses_columns"));
+    R.P = P; R.count = (int64_t)k; R.valid = true;
+    *count = R.count;
+    return ARP_OK;
+}
+
+int arp_poses_contacts_fetch(arp_ctx* c, int64_t cap, uint64_t* pose_off, int32_t* i, int32_t* j, float* dist, uint16_t* sift,
+                             uint8_t* ctype, uint32_t* summary, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const PosesResult& R = c->poses;
+    if (!R.valid) FAIL(c, ARP_E_ARG, "arp_poses_contacts_fetch: no result (arp_poses_contacts_launch; an input or the selection changed since)");
+    *count = R.count;
+    const bool records = i || j || dist || sift || ctype;
+    if (records && R.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_poses_contacts_fetch: output buffers too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)R.count;
+    CHK(download_async(c, (unsigned long long*)pose_off, (const unsigned long long*)R.pose_off.p, (size_t)R.P + 1));
+    CHK(download_async(c, summary, (const uint32_t*)R.summary.p, (size_t)R.P * POSES_SUMMARY));
+    if (records && k > 0) {
+        const uint8_t* const slab = R.slab.p;
+        CHK(download_async(c, i, (const int32_t*)(slab + R.off[0]), k));
+        CHK(download_async(c, j, (const int32_t*)(slab + R.off[1]), k));
+        CHK(download_async(c, dist, (const float*)(slab + R.off[2]), k));
+        CHK(download_async(c, sift, (const uint16_t*)(slab + R.off[3]), k));
+        CHK(download_async(c, ctype, (const uint8_t*)(slab + R.off[4]), k));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ARP_OK;
+}
+
+int arp_poses_contacts_info(arp_ctx* c, int64_t info[4]) {
+    if (!c || !info) return ARP_E_ARG;
+    const PosesResult& R = c->poses;
+    info[0] = R.valid ? R.P : 0;
+    info[1] = R.valid ? R.S : 0;
+    info[2] = R.valid ? R.SH : 0;
+    info[3] = R.valid ? R.count : 0;
     return ARP_OK;
 }
 

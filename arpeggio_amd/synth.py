@@ -703,3 +703,44 @@ def models_of(pc: PackedComplex, n_models: int, seed: int = 0, jitter: float = 0
                 h = h + noise[3 * n:].reshape(nh, 3)
             xyz[f], h_xyz[f] = a.astype(np.float32), h
     return xyz, h_xyz
+
+
+def poses_of(pc: PackedComplex, sel, n_poses: int, seed: int = 0, shift: float = 3.0, jitter: float = 0.0, stretch: float = 0.0):
+    """Poses of the movable set ``sel`` (mask or atom ids; ``arpeggio_amd.poses.movable``) of ``pc`` for
+    ``Context.poses_contacts``: ``(xyz float32 [P, S, 3], h_xyz float64 [P, SH, 3])``.  Pose 0 is the resident coordinates;
+    every other pose is the movable set turned as a rigid body about its centroid (a random rotation) and shifted by up to
+    ``shift`` A per axis, so every bond inside the set keeps its length.  ``jitter`` > 0 adds independent normal noise of that
+    sigma to every atom and hydrogen row; ``stretch`` scales the vector from each parent atom to its hydrogen rows by
+    1 + ``stretch`` (X-H distances beyond any of the resident structure).  Hydrogens that are atoms of the set move with it as
+    atoms and are not stretched (a pass skips them)."""
+    from . import poses as _poses
+    atoms, rows = _poses.movable(pc, sel)
+    P, S, SH = int(n_poses), len(atoms), len(rows)
+    x0 = np.asarray(pc.xyz, np.float64)[atoms]
+    h0 = np.asarray(pc.h_xyz, np.float64).reshape(-1, 3)[rows]
+    owner = np.repeat(np.arange(pc.n_atoms), np.diff(np.asarray(pc.h_off, np.int64)))[rows]
+    parent = np.searchsorted(atoms, owner)                               # position of every row's parent in the set
+    xyz = np.empty((P, S, 3), np.float32)
+    h_xyz = np.empty((P, SH, 3), np.float64)
+    if P < 1:
+        return xyz, h_xyz
+    xyz[0], h_xyz[0] = pc.xyz[atoms], h0
+    centre = x0.mean(axis=0) if S else np.zeros(3)
+    if P > 1:
+        rot = _rotation_matrices(seed, 50, np.arange(1, P, dtype=np.uint64))
+        for f in range(1, P):
+            k = np.arange(3 * f, 3 * f + 3, dtype=np.uint64)
+            move = shift * (2.0 * u01(seed, 53, k) - 1.0)
+            R = rot[f - 1]
+            a = (x0 - centre) @ R.T + centre + move
+            h = (h0 - centre) @ R.T + centre + move
+            if jitter > 0:
+                idx = np.arange(3 * (S + SH), dtype=np.uint64) + np.uint64(f * 3 * (S + SH + 1))
+                g1, g2 = np.maximum(u01(seed, 56, idx), 1e-12), u01(seed, 57, idx)
+                noise = jitter * np.sqrt(-2.0 * np.log(g1)) * np.cos(2.0 * np.pi * g2)
+                a = a + noise[:3 * S].reshape(S, 3)
+                h = h + noise[3 * S:].reshape(SH, 3)
+            if stretch != 0.0 and SH:
+                h = a[parent] + (1.0 + stretch) * (h - a[parent])
+            xyz[f], h_xyz[f] = a.astype(np.float32), h
+    return xyz, h_xyz

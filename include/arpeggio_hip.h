@@ -987,6 +987,62 @@ int arp_networks_fetch(arp_ctx* ctx, int64_t cap, int32_t* root, int32_t* n_node
                        uint8_t* ctype_or, int64_t* count);
 int arp_networks_labels_fetch(arp_ctx* ctx, int64_t cap, int32_t* label, int64_t* nodes);
 int arp_networks_info(arp_ctx* ctx, int64_t info[3]);
+/* Ligand poses on the resident receptor: every pose's ligand - receptor contacts in one launch (csrc/arp_poses.h).  Docking and
+ * virtual screening keep the receptor fixed and move the ligand thousands of times; what is wanted of each placement is its
+ * interaction fingerprint.  The receptor is uploaded once; a pose is 12 bytes per ligand atom and 24 per ligand hydrogen.  It
+ * is an extension beside the mirror.
+ *
+ * Contract.  ONE structure is resident (no batch, no models, no shard) with a selection uploaded by arp_set_selection: the
+ *   MOVABLE SET, its S selected atoms in ascending packed order, 1 <= S <= ARP_POSES_MAX_ATOMS, S < n.  A pose is
+ *   xyz    float32 [S][3]   coordinates of those atoms, in that order
+ *   h_xyz  float64 [SH][3]  coordinates of the hydrogen rows (h_off order) whose parent atom is selected; SH is answered by
+ *                           arp_poses_contacts_info after a launch and is a function of structure and selection
+ *   and a launch takes n_poses of them, pose-major.  h_xyz may be NULL when SH = 0.
+ * Result.  For pose p exactly the atom-atom records with one selected and one unselected atom that a pass would emit if it ran on
+ *   the structure with those coordinates scattered in, with the same selection and the same (cutoff, vdw_comp,
+ *   include_sequence_adjacent): the same i < j by packed id, the same float32 distance bits, the same 15-bit SIFt, the same
+ *   contact type.  Records of two selected or two unselected atoms are not produced.  The records are in ascending (pose, i, j).
+ *   Of a selected atom everything the decision reads is the pose's — its coordinate, its hydrogens, and the coordinate of its
+ *   single-bond neighbour when that neighbour is selected too —; of an unselected atom everything is the resident structure's,
+ *   except that ITS single-bond neighbour moves with the pose when that neighbour is selected (the uploaded neighbour index
+ *   says which atom it is).  The covalent test is membership in the bond list at any distance; a pose may stretch bonds and
+ *   X-H distances beyond any of the resident structure.
+ *   summary  uint32 [n_poses][ARP_POSES_SUMMARY]  per pose: records with SIFt bit k (ARP_S_CLASH ... ARP_S_WEAK_POLAR) in slot
+ *                           k < 15, all its records in slot 15 — enough to rank poses without copying a record
+ *   pose_off uint64 [n_poses + 1]  the records of pose p are [pose_off[p], pose_off[p + 1])
+ * Limits.  cutoff <= ARP_POSES_MAX_CUTOFF = 6.0: every accepted partner of a selected atom is then inside selection_plus
+ *   whatever the pose (I:1420-1424), so no expansion is needed; beyond it membership would depend on the other ligand atoms.
+ *   n < 2^21 and n_poses <= ARP_POSES_MAX_POSES a launch (the records are sorted by a 64-bit key of pose and two atom ids);
+ *   callers chunk their poses.  Fewer than 2^31 records a launch.
+ *   Not produced: atom-plane and plane-plane records of a pose (the ligand's own rings and amides), the per-atom accumulators.
+ *
+ * arp_poses_contacts_launch: uploads the poses, enqueues the work on the context's stream (arp_use_stream's, if set) and waits
+ * for *count = records (and once per structure and selection for SH).  ARP_E_ARG with a message naming the cause: no
+ * structure resident; a batch, models or shard ownership resident; no selection uploaded by arp_set_selection; a selection
+ * of the whole structure; S or n_poses beyond the limits; cutoff > 6.0 or <= 0; single-bond neighbours given as coordinates
+ * only (arp_set_single_bond_neighbour_coords); a pass enqueued and not waited for.  None of these touches a resident result.
+ * A non-finite pose coordinate, found on the device: ARP_E_ARG and NO result — the result of the launch before is gone as
+ * well, since a launch that has passed its argument checks voids it before it uploads.  A halogen-bond donor without a
+ * single-bond neighbour: ARP_E_XBOND_NBR, as in a pass.  ARP_E_CAPACITY: 2^31 records or more, *count = their number.
+ * The result is valid until an input of the structure or the selection changes (any setter, a new structure, models): the
+ * fetch then refuses.  It reads no result bag and writing it voids nothing: the bags of the last pass and every table made
+ * from them stay fetchable and byte-equal.  (It asks for the static columns in the cell order of `cutoff`, as a pass does.)
+ *
+ * arp_poses_contacts_fetch: copies what is asked for; ANY output pointer may be NULL (the summary alone: every record pointer
+ * NULL, cap is then not looked at).  *count = records.  ARP_E_CAPACITY when a record column is asked for and cap < *count;
+ * ARP_E_ARG without a valid result.
+ *
+ * arp_poses_contacts_info: info[0] = poses P, info[1] = S, info[2] = SH, info[3] = records of the resident result (all 0
+ * while there is none). */
+#define ARP_POSES_MAX_ATOMS 1024
+#define ARP_POSES_MAX_POSES (1 << 20)
+#define ARP_POSES_MAX_CUTOFF 6.0
+#define ARP_POSES_SUMMARY 16
+int arp_poses_contacts_launch(arp_ctx* ctx, int64_t n_poses, const float* xyz, const double* h_xyz, double cutoff,
+                              double vdw_comp, int include_sequence_adjacent, int64_t* count);
+int arp_poses_contacts_fetch(arp_ctx* ctx, int64_t cap, uint64_t* pose_off, int32_t* i, int32_t* j, float* dist, uint16_t* sift,
+                             uint8_t* ctype, uint32_t* summary, int64_t* count);
+int arp_poses_contacts_info(arp_ctx* ctx, int64_t info[4]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
