@@ -49,12 +49,15 @@ SYMBOLS = (
     'arp_models_lifetimes_launch', 'arp_models_lifetimes_fetch', 'arp_models_lifetimes_info',
     'arp_networks_launch', 'arp_networks_fetch', 'arp_networks_labels_fetch', 'arp_networks_info',
     'arp_poses_contacts_launch', 'arp_poses_contacts_fetch', 'arp_poses_contacts_info',
+    'arp_set_plane_atoms', 'arp_poses_planes_launch', 'arp_poses_planes_fetch', 'arp_poses_planes_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
 PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
 # ligand poses on the resident receptor (ARP_POSES_*)
 POSES_MAX_ATOMS, POSES_MAX_POSES, POSES_MAX_CUTOFF, POSES_SUMMARY = 1024, 1 << 20, 6.0, 16
+# ... their ring and amide contacts (ARP_POSES_PLANES_*)
+POSES_PLANES_SUMMARY, POSES_PLANES_MAX_RINGS, POSES_PLANES_MAX_HOME, POSES_PLANES_MAX_AMIDES, POSES_PLANES_MAX_NEAR = 16, 512, 512, 512, 256
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -233,6 +236,10 @@ def load():
     L.arp_poses_contacts_launch.argtypes = [vp, i64, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(i64)]
     L.arp_poses_contacts_fetch.argtypes = [vp, i64] + [vp] * 7 + [C.POINTER(i64)]
     L.arp_poses_contacts_info.argtypes = [vp, vp]
+    L.arp_set_plane_atoms.argtypes = [vp, vp, vp, vp]
+    L.arp_poses_planes_launch.argtypes = [vp, i64, vp, vp]
+    L.arp_poses_planes_fetch.argtypes = [vp, C.c_int, i64] + [vp] * 11 + [C.POINTER(i64)]
+    L.arp_poses_planes_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -944,6 +951,81 @@ class Context:
         info = np.zeros(4, np.int64)
         self._check(self._L.arp_poses_contacts_info(self._h, _p(info)), 'arp_poses_contacts_info')
         return dict(poses=int(info[0]), atoms=int(info[1]), hydrogens=int(info[2]), records=int(info[3]))
+
+    def set_plane_atoms(self, pc):
+        """The atoms of the resident rings and amides (arp_set_plane_atoms): ``pc.ring_atoms`` in ring-path order and
+        ``pc.amide_atoms`` (N, C, O, C-alpha) of the structure that is resident.  What ``poses_planes`` rebuilds a pose's ring
+        and amide geometry from; dropped with the structure, its rings or its amides."""
+        nr, na = pc.n_rings, pc.n_amides
+        if nr != self.n_rings or na != self.n_amides or pc.n_atoms != self.n:
+            raise ValueError('set_plane_atoms: counts differ from the resident structure')
+        if nr and len(pc.ring_atoms) != nr:
+            raise ValueError('set_plane_atoms: the pack needs the atoms of every ring (ring_atoms)')
+        off = np.zeros(nr + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in pc.ring_atoms]) if nr else []
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(a, np.int32) for a in pc.ring_atoms]) if nr else np.zeros(1, np.int32))
+        am = np.ascontiguousarray(pc.amide_atoms, np.int32).reshape(-1, 4)
+        if len(am) != na:
+            raise ValueError('set_plane_atoms: counts differ from the resident structure (amide_atoms)')
+        self._check(self._L.arp_set_plane_atoms(self._h, _p(off), _p(idx), _p(am) if na else None), 'arp_set_plane_atoms')
+
+    def _poses_planes_launch(self, xyz):
+        sel = getattr(self, '_sel', None)
+        if sel is None or len(sel) != self.n:
+            raise ValueError('poses_planes: no uploaded selection (set_selection names the movable set)')
+        atoms = np.nonzero(sel)[0].astype(np.int32)
+        S = len(atoms)
+        x = np.ascontiguousarray(xyz, np.float32)
+        if x.ndim != 3 or x.shape[1:] != (S, 3) or x.shape[0] < 1:
+            raise ValueError(f'poses_planes: xyz must be [P >= 1, {S}, 3] (the selected atoms in ascending order)')
+        counts = np.zeros(4, np.int64)
+        self._check(self._L.arp_poses_planes_launch(self._h, x.shape[0], _p(x), _p(counts)), 'arp_poses_planes_launch')
+        return x.shape[0], counts, atoms
+
+    def poses_planes(self, xyz):
+        """Every pose's ring and amide contacts in one launch (arp_poses_planes_*; ``arpeggio_amd.poses``).  The uploaded selection
+        is the movable set, ``set_plane_atoms`` has named the ring and amide atoms; ``xyz`` float32 [P, S, 3].  Returns a dict with
+        one table per bag — ``atom_plane``, ``plane_plane``, ``group_group``, ``group_plane``: the columns of ``fetch_bag`` plus
+        ``pose_off`` uint64 [P + 1], per pose exactly the records of the posed structure's bag that involve an affected entity
+        (``poses.affected``), in the bag's canonical order —, ``summary`` uint32 [P, 16] and ``movable``."""
+        from . import poses as _poses
+        P, counts, atoms = self._poses_planes_launch(xyz)
+        out = {}
+        n = C.c_int64(0)
+        summary = np.empty((P, POSES_PLANES_SUMMARY), np.uint32)
+        for t, name in enumerate(_poses.PLANE_TABLES):
+            k = int(counts[t])
+            ids, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
+            tab = {c: np.empty(k, np.int32) for c in ids}
+            tab.update({c: np.empty(k, vdt) for c in vals})
+            tab.update({c: np.empty(k, np.uint8) for c in byts})
+            tab['pose_off'] = np.empty(P + 1, np.uint64)
+            args = [_p(tab[c]) for c in ids] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
+            self._check(self._L.arp_poses_planes_fetch(self._h, t, k, _p(tab['pose_off']), *args, _p(summary) if t == 0 else None, C.byref(n)),
+                        'arp_poses_planes_fetch')
+            out[name] = tab
+        out['summary'] = summary
+        out['movable'] = atoms
+        return out
+
+    def poses_planes_summary(self, xyz):
+        """``poses_planes`` with only the per-pose summary copied to the host: uint32 [P, 16] (slots: ``poses.PLANE_SUMMARY_SLOTS``)."""
+        P, _, _ = self._poses_planes_launch(xyz)
+        s = np.empty((P, POSES_PLANES_SUMMARY), np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.arp_poses_planes_fetch(self._h, 0, 0, *([None] * 10), _p(s), C.byref(n)), 'arp_poses_planes_fetch')
+        return s
+
+    def poses_planes_info(self):
+        """arp_poses_planes_info: poses, atoms and records per table of the resident result (zeros while there is none), the sizes of
+        the movable set's lists, whether plane atoms are resident, and the kernel launches so far."""
+        from . import poses as _poses
+        info = np.zeros(12, np.int64)
+        self._check(self._L.arp_poses_planes_info(self._h, _p(info)), 'arp_poses_planes_info')
+        d = dict(poses=int(info[0]), atoms=int(info[1]))
+        d.update({name: int(info[2 + t]) for t, name in enumerate(_poses.PLANE_TABLES)})
+        d.update(moved_rings=int(info[6]), home_rings=int(info[7]), moved_amides=int(info[8]), plane_atoms=bool(info[9]), launches=int(info[10]))
+        return d
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

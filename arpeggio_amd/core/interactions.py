@@ -408,7 +408,7 @@ class InteractionComplex:
         label, table = self.networks(contacts, interacting_entities, level)
         return nw.write_networks(wd, self.id, label, table, self.pc, level, self.component_types)
 
-    def run_poses(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None):
+    def run_poses(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None, planes=False):
         """Extension beside the mirror (the reference evaluates one placement per run): the contacts of many poses of a ligand
         against this structure as the fixed receptor.  ``user_selections`` names the ligand, the MOVABLE SET (selectors, or
         an integer array of packed atom ids); ``xyz`` float32 [P, S, 3] are its atoms' coordinates per pose in ascending packed
@@ -417,7 +417,9 @@ class InteractionComplex:
         find on the structure with the pose scattered in — computed on the GPU against the resident receptor, only the poses
         uploaded.  Returns the table ``arpeggio_amd.poses`` describes (also kept in ``self.poses``); the poses go to the device
         ``chunk`` at a time (default: all at once, at most ``_capi.POSES_MAX_POSES``).  ``interacting_cutoff`` <= 6.0.  The
-        results of the last ``run_arpeggio`` stay as they are, but the selection on the device is the ligand from here on."""
+        results of the last ``run_arpeggio`` stay as they are, but the selection on the device is the ligand from here on.
+        ``planes=True``: the ring and amide contacts of every pose as well (``Context.poses_planes``; the pack needs
+        ``ring_atoms`` and ``amide_atoms``), kept in ``self.pose_planes`` (``poses.concat_planes`` over the chunks)."""
         from .. import _capi, poses as _poses
         if self._ctx is None:
             self.initialize()
@@ -439,6 +441,10 @@ class InteractionComplex:
         if not parts:
             raise ValueError('run_poses: no pose given')
         self.poses = parts[0] if len(parts) == 1 else _poses.concat(parts)
+        if planes:
+            ctx.set_plane_atoms(pc)
+            pparts = [ctx.poses_planes(x[a:a + step]) for a in range(0, len(x), step)]
+            self.pose_planes = pparts[0] if len(pparts) == 1 else _poses.concat_planes(pparts)
         return self.poses
 
     def write_poses(self, wd):
@@ -447,6 +453,13 @@ class InteractionComplex:
         if getattr(self, 'poses', None) is None:
             raise AttributeError('no poses yet: call run_poses() first')
         return _poses.write_poses(wd, self.id, self.poses, self.pc, self.component_types)
+
+    def write_pose_planes(self, wd):
+        """'<id>.poseplanes': the ring / amide tables of the last ``run_poses(..., planes=True)`` as CSV (``poses.write_planes_csv``)."""
+        from .. import poses as _poses
+        if getattr(self, 'pose_planes', None) is None:
+            raise AttributeError('no pose planes yet: call run_poses(..., planes=True) first')
+        return _poses.write_pose_planes(wd, self.id, self.pose_planes, self.pc, self.component_types)
 
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):

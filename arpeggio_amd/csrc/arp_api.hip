@@ -39,6 +39,7 @@
 #include "arp_lifetimes.h"
 #include "arp_networks.h"
 #include "arp_poses.h"
+#include "arp_poses_planes.h"
 #include "arp_blob.h"
 
 namespace {
@@ -309,6 +310,37 @@ struct PosesResult {
     bool valid = false;
 };
 
+// the ring / amide contacts of ligand poses (arp_poses_planes_launch, arp_poses_planes.h): the atoms of the resident rings and
+// amides (arp_set_plane_atoms), the movable set's tables (made once per structure, selection and plane atoms), an all-atom 6 A
+// grid of its own by local id (the static order of the passes is left alone), the per-block lists, the records and their sort
+struct PosesPlanesResult {
+    DevBuf<int> ring_off, ring_idx, amide_atoms;
+    bool have_atoms = false;
+    DevBuf<int> pos_of, hist, res_off, res_atoms, mring, hring, mamide, am_pos, cnt, sums;
+    DevBuf<uint8_t> res_selm, ring_static;
+    Grid grid;
+    bool setup = false;
+    int n_mring = 0, n_hring = 0, n_mamide = 0;
+    DevBuf<float> xyz;
+    DevBuf<PplRing> ws_ring;
+    DevBuf<PplAmide> ws_amide;
+    DevBuf<PlaneRec> rec;
+    DevBuf<unsigned long long> ctr, pose_off;
+    DevBuf<uint32_t> summary;
+    SortScratch sort;
+    DevBuf<uint8_t> slab;
+    PplColumns col{};
+    int64_t counts[4] = {0, 0, 0, 0};
+    int64_t P = 0, S = 0, launches = 0;
+    bool valid = false;
+    void release() {
+        ring_off.release(); ring_idx.release(); amide_atoms.release(); pos_of.release(); hist.release(); res_off.release(); res_atoms.release();
+        mring.release(); hring.release(); mamide.release(); am_pos.release(); cnt.release(); sums.release(); res_selm.release(); ring_static.release();
+        grid.release(); xyz.release(); ws_ring.release(); ws_amide.release(); rec.release(); ctr.release(); pose_off.release(); summary.release();
+        sort.release(); slab.release(); have_atoms = setup = valid = false;
+    }
+};
+
 struct arp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless arp_use_stream)
@@ -548,6 +580,7 @@ struct arp_ctx {
     int64_t net_nodes = 0;
     ResultTable coupling;                 // arp_models_coupling_launch: features and pairs in one slab; count = kept pairs
     CouplingScratch couple;
+    PosesPlanesResult pplanes;            // arp_poses_planes_launch: likewise; its plane atoms go with the structure, rings or amides
     PosesResult poses;                    // arp_poses_contacts_launch: reads no bag, voided with the inputs (inputs_changed)
     // ---- profiling
     bool profiling = false;
@@ -835,7 +868,9 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         void_results(c, RES_AA | RES_PLANES);
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
         c->poses.valid = false;      // (made from the inputs alone, the selection among them: no row in void_results)
+        c->pplanes.valid = c->pplanes.setup = false;
     }
+    if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->pplanes.have_atoms = false;
 }
 
 // Several structures in one grid (arp_set_batch): the placement of arp_batchgrid.h (batch_layout), cached per radius in four
@@ -2369,6 +2404,7 @@ void arp_destroy(arp_ctx* c) {
     c->networks.slab.release(); c->net_label.release(); c->net_scratch.release();
     c->similarity.bits.release(); c->similarity.inter.release();
     c->poses.sel_h.release(); c->poses.pos_of.release(); c->poses.xyz.release(); c->poses.hx.release(); c->poses.ctr.release();
+    c->pplanes.release();
     c->poses.summary.release(); c->poses.pose_off.release(); c->poses.sort.release(); c->poses.slab.release(); c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -5386,6 +5422,265 @@ int arp_poses_contacts_info(arp_ctx* c, int64_t info[4]) {
     info[1] = R.valid ? R.S : 0;
     info[2] = R.valid ? R.SH : 0;
     info[3] = R.valid ? R.count : 0;
+    return ARP_OK;
+}
+
+// ---- ligand poses on the resident receptor, ring and amide contacts (arp_poses_planes.h)
+// No bag is read and none is written.  The resident centres, normals and residues, the two centre grids and an all-atom grid of
+// this result's own (by local id: ensure_static's order, which arp_poses_contacts_launch re-sorts per cutoff, is not touched) are
+// read; records are appended unsorted with a key, sorted by every bit of it and gathered into four tables.  Waits: the three list
+// sizes when the set-up is new, and the counters (records, error word, records per table).
+static_assert(PPL_SUMMARY == ARP_POSES_PLANES_SUMMARY && PPL_MAX_RINGS == ARP_POSES_PLANES_MAX_RINGS && PPL_MAX_AMIDES == ARP_POSES_PLANES_MAX_AMIDES &&
+              PPL_MAX_HOME == ARP_POSES_PLANES_MAX_HOME && PPL_MAX_NEAR == ARP_POSES_PLANES_MAX_NEAR, "arp_poses_planes.h names the header's limits");
+int arp_set_plane_atoms(arp_ctx* c, const int32_t* ring_off, const int32_t* ring_idx, const int32_t* amide_atoms) {
+    if (!c) return ARP_E_ARG;
+    const std::string fn = "arp_set_plane_atoms: ";
+    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
+    if (c->models_n > 0 || c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "models or a batch are resident (one structure)");
+    if ((c->nring > 0 && !ring_off) || (c->namide > 0 && !amide_atoms)) FAIL(c, ARP_E_ARG, fn + "counts differ: the resident structure has rings or amides whose atoms are missing");
+    CHK(check_ring_atoms(c, "arp_set_plane_atoms", c->nring, ring_off, ring_idx, c->n));
+    CHK(check_amide_atoms(c, "arp_set_plane_atoms", c->namide, amide_atoms, c->n));
+    HIPCHK(c, hipSetDevice(c->device));
+    PosesPlanesResult& R = c->pplanes;
+    R.valid = R.setup = R.have_atoms = false;
+    const int32_t zero = 0;
+    const size_t nidx = c->nring > 0 ? (size_t)ring_off[c->nring] : 0;
+    CHK(upload(c, R.ring_off, c->nring > 0 ? ring_off : &zero, (size_t)c->nring + 1));
+    CHK(upload(c, R.ring_idx, nidx > 0 ? ring_idx : &zero, std::max<size_t>(nidx, 1)));
+    CHK(upload(c, R.amide_atoms, c->namide > 0 ? amide_atoms : &zero, std::max<size_t>(4 * (size_t)c->namide, 1)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    R.have_atoms = true;
+    return ARP_OK;
+}
+
+struct PtsF4 {  // the atoms as uploaded, by local id
+    const float4* p;
+    __device__ __forceinline__ num::d3 get(int i) const { const float4 v = p[i]; return {(double)v.x, (double)v.y, (double)v.z}; }
+};
+
+static int poses_planes_setup(arp_ctx* c, const std::string& fn) {
+    PosesPlanesResult& R = c->pplanes;
+    const int n = (int)c->n, S = (int)c->nsel, nring = (int)c->nring, namide = (int)c->namide;
+    const int nres = (int)std::max<int64_t>(c->nres, 1);
+    R.setup = false;
+    HIPCHK(c, R.pos_of.reserve((size_t)n));
+    HIPCHK(c, R.res_selm.reserve((size_t)nres));
+    HIPCHK(c, R.hist.reserve(scan_padded(nres)));
+    HIPCHK(c, R.res_off.reserve(scan_padded(nres)));
+    HIPCHK(c, R.res_atoms.reserve((size_t)n));
+    HIPCHK(c, R.mring.reserve(PPL_MAX_RINGS)); HIPCHK(c, R.hring.reserve(PPL_MAX_HOME)); HIPCHK(c, R.mamide.reserve(PPL_MAX_AMIDES));
+    HIPCHK(c, R.ring_static.reserve((size_t)std::max(nring, 1))); HIPCHK(c, R.am_pos.reserve((size_t)std::max(namide, 1)));
+    HIPCHK(c, R.cnt.reserve(4));
+    HIPCHK(c, hipMemsetAsync(R.pos_of.p, 0xFF, (size_t)n * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(R.res_selm.p, 0, (size_t)nres, c->stream));
+    HIPCHK(c, hipMemsetAsync(R.hist.p, 0, R.hist.cap * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(R.cnt.p, 0, 4 * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_ppl_mark, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, S, c->sel_list.p, c->sel.p, c->res_id.p, R.pos_of.p, R.res_selm.p, R.hist.p);
+    CHK(check_launch(c, "k_ppl_mark"));
+    // residue -> atoms: the scan and the scatter of the point grids (the histogram is counted down to zero again)
+    CHK(enqueue_scan(c, c->stream, R.hist.p, nres, R.res_off.p, R.sums));
+    hipLaunchKernelGGL(k_scatter, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->res_id.p, R.res_off.p, R.hist.p, R.res_atoms.p);
+    CHK(check_launch(c, "k_scatter (residue atoms)"));
+    if (nring + namide > 0) {
+        PplArgs A{};
+        A.n = n; A.S = S; A.nring = nring; A.namide = namide;
+        A.sel_list = c->sel_list.p; A.pos_of = R.pos_of.p; A.xyz = c->xyz.p; A.ring_c = c->ring_c.p;
+        A.ring_off = R.ring_off.p; A.ring_idx = R.ring_idx.p; A.amide_atoms = R.amide_atoms.p;
+        hipLaunchKernelGGL(k_ppl_lists, dim3(nblocks(nring + namide, 256)), dim3(256), 0, c->stream, A, R.mring.p, R.hring.p, R.mamide.p, R.ring_static.p,
+                           R.am_pos.p, R.cnt.p);
+        CHK(check_launch(c, "k_ppl_lists"));
+    }
+    // the all-atom grid of this result, cell edge 6 A, entries = local ids
+    CHK(build_grid<PtsF4>(c, R.grid, PtsF4{c->xyz.p}, n, c->lo, c->hi, 6.0, nullptr));
+    CHK(stage_copy(c, R.cnt.p, 4 * sizeof(int)));
+    int h[4];
+    memcpy(h, c->table_stage, sizeof(h));
+    if (h[0] > PPL_MAX_RINGS) FAIL(c, ARP_E_ARG, fn + "more than ARP_POSES_PLANES_MAX_RINGS rings hold a movable atom");
+    if (h[1] > PPL_MAX_HOME) FAIL(c, ARP_E_ARG, fn + "more than ARP_POSES_PLANES_MAX_HOME further rings have a movable atom within 3 A of their centre");
+    if (h[2] > PPL_MAX_AMIDES) FAIL(c, ARP_E_ARG, fn + "more than ARP_POSES_PLANES_MAX_AMIDES amides hold a movable atom");
+    R.n_mring = h[0]; R.n_hring = h[1]; R.n_mamide = h[2];
+    R.setup = true;
+    return ARP_OK;
+}
+
+int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64_t counts[4]) {
+    if (!c || !counts) return ARP_E_ARG;
+    const std::string fn = "arp_poses_planes_launch: ";
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
+    if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
+    if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
+    if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
+    if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
+    if (n_poses < 1 || n_poses > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    if (c->n >= POSES_MAX_N || c->nring >= POSES_MAX_N || c->namide >= POSES_MAX_N) FAIL(c, ARP_E_ARG, fn + "2^21 atoms, rings or amides, or more (the sort key holds 21 bits per id)");
+    PosesPlanesResult& R = c->pplanes;
+    if (!R.have_atoms) FAIL(c, ARP_E_ARG, fn + "no plane atoms (arp_set_plane_atoms after the structure, its rings and its amides)");
+    if (!xyz) FAIL(c, ARP_E_ARG, fn + "xyz missing");
+    CHK(check_residue_ranges(c));
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    CHK(ensure_static(c));               // (radius 0: the order in place stays, only missing columns are made)
+    CHK(ensure_center_grids(c));
+    if (!R.setup) CHK(poses_planes_setup(c, fn));
+    const int n = (int)c->n, S = (int)c->nsel;
+    const int64_t P = n_poses;
+    // ---- from here on the previous result is gone
+    R.valid = false;
+    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
+    const int blocks = (int)std::min<int64_t>(P, PPL_MAX_BLOCKS);
+    const int ws_rings = R.n_mring + R.n_hring + PPL_MAX_NEAR;
+    HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
+    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)P * S * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, R.ws_ring.reserve((size_t)blocks * ws_rings));
+    HIPCHK(c, R.ws_amide.reserve((size_t)blocks * std::max(R.n_mamide, 1)));
+    HIPCHK(c, R.ctr.reserve(8));
+    HIPCHK(c, R.summary.reserve((size_t)P * PPL_SUMMARY));
+    HIPCHK(c, R.pose_off.reserve(4 * ((size_t)P + 1)));
+    PplArgs A{};
+    A.n = n; A.S = S; A.P = (int)P; A.nring = (int)c->nring; A.namide = (int)c->namide;
+    A.sel_list = c->sel_list.p; A.pos_of = R.pos_of.p; A.sel = c->sel.p; A.pxyz = R.xyz.p;
+    A.ring_off = R.ring_off.p; A.ring_idx = R.ring_idx.p; A.amide_atoms = R.amide_atoms.p;
+    A.mring = R.mring.p; A.hring = R.hring.p; A.mamide = R.mamide.p;
+    A.n_mring = R.n_mring; A.n_hring = R.n_hring; A.n_mamide = R.n_mamide;
+    A.ring_static = R.ring_static.p; A.am_pos = R.am_pos.p; A.res_selm = R.res_selm.p; A.res_off = R.res_off.p; A.res_atoms = R.res_atoms.p;
+    A.xyz = c->xyz.p; A.st_xyzm = c->st_xyzm.p; A.res_id = c->res_id.p;
+    A.ring_c = c->ring_c.p; A.ring_n = c->ring_n.p; A.ring_res = c->ring_res.p;
+    A.am_c = c->am_c.p; A.am_n = c->am_n.p; A.am_res = c->am_res.p;
+    A.ga = R.grid.d; A.a_start = R.grid.start.p; A.a_perm = R.grid.perm.p;
+    if (c->nring > 0) { A.gr = c->ring_grid.d; A.r_start = c->ring_grid.start.p; A.r_perm = c->ring_grid.perm.p; }
+    if (c->namide > 0) { A.gm = c->amide_grid.d; A.m_start = c->amide_grid.start.p; A.m_perm = c->amide_grid.perm.p; }
+    A.ws_ring = R.ws_ring.p; A.ws_amide = R.ws_amide.p; A.ws_rings = ws_rings;
+    A.ctr = R.ctr.p; A.summary = R.summary.p;
+    A.idbits = index_bits(std::max({c->n, c->nring, c->namide})); A.pbits = index_bits(P);
+    const int keybits = 2 + A.pbits + 2 * A.idbits;
+    const size_t limit = ((size_t)1 << 31) - 1;
+    size_t cap = std::min(limit, std::max<size_t>((size_t)1 << 16, (size_t)P * 64));
+    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+    for (int attempt = 0;; ++attempt) {
+        CHK(reserve_key_sort(c, R.sort, cap, cap));
+        HIPCHK(c, R.rec.reserve(cap));
+        A.rec = R.rec.p; A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
+        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 6 * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_poses_planes, dim3((unsigned)blocks), dim3(PPL_THREADS), 0, c->stream, A);
+        CHK(check_launch(c, "k_poses_planes"));
+        ++R.launches;
+        CHK(stage_copy(c, R.ctr.p, sizeof(h)));
+        memcpy(h, c->table_stage, sizeof(h));
+        const int dev = (int)(uint32_t)h[1];
+        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
+        if (dev == PPL_E_NEAR) FAIL(c, ARP_E_ARG, fn + "a pose brings more than ARP_POSES_PLANES_MAX_NEAR further rings within 3 A of a movable atom");
+        if (dev != 0) FAIL(c, ARP_E_HIP, fn + "device error");
+        if (h[0] <= cap) break;
+        if (h[0] > limit) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more (fewer poses a launch)");
+        if (attempt == 1) FAIL(c, ARP_E_CAPACITY, fn + "record buffer could not be sized");
+        cap = (size_t)h[0];
+    }
+    const size_t k = (size_t)h[0];
+    if (h[2] + h[3] + h[4] + h[5] != h[0]) FAIL(c, ARP_E_HIP, fn + "the tables' record counts do not add up");
+    hipLaunchKernelGGL(k_ppl_offsets, dim3(4), dim3(1024), 0, c->stream, (int)P, R.summary.p, R.pose_off.p);
+    // the four tables in one slab: two id columns, the value columns (float64; group-group float32), the byte columns
+    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
+    PplColumns col{};
+    size_t bytes = 0;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off_i0[4], off_i1[4], off_d[4][4], off_u[4][3];
+    col.base[0] = 0;
+    for (int t = 0; t < 4; ++t) {
+        const size_t m = (size_t)h[2 + t];
+        col.base[t + 1] = col.base[t] + (long long)m;
+        off_i0[t] = bytes; bytes += al(m * sizeof(int));
+        off_i1[t] = bytes; bytes += al(m * sizeof(int));
+        for (int q = 0; q < n_val[t]; ++q) { off_d[t][q] = bytes; bytes += al(m * (t == 2 ? sizeof(float) : sizeof(double))); }
+        for (int q = 0; q < n_byte[t]; ++q) { off_u[t][q] = bytes; bytes += al(m); }
+    }
+    HIPCHK(c, R.slab.reserve(std::max<size_t>(bytes, 256)));
+    for (int t = 0; t < 4; ++t) {
+        col.i0[t] = (int*)(R.slab.p + off_i0[t]); col.i1[t] = (int*)(R.slab.p + off_i1[t]);
+        for (int q = 0; q < n_val[t]; ++q) col.d[t][q] = (double*)(R.slab.p + off_d[t][q]);
+        for (int q = 0; q < n_byte[t]; ++q) col.u[t][q] = R.slab.p + off_u[t][q];
+    }
+    if (k > 0) {
+        int sorted = 0;
+        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
+        hipLaunchKernelGGL(k_ppl_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, R.sort.val[sorted].p, R.rec.p, col);
+    }
+    CHK(check_launch(c, "k_ppl_offsets / sort / k_ppl_columns"));
+    R.col = col;
+    R.P = P; R.S = S; R.valid = true;
+    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = (int64_t)h[2 + t];
+    return ARP_OK;
+}
+
+int arp_poses_planes_fetch(arp_ctx* c, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0, void* v1, void* v2,
+                           void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const PosesPlanesResult& R = c->pplanes;
+    if (!R.valid) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: no result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
+    if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
+    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
+    const int t = table;
+    *count = R.counts[t];
+    void* const v[4] = {v0, v1, v2, v3};
+    uint8_t* const u[3] = {u0, u1, u2};
+    bool records = first || second;
+    for (int q = 0; q < 4; ++q) {
+        if (v[q] && q >= n_val[t]) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: the table has no such value column");
+        records = records || v[q];
+    }
+    for (int q = 0; q < 3; ++q) {
+        if (u[q] && q >= n_byte[t]) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: the table has no such byte column");
+        records = records || u[q];
+    }
+    if (records && R.counts[t] > cap) FAIL(c, ARP_E_CAPACITY, "arp_poses_planes_fetch: output buffers too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)R.counts[t];
+    // everything that is asked for goes through the page-locked stage in one wait (pageable destinations cost a copy of
+    // a few tens of kB milliseconds now and then), then to the caller's arrays
+    struct Piece { void* dst; const void* src; size_t bytes; };
+    std::vector<Piece> pieces;
+    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(Piece{dst, src, bytes}); };
+    want(pose_off, R.pose_off.p + (size_t)t * ((size_t)R.P + 1), ((size_t)R.P + 1) * sizeof(unsigned long long));
+    want(summary, R.summary.p, (size_t)R.P * PPL_SUMMARY * sizeof(uint32_t));
+    if (records && k > 0) {
+        want(first, R.col.i0[t], k * sizeof(int32_t));
+        want(second, R.col.i1[t], k * sizeof(int32_t));
+        for (int q = 0; q < n_val[t]; ++q) want(v[q], R.col.d[t][q], k * (t == 2 ? sizeof(float) : sizeof(double)));
+        for (int q = 0; q < n_byte[t]; ++q) want(u[q], R.col.u[t][q], k);
+    }
+    size_t total = 0;
+    for (const Piece& pc_ : pieces) total += (pc_.bytes + 15) & ~(size_t)15;
+    if (total > 0) {
+        CHK(table_stage_reserve(c, total));
+        size_t at = 0;
+        for (const Piece& pc_ : pieces) {
+            HIPCHK(c, hipMemcpyAsync((uint8_t*)c->table_stage + at, pc_.src, pc_.bytes, hipMemcpyDeviceToHost, c->stream));
+            at += (pc_.bytes + 15) & ~(size_t)15;
+        }
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    size_t at = 0;
+    for (const Piece& pc_ : pieces) {
+        memcpy(pc_.dst, (const uint8_t*)c->table_stage + at, pc_.bytes);
+        at += (pc_.bytes + 15) & ~(size_t)15;
+    }
+    return ARP_OK;
+}
+
+int arp_poses_planes_info(arp_ctx* c, int64_t info[12]) {
+    if (!c || !info) return ARP_E_ARG;
+    const PosesPlanesResult& R = c->pplanes;
+    info[0] = R.valid ? R.P : 0;
+    info[1] = R.valid ? R.S : 0;
+    for (int t = 0; t < 4; ++t) info[2 + t] = R.valid ? R.counts[t] : 0;
+    info[6] = R.setup ? R.n_mring : 0;
+    info[7] = R.setup ? R.n_hring : 0;
+    info[8] = R.setup ? R.n_mamide : 0;
+    info[9] = R.have_atoms ? 1 : 0;
+    info[10] = R.launches;
+    info[11] = 0;
     return ARP_OK;
 }
 

@@ -13,6 +13,10 @@ A result (``table``) is a dict:
     summary    uint32 [P, 16]  per pose: records with SIFt bit k (config.SIFT_NAMES) in slot k, all its records in slot 15
     movable    int32 [S]       the movable set
 
+The ring and amide contacts of the same poses (``Context.poses_planes``, csrc/arp_poses_planes.h) have their host side in the
+second half of this module: ``affected``, ``plane_reference_rows``, ``split_planes``, ``concat_planes``, ``planes_to_records``,
+``write_planes_csv``.
+
 Everything here is NumPy on the host; nothing imports the native library.
 """
 import csv
@@ -189,3 +193,204 @@ def reference_rows(bag, sel_mask):
     keep = m[i] != m[j]
     order = np.lexsort((j[keep], i[keep]))
     return {k: np.asarray(bag[k])[keep][order] for k in COLUMNS}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Ring and amide contacts of the poses: host side of ``Context.poses_planes`` (arp_poses_planes_*, csrc/arp_poses_planes.h)
+#
+# A result (``table``) is a dict with one sub-table per bag — the columns ``Context.fetch_bag`` gives that bag plus ``pose_off``
+# uint64 [P + 1], the records of a pose in the bag's canonical order —, ``summary`` uint32 [P, 16] and ``movable``.
+# ---------------------------------------------------------------------------------------------------------------------
+PLANE_TABLES = ('atom_plane', 'plane_plane', 'group_group', 'group_plane')
+# per table: id columns, value columns, byte columns, dtype of the value columns (the order of arp_poses_planes_fetch's arguments)
+PLANE_COLUMNS = {
+    'atom_plane': (('atom', 'ring'), ('dist', 'theta'), ('mask', 'ctype'), np.float64),
+    'plane_plane': (('bgn', 'end'), ('dist', 'dihedral', 'theta_bgn', 'theta_end'), ('type1', 'type2', 'ctype'), np.float64),
+    'group_group': (('bgn', 'end'), ('dist', 'dihedral', 'theta'), ('ctype',), np.float32),
+    'group_plane': (('amide', 'ring'), ('dist', 'dihedral', 'theta'), ('ctype',), np.float64),
+}
+PLANE_ORDER = {'atom_plane': ('ring', 'atom'), 'plane_plane': ('bgn', 'end'), 'group_group': ('bgn', 'end'), 'group_plane': ('amide', 'ring')}
+PLANE_SUMMARY_SLOTS = ('atom_plane', 'plane_plane', 'group_group', 'group_plane', 'inter_carbonpi', 'inter_cationpi', 'inter_donorpi',
+                       'inter_halogenpi', 'inter_metsulphurpi', 'inter_plane_plane', 'inter_group_group', 'inter_group_plane',
+                       'affected_rings', 'rings_residue_changed', 'rings_without_residue', 'records')
+CT_INTER = config.CONTACT_TYPE_NAMES.index('INTER')
+
+
+def plane_columns(name):
+    """Every record column of table ``name`` with its dtype, in fetch order."""
+    ids, vals, byts, vdt = PLANE_COLUMNS[name]
+    return [(c, np.int32) for c in ids] + [(c, vdt) for c in vals] + [(c, np.uint8) for c in byts]
+
+
+def _kd2(a, b):
+    """Bio.PDB.kdtrees' membership quantity between every row of ``a`` and every row of ``b``: float64 sum of squares in x, y, z
+    order, no fusion (num::dist2_kd on the device)."""
+    d = np.asarray(a, np.float64)[:, None, :] - np.asarray(b, np.float64)[None, :, :]
+    r = d[..., 0] * d[..., 0]
+    r = r + d[..., 1] * d[..., 1]
+    r = r + d[..., 2] * d[..., 2]
+    return r
+
+
+def affected(pc, sel, xyz_pose):
+    """What one pose of movable set ``sel`` affects: ``(moved_amides, affected_rings)``, ascending ids.  An amide is moved when
+    its N, C or O is movable.  A ring is affected when a movable atom is in its path, or lies within 3.0 A (inclusive, float64
+    sum of squares) of its resident centre at the atom's pose coordinate ``xyz_pose`` [S, 3] or at its resident coordinate."""
+    m = _mask(pc, sel)
+    atoms = np.nonzero(m)[0]
+    x_pose = np.asarray(xyz_pose, np.float32).reshape(-1, 3)
+    if len(x_pose) != len(atoms):
+        raise ValueError(f'affected: xyz_pose must be [{len(atoms)}, 3]')
+    am = np.asarray(pc.amide_atoms, np.int64).reshape(-1, 4)
+    moved = np.nonzero(m[am[:, :3]].any(axis=1))[0] if len(am) else np.zeros(0, np.int64)
+    nr = pc.n_rings
+    aff = np.zeros(nr, bool)
+    if nr:
+        aff |= np.array([bool(m[np.asarray(a, np.int64)].any()) for a in pc.ring_atoms])
+        ctr = np.asarray(pc.ring_center, np.float64).reshape(-1, 3)
+        for x in (x_pose, np.asarray(pc.xyz, np.float32)[atoms]):
+            aff |= (_kd2(ctr, x.astype(np.float64)) <= 9.0).any(axis=1)
+    return moved.astype(np.int64), np.nonzero(aff)[0].astype(np.int64)
+
+
+def plane_reference_rows(bags, pc, sel, xyz_pose):
+    """Of the four ring / amide bags of a pass over one pose as a whole structure or model: the rows that involve an affected
+    entity (``affected``), each bag in its canonical order — what the pose's records must equal."""
+    m = _mask(pc, sel)
+    moved, rings = affected(pc, sel, xyz_pose)
+    am = np.zeros(pc.n_amides, bool)
+    am[moved] = True
+    rg = np.zeros(pc.n_rings, bool)
+    rg[rings] = True
+    keep = {'atom_plane': lambda b: m[b['atom']] | rg[b['ring']], 'plane_plane': lambda b: rg[b['bgn']] | rg[b['end']],
+            'group_group': lambda b: am[b['bgn']] | am[b['end']], 'group_plane': lambda b: am[b['amide']] | rg[b['ring']]}
+    out = {}
+    for name in PLANE_TABLES:
+        b = {c: np.asarray(bags[name][c]) for c, _ in plane_columns(name)}
+        k = keep[name](b) if len(b[PLANE_ORDER[name][0]]) else np.zeros(0, bool)
+        first, second = PLANE_ORDER[name]
+        order = np.lexsort((b[second][k], b[first][k]))
+        out[name] = {c: b[c][k][order].astype(dt) for c, dt in plane_columns(name)}
+    return out
+
+
+def summarise_planes(rows):
+    """Slots 0 - 11 and 15 of the summary row of one pose's records (slots 12 - 14 count rings, not records: left 0)."""
+    s = np.zeros(SUMMARY, np.uint32)
+    for t, name in enumerate(PLANE_TABLES):
+        ct = np.asarray(rows[name]['ctype'])
+        s[t] = len(ct)
+        inter = ct == CT_INTER
+        if t == 0:
+            mask = np.asarray(rows[name]['mask'])
+            for b in range(5):
+                s[4 + b] = int((inter & (((mask >> b) & 1) != 0)).sum())
+        else:
+            s[8 + t] = int(inter.sum())
+    s[15] = int(s[:4].sum())
+    return s
+
+
+def empty_planes(n=0, movable_atoms=()):
+    t = {name: dict({c: np.zeros(0, dt) for c, dt in plane_columns(name)}, pose_off=np.zeros(n + 1, np.uint64)) for name in PLANE_TABLES}
+    t['summary'] = np.zeros((n, SUMMARY), np.uint32)
+    t['movable'] = np.asarray(movable_atoms, np.int32)
+    return t
+
+
+def planes_from_rows(rows, movable_atoms, summary=None):
+    """Per-pose rows (a list of ``plane_reference_rows`` results) as the table the device returns (summary slots 12 - 14 from
+    ``summary`` when given, else 0)."""
+    t = {}
+    for name in PLANE_TABLES:
+        t[name] = {c: (np.concatenate([r[name][c] for r in rows]) if rows else np.zeros(0)).astype(dt) for c, dt in plane_columns(name)}
+        t[name]['pose_off'] = np.concatenate([[0], np.cumsum([len(r[name]['ctype']) for r in rows])]).astype(np.uint64)
+    t['summary'] = np.stack([summarise_planes(r) for r in rows]) if rows else np.zeros((0, SUMMARY), np.uint32)
+    if summary is not None:
+        t['summary'][:, 12:15] = np.asarray(summary)[:, 12:15]
+    t['movable'] = np.asarray(movable_atoms, np.int32)
+    return t
+
+
+def split_planes(table):
+    """One dict of four bags per pose."""
+    P = len(table['summary'])
+    out = []
+    for p in range(P):
+        one = {}
+        for name in PLANE_TABLES:
+            off = np.asarray(table[name]['pose_off']).astype(np.int64)
+            one[name] = {c: np.asarray(table[name][c])[off[p]:off[p + 1]] for c, _ in plane_columns(name)}
+        out.append(one)
+    return out
+
+
+def concat_planes(chunks):
+    """The results of consecutive chunks of poses as one."""
+    chunks = list(chunks)
+    if not chunks:
+        return empty_planes()
+    out = {}
+    for name in PLANE_TABLES:
+        out[name] = {c: np.concatenate([np.asarray(ch[name][c]) for ch in chunks]).astype(dt) for c, dt in plane_columns(name)}
+        base, offs = 0, [np.zeros(1, np.uint64)]
+        for ch in chunks:
+            o = np.asarray(ch[name]['pose_off']).astype(np.uint64)
+            offs.append(o[1:] + np.uint64(base))
+            base += int(o[-1])
+        out[name]['pose_off'] = np.concatenate(offs)
+    out['summary'] = np.concatenate([np.asarray(ch['summary'], np.uint32).reshape(-1, SUMMARY) for ch in chunks])
+    mv = [np.asarray(ch['movable']) for ch in chunks if 'movable' in ch]
+    if mv:
+        if any(not np.array_equal(mv[0], m) for m in mv[1:]):
+            raise ValueError('concat_planes: the chunks have different movable sets')
+        out['movable'] = mv[0]
+    return out
+
+
+def planes_to_records(table, pc, component_types=None):
+    """The records as the dicts ``get_contacts`` returns for the four bags (export.py), each with its 'pose'.  Rings and amides
+    are labelled by their resident residue."""
+    from .core import export
+    ctypes_ = pc.component_types if component_types is None else component_types
+    out = []
+    for p, bags in enumerate(split_planes(table)):
+        for rec in export.contacts_json(pc, bags, ctypes_):
+            rec['pose'] = p
+            out.append(rec)
+    return out
+
+
+PLANES_CSV_HEADER = ['pose', 'type', 'bgn', 'end', 'distance', 'contacts', 'interacting_entities']
+
+
+def write_planes_csv(path, table, pc, component_types=None):
+    """One row per record: pose, bag, the two entities ('A/508/O' for an atom, 'ring/<id>' and 'amide/<id>' otherwise), the
+    distance rounded as ``get_contacts`` rounds it, the contacts by name joined with '|', the interacting entities."""
+    from .core import export
+    lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
+    ct, pp, ap = config.CONTACT_TYPE_NAMES, config.PLANE_PLANE_NAMES, config.ATOM_PLANE_NAMES
+    with open(path, 'w', newline='') as fh:
+        w = csv.writer(fh, delimiter=',', quotechar='"', quoting=csv.QUOTE_MINIMAL)
+        w.writerow(PLANES_CSV_HEADER)
+        for p, bags in enumerate(split_planes(table)):
+            b = bags['atom_plane']
+            for a, r, d, m, c in zip(b['atom'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['mask'].tolist(), b['ctype'].tolist()):
+                w.writerow([p, 'atom-plane', lab.atom_macro(a), f'ring/{r}', d, '|'.join(n for k, n in enumerate(ap) if (m >> k) & 1), ct[c]])
+            b = bags['plane_plane']
+            for r1, r2, d, t1, t2, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['type1'].tolist(), b['type2'].tolist(),
+                                            b['ctype'].tolist()):
+                w.writerow([p, 'plane-plane', f'ring/{r1}', f'ring/{r2}', d, '|'.join([pp[t1]] + ([pp[t2]] if t2 < config.PP_SAME else [])), ct[c]])
+            b = bags['group_group']
+            for a1, a2, d, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
+                w.writerow([p, 'group-group', f'amide/{a1}', f'amide/{a2}', d, 'AMIDEAMIDE', ct[c]])
+            b = bags['group_plane']
+            for a, r, d, c in zip(b['amide'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
+                w.writerow([p, 'group-plane', f'amide/{a}', f'ring/{r}', d, 'AMIDERING', ct[c]])
+
+
+def write_pose_planes(wd, sid, table, pc, component_types=None):
+    """'<id>.poseplanes' in ``wd``."""
+    path = os.path.join(wd, sid + '.poseplanes')
+    write_planes_csv(path, table, pc, component_types)
+    return path

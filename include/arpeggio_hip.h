@@ -1043,6 +1043,55 @@ int arp_poses_contacts_launch(arp_ctx* ctx, int64_t n_poses, const float* xyz, c
 int arp_poses_contacts_fetch(arp_ctx* ctx, int64_t cap, uint64_t* pose_off, int32_t* i, int32_t* j, float* dist, uint16_t* sift,
                              uint8_t* ctype, uint32_t* summary, int64_t* count);
 int arp_poses_contacts_info(arp_ctx* ctx, int64_t info[4]);
+/* Ligand poses on the resident receptor: the ring and amide contacts of every pose in one launch (csrc/arp_poses_planes.h).
+ * The movable set and its preconditions are those of arp_poses_contacts_launch, without cutoff, hydrogen rows and single-bond
+ * neighbours: none of the four ring / amide loops reads them.
+ *
+ * arp_set_plane_atoms: the atom paths of the resident rings (CSR ring_off [nring + 1] / ring_idx, ring-path order) and the
+ *   atoms of the resident amides (amide_atoms [namide][4]: N, C, O, C-alpha), for the nring rings and namide amides that are
+ *   resident.  Checked as arp_ring_geometry / arp_amide_geometry check theirs.  They are dropped with the structure, its rings
+ *   or its amides, and uploading them voids the result below.
+ *
+ * The POSED structure of a pose is the resident one with the pose's coordinates scattered in, the geometry of its rings and
+ * amides and its ring residues made again as initialize() makes them, and _make_selection with the same selection and the
+ * 6.0 A expansion.  AFFECTED by a pose are: every movable atom; every amide whose N, C or O is movable; every ring with a
+ * movable atom in its path or with a movable atom within 3.0 A (inclusive, float64 sum of squares) of its centre, at the atom's
+ * pose coordinate or at its resident one.  The result holds exactly those records of the posed structure's four bags that
+ * involve an affected entity, every column as the pass gives it; records between two unaffected entities are not reported.
+ *
+ * arp_poses_planes_launch: xyz float32 [n_poses][S][3].  counts[4] = records of the tables ARP_POSES_PLANES_ATOM_PLANE ...
+ *   ARP_POSES_PLANES_GROUP_PLANE.  Nothing is truncated (a record buffer that was too small is grown to the counted size and the
+ *   launch repeated once); the result is deterministic.  Refusals are ARP_E_ARG with the cause named: those of
+ *   arp_poses_contacts_launch, "no plane atoms", "counts differ" (arp_set_plane_atoms), a non-finite pose coordinate (found on
+ *   the device; no result is left), and the limits below by their names.  The result stays resident until an input, the
+ *   selection or the plane atoms change; making it voids nothing else.
+ *
+ * arp_poses_planes_fetch: one table a call.  The id columns first / second are (atom, ring) for atom_plane, (bgn, end) for
+ *   plane_plane and group_group, (amide, ring) for group_plane; records are in ascending pose, then in the canonical order of
+ *   the bag: (ring, atom) for atom_plane, (first, second) for the others.  pose_off uint64 [n_poses + 1] are the table's offsets.  Value columns v0 ..: atom_plane
+ *   dist, theta; plane_plane dist, dihedral, theta_bgn, theta_end; group_group dist, dihedral, theta (float32); group_plane
+ *   dist, dihedral, theta (float64 unless said).  Byte columns u0 ..: atom_plane mask, ctype; plane_plane type1, type2, ctype;
+ *   the others ctype.  ANY pointer may be NULL; a column the table does not have must be.  summary uint32
+ *   [n_poses][ARP_POSES_PLANES_SUMMARY] per pose: slots 0-3 records per table, 4-8 INTER atom_plane records with
+ *   ARP_AP_CARBONPI ... ARP_AP_METSULPHURPI, 9-11 INTER records of the other three tables, 12 affected rings, 13 those whose
+ *   residue differs from the resident one, 14 those without a residue, 15 all records.
+ *
+ * arp_poses_planes_info: info[0] poses, [1] S, [2..5] records per table (0 without a result), [6] rings with a movable atom,
+ *   [7] further rings affected at home, [8] moved amides, [9] plane atoms resident, [10] kernel launches so far, [11] 0. */
+#define ARP_POSES_PLANES_SUMMARY 16
+#define ARP_POSES_PLANES_MAX_RINGS 512     /* rings with a movable atom */
+#define ARP_POSES_PLANES_MAX_HOME 512      /* further rings with a movable atom within 3 A at home */
+#define ARP_POSES_PLANES_MAX_AMIDES 512    /* amides with a movable N, C or O */
+#define ARP_POSES_PLANES_MAX_NEAR 256      /* further rings one pose brings within 3 A of a movable atom */
+#define ARP_POSES_PLANES_ATOM_PLANE 0
+#define ARP_POSES_PLANES_PLANE_PLANE 1
+#define ARP_POSES_PLANES_GROUP_GROUP 2
+#define ARP_POSES_PLANES_GROUP_PLANE 3
+int arp_set_plane_atoms(arp_ctx* ctx, const int32_t* ring_off, const int32_t* ring_idx, const int32_t* amide_atoms);
+int arp_poses_planes_launch(arp_ctx* ctx, int64_t n_poses, const float* xyz, int64_t counts[4]);
+int arp_poses_planes_fetch(arp_ctx* ctx, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0,
+                           void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count);
+int arp_poses_planes_info(arp_ctx* ctx, int64_t info[12]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
