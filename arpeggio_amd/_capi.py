@@ -50,6 +50,7 @@ SYMBOLS = (
     'arp_networks_launch', 'arp_networks_fetch', 'arp_networks_labels_fetch', 'arp_networks_info',
     'arp_poses_contacts_launch', 'arp_poses_contacts_fetch', 'arp_poses_contacts_info',
     'arp_set_plane_atoms', 'arp_poses_planes_launch', 'arp_poses_planes_fetch', 'arp_poses_planes_info',
+    'arp_poses_fingerprints_launch', 'arp_poses_fingerprints_fetch', 'arp_poses_fingerprints_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -58,6 +59,8 @@ PERSIST_BITS = RESPAIR_BITS = RESPERSIST_BITS = WBP_BITS = tables.N_BITS
 POSES_MAX_ATOMS, POSES_MAX_POSES, POSES_MAX_CUTOFF, POSES_SUMMARY = 1024, 1 << 20, 6.0, 16
 # ... their ring and amide contacts (ARP_POSES_PLANES_*)
 POSES_PLANES_SUMMARY, POSES_PLANES_MAX_RINGS, POSES_PLANES_MAX_HOME, POSES_PLANES_MAX_AMIDES, POSES_PLANES_MAX_NEAR = 16, 512, 512, 512, 256
+# ... their fingerprints (ARP_POSEFP_*)
+POSEFP_PLANES, POSEFP_MAX_REFS, POSEFP_BY_RESIDUE, POSEFP_ALL_PAIRS = 15, 64, 1, 2
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -240,6 +243,9 @@ def load():
     L.arp_poses_planes_launch.argtypes = [vp, i64, vp, vp]
     L.arp_poses_planes_fetch.argtypes = [vp, C.c_int, i64] + [vp] * 11 + [C.POINTER(i64)]
     L.arp_poses_planes_info.argtypes = [vp, vp]
+    L.arp_poses_fingerprints_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp]
+    L.arp_poses_fingerprints_fetch.argtypes = [vp, i64] + [vp] * 6 + [C.POINTER(i64)]
+    L.arp_poses_fingerprints_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1027,6 +1033,42 @@ class Context:
         d.update(moved_rings=int(info[6]), home_rings=int(info[7]), moved_amides=int(info[8]), plane_atoms=bool(info[9]), launches=int(info[10]))
         return d
 
+    def poses_fingerprints(self, planes, ctype_mask=CTYPE_ALL, by_residue=True, n_refs=0, all_pairs=False, bits=False):
+        """The resident poses result (``poses_contacts`` / ``poses_summary``) reduced on the device to interaction fingerprints
+        and their scores (arp_poses_fingerprints_*; ``arpeggio_amd.pose_fingerprints``).  The first ``n_refs`` poses of that
+        launch are the references (at most ``POSEFP_MAX_REFS``).  A feature is (node, plane): the receptor residue
+        (``by_residue=False``: receptor atom) of a record whose ``ctype`` bit is in ``ctype_mask``, and one of the SIFt bits of
+        ``planes`` (``pose_fingerprints.planes``) the record has.  Returns a dict: ``ids`` int32 [U], the nodes that occur,
+        ascending; ``count`` uint32 [P], features per pose; ``cross`` uint32 [P, n_refs], features a pose shares with a
+        reference; ``occupancy`` uint32 [U, NP], poses behind the references that have the feature; ``planes``, ``n_refs``,
+        ``level``; with ``bits=True`` the bit matrix ``bits`` uint64 [P, NP, ceil(U / 64)]; with ``all_pairs=True`` (at most
+        ``SIM_MAX_MODELS`` poses) ``inter`` uint32 [P, P].  No record is copied.  A repeated call with the same arguments on
+        the same poses result launches nothing (``poses_fingerprints_info()['launches']``)."""
+        flags = (POSEFP_BY_RESIDUE if by_residue else 0) | (POSEFP_ALL_PAIRS if all_pairs else 0)
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_fingerprints_launch(self._h, int(planes), int(ctype_mask), flags, int(n_refs), _p(info)),
+                    'arp_poses_fingerprints_launch')
+        P, Q, U, NP, W = (int(v) for v in info[:5])
+        NP = bin(int(planes)).count('1')      # (what info[3] holds)
+        out = dict(ids=np.empty(U, np.int32), count=np.empty(P, np.uint32), cross=np.empty((P, Q), np.uint32),
+                   occupancy=np.empty((U, NP), np.uint32))
+        if bits:
+            out['bits'] = np.empty((P, NP, (U + 63) // 64), np.uint64)
+        if all_pairs:
+            out['inter'] = np.empty((P, P), np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.arp_poses_fingerprints_fetch(self._h, U, _p(out['ids']), _p(out['count']), _p(out['cross']), _p(out['occupancy']),
+                                                         _p(out.get('bits')), _p(out.get('inter')), C.byref(n)), 'arp_poses_fingerprints_fetch')
+        out.update(planes=int(planes), n_refs=Q, level='residue' if by_residue else 'atom')
+        return out
+
+    def poses_fingerprints_info(self):
+        """arp_poses_fingerprints_info: poses, references, columns, planes, words per pose and word slices of the resident
+        fingerprint result (zeros while there is none), the launches that did work so far, and the flags."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_fingerprints_info(self._h, _p(info)), 'arp_poses_fingerprints_info')
+        return dict(zip(('poses', 'n_refs', 'nodes', 'planes', 'words', 'slices', 'launches', 'flags'), (int(v) for v in info)))
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
@@ -1503,9 +1545,12 @@ class Context:
         self._check(self._L.arp_networks_info(self._h, _p(nw)), 'arp_networks_info')
         cp = np.zeros(4, np.int64)
         self._check(self._L.arp_models_coupling_info(self._h, _p(cp)), 'arp_models_coupling_info')
+        fp = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_fingerprints_info(self._h, _p(fp)), 'arp_poses_fingerprints_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
                     sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
+                    posefp_nodes=int(fp[2]), posefp_words=int(fp[4]), posefp_slices=int(fp[5]), posefp_launches=int(fp[6]),
                     lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]),
                     couple_rows=int(cp[0]), couple_features=int(cp[1]), couple_tile_pairs=int(cp[2]), couple_launches=int(cp[3]),
                     networks_rows=int(nw[0]), networks_nodes=int(nw[1]), networks_launches=int(nw[2]))

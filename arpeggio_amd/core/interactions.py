@@ -461,6 +461,77 @@ class InteractionComplex:
             raise AttributeError('no pose planes yet: call run_poses(..., planes=True) first')
         return _poses.write_pose_planes(wd, self.id, self.pose_planes, self.pc, self.component_types)
 
+    def run_pose_fingerprints(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent,
+                              refs_xyz=None, refs_h_xyz=None, contacts=None, interacting_entities=None, level='residue', chunk=None,
+                              all_pairs=False):
+        """Extension beside the mirror: the interaction fingerprints of many poses of a ligand scored against reference poses ON
+        THE DEVICE — no record is copied.  Selection, ``xyz``, ``h_xyz`` and the three parameters are those of ``run_poses``.
+        ``refs_xyz`` float32 [Q, S, 3] / ``refs_h_xyz`` float64 [Q, SH, 3] are the reference poses (at most
+        ``pose_fingerprints.MAX_REFS``); the default is the resident coordinates of the movable set, Q = 1.  A feature is
+        (receptor residue or, ``level='atom'``, receptor atom; contact): ``contacts`` names the contacts
+        (``pose_fingerprints.planes``: ``None`` = every contact but bare proximity), ``interacting_entities`` the kinds of
+        entities whose records take part (``contact_filter.masks``; ``None`` = all).  Every chunk of ``chunk`` poses (default:
+        all at once) is launched as references ++ chunk (``Context.poses_summary``, then ``Context.poses_fingerprints``) and the
+        chunks are merged (``pose_fingerprints.merge``).  Returns the result ``arpeggio_amd.pose_fingerprints`` describes, with the
+        reference rows moved to ``reference_count`` / ``reference_cross`` (also kept in ``self.pose_fingerprints``): ``count`` [P],
+        ``cross`` [P, Q], ``occupancy`` over the P poses.  ``all_pairs=True`` adds ``inter`` uint32 [P, P] (one chunk of at most
+        ``similarity.MAX_MODELS`` - Q poses)."""
+        from .. import _capi, contact_filter, poses as _poses, pose_fingerprints as _fp
+        if level not in _fp.LEVELS:
+            raise ValueError(f"run_pose_fingerprints: level must be 'residue' or 'atom', not {level!r}")
+        mask = _fp.planes(contacts)
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx = self.pc, self._ctx
+        if isinstance(user_selections, np.ndarray):
+            idx = np.unique(user_selections.astype(np.int64))
+        else:
+            idx = utils.selection_parser(user_selections, pc) if user_selections else np.zeros(0, np.int64)
+        if idx.size == 0:
+            raise AttributeError('Selection must not be empty.')
+        sel = np.zeros(pc.n_atoms, np.uint8)
+        sel[idx] = 1
+        atoms, rows = _poses.movable(pc, idx)
+        x = np.ascontiguousarray(xyz, np.float32)
+        h = np.zeros((len(x), 0, 3)) if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64)
+        if refs_xyz is None:
+            rx = np.asarray(pc.xyz, np.float32)[atoms][None]
+            rh = np.asarray(pc.h_xyz, np.float64).reshape(-1, 3)[rows][None]
+        else:
+            rx = np.ascontiguousarray(refs_xyz, np.float32)
+            rh = np.zeros((len(rx), 0, 3)) if refs_h_xyz is None else np.ascontiguousarray(refs_h_xyz, np.float64)
+        Q = len(rx)
+        if not 1 <= Q <= _fp.MAX_REFS:
+            raise ValueError(f'run_pose_fingerprints: 1 ... {_fp.MAX_REFS} reference poses')
+        if len(x) < 1:
+            raise ValueError('run_pose_fingerprints: no pose given')
+        if x.shape[1:] != rx.shape[1:] or h.shape[1:] != rh.shape[1:]:
+            raise ValueError('run_pose_fingerprints: the references and the poses must have the same atoms and hydrogen rows')
+        step = int(chunk) if chunk else min(len(x), _capi.POSES_MAX_POSES - Q)
+        if step < 1:
+            raise ValueError('run_pose_fingerprints: chunk must be at least 1')
+        if all_pairs and step < len(x):
+            raise ValueError('run_pose_fingerprints: all_pairs needs all poses in one chunk')
+        ctx.set_selection(sel)
+        parts = []
+        for a in range(0, len(x), step):
+            ctx.poses_summary(np.concatenate([rx, x[a:a + step]]), np.concatenate([rh, h[a:a + step]]), interacting_cutoff, vdw_comp,
+                              include_sequence_adjacent)
+            parts.append(ctx.poses_fingerprints(mask, ctype_mask, by_residue=level == 'residue', n_refs=Q, all_pairs=all_pairs))
+        out = _fp.strip_references(parts[0] if len(parts) == 1 else _fp.merge(parts))
+        if all_pairs:
+            out['inter'] = np.ascontiguousarray(parts[0]['inter'][Q:, Q:])
+        self.pose_fingerprints = out
+        return out
+
+    def write_pose_fingerprints(self, wd):
+        """'<id>.posefp': the result of the last ``run_pose_fingerprints`` as CSV (``pose_fingerprints.write_csv``)."""
+        from .. import pose_fingerprints as _fp
+        if getattr(self, 'pose_fingerprints', None) is None:
+            raise AttributeError('no pose fingerprints yet: call run_pose_fingerprints() first')
+        return _fp.write_pose_fingerprints(wd, self.id, self.pose_fingerprints, self.pc, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""

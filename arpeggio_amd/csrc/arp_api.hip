@@ -40,6 +40,7 @@
 #include "arp_networks.h"
 #include "arp_poses.h"
 #include "arp_poses_planes.h"
+#include "arp_poses_fingerprints.h"
 #include "arp_blob.h"
 
 namespace {
@@ -308,6 +309,23 @@ struct PosesResult {
     size_t off[5] = {0, 0, 0, 0, 0};
     int64_t P = 0, S = 0, SH = 0, count = 0;
     bool valid = false;
+};
+
+// the fingerprints of the resident poses result (arp_poses_fingerprints_launch, arp_poses_fingerprints.h): the presence bitmap of
+// the nodes with its word bases, the columns, the bit matrix, the scores, and what they were made for.  Valid only while the
+// poses result it was made from is (arp_poses_contacts_launch and inputs_changed void both)
+struct PoseFpResult {
+    DevBuf<unsigned long long> presence, bits;
+    DevBuf<uint32_t> base, count, cross, occ, inter;
+    DevBuf<long long> total;
+    DevBuf<int> ids;
+    int64_t P = 0, Q = 0, U = 0, NP = 0, W = 0, slices = 0, launches = 0;
+    uint32_t planes = 0, ctype_mask = 0, flags = 0;
+    bool valid = false;
+    void release() {
+        presence.release(); bits.release(); base.release(); count.release(); cross.release(); occ.release(); inter.release();
+        total.release(); ids.release(); valid = false;
+    }
 };
 
 // the ring / amide contacts of ligand poses (arp_poses_planes_launch, arp_poses_planes.h): the atoms of the resident rings and
@@ -582,6 +600,7 @@ struct arp_ctx {
     CouplingScratch couple;
     PosesPlanesResult pplanes;            // arp_poses_planes_launch: likewise; its plane atoms go with the structure, rings or amides
     PosesResult poses;                    // arp_poses_contacts_launch: reads no bag, voided with the inputs (inputs_changed)
+    PoseFpResult posefp;                  // arp_poses_fingerprints_launch: reads the poses result alone, voided with it
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -868,6 +887,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         void_results(c, RES_AA | RES_PLANES);
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
         c->poses.valid = false;      // (made from the inputs alone, the selection among them: no row in void_results)
+        c->posefp.valid = false;     // (made from the poses result alone)
         c->pplanes.valid = c->pplanes.setup = false;
     }
     if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->pplanes.have_atoms = false;
@@ -2405,6 +2425,7 @@ void arp_destroy(arp_ctx* c) {
     c->similarity.bits.release(); c->similarity.inter.release();
     c->poses.sel_h.release(); c->poses.pos_of.release(); c->poses.xyz.release(); c->poses.hx.release(); c->poses.ctr.release();
     c->pplanes.release();
+    c->posefp.release();
     c->poses.summary.release(); c->poses.pose_off.release(); c->poses.sort.release(); c->poses.slab.release(); c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -5328,8 +5349,9 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     }
     const int64_t SH = R.SH;
     if (SH > 0 && !h_xyz) FAIL(c, ARP_E_ARG, fn + "h_xyz missing (the movable set has hydrogens)");
-    // ---- from here on the previous result is gone
+    // ---- from here on the previous result is gone, and the fingerprints made from it
     R.valid = false;
+    c->posefp.valid = false;
     R.count = 0;
     HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
     HIPCHK(c, R.hx.reserve(std::max<size_t>((size_t)P * (size_t)SH * 3, 1)));
@@ -5681,6 +5703,160 @@ int arp_poses_planes_info(arp_ctx* c, int64_t info[12]) {
     info[9] = R.have_atoms ? 1 : 0;
     info[10] = R.launches;
     info[11] = 0;
+    return ARP_OK;
+}
+
+// ---- pose fingerprints (arp_poses_fingerprints.h): the resident poses result -> bit matrix -> scores
+// Only the poses result is read (its sorted slab, pose_off, pos_of) and res_id; only this result's own buffers are written.
+// Nothing is sorted: the columns come from a presence bitmap of the nodes.  One wait: U, which sizes the matrix.
+static_assert(POSEFP_PLANES == ARP_POSEFP_PLANES && POSEFP_PLANES == TABLE_SIFT_BITS && POSEFP_MAX_REFS == ARP_POSEFP_MAX_REFS &&
+              POSEFP_BY_RESIDUE == ARP_POSEFP_BY_RESIDUE && POSEFP_ALL_PAIRS == ARP_POSEFP_ALL_PAIRS && POSEFP_MAX_REFS == POSEFP_TILE &&
+              POSEFP_TILE == SIM_TILE && POSEFP_KC == SIM_KC, "arp_poses_fingerprints.h names the header's limits and k_sim_gram's panel");
+
+// word slices of a popcount product over W words whose tiles number `tiles`: as many as fill the device, a slice no shorter
+// than one staged panel (the rule of arp_models_similarity_launch)
+static void popcount_slices(const arp_ctx* c, long long W, long long tiles, long long* per, long long* slices) {
+    const long long chunks = (W + SIM_KC - 1) / SIM_KC;
+    const long long want = std::max<long long>(1, std::min<long long>(chunks, (2ll * c->num_cu + tiles - 1) / tiles));
+    *per = (chunks + want - 1) / want * SIM_KC;
+    *slices = (W + *per - 1) / *per;
+}
+
+static void posefp_info(const PoseFpResult& F, int64_t info[8]) {
+    const int64_t v[8] = {F.P, F.Q, F.U, F.NP, F.W, F.slices, F.launches, (int64_t)F.flags};
+    for (int q = 0; q < 8; ++q) info[q] = (F.valid || q == 6) ? v[q] : 0;
+}
+
+int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_poses_fingerprints_launch: ";
+    PoseFpResult& F = c->posefp;
+    const PosesResult& R = c->poses;
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
+    if (planes & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
+    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
+    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no record");
+    if (flags & ~(ARP_POSEFP_BY_RESIDUE | ARP_POSEFP_ALL_PAIRS)) FAIL(c, ARP_E_ARG, fn + "unknown flag");
+    const int64_t P = R.P, Q = n_refs;
+    if (Q < 0 || Q > ARP_POSEFP_MAX_REFS || Q > P) FAIL(c, ARP_E_ARG, fn + "n_refs must be 0 ... min(ARP_POSEFP_MAX_REFS, poses of the launch)");
+    const bool by_res = (flags & ARP_POSEFP_BY_RESIDUE) != 0, all_pairs = (flags & ARP_POSEFP_ALL_PAIRS) != 0;
+    if (by_res && (!c->has_res || c->nres <= 0)) FAIL(c, ARP_E_ARG, fn + "no residues resident (ARP_POSEFP_BY_RESIDUE)");
+    if (all_pairs && P > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "ARP_POSEFP_ALL_PAIRS with more than ARP_SIM_MAX_MODELS = 4096 poses (the matrix would pass 64 MiB)");
+    if (F.valid && F.planes == planes && F.ctype_mask == ctype_mask && F.flags == flags && F.Q == Q) { posefp_info(F, info); return ARP_OK; }
+    F.valid = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t N = by_res ? c->nres : c->n, NW = (N + 63) / 64;
+    const int NP = __builtin_popcount(planes);
+    const size_t k = (size_t)R.count;
+    HIPCHK(c, F.presence.reserve((size_t)NW));
+    HIPCHK(c, F.base.reserve((size_t)NW));
+    HIPCHK(c, F.total.reserve(1));
+    HIPCHK(c, F.count.reserve((size_t)P));
+    HIPCHK(c, F.cross.reserve(std::max<size_t>((size_t)(P * Q), 1)));
+    if (all_pairs) HIPCHK(c, F.inter.reserve((size_t)(P * P)));
+    PoseFpArgs A{};
+    const uint8_t* const slab = R.slab.p;
+    A.ci = (const int*)(slab + R.off[0]); A.cj = (const int*)(slab + R.off[1]);
+    A.sift = (const uint16_t*)(slab + R.off[3]); A.ctype = slab + R.off[4];
+    A.pose_off = R.pose_off.p; A.pos_of = R.pos_of.p; A.res_id = c->res_id.p;
+    A.k = (long long)k; A.P = (int)P; A.Q = (int)Q; A.N = N; A.by_res = by_res ? 1 : 0;
+    A.planes = planes; A.ctype_mask = ctype_mask;
+    A.presence = F.presence.p; A.base = F.base.p; A.NW = NW; A.total = F.total.p;
+    A.NP = NP; A.count = F.count.p; A.cross = F.cross.p;
+    const auto done = [&](long long U, long long W, long long slices) {
+        F.P = P; F.Q = Q; F.U = U; F.NP = NP; F.W = W; F.slices = slices;
+        F.planes = planes; F.ctype_mask = ctype_mask; F.flags = flags;
+        F.valid = true;
+        ++F.launches;
+        posefp_info(F, info);
+        return ARP_OK;
+    };
+    // ---- the columns: presence bitmap of the nodes, popcounts, scan; the host learns U (the one wait)
+    long long U = 0;
+    if (k > 0) {
+        HIPCHK(c, hipMemsetAsync(F.presence.p, 0, (size_t)NW * sizeof(unsigned long long), c->stream));
+        // (a block a CU: the threads that run first all see their bit unset and OR; the fewer they are, the fewer ORs queue up
+        // on the few words around the ligand — those behind them read the bit and skip)
+        hipLaunchKernelGGL(k_pfp_mark, dim3(nblocks((int64_t)k, 256, c->num_cu)), dim3(256), 0, c->stream, A);
+        hipLaunchKernelGGL(k_pfp_scan, dim3(1), dim3(POSEFP_SCAN_THREADS), 0, c->stream, A);
+        CHK(wait_count(c, F.total.p, &U, fn + "mark / scan"));
+        if (U < 0 || U > N) FAIL(c, ARP_E_HIP, fn + "column count out of range");
+    }
+    if (U == 0) {      // no participating record: no column, no feature in any pose
+        HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)P * sizeof(uint32_t), c->stream));
+        if (Q > 0) HIPCHK(c, hipMemsetAsync(F.cross.p, 0, (size_t)(P * Q) * sizeof(uint32_t), c->stream));
+        if (all_pairs) HIPCHK(c, hipMemsetAsync(F.inter.p, 0, (size_t)(P * P) * sizeof(uint32_t), c->stream));
+        return done(0, 0, 0);
+    }
+    // ---- the bit matrix: NP planes of ceil(U / 64) words a pose, OR-ed into zeroed memory by a wave per pose
+    const long long wpp = (U + 63) / 64, W = (long long)NP * wpp;
+    if ((long long)NP * U >= (1ll << 32)) FAIL(c, ARP_E_CAPACITY, fn + "2^32 features or more (a count would not fit uint32)");
+    if (P * W >= (1ll << 29)) FAIL(c, ARP_E_CAPACITY, fn + "a bit matrix of 4 GiB or more (launch fewer poses)");
+    HIPCHK(c, F.ids.reserve((size_t)U));
+    HIPCHK(c, F.occ.reserve((size_t)(U * NP)));
+    HIPCHK(c, F.bits.reserve((size_t)(P * W)));
+    HIPCHK(c, hipMemsetAsync(F.bits.p, 0, (size_t)(P * W) * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(F.occ.p, 0, (size_t)(U * NP) * sizeof(uint32_t), c->stream));
+    A.ids = F.ids.p; A.U = U; A.bits = F.bits.p; A.wpp = wpp; A.W = W; A.occ = F.occ.p;
+    hipLaunchKernelGGL(k_pfp_ids, dim3(nblocks(NW, 256, 1024)), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_pfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A);
+    // ---- cross = B R^T and count: the pose tiles times as many word slices as fill the device
+    const long long tiles = (P + POSEFP_TILE - 1) / POSEFP_TILE;
+    long long per = 0, slices = 0;
+    popcount_slices(c, W, tiles, &per, &slices);
+    A.per = per; A.slices = (int)slices;
+    if (slices > 1) {
+        HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)P * sizeof(uint32_t), c->stream));
+        if (Q > 0) HIPCHK(c, hipMemsetAsync(F.cross.p, 0, (size_t)(P * Q) * sizeof(uint32_t), c->stream));
+    }
+    hipLaunchKernelGGL(k_pfp_cross, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, c->stream, A);
+    // ---- occupancy: column sums over the poses behind the references, the pose tiles cut into as many slices as fill the device
+    const long long chunks = (W + POSEFP_KC - 1) / POSEFP_KC;
+    // (a block keeps at least eight pose tiles where there are that many: its sums stay in registers, and fewer blocks meet on
+    // a counter at the end)
+    const long long pose_slices = std::max<long long>(1, std::min<long long>((tiles + 7) / 8, (2ll * c->num_cu + chunks - 1) / chunks));
+    A.occ_tiles = (int)((tiles + pose_slices - 1) / pose_slices);
+    hipLaunchKernelGGL(k_pfp_occupancy, dim3((unsigned)chunks, (unsigned)((tiles + A.occ_tiles - 1) / A.occ_tiles)), dim3(256), 0, c->stream, A);
+    // ---- all pairs: k_sim_gram on this matrix, the poses as its models
+    if (all_pairs) {
+        SimArgs G{};
+        const long long pairs = tiles * (tiles + 1) / 2;
+        long long gper = 0, gslices = 0;
+        popcount_slices(c, W, pairs, &gper, &gslices);
+        G.F = (uint32_t)P; G.bits = F.bits.p; G.wpp = wpp; G.W = W; G.per = gper; G.slices = (int)gslices; G.tiles = (int)tiles;
+        G.inter = F.inter.p;
+        if (gslices > 1) HIPCHK(c, hipMemsetAsync(F.inter.p, 0, (size_t)(P * P) * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(k_sim_gram, dim3((unsigned)pairs, (unsigned)gslices), dim3(256), 0, c->stream, G);
+    }
+    CHK(check_launch(c, (fn + "ids / bits / cross / occupancy").c_str()));
+    return done(U, W, slices);
+}
+
+int arp_poses_fingerprints_fetch(arp_ctx* c, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy,
+                                 uint64_t* bits, uint32_t* inter, int64_t* n_nodes) {
+    if (!c || !n_nodes) return ARP_E_ARG;
+    const PoseFpResult& F = c->posefp;
+    if (!F.valid)      // (voided wherever the poses result is)
+        FAIL(c, ARP_E_ARG, "arp_poses_fingerprints_fetch: no result (arp_poses_fingerprints_launch; the poses result was replaced or an input or the selection changed since)");
+    *n_nodes = F.U;
+    if ((ids || occupancy || bits) && F.U > cap_nodes) FAIL(c, ARP_E_CAPACITY, "arp_poses_fingerprints_fetch: output buffers too small (cap_nodes < *n_nodes)");
+    if (inter && !(F.flags & ARP_POSEFP_ALL_PAIRS)) FAIL(c, ARP_E_ARG, "arp_poses_fingerprints_fetch: no all-pairs matrix (launch with ARP_POSEFP_ALL_PAIRS)");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(download_async(c, ids, (const int32_t*)F.ids.p, (size_t)F.U));
+    CHK(download_async(c, count, (const uint32_t*)F.count.p, (size_t)F.P));
+    CHK(download_async(c, cross, (const uint32_t*)F.cross.p, (size_t)(F.P * F.Q)));
+    CHK(download_async(c, occupancy, (const uint32_t*)F.occ.p, (size_t)(F.U * F.NP)));
+    CHK(download_async(c, (unsigned long long*)bits, (const unsigned long long*)F.bits.p, (size_t)(F.P * F.W)));
+    CHK(download_async(c, inter, (const uint32_t*)F.inter.p, (size_t)(F.P * F.P)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ARP_OK;
+}
+
+int arp_poses_fingerprints_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    posefp_info(c->posefp, info);
     return ARP_OK;
 }
 

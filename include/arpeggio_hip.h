@@ -1092,6 +1092,60 @@ int arp_poses_planes_launch(arp_ctx* ctx, int64_t n_poses, const float* xyz, int
 int arp_poses_planes_fetch(arp_ctx* ctx, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0,
                            void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count);
 int arp_poses_planes_info(arp_ctx* ctx, int64_t info[12]);
+/* Pose fingerprints: the resident result of arp_poses_contacts_launch reduced on the device to interaction fingerprints and
+ * their scores against reference poses (csrc/arp_poses_fingerprints.h).  Only small integers cross PCIe: no
+ * record is copied.
+ *
+ * The first n_refs poses of the poses launch are the REFERENCES, 0 <= n_refs <= ARP_POSEFP_MAX_REFS and n_refs <= P.
+ *   node      the receptor partner of a record: whichever of i / j is not in the movable set — that atom's packed id or, with
+ *             ARP_POSEFP_BY_RESIDUE, its res_id.
+ *   plane     q < ARP_POSEFP_PLANES = 15, "SIFt bit q" (ARP_S_CLASH ... ARP_S_WEAK_POLAR); `planes` is a non-zero mask of them,
+ *             NP = popcount(planes).  The k-th selected plane is the k-th set bit of `planes`, ascending.
+ *   A record PARTICIPATES when bit ctype of ctype_mask is set (the 7 contact types, as in arp_contacts_filter_launch) and
+ *   sift & planes != 0.
+ *   columns   the distinct nodes of the participating records of the whole launch, references included, ascending: ids[U].
+ *   Feature (u, q) is PRESENT in pose p when a participating record of pose p has node ids[u] and SIFt bit q.
+ *
+ * Results (arp_poses_fingerprints_fetch; ANY pointer may be NULL):
+ *   ids        int32  [U]                      the columns
+ *   count      uint32 [P]                      features present in pose p
+ *   cross      uint32 [P][n_refs]              features present in pose p and in reference q; the rows of the references
+ *                                              themselves are included
+ *   occupancy  uint32 [U][NP]                  poses p >= n_refs in which the feature is present: the references are not
+ *                                              counted, so chunks that each carry the same references add up exactly
+ *   bits       uint64 [P][NP][ceil(U / 64)]    the bit matrix: feature (u, k-th selected plane) is bit u & 63 of word u >> 6 of
+ *                                              plane k (the layout of arp_models_similarity's matrix); padding bits are zero
+ *   inter      uint32 [P][P]                   only with ARP_POSEFP_ALL_PAIRS (P <= ARP_SIM_MAX_MODELS): features present in pose
+ *                                              f and in pose g; the diagonal is count
+ * Everything is a presence or a count: no float exists on the device and the order of the records cannot show in a result.
+ * The ring and amide records of the poses (arp_poses_planes_launch) take no part: mapping them to receptor residues needs the
+ * ring residues that launch rebuilds per pose — the follow-up.
+ *
+ * arp_poses_fingerprints_launch: info[8] as arp_poses_fingerprints_info gives it.  One host wait (U, which sizes the matrix);
+ *   every launch and copy goes on the context's stream.  A second launch with the same arguments on the same poses result
+ *   returns without work (info[6], the launches that did work, stays); other arguments remake the result.  Refusals are
+ *   ARP_E_ARG with the cause named, and none of them touches a resident result: no poses result; planes 0 or with bits beyond
+ *   bit 14; ctype_mask 0 or with bits beyond the 7 types; an unknown flag; n_refs < 0, > ARP_POSEFP_MAX_REFS or > P; a pass
+ *   enqueued and not waited for.  ARP_E_CAPACITY: ARP_POSEFP_ALL_PAIRS with P > ARP_SIM_MAX_MODELS = 4096 (nothing touched);
+ *   NP * U >= 2^32; a bit matrix of 4 GiB or more (launch fewer poses) — the last two leave no fingerprint result.
+ *   The result is void exactly when the poses result it was made from is void or replaced: a new arp_poses_contacts_launch,
+ *   arp_set_selection, a new structure, models or a batch.  It reads no bag and voids nothing: the bags of the last pass, every
+ *   table made from them and both poses results stay fetchable and byte-equal.
+ *
+ * arp_poses_fingerprints_fetch: *n_nodes = U.  ARP_E_CAPACITY when ids, occupancy or bits is asked for and cap_nodes < U;
+ *   ARP_E_ARG without a valid result, and when inter is asked for of a launch without ARP_POSEFP_ALL_PAIRS.
+ *
+ * arp_poses_fingerprints_info: info[0] = P, [1] = n_refs, [2] = U, [3] = NP, [4] = words per pose W = NP * ceil(U / 64),
+ *   [5] = word slices of the cross product (> 1: integer atomic adds into zeroed arrays), [6] = launches that did work,
+ *   [7] = flags.  [0] ... [5] and [7] are 0 while there is no result. */
+#define ARP_POSEFP_PLANES 15
+#define ARP_POSEFP_MAX_REFS 64
+#define ARP_POSEFP_BY_RESIDUE 1u
+#define ARP_POSEFP_ALL_PAIRS 2u
+int arp_poses_fingerprints_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]);
+int arp_poses_fingerprints_fetch(arp_ctx* ctx, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy,
+                                 uint64_t* bits, uint32_t* inter, int64_t* n_nodes);
+int arp_poses_fingerprints_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
