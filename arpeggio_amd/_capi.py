@@ -51,6 +51,7 @@ SYMBOLS = (
     'arp_poses_contacts_launch', 'arp_poses_contacts_fetch', 'arp_poses_contacts_info',
     'arp_set_plane_atoms', 'arp_poses_planes_launch', 'arp_poses_planes_fetch', 'arp_poses_planes_info',
     'arp_poses_fingerprints_launch', 'arp_poses_fingerprints_fetch', 'arp_poses_fingerprints_info',
+    'arp_poses_fingerprints_planes_launch',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -61,6 +62,7 @@ POSES_MAX_ATOMS, POSES_MAX_POSES, POSES_MAX_CUTOFF, POSES_SUMMARY = 1024, 1 << 2
 POSES_PLANES_SUMMARY, POSES_PLANES_MAX_RINGS, POSES_PLANES_MAX_HOME, POSES_PLANES_MAX_AMIDES, POSES_PLANES_MAX_NEAR = 16, 512, 512, 512, 256
 # ... their fingerprints (ARP_POSEFP_*)
 POSEFP_PLANES, POSEFP_MAX_REFS, POSEFP_BY_RESIDUE, POSEFP_ALL_PAIRS = 15, 64, 1, 2
+POSEFP_ALL_PLANES = 29           # ARP_POSEFP_ALL_PLANES: the SIFt bits and the 14 ring / amide class planes behind them
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -244,6 +246,7 @@ def load():
     L.arp_poses_planes_fetch.argtypes = [vp, C.c_int, i64] + [vp] * 11 + [C.POINTER(i64)]
     L.arp_poses_planes_info.argtypes = [vp, vp]
     L.arp_poses_fingerprints_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp]
+    L.arp_poses_fingerprints_planes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp]
     L.arp_poses_fingerprints_fetch.argtypes = [vp, i64] + [vp] * 6 + [C.POINTER(i64)]
     L.arp_poses_fingerprints_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
@@ -1043,11 +1046,15 @@ class Context:
         reference; ``occupancy`` uint32 [U, NP], poses behind the references that have the feature; ``planes``, ``n_refs``,
         ``level``; with ``bits=True`` the bit matrix ``bits`` uint64 [P, NP, ceil(U / 64)]; with ``all_pairs=True`` (at most
         ``SIM_MAX_MODELS`` poses) ``inter`` uint32 [P, P].  No record is copied.  A repeated call with the same arguments on
-        the same poses result launches nothing (``poses_fingerprints_info()['launches']``)."""
+        the same poses result launches nothing (``poses_fingerprints_info()['launches']``).
+
+        A ``planes`` mask with a bit from ``POSEFP_PLANES`` on (``pose_fingerprints.planes(classes=...)``) adds the ring and amide
+        classes as planes (arp_poses_fingerprints_planes_launch): the resident ``poses_planes`` result of the SAME poses is
+        reduced into the same matrix, residue level only; ``planes`` in the result is the unified mask."""
         flags = (POSEFP_BY_RESIDUE if by_residue else 0) | (POSEFP_ALL_PAIRS if all_pairs else 0)
         info = np.zeros(8, np.int64)
-        self._check(self._L.arp_poses_fingerprints_launch(self._h, int(planes), int(ctype_mask), flags, int(n_refs), _p(info)),
-                    'arp_poses_fingerprints_launch')
+        entry = 'arp_poses_fingerprints_planes_launch' if int(planes) >> POSEFP_PLANES else 'arp_poses_fingerprints_launch'
+        self._check(getattr(self._L, entry)(self._h, int(planes), int(ctype_mask), flags, int(n_refs), _p(info)), entry)
         P, Q, U, NP, W = (int(v) for v in info[:5])
         NP = bin(int(planes)).count('1')      # (what info[3] holds)
         out = dict(ids=np.empty(U, np.int32), count=np.empty(P, np.uint32), cross=np.empty((P, Q), np.uint32),

@@ -463,7 +463,7 @@ class InteractionComplex:
 
     def run_pose_fingerprints(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent,
                               refs_xyz=None, refs_h_xyz=None, contacts=None, interacting_entities=None, level='residue', chunk=None,
-                              all_pairs=False):
+                              all_pairs=False, classes=()):
         """Extension beside the mirror: the interaction fingerprints of many poses of a ligand scored against reference poses ON
         THE DEVICE — no record is copied.  Selection, ``xyz``, ``h_xyz`` and the three parameters are those of ``run_poses``.
         ``refs_xyz`` float32 [Q, S, 3] / ``refs_h_xyz`` float64 [Q, SH, 3] are the reference poses (at most
@@ -475,11 +475,17 @@ class InteractionComplex:
         chunks are merged (``pose_fingerprints.merge``).  Returns the result ``arpeggio_amd.pose_fingerprints`` describes, with the
         reference rows moved to ``reference_count`` / ``reference_cross`` (also kept in ``self.pose_fingerprints``): ``count`` [P],
         ``cross`` [P, Q], ``occupancy`` over the P poses.  ``all_pairs=True`` adds ``inter`` uint32 [P, P] (one chunk of at most
-        ``similarity.MAX_MODELS`` - Q poses)."""
+        ``similarity.MAX_MODELS`` - Q poses).  ``classes`` adds the ring and amide classes as planes
+        (``pose_fingerprints.planes``: names of ``CLASS_PLANE_NAMES``, a table's name or 'all'; residue level only; the pack
+        needs ``ring_atoms`` and ``amide_atoms``): every chunk is then also launched as ``Context.poses_planes_summary`` on
+        the same references ++ chunk coordinates, and both resident results are reduced into one matrix."""
         from .. import _capi, contact_filter, poses as _poses, pose_fingerprints as _fp
         if level not in _fp.LEVELS:
             raise ValueError(f"run_pose_fingerprints: level must be 'residue' or 'atom', not {level!r}")
-        mask = _fp.planes(contacts)
+        mask = _fp.planes(contacts, classes)
+        with_classes = (mask >> _fp.N_PLANES) != 0
+        if with_classes and level != 'residue':
+            raise ValueError("run_pose_fingerprints: the ring / amide class planes exist at level='residue' only")
         ctype_mask = contact_filter.masks(None, interacting_entities)[1]
         if self._ctx is None:
             self.initialize()
@@ -514,10 +520,14 @@ class InteractionComplex:
         if all_pairs and step < len(x):
             raise ValueError('run_pose_fingerprints: all_pairs needs all poses in one chunk')
         ctx.set_selection(sel)
+        if with_classes:
+            ctx.set_plane_atoms(pc)
         parts = []
         for a in range(0, len(x), step):
-            ctx.poses_summary(np.concatenate([rx, x[a:a + step]]), np.concatenate([rh, h[a:a + step]]), interacting_cutoff, vdw_comp,
-                              include_sequence_adjacent)
+            both = np.concatenate([rx, x[a:a + step]])
+            ctx.poses_summary(both, np.concatenate([rh, h[a:a + step]]), interacting_cutoff, vdw_comp, include_sequence_adjacent)
+            if with_classes:
+                ctx.poses_planes_summary(both)
             parts.append(ctx.poses_fingerprints(mask, ctype_mask, by_residue=level == 'residue', n_refs=Q, all_pairs=all_pairs))
         out = _fp.strip_references(parts[0] if len(parts) == 1 else _fp.merge(parts))
         if all_pairs:

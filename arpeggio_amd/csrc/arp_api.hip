@@ -313,7 +313,8 @@ struct PosesResult {
 
 // the fingerprints of the resident poses result (arp_poses_fingerprints_launch, arp_poses_fingerprints.h): the presence bitmap of
 // the nodes with its word bases, the columns, the bit matrix, the scores, and what they were made for.  Valid only while the
-// poses result it was made from is (arp_poses_contacts_launch and inputs_changed void both)
+// poses result it was made from is (arp_poses_contacts_launch and inputs_changed void both); one made with class planes
+// (arp_poses_fingerprints_planes_launch: `classes`) read the poses-planes result too and goes with either
 struct PoseFpResult {
     DevBuf<unsigned long long> presence, bits;
     DevBuf<uint32_t> base, count, cross, occ, inter;
@@ -321,7 +322,7 @@ struct PoseFpResult {
     DevBuf<int> ids;
     int64_t P = 0, Q = 0, U = 0, NP = 0, W = 0, slices = 0, launches = 0;
     uint32_t planes = 0, ctype_mask = 0, flags = 0;
-    bool valid = false;
+    bool valid = false, classes = false;
     void release() {
         presence.release(); bits.release(); base.release(); count.release(); cross.release(); occ.release(); inter.release();
         total.release(); ids.release(); valid = false;
@@ -5465,6 +5466,7 @@ int arp_set_plane_atoms(arp_ctx* c, const int32_t* ring_off, const int32_t* ring
     HIPCHK(c, hipSetDevice(c->device));
     PosesPlanesResult& R = c->pplanes;
     R.valid = R.setup = R.have_atoms = false;
+    if (c->posefp.classes) c->posefp.valid = false;
     const int32_t zero = 0;
     const size_t nidx = c->nring > 0 ? (size_t)ring_off[c->nring] : 0;
     CHK(upload(c, R.ring_off, c->nring > 0 ? ring_off : &zero, (size_t)c->nring + 1));
@@ -5549,8 +5551,9 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     if (!R.setup) CHK(poses_planes_setup(c, fn));
     const int n = (int)c->n, S = (int)c->nsel;
     const int64_t P = n_poses;
-    // ---- from here on the previous result is gone
+    // ---- from here on the previous result is gone, and the fingerprints made with its class planes
     R.valid = false;
+    if (c->posefp.classes) c->posefp.valid = false;
     for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
     const int blocks = (int)std::min<int64_t>(P, PPL_MAX_BLOCKS);
     const int ws_rings = R.n_mring + R.n_hring + PPL_MAX_NEAR;
@@ -5707,11 +5710,16 @@ int arp_poses_planes_info(arp_ctx* c, int64_t info[12]) {
 }
 
 // ---- pose fingerprints (arp_poses_fingerprints.h): the resident poses result -> bit matrix -> scores
-// Only the poses result is read (its sorted slab, pose_off, pos_of) and res_id; only this result's own buffers are written.
+// Only the poses result is read (its sorted slab, pose_off, pos_of) and res_id — with class planes (5r) also the poses-planes
+// result's four tables, offsets and set-up tables —; only this result's own buffers are written.
 // Nothing is sorted: the columns come from a presence bitmap of the nodes.  One wait: U, which sizes the matrix.
 static_assert(POSEFP_PLANES == ARP_POSEFP_PLANES && POSEFP_PLANES == TABLE_SIFT_BITS && POSEFP_MAX_REFS == ARP_POSEFP_MAX_REFS &&
               POSEFP_BY_RESIDUE == ARP_POSEFP_BY_RESIDUE && POSEFP_ALL_PAIRS == ARP_POSEFP_ALL_PAIRS && POSEFP_MAX_REFS == POSEFP_TILE &&
               POSEFP_TILE == SIM_TILE && POSEFP_KC == SIM_KC, "arp_poses_fingerprints.h names the header's limits and k_sim_gram's panel");
+// the class planes: the four tables of the poses-planes result are read as well, and nothing of it is written
+static_assert(POSEFP_ALL_PLANES == ARP_POSEFP_ALL_PLANES && POSEFP_PLANE_AP_ATOM == ARP_POSEFP_PLANES &&
+              POSEFP_PLANE_GP_RING == ARP_POSEFP_ALL_PLANES - 1 && (ARP_AP_METSULPHURPI >> (POSEFP_AP_BITS - 1)) == 1u,
+              "arp_poses_fingerprints.h names the header's planes");
 
 // word slices of a popcount product over W words whose tiles number `tiles`: as many as fill the device, a slice no shorter
 // than one staged panel (the rule of arp_models_similarity_launch)
@@ -5727,14 +5735,20 @@ static void posefp_info(const PoseFpResult& F, int64_t info[8]) {
     for (int q = 0; q < 8; ++q) info[q] = (F.valid || q == 6) ? v[q] : 0;
 }
 
-int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]) {
-    if (!c || !info) return ARP_E_ARG;
-    const std::string fn = "arp_poses_fingerprints_launch: ";
+// Both entries: arp_poses_fingerprints_launch admits the 15 SIFt bits and reads the poses result alone; with a bit from
+// ARP_POSEFP_PLANES on (arp_poses_fingerprints_planes_launch) the four tables of the poses-planes result are
+// marked and walked as well, after a check on the device that both results were made from the same pose coordinates — its flag
+// comes back with U, in the one wait.
+static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
+                         int64_t info[8]) {
     PoseFpResult& F = c->posefp;
     const PosesResult& R = c->poses;
+    const PosesPlanesResult& L = c->pplanes;
+    const bool classes = (planes >> ARP_POSEFP_PLANES) != 0;
     if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
     if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
-    if (planes & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (n_planes == ARP_POSEFP_PLANES && (planes & ~((1u << ARP_POSEFP_PLANES) - 1u))) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (planes & ~((1u << ARP_POSEFP_ALL_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 29 planes (15 SIFt bits, 14 ring / amide classes)");
     if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
     if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
     if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no record");
@@ -5744,15 +5758,21 @@ int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_ma
     const bool by_res = (flags & ARP_POSEFP_BY_RESIDUE) != 0, all_pairs = (flags & ARP_POSEFP_ALL_PAIRS) != 0;
     if (by_res && (!c->has_res || c->nres <= 0)) FAIL(c, ARP_E_ARG, fn + "no residues resident (ARP_POSEFP_BY_RESIDUE)");
     if (all_pairs && P > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "ARP_POSEFP_ALL_PAIRS with more than ARP_SIM_MAX_MODELS = 4096 poses (the matrix would pass 64 MiB)");
+    if (classes) {
+        if (!by_res) FAIL(c, ARP_E_ARG, fn + "ring / amide class planes need ARP_POSEFP_BY_RESIDUE (their nodes are residues)");
+        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no poses-planes result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
+        if (L.P != R.P || L.S != R.S) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result differ in P or S (launch both on the same poses)");
+    }
     if (F.valid && F.planes == planes && F.ctype_mask == ctype_mask && F.flags == flags && F.Q == Q) { posefp_info(F, info); return ARP_OK; }
     F.valid = false;
+    F.classes = classes;
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t N = by_res ? c->nres : c->n, NW = (N + 63) / 64;
     const int NP = __builtin_popcount(planes);
     const size_t k = (size_t)R.count;
     HIPCHK(c, F.presence.reserve((size_t)NW));
     HIPCHK(c, F.base.reserve((size_t)NW));
-    HIPCHK(c, F.total.reserve(1));
+    HIPCHK(c, F.total.reserve(2));      // U; the same-poses flag
     HIPCHK(c, F.count.reserve((size_t)P));
     HIPCHK(c, F.cross.reserve(std::max<size_t>((size_t)(P * Q), 1)));
     if (all_pairs) HIPCHK(c, F.inter.reserve((size_t)(P * P)));
@@ -5773,15 +5793,42 @@ int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_ma
         posefp_info(F, info);
         return ARP_OK;
     };
+    // ---- the ring / amide tables (class planes): the poses-planes result's columns, offsets and set-up tables
+    PoseFpTables T{};
+    int64_t k_classes = 0;
+    if (classes) {
+        static const int ctype_col[4] = {1, 2, 0, 0};      // the byte column that holds ctype (arp_poses_planes_fetch)
+        for (int t = 0; t < 4; ++t) {
+            T.first[t] = L.col.i0[t]; T.second[t] = L.col.i1[t]; T.ctype[t] = L.col.u[t][ctype_col[t]];
+            T.count[t] = L.counts[t];
+            k_classes = std::max(k_classes, L.counts[t]);
+        }
+        T.ap_mask = L.col.u[0][0];
+        T.pose_off = L.pose_off.p;
+        T.pos_of = L.pos_of.p; T.ring_static = L.ring_static.p; T.am_pos = L.am_pos.p;
+        T.ring_off = L.ring_off.p; T.ring_idx = L.ring_idx.p; T.am_res = c->am_res.p;
+        T.n = (int)c->n; T.nring = (int)c->nring; T.namide = (int)c->namide;
+    }
     // ---- the columns: presence bitmap of the nodes, popcounts, scan; the host learns U (the one wait)
     long long U = 0;
-    if (k > 0) {
+    if (k > 0 || classes) {
         HIPCHK(c, hipMemsetAsync(F.presence.p, 0, (size_t)NW * sizeof(unsigned long long), c->stream));
+        if (classes) HIPCHK(c, hipMemsetAsync(F.total.p + 1, 0, sizeof(long long), c->stream));
         // (a block a CU: the threads that run first all see their bit unset and OR; the fewer they are, the fewer ORs queue up
         // on the few words around the ligand — those behind them read the bit and skip)
-        hipLaunchKernelGGL(k_pfp_mark, dim3(nblocks((int64_t)k, 256, c->num_cu)), dim3(256), 0, c->stream, A);
+        if (k > 0) hipLaunchKernelGGL(k_pfp_mark, dim3(nblocks((int64_t)k, 256, c->num_cu)), dim3(256), 0, c->stream, A);
+        if (classes) {
+            hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(P * R.S * 3, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.xyz.p,
+                               (const uint32_t*)L.xyz.p, (long long)(P * R.S * 3), (uint32_t*)(F.total.p + 1));
+            if (k_classes > 0) hipLaunchKernelGGL(k_pfp_mark_planes, dim3(nblocks(k_classes, 256, c->num_cu), 4), dim3(256), 0, c->stream, A, T);
+        }
         hipLaunchKernelGGL(k_pfp_scan, dim3(1), dim3(POSEFP_SCAN_THREADS), 0, c->stream, A);
-        CHK(wait_count(c, F.total.p, &U, fn + "mark / scan"));
+        CHK(check_launch(c, (fn + "mark / scan").c_str()));
+        CHK(stage_copy(c, F.total.p, 2 * sizeof(long long)));
+        long long h[2];
+        memcpy(h, c->table_stage, sizeof(h));
+        if (classes && h[1] != 0) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result were made from different poses");
+        U = h[0];
         if (U < 0 || U > N) FAIL(c, ARP_E_HIP, fn + "column count out of range");
     }
     if (U == 0) {      // no participating record: no column, no feature in any pose
@@ -5801,7 +5848,8 @@ int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_ma
     HIPCHK(c, hipMemsetAsync(F.occ.p, 0, (size_t)(U * NP) * sizeof(uint32_t), c->stream));
     A.ids = F.ids.p; A.U = U; A.bits = F.bits.p; A.wpp = wpp; A.W = W; A.occ = F.occ.p;
     hipLaunchKernelGGL(k_pfp_ids, dim3(nblocks(NW, 256, 1024)), dim3(256), 0, c->stream, A);
-    hipLaunchKernelGGL(k_pfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A);
+    if (k > 0) hipLaunchKernelGGL(k_pfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A);
+    if (k_classes > 0) hipLaunchKernelGGL(k_pfp_bits_planes, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A, T);
     // ---- cross = B R^T and count: the pose tiles times as many word slices as fill the device
     const long long tiles = (P + POSEFP_TILE - 1) / POSEFP_TILE;
     long long per = 0, slices = 0;
@@ -5832,6 +5880,16 @@ int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_ma
     }
     CHK(check_launch(c, (fn + "ids / bits / cross / occupancy").c_str()));
     return done(U, W, slices);
+}
+
+int arp_poses_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    return posefp_launch(c, "arp_poses_fingerprints_launch: ", ARP_POSEFP_PLANES, planes, ctype_mask, flags, n_refs, info);
+}
+
+int arp_poses_fingerprints_planes_launch(arp_ctx* c, uint32_t planes29, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    return posefp_launch(c, "arp_poses_fingerprints_planes_launch: ", ARP_POSEFP_ALL_PLANES, planes29, ctype_mask, flags, n_refs, info);
 }
 
 int arp_poses_fingerprints_fetch(arp_ctx* c, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy,

@@ -24,6 +24,8 @@
 //                    8 word columns, lane l = pose l reads one word, and 64 ballots transpose it: lane b keeps the count of bit
 //                    b.  One uint32 atomicAdd per (block, feature) into the zeroed table at the end.
 // The all-pairs matrix is k_sim_gram itself (arp_similarity.h), launched unchanged on this matrix.
+// The ring / amide records of the same poses (arp_poses_planes.h) enter the same matrix as 14 further planes through the three
+// kernels in the middle of this file; the kernels above and below them run unchanged over the wider plane axis.
 // No float exists here; every result is a presence or a count, and an OR / an integer add commute: record order cannot show.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -164,6 +166,149 @@ __global__ __launch_bounds__(256) void k_pfp_bits(PoseFpArgs A) {
                 pfp_set_bit(mine + q * A.wpp, bit);
             }
         }
+    }
+}
+
+// ---- the ring / amide classes as planes: the four tables of the poses-planes result (arp_poses_planes.h), which
+// is resident beside the poses result and sorted by pose as well.  An entity is on the LIGAND side when it is a movable atom
+// (pos_of >= 0), a ring with a movable atom in its path (ring_static == 1) or a moved amide (am_pos >= 0); a ring that a pose
+// merely comes near (ring_static 0 or 2) is the receptor's.  A record takes part when bit ctype of ctype_mask is set, exactly
+// one of its two entities is on the ligand side and its plane is selected; its node is the residue of the receptor entity.
+//   plane 15 + b   atom_plane, bit b of its mask, the ATOM is the ligand's    node: the ring's residue
+//   plane 20 + b   atom_plane, bit b of its mask, the RING is the ligand's    node: res_id[atom]
+//   plane 25       plane_plane (any class)                                    node: the other ring's residue
+//   plane 26       group_group                                                node: am_res of the other amide
+//   plane 27       group_plane, the AMIDE is the ligand's                     node: the ring's residue
+//   plane 28       group_plane, the RING is the ligand's                      node: am_res[amide]
+// The residue of a receptor ring is res_id of the first atom of its path — static, nothing per pose.  It is NOT the posed
+// ring_res ("the nearest atom within 3 A of the centre"): a ligand atom that sits on the ring takes that over, and the feature
+// would name the ligand's own residue.
+//   k_pfp_same_poses   both results keep their uploaded poses: compared as 32-bit words, a mismatch ORs 1 into a flag word
+//   k_pfp_mark_planes  grid (x, 4), a row per table: the sibling of k_pfp_mark, into the same presence bitmap, before k_pfp_scan
+//   k_pfp_bits_planes  a wave per pose walks the pose's slice of each table (its pose_off): the sibling of k_pfp_bits, into
+//                      the same rows, after it.  Kept apart from k_pfp_bits: that kernel stays as 5q measured it, and an
+//                      empty table or a pose without records costs two loads of its offsets here.
+#define POSEFP_ALL_PLANES 29     // ARP_POSEFP_ALL_PLANES
+#define POSEFP_AP_BITS 5         // ARP_AP_CARBONPI ... ARP_AP_METSULPHURPI
+#define POSEFP_PLANE_AP_ATOM 15
+#define POSEFP_PLANE_AP_RING 20
+#define POSEFP_PLANE_PP 25
+#define POSEFP_PLANE_GG 26
+#define POSEFP_PLANE_GP_AMIDE 27
+#define POSEFP_PLANE_GP_RING 28
+
+struct PoseFpTables {
+    const int* first[4];                     // atom, bgn, bgn, amide
+    const int* second[4];                    // ring, end, end, ring
+    const uint8_t* ctype[4];
+    const uint8_t* ap_mask;                  // atom_plane: ARP_AP_* bits
+    const unsigned long long* pose_off;      // [4][P + 1]
+    long long count[4];
+    const int* pos_of;                       // [n]: the poses-planes result's
+    const uint8_t* ring_static;              // [nring]
+    const int* am_pos;                       // [namide]
+    const int* ring_off;
+    const int* ring_idx;
+    const int* am_res;                       // [namide]
+    int n, nring, namide;
+};
+
+__device__ __forceinline__ int pfp_ring_res(const PoseFpArgs& A, const PoseFpTables& T, int r) {
+    const int s = T.ring_off[r];
+    return s < T.ring_off[r + 1] ? A.res_id[T.ring_idx[s]] : -1;
+}
+
+// the selected planes of record r of table t and its node (-1: none); 0 when the record takes no part.  The table is a template
+// parameter: an index into the argument's arrays that is known only at run time would send them to scratch memory
+template <int t>
+__device__ __forceinline__ uint32_t pfp_class_planes(const PoseFpArgs& A, const PoseFpTables& T, long long r, long long* node) {
+    const uint32_t ct = T.ctype[t][r];
+    if (ct >= POSEFP_CTYPES || !((A.ctype_mask >> ct) & 1u)) return 0u;
+    const int a = T.first[t][r], b = T.second[t][r];
+    const int na = t == 0 ? T.n : t == 1 ? T.nring : T.namide, nb = (t == 0 || t == 1 || t == 3) ? T.nring : T.namide;
+    if (a < 0 || a >= na || b < 0 || b >= nb) return 0u;      // (never: the ids are those k_poses_planes wrote)
+    bool la, lb;
+    uint32_t m;
+    if (t == 0) {
+        la = T.pos_of[a] >= 0; lb = T.ring_static[b] == 1;
+        m = ((uint32_t)T.ap_mask[r] & ((1u << POSEFP_AP_BITS) - 1u)) << (la ? POSEFP_PLANE_AP_ATOM : POSEFP_PLANE_AP_RING);
+    } else if (t == 1) {
+        la = T.ring_static[a] == 1; lb = T.ring_static[b] == 1;
+        m = 1u << POSEFP_PLANE_PP;
+    } else if (t == 2) {
+        la = T.am_pos[a] >= 0; lb = T.am_pos[b] >= 0;
+        m = 1u << POSEFP_PLANE_GG;
+    } else {
+        la = T.am_pos[a] >= 0; lb = T.ring_static[b] == 1;
+        m = 1u << (la ? POSEFP_PLANE_GP_AMIDE : POSEFP_PLANE_GP_RING);
+    }
+    m &= A.planes;
+    if (la == lb || !m) return 0u;
+    int res;
+    if (t == 0) res = la ? pfp_ring_res(A, T, b) : A.res_id[a];
+    else if (t == 1) res = pfp_ring_res(A, T, la ? b : a);
+    else if (t == 2) res = T.am_res[la ? b : a];
+    else res = la ? pfp_ring_res(A, T, b) : T.am_res[a];
+    *node = (res >= 0 && (long long)res < A.N) ? (long long)res : -1;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void k_pfp_same_poses(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, long long words,
+                                                        uint32_t* __restrict__ flag) {
+    uint32_t differ = 0;
+    for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (long long)gridDim.x * blockDim.x) differ |= a[w] ^ b[w];
+    if (differ) atomicOr(flag, 1u);
+}
+
+template <int t>
+__device__ __forceinline__ void pfp_mark_table(const PoseFpArgs& A, const PoseFpTables& T) {
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < T.count[t]; r += (long long)gridDim.x * blockDim.x) {
+        long long node = -1;
+        if (!pfp_class_planes<t>(A, T, r, &node) || node < 0) continue;
+        pfp_set_bit(A.presence + (node >> 6), 1ull << (node & 63));
+    }
+}
+// grid (x, 4): row y marks table y
+__global__ __launch_bounds__(256) void k_pfp_mark_planes(PoseFpArgs A, PoseFpTables T) {
+    switch (blockIdx.y) {
+        case 0: pfp_mark_table<0>(A, T); break;
+        case 1: pfp_mark_table<1>(A, T); break;
+        case 2: pfp_mark_table<2>(A, T); break;
+        default: pfp_mark_table<3>(A, T); break;
+    }
+}
+
+// the slice of table t that belongs to pose p, 64 records a step, into the pose's row
+template <int t>
+__device__ __forceinline__ void pfp_bits_table(const PoseFpArgs& A, const PoseFpTables& T, long long p, int lane, unsigned long long* row) {
+    if (T.count[t] == 0) return;
+    const unsigned long long* const off = T.pose_off + (long long)t * ((long long)A.P + 1) + p;
+    const long long s = (long long)off[0], e = min((long long)off[1], T.count[t]);
+    for (long long r = s + lane; r < e; r += 64) {
+        long long node = -1;
+        uint32_t m = pfp_class_planes<t>(A, T, r, &node);
+        if (!m || node < 0) continue;
+        const long long col = (long long)A.base[node >> 6] + __popcll(A.presence[node >> 6] & ((1ull << (node & 63)) - 1ull));
+        if (col >= A.U) continue;      // (never: k_pfp_mark_planes set this node's bit)
+        const unsigned long long bit = 1ull << (col & 63);
+        unsigned long long* const mine = row + (col >> 6);
+        while (m) {
+            const int b = __ffs((int)m) - 1;
+            m &= m - 1u;
+            const long long q = (long long)__popc(A.planes & ((1u << b) - 1u));
+            pfp_set_bit(mine + q * A.wpp, bit);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_pfp_bits_planes(PoseFpArgs A, PoseFpTables T) {
+    const int lane = threadIdx.x & 63;
+    const long long waves = (long long)gridDim.x * (blockDim.x >> 6);
+    for (long long p = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < A.P; p += waves) {
+        unsigned long long* const row = A.bits + p * A.W;
+        pfp_bits_table<0>(A, T, p, lane, row);
+        pfp_bits_table<1>(A, T, p, lane, row);
+        pfp_bits_table<2>(A, T, p, lane, row);
+        pfp_bits_table<3>(A, T, p, lane, row);
     }
 }
 

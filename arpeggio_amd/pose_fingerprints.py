@@ -27,19 +27,43 @@ from . import similarity
 from .core import config
 
 N_PLANES = 15          # ARP_POSEFP_PLANES
+N_ALL_PLANES = 29      # ARP_POSEFP_ALL_PLANES
 MAX_REFS = 64          # ARP_POSEFP_MAX_REFS
 LEVELS = ('residue', 'atom')
+# The ring and amide classes as planes 15 ... 28 (residue level only).  A record takes part when exactly one of its two entities
+# is the ligand's; the name says which side the ligand supplies where the table has two kinds of entity, the node is the
+# residue of the other.
+CLASS_PLANE_NAMES = tuple([f'{n}_LIGAND_ATOM' for n in config.ATOM_PLANE_NAMES] + [f'{n}_LIGAND_RING' for n in config.ATOM_PLANE_NAMES] +
+                          ['PLANE_PLANE', 'GROUP_GROUP', 'GROUP_PLANE_LIGAND_AMIDE', 'GROUP_PLANE_LIGAND_RING'])
+CLASS_SHORTHANDS = {'atom_plane': CLASS_PLANE_NAMES[:10], 'plane_plane': CLASS_PLANE_NAMES[10:11], 'group_group': CLASS_PLANE_NAMES[11:12],
+                    'group_plane': CLASS_PLANE_NAMES[12:], 'all': CLASS_PLANE_NAMES}
+assert len(CLASS_PLANE_NAMES) == N_ALL_PLANES - N_PLANES
 
 
-def planes(contacts=None):
+def planes(contacts=None, classes=()):
     """The ``planes`` mask of the contacts named in ``contacts`` (``similarity.planes`` without class planes: ``None`` means
-    every contact but bare proximity)."""
-    return similarity.planes(contacts)
+    every contact but bare proximity) and of the ring / amide classes named in ``classes``: names of ``CLASS_PLANE_NAMES``, the
+    shorthands 'atom_plane', 'plane_plane', 'group_group', 'group_plane' (every plane of that table) or 'all' (all 14); a
+    single name may be given as a string.  ``contacts=[]`` with classes gives the class planes alone; a mask without any plane
+    raises ``ValueError``."""
+    chosen = tuple((classes,) if isinstance(classes, str) else classes)
+    mask = 0 if (chosen and contacts is not None and len(contacts) == 0) else similarity.planes(contacts)
+    for name in chosen:
+        if name in CLASS_SHORTHANDS:
+            members = CLASS_SHORTHANDS[name]
+        elif name in CLASS_PLANE_NAMES:
+            members = (name,)
+        else:
+            raise ValueError(f'planes: no class plane {name!r} (CLASS_PLANE_NAMES, or a table, or all)')
+        for m in members:
+            mask |= 1 << (N_PLANES + CLASS_PLANE_NAMES.index(m))
+    return mask
 
 
 def plane_names(mask):
     """The names of the selected planes, in the order of the plane axis."""
-    return [config.SIFT_NAMES[k] for k in range(N_PLANES) if (int(mask) >> k) & 1]
+    return [config.SIFT_NAMES[k] for k in range(N_PLANES) if (int(mask) >> k) & 1] + \
+           [CLASS_PLANE_NAMES[k - N_PLANES] for k in range(N_PLANES, N_ALL_PLANES) if (int(mask) >> k) & 1]
 
 
 def reference_counts(result):

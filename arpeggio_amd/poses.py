@@ -348,6 +348,66 @@ def concat_planes(chunks):
     return out
 
 
+CLASS_PLANE = 15          # the first class plane of a pose fingerprint (pose_fingerprints.CLASS_PLANE_NAMES, ARP_POSEFP_PLANES)
+
+
+def ligand_side(pc, idx):
+    """Which entities are the ligand's for movable set ``idx``: ``(atoms bool [n], rings bool [n_rings], amides bool [n_amides])``
+    — a movable atom, a ring with a movable atom in its path, an amide whose N, C or O is movable.  A ring a pose merely comes
+    near stays the receptor's."""
+    m = _mask(pc, idx)
+    rings = np.array([bool(m[np.asarray(a, np.int64)].any()) for a in pc.ring_atoms], bool).reshape(-1)
+    am = np.asarray(pc.amide_atoms, np.int64).reshape(-1, 4)
+    amides = m[am[:, :3]].any(axis=1) if len(am) else np.zeros(0, bool)
+    return m, rings, amides
+
+
+def ring_home_residue(pc):
+    """int64 [n_rings]: the residue of the first atom of every ring's path — the node of a receptor ring in a pose
+    fingerprint.  Not ``ring_res``: that is the nearest atom within 3 A of the centre, which a ligand atom on the ring takes over."""
+    return np.array([int(pc.res_id[int(a[0])]) if len(a) else -1 for a in pc.ring_atoms], np.int64).reshape(-1)
+
+
+def plane_fingerprints(planes_table, pc, idx, ctype_mask=0x7F):
+    """The host route to the class planes of the pose fingerprints, over a fetched ``Context.poses_planes`` table: per pose the
+    set of ``(node, plane)`` — plane 15 ... 28 as ``pose_fingerprints.CLASS_PLANE_NAMES`` numbers them, node the residue of the
+    receptor entity — of the records whose ``ctype`` bit is in ``ctype_mask`` and of whose two entities exactly one is the
+    ligand's (``ligand_side``).  A node outside [0, n_residues) is skipped.  Returns a list of P sets."""
+    atoms, rings, amides = ligand_side(pc, idx)
+    ring_res = ring_home_residue(pc)
+    res_id = np.asarray(pc.res_id, np.int64)
+    am_res = np.asarray(pc.amide_res, np.int64).reshape(-1)
+    P = len(planes_table['summary'])
+    out = [set() for _ in range(P)]
+
+    def add(name, keep, node, plane):
+        off = np.asarray(planes_table[name]['pose_off']).astype(np.int64)
+        pose = np.repeat(np.arange(P), np.diff(off))
+        ct = np.asarray(planes_table[name]['ctype']).astype(np.int64)
+        keep = keep & (((int(ctype_mask) >> ct) & 1) != 0) & (node >= 0) & (node < pc.n_residues)
+        for p, u, q in zip(pose[keep].tolist(), node[keep].tolist(), np.broadcast_to(plane, keep.shape)[keep].tolist()):
+            out[p].add((u, q))
+
+    b = planes_table['atom_plane']
+    a, r, mask = np.asarray(b['atom'], np.int64), np.asarray(b['ring'], np.int64), np.asarray(b['mask'], np.int64)
+    for bit in range(5 if len(a) else 0):
+        add('atom_plane', (atoms[a] != rings[r]) & (((mask >> bit) & 1) != 0), np.where(atoms[a], ring_res[r], res_id[a]),
+            np.where(atoms[a], CLASS_PLANE + bit, CLASS_PLANE + 5 + bit))
+    b = planes_table['plane_plane']
+    r1, r2 = np.asarray(b['bgn'], np.int64), np.asarray(b['end'], np.int64)
+    if len(r1):
+        add('plane_plane', rings[r1] != rings[r2], np.where(rings[r1], ring_res[r2], ring_res[r1]), CLASS_PLANE + 10)
+    b = planes_table['group_group']
+    a1, a2 = np.asarray(b['bgn'], np.int64), np.asarray(b['end'], np.int64)
+    if len(a1):
+        add('group_group', amides[a1] != amides[a2], np.where(amides[a1], am_res[a2], am_res[a1]), CLASS_PLANE + 11)
+    b = planes_table['group_plane']
+    a, r = np.asarray(b['amide'], np.int64), np.asarray(b['ring'], np.int64)
+    if len(a):
+        add('group_plane', amides[a] != rings[r], np.where(amides[a], ring_res[r], am_res[a]), np.where(amides[a], CLASS_PLANE + 12, CLASS_PLANE + 13))
+    return out
+
+
 def planes_to_records(table, pc, component_types=None):
     """The records as the dicts ``get_contacts`` returns for the four bags (export.py), each with its 'pose'.  Rings and amides
     are labelled by their resident residue."""

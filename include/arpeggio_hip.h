@@ -1118,8 +1118,8 @@ int arp_poses_planes_info(arp_ctx* ctx, int64_t info[12]);
  *   inter      uint32 [P][P]                   only with ARP_POSEFP_ALL_PAIRS (P <= ARP_SIM_MAX_MODELS): features present in pose
  *                                              f and in pose g; the diagonal is count
  * Everything is a presence or a count: no float exists on the device and the order of the records cannot show in a result.
- * The ring and amide records of the poses (arp_poses_planes_launch) take no part: mapping them to receptor residues needs the
- * ring residues that launch rebuilds per pose — the follow-up.
+ * The ring and amide records of the poses (arp_poses_planes_launch) take no part in this entry: they are the class planes of
+ * arp_poses_fingerprints_planes_launch, below.
  *
  * arp_poses_fingerprints_launch: info[8] as arp_poses_fingerprints_info gives it.  One host wait (U, which sizes the matrix);
  *   every launch and copy goes on the context's stream.  A second launch with the same arguments on the same poses result
@@ -1137,12 +1137,43 @@ int arp_poses_planes_info(arp_ctx* ctx, int64_t info[12]);
  *
  * arp_poses_fingerprints_info: info[0] = P, [1] = n_refs, [2] = U, [3] = NP, [4] = words per pose W = NP * ceil(U / 64),
  *   [5] = word slices of the cross product (> 1: integer atomic adds into zeroed arrays), [6] = launches that did work,
- *   [7] = flags.  [0] ... [5] and [7] are 0 while there is no result. */
+ *   [7] = flags.  [0] ... [5] and [7] are 0 while there is no result.
+ *
+ * THE RING AND AMIDE CLASSES AS PLANES (arp_poses_fingerprints_planes_launch).  planes29 is a mask over
+ * ARP_POSEFP_ALL_PLANES = 29 planes: the 15 SIFt bits and, behind them, 14 class planes fed by the four tables of the resident
+ * poses-planes result (arp_poses_planes_launch).  An entity is on the LIGAND side when it is an atom of the movable set, a ring
+ * with a movable atom in its path, or an amide whose N, C or O is movable; everything else — a receptor ring that a pose merely
+ * comes near included — is on the receptor side.  A ring / amide record participates when bit ctype of ctype_mask is set,
+ * EXACTLY ONE of its two entities is on the ligand side, and its plane is in the mask:
+ *   plane 15 + b  atom_plane, bit b of mask (ARP_AP_*), the atom is the ligand's    node: the ring's residue
+ *   plane 20 + b  atom_plane, bit b of mask, the ring is the ligand's               node: res_id[atom]
+ *   plane 25      plane_plane (any class), one ring is the ligand's                 node: the other ring's residue
+ *   plane 26      group_group, one amide is the ligand's                            node: am_res of the other amide
+ *   plane 27      group_plane, the amide is the ligand's                            node: the ring's residue
+ *   plane 28      group_plane, the ring is the ligand's                             node: am_res[amide]
+ * THE RESIDUE OF A RECEPTOR RING is res_id of the first atom of its path (arp_set_plane_atoms): static, nothing per pose.  It
+ * is deliberately not the posed ring_res — "the nearest atom within 3 A of the centre", which a ligand atom sitting on the
+ * ring takes over, so that the feature would name the ligand's own residue (arp_residue_contacts keeps using ring_res).  A
+ * node outside [0, nres) is skipped.  Class planes exist at residue level only.  ids[U] are the distinct nodes of all
+ * participating records, atom-atom and ring / amide together; the plane axis is the set bits of planes29, ascending; count,
+ * cross, occupancy, bits and inter mean what they mean above, over the widened feature set.
+ *   Without a bit from 15 on, the entry is arp_poses_fingerprints_launch.  With one: both a poses result and a poses-planes
+ *   result must be resident, with equal P and S and made from the same pose coordinates — both keep their uploaded poses, which
+ *   are compared on the device as 32-bit words, the outcome read in the one wait for U.  ARP_E_ARG, cause named, resident
+ *   results untouched: "no poses-planes result"; "differ in P or S"; "made from different poses" (no fingerprint result is
+ *   left); class planes without ARP_POSEFP_BY_RESIDUE; planes29 0 or with bits beyond bit 28; the refusals above.
+ *   ARP_E_CAPACITY as above.  The result is the one arp_poses_fingerprints_fetch / _info serve (info[3] = NP counts the class
+ *   planes); a launch of either entry with other arguments remakes it.  One made with class planes is void when either source
+ *   is: arp_poses_planes_launch and arp_set_plane_atoms void it too; one made without is not touched by those.  Making it
+ *   voids nothing; everything goes on the context's stream. */
 #define ARP_POSEFP_PLANES 15
+#define ARP_POSEFP_ALL_PLANES 29
 #define ARP_POSEFP_MAX_REFS 64
 #define ARP_POSEFP_BY_RESIDUE 1u
 #define ARP_POSEFP_ALL_PAIRS 2u
 int arp_poses_fingerprints_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, int64_t info[8]);
+int arp_poses_fingerprints_planes_launch(arp_ctx* ctx, uint32_t planes29, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
+                                         int64_t info[8]);
 int arp_poses_fingerprints_fetch(arp_ctx* ctx, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy,
                                  uint64_t* bits, uint32_t* inter, int64_t* n_nodes);
 int arp_poses_fingerprints_info(arp_ctx* ctx, int64_t info[8]);
