@@ -52,6 +52,7 @@ SYMBOLS = (
     'arp_set_plane_atoms', 'arp_poses_planes_launch', 'arp_poses_planes_fetch', 'arp_poses_planes_info',
     'arp_poses_fingerprints_launch', 'arp_poses_fingerprints_fetch', 'arp_poses_fingerprints_info',
     'arp_poses_fingerprints_planes_launch',
+    'arp_poses_shortlist_launch', 'arp_poses_shortlist_fetch', 'arp_poses_shortlist_planes_fetch', 'arp_poses_shortlist_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -63,6 +64,9 @@ POSES_PLANES_SUMMARY, POSES_PLANES_MAX_RINGS, POSES_PLANES_MAX_HOME, POSES_PLANE
 # ... their fingerprints (ARP_POSEFP_*)
 POSEFP_PLANES, POSEFP_MAX_REFS, POSEFP_BY_RESIDUE, POSEFP_ALL_PAIRS = 15, 64, 1, 2
 POSEFP_ALL_PLANES = 29           # ARP_POSEFP_ALL_PLANES: the SIFt bits and the 14 ring / amide class planes behind them
+# ... their shortlist (ARP_SHORTLIST_*)
+SHORTLIST_LIST, SHORTLIST_SUMMARY, SHORTLIST_TANIMOTO, SHORTLIST_TABLES, SHORTLIST_MAX_WEIGHT = 0, 1, 2, 5, 1 << 24
+INT64_MIN = -(1 << 63)
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -249,6 +253,10 @@ def load():
     L.arp_poses_fingerprints_planes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp]
     L.arp_poses_fingerprints_fetch.argtypes = [vp, i64] + [vp] * 6 + [C.POINTER(i64)]
     L.arp_poses_fingerprints_info.argtypes = [vp, vp]
+    L.arp_poses_shortlist_launch.argtypes = [vp, C.c_int, vp, i64, vp, i64, i64, i64, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.arp_poses_shortlist_fetch.argtypes = [vp, i64, i64] + [vp] * 10 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_poses_shortlist_planes_fetch.argtypes = [vp, C.c_int, i64, i64] + [vp] * 10 + [C.POINTER(i64)]
+    L.arp_poses_shortlist_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1075,6 +1083,81 @@ class Context:
         info = np.zeros(8, np.int64)
         self._check(self._L.arp_poses_fingerprints_info(self._h, _p(info)), 'arp_poses_fingerprints_info')
         return dict(zip(('poses', 'n_refs', 'nodes', 'planes', 'words', 'slices', 'launches', 'flags'), (int(v) for v in info)))
+
+    def poses_shortlist(self, kind, *, weights=None, ref=0, pose_ids=None, skip=0, k=None, min_score=None, tables=('atom_atom',),
+                        sift_mask=0, ctype_mask=CTYPE_ALL):
+        """The poses of the resident poses result (``poses_contacts`` / ``poses_summary``) ranked on the device and the chosen
+        poses' records fetched, no other record copied (arp_poses_shortlist_*; ``arpeggio_amd.pose_shortlist``).  ``kind``:
+        'summary' — score = ``weights`` (int32 [32], ``pose_shortlist.weights``) times the summary slots of the poses result
+        and, second half, of the resident ``poses_planes`` result of the same poses; 'tanimoto' — the Tanimoto similarity (32
+        fractional bits) to reference ``ref`` of the resident ``poses_fingerprints`` result, ``ref=-1`` the best over its
+        references; 'list' — the poses ``pose_ids`` in that order.  Ranked are the poses from ``skip`` on, in descending score,
+        ties by ascending pose id; chosen are the first ``k`` (default: all) with a score of at least ``min_score``.
+        ``tables`` names what is fetched (``pose_shortlist.TABLES``); ``sift_mask`` / ``ctype_mask`` filter the records as
+        ``contacts_filtered`` does (ring and amide records by ``ctype_mask``).  Returns a dict: ``pose`` int32 [K], ``score``
+        int64 [K], ``summary`` uint32 [K, 16] (unfiltered), ``planes_summary`` when the planes result was read, ``movable``;
+        for 'atom_atom' the five columns and ``pose_off`` — a ``poses`` table of K poses; per ring / amide table a dict
+        shaped as ``poses_planes`` gives it."""
+        from . import pose_shortlist as _sl, poses as _poses
+        if kind not in _sl.KINDS:
+            raise ValueError(f'poses_shortlist: kind must be one of {_sl.KINDS}')
+        mask = _sl.tables_mask(tables)
+        code = _sl.KINDS.index(kind)
+        w = None if weights is None else np.ascontiguousarray(weights, np.int32).reshape(-1)
+        if w is not None and len(w) != 32:
+            raise ValueError('poses_shortlist: weights must be int32 [32] (pose_shortlist.weights)')
+        ids = None if pose_ids is None else np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
+        if code == SHORTLIST_LIST:
+            kk, ms = (0 if k is None else int(k)), (INT64_MIN if min_score is None else int(min_score))
+        else:
+            kk, ms = (POSES_MAX_POSES if k is None else int(k)), (INT64_MIN if min_score is None else int(min_score))
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_shortlist_launch(self._h, code, _p(w), int(ref), _p(ids), 0 if ids is None else len(ids), int(skip), kk, ms,
+                                                       mask, int(sift_mask), int(ctype_mask), _p(info)), 'arp_poses_shortlist_launch')
+        K = int(info[0])
+        planes_read = (mask >> 1) != 0 or (code == SHORTLIST_SUMMARY and w is not None and bool(np.any(w[16:])))
+        out = dict(pose=np.empty(K, np.int32), score=np.empty(K, np.int64), summary=np.empty((K, POSES_SUMMARY), np.uint32))
+        if planes_read:
+            out['planes_summary'] = np.empty((K, POSES_PLANES_SUMMARY), np.uint32)
+        n, m = C.c_int64(0), C.c_int64(0)
+        if mask & 1:
+            kept = int(info[1])
+            out.update(i=np.empty(kept, np.int32), j=np.empty(kept, np.int32), dist=np.empty(kept, np.float32), sift=np.empty(kept, np.uint16),
+                       ctype=np.empty(kept, np.uint8), pose_off=np.empty(K + 1, np.uint64))
+        else:
+            kept = 0
+        self._check(self._L.arp_poses_shortlist_fetch(self._h, K, kept, _p(out['pose']), _p(out['score']), _p(out['summary']),
+                                                      _p(out.get('planes_summary')), _p(out.get('pose_off')), _p(out.get('i')), _p(out.get('j')),
+                                                      _p(out.get('dist')), _p(out.get('sift')), _p(out.get('ctype')), C.byref(n), C.byref(m)),
+                    'arp_poses_shortlist_fetch')
+        for t, name in enumerate(_poses.PLANE_TABLES):
+            if not (mask >> (t + 1)) & 1:
+                continue
+            kept = int(info[2 + t])
+            idc, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
+            tab = {c: np.empty(kept, np.int32) for c in idc}
+            tab.update({c: np.empty(kept, vdt) for c in vals})
+            tab.update({c: np.empty(kept, np.uint8) for c in byts})
+            tab['pose_off'] = np.empty(K + 1, np.uint64)
+            args = [_p(tab[c]) for c in idc] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
+            self._check(self._L.arp_poses_shortlist_planes_fetch(self._h, t, K, kept, _p(tab['pose_off']), *args, C.byref(m)),
+                        'arp_poses_shortlist_planes_fetch')
+            out[name] = tab
+        sel = getattr(self, '_sel', None)
+        out['movable'] = np.nonzero(sel)[0].astype(np.int32) if sel is not None else np.zeros(0, np.int32)
+        out['kind'] = kind
+        return out
+
+    def poses_shortlist_info(self):
+        """arp_poses_shortlist_info: the chosen poses and the kept records per table of the resident shortlist (zeros while there
+        is none), the launches that did work so far, and the kind."""
+        from . import pose_shortlist as _sl
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_shortlist_info(self._h, _p(info)), 'arp_poses_shortlist_info')
+        d = dict(chosen=int(info[0]))
+        d.update({name: int(info[1 + t]) for t, name in enumerate(_sl.TABLES)})
+        d.update(launches=int(info[6]), kind=int(info[7]))
+        return d
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

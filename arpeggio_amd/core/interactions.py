@@ -542,6 +542,96 @@ class InteractionComplex:
             raise AttributeError('no pose fingerprints yet: call run_pose_fingerprints() first')
         return _fp.write_pose_fingerprints(wd, self.id, self.pose_fingerprints, self.pc, self.component_types)
 
+    def run_pose_shortlist(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent, k, by='summary',
+                           weights=None, refs_xyz=None, refs_h_xyz=None, contacts=None, interacting_entities=None, min_score=None,
+                           planes=False, chunk=None):
+        """Extension beside the mirror: the best ``k`` of many poses of a ligand, ranked ON THE DEVICE, with their records — no
+        other pose's record is copied.  Selection, ``xyz``, ``h_xyz`` and the three parameters are those of ``run_poses``.
+        ``by='summary'``: the score is ``weights`` (``pose_shortlist.weights``; default: one per record) times the summary
+        slots; ``by='tanimoto'``: the Tanimoto similarity of the pose's fingerprint (``contacts`` as
+        ``pose_fingerprints.planes`` reads it, residue level) to the reference poses ``refs_xyz`` / ``refs_h_xyz`` (default: the
+        resident coordinates), the best over the references, in 32 fractional bits.  Higher is better, a tie goes to the lower
+        pose id; ``min_score`` drops poses below it.  ``contacts`` / ``interacting_entities`` also name the records that are
+        fetched (``contact_filter.masks``; ``None`` = all).  ``planes=True``: the ring and amide tables of the chosen poses as
+        well, and the planes half of ``weights`` (the pack needs ``ring_atoms`` and ``amide_atoms``).  Every chunk of ``chunk``
+        poses (default: all at once) is launched as ``Context.poses_summary`` (``poses_planes_summary``,
+        ``poses_fingerprints`` with the references in front) and ``Context.poses_shortlist(k)``; the chunks' shortlists are
+        merged on the host (``pose_shortlist.merge``).  Returns the shortlist ``arpeggio_amd.pose_shortlist`` describes, ``pose``
+        in the caller's numbering (also kept in ``self.pose_shortlist``)."""
+        from .. import _capi, contact_filter, poses as _poses, pose_fingerprints as _fp, pose_shortlist as _sl
+        if by not in ('summary', 'tanimoto'):
+            raise ValueError(f"run_pose_shortlist: by must be 'summary' or 'tanimoto', not {by!r}")
+        if int(k) < 1:
+            raise ValueError('run_pose_shortlist: k must be at least 1')
+        sift_mask = 0 if contacts is None else contact_filter.masks(contacts, None)[0]
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx = self.pc, self._ctx
+        if isinstance(user_selections, np.ndarray):
+            idx = np.unique(user_selections.astype(np.int64))
+        else:
+            idx = utils.selection_parser(user_selections, pc) if user_selections else np.zeros(0, np.int64)
+        if idx.size == 0:
+            raise AttributeError('Selection must not be empty.')
+        sel = np.zeros(pc.n_atoms, np.uint8)
+        sel[idx] = 1
+        atoms, rows = _poses.movable(pc, idx)
+        x = np.ascontiguousarray(xyz, np.float32)
+        h = np.zeros((len(x), 0, 3)) if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64)
+        if len(x) < 1:
+            raise ValueError('run_pose_shortlist: no pose given')
+        Q = 0
+        if by == 'tanimoto':
+            if refs_xyz is None:
+                rx = np.asarray(pc.xyz, np.float32)[atoms][None]
+                rh = np.asarray(pc.h_xyz, np.float64).reshape(-1, 3)[rows][None]
+            else:
+                rx = np.ascontiguousarray(refs_xyz, np.float32)
+                rh = np.zeros((len(rx), 0, 3)) if refs_h_xyz is None else np.ascontiguousarray(refs_h_xyz, np.float64)
+            Q = len(rx)
+            if not 1 <= Q <= _fp.MAX_REFS:
+                raise ValueError(f'run_pose_shortlist: 1 ... {_fp.MAX_REFS} reference poses')
+            if x.shape[1:] != rx.shape[1:] or h.shape[1:] != rh.shape[1:]:
+                raise ValueError('run_pose_shortlist: the references and the poses must have the same atoms and hydrogen rows')
+            fp_planes = _fp.planes(contacts)
+        elif weights is None:
+            weights = _sl.weights(atom_atom={'records': 1})
+        step = int(chunk) if chunk else min(len(x), _capi.POSES_MAX_POSES - Q)
+        if step < 1:
+            raise ValueError('run_pose_shortlist: chunk must be at least 1')
+        tables = _sl.TABLES if planes else ('atom_atom',)
+        ctx.set_selection(sel)
+        if planes:
+            ctx.set_plane_atoms(pc)
+        parts = []
+        for a in range(0, len(x), step):
+            cx, ch = x[a:a + step], h[a:a + step]
+            if Q:
+                cx, ch = np.concatenate([rx, cx]), np.concatenate([rh, ch])
+            ctx.poses_summary(cx, ch, interacting_cutoff, vdw_comp, include_sequence_adjacent)
+            if planes:
+                ctx.poses_planes_summary(cx)
+            if by == 'tanimoto':
+                ctx.poses_fingerprints(fp_planes, ctype_mask, by_residue=True, n_refs=Q)
+                part = ctx.poses_shortlist('tanimoto', ref=-1, skip=Q, k=int(k), min_score=min_score, tables=tables, sift_mask=sift_mask,
+                                           ctype_mask=ctype_mask)
+            else:
+                part = ctx.poses_shortlist('summary', weights=weights, k=int(k), min_score=min_score, tables=tables, sift_mask=sift_mask,
+                                           ctype_mask=ctype_mask)
+            parts.append(_sl.shift(part, a - Q))
+        out = _sl.merge(parts, int(k))
+        out.update(by=by, n_refs=Q)
+        self.pose_shortlist = out
+        return out
+
+    def write_pose_shortlist(self, wd):
+        """'<id>.shortlist': the atom-atom records of the last ``run_pose_shortlist`` as CSV (``pose_shortlist.write_csv``)."""
+        from .. import pose_shortlist as _sl
+        if getattr(self, 'pose_shortlist', None) is None:
+            raise AttributeError('no pose shortlist yet: call run_pose_shortlist() first')
+        return _sl.write_pose_shortlist(wd, self.id, self.pose_shortlist, self.pc, self.component_types)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""

@@ -41,6 +41,7 @@
 #include "arp_poses.h"
 #include "arp_poses_planes.h"
 #include "arp_poses_fingerprints.h"
+#include "arp_poses_shortlist.h"
 #include "arp_blob.h"
 
 namespace {
@@ -329,6 +330,29 @@ struct PoseFpResult {
     }
 };
 
+// the shortlist of the resident poses result (arp_poses_shortlist_launch, arp_poses_shortlist.h): a sort scratch of its own (the
+// source's sorted buffers are not disturbed), the chosen poses with their scores and summary rows, lengths and offsets per table,
+// the word block of the one wait, and the chosen poses' records in one slab.  Valid only while the poses result is; one that
+// read the poses-planes result (`planes`) goes with that as well
+struct ShortlistResult {
+    SortScratch sort;
+    DevBuf<int> ids, pose;
+    DevBuf<long long> score;
+    DevBuf<uint32_t> summary, pl_summary;
+    DevBuf<unsigned long long> len, off, words;
+    DevBuf<uint8_t> slab;
+    size_t aa_off[5] = {0, 0, 0, 0, 0};
+    PplColumns col{};
+    int64_t K = 0, ncand = 0, total[PSL_TABLES] = {0, 0, 0, 0, 0}, launches = 0;
+    int kind = 0;
+    uint32_t tables = 0;
+    bool valid = false, planes = false;
+    void release() {
+        sort.release(); ids.release(); pose.release(); score.release(); summary.release(); pl_summary.release(); len.release(); off.release();
+        words.release(); slab.release(); valid = false;
+    }
+};
+
 // the ring / amide contacts of ligand poses (arp_poses_planes_launch, arp_poses_planes.h): the atoms of the resident rings and
 // amides (arp_set_plane_atoms), the movable set's tables (made once per structure, selection and plane atoms), an all-atom 6 A
 // grid of its own by local id (the static order of the passes is left alone), the per-block lists, the records and their sort
@@ -602,6 +626,7 @@ struct arp_ctx {
     PosesPlanesResult pplanes;            // arp_poses_planes_launch: likewise; its plane atoms go with the structure, rings or amides
     PosesResult poses;                    // arp_poses_contacts_launch: reads no bag, voided with the inputs (inputs_changed)
     PoseFpResult posefp;                  // arp_poses_fingerprints_launch: reads the poses result alone, voided with it
+    ShortlistResult shortlist;            // arp_poses_shortlist_launch: likewise; with the poses-planes result when it read that
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -889,6 +914,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
         c->poses.valid = false;      // (made from the inputs alone, the selection among them: no row in void_results)
         c->posefp.valid = false;     // (made from the poses result alone)
+        c->shortlist.valid = false;  // (likewise)
         c->pplanes.valid = c->pplanes.setup = false;
     }
     if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->pplanes.have_atoms = false;
@@ -2427,6 +2453,7 @@ void arp_destroy(arp_ctx* c) {
     c->poses.sel_h.release(); c->poses.pos_of.release(); c->poses.xyz.release(); c->poses.hx.release(); c->poses.ctr.release();
     c->pplanes.release();
     c->posefp.release();
+    c->shortlist.release();
     c->poses.summary.release(); c->poses.pose_off.release(); c->poses.sort.release(); c->poses.slab.release(); c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -5353,6 +5380,7 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     // ---- from here on the previous result is gone, and the fingerprints made from it
     R.valid = false;
     c->posefp.valid = false;
+    c->shortlist.valid = false;
     R.count = 0;
     HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
     HIPCHK(c, R.hx.reserve(std::max<size_t>((size_t)P * (size_t)SH * 3, 1)));
@@ -5467,6 +5495,7 @@ int arp_set_plane_atoms(arp_ctx* c, const int32_t* ring_off, const int32_t* ring
     PosesPlanesResult& R = c->pplanes;
     R.valid = R.setup = R.have_atoms = false;
     if (c->posefp.classes) c->posefp.valid = false;
+    if (c->shortlist.planes) c->shortlist.valid = false;
     const int32_t zero = 0;
     const size_t nidx = c->nring > 0 ? (size_t)ring_off[c->nring] : 0;
     CHK(upload(c, R.ring_off, c->nring > 0 ? ring_off : &zero, (size_t)c->nring + 1));
@@ -5554,6 +5583,7 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     // ---- from here on the previous result is gone, and the fingerprints made with its class planes
     R.valid = false;
     if (c->posefp.classes) c->posefp.valid = false;
+    if (c->shortlist.planes) c->shortlist.valid = false;
     for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
     const int blocks = (int)std::min<int64_t>(P, PPL_MAX_BLOCKS);
     const int ws_rings = R.n_mring + R.n_hring + PPL_MAX_NEAR;
@@ -5915,6 +5945,267 @@ int arp_poses_fingerprints_fetch(arp_ctx* c, int64_t cap_nodes, int32_t* ids, ui
 int arp_poses_fingerprints_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     posefp_info(c->posefp, info);
+    return ARP_OK;
+}
+
+// ---- pose shortlist (arp_poses_shortlist.h): the resident poses result -> ranked poses -> the chosen ones' records
+// The poses result, and depending on the arguments the poses-planes result and the fingerprint result, are read; only this
+// result's own buffers are written (its sort scratch included: PosesResult::sort keeps the source's sorted buffers).  One wait:
+// K, the five totals, the same-poses flag and the device's error word, which size the columns the gather then fills.
+static_assert(PSL_LIST == ARP_SHORTLIST_LIST && PSL_SUMMARY == ARP_SHORTLIST_SUMMARY && PSL_TANIMOTO == ARP_SHORTLIST_TANIMOTO &&
+              PSL_TABLES == ARP_SHORTLIST_TABLES && PSL_SLOTS == POSES_SUMMARY && PSL_SLOTS == PPL_SUMMARY &&
+              PSL_MAX_WEIGHT == ARP_SHORTLIST_MAX_WEIGHT && PSL_CTYPES_ALL == ARP_FILTER_CTYPE_ALL, "arp_poses_shortlist.h names the header's constants");
+
+static void shortlist_info(const ShortlistResult& S, int64_t info[8]) {
+    const int64_t v[8] = {S.K, S.total[0], S.total[1], S.total[2], S.total[3], S.total[4], S.launches, (int64_t)S.kind};
+    for (int q = 0; q < 8; ++q) info[q] = (S.valid || q == 6) ? v[q] : 0;
+}
+
+int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, int64_t ref, const int32_t* pose_ids, int64_t n_ids, int64_t skip,
+                               int64_t k, int64_t min_score, uint32_t tables, uint32_t sift_mask, uint32_t ctype_mask, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_poses_shortlist_launch: ";
+    ShortlistResult& S = c->shortlist;
+    const PosesResult& R = c->poses;
+    const PosesPlanesResult& L = c->pplanes;
+    const PoseFpResult& F = c->posefp;
+    // ---- the refusals: none of them touches a resident result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
+    if (kind != ARP_SHORTLIST_LIST && kind != ARP_SHORTLIST_SUMMARY && kind != ARP_SHORTLIST_TANIMOTO)
+        FAIL(c, ARP_E_ARG, fn + "unknown kind (ARP_SHORTLIST_LIST, ARP_SHORTLIST_SUMMARY or ARP_SHORTLIST_TANIMOTO)");
+    const int64_t P = R.P;
+    if (!tables || (tables & ~((1u << ARP_SHORTLIST_TABLES) - 1u))) FAIL(c, ARP_E_ARG, fn + "tables must be a non-zero mask of the five tables");
+    if (sift_mask & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_mask has bits beyond the 15 SIFt bits");
+    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
+    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 keeps no record");
+    bool planes = (tables >> 1) != 0;
+    if (kind == ARP_SHORTLIST_LIST) {
+        if (!pose_ids) FAIL(c, ARP_E_ARG, fn + "pose_ids missing (ARP_SHORTLIST_LIST)");
+        if (n_ids < 1 || n_ids > ARP_POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "n_ids must be 1 ... ARP_POSES_MAX_POSES");
+        if (skip != 0 || k != 0 || min_score != INT64_MIN) FAIL(c, ARP_E_ARG, fn + "ARP_SHORTLIST_LIST takes skip = 0, k = 0 and min_score = INT64_MIN (the list is the choice)");
+        for (int64_t q = 0; q < n_ids; ++q)
+            if (pose_ids[q] < 0 || pose_ids[q] >= P) FAIL(c, ARP_E_ARG, fn + "pose_ids has an id outside [0, P)");
+    } else {
+        if (skip < 0 || skip >= P) FAIL(c, ARP_E_ARG, fn + "skip must be in [0, P)");
+        if (k < 1) FAIL(c, ARP_E_ARG, fn + "k must be at least 1");
+    }
+    if (kind == ARP_SHORTLIST_SUMMARY) {
+        if (!weights32) FAIL(c, ARP_E_ARG, fn + "weights missing (ARP_SHORTLIST_SUMMARY)");
+        for (int q = 0; q < 2 * PSL_SLOTS; ++q) {
+            if (weights32[q] > ARP_SHORTLIST_MAX_WEIGHT || weights32[q] < -ARP_SHORTLIST_MAX_WEIGHT) FAIL(c, ARP_E_ARG, fn + "weights has an entry beyond +-ARP_SHORTLIST_MAX_WEIGHT = 2^24");
+            if (q >= PSL_SLOTS && weights32[q] != 0) planes = true;
+        }
+    }
+    if (kind == ARP_SHORTLIST_TANIMOTO) {
+        if (!F.valid) FAIL(c, ARP_E_ARG, fn + "no fingerprint result (arp_poses_fingerprints_launch; ARP_SHORTLIST_TANIMOTO)");
+        if (F.Q < 1) FAIL(c, ARP_E_ARG, fn + "the fingerprint result has no references (n_refs = 0)");
+        if (F.P != P) FAIL(c, ARP_E_ARG, fn + "the fingerprint result and the poses result differ in P");
+        if (ref < -1 || ref >= F.Q) FAIL(c, ARP_E_ARG, fn + "ref must be -1 or in [0, n_refs)");
+    }
+    if (planes) {
+        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no poses-planes result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
+        if (L.P != R.P || L.S != R.S) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result differ in P or S (launch both on the same poses)");
+    }
+    // ---- from here on the previous shortlist is gone
+    S.valid = false;
+    S.planes = planes;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool list = kind == ARP_SHORTLIST_LIST;
+    const int64_t M = P - skip, ncand = list ? n_ids : std::min(k, M);
+    HIPCHK(c, S.words.reserve(8));
+    HIPCHK(c, S.pose.reserve((size_t)ncand));
+    HIPCHK(c, S.score.reserve((size_t)ncand));
+    HIPCHK(c, S.summary.reserve((size_t)ncand * PSL_SLOTS));
+    HIPCHK(c, S.pl_summary.reserve((size_t)ncand * PSL_SLOTS));
+    HIPCHK(c, S.len.reserve((size_t)ncand * PSL_TABLES));
+    HIPCHK(c, S.off.reserve(((size_t)ncand + 1) * PSL_TABLES));
+    PslArgs A{};
+    const uint8_t* const slab = R.slab.p;      // (no record: the columns are never read, every segment is empty)
+    if (R.count > 0) {
+        A.ci = (const int*)(slab + R.off[0]); A.cj = (const int*)(slab + R.off[1]); A.cd = (const float*)(slab + R.off[2]);
+        A.cs = (const uint16_t*)(slab + R.off[3]); A.cct = slab + R.off[4];
+    }
+    A.aa_off = R.pose_off.p; A.aa_count = R.count;
+    A.summary = R.summary.p; A.P = (int)P;
+    if (planes) {
+        A.pl = L.col; A.pl_off = L.pose_off.p; A.pl_summary = L.summary.p;
+        for (int t = 0; t < 4; ++t) A.pl_count[t] = L.counts[t];
+    }
+    A.kind = kind; A.skip = (int)skip; A.M = (int)M;
+    if (kind == ARP_SHORTLIST_SUMMARY)
+        for (int q = 0; q < 2 * PSL_SLOTS; ++q) A.w[q] = weights32[q];
+    if (kind == ARP_SHORTLIST_TANIMOTO) { A.fp_count = F.count.p; A.fp_cross = F.cross.p; A.Q = (int)F.Q; A.ref = (int)ref; }
+    A.ncand = (int)ncand; A.min_score = list ? INT64_MIN : min_score;
+    A.tables = tables; A.sift_mask = sift_mask; A.ctype_mask = ctype_mask;
+    A.pose = S.pose.p; A.score = S.score.p; A.out_summary = S.summary.p; A.out_pl_summary = S.pl_summary.p;
+    A.len = S.len.p; A.off = S.off.p; A.words = S.words.p;
+    HIPCHK(c, hipMemsetAsync(S.words.p, 0, 8 * sizeof(unsigned long long), c->stream));
+    if (planes)
+        hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(P * R.S * 3, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.xyz.p,
+                           (const uint32_t*)L.xyz.p, (long long)(P * R.S * 3), (uint32_t*)(S.words.p + PSL_W_DIFFER));
+    if (list) {
+        CHK(upload_async(c, S.ids, (const int*)pose_ids, (size_t)n_ids));      // (the wait below is before the caller's array goes away)
+        A.ids = S.ids.p;
+    } else {
+        // ---- score and rank: keys of all 64 bits, stable, so that ties stay in ascending pose
+        CHK(reserve_key_sort(c, S.sort, (size_t)M, (size_t)M));
+        A.key = S.sort.key[0].p; A.val = S.sort.val[0].p;
+        hipLaunchKernelGGL(k_psl_score, dim3(nblocks(M, 256)), dim3(256), 0, c->stream, A);
+        int sorted = 0;
+        enqueue_key_sort(c, S.sort, (size_t)M, 64, &sorted);
+        A.skey = S.sort.key[sorted].p; A.sval = S.sort.val[sorted].p;
+    }
+    // ---- lengths, offsets, and the one wait
+    hipLaunchKernelGGL(k_psl_lengths, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_psl_offsets, dim3(PSL_TABLES), dim3(1024), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "score / sort / lengths / offsets").c_str()));
+    CHK(stage_copy(c, S.words.p, 8 * sizeof(unsigned long long)));
+    unsigned long long h[8];
+    memcpy(h, c->table_stage, sizeof(h));
+    ++S.launches;
+    if (planes && h[PSL_W_DIFFER] != 0) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result were made from different poses");
+    if (h[PSL_W_ERR] != 0) FAIL(c, ARP_E_HIP, fn + "device error (a pose id out of range)");
+    if (h[PSL_W_K] > (unsigned long long)ncand) FAIL(c, ARP_E_HIP, fn + "chosen count out of range");
+    for (int t = 0; t < PSL_TABLES; ++t)
+        if (h[PSL_W_TOTAL + t] >= (1ull << 31)) FAIL(c, ARP_E_CAPACITY, fn + "a table of 2^31 records or more (a smaller k)");
+    // ---- the columns of the requested tables in one slab: atom-atom as the sorted slab is laid out, the others as the
+    // poses-planes result lays out its own
+    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
+    size_t bytes = 0;
+    sorted_layout((size_t)h[PSL_W_TOTAL], S.aa_off, &bytes, (size_t)h[PSL_W_TOTAL]);
+    PplColumns col{};
+    size_t off_i0[4], off_i1[4], off_d[4][4] = {}, off_u[4][3] = {};
+    for (int t = 0; t < 4; ++t) {
+        const size_t m = (size_t)h[PSL_W_TOTAL + 1 + t];
+        off_i0[t] = bytes; bytes += al256(m * sizeof(int));
+        off_i1[t] = bytes; bytes += al256(m * sizeof(int));
+        for (int q = 0; q < n_val[t]; ++q) { off_d[t][q] = bytes; bytes += al256(m * (t == 2 ? sizeof(float) : sizeof(double))); }
+        for (int q = 0; q < n_byte[t]; ++q) { off_u[t][q] = bytes; bytes += al256(m); }
+    }
+    HIPCHK(c, S.slab.reserve(std::max<size_t>(bytes, 256)));
+    for (int t = 0; t < 4; ++t) {
+        col.i0[t] = (int*)(S.slab.p + off_i0[t]); col.i1[t] = (int*)(S.slab.p + off_i1[t]);
+        for (int q = 0; q < n_val[t]; ++q) col.d[t][q] = (double*)(S.slab.p + off_d[t][q]);
+        for (int q = 0; q < n_byte[t]; ++q) col.u[t][q] = S.slab.p + off_u[t][q];
+    }
+    const Columns aa{S.slab.p, S.aa_off};
+    A.oi = aa[0]; A.oj = aa[1]; A.od = aa[2]; A.os = aa[3]; A.oct = aa[4];
+    A.opl = col;
+    int64_t all = 0;
+    for (int t = 0; t < PSL_TABLES; ++t) { A.total[t] = (long long)h[PSL_W_TOTAL + t]; all += A.total[t]; }
+    if (all > 0) {
+        hipLaunchKernelGGL(k_psl_gather, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
+        CHK(check_launch(c, (fn + "gather").c_str()));
+    }
+    S.col = col;
+    S.K = (int64_t)h[PSL_W_K]; S.ncand = ncand; S.kind = kind; S.tables = A.tables;
+    for (int t = 0; t < PSL_TABLES; ++t) S.total[t] = A.total[t];
+    S.valid = true;
+    shortlist_info(S, info);
+    return ARP_OK;
+}
+
+// what a shortlist fetch copies: every piece through the page-locked stage in one wait, then to the caller's arrays; the
+// device's error word rides along (the gather runs after the launch's wait)
+namespace {
+struct StagePiece { void* dst; const void* src; size_t bytes; };
+int shortlist_stage(arp_ctx* c, std::vector<StagePiece>& pieces, const char* fn) {
+    unsigned long long err = 0;
+    pieces.push_back(StagePiece{&err, c->shortlist.words.p + PSL_W_ERR, sizeof(err)});
+    size_t total = 0;
+    for (const StagePiece& pc_ : pieces) total += (pc_.bytes + 15) & ~(size_t)15;
+    CHK(table_stage_reserve(c, total));
+    size_t at = 0;
+    for (const StagePiece& pc_ : pieces) {
+        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->table_stage + at, pc_.src, pc_.bytes, hipMemcpyDeviceToHost, c->stream));
+        at += (pc_.bytes + 15) & ~(size_t)15;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    at = 0;
+    for (const StagePiece& pc_ : pieces) {
+        memcpy(pc_.dst, (const uint8_t*)c->table_stage + at, pc_.bytes);
+        at += (pc_.bytes + 15) & ~(size_t)15;
+    }
+    if (err != 0) FAIL(c, ARP_E_HIP, std::string(fn) + ": device error (a record beyond its table's total)");
+    return ARP_OK;
+}
+}  // namespace
+
+int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_t* pose, int64_t* score, uint32_t* summary, uint32_t* planes_summary,
+                              uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift, uint8_t* ctype, int64_t* n_chosen, int64_t* count) {
+    if (!c || !n_chosen || !count) return ARP_E_ARG;
+    const ShortlistResult& S = c->shortlist;
+    if (!S.valid)      // (voided wherever the poses result is; with the poses-planes result when it read that)
+        FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: no result (arp_poses_shortlist_launch; a result it was made from was replaced or an input or the selection changed since)");
+    *n_chosen = S.K;
+    *count = S.total[0];
+    const bool records = i || j || dist || sift || ctype;
+    if ((off || records) && !(S.tables & 1u)) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: the atom-atom table was not requested (tables bit 0)");
+    if (planes_summary && !S.planes) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: the launch did not read the poses-planes result (no planes_summary)");
+    if ((pose || score || summary || planes_summary || off) && cap_poses < S.K) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_fetch: output buffers too small (cap_poses < *n_chosen)");
+    if (records && cap < S.total[0]) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_fetch: output buffers too small (cap < *count)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = (size_t)S.K, n = (size_t)S.total[0];
+    std::vector<StagePiece> pieces;
+    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(StagePiece{dst, src, bytes}); };
+    want(pose, S.pose.p, K * sizeof(int32_t));
+    want(score, S.score.p, K * sizeof(int64_t));
+    want(summary, S.summary.p, K * PSL_SLOTS * sizeof(uint32_t));
+    want(planes_summary, S.pl_summary.p, K * PSL_SLOTS * sizeof(uint32_t));
+    want(off, S.off.p, (K + 1) * sizeof(unsigned long long));
+    if (records && n > 0) {
+        const uint8_t* const slab = S.slab.p;
+        want(i, slab + S.aa_off[0], n * sizeof(int32_t));
+        want(j, slab + S.aa_off[1], n * sizeof(int32_t));
+        want(dist, slab + S.aa_off[2], n * sizeof(float));
+        want(sift, slab + S.aa_off[3], n * sizeof(uint16_t));
+        want(ctype, slab + S.aa_off[4], n * sizeof(uint8_t));
+    }
+    return shortlist_stage(c, pieces, "arp_poses_shortlist_fetch");
+}
+
+int arp_poses_shortlist_planes_fetch(arp_ctx* c, int table, int64_t cap_poses, int64_t cap, uint64_t* off, int32_t* first, int32_t* second, void* v0,
+                                     void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const ShortlistResult& S = c->shortlist;
+    if (!S.valid)
+        FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: no result (arp_poses_shortlist_launch; a result it was made from was replaced or an input or the selection changed since)");
+    if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
+    const int t = table;
+    if (!((S.tables >> (t + 1)) & 1u)) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table was not requested (tables bit table + 1)");
+    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
+    *count = S.total[t + 1];
+    void* const v[4] = {v0, v1, v2, v3};
+    uint8_t* const u[3] = {u0, u1, u2};
+    bool records = first || second;
+    for (int q = 0; q < 4; ++q) {
+        if (v[q] && q >= n_val[t]) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table has no such value column");
+        records = records || v[q];
+    }
+    for (int q = 0; q < 3; ++q) {
+        if (u[q] && q >= n_byte[t]) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table has no such byte column");
+        records = records || u[q];
+    }
+    if (off && cap_poses < S.K) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap_poses < chosen poses)");
+    if (records && cap < S.total[t + 1]) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap < *count)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t K = (size_t)S.K, n = (size_t)S.total[t + 1];
+    std::vector<StagePiece> pieces;
+    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(StagePiece{dst, src, bytes}); };
+    want(off, S.off.p + (size_t)(t + 1) * ((size_t)S.ncand + 1), (K + 1) * sizeof(unsigned long long));
+    if (records && n > 0) {
+        want(first, S.col.i0[t], n * sizeof(int32_t));
+        want(second, S.col.i1[t], n * sizeof(int32_t));
+        for (int q = 0; q < n_val[t]; ++q) want(v[q], S.col.d[t][q], n * (t == 2 ? sizeof(float) : sizeof(double)));
+        for (int q = 0; q < n_byte[t]; ++q) want(u[q], S.col.u[t][q], n);
+    }
+    return shortlist_stage(c, pieces, "arp_poses_shortlist_planes_fetch");
+}
+
+int arp_poses_shortlist_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    shortlist_info(c->shortlist, info);
     return ARP_OK;
 }
 

@@ -1177,6 +1177,77 @@ int arp_poses_fingerprints_planes_launch(arp_ctx* ctx, uint32_t planes29, uint32
 int arp_poses_fingerprints_fetch(arp_ctx* ctx, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy,
                                  uint64_t* bits, uint32_t* inter, int64_t* n_nodes);
 int arp_poses_fingerprints_info(arp_ctx* ctx, int64_t info[8]);
+/* Pose shortlist: the poses of the resident result of arp_poses_contacts_launch ranked on the device, and only the chosen
+ * poses' records — optionally filtered — compacted for the fetch (csrc/arp_poses_shortlist.h).
+ *
+ * SOURCE: the resident poses result, P poses; depending on the arguments also the resident poses-planes result and the
+ *   resident fingerprint result.  Nothing of them is written.
+ * RANKED POSES: skip <= p < P, 0 <= skip < P.  The leading `skip` poses are the references of a fingerprint launch and take no
+ *   part.
+ * SCORE: an int64 of one of three kinds.
+ *   ARP_SHORTLIST_LIST      no score (0).  The chosen poses are the caller's pose_ids[n_ids] in the caller's order: each id in
+ *                           [0, P), repeats allowed, 1 <= n_ids <= ARP_POSES_MAX_POSES.  skip, k and min_score must be 0, 0 and
+ *                           INT64_MIN.
+ *   ARP_SHORTLIST_SUMMARY   score[p] = sum_{s<16} w[s] summary[p][s] + sum_{s<16} w[16 + s] planes_summary[p][s], weights32 =
+ *                           int32[32] with |w| <= ARP_SHORTLIST_MAX_WEIGHT = 2^24 (the sum fits 60 bits).  A non-zero weight in
+ *                           the second half needs the poses-planes result of the SAME POSES (below).
+ *   ARP_SHORTLIST_TANIMOTO  from the resident fingerprint result (either entry; n_refs >= 1; its P the source's).  For reference
+ *                           q: t = cross[p][q], u = count[p] + count[q] - t, score_q = (u == 0) ? 2^32 : floor(t 2^32 / u) in
+ *                           unsigned 64-bit arithmetic (t < 2^32: the product fits); 0 / 0 is 1.0.  ref in [0, n_refs) names
+ *                           the reference, ref = -1 takes the largest score_q over all references.  The scores are taken at
+ *                           launch: the shortlist does not read the fingerprint result afterwards.
+ * ORDER: descending score, ties by ascending pose id.  The chosen poses are the first K = min(k, P - skip) of that order whose
+ *   score is >= min_score, k >= 1; INT64_MIN: no threshold.  K = 0 is a valid, empty shortlist.
+ * TABLES: a non-zero mask.  Bit 0: the atom-atom table; bits 1 ... 4: atom_plane, plane_plane, group_group, group_plane of the
+ *   poses-planes result (SAME POSES).
+ * RECORD FILTER: an atom-atom record is kept when bit ctype of ctype_mask is set (7 types, non-zero) and sift_mask == 0 or
+ *   sift & sift_mask != 0 (15 bits); a ring / amide record when bit ctype of ctype_mask is set.  sift_mask = 0 with ctype_mask =
+ *   ARP_FILTER_CTYPE_ALL keeps everything.
+ * RESULT: pose int32 [K]; score int64 [K]; summary uint32 [K][16] and planes_summary uint32 [K][16], the source rows of the
+ *   chosen poses, unfiltered (what the pose has, not what was kept); per requested table off uint64 [K + 1] and the table's
+ *   columns: the records of chosen pose r are [off[r], off[r + 1]), the kept records of that pose in the order the source holds
+ *   them, every column with the source's type and bits.  Nothing is truncated; the result is deterministic.
+ * SAME POSES: wherever the poses-planes result is read (tables bits 1 ... 4, a non-zero weight 16 ... 31) it must have the
+ *   source's P and S and must have been made from the same uploaded coordinates (compared on the device as 32-bit words, the
+ *   outcome read in the launch's one wait).
+ *
+ * arp_poses_shortlist_launch: info[8] as arp_poses_shortlist_info gives it.  One host wait (K, the five totals, the same-poses
+ *   flag, the device's error word); every launch and copy goes on the context's stream.  Refusals are ARP_E_ARG with the cause
+ *   named, and none of them touches a resident result: no poses result; a pass not waited for; unknown kind; weights, pose_ids
+ *   (or an id, or n_ids) or ref missing or out of range; skip or k out of range; tables 0 or beyond bit 4, sift_mask beyond 15
+ *   bits, ctype_mask 0 or beyond 7 bits; ARP_SHORTLIST_LIST with skip / k / min_score set; ARP_SHORTLIST_TANIMOTO without a
+ *   fingerprint result, with n_refs = 0 or with another P; "no poses-planes result"; "differ in P or S".  "Made from different
+ *   poses" is ARP_E_ARG too, found on the device: no shortlist is left after it.  ARP_E_CAPACITY: a table of 2^31 records or
+ *   more (no shortlist left).  Every successful launch remakes the result.
+ *   The shortlist is void exactly when the poses result is void or replaced (a new arp_poses_contacts_launch,
+ *   arp_set_selection, a new structure, models or a batch); one that read the poses-planes result also when that is
+ *   (arp_poses_planes_launch, arp_set_plane_atoms).  Making it voids nothing: the bags of the last pass, every table made from
+ *   them, both poses results and the fingerprint result stay fetchable and byte-equal.
+ *
+ * arp_poses_shortlist_fetch: the per-pose arrays and the atom-atom table; ANY pointer but n_chosen and count may be NULL.
+ *   *n_chosen = K, *count = kept atom-atom records.  ARP_E_CAPACITY when a per-pose array (pose, score, summary, planes_summary,
+ *   off) is asked for and cap_poses < K, or a record column is asked for and cap < *count.  ARP_E_ARG: no valid result; off or a
+ *   record column of a launch without tables bit 0; planes_summary of a launch that did not read the poses-planes result.
+ * arp_poses_shortlist_planes_fetch: one ring / amide table a call (ARP_POSES_PLANES_ATOM_PLANE ...), columns and their types as
+ *   arp_poses_planes_fetch; *count = kept records of the table.  ARP_E_ARG for a table that was not requested and for a column
+ *   the table does not have; ARP_E_CAPACITY as above.  Both fetches pass every piece through the page-locked stage in one wait.
+ * arp_poses_shortlist_info: info[0] = K, [1] ... [5] = kept records of the five tables (0 for a table not requested), [6] =
+ *   launches that did work so far, [7] = kind.  [0] ... [5] and [7] are 0 while there is no result. */
+#define ARP_SHORTLIST_LIST 0
+#define ARP_SHORTLIST_SUMMARY 1
+#define ARP_SHORTLIST_TANIMOTO 2
+#define ARP_SHORTLIST_TABLES 5
+#define ARP_SHORTLIST_MAX_WEIGHT (1 << 24)
+int arp_poses_shortlist_launch(arp_ctx* ctx, int kind, const int32_t* weights32, int64_t ref, const int32_t* pose_ids, int64_t n_ids,
+                               int64_t skip, int64_t k, int64_t min_score, uint32_t tables, uint32_t sift_mask, uint32_t ctype_mask,
+                               int64_t info[8]);
+int arp_poses_shortlist_fetch(arp_ctx* ctx, int64_t cap_poses, int64_t cap, int32_t* pose, int64_t* score, uint32_t* summary,
+                              uint32_t* planes_summary, uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift,
+                              uint8_t* ctype, int64_t* n_chosen, int64_t* count);
+int arp_poses_shortlist_planes_fetch(arp_ctx* ctx, int table, int64_t cap_poses, int64_t cap, uint64_t* off, int32_t* first,
+                                     int32_t* second, void* v0, void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2,
+                                     int64_t* count);
+int arp_poses_shortlist_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
