@@ -999,6 +999,19 @@ class Context:
         self._check(self._L.arp_poses_planes_launch(self._h, x.shape[0], _p(x), _p(counts)), 'arp_poses_planes_launch')
         return x.shape[0], counts, atoms
 
+    @staticmethod
+    def _plane_table_buffers(name, k, n_off):
+        """A ring / amide table of ``k`` records with ``pose_off`` [n_off], and its columns as the pointers of a plane fetch (two
+        ids, four values, three bytes: ``poses.PLANE_COLUMNS``; the columns the table does not have are null)."""
+        from . import poses as _poses
+        ids, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
+        tab = {c: np.empty(k, np.int32) for c in ids}
+        tab.update({c: np.empty(k, vdt) for c in vals})
+        tab.update({c: np.empty(k, np.uint8) for c in byts})
+        tab['pose_off'] = np.empty(n_off, np.uint64)
+        args = [_p(tab[c]) for c in ids] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
+        return tab, args
+
     def poses_planes(self, xyz):
         """Every pose's ring and amide contacts in one launch (arp_poses_planes_*; ``arpeggio_amd.poses``).  The uploaded selection
         is the movable set, ``set_plane_atoms`` has named the ring and amide atoms; ``xyz`` float32 [P, S, 3].  Returns a dict with
@@ -1012,12 +1025,7 @@ class Context:
         summary = np.empty((P, POSES_PLANES_SUMMARY), np.uint32)
         for t, name in enumerate(_poses.PLANE_TABLES):
             k = int(counts[t])
-            ids, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
-            tab = {c: np.empty(k, np.int32) for c in ids}
-            tab.update({c: np.empty(k, vdt) for c in vals})
-            tab.update({c: np.empty(k, np.uint8) for c in byts})
-            tab['pose_off'] = np.empty(P + 1, np.uint64)
-            args = [_p(tab[c]) for c in ids] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
+            tab, args = self._plane_table_buffers(name, k, P + 1)
             self._check(self._L.arp_poses_planes_fetch(self._h, t, k, _p(tab['pose_off']), *args, _p(summary) if t == 0 else None, C.byref(n)),
                         'arp_poses_planes_fetch')
             out[name] = tab
@@ -1134,12 +1142,7 @@ class Context:
             if not (mask >> (t + 1)) & 1:
                 continue
             kept = int(info[2 + t])
-            idc, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
-            tab = {c: np.empty(kept, np.int32) for c in idc}
-            tab.update({c: np.empty(kept, vdt) for c in vals})
-            tab.update({c: np.empty(kept, np.uint8) for c in byts})
-            tab['pose_off'] = np.empty(K + 1, np.uint64)
-            args = [_p(tab[c]) for c in idc] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
+            tab, args = self._plane_table_buffers(name, kept, K + 1)
             self._check(self._L.arp_poses_shortlist_planes_fetch(self._h, t, K, kept, _p(tab['pose_off']), *args, C.byref(m)),
                         'arp_poses_shortlist_planes_fetch')
             out[name] = tab

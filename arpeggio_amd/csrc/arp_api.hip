@@ -310,11 +310,15 @@ struct PosesResult {
     size_t off[5] = {0, 0, 0, 0, 0};
     int64_t P = 0, S = 0, SH = 0, count = 0;
     bool valid = false;
+    void release() {
+        sel_h.release(); pos_of.release(); xyz.release(); hx.release(); ctr.release(); summary.release(); pose_off.release(); sort.release();
+        slab.release(); movable_static = movable_sel = 0; valid = false;
+    }
 };
 
 // the fingerprints of the resident poses result (arp_poses_fingerprints_launch, arp_poses_fingerprints.h): the presence bitmap of
 // the nodes with its word bases, the columns, the bit matrix, the scores, and what they were made for.  Valid only while the
-// poses result it was made from is (arp_poses_contacts_launch and inputs_changed void both); one made with class planes
+// poses result it was made from is (void_pose_results); one made with class planes
 // (arp_poses_fingerprints_planes_launch: `classes`) read the poses-planes result too and goes with either
 struct PoseFpResult {
     DevBuf<unsigned long long> presence, bits;
@@ -623,10 +627,11 @@ struct arp_ctx {
     int64_t net_nodes = 0;
     ResultTable coupling;                 // arp_models_coupling_launch: features and pairs in one slab; count = kept pairs
     CouplingScratch couple;
-    PosesPlanesResult pplanes;            // arp_poses_planes_launch: likewise; its plane atoms go with the structure, rings or amides
-    PosesResult poses;                    // arp_poses_contacts_launch: reads no bag, voided with the inputs (inputs_changed)
-    PoseFpResult posefp;                  // arp_poses_fingerprints_launch: reads the poses result alone, voided with it
-    ShortlistResult shortlist;            // arp_poses_shortlist_launch: likewise; with the poses-planes result when it read that
+    // the ligand-pose family: no bag is read; void_pose_results says what each reads
+    PosesPlanesResult pplanes;            // arp_poses_planes_launch; its plane atoms go with the structure, rings or amides
+    PosesResult poses;                    // arp_poses_contacts_launch
+    PoseFpResult posefp;                  // arp_poses_fingerprints_launch
+    ShortlistResult shortlist;            // arp_poses_shortlist_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -827,6 +832,28 @@ void void_results(arp_ctx* c, unsigned lost) {
         if (r.reads & lost) { *r.valid = false; lost |= r.makes; }
 }
 
+// The same rule for the results of the ligand-pose family (DESIGN.md 5o ... 5s), which read no bag: `lost` names what was
+// replaced or is about to be — the structure, the selection, or one of the rows below itself.  A row goes when it
+// is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The fingerprint and the
+// shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight.
+// A launch names its own result here before it writes it, and sets it valid again at its end.
+enum : unsigned {
+    POSE_STRUCTURE = 1u << 0, POSE_SELECTION = 1u << 1, POSE_PLANE_ATOMS = 1u << 2, POSE_MOVABLE = 1u << 3, POSE_CONTACTS = 1u << 4,
+    POSE_PLANES = 1u << 5, POSE_FINGERPRINT = 1u << 6, POSE_SHORTLIST = 1u << 7
+};
+void void_pose_results(arp_ctx* c, unsigned lost) {
+    const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
+    const struct { bool* valid; unsigned is, reads; } results[] = {
+        {&c->pplanes.have_atoms, POSE_PLANE_ATOMS, POSE_STRUCTURE},
+        {&c->pplanes.setup, POSE_MOVABLE, inputs | POSE_PLANE_ATOMS},      // (the movable set's tables of the poses-planes result)
+        {&c->pplanes.valid, POSE_PLANES, POSE_MOVABLE},
+        {&c->poses.valid, POSE_CONTACTS, inputs},       // (its movable tables go by static_epoch / sel_epoch)
+        {&c->posefp.valid, POSE_FINGERPRINT, POSE_CONTACTS | (c->posefp.classes ? POSE_PLANES : 0u)},
+        {&c->shortlist.valid, POSE_SHORTLIST, POSE_CONTACTS | (c->shortlist.planes ? POSE_PLANES : 0u)}};
+    for (const auto& r : results)
+        if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
+}
+
 // What a caller can replace, for inputs_changed.  IN_BATCH_GRIDS is no input: batch_grid_desc started the grid tables of the
 // batch over (every slot held another radius; arp_get_stats counts it in stats[7]).
 enum : unsigned {
@@ -840,19 +867,19 @@ enum : unsigned {
 
 // The one place that marks derived state stale because an input changed; whoever builds an artefact sets it valid again.
 //
-//   input                  static  lists  contact  all-atom  centre  batch  selection  default    results  model
-//                          columns        grid     grid      grids                     selection           mode
-//   atoms                  x       x      x        x         (b)     x      x          x          x        x
-//   residues               x       x      x        x                        x                     x        x
-//   bonds, hydrogens       x       x                                                              x        x
-//   single-bond nbrs       x       x                                                              x        x
-//   rings / amides         x       x                         own(b)  x      x                     x        x
-//   ownership              x       x      x        x         (b)     x                            x        x
-//   group ownership        x       x                         (b)     x                            x        x
-//   selection                                      x                        x                     x
-//   selection state        x (s)   x      x        x                        x                     x
-//   batch                  x       x      x        x         x       x                            x        x
-//   whole structure                                                                               x
+//   input                  static  lists  contact  all-atom  centre  batch  selection  default    results  model  pose     plane
+//                          columns        grid     grid      grids                     selection           mode   results  atoms
+//   atoms                  x       x      x        x         (b)     x      x          x          x        x      x        x
+//   residues               x       x      x        x                        x                     x        x      x        x
+//   bonds, hydrogens       x       x                                                              x        x      x        x
+//   single-bond nbrs       x       x                                                              x        x      x        x
+//   rings / amides         x       x                         own(b)  x      x                     x        x      x        x
+//   ownership              x       x      x        x         (b)     x                            x        x      x        x
+//   group ownership        x       x                         (b)     x                            x        x      x        x
+//   selection                                      x                        x                     x               x
+//   selection state        x (s)   x      x        x                        x                     x               x
+//   batch                  x       x      x        x         x       x                            x        x      x        x
+//   whole structure                                                                               x               x
 //   batch grid tables      x (k)   x      x        x         x                                    (no input)
 //   models                 as a blob upload (everything), then as a batch; model mode begins after both      (m)
 //
@@ -879,6 +906,9 @@ enum : unsigned {
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  What
 //   is made from them on the device goes with them by the one rule of void_results.
+// pose results: the poses result, the poses-planes result with its movable set-up, the fingerprint and the shortlist read the
+//   structure and the selection, no bag; plane atoms (arp_set_plane_atoms) name atoms of the structure and stay through a new
+//   selection.  void_pose_results is the one statement of what each of them reads.
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -888,6 +918,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     const unsigned columns = IN_EVERYTHING & ~(IN_SELECTION | IN_WHOLE_STRUCTURE);
     const unsigned partition = IN_ATOMS | IN_RINGS | IN_AMIDES | IN_OWNERSHIP | IN_GROUP_OWNERSHIP | IN_BATCH;
     const unsigned layout = IN_BATCH | IN_BATCH_GRIDS;
+    const unsigned structure = IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE);
     if (what & (columns | IN_BATCH_GRIDS)) { c->static_dirty = c->lists_dirty = true; c->sp_keep_epoch = 0; }
     if (what & columns) c->contacts_expected = 0;
     if (what & (IN_ATOMS | IN_RESIDUES | IN_OWNERSHIP | IN_SELECTION_STATE | layout)) c->atom_grid.valid = false;
@@ -907,17 +938,13 @@ void inputs_changed(arp_ctx* c, unsigned what) {
         c->sel_uploaded = c->sel_prefilled = c->sel_all = c->whole_structure = false;
         c->nsel = -1;
     }
-    if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->models_n = 0;
+    if (what & structure) c->models_n = 0;
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
         void_results(c, RES_AA | RES_PLANES);
         c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
-        c->poses.valid = false;      // (made from the inputs alone, the selection among them: no row in void_results)
-        c->posefp.valid = false;     // (made from the poses result alone)
-        c->shortlist.valid = false;  // (likewise)
-        c->pplanes.valid = c->pplanes.setup = false;
     }
-    if (what & (IN_EVERYTHING & ~(IN_SELECTION | IN_SELECTION_STATE | IN_WHOLE_STRUCTURE))) c->pplanes.have_atoms = false;
+    void_pose_results(c, ((what & structure) ? POSE_STRUCTURE : 0u) | ((what & IN_EVERYTHING & ~structure) ? POSE_SELECTION : 0u));
 }
 
 // Several structures in one grid (arp_set_batch): the placement of arp_batchgrid.h (batch_layout), cached per radius in four
@@ -2450,11 +2477,11 @@ void arp_destroy(arp_ctx* c) {
     c->lifetimes.slab.release();
     c->networks.slab.release(); c->net_label.release(); c->net_scratch.release();
     c->similarity.bits.release(); c->similarity.inter.release();
-    c->poses.sel_h.release(); c->poses.pos_of.release(); c->poses.xyz.release(); c->poses.hx.release(); c->poses.ctr.release();
+    c->poses.release();
     c->pplanes.release();
     c->posefp.release();
     c->shortlist.release();
-    c->poses.summary.release(); c->poses.pose_off.release(); c->poses.sort.release(); c->poses.slab.release(); c->sb_idx.release();
+    c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
     if (c->bag_stage) (void)hipHostFree(c->bag_stage);
@@ -5327,6 +5354,126 @@ int arp_models_coupling_info(arp_ctx* c, int64_t info[4]) {
     return ARP_OK;
 }
 
+// ---- the ligand-pose family (DESIGN.md 5o ... 5s): what its entries share
+namespace {
+// what both pose launches refuse first, in this order
+int pose_launch_refusals(arp_ctx* c, const std::string& fn, int64_t n_poses) {
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
+    if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
+    if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
+    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
+    if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
+    if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
+    if (n_poses < 1 || n_poses > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    return ARP_OK;
+}
+// what the entries that read resident pose results refuse (other poses: P and S here, the coordinates on the device, enqueue_same_poses)
+int need_poses_result(arp_ctx* c, const std::string& fn) {
+    if (!c->poses.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
+    return ARP_OK;
+}
+int need_planes_result_of_same_poses(arp_ctx* c, const std::string& fn) {
+    const PosesPlanesResult& L = c->pplanes;
+    if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no poses-planes result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
+    if (L.P != c->poses.P || L.S != c->poses.S) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result differ in P or S (launch both on the same poses)");
+    return ARP_OK;
+}
+// both results keep their uploaded poses: a word that differs ORs 1 into *flag_word (zeroed by the caller, read in its one wait)
+void enqueue_same_poses(arp_ctx* c, void* flag_word) {
+    const long long words = (long long)(c->poses.P * c->poses.S * 3);
+    hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(words, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)c->poses.xyz.p,
+                       (const uint32_t*)c->pplanes.xyz.p, words, (uint32_t*)flag_word);
+}
+
+// The four ring / amide tables (PplColumns, arp_poses_planes.h), of the poses-planes result and of a shortlist alike: two int32 id
+// columns, then per table this many value columns of this element size and this many byte columns, one of which holds ctype.
+// In a slab: table after table, column after column in that order, each on a 256-byte boundary.
+const struct { int n_val[4], n_byte[4]; size_t val_size[4]; int ctype_col[4]; } PLANE_TABLES = {
+    {2, 4, 3, 3}, {2, 3, 1, 1}, {sizeof(double), sizeof(double), sizeof(float), sizeof(double)}, {1, 2, 0, 0}};
+struct PlaneLayout { size_t i0[4], i1[4], d[4][4], u[4][3]; };
+PlaneLayout plane_tables_layout(const size_t counts[4], size_t start, size_t* bytes) {
+    PlaneLayout L{};
+    size_t at = start;
+    for (int t = 0; t < 4; ++t) {
+        const size_t m = counts[t];
+        L.i0[t] = at; at += al256(m * sizeof(int));
+        L.i1[t] = at; at += al256(m * sizeof(int));
+        for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) { L.d[t][q] = at; at += al256(m * PLANE_TABLES.val_size[t]); }
+        for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) { L.u[t][q] = at; at += al256(m); }
+    }
+    *bytes = at;
+    return L;
+}
+PplColumns bind_plane_columns(uint8_t* slab, const PlaneLayout& L) {      // (base, the tables' sorted positions, is the caller's)
+    PplColumns col{};
+    for (int t = 0; t < 4; ++t) {
+        col.i0[t] = (int*)(slab + L.i0[t]); col.i1[t] = (int*)(slab + L.i1[t]);
+        for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) col.d[t][q] = (double*)(slab + L.d[t][q]);
+        for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) col.u[t][q] = slab + L.u[t][q];
+    }
+    return col;
+}
+
+// What a fetch copies: every piece through the page-locked stage in one wait (pageable destinations cost a copy of a few tens of
+// kB milliseconds now and then), then to the caller's arrays.
+struct StagePiece { void* dst; const void* src; size_t bytes; };
+void want_piece(std::vector<StagePiece>& pieces, void* dst, const void* src, size_t bytes) {
+    if (dst && bytes) pieces.push_back(StagePiece{dst, src, bytes});
+}
+int stage_fetch(arp_ctx* c, const std::vector<StagePiece>& pieces) {
+    std::vector<size_t> at(pieces.size() + 1, 0);      // (every piece on a 16-byte boundary of the stage)
+    for (size_t q = 0; q < pieces.size(); ++q) at[q + 1] = at[q] + ((pieces[q].bytes + 15) & ~(size_t)15);
+    if (at.back() > 0) CHK(table_stage_reserve(c, at.back()));
+    for (size_t q = 0; q < pieces.size(); ++q)
+        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->table_stage + at[q], pieces[q].src, pieces[q].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t q = 0; q < pieces.size(); ++q) memcpy(pieces[q].dst, (const uint8_t*)c->table_stage + at[q], pieces[q].bytes);
+    return ARP_OK;
+}
+// A fetch of plane table t: the caller's column pointers are columns the table has (*records: a record column is asked for) ...
+int plane_fetch_columns(arp_ctx* c, const std::string& fn, int t, const void* first, const void* second, void* const v[4], uint8_t* const u[3], bool* records) {
+    *records = first || second;
+    for (int q = 0; q < 4; ++q) {
+        if (v[q] && q >= PLANE_TABLES.n_val[t]) FAIL(c, ARP_E_ARG, fn + "the table has no such value column");
+        *records = *records || v[q];
+    }
+    for (int q = 0; q < 3; ++q) {
+        if (u[q] && q >= PLANE_TABLES.n_byte[t]) FAIL(c, ARP_E_ARG, fn + "the table has no such byte column");
+        *records = *records || u[q];
+    }
+    return ARP_OK;
+}
+// ... and, once the fetch has checked its capacities, the k records of those columns as pieces
+void plane_fetch_pieces(std::vector<StagePiece>& pieces, const PplColumns& col, int t, size_t k, void* first, void* second, void* const v[4], uint8_t* const u[3]) {
+    want_piece(pieces, first, col.i0[t], k * sizeof(int32_t));
+    want_piece(pieces, second, col.i1[t], k * sizeof(int32_t));
+    for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) want_piece(pieces, v[q], col.d[t][q], k * PLANE_TABLES.val_size[t]);
+    for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) want_piece(pieces, u[q], col.u[t][q], k);
+}
+
+// Append until it fits: `launch(cap)` reserves room for cap records, zeroes the counters and launches; the first `words` counters
+// come back through the stage into h — h[0] the records there are, h[1] the device's error word, which `device_error` turns into
+// the launch's own refusal.  A buffer that was too small is grown to the exact count and the launch repeated, `attempts` launches
+// at the most: nothing is truncated.  *needed (when given) names the count before a capacity failure.
+const size_t POSE_RECORD_LIMIT = ((size_t)1 << 31) - 1;
+int append_until_it_fits(arp_ctx* c, const std::string& fn, size_t cap, const unsigned long long* ctr, int words, unsigned long long* h, int attempts,
+                         const std::function<int(size_t)>& launch, const std::function<int(int)>& device_error, int64_t* needed) {
+    for (int attempt = 1;; ++attempt) {
+        CHK(launch(cap));
+        CHK(stage_copy(c, ctr, (size_t)words * sizeof(unsigned long long)));
+        memcpy(h, c->table_stage, (size_t)words * sizeof(unsigned long long));
+        if ((uint32_t)h[1] != 0) return device_error((int)(uint32_t)h[1]);
+        if (h[0] <= cap) return ARP_OK;
+        if (needed) *needed = (int64_t)h[0];
+        if (h[0] > POSE_RECORD_LIMIT) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more (fewer poses a launch)");
+        if (attempt == attempts) FAIL(c, ARP_E_CAPACITY, fn + "record buffer could not be sized");
+        cap = (size_t)h[0];
+    }
+}
+}  // namespace
+
 // ---- ligand poses on the resident receptor (arp_poses.h): every pose's ligand - receptor records in one launch
 // No bag is read and none is written: the receptor is the static columns in the cell order of ensure_static(cutoff), the poses
 // are uploaded, the records are appended as (key, payload), sorted by every bit of the key (enqueue_key_sort over the result's
@@ -5339,15 +5486,7 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
                               int include_sequence_adjacent, int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
     const std::string fn = "arp_poses_contacts_launch: ";
-    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
-    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
-    if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
-    if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
-    if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
-    if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
-    if (n_poses < 1 || n_poses > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    CHK(pose_launch_refusals(c, fn, n_poses));
     if (c->n >= POSES_MAX_N) FAIL(c, ARP_E_ARG, fn + "2^21 atoms or more (the sort key holds 21 bits per atom id)");
     if (!(cutoff > 0) || !(cutoff <= ARP_POSES_MAX_CUTOFF)) FAIL(c, ARP_E_ARG, fn + "cutoff must be in (0, 6.0] (beyond 6.0 selection_plus would depend on the pose)");
     if (!std::isfinite(vdw_comp)) FAIL(c, ARP_E_ARG, fn + "vdw_comp is not finite");
@@ -5377,10 +5516,8 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     }
     const int64_t SH = R.SH;
     if (SH > 0 && !h_xyz) FAIL(c, ARP_E_ARG, fn + "h_xyz missing (the movable set has hydrogens)");
-    // ---- from here on the previous result is gone, and the fingerprints made from it
-    R.valid = false;
-    c->posefp.valid = false;
-    c->shortlist.valid = false;
+    // ---- from here on the previous result is gone, and what was made from it
+    void_pose_results(c, POSE_CONTACTS);
     R.count = 0;
     HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
     HIPCHK(c, R.hx.reserve(std::max<size_t>((size_t)P * (size_t)SH * 3, 1)));
@@ -5403,29 +5540,23 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     A.count = R.ctr.p; A.err = (int*)(R.ctr.p + 1);
     A.summary = R.summary.p;
     const int keybits = 2 * A.idbits + index_bits(P);
-    const size_t limit = ((size_t)1 << 31) - 1;
-    size_t cap = std::min(limit, std::max<size_t>((size_t)1 << 16, (size_t)P * (size_t)S * 32));
     unsigned long long h[2] = {0, 0};
-    for (int attempt = 0;; ++attempt) {
+    const auto launch = [&](size_t cap) -> int {
         CHK(reserve_key_sort(c, R.sort, cap, cap));
         A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
         HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_poses_contacts, dim3((unsigned)P), dim3(POSES_THREADS), 0, c->stream, A);
-        CHK(check_launch(c, "k_poses_contacts"));
-        CHK(stage_copy(c, R.ctr.p, sizeof(h)));
-        memcpy(h, c->table_stage, sizeof(h));
-        const int dev = (int)(uint32_t)h[1];
+        return check_launch(c, "k_poses_contacts");
+    };
+    const auto device_error = [&](int dev) -> int {
         if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
         if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
-        if (dev != 0) FAIL(c, ARP_E_HIP, fn + "device error");
-        if (h[0] <= cap) break;
-        *count = (int64_t)h[0];
-        if (h[0] > limit) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more (fewer poses a launch)");
-        if (attempt == 2) FAIL(c, ARP_E_CAPACITY, fn + "record buffer could not be sized");
-        cap = (size_t)h[0];
-    }
+        FAIL(c, ARP_E_HIP, fn + "device error");
+    };
+    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)P * (size_t)S * 32)), R.ctr.p, 2, h, 3, launch,
+                             device_error, count));
     const size_t k = (size_t)h[0];
-    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)P, R.summary.p, R.pose_off.p);
+    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)P, POSES_SUMMARY - 1, R.summary.p, R.pose_off.p);
     if (k > 0) {
         int sorted = 0;
         enqueue_key_sort(c, R.sort, k, keybits, &sorted);
@@ -5493,9 +5624,7 @@ int arp_set_plane_atoms(arp_ctx* c, const int32_t* ring_off, const int32_t* ring
     CHK(check_amide_atoms(c, "arp_set_plane_atoms", c->namide, amide_atoms, c->n));
     HIPCHK(c, hipSetDevice(c->device));
     PosesPlanesResult& R = c->pplanes;
-    R.valid = R.setup = R.have_atoms = false;
-    if (c->posefp.classes) c->posefp.valid = false;
-    if (c->shortlist.planes) c->shortlist.valid = false;
+    void_pose_results(c, POSE_PLANE_ATOMS);
     const int32_t zero = 0;
     const size_t nidx = c->nring > 0 ? (size_t)ring_off[c->nring] : 0;
     CHK(upload(c, R.ring_off, c->nring > 0 ? ring_off : &zero, (size_t)c->nring + 1));
@@ -5515,7 +5644,6 @@ static int poses_planes_setup(arp_ctx* c, const std::string& fn) {
     PosesPlanesResult& R = c->pplanes;
     const int n = (int)c->n, S = (int)c->nsel, nring = (int)c->nring, namide = (int)c->namide;
     const int nres = (int)std::max<int64_t>(c->nres, 1);
-    R.setup = false;
     HIPCHK(c, R.pos_of.reserve((size_t)n));
     HIPCHK(c, R.res_selm.reserve((size_t)nres));
     HIPCHK(c, R.hist.reserve(scan_padded(nres)));
@@ -5559,15 +5687,7 @@ static int poses_planes_setup(arp_ctx* c, const std::string& fn) {
 int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64_t counts[4]) {
     if (!c || !counts) return ARP_E_ARG;
     const std::string fn = "arp_poses_planes_launch: ";
-    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
-    if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
-    if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
-    if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
-    if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
-    if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
-    if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
-    if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
-    if (n_poses < 1 || n_poses > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    CHK(pose_launch_refusals(c, fn, n_poses));
     if (c->n >= POSES_MAX_N || c->nring >= POSES_MAX_N || c->namide >= POSES_MAX_N) FAIL(c, ARP_E_ARG, fn + "2^21 atoms, rings or amides, or more (the sort key holds 21 bits per id)");
     PosesPlanesResult& R = c->pplanes;
     if (!R.have_atoms) FAIL(c, ARP_E_ARG, fn + "no plane atoms (arp_set_plane_atoms after the structure, its rings and its amides)");
@@ -5580,10 +5700,8 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     if (!R.setup) CHK(poses_planes_setup(c, fn));
     const int n = (int)c->n, S = (int)c->nsel;
     const int64_t P = n_poses;
-    // ---- from here on the previous result is gone, and the fingerprints made with its class planes
-    R.valid = false;
-    if (c->posefp.classes) c->posefp.valid = false;
-    if (c->shortlist.planes) c->shortlist.valid = false;
+    // ---- from here on the previous result is gone, and what was made with it
+    void_pose_results(c, POSE_PLANES);
     for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
     const int blocks = (int)std::min<int64_t>(P, PPL_MAX_BLOCKS);
     const int ws_rings = R.n_mring + R.n_hring + PPL_MAX_NEAR;
@@ -5611,10 +5729,8 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     A.ctr = R.ctr.p; A.summary = R.summary.p;
     A.idbits = index_bits(std::max({c->n, c->nring, c->namide})); A.pbits = index_bits(P);
     const int keybits = 2 + A.pbits + 2 * A.idbits;
-    const size_t limit = ((size_t)1 << 31) - 1;
-    size_t cap = std::min(limit, std::max<size_t>((size_t)1 << 16, (size_t)P * 64));
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-    for (int attempt = 0;; ++attempt) {
+    const auto launch = [&](size_t cap) -> int {
         CHK(reserve_key_sort(c, R.sort, cap, cap));
         HIPCHK(c, R.rec.reserve(cap));
         A.rec = R.rec.p; A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
@@ -5622,47 +5738,31 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
         hipLaunchKernelGGL(k_poses_planes, dim3((unsigned)blocks), dim3(PPL_THREADS), 0, c->stream, A);
         CHK(check_launch(c, "k_poses_planes"));
         ++R.launches;
-        CHK(stage_copy(c, R.ctr.p, sizeof(h)));
-        memcpy(h, c->table_stage, sizeof(h));
-        const int dev = (int)(uint32_t)h[1];
+        return ARP_OK;
+    };
+    const auto device_error = [&](int dev) -> int {
         if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
         if (dev == PPL_E_NEAR) FAIL(c, ARP_E_ARG, fn + "a pose brings more than ARP_POSES_PLANES_MAX_NEAR further rings within 3 A of a movable atom");
-        if (dev != 0) FAIL(c, ARP_E_HIP, fn + "device error");
-        if (h[0] <= cap) break;
-        if (h[0] > limit) FAIL(c, ARP_E_CAPACITY, fn + "2^31 records or more (fewer poses a launch)");
-        if (attempt == 1) FAIL(c, ARP_E_CAPACITY, fn + "record buffer could not be sized");
-        cap = (size_t)h[0];
-    }
+        FAIL(c, ARP_E_HIP, fn + "device error");
+    };
+    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)P * 64)), R.ctr.p, 6, h, 2, launch, device_error,
+                             nullptr));
     const size_t k = (size_t)h[0];
     if (h[2] + h[3] + h[4] + h[5] != h[0]) FAIL(c, ARP_E_HIP, fn + "the tables' record counts do not add up");
-    hipLaunchKernelGGL(k_ppl_offsets, dim3(4), dim3(1024), 0, c->stream, (int)P, R.summary.p, R.pose_off.p);
-    // the four tables in one slab: two id columns, the value columns (float64; group-group float32), the byte columns
-    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
-    PplColumns col{};
+    hipLaunchKernelGGL(k_poses_offsets, dim3(4), dim3(1024), 0, c->stream, (int)P, 0, R.summary.p, R.pose_off.p);
+    // the four tables in one slab
+    const size_t m[4] = {(size_t)h[2], (size_t)h[3], (size_t)h[4], (size_t)h[5]};
     size_t bytes = 0;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off_i0[4], off_i1[4], off_d[4][4], off_u[4][3];
-    col.base[0] = 0;
-    for (int t = 0; t < 4; ++t) {
-        const size_t m = (size_t)h[2 + t];
-        col.base[t + 1] = col.base[t] + (long long)m;
-        off_i0[t] = bytes; bytes += al(m * sizeof(int));
-        off_i1[t] = bytes; bytes += al(m * sizeof(int));
-        for (int q = 0; q < n_val[t]; ++q) { off_d[t][q] = bytes; bytes += al(m * (t == 2 ? sizeof(float) : sizeof(double))); }
-        for (int q = 0; q < n_byte[t]; ++q) { off_u[t][q] = bytes; bytes += al(m); }
-    }
+    const PlaneLayout lay = plane_tables_layout(m, 0, &bytes);
     HIPCHK(c, R.slab.reserve(std::max<size_t>(bytes, 256)));
-    for (int t = 0; t < 4; ++t) {
-        col.i0[t] = (int*)(R.slab.p + off_i0[t]); col.i1[t] = (int*)(R.slab.p + off_i1[t]);
-        for (int q = 0; q < n_val[t]; ++q) col.d[t][q] = (double*)(R.slab.p + off_d[t][q]);
-        for (int q = 0; q < n_byte[t]; ++q) col.u[t][q] = R.slab.p + off_u[t][q];
-    }
+    PplColumns col = bind_plane_columns(R.slab.p, lay);
+    for (int t = 0; t < 4; ++t) col.base[t + 1] = col.base[t] + (long long)m[t];
     if (k > 0) {
         int sorted = 0;
         enqueue_key_sort(c, R.sort, k, keybits, &sorted);
         hipLaunchKernelGGL(k_ppl_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, R.sort.val[sorted].p, R.rec.p, col);
     }
-    CHK(check_launch(c, "k_ppl_offsets / sort / k_ppl_columns"));
+    CHK(check_launch(c, "k_poses_offsets / sort / k_ppl_columns"));
     R.col = col;
     R.P = P; R.S = S; R.valid = true;
     for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = (int64_t)h[2 + t];
@@ -5675,53 +5775,19 @@ int arp_poses_planes_fetch(arp_ctx* c, int table, int64_t cap, uint64_t* pose_of
     const PosesPlanesResult& R = c->pplanes;
     if (!R.valid) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: no result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
     if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
-    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
     const int t = table;
     *count = R.counts[t];
     void* const v[4] = {v0, v1, v2, v3};
     uint8_t* const u[3] = {u0, u1, u2};
-    bool records = first || second;
-    for (int q = 0; q < 4; ++q) {
-        if (v[q] && q >= n_val[t]) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: the table has no such value column");
-        records = records || v[q];
-    }
-    for (int q = 0; q < 3; ++q) {
-        if (u[q] && q >= n_byte[t]) FAIL(c, ARP_E_ARG, "arp_poses_planes_fetch: the table has no such byte column");
-        records = records || u[q];
-    }
+    bool records = false;
+    CHK(plane_fetch_columns(c, "arp_poses_planes_fetch: ", t, first, second, v, u, &records));
     if (records && R.counts[t] > cap) FAIL(c, ARP_E_CAPACITY, "arp_poses_planes_fetch: output buffers too small");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)R.counts[t];
-    // everything that is asked for goes through the page-locked stage in one wait (pageable destinations cost a copy of
-    // a few tens of kB milliseconds now and then), then to the caller's arrays
-    struct Piece { void* dst; const void* src; size_t bytes; };
-    std::vector<Piece> pieces;
-    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(Piece{dst, src, bytes}); };
-    want(pose_off, R.pose_off.p + (size_t)t * ((size_t)R.P + 1), ((size_t)R.P + 1) * sizeof(unsigned long long));
-    want(summary, R.summary.p, (size_t)R.P * PPL_SUMMARY * sizeof(uint32_t));
-    if (records && k > 0) {
-        want(first, R.col.i0[t], k * sizeof(int32_t));
-        want(second, R.col.i1[t], k * sizeof(int32_t));
-        for (int q = 0; q < n_val[t]; ++q) want(v[q], R.col.d[t][q], k * (t == 2 ? sizeof(float) : sizeof(double)));
-        for (int q = 0; q < n_byte[t]; ++q) want(u[q], R.col.u[t][q], k);
-    }
-    size_t total = 0;
-    for (const Piece& pc_ : pieces) total += (pc_.bytes + 15) & ~(size_t)15;
-    if (total > 0) {
-        CHK(table_stage_reserve(c, total));
-        size_t at = 0;
-        for (const Piece& pc_ : pieces) {
-            HIPCHK(c, hipMemcpyAsync((uint8_t*)c->table_stage + at, pc_.src, pc_.bytes, hipMemcpyDeviceToHost, c->stream));
-            at += (pc_.bytes + 15) & ~(size_t)15;
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    size_t at = 0;
-    for (const Piece& pc_ : pieces) {
-        memcpy(pc_.dst, (const uint8_t*)c->table_stage + at, pc_.bytes);
-        at += (pc_.bytes + 15) & ~(size_t)15;
-    }
-    return ARP_OK;
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, pose_off, R.pose_off.p + (size_t)t * ((size_t)R.P + 1), ((size_t)R.P + 1) * sizeof(unsigned long long));
+    want_piece(pieces, summary, R.summary.p, (size_t)R.P * PPL_SUMMARY * sizeof(uint32_t));
+    if (records) plane_fetch_pieces(pieces, R.col, t, (size_t)R.counts[t], first, second, v, u);
+    return stage_fetch(c, pieces);
 }
 
 int arp_poses_planes_info(arp_ctx* c, int64_t info[12]) {
@@ -5776,7 +5842,7 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     const PosesPlanesResult& L = c->pplanes;
     const bool classes = (planes >> ARP_POSEFP_PLANES) != 0;
     if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
-    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
+    CHK(need_poses_result(c, fn));
     if (n_planes == ARP_POSEFP_PLANES && (planes & ~((1u << ARP_POSEFP_PLANES) - 1u))) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
     if (planes & ~((1u << ARP_POSEFP_ALL_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 29 planes (15 SIFt bits, 14 ring / amide classes)");
     if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
@@ -5790,11 +5856,10 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     if (all_pairs && P > ARP_SIM_MAX_MODELS) FAIL(c, ARP_E_CAPACITY, fn + "ARP_POSEFP_ALL_PAIRS with more than ARP_SIM_MAX_MODELS = 4096 poses (the matrix would pass 64 MiB)");
     if (classes) {
         if (!by_res) FAIL(c, ARP_E_ARG, fn + "ring / amide class planes need ARP_POSEFP_BY_RESIDUE (their nodes are residues)");
-        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no poses-planes result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
-        if (L.P != R.P || L.S != R.S) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result differ in P or S (launch both on the same poses)");
+        CHK(need_planes_result_of_same_poses(c, fn));
     }
     if (F.valid && F.planes == planes && F.ctype_mask == ctype_mask && F.flags == flags && F.Q == Q) { posefp_info(F, info); return ARP_OK; }
-    F.valid = false;
+    void_pose_results(c, POSE_FINGERPRINT);
     F.classes = classes;
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t N = by_res ? c->nres : c->n, NW = (N + 63) / 64;
@@ -5827,9 +5892,8 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     PoseFpTables T{};
     int64_t k_classes = 0;
     if (classes) {
-        static const int ctype_col[4] = {1, 2, 0, 0};      // the byte column that holds ctype (arp_poses_planes_fetch)
         for (int t = 0; t < 4; ++t) {
-            T.first[t] = L.col.i0[t]; T.second[t] = L.col.i1[t]; T.ctype[t] = L.col.u[t][ctype_col[t]];
+            T.first[t] = L.col.i0[t]; T.second[t] = L.col.i1[t]; T.ctype[t] = L.col.u[t][PLANE_TABLES.ctype_col[t]];
             T.count[t] = L.counts[t];
             k_classes = std::max(k_classes, L.counts[t]);
         }
@@ -5848,8 +5912,7 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
         // on the few words around the ligand — those behind them read the bit and skip)
         if (k > 0) hipLaunchKernelGGL(k_pfp_mark, dim3(nblocks((int64_t)k, 256, c->num_cu)), dim3(256), 0, c->stream, A);
         if (classes) {
-            hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(P * R.S * 3, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.xyz.p,
-                               (const uint32_t*)L.xyz.p, (long long)(P * R.S * 3), (uint32_t*)(F.total.p + 1));
+            enqueue_same_poses(c, F.total.p + 1);
             if (k_classes > 0) hipLaunchKernelGGL(k_pfp_mark_planes, dim3(nblocks(k_classes, 256, c->num_cu), 4), dim3(256), 0, c->stream, A, T);
         }
         hipLaunchKernelGGL(k_pfp_scan, dim3(1), dim3(POSEFP_SCAN_THREADS), 0, c->stream, A);
@@ -5971,7 +6034,7 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     const PoseFpResult& F = c->posefp;
     // ---- the refusals: none of them touches a resident result
     if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
-    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no poses result (arp_poses_contacts_launch; an input or the selection changed since)");
+    CHK(need_poses_result(c, fn));
     if (kind != ARP_SHORTLIST_LIST && kind != ARP_SHORTLIST_SUMMARY && kind != ARP_SHORTLIST_TANIMOTO)
         FAIL(c, ARP_E_ARG, fn + "unknown kind (ARP_SHORTLIST_LIST, ARP_SHORTLIST_SUMMARY or ARP_SHORTLIST_TANIMOTO)");
     const int64_t P = R.P;
@@ -6003,12 +6066,9 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
         if (F.P != P) FAIL(c, ARP_E_ARG, fn + "the fingerprint result and the poses result differ in P");
         if (ref < -1 || ref >= F.Q) FAIL(c, ARP_E_ARG, fn + "ref must be -1 or in [0, n_refs)");
     }
-    if (planes) {
-        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no poses-planes result (arp_poses_planes_launch; an input, the selection or the plane atoms changed since)");
-        if (L.P != R.P || L.S != R.S) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result differ in P or S (launch both on the same poses)");
-    }
+    if (planes) CHK(need_planes_result_of_same_poses(c, fn));
     // ---- from here on the previous shortlist is gone
-    S.valid = false;
+    void_pose_results(c, POSE_SHORTLIST);
     S.planes = planes;
     HIPCHK(c, hipSetDevice(c->device));
     const bool list = kind == ARP_SHORTLIST_LIST;
@@ -6041,9 +6101,7 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     A.pose = S.pose.p; A.score = S.score.p; A.out_summary = S.summary.p; A.out_pl_summary = S.pl_summary.p;
     A.len = S.len.p; A.off = S.off.p; A.words = S.words.p;
     HIPCHK(c, hipMemsetAsync(S.words.p, 0, 8 * sizeof(unsigned long long), c->stream));
-    if (planes)
-        hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(P * R.S * 3, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.xyz.p,
-                           (const uint32_t*)L.xyz.p, (long long)(P * R.S * 3), (uint32_t*)(S.words.p + PSL_W_DIFFER));
+    if (planes) enqueue_same_poses(c, S.words.p + PSL_W_DIFFER);
     if (list) {
         CHK(upload_async(c, S.ids, (const int*)pose_ids, (size_t)n_ids));      // (the wait below is before the caller's array goes away)
         A.ids = S.ids.p;
@@ -6071,24 +6129,12 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
         if (h[PSL_W_TOTAL + t] >= (1ull << 31)) FAIL(c, ARP_E_CAPACITY, fn + "a table of 2^31 records or more (a smaller k)");
     // ---- the columns of the requested tables in one slab: atom-atom as the sorted slab is laid out, the others as the
     // poses-planes result lays out its own
-    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
     size_t bytes = 0;
     sorted_layout((size_t)h[PSL_W_TOTAL], S.aa_off, &bytes, (size_t)h[PSL_W_TOTAL]);
-    PplColumns col{};
-    size_t off_i0[4], off_i1[4], off_d[4][4] = {}, off_u[4][3] = {};
-    for (int t = 0; t < 4; ++t) {
-        const size_t m = (size_t)h[PSL_W_TOTAL + 1 + t];
-        off_i0[t] = bytes; bytes += al256(m * sizeof(int));
-        off_i1[t] = bytes; bytes += al256(m * sizeof(int));
-        for (int q = 0; q < n_val[t]; ++q) { off_d[t][q] = bytes; bytes += al256(m * (t == 2 ? sizeof(float) : sizeof(double))); }
-        for (int q = 0; q < n_byte[t]; ++q) { off_u[t][q] = bytes; bytes += al256(m); }
-    }
+    const size_t m[4] = {(size_t)h[PSL_W_TOTAL + 1], (size_t)h[PSL_W_TOTAL + 2], (size_t)h[PSL_W_TOTAL + 3], (size_t)h[PSL_W_TOTAL + 4]};
+    const PlaneLayout lay = plane_tables_layout(m, bytes, &bytes);
     HIPCHK(c, S.slab.reserve(std::max<size_t>(bytes, 256)));
-    for (int t = 0; t < 4; ++t) {
-        col.i0[t] = (int*)(S.slab.p + off_i0[t]); col.i1[t] = (int*)(S.slab.p + off_i1[t]);
-        for (int q = 0; q < n_val[t]; ++q) col.d[t][q] = (double*)(S.slab.p + off_d[t][q]);
-        for (int q = 0; q < n_byte[t]; ++q) col.u[t][q] = S.slab.p + off_u[t][q];
-    }
+    const PplColumns col = bind_plane_columns(S.slab.p, lay);
     const Columns aa{S.slab.p, S.aa_off};
     A.oi = aa[0]; A.oj = aa[1]; A.od = aa[2]; A.os = aa[3]; A.oct = aa[4];
     A.opl = col;
@@ -6106,31 +6152,14 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     return ARP_OK;
 }
 
-// what a shortlist fetch copies: every piece through the page-locked stage in one wait, then to the caller's arrays; the
-// device's error word rides along (the gather runs after the launch's wait)
-namespace {
-struct StagePiece { void* dst; const void* src; size_t bytes; };
-int shortlist_stage(arp_ctx* c, std::vector<StagePiece>& pieces, const char* fn) {
+// a shortlist fetch: the device's error word rides along with the pieces (the gather runs after the launch's wait)
+static int shortlist_stage(arp_ctx* c, std::vector<StagePiece>& pieces, const char* fn) {
     unsigned long long err = 0;
     pieces.push_back(StagePiece{&err, c->shortlist.words.p + PSL_W_ERR, sizeof(err)});
-    size_t total = 0;
-    for (const StagePiece& pc_ : pieces) total += (pc_.bytes + 15) & ~(size_t)15;
-    CHK(table_stage_reserve(c, total));
-    size_t at = 0;
-    for (const StagePiece& pc_ : pieces) {
-        HIPCHK(c, hipMemcpyAsync((uint8_t*)c->table_stage + at, pc_.src, pc_.bytes, hipMemcpyDeviceToHost, c->stream));
-        at += (pc_.bytes + 15) & ~(size_t)15;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    at = 0;
-    for (const StagePiece& pc_ : pieces) {
-        memcpy(pc_.dst, (const uint8_t*)c->table_stage + at, pc_.bytes);
-        at += (pc_.bytes + 15) & ~(size_t)15;
-    }
+    CHK(stage_fetch(c, pieces));
     if (err != 0) FAIL(c, ARP_E_HIP, std::string(fn) + ": device error (a record beyond its table's total)");
     return ARP_OK;
 }
-}  // namespace
 
 int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_t* pose, int64_t* score, uint32_t* summary, uint32_t* planes_summary,
                               uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift, uint8_t* ctype, int64_t* n_chosen, int64_t* count) {
@@ -6148,19 +6177,18 @@ int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_
     HIPCHK(c, hipSetDevice(c->device));
     const size_t K = (size_t)S.K, n = (size_t)S.total[0];
     std::vector<StagePiece> pieces;
-    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(StagePiece{dst, src, bytes}); };
-    want(pose, S.pose.p, K * sizeof(int32_t));
-    want(score, S.score.p, K * sizeof(int64_t));
-    want(summary, S.summary.p, K * PSL_SLOTS * sizeof(uint32_t));
-    want(planes_summary, S.pl_summary.p, K * PSL_SLOTS * sizeof(uint32_t));
-    want(off, S.off.p, (K + 1) * sizeof(unsigned long long));
+    want_piece(pieces, pose, S.pose.p, K * sizeof(int32_t));
+    want_piece(pieces, score, S.score.p, K * sizeof(int64_t));
+    want_piece(pieces, summary, S.summary.p, K * PSL_SLOTS * sizeof(uint32_t));
+    want_piece(pieces, planes_summary, S.pl_summary.p, K * PSL_SLOTS * sizeof(uint32_t));
+    want_piece(pieces, off, S.off.p, (K + 1) * sizeof(unsigned long long));
     if (records && n > 0) {
         const uint8_t* const slab = S.slab.p;
-        want(i, slab + S.aa_off[0], n * sizeof(int32_t));
-        want(j, slab + S.aa_off[1], n * sizeof(int32_t));
-        want(dist, slab + S.aa_off[2], n * sizeof(float));
-        want(sift, slab + S.aa_off[3], n * sizeof(uint16_t));
-        want(ctype, slab + S.aa_off[4], n * sizeof(uint8_t));
+        want_piece(pieces, i, slab + S.aa_off[0], n * sizeof(int32_t));
+        want_piece(pieces, j, slab + S.aa_off[1], n * sizeof(int32_t));
+        want_piece(pieces, dist, slab + S.aa_off[2], n * sizeof(float));
+        want_piece(pieces, sift, slab + S.aa_off[3], n * sizeof(uint16_t));
+        want_piece(pieces, ctype, slab + S.aa_off[4], n * sizeof(uint8_t));
     }
     return shortlist_stage(c, pieces, "arp_poses_shortlist_fetch");
 }
@@ -6174,32 +6202,17 @@ int arp_poses_shortlist_planes_fetch(arp_ctx* c, int table, int64_t cap_poses, i
     if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
     const int t = table;
     if (!((S.tables >> (t + 1)) & 1u)) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table was not requested (tables bit table + 1)");
-    static const int n_val[4] = {2, 4, 3, 3}, n_byte[4] = {2, 3, 1, 1};
     *count = S.total[t + 1];
     void* const v[4] = {v0, v1, v2, v3};
     uint8_t* const u[3] = {u0, u1, u2};
-    bool records = first || second;
-    for (int q = 0; q < 4; ++q) {
-        if (v[q] && q >= n_val[t]) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table has no such value column");
-        records = records || v[q];
-    }
-    for (int q = 0; q < 3; ++q) {
-        if (u[q] && q >= n_byte[t]) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table has no such byte column");
-        records = records || u[q];
-    }
+    bool records = false;
+    CHK(plane_fetch_columns(c, "arp_poses_shortlist_planes_fetch: ", t, first, second, v, u, &records));
     if (off && cap_poses < S.K) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap_poses < chosen poses)");
     if (records && cap < S.total[t + 1]) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap < *count)");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t K = (size_t)S.K, n = (size_t)S.total[t + 1];
     std::vector<StagePiece> pieces;
-    auto want = [&](void* dst, const void* src, size_t bytes) { if (dst && bytes) pieces.push_back(StagePiece{dst, src, bytes}); };
-    want(off, S.off.p + (size_t)(t + 1) * ((size_t)S.ncand + 1), (K + 1) * sizeof(unsigned long long));
-    if (records && n > 0) {
-        want(first, S.col.i0[t], n * sizeof(int32_t));
-        want(second, S.col.i1[t], n * sizeof(int32_t));
-        for (int q = 0; q < n_val[t]; ++q) want(v[q], S.col.d[t][q], n * (t == 2 ? sizeof(float) : sizeof(double)));
-        for (int q = 0; q < n_byte[t]; ++q) want(u[q], S.col.u[t][q], n);
-    }
+    want_piece(pieces, off, S.off.p + (size_t)(t + 1) * ((size_t)S.ncand + 1), ((size_t)S.K + 1) * sizeof(unsigned long long));
+    if (records) plane_fetch_pieces(pieces, S.col, t, (size_t)S.total[t + 1], first, second, v, u);
     return shortlist_stage(c, pieces, "arp_poses_shortlist_planes_fetch");
 }
 

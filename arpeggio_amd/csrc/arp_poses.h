@@ -12,7 +12,8 @@
 //                     resident cell order, filters, decision, records appended as (key, payload) for the radix sort of
 //                     arp_sort.h, and the per-pose summary (records per SIFt bit, total) reduced in LDS: one store per pose
 //   k_poses_columns   the sorted (key, payload) pairs as the five columns
-//   k_poses_offsets   pose_off[p] = exclusive prefix of the summaries' totals
+//   k_poses_offsets   pose_off[p] = exclusive prefix of the summaries' totals (block t: of slot first_slot + t; the poses-planes
+//                     result launches it too, a block per table)
 //
 // The key is pose << 2 b | i << b | j with b = the bits of the largest packed id (b <= 21), i < j packed ids: its order is
 // ascending (pose, i, j), the order of the result.  Limits that follow: n < 2^21 atoms (POSES_MAX_N), at most 2^20 poses a
@@ -28,6 +29,7 @@
 #include <stdint.h>
 
 #include "arp_pairs.h"
+#include "arp_runs.h"
 
 #define POSES_MAX_ATOMS 1024
 #define POSES_MAX_POSES (1 << 20)
@@ -407,29 +409,20 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
     }
 }
 
-// pose_off[p] = records of the poses before p (the summaries' totals), pose_off[P] = all of them: one block, a running carry
-__global__ __launch_bounds__(1024) void k_poses_offsets(int P, const uint32_t* __restrict__ summary, u64* __restrict__ pose_off) {
+// Block t: pose_off[t][p] = what slot first_slot + t of the summary rows (POSES_SUMMARY words each) counts in the poses before p,
+// pose_off[t][P] = in all of them (scan_round, arp_runs.h).  The poses result: one block on its last slot, the records of a
+// pose; the poses-planes result (arp_poses_planes.h, rows of as many words): four blocks on slots 0 ... 3, its tables' counts.
+__global__ __launch_bounds__(1024) void k_poses_offsets(int P, int first_slot, const uint32_t* __restrict__ summary, u64* __restrict__ pose_off) {
     __shared__ u64 s_w[16];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t = (int)blockIdx.x;
+    u64* const out = pose_off + (size_t)t * ((size_t)P + 1);
     u64 carry = 0;
     for (int p0 = 0; p0 < P; p0 += 1024) {
         const int p = p0 + (int)threadIdx.x;
-        const u64 v = p < P ? (u64)summary[(size_t)p * POSES_SUMMARY + POSES_SUMMARY - 1] : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u64 u = __shfl_up(incl, off);
-            if (lane >= off) incl += u;
-        }
-        __syncthreads();      // (s_w: read in the round before)
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        u64 before = carry;
-        for (int k = 0; k < wv; ++k) before += s_w[k];
-        if (p < P) pose_off[p] = before + incl - v;
-        for (int k = 0; k < 16; ++k) carry += s_w[k];
+        const u64 before = scan_round(p < P ? (u64)summary[(size_t)p * POSES_SUMMARY + first_slot + t] : 0ull, s_w, carry);
+        if (p < P) out[p] = before;
     }
-    if (threadIdx.x == 0) pose_off[P] = carry;
+    if (threadIdx.x == 0) out[P] = carry;
 }
 
 // the sorted (key, payload) pairs as the result's five columns

@@ -22,7 +22,7 @@
 //                     lane with the operation sequences of ap_eval / pp_eval / gg_eval / gp_eval on VALUES (a moved entity's
 //                     operands are the pose's, an unmoved one's the resident arrays').  Records leave with one atomic per
 //                     evaluated wave, unsorted, with a sort key table | pose | first id | second id
-//   k_ppl_offsets     per table: pose_off[p] = exclusive prefix of the summaries' counts
+//   (k_poses_offsets  of arp_poses.h, a block per table: pose_off[t][p] = exclusive prefix of the summaries' counts)
 //   k_ppl_columns     the sorted slots gathered into each table's columns
 //
 // selection_plus of a pose: an unselected atom is in it when it lies within 6.0 A (inclusive, float64) of a movable atom's
@@ -758,32 +758,6 @@ __global__ __launch_bounds__(PPL_THREADS) void k_poses_planes(PplArgs A) {
         if (tid < 4 && sh->sum[tid]) atomicAdd(A.ctr + 2 + tid, (unsigned long long)sh->sum[tid]);
         __syncthreads();
     }
-}
-
-// pose_off[t][p] = records of table t in the poses before p, pose_off[t][P] = all of them: block t, a running carry
-__global__ __launch_bounds__(1024) void k_ppl_offsets(int P, const uint32_t* __restrict__ summary, u64* __restrict__ pose_off) {
-    __shared__ u64 s_w[16];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = (int)blockIdx.x;
-    u64* const out = pose_off + (size_t)t * ((size_t)P + 1);
-    u64 carry = 0;
-    for (int p0 = 0; p0 < P; p0 += 1024) {
-        const int p = p0 + (int)threadIdx.x;
-        const u64 v = p < P ? (u64)summary[(size_t)p * PPL_SUMMARY + t] : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u64 u = __shfl_up(incl, off);
-            if (lane >= off) incl += u;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        u64 before = carry;
-        for (int k = 0; k < wv; ++k) before += s_w[k];
-        if (p < P) out[p] = before + incl - v;
-        for (int k = 0; k < 16; ++k) carry += s_w[k];
-    }
-    if (threadIdx.x == 0) out[P] = carry;
 }
 
 // the sorted slots as the columns of the four tables (table t holds the sorted positions [base[t], base[t + 1]))

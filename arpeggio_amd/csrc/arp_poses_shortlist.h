@@ -14,7 +14,7 @@
 //                   sorted order (or the caller's list); a candidate below min_score has length 0 in every table — the scores
 //                   are sorted, so those are a suffix.  Nothing filtered: the difference of the source's pose_off; filtered:
 //                   64 records a step, counted by ballot / popcount.  Row 0 also writes pose, score and the two summary rows.
-//   k_psl_offsets   block t: exclusive prefix of table t's lengths with a running carry (k_poses_offsets' scan) -> off[t][.],
+//   k_psl_offsets   block t: exclusive prefix of table t's lengths with a running carry (scan_round, arp_runs.h) -> off[t][.],
 //                   the total into the word block; block 0 counts the kept candidates: K.
 //   k_psl_gather    grid (x, 5), a wave per (chosen pose r, table t): the pose's segment of the source, 64 records a step, to
 //                   off[t][r] onwards; filtered: the position is the running count plus the ballot's prefix, so the order inside
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void k_psl_lengths(PslArgs A) {
 __global__ __launch_bounds__(1024) void k_psl_offsets(PslArgs A) {
     __shared__ unsigned long long s_w[16];
     __shared__ unsigned int s_kept;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = (int)blockIdx.x;
+    const int t = (int)blockIdx.x;
     const unsigned long long* const len = A.len + (long long)t * A.ncand;
     unsigned long long* const out = A.off + (long long)t * ((long long)A.ncand + 1);
     if (threadIdx.x == 0) s_kept = 0u;
@@ -238,19 +238,8 @@ __global__ __launch_bounds__(1024) void k_psl_offsets(PslArgs A) {
             long long score;
             kept += psl_candidate(A, r, &p, &score) ? 1u : 0u;
         }
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long u = __shfl_up(incl, d);
-            if (lane >= d) incl += u;
-        }
-        __syncthreads();      // (s_w: read in the round before)
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < wv; ++k) before += s_w[k];
-        if (r < A.ncand) out[r] = before + incl - v;
-        for (int k = 0; k < 16; ++k) carry += s_w[k];
+        const unsigned long long before = scan_round(v, s_w, carry);
+        if (r < A.ncand) out[r] = before;
     }
     if (threadIdx.x == 0) {
         out[A.ncand] = carry;

@@ -6,6 +6,8 @@
 //   k_runs_scan    one block: exclusive prefix of those counts over the tiles; their sum U = rows of the table
 //   (the host reads U — the one wait — and sizes the table)
 //   k_runs_starts  block t: row_start[prefix[t] + rank in the tile] = position of the run's first record
+//   scan_round     a round of 1024 values of a prefix sum with a running carry: the offsets kernels of the pose results
+//                  (arp_poses.h, arp_poses_shortlist.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +33,27 @@ __device__ __forceinline__ float payload_distance(unsigned long long v) { return
 __device__ __forceinline__ uint32_t payload_sift(unsigned long long v) { return (uint32_t)(v >> 32) & 0x7FFFu; }
 __device__ __forceinline__ uint32_t payload_type(unsigned long long v) { return (uint32_t)(v >> TABLE_TYPE_SHIFT) & 7u; }
 __device__ __forceinline__ uint32_t payload_class(unsigned long long v) { return (uint32_t)(v >> TABLE_CLASS_SHIFT) & 7u; }
+
+// One round of a block-wide prefix sum over more values than the block has threads: the 1024 threads (16 waves) of a block each
+// bring one value of the round, get the sum of everything before it — the rounds before included, through `carry`, which every
+// thread keeps and which ends as the sum of all rounds — and go on to the next round.  Every thread of the block calls it, the
+// same number of times.  s_w is the caller's: 16 words of shared memory that nothing else uses between the rounds.
+__device__ __forceinline__ unsigned long long scan_round(unsigned long long v, unsigned long long* s_w, unsigned long long& carry) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long u = __shfl_up(incl, d);
+        if (lane >= d) incl += u;
+    }
+    __syncthreads();      // (s_w: read in the round before)
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    unsigned long long before = carry;
+    for (int k = 0; k < wv; ++k) before += s_w[k];
+    for (int k = 0; k < 16; ++k) carry += s_w[k];
+    return before + incl - v;
+}
 
 // What finding the runs of a sorted key array needs: a run = consecutive records with equal key >> shift.  A record whose
 // key >> shift is all ones (~0ull >> shift) never BEGINS a run: no key of the persistence table has 64 bits, and the
