@@ -53,6 +53,7 @@ SYMBOLS = (
     'arp_poses_fingerprints_launch', 'arp_poses_fingerprints_fetch', 'arp_poses_fingerprints_info',
     'arp_poses_fingerprints_planes_launch',
     'arp_poses_shortlist_launch', 'arp_poses_shortlist_fetch', 'arp_poses_shortlist_planes_fetch', 'arp_poses_shortlist_info',
+    'arp_poses_clusters_launch', 'arp_poses_clusters_fetch', 'arp_poses_clusters_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -67,6 +68,8 @@ POSEFP_ALL_PLANES = 29           # ARP_POSEFP_ALL_PLANES: the SIFt bits and the 
 # ... their shortlist (ARP_SHORTLIST_*)
 SHORTLIST_LIST, SHORTLIST_SUMMARY, SHORTLIST_TANIMOTO, SHORTLIST_TABLES, SHORTLIST_MAX_WEIGHT = 0, 1, 2, 5, 1 << 24
 INT64_MIN = -(1 << 63)
+# ... their clusters (ARP_POSECL_*; the rounds enqueued between two waits of arp_poses_clusters_launch)
+POSECL_MAX_CLUSTERS, POSECL_ROUNDS_PER_WAIT = 4096, 64
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -257,6 +260,9 @@ def load():
     L.arp_poses_shortlist_fetch.argtypes = [vp, i64, i64] + [vp] * 10 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_poses_shortlist_planes_fetch.argtypes = [vp, C.c_int, i64, i64] + [vp] * 10 + [C.POINTER(i64)]
     L.arp_poses_shortlist_info.argtypes = [vp, vp]
+    L.arp_poses_clusters_launch.argtypes = [vp, vp, i64, i64, C.c_uint64, i64, vp]
+    L.arp_poses_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 6 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_poses_clusters_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1162,6 +1168,37 @@ class Context:
         d.update(launches=int(info[6]), kind=int(info[7]))
         return d
 
+    def poses_clusters(self, threshold_q32, *, order=None, skip=0, max_clusters=256):
+        """Leader clustering of the poses of the resident fingerprint result (``poses_fingerprints``, either entry) by the Tanimoto
+        similarity of their fingerprints, on the device (arp_poses_clusters_*; ``arpeggio_amd.pose_clusters``).  Position m names
+        pose ``order[m]`` (int32 ids in [0, P), repeats allowed) or, without ``order``, pose ``skip + m``.  Walking the positions,
+        a pose whose similarity (32 fractional bits) to some leader's pose reaches ``threshold_q32``
+        (``pose_clusters.threshold_q32``) joins the FIRST such leader; otherwise it becomes the next leader while there are
+        fewer than ``max_clusters`` (at most ``POSECL_MAX_CLUSTERS``), and stays unassigned after that.  Returns a dict: ``pose``
+        int32 [M]; ``cluster`` int32 [M], -1 when unassigned; ``similarity`` int64 [M], to its own leader, 2^32 for a leader, -1
+        when unassigned; ``leader`` int32 [C]; ``leader_position`` int32 [C]; ``size`` uint32 [C]; ``threshold_q32``,
+        ``max_clusters``, ``unassigned``.  No record and no bit is copied."""
+        ids = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_clusters_launch(self._h, _p(ids), 0 if ids is None else len(ids), int(skip), int(threshold_q32),
+                                                      int(max_clusters), _p(info)), 'arp_poses_clusters_launch')
+        M, Cn = int(info[0]), int(info[1])
+        out = dict(pose=np.empty(M, np.int32), cluster=np.empty(M, np.int32), similarity=np.empty(M, np.int64), leader=np.empty(Cn, np.int32),
+                   leader_position=np.empty(Cn, np.int32), size=np.empty(Cn, np.uint32))
+        n, m = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.arp_poses_clusters_fetch(self._h, M, Cn, _p(out['pose']), _p(out['cluster']), _p(out['similarity']), _p(out['leader']),
+                                                     _p(out['leader_position']), _p(out['size']), C.byref(n), C.byref(m)), 'arp_poses_clusters_fetch')
+        out.update(threshold_q32=int(info[7]), max_clusters=int(info[3]), unassigned=int(info[2]))
+        return out
+
+    def poses_clusters_info(self):
+        """arp_poses_clusters_info: positions, clusters, unassigned positions, ``max_clusters``, words per pose and the lanes per
+        pose of the round kernel of the resident clusters (zeros while there are none), the launches that did work so far, and
+        the threshold."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_clusters_info(self._h, _p(info)), 'arp_poses_clusters_info')
+        return dict(zip(('positions', 'clusters', 'unassigned', 'max_clusters', 'words', 'lanes', 'launches', 'threshold_q32'), (int(v) for v in info)))
+
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""
         self._keep = blob
@@ -1640,10 +1677,13 @@ class Context:
         self._check(self._L.arp_models_coupling_info(self._h, _p(cp)), 'arp_models_coupling_info')
         fp = np.zeros(8, np.int64)
         self._check(self._L.arp_poses_fingerprints_info(self._h, _p(fp)), 'arp_poses_fingerprints_info')
+        cl = np.zeros(8, np.int64)
+        self._check(self._L.arp_poses_clusters_info(self._h, _p(cl)), 'arp_poses_clusters_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
                     sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
                     posefp_nodes=int(fp[2]), posefp_words=int(fp[4]), posefp_slices=int(fp[5]), posefp_launches=int(fp[6]),
+                    posecl_positions=int(cl[0]), posecl_clusters=int(cl[1]), posecl_launches=int(cl[6]),
                     lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]),
                     couple_rows=int(cp[0]), couple_features=int(cp[1]), couple_tile_pairs=int(cp[2]), couple_launches=int(cp[3]),
                     networks_rows=int(nw[0]), networks_nodes=int(nw[1]), networks_launches=int(nw[2]))

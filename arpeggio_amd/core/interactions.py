@@ -632,6 +632,98 @@ class InteractionComplex:
             raise AttributeError('no pose shortlist yet: call run_pose_shortlist() first')
         return _sl.write_pose_shortlist(wd, self.id, self.pose_shortlist, self.pc, self.component_types)
 
+    def run_pose_clusters(self, user_selections, xyz, h_xyz, interacting_cutoff, vdw_comp, include_sequence_adjacent, threshold=0.5,
+                          by='summary', weights=None, refs_xyz=None, refs_h_xyz=None, contacts=None, interacting_entities=None, level='residue',
+                          classes=(), max_clusters=256, records=False):
+        """Extension beside the mirror: many poses of a ligand grouped into binding modes ON THE DEVICE — leader clustering in rank
+        order by the Tanimoto similarity of their interaction fingerprints; no record and no fingerprint is copied.  Selection,
+        ``xyz``, ``h_xyz`` and the three parameters are those of ``run_poses``; ``refs_xyz`` / ``refs_h_xyz`` (default: the
+        resident coordinates), ``contacts``, ``interacting_entities``, ``level`` and ``classes`` those of
+        ``run_pose_fingerprints``.  The poses are walked from best to worst: ``by='summary'`` ranks by ``weights``
+        (``pose_shortlist.weights``; default: one per record) times the summary slots, ``by='tanimoto'`` by the best similarity
+        to a reference pose, ``by='input'`` keeps the order given; a tie goes to the lower pose id.  A pose whose similarity to
+        an earlier leader is at least ``threshold`` (a float in [0, 1], ``pose_clusters.threshold_q32``) joins the first such
+        leader, otherwise it leads a new cluster — at most ``max_clusters``, the poses after that stay unassigned.  One launch
+        of references ++ poses (``Context.poses_summary``, ``poses_planes_summary`` with ``classes``,
+        ``poses_fingerprints``), the rank order on the host from what those calls copied anyway, ``Context.poses_clusters``.
+        There is no ``chunk``: a clustering does not decompose over launches (a pose's leader may sit in any other chunk), so
+        references and poses together are at most ``_capi.POSES_MAX_POSES``.  Returns the dict ``arpeggio_amd.pose_clusters``
+        describes, pose ids in the caller's numbering, with ``by`` and ``n_refs`` (also kept in ``self.pose_clusters``);
+        ``records=True`` adds ``'records'``: the atom-atom records of the leaders as a shortlist
+        (``Context.poses_shortlist('list', ...)``), ``pose`` in the caller's numbering."""
+        from .. import _capi, contact_filter, poses as _poses, pose_clusters as _cl, pose_fingerprints as _fp, pose_shortlist as _sl
+        if by not in ('summary', 'tanimoto', 'input'):
+            raise ValueError(f"run_pose_clusters: by must be 'summary', 'tanimoto' or 'input', not {by!r}")
+        if level not in _fp.LEVELS:
+            raise ValueError(f"run_pose_clusters: level must be 'residue' or 'atom', not {level!r}")
+        thr = _cl.threshold_q32(threshold)
+        if not 1 <= int(max_clusters) <= _cl.MAX_CLUSTERS:
+            raise ValueError(f'run_pose_clusters: max_clusters must be 1 ... {_cl.MAX_CLUSTERS}')
+        mask = _fp.planes(contacts, classes)
+        with_classes = (mask >> _fp.N_PLANES) != 0
+        if with_classes and level != 'residue':
+            raise ValueError("run_pose_clusters: the ring / amide class planes exist at level='residue' only")
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        if self._ctx is None:
+            self.initialize()
+        pc, ctx = self.pc, self._ctx
+        if isinstance(user_selections, np.ndarray):
+            idx = np.unique(user_selections.astype(np.int64))
+        else:
+            idx = utils.selection_parser(user_selections, pc) if user_selections else np.zeros(0, np.int64)
+        if idx.size == 0:
+            raise AttributeError('Selection must not be empty.')
+        sel = np.zeros(pc.n_atoms, np.uint8)
+        sel[idx] = 1
+        atoms, rows = _poses.movable(pc, idx)
+        x = np.ascontiguousarray(xyz, np.float32)
+        h = np.zeros((len(x), 0, 3)) if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64)
+        if refs_xyz is None:
+            rx = np.asarray(pc.xyz, np.float32)[atoms][None]
+            rh = np.asarray(pc.h_xyz, np.float64).reshape(-1, 3)[rows][None]
+        else:
+            rx = np.ascontiguousarray(refs_xyz, np.float32)
+            rh = np.zeros((len(rx), 0, 3)) if refs_h_xyz is None else np.ascontiguousarray(refs_h_xyz, np.float64)
+        Q = len(rx)
+        if not 1 <= Q <= _fp.MAX_REFS:
+            raise ValueError(f'run_pose_clusters: 1 ... {_fp.MAX_REFS} reference poses')
+        if len(x) < 1:
+            raise ValueError('run_pose_clusters: no pose given')
+        if Q + len(x) > _capi.POSES_MAX_POSES:
+            raise ValueError('run_pose_clusters: references and poses together exceed one launch (a clustering does not decompose over launches)')
+        if x.shape[1:] != rx.shape[1:] or h.shape[1:] != rh.shape[1:]:
+            raise ValueError('run_pose_clusters: the references and the poses must have the same atoms and hydrogen rows')
+        if by == 'summary' and weights is None:
+            weights = _sl.weights(atom_atom={'records': 1})
+        ctx.set_selection(sel)
+        if with_classes:
+            ctx.set_plane_atoms(pc)
+        both = np.concatenate([rx, x])
+        summary = ctx.poses_summary(both, np.concatenate([rh, h]), interacting_cutoff, vdw_comp, include_sequence_adjacent)
+        planes_summary = ctx.poses_planes_summary(both) if with_classes else None
+        f = ctx.poses_fingerprints(mask, ctype_mask, by_residue=level == 'residue', n_refs=Q)
+        if by == 'summary':
+            if planes_summary is None and np.asarray(weights).reshape(-1)[16:].any():
+                raise ValueError('run_pose_clusters: a weight on a planes slot needs classes (the ring and amide contacts)')
+            rank = _sl.order(_sl.scores('summary', summary=summary, planes_summary=planes_summary, w=weights), Q)
+        elif by == 'tanimoto':
+            rank = _sl.order(_sl.tanimoto_q32(f['count'], f['cross'], Q, -1), Q)
+        else:
+            rank = np.arange(Q, Q + len(x), dtype=np.int64)
+        out = _cl.shift(ctx.poses_clusters(thr, order=rank, max_clusters=int(max_clusters)), -Q)
+        out.update(by=by, n_refs=Q, level=level)
+        if records:
+            out['records'] = _sl.shift(ctx.poses_shortlist('list', pose_ids=np.asarray(out['leader']) + Q), -Q)
+        self.pose_clusters = out
+        return out
+
+    def write_pose_clusters(self, wd):
+        """'<id>.poseclusters': the clusters of the last ``run_pose_clusters`` as CSV, one row per position (``pose_clusters.write_csv``)."""
+        from .. import pose_clusters as _cl
+        if getattr(self, 'pose_clusters', None) is None:
+            raise AttributeError('no pose clusters yet: call run_pose_clusters() first')
+        return _cl.write_pose_clusters(wd, self.id, self.pose_clusters)
+
     # ---- the legacy CSV tables (I:135-170, 349-366, 405-466) ----
     def write_atom_types(self, wd):
         """I:135-149: '<id>_atomtypes.csv'."""

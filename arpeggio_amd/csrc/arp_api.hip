@@ -42,6 +42,7 @@
 #include "arp_poses_planes.h"
 #include "arp_poses_fingerprints.h"
 #include "arp_poses_shortlist.h"
+#include "arp_poses_clusters.h"
 #include "arp_blob.h"
 
 namespace {
@@ -357,6 +358,24 @@ struct ShortlistResult {
     }
 };
 
+// the leader clustering of the resident fingerprint result (arp_poses_clusters_launch, arp_poses_clusters.h): the leaders' positions
+// round by round (`next`), the per-position and per-cluster arrays, the uploaded order (or none) and the word block of the last
+// wait.  The fingerprint result is read only while the launch runs: valid while the poses result is; one made from a fingerprint
+// with class planes (`classes`) goes with the poses-planes result as well
+struct ClustersResult {
+    DevBuf<uint32_t> next, size;
+    DevBuf<int> order, pose, cluster, leader, leader_position;
+    DevBuf<long long> similarity;
+    DevBuf<unsigned long long> words;
+    int64_t M = 0, C = 0, unassigned = 0, max_clusters = 0, W = 0, lanes = 0, launches = 0;
+    uint64_t threshold = 0;
+    bool valid = false, classes = false;
+    void release() {
+        next.release(); size.release(); order.release(); pose.release(); cluster.release(); leader.release(); leader_position.release();
+        similarity.release(); words.release(); valid = false;
+    }
+};
+
 // the ring / amide contacts of ligand poses (arp_poses_planes_launch, arp_poses_planes.h): the atoms of the resident rings and
 // amides (arp_set_plane_atoms), the movable set's tables (made once per structure, selection and plane atoms), an all-atom 6 A
 // grid of its own by local id (the static order of the passes is left alone), the per-block lists, the records and their sort
@@ -632,6 +651,7 @@ struct arp_ctx {
     PosesResult poses;                    // arp_poses_contacts_launch
     PoseFpResult posefp;                  // arp_poses_fingerprints_launch
     ShortlistResult shortlist;            // arp_poses_shortlist_launch
+    ClustersResult clusters;              // arp_poses_clusters_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -835,11 +855,13 @@ void void_results(arp_ctx* c, unsigned lost) {
 // The same rule for the results of the ligand-pose family (DESIGN.md 5o ... 5s), which read no bag: `lost` names what was
 // replaced or is about to be — the structure, the selection, or one of the rows below itself.  A row goes when it
 // is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The fingerprint and the
-// shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight.
+// shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight; the
+// clusters read the fingerprint result only while their launch runs, so they stand behind what THAT was made from, not behind it.
 // A launch names its own result here before it writes it, and sets it valid again at its end.
 enum : unsigned {
     POSE_STRUCTURE = 1u << 0, POSE_SELECTION = 1u << 1, POSE_PLANE_ATOMS = 1u << 2, POSE_MOVABLE = 1u << 3, POSE_CONTACTS = 1u << 4,
-    POSE_PLANES = 1u << 5, POSE_FINGERPRINT = 1u << 6, POSE_SHORTLIST = 1u << 7
+    POSE_PLANES = 1u << 5, POSE_FINGERPRINT = 1u << 6, POSE_SHORTLIST = 1u << 7,
+    POSE_CLUSTERS = 1u << 8
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -849,7 +871,8 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->pplanes.valid, POSE_PLANES, POSE_MOVABLE},
         {&c->poses.valid, POSE_CONTACTS, inputs},       // (its movable tables go by static_epoch / sel_epoch)
         {&c->posefp.valid, POSE_FINGERPRINT, POSE_CONTACTS | (c->posefp.classes ? POSE_PLANES : 0u)},
-        {&c->shortlist.valid, POSE_SHORTLIST, POSE_CONTACTS | (c->shortlist.planes ? POSE_PLANES : 0u)}};
+        {&c->shortlist.valid, POSE_SHORTLIST, POSE_CONTACTS | (c->shortlist.planes ? POSE_PLANES : 0u)},
+        {&c->clusters.valid, POSE_CLUSTERS, POSE_CONTACTS | (c->clusters.classes ? POSE_PLANES : 0u)}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -906,9 +929,9 @@ enum : unsigned {
 //   with everything selected (I:1395) and no whole-structure assertion.
 // results: the atom-atom bag and the four ring / amide bags of the last pass; the fetches refuse until the next launch.  What
 //   is made from them on the device goes with them by the one rule of void_results.
-// pose results: the poses result, the poses-planes result with its movable set-up, the fingerprint and the shortlist read the
-//   structure and the selection, no bag; plane atoms (arp_set_plane_atoms) name atoms of the structure and stay through a new
-//   selection.  void_pose_results is the one statement of what each of them reads.
+// pose results: the poses result, the poses-planes result with its movable set-up, the fingerprint, the shortlist and the
+//   clusters read the structure and the selection, no bag; plane atoms (arp_set_plane_atoms) name atoms of the structure and
+//   stay through a new selection.  void_pose_results is the one statement of what each of them reads.
 // model mode: the resident structure is the F models of the kept topology (arp_models_planes answers); any other structure
 //   input ends it — a blob, a setter, a batch — while a selection keeps it.  (m) arp_set_models uploads and validates the
 //   expanded blob (IN_EVERYTHING), declares the partition (IN_BATCH) and then writes the ring residues of every model, which
@@ -2481,6 +2504,7 @@ void arp_destroy(arp_ctx* c) {
     c->pplanes.release();
     c->posefp.release();
     c->shortlist.release();
+    c->clusters.release();
     c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -6219,6 +6243,134 @@ int arp_poses_shortlist_planes_fetch(arp_ctx* c, int table, int64_t cap_poses, i
 int arp_poses_shortlist_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     shortlist_info(c->shortlist, info);
+    return ARP_OK;
+}
+
+// ---- pose clusters (arp_poses_clusters.h): the resident fingerprint result -> leaders and members
+// The fingerprint result is read while the launch runs (bits, count); only this result's own buffers are written.  The rounds are
+// enqueued back to back, POSECL_ROUNDS_PER_WAIT at a time: after such a group one word — the next leader's position — comes back
+// through the stage, and a sentinel there ends the rounds (no position is left).  Up to that many rounds there is one wait: the
+// word block of k_pcl_finish (C, the unassigned count).
+static_assert(PCL_MAX_CLUSTERS == ARP_POSECL_MAX_CLUSTERS, "arp_poses_clusters.h names the header's constant");
+const int64_t POSECL_ROUNDS_PER_WAIT = 64;
+
+static void clusters_info(const ClustersResult& S, int64_t info[8]) {
+    const int64_t v[8] = {S.M, S.C, S.unassigned, S.max_clusters, S.W, S.lanes, S.launches, (int64_t)S.threshold};
+    for (int q = 0; q < 8; ++q) info[q] = (S.valid || q == 6) ? v[q] : 0;
+}
+
+int arp_poses_clusters_launch(arp_ctx* c, const int32_t* order, int64_t n_order, int64_t skip, uint64_t threshold_q32, int64_t max_clusters,
+                              int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_poses_clusters_launch: ";
+    ClustersResult& S = c->clusters;
+    const PoseFpResult& F = c->posefp;
+    // ---- the refusals: none of them touches a resident result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    CHK(need_poses_result(c, fn));
+    if (!F.valid) FAIL(c, ARP_E_ARG, fn + "no fingerprint result (arp_poses_fingerprints_launch)");
+    if (F.P != c->poses.P) FAIL(c, ARP_E_ARG, fn + "the fingerprint result and the poses result differ in P");
+    const int64_t P = F.P;
+    if (threshold_q32 > PCL_ONE_Q32) FAIL(c, ARP_E_ARG, fn + "threshold_q32 must be 0 ... 2^32 (1.0)");
+    if (max_clusters < 1 || max_clusters > ARP_POSECL_MAX_CLUSTERS) FAIL(c, ARP_E_ARG, fn + "max_clusters must be 1 ... ARP_POSECL_MAX_CLUSTERS");
+    if (order) {
+        if (skip != 0) FAIL(c, ARP_E_ARG, fn + "an order takes skip = 0 (the list names the positions)");
+        if (n_order < 1 || n_order > ARP_POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "n_order must be 1 ... ARP_POSES_MAX_POSES");
+        for (int64_t q = 0; q < n_order; ++q)
+            if (order[q] < 0 || order[q] >= P) FAIL(c, ARP_E_ARG, fn + "order has an id outside [0, P)");
+    } else {
+        if (n_order != 0) FAIL(c, ARP_E_ARG, fn + "n_order must be 0 without an order");
+        if (skip < 0 || skip >= P) FAIL(c, ARP_E_ARG, fn + "skip must be in [0, P)");
+    }
+    // ---- from here on the previous clusters are gone
+    void_pose_results(c, POSE_CLUSTERS);
+    S.classes = F.classes;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t M = order ? n_order : P - skip, W = F.U > 0 ? F.W : 0;
+    const size_t mc = (size_t)max_clusters;
+    HIPCHK(c, S.words.reserve(4));
+    HIPCHK(c, S.next.reserve(mc + 1));
+    HIPCHK(c, S.size.reserve(mc));
+    HIPCHK(c, S.leader.reserve(mc));
+    HIPCHK(c, S.leader_position.reserve(mc));
+    HIPCHK(c, S.pose.reserve((size_t)M));
+    HIPCHK(c, S.cluster.reserve((size_t)M));
+    HIPCHK(c, S.similarity.reserve((size_t)M));
+    PclArgs A{};
+    A.bits = W > 0 ? F.bits.p : nullptr;      // (U = 0: the matrix was never allocated)
+    A.count = F.count.p; A.W = W;
+    A.skip = (int)skip; A.M = (int)M;
+    A.threshold = threshold_q32; A.max_clusters = (int)max_clusters;
+    A.g = pcl_group_width(W); A.g_log2 = __builtin_ctz((unsigned)A.g);
+    A.next = S.next.p; A.pose = S.pose.p; A.cluster = S.cluster.p; A.similarity = S.similarity.p;
+    A.leader = S.leader.p; A.leader_position = S.leader_position.p; A.size = S.size.p; A.words = S.words.p;
+    if (order) {
+        CHK(upload_async(c, S.order, (const int*)order, (size_t)n_order));      // (the wait below is before the caller's array goes away)
+        A.order = S.order.p;
+    }
+    // ---- nothing assigned: cluster = -1, similarity = -1, every next but the first the sentinel
+    HIPCHK(c, hipMemsetAsync(S.words.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.size.p, 0, mc * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.cluster.p, 0xFF, (size_t)M * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.similarity.p, 0xFF, (size_t)M * sizeof(long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.next.p, 0xFF, (mc + 1) * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.next.p, 0, sizeof(uint32_t), c->stream));
+    // ---- the rounds
+    const int64_t rounds = std::min(max_clusters, M);
+    const int per_block = PCL_THREADS / A.g;
+    const dim3 grid(nblocks(M, per_block, 16 * std::max(c->num_cu, 1)));
+    int64_t enqueued = 0;
+    while (enqueued < rounds) {
+        const int64_t end = std::min(rounds, enqueued + POSECL_ROUNDS_PER_WAIT);
+        for (; enqueued < end; ++enqueued) hipLaunchKernelGGL(k_pcl_round, grid, dim3(PCL_THREADS), 0, c->stream, A, (int)enqueued);
+        CHK(check_launch(c, (fn + "rounds").c_str()));
+        if (enqueued < rounds) {
+            CHK(stage_copy(c, S.next.p + enqueued, sizeof(uint32_t)));
+            uint32_t next_leader;
+            memcpy(&next_leader, c->table_stage, sizeof(next_leader));
+            if (next_leader == PCL_SENTINEL) break;
+        }
+    }
+    hipLaunchKernelGGL(k_pcl_finish, dim3(nblocks(M, PCL_THREADS, 256)), dim3(PCL_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "finish").c_str()));
+    CHK(stage_copy(c, S.words.p, 4 * sizeof(unsigned long long)));
+    unsigned long long h[4];
+    memcpy(h, c->table_stage, sizeof(h));
+    ++S.launches;
+    if (h[PCL_W_CLUSTERS] < 1 || h[PCL_W_CLUSTERS] > (unsigned long long)rounds || h[PCL_W_UNASSIGNED] > (unsigned long long)M)
+        FAIL(c, ARP_E_HIP, fn + "cluster count out of range");
+    S.M = M; S.C = (int64_t)h[PCL_W_CLUSTERS]; S.unassigned = (int64_t)h[PCL_W_UNASSIGNED]; S.max_clusters = max_clusters;
+    S.W = W; S.lanes = A.g; S.threshold = threshold_q32;
+    S.valid = true;
+    clusters_info(S, info);
+    return ARP_OK;
+}
+
+int arp_poses_clusters_fetch(arp_ctx* c, int64_t cap_positions, int64_t cap_clusters, int32_t* pose, int32_t* cluster, int64_t* similarity,
+                             int32_t* leader, int32_t* leader_position, uint32_t* size, int64_t* n_positions, int64_t* n_clusters) {
+    if (!c || !n_positions || !n_clusters) return ARP_E_ARG;
+    const ClustersResult& S = c->clusters;
+    if (!S.valid)      // (voided wherever the poses result is; with the poses-planes result when the fingerprint had class planes)
+        FAIL(c, ARP_E_ARG, "arp_poses_clusters_fetch: no result (arp_poses_clusters_launch; a result it was made from was replaced or an input or the selection changed since)");
+    *n_positions = S.M;
+    *n_clusters = S.C;
+    if ((pose || cluster || similarity) && cap_positions < S.M) FAIL(c, ARP_E_CAPACITY, "arp_poses_clusters_fetch: output buffers too small (cap_positions < *n_positions)");
+    if ((leader || leader_position || size) && cap_clusters < S.C) FAIL(c, ARP_E_CAPACITY, "arp_poses_clusters_fetch: output buffers too small (cap_clusters < *n_clusters)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t M = (size_t)S.M, C = (size_t)S.C;
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, pose, S.pose.p, M * sizeof(int32_t));
+    want_piece(pieces, cluster, S.cluster.p, M * sizeof(int32_t));
+    want_piece(pieces, similarity, S.similarity.p, M * sizeof(int64_t));
+    want_piece(pieces, leader, S.leader.p, C * sizeof(int32_t));
+    want_piece(pieces, leader_position, S.leader_position.p, C * sizeof(int32_t));
+    want_piece(pieces, size, S.size.p, C * sizeof(uint32_t));
+    return stage_fetch(c, pieces);
+}
+
+int arp_poses_clusters_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    clusters_info(c->clusters, info);
     return ARP_OK;
 }
 

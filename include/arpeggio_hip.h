@@ -1248,6 +1248,52 @@ int arp_poses_shortlist_planes_fetch(arp_ctx* ctx, int table, int64_t cap_poses,
                                      int32_t* second, void* v0, void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2,
                                      int64_t* count);
 int arp_poses_shortlist_info(arp_ctx* ctx, int64_t info[8]);
+/* Pose clusters: leader clustering (sphere exclusion in rank order) of the poses of the resident fingerprint result by the
+ * Tanimoto similarity of their fingerprints, on the device (csrc/arp_poses_clusters.h).  No P x P matrix is made:
+ * at most positions x clusters row products, so it works at ARP_POSES_MAX_POSES poses.
+ *
+ * SOURCE: the resident fingerprint result, from either entry, at any level and with any planes: P, U, NP, W = NP ceil(U / 64),
+ *   bits [P][W] and count [P].  Nothing of it, or of any other resident result, is written.
+ * POSITIONS: order == NULL: position m names pose skip + m, M = P - skip, 0 <= skip < P (the leading `skip` poses are references
+ *   and take no part); n_order must be 0.  order != NULL: M = n_order, 1 <= M <= ARP_POSES_MAX_POSES, position m names pose
+ *   order[m]; every id in [0, P), checked on the host before anything is touched; repeats allowed; skip must be 0.
+ * SIMILARITY of poses a and b (the arithmetic of ARP_SHORTLIST_TANIMOTO): t = sum over the W words of popcount(bits[a][w] &
+ *   bits[b][w]), u = count[a] + count[b] - t, q(a, b) = (u == 0) ? 2^32 : floor(t 2^32 / u) in unsigned 64-bit arithmetic
+ *   (t < 2^32: the product fits); 0 / 0 is 1.0.  a and b are SIMILAR when q >= threshold_q32, 0 <= threshold_q32 <= 2^32.
+ * CLUSTERING, defined sequentially: walk the positions m = 0 ... M - 1 and keep the list of leaders made so far.  A position
+ *   whose pose is similar to some leader's pose joins the FIRST such leader in leader order (not the most similar one);
+ *   otherwise, while fewer than max_clusters leaders exist (1 <= max_clusters <= ARP_POSECL_MAX_CLUSTERS), it becomes the next
+ *   leader; otherwise it stays unassigned.  Position 0 is always leader 0.
+ * RESULT: pose int32 [M], the pose of each position; cluster int32 [M], the index in leader order, -1 when unassigned;
+ *   similarity int64 [M], q to its own leader's pose, 2^32 for a leader, -1 when unassigned; leader int32 [C], the leaders' pose
+ *   ids; leader_position int32 [C], their positions, strictly ascending; size uint32 [C], the members per cluster, the leader
+ *   included.  Sum of size + unassigned = M.  Everything is an integer: the result is a pure function of the arguments and the
+ *   fingerprint result.  U = 0 (no feature in any pose) gives q = 2^32 everywhere: one cluster of M members.
+ *
+ * arp_poses_clusters_launch: info[8] as arp_poses_clusters_info gives it.  One launch per round, enqueued back to back on the
+ *   context's stream, 64 at a time: after such a group one word (the next leader's position) is read back and the rounds end
+ *   when no position is left; up to 64 rounds there is the one wait for C and the unassigned count.  Refusals are ARP_E_ARG with
+ *   the cause named, and none of them touches a resident result: a pass not waited for; no poses result; no fingerprint result;
+ *   the fingerprint's P is not the poses result's; threshold_q32 > 2^32; max_clusters outside [1, 4096]; skip out of range; an
+ *   order with skip != 0; n_order out of range; an id outside [0, P); order == NULL with n_order != 0.  Every successful launch
+ *   remakes the result.
+ *   The launch reads the fingerprint result only while it runs: a later fingerprint launch with other arguments does not void
+ *   the clusters.  They are void exactly when the poses result is void or replaced (a new arp_poses_contacts_launch,
+ *   arp_set_selection, a new structure, models or a batch); when the fingerprint they were made from had class planes also when
+ *   the poses-planes result is (arp_poses_planes_launch, arp_set_plane_atoms).  Making them voids nothing.
+ * arp_poses_clusters_fetch: ANY pointer but n_positions and n_clusters may be NULL.  *n_positions = M, *n_clusters = C.
+ *   ARP_E_CAPACITY when a per-position array (pose, cluster, similarity) is asked for and cap_positions < M, or a per-cluster
+ *   array (leader, leader_position, size) and cap_clusters < C.  ARP_E_ARG: no valid result.  Every piece goes through the
+ *   page-locked stage in one wait.
+ * arp_poses_clusters_info: info[0] = M, [1] = C, [2] = unassigned, [3] = max_clusters, [4] = W, [5] = lanes per pose of the round
+ *   kernel, [6] = launches that did work so far, [7] = threshold_q32.  All but [6] are 0 while there is no result. */
+#define ARP_POSECL_MAX_CLUSTERS 4096
+int arp_poses_clusters_launch(arp_ctx* ctx, const int32_t* order, int64_t n_order, int64_t skip, uint64_t threshold_q32,
+                              int64_t max_clusters, int64_t info[8]);
+int arp_poses_clusters_fetch(arp_ctx* ctx, int64_t cap_positions, int64_t cap_clusters, int32_t* pose, int32_t* cluster,
+                             int64_t* similarity, int32_t* leader, int32_t* leader_position, uint32_t* size, int64_t* n_positions,
+                             int64_t* n_clusters);
+int arp_poses_clusters_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
