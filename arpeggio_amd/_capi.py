@@ -171,10 +171,9 @@ def load():
     L.arp_atom_contacts.argtypes = [vp, dbl, dbl, i32, i64, vp, vp, vp, vp, vp, C.POINTER(i64)]
     L.arp_atom_contacts_sort.argtypes = [vp]
     L.arp_fetch_packed.argtypes = [vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
-    L.arp_atom_plane.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
-    L.arp_plane_plane.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
-    L.arp_group_group.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
-    L.arp_group_plane.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]
+    for name in tables.PLANE_BAGS:      # launch + fetch, and fetch alone: cap, one pointer per column, count
+        for fn in (getattr(L, f'arp_{name}'), getattr(L, f'arp_{name}_fetch')):
+            fn.argtypes = [vp, i64] + [vp] * len(tables.bag_columns(name)) + [C.POINTER(i64)]
     L.arp_set_ownership.argtypes = [vp, vp, vp]
     L.arp_set_selection.argtypes = [vp, vp]
     L.arp_atom_accumulators.argtypes = [vp, vp, vp]
@@ -1008,14 +1007,11 @@ class Context:
     @staticmethod
     def _plane_table_buffers(name, k, n_off):
         """A ring / amide table of ``k`` records with ``pose_off`` [n_off], and its columns as the pointers of a plane fetch (two
-        ids, four values, three bytes: ``poses.PLANE_COLUMNS``; the columns the table does not have are null)."""
-        from . import poses as _poses
-        ids, vals, byts, vdt = _poses.PLANE_COLUMNS[name]
-        tab = {c: np.empty(k, np.int32) for c in ids}
-        tab.update({c: np.empty(k, vdt) for c in vals})
-        tab.update({c: np.empty(k, np.uint8) for c in byts})
+        ids, four values, three bytes: ``tables.BAGS``; the columns the table does not have are null)."""
+        b = tables.BAGS[name]
+        tab = {c: np.empty(k, dt) for c, dt, _ in tables.bag_columns(name)}
+        args = [_p(tab[c]) for c, _ in b.ids] + [_p(tab[c]) for c in b.vals] + [None] * (4 - len(b.vals)) + [_p(tab[c]) for c in b.bytes] + [None] * (3 - len(b.bytes))
         tab['pose_off'] = np.empty(n_off, np.uint64)
-        args = [_p(tab[c]) for c in ids] + [_p(tab[c]) for c in vals] + [None] * (4 - len(vals)) + [_p(tab[c]) for c in byts] + [None] * (3 - len(byts))
         return tab, args
 
     def poses_planes(self, xyz):
@@ -1453,17 +1449,7 @@ class Context:
         self._check(self._L.arp_atom_contacts_sort(self._h), 'arp_atom_contacts_sort')
 
     # columns of the four ring / amide bags inside a packed fetch: (key, slot q of arp_fetch_packed's offsets, dtype)
-    _PACKED_BAGS = (
-        ('plane_plane', (('bgn', 0, np.int32), ('end', 1, np.int32), ('dist', 2, np.float64), ('dihedral', 3, np.float64),
-                         ('theta_bgn', 4, np.float64), ('theta_end', 5, np.float64), ('type1', 9, np.uint8), ('type2', 10, np.uint8),
-                         ('ctype', 11, np.uint8))),
-        ('atom_plane', (('atom', 0, np.int32), ('ring', 1, np.int32), ('dist', 2, np.float64), ('theta', 3, np.float64),
-                        ('mask', 9, np.uint8), ('ctype', 10, np.uint8))),
-        ('group_group', (('bgn', 0, np.int32), ('end', 1, np.int32), ('dist', 6, np.float32), ('dihedral', 7, np.float32),
-                         ('theta', 8, np.float32), ('ctype', 9, np.uint8))),
-        ('group_plane', (('amide', 0, np.int32), ('ring', 1, np.int32), ('dist', 2, np.float64), ('dihedral', 3, np.float64),
-                         ('theta', 4, np.float64), ('ctype', 9, np.uint8))),
-    )
+    _PACKED_BAGS = tuple((name, tuple((key, q, dt) for key, dt, q in tables.bag_columns(name))) for name in tables.PACKED_ORDER)
 
     def fetch_packed(self, buf=None, sort_bags=True):
         """All five result bags of the last pass with ONE device-to-host copy (arp_fetch_packed): the atom-atom bag in
@@ -1570,9 +1556,7 @@ class Context:
     # ---- ring / amide contacts ----
     def pinned_bag_buffers(self, name, capacity):
         """Page-locked result buffers for ``fetch_bag(name, out=...)`` (allocate once, reuse for every structure)."""
-        mk, keys, order = self._BAGS[name]
-        cap = max(int(capacity), 64)
-        return [pinned_empty(cap, a.dtype) for a in mk(1)]
+        return tables.bag_buffers(name, max(int(capacity), 64), pinned_empty)
 
     def fetch_bag(self, name, sort=True, out=None):
         """Fetch one of the ring/amide bags left in HBM by run_launch (no re-computation).  ``out``: buffers from
@@ -1608,60 +1592,30 @@ class Context:
             k = int(cnt.value)
             return [a[:k] for a in arrs]
 
-    def atom_plane(self):
-        def mk(cap):
-            return [np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64), np.empty(cap, np.float64),
-                    np.empty(cap, np.uint8), np.empty(cap, np.uint8)]
-        a = self._grow(lambda cap, r, cnt: self._L.arp_atom_plane(self._h, cap, *[_p(x) for x in r], C.byref(cnt)), mk,
-                       'arp_atom_plane', 8 * self.n_rings)
-        out = dict(atom=a[0], ring=a[1], dist=a[2], theta=a[3], mask=a[4], ctype=a[5])
-        o = np.lexsort((out['atom'], out['ring']))
+    def _bag_launch_fetch(self, name, guess):
+        """Launch one ring / amide loop and fetch its bag in canonical order (arp_<name>)."""
+        fn = getattr(self._L, f'arp_{name}')
+        mk, keys, order = self._BAGS[name]
+        a = self._grow(lambda cap, r, cnt: fn(self._h, cap, *[_p(x) for x in r], C.byref(cnt)), mk, f'arp_{name}', guess)
+        out = dict(zip(keys, a))
+        o = np.lexsort((out[order[1]], out[order[0]]))      # = the reference's creation order
         return {k: v[o] for k, v in out.items()}
+
+    def atom_plane(self):
+        return self._bag_launch_fetch('atom_plane', 8 * self.n_rings)
 
     def plane_plane(self):
-        def mk(cap):
-            return [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float64) for _ in range(4)] + \
-                   [np.empty(cap, np.uint8) for _ in range(3)]
-        a = self._grow(lambda cap, r, cnt: self._L.arp_plane_plane(self._h, cap, *[_p(x) for x in r], C.byref(cnt)), mk,
-                       'arp_plane_plane', 16 * self.n_rings)
-        out = dict(bgn=a[0], end=a[1], dist=a[2], dihedral=a[3], theta_bgn=a[4], theta_end=a[5], type1=a[6], type2=a[7], ctype=a[8])
-        o = np.lexsort((out['end'], out['bgn']))   # = the reference's creation order (ring-id order)
-        return {k: v[o] for k, v in out.items()}
+        return self._bag_launch_fetch('plane_plane', 16 * self.n_rings)
 
     def group_group(self):
-        def mk(cap):
-            return [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float32) for _ in range(3)] + \
-                   [np.empty(cap, np.uint8)]
-        a = self._grow(lambda cap, r, cnt: self._L.arp_group_group(self._h, cap, *[_p(x) for x in r], C.byref(cnt)), mk,
-                       'arp_group_group', 8 * self.n_amides)
-        out = dict(bgn=a[0], end=a[1], dist=a[2], dihedral=a[3], theta=a[4], ctype=a[5])
-        o = np.lexsort((out['end'], out['bgn']))
-        return {k: v[o] for k, v in out.items()}
+        return self._bag_launch_fetch('group_group', 8 * self.n_amides)
 
     def group_plane(self):
-        def mk(cap):
-            return [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float64) for _ in range(3)] + \
-                   [np.empty(cap, np.uint8)]
-        a = self._grow(lambda cap, r, cnt: self._L.arp_group_plane(self._h, cap, *[_p(x) for x in r], C.byref(cnt)), mk,
-                       'arp_group_plane', 8 * self.n_amides)
-        out = dict(amide=a[0], ring=a[1], dist=a[2], dihedral=a[3], theta=a[4], ctype=a[5])
-        o = np.lexsort((out['ring'], out['amide']))
-        return {k: v[o] for k, v in out.items()}
+        return self._bag_launch_fetch('group_plane', 8 * self.n_amides)
 
-    _BAGS = {
-        'atom_plane': (lambda cap: [np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64),
-                                    np.empty(cap, np.float64), np.empty(cap, np.uint8), np.empty(cap, np.uint8)],
-                       ('atom', 'ring', 'dist', 'theta', 'mask', 'ctype'), ('ring', 'atom')),
-        'plane_plane': (lambda cap: [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float64) for _ in range(4)]
-                        + [np.empty(cap, np.uint8) for _ in range(3)],
-                        ('bgn', 'end', 'dist', 'dihedral', 'theta_bgn', 'theta_end', 'type1', 'type2', 'ctype'), ('bgn', 'end')),
-        'group_group': (lambda cap: [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float32) for _ in range(3)]
-                        + [np.empty(cap, np.uint8)],
-                        ('bgn', 'end', 'dist', 'dihedral', 'theta', 'ctype'), ('bgn', 'end')),
-        'group_plane': (lambda cap: [np.empty(cap, np.int32), np.empty(cap, np.int32)] + [np.empty(cap, np.float64) for _ in range(3)]
-                        + [np.empty(cap, np.uint8)],
-                        ('amide', 'ring', 'dist', 'dihedral', 'theta', 'ctype'), ('amide', 'ring')),
-    }
+    # per bag: (buffers for cap records, column names, sort keys) -- from tables.BAGS
+    _BAGS = {name: ((lambda cap, name=name: tables.bag_buffers(name, cap)), tuple(c for c, _, _ in tables.bag_columns(name)), b.order)
+             for name, b in tables.BAGS.items()}
 
     # ---- measurement ----
     def stats(self):

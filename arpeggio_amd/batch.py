@@ -14,6 +14,7 @@ from typing import Dict, List, Sequence
 
 import numpy as np
 
+from . import tables
 from .core.packed import PackedComplex
 
 
@@ -89,13 +90,7 @@ def split_atom_contacts(res, offsets):
 
 
 def split_bag(name, res, offsets):
-    a, r, m = offsets['atom'], offsets['ring'], offsets['amide']
-    if name == 'atom_plane':
-        return _split(res, 'ring', r, {'atom': a, 'ring': r})
-    if name == 'plane_plane':
-        return _split(res, 'bgn', r, {'bgn': r, 'end': r})
-    if name == 'group_group':
-        return _split(res, 'bgn', m, {'bgn': m, 'end': m})
-    if name == 'group_plane':
-        return _split(res, 'amide', m, {'amide': m, 'ring': r})
-    raise KeyError(name)
+    """Cut a ring / amide bag into its structures by the major key of its canonical order (``tables.BAGS``)."""
+    shifts = {col: offsets[entity] for col, entity in tables.BAGS[name].ids}
+    key = tables.BAGS[name].order[0]
+    return _split(res, key, shifts[key], shifts)

@@ -20,6 +20,7 @@
 #include "arp_grid.h"
 #include "arp_numerics.h"
 #include "arp_pairs.h"
+#include "arp_bag_table.h"
 #include "arp_planes.h"
 #include "arp_prepare.h"
 #include "arp_models.h"
@@ -103,26 +104,20 @@ struct Grid {
                      cnt2.release(); chain.release(); valid = false; }
 };
 
-struct Bag {  // outputs of one ring/amide kernel, resident in HBM until fetched
-    const int slot;           // its record counter (C_AP ... C_GP)
-    const bool d, f;          // its columns besides a, b, u0-u2: d0-d3 (double), f0-f2 (float)
-    Bag(int slot_, bool d_, bool f_) : slot(slot_), d(d_), f(f_) {}
+struct Bag {  // outputs of one ring/amide kernel, resident in HBM until fetched: the columns PLANE_TABLES (arp_bag_table.h) names
     // the arrays are sub-ranges of ONE allocation (slab), so that a small bag reaches the host with one copy
     DevBuf<uint8_t> slab;
-    DevBuf<int> a, b;
-    DevBuf<double> d0, d1, d2, d3;
-    DevBuf<float> f0, f1, f2;
-    DevBuf<uint8_t> u0, u1, u2;
+    uint8_t* col[BAG_COLS] = {};   // column j of the table; null: the bag has no such column
+    int* id(int q) const { return (int*)col[q]; }
+    template <class T> T* val(int q) const { return (T*)col[BAG_VAL0 + q]; }
+    uint8_t* byte(int q) const { return col[BAG_BYTE0 + q]; }
     size_t cap = 0;
-    size_t slab_bytes = 0;
     int64_t count = 0;
     bool valid = false;
     uint64_t version = 0;        // bumped whenever a launch refills the bag
     uint64_t staged_version = 0; // version whose records are in the context's page-locked staging area, at stage_off[]
-    uint32_t stage_off[12] = {0};
-    void release() { a.release(); b.release(); d0.release(); d1.release(); d2.release(); d3.release(); f0.release();
-                     f1.release(); f2.release(); u0.release(); u1.release(); u2.release(); slab.release(); cap = 0; slab_bytes = 0;
-                     valid = false; staged_version = 0; }
+    size_t stage_off[BAG_COLS] = {0};
+    void release() { slab.release(); for (uint8_t*& p : col) p = nullptr; cap = 0; valid = false; staged_version = 0; }
 };
 
 // scratch of the radix sort (arp_sort.h: radix_sort): keys and payload double-buffered, digit table, digit totals
@@ -589,7 +584,9 @@ struct arp_ctx {
     bool fuse_sets = false;        // the contact-grid build of the current pass also makes the residue / ring / amide sets
     bool init_plus_in_bin = false; // ... and writes selection_plus = selection (whole-structure selection)
     // ---- device-resident result bags of the ring / amide kernels
-    Bag bag_ap{C_AP, true, false}, bag_pp{C_PP, true, false}, bag_gg{C_GG, false, true}, bag_gp{C_GP, true, false};
+    Bag bag[BAG_KINDS];
+    void void_bags() { for (Bag& b : bag) b.valid = false; }
+    bool bags_valid() const { bool v = true; for (const Bag& b : bag) v = v && b.valid; return v; }
     DevBuf<uint32_t> bag_perm_big[4];   // ... of a bag beyond BAG_SORT_MAX records (bag_order_large)
     SortScratch sort_bags;                // ... the radix sort's scratch for them
     DevBuf<int> bagsort_i, bagsort_j;
@@ -965,7 +962,7 @@ void inputs_changed(arp_ctx* c, unsigned what) {
     if (what & IN_EVERYTHING) {
         c->contacts_valid = false;
         void_results(c, RES_AA | RES_PLANES);
-        c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
+        c->void_bags();
     }
     void_pose_results(c, ((what & structure) ? POSE_STRUCTURE : 0u) | ((what & IN_EVERYTHING & ~structure) ? POSE_SELECTION : 0u));
 }
@@ -1604,7 +1601,7 @@ int enqueue_expansion(arp_ctx* c, double radius, hipStream_t st = nullptr) {
     }
     // all_grid stays usable for the atom-plane kernel: it reads plus[] directly, M_SEL is current
     c->contacts_valid = false;
-    c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
+    c->void_bags();
     return ARP_OK;
 }
 
@@ -1660,37 +1657,17 @@ int ensure_default_selection(arp_ctx* c) {  // whole structure selected (I:1395 
     return enqueue_selection(c, 6.0);   // an uploaded selection that was not expanded yet is expanded here
 }
 
-int bag_reserve(arp_ctx* c, Bag& b, size_t cap) {
-    const bool d = b.d, f = b.f;
+int bag_reserve(arp_ctx* c, int kind, size_t cap) {
+    Bag& b = c->bag[kind];
     cap = cap + cap / 4 + 64;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t bi = al(cap * sizeof(int)), bd = al(cap * sizeof(double)), bf = al(cap * sizeof(float)), bu = al(cap);
-    const size_t total = 2 * bi + (d ? 4 * bd : 0) + (f ? 3 * bf : 0) + 3 * bu;
+    size_t off[BAG_COLS];
+    const size_t total = bag_slab_layout(kind, cap, 0, off);
     b.release();
     HIPCHK(c, b.slab.reserve(total));
-    uint8_t* p = b.slab.p;
-    b.a.borrow(p, cap); p += bi; b.b.borrow(p, cap); p += bi;
-    if (d) { b.d0.borrow(p, cap); p += bd; b.d1.borrow(p, cap); p += bd; b.d2.borrow(p, cap); p += bd; b.d3.borrow(p, cap); p += bd; }
-    if (f) { b.f0.borrow(p, cap); p += bf; b.f1.borrow(p, cap); p += bf; b.f2.borrow(p, cap); p += bf; }
-    b.u0.borrow(p, cap); p += bu; b.u1.borrow(p, cap); p += bu; b.u2.borrow(p, cap); p += bu;
+    for (int j = 0; j < BAG_COLS; ++j)
+        if (bag_has(kind, j)) b.col[j] = b.slab.p + off[j];
     b.cap = cap;
-    b.slab_bytes = total;
     return ARP_OK;
-}
-
-// Small bags travel to the host in one piece: the first *_fetch after a pass gathers the used prefix of every array of
-// EVERY valid bag into one device buffer (k_pack_segments), copies it to page-locked memory and synchronises once; the
-// fetch calls hand the arrays out from there — instead of six to nine small copies and a synchronisation per bag.
-#define BAG_STAGE_MAX ((size_t)4 << 20)
-int stage_bags(arp_ctx* c);
-inline bool bag_is_staged(const arp_ctx* c, const Bag& b) { return c->bag_stage && b.staged_version == b.version && b.version != 0; }
-template <class T>
-int bag_download(arp_ctx* c, const Bag& b, T* dst, const DevBuf<T>& src, int idx, size_t m) {
-    if (bag_is_staged(c, b)) {
-        if (m && dst) memcpy(dst, c->bag_stage + b.stage_off[idx], m * sizeof(T));
-        return ARP_OK;
-    }
-    return download_async(c, dst, src.p, m);
 }
 
 // One wavefront per ring / amide up to PLANE_BLOCKS blocks, several items per wave beyond: the waves queue their
@@ -1707,10 +1684,10 @@ int plane_blocks(int64_t items) {
 // (nb = number of blocks, 0 when there is nothing to do); enqueue_* launches one of them, enqueue_planes all
 // four as ONE launch (k_planes).
 int prepare_atom_plane(arp_ctx* c, AtomPlaneArgs& a, int& nb, bool contact_grid = false) {  // I:947-1062
-    Bag& b = c->bag_ap;
+    Bag& b = c->bag[BAG_AP];
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 8 + 256));
-    CHK(zero_counter(c, b.slot, 1));
+    if (!b.cap) CHK(bag_reserve(c, BAG_AP, (size_t)c->nring * 8 + 256));
+    CHK(zero_counter(c, C_AP, 1));
     if (c->nring == 0 || c->n == 0) return ARP_OK;
     // contact_grid: the grid of the pass (selection_plus without hydrogens, atom_plane_cg_body); else the all-atom 6 A grid
     // (I:960 radius): the one the selection expansion has just built, if it is still current
@@ -1719,51 +1696,51 @@ int prepare_atom_plane(arp_ctx* c, AtomPlaneArgs& a, int& nb, bool contact_grid 
     a = AtomPlaneArgs{G.d, G.start.p, contact_grid ? c->s_xyzm.p : c->a_xyzm.p, contact_grid ? c->s_aux.p : c->a_aux.p, (int)c->nring,
                       c->ring_c.p, c->ring_n.p, c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->plus.p,
                       c->has_group_owner ? c->ring_home.p : nullptr, c->has_group_owner ? c->ring_gid.p : nullptr, c->has_gid ? c->gid.p : nullptr,
-                      (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.u0.p, b.u1.p, c->d_ctr + ctr_dev(b.slot),
+                      (long long)b.cap, b.id(0), b.id(1), b.val<double>(0), b.val<double>(1), b.byte(0), b.byte(1), c->d_ctr + ctr_dev(C_AP),
                       c->st_xyzm.p, c->sel_made ? c->sel.p : nullptr, (c->sel_made && c->sel_all) ? 1 : 0};
     nb = plane_blocks(c->nring);
     return ARP_OK;
 }
 int prepare_plane_plane(arp_ctx* c, PlanePlaneArgs& a, int& nb) {  // I:1064-1194
-    Bag& b = c->bag_pp;
+    Bag& b = c->bag[BAG_PP];
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->nring * 16 + 256));
-    CHK(zero_counter(c, b.slot, 1));
+    if (!b.cap) CHK(bag_reserve(c, BAG_PP, (size_t)c->nring * 16 + 256));
+    CHK(zero_counter(c, C_PP, 1));
     if (c->nring == 0) return ARP_OK;
     CHK(ensure_ring_grid(c));
     a = PlanePlaneArgs{c->ring_grid.d, c->ring_grid.start.p, c->ring_grid.perm.p, (int)c->nring, c->ring_c.p, c->ring_n.p,
                        c->ring_res.p, c->ring_sel.p, c->ring_plus.p, c->has_group_owner ? c->ring_home.p : nullptr,
-                       c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.d2.p,
-                       b.d3.p, b.u0.p, b.u1.p, b.u2.p, c->d_ctr + ctr_dev(b.slot)};
+                       c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.id(0), b.id(1), b.val<double>(0), b.val<double>(1),
+                       b.val<double>(2), b.val<double>(3), b.byte(0), b.byte(1), b.byte(2), c->d_ctr + ctr_dev(C_PP)};
     nb = plane_blocks(c->nring);
     return ARP_OK;
 }
 int prepare_group_group(arp_ctx* c, GroupGroupArgs& a, int& nb) {  // I:1217-1300
-    Bag& b = c->bag_gg;
+    Bag& b = c->bag[BAG_GG];
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256));
-    CHK(zero_counter(c, b.slot, 1));
+    if (!b.cap) CHK(bag_reserve(c, BAG_GG, (size_t)c->namide * 8 + 256));
+    CHK(zero_counter(c, C_GG, 1));
     if (c->namide == 0) return ARP_OK;
     CHK(ensure_amide_grid(c));
     a = GroupGroupArgs{c->amide_grid.d, c->amide_grid.start.p, c->amide_grid.perm.p, (int)c->namide, c->am_c.p, c->am_n.p,
                        c->am_sel.p, c->am_plus.p, c->has_group_owner ? c->am_home.p : nullptr,
-                       c->has_group_owner ? c->am_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.f0.p, b.f1.p, b.f2.p,
-                       b.u0.p, c->d_ctr + ctr_dev(b.slot)};
+                       c->has_group_owner ? c->am_gid.p : nullptr, (long long)b.cap, b.id(0), b.id(1), b.val<float>(0), b.val<float>(1),
+                       b.val<float>(2), b.byte(0), c->d_ctr + ctr_dev(C_GG)};
     nb = plane_blocks(c->namide);
     return ARP_OK;
 }
 int prepare_group_plane(arp_ctx* c, GroupPlaneArgs& a, int& nb) {  // I:1302-1382
-    Bag& b = c->bag_gp;
+    Bag& b = c->bag[BAG_GP];
     nb = 0;
-    if (!b.cap) CHK(bag_reserve(c, b, (size_t)c->namide * 8 + 256));
-    CHK(zero_counter(c, b.slot, 1));
+    if (!b.cap) CHK(bag_reserve(c, BAG_GP, (size_t)c->namide * 8 + 256));
+    CHK(zero_counter(c, C_GP, 1));
     if (c->namide == 0 || c->nring == 0) return ARP_OK;
     CHK(ensure_ring_grid(c));
     a = GroupPlaneArgs{c->ring_grid.d, c->ring_grid.start.p, c->ring_grid.perm.p, (int)c->namide, c->am_c.p, c->am_n.p,
                        c->am_sel.p, c->am_plus.p, c->ring_c.p, c->ring_n.p, c->ring_sel.p, c->ring_plus.p,
                        c->has_group_owner ? c->am_home.p : nullptr, c->has_group_owner ? c->am_gid.p : nullptr,
-                       c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.a.p, b.b.p, b.d0.p, b.d1.p, b.d2.p,
-                       b.u0.p, c->d_ctr + ctr_dev(b.slot)};
+                       c->has_group_owner ? c->ring_gid.p : nullptr, (long long)b.cap, b.id(0), b.id(1), b.val<double>(0), b.val<double>(1),
+                       b.val<double>(2), b.byte(0), c->d_ctr + ctr_dev(C_GP)};
     nb = plane_blocks(c->namide);
     return ARP_OK;
 }
@@ -2157,7 +2134,6 @@ bool finish_contacts(arp_ctx* c) {
 // ---- canonical order of the atom-atom bag (arp_sort.h) --------------------------------------------------------
 // Layout of the sorted slab: the five columns one after the other, each on a 256-byte boundary; what follows them
 // (sorted_extra bytes) is the caller's (the packed ring / amide bags of arp_fetch_packed).
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 void sorted_layout(size_t k, size_t off[5], size_t* bytes, size_t first_col_entries) {      // (first column: k bgn ids, or N + 1 row offsets)
     off[0] = 0;
     off[1] = off[0] + al256(first_col_entries * sizeof(int32_t));
@@ -2281,8 +2257,9 @@ int finish_plane_lists(arp_ctx* c, bool grow) {
     }
     return again;
 }
-bool finish_bag(arp_ctx* c, Bag& b) {
-    const u64 k = c->h_ctr[b.slot];
+bool finish_bag(arp_ctx* c, int kind) {
+    Bag& b = c->bag[kind];
+    const u64 k = c->h_ctr[PLANE_TABLES[kind].counter];
     if (k > b.cap) return true;
     b.count = (int64_t)k;
     b.valid = true;
@@ -2296,11 +2273,7 @@ int grow_pairs(arp_ctx* c) {
     HIPCHK(c, c->pairs.reserve(need));
     return ARP_OK;
 }
-int grow_bag(arp_ctx* c, Bag& b) {
-    const size_t need = (size_t)c->h_ctr[b.slot];
-    b.release();
-    return bag_reserve(c, b, need);
-}
+int grow_bag(arp_ctx* c, int kind) { return bag_reserve(c, kind, (size_t)c->h_ctr[PLANE_TABLES[kind].counter]); }
 int device_error(arp_ctx* c) {
     if ((int)(uint32_t)c->h_ctr[C_ERR] == ARP_E_XBOND_NBR)
         FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
@@ -2338,7 +2311,7 @@ int enqueue_bag_from_lists(arp_ctx* c, int kind) {
 }
 // One ring / amide loop alone (arp_*_launch), from its candidate list or by its grid walk (ARP_BAG_LISTS), once more while a
 // bag or a list was too small (re-sized: a list is rebuilt by the next attempt)
-int bag_launch(arp_ctx* c, Bag& b, int kind, int64_t* count) {
+int bag_launch(arp_ctx* c, int kind, int64_t* count) {
     const bool from_lists = ((sw().bag_lists >> kind) & 1) != 0;
     HIPCHK(c, hipSetDevice(c->device));
     CHK(ensure_default_selection(c));
@@ -2347,12 +2320,12 @@ int bag_launch(arp_ctx* c, Bag& b, int kind, int64_t* count) {
         CHK(read_counters(c));
         collect_events(c);
         const bool list_small = from_lists && finish_plane_lists(c, /*grow=*/true) != 0;
-        const bool bag_small = finish_bag(c, b);
+        const bool bag_small = finish_bag(c, kind);
         if (!list_small && !bag_small) break;
         if (attempt == (from_lists ? 3 : 2)) FAIL(c, ARP_E_CAPACITY, "result bag could not be sized");
-        if (bag_small) CHK(grow_bag(c, b));
+        if (bag_small) CHK(grow_bag(c, kind));
     }
-    if (count) *count = b.count;
+    if (count) *count = c->bag[kind].count;
     return ARP_OK;
 }
 
@@ -2361,8 +2334,8 @@ int bag_launch(arp_ctx* c, Bag& b, int kind, int64_t* count) {
 int finish_pass(arp_ctx* c) {
     int again = 0;
     if (finish_contacts(c)) { CHK(grow_pairs(c)); again = 1; }
-    for (Bag* b : {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp})
-        if (finish_bag(c, *b)) { CHK(grow_bag(c, *b)); again = 1; }
+    for (int kind = 0; kind < BAG_KINDS; ++kind)
+        if (finish_bag(c, kind)) { CHK(grow_bag(c, kind)); again = 1; }
     const int lists = finish_plane_lists(c, true);
     if (lists < 0) return lists;
     return again | lists;
@@ -2371,8 +2344,8 @@ void pass_counts(arp_ctx* c, int64_t counts[5]) {      // expansion statistics a
     c->stats[5] = (int64_t)c->h_ctr[C_MARK_CAND];
     c->stats[6] = (int64_t)c->h_ctr[C_MARK_ACC];
     if (counts) {
-        counts[0] = c->n_contacts; counts[1] = c->bag_pp.count; counts[2] = c->bag_ap.count;
-        counts[3] = c->bag_gg.count; counts[4] = c->bag_gp.count;
+        counts[0] = c->n_contacts;
+        for (int b = 0; b < BAG_KINDS; ++b) counts[1 + b] = c->bag[PACKED_ORDER[b]].count;
     }
 }
 
@@ -2489,7 +2462,7 @@ void arp_destroy(arp_ctx* c) {
     c->sp_xyzm.release(); c->sp_aux.release(); c->sp_qa.release(); c->st_h.release(); c->sp_h.release(); c->s_h.release(); c->sp_cnt.release(); c->sp_cr.release();
     c->atom_grid.release(); c->all_grid.release(); c->a_xyzm.release(); c->a_aux.release(); c->ring_grid.release(); c->amide_grid.release(); c->tmp_u8.release();
     c->pairs.release(); c->out_i.release(); c->out_j.release(); c->out_d.release(); c->out_s.release(); c->out_ct.release();
-    c->bag_ap.release(); c->bag_pp.release(); c->bag_gg.release(); c->bag_gp.release();
+    for (Bag& b : c->bag) b.release();
     c->bag_pack.release(); c->bag_perm.release();
     c->sort_aa.release(); c->sort_bags.release(); c->sorted_slab.release();
     c->table_sort.release(); c->table_tiles.release(); c->table_rows.release(); c->table_total.release();
@@ -3419,13 +3392,10 @@ struct PackedAtomBag {
 struct PackedPlan {
     size_t off[5], cbytes, total;
     PackTable t;
-    int seg_of[4][12];
-    Bag* bags[4];
+    int seg_of[BAG_KINDS][BAG_COLS];      // [b][j]: bag b in the order of get_contacts (PACKED_ORDER), column j of its table
 };
 int packed_plan(arp_ctx* c, const PackedAtomBag& S, PackedPlan& P, int64_t counts[5], uint64_t offsets[ARP_PACKED_OFFSETS]) {
     const std::string who = S.who;
-    static const size_t es[12] = {4, 4, 8, 8, 8, 8, 4, 4, 4, 1, 1, 1};
-    Bag* const bags[4] = {&c->bag_pp, &c->bag_ap, &c->bag_gg, &c->bag_gp};
     sorted_layout((size_t)S.k, P.off, &P.cbytes, S.csr ? (size_t)std::max<int64_t>(c->n, 0) + 1 : (size_t)S.k);
     size_t total = P.cbytes;
     PackTable& t = P.t;
@@ -3433,26 +3403,26 @@ int packed_plan(arp_ctx* c, const PackedAtomBag& S, PackedPlan& P, int64_t count
     for (int q = 0; q < ARP_PACKED_OFFSETS; ++q) offsets[q] = 0;
     for (int q = 0; q < 5; ++q) offsets[q] = P.off[q];
     counts[0] = S.k;
-    for (int b = 0; b < 4; ++b) {
-        Bag& g = *bags[b];
-        P.bags[b] = bags[b];
+    for (int b = 0; b < BAG_KINDS; ++b) {
+        const int kind = PACKED_ORDER[b];
+        const Bag& g = c->bag[kind];
         counts[1 + b] = g.valid ? g.count : 0;
-        for (int q = 0; q < 12; ++q) P.seg_of[b][q] = -1;
+        for (int j = 0; j < BAG_COLS; ++j) P.seg_of[b][j] = -1;
         if (!g.valid || g.count == 0) continue;
         if ((uint64_t)g.count >= ((uint64_t)1 << 31)) FAIL(c, ARP_E_CAPACITY, who + ": a ring / amide bag of 2^31 records or more (fetch the bags one by one)");
-        const uint8_t* ptr[12] = {(const uint8_t*)g.a.p, (const uint8_t*)g.b.p, (const uint8_t*)g.d0.p, (const uint8_t*)g.d1.p,
-                                  (const uint8_t*)g.d2.p, (const uint8_t*)g.d3.p, (const uint8_t*)g.f0.p, (const uint8_t*)g.f1.p,
-                                  (const uint8_t*)g.f2.p, g.u0.p, g.u1.p, g.u2.p};
-        for (int q = 0; q < 12; ++q) {
-            if (!ptr[q]) continue;
-            const size_t bytes = (size_t)g.count * es[q];
-            if (t.n >= 48 || bytes >= ((size_t)1 << 32) || total >= ((size_t)1 << 32)) FAIL(c, ARP_E_CAPACITY, who + ": ring / amide bags too large for one piece (fetch them one by one)");
-            offsets[5 + 12 * b + q] = total;
-            P.seg_of[b][q] = t.n;
-            t.s[t.n++] = PackSeg{ptr[q], (uint32_t)total, (uint32_t)bytes, nullptr, (uint32_t)es[q]};
-            total = (total + bytes + 15) & ~(size_t)15;
+        size_t at[BAG_COLS];
+        const size_t end = bag_piece_layout(kind, (size_t)g.count, total, at);
+        for (int j = 0; j < BAG_COLS; ++j) {
+            if (!bag_has(kind, j)) continue;
+            const size_t bytes = (size_t)g.count * bag_es(kind, j);
+            if (bytes >= ((size_t)1 << 32) || at[j] >= ((size_t)1 << 32)) FAIL(c, ARP_E_CAPACITY, who + ": ring / amide bags too large for one piece (fetch them one by one)");
+            offsets[5 + 12 * b + bag_slot(kind, j)] = at[j];
+            P.seg_of[b][j] = t.n;
+            t.s[t.n++] = PackSeg{g.col[j], (uint32_t)at[j], (uint32_t)bytes, nullptr, (uint32_t)bag_es(kind, j)};
         }
+        total = end;
     }
+    static_assert(BAG_KINDS * BAG_COLS <= sizeof(PackTable::s) / sizeof(PackSeg), "PackTable");
     P.total = total;
     return ARP_OK;
 }
@@ -3463,29 +3433,28 @@ int fetch_packed_from(arp_ctx* c, const PackedAtomBag& S, void* host, uint64_t h
     *bytes_used = 0;
     PackedPlan P;
     CHK(packed_plan(c, S, P, counts, offsets));
-    Bag* const* bags = P.bags;
     PackTable& t = P.t;
     const size_t total = P.total, cbytes = P.cbytes;
     *bytes_used = total;
     if (!host || host_bytes < total) FAIL(c, ARP_E_CAPACITY, who + ": host buffer too small (bytes_used holds the size needed)");
     if (S.filtered && S.filtered->slab.cap < total) FAIL(c, ARP_E_HIP, who + ": the filtered slab has no room for the ring / amide bags");      // (sized by the launch; finish_bag voids it)
-    // canonical order of the small bags, made on the device: plane-plane, group-group, group-plane by (first id, second id),
-    // atom-plane by (ring, atom) — the order the reference's loops create them in
+    // canonical order of the small bags, made on the device by the two sort keys the table names (plane-plane, group-group,
+    // group-plane by (first id, second id), atom-plane by (ring, atom)) — the order the reference's loops create them in
     BagOrderArgs bo{};
     bool any_order = false;
     HIPCHK(c, c->bag_perm.reserve(4 * (size_t)BAG_SORT_MAX));
     for (int b = 0; b < 4; ++b) {
-        Bag& g = *bags[b];
+        const Bag& g = c->bag[PACKED_ORDER[b]];
         const bool small = g.valid && g.count > 0 && g.count <= BAG_SORT_MAX;
-        bo.first[b] = (b == 1) ? g.b.p : g.a.p;          // (atom-plane: a = atom, b = ring)
-        bo.second[b] = (b == 1) ? g.a.p : g.b.p;
+        bo.first[b] = g.id(PLANE_TABLES[PACKED_ORDER[b]].key[0]);
+        bo.second[b] = g.id(PLANE_TABLES[PACKED_ORDER[b]].key[1]);
         bo.n[b] = small ? (int)g.count : 0;
         bo.perm[b] = c->bag_perm.p + (size_t)b * BAG_SORT_MAX;
         any_order = any_order || small;
     }
     const uint32_t* big_perm[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int b = 0; b < 4; ++b) {
-        Bag& g = *bags[b];
+        const Bag& g = c->bag[PACKED_ORDER[b]];
         if (!(g.valid && g.count > BAG_SORT_MAX)) continue;
         const int64_t idmax = (c->has_gid || c->has_group_owner) ? (((int64_t)1 << 31) - 1) : std::max<int64_t>({c->n, c->nring, c->namide, 2}) - 1;      // (a shard's records carry global ids)
         CHK(bag_order_large(c, bo.first[b], bo.second[b], (size_t)g.count, idmax, c->bag_perm_big[b]));
@@ -3494,7 +3463,7 @@ int fetch_packed_from(arp_ctx* c, const PackedAtomBag& S, void* host, uint64_t h
     // (on the second stream, beside the radix passes of the atom-atom bag: one block per bag, 80 us for a bag of 4096)
     const bool order_aside = any_order && c->stream2 && !c->external_stream;      // (beside the sort, which may be under way already: arp_set_sort_after_pass)
     for (int b = 0; b < 4; ++b)
-        for (int q = 0; q < 12; ++q)
+        for (int q = 0; q < BAG_COLS; ++q)
             if (P.seg_of[b][q] >= 0) t.s[P.seg_of[b][q]].perm = bo.n[b] > 0 ? bo.perm[b] : big_perm[b];
     if (!S.filtered) c->contacts_sorted = c->contacts_sorted && c->sorted_slab.cap >= total && c->sorted_is_csr == S.csr;
     // (aside: the sort's launches go out first — they are the critical path, the host needs ~5 us per launch —, the one block per
@@ -3627,44 +3596,32 @@ int arp_atom_integer_sifts(arp_ctx* c, uint8_t* out_isift) {
 // atoms of a ring's cells as it meets them, does less); the two amide loops 19 - 20 us either way (a chain of five dependent round
 // trips whatever evaluates 1.5 k records).  ARP_BAG_LISTS: bit k = loop k from its list (default 2: plane-plane), 0 = every loop by
 // its grid walk as through round 5, 15 = all four from the lists (the way a whole pass evaluates them).
-int arp_atom_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_ap, 0, count) : ARP_E_ARG; }
-int arp_plane_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_pp, 1, count) : ARP_E_ARG; }
-int arp_group_group_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_gg, 2, count) : ARP_E_ARG; }
-int arp_group_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, c->bag_gp, 3, count) : ARP_E_ARG; }
-
-#define FETCH_PROLOGUE(bag, what)                                                                  \
-    if (!c || !count) return ARP_E_ARG;                                                           \
-    if (!(bag).valid) FAIL(c, ARP_E_ARG, what ": no launch results");                             \
-    HIPCHK(c, hipSetDevice(c->device));                                                           \
-    *count = (bag).count;                                                                         \
-    if ((bag).count > cap) FAIL(c, ARP_E_CAPACITY, what ": output buffer too small");             \
-    const size_t m = (size_t)(bag).count;
+int arp_atom_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, BAG_AP, count) : ARP_E_ARG; }
+int arp_plane_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, BAG_PP, count) : ARP_E_ARG; }
+int arp_group_group_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, BAG_GG, count) : ARP_E_ARG; }
+int arp_group_plane_launch(arp_ctx* c, int64_t* count) { return c ? bag_launch(c, BAG_GP, count) : ARP_E_ARG; }
 
 namespace {
+// Small bags travel to the host in one piece: the first *_fetch after a pass gathers the used prefix of every array of
+// EVERY valid bag into one device buffer (k_pack_segments), copies it to page-locked memory and synchronises once; the
+// fetch calls hand the arrays out from there — instead of six to nine small copies and a synchronisation per bag.
+#define BAG_STAGE_MAX ((size_t)4 << 20)
 int stage_bags(arp_ctx* c) {
-    Bag* bags[4] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};
     bool stale = false;
-    for (Bag* b : bags) stale = stale || (b->valid && b->staged_version != b->version);
+    for (const Bag& b : c->bag) stale = stale || (b.valid && b.staged_version != b.version);
     if (!stale) return ARP_OK;
     PackTable t;
     t.n = 0;
     size_t total = 0;
-    for (Bag* b : bags) {
-        if (!b->valid) continue;
-        const uint8_t* ptr[12] = {(const uint8_t*)b->a.p, (const uint8_t*)b->b.p, (const uint8_t*)b->d0.p, (const uint8_t*)b->d1.p,
-                                  (const uint8_t*)b->d2.p, (const uint8_t*)b->d3.p, (const uint8_t*)b->f0.p, (const uint8_t*)b->f1.p,
-                                  (const uint8_t*)b->f2.p, b->u0.p, b->u1.p, b->u2.p};
-        const size_t es[12] = {4, 4, 8, 8, 8, 8, 4, 4, 4, 1, 1, 1};
-        for (int k = 0; k < 12; ++k) {
-            b->stage_off[k] = (uint32_t)total;
-            if (!ptr[k] || b->count == 0) continue;
-            const size_t bytes = (size_t)b->count * es[k];
-            t.s[t.n++] = PackSeg{ptr[k], (uint32_t)total, (uint32_t)bytes, nullptr, 0u};
-            total = (total + bytes + 15) & ~(size_t)15;
-        }
+    for (int kind = 0; kind < BAG_KINDS; ++kind) {
+        Bag& b = c->bag[kind];
+        if (!b.valid) continue;
+        total = bag_piece_layout(kind, (size_t)b.count, total, b.stage_off);
+        for (int j = 0; j < BAG_COLS; ++j)      // (offsets beyond 32 bits: only when the total is past BAG_STAGE_MAX, and then unused)
+            if (bag_has(kind, j) && b.count > 0) t.s[t.n++] = PackSeg{b.col[j], (uint32_t)b.stage_off[j], (uint32_t)((size_t)b.count * bag_es(kind, j)), nullptr, 0u};
     }
     if (total > BAG_STAGE_MAX) {   // big bags (configs[4]): array by array, as before
-        for (Bag* b : bags) b->staged_version = 0;
+        for (Bag& b : c->bag) b.staged_version = 0;
         return ARP_OK;
     }
     if (total > 0) {
@@ -3685,82 +3642,85 @@ int stage_bags(arp_ctx* c) {
         if (hipHostMalloc((void**)&c->bag_stage, 4096, hipHostMallocDefault) != hipSuccess) { c->bag_stage = nullptr; return ARP_OK; }
         c->bag_stage_cap = 4096;
     }
-    for (Bag* b : bags)
-        if (b->valid) b->staged_version = b->version;
+    for (Bag& b : c->bag)
+        if (b.valid) b.staged_version = b.version;
     return ARP_OK;
+}
+// One bag to the caller's arrays: out[j] receives column j of the table (null: not wanted).  A too-small capacity returns
+// ARP_E_CAPACITY with the required count.
+int bag_fetch(arp_ctx* c, int kind, int64_t cap, void* const (&out)[BAG_COLS], int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const Bag& b = c->bag[kind];
+    auto what = [kind] { return std::string("arp_") + PLANE_TABLES[kind].name + "_fetch"; };
+    if (!b.valid) FAIL(c, ARP_E_ARG, what() + ": no launch results");
+    HIPCHK(c, hipSetDevice(c->device));
+    *count = b.count;
+    if (b.count > cap) FAIL(c, ARP_E_CAPACITY, what() + ": output buffer too small");
+    CHK(stage_bags(c));
+    const bool staged = c->bag_stage && b.staged_version == b.version && b.version != 0;
+    for (int j = 0; j < BAG_COLS; ++j) {      // column by column: out of the stage, or a copy of its own
+        const size_t bytes = (size_t)b.count * bag_es(kind, j);
+        if (!bag_has(kind, j) || !out[j] || !bytes) continue;
+        if (staged) memcpy(out[j], c->bag_stage + b.stage_off[j], bytes);
+        else HIPCHK(c, hipMemcpyAsync(out[j], b.col[j], bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (!staged) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ARP_OK;
+}
+// launch + fetch
+int bag_launch_fetch(arp_ctx* c, int kind, int64_t cap, void* const (&out)[BAG_COLS], int64_t* count) {
+    if (!c || !count || cap < 0) return ARP_E_ARG;
+    CHK(bag_launch(c, kind, count));
+    return bag_fetch(c, kind, cap, out, count);
 }
 }  // namespace
 
+// The C entries name their columns; column j of the table is argument j behind cap (a table without value column 2, 3 or byte
+// column 1, 2 has no such argument).
+#define AP_COLS {out_atom, out_ring, out_dist, out_theta, nullptr, nullptr, out_mask, out_ctype, nullptr}
+#define PP_COLS {out_bgn, out_end, out_dist, out_dihedral, out_theta_bgn, out_theta_end, out_type1, out_type2, out_ctype}
+#define GG_COLS {out_bgn, out_end, out_dist, out_dihedral, out_theta, nullptr, out_ctype, nullptr, nullptr}
+#define GP_COLS {out_amide, out_ring, out_dist, out_dihedral, out_theta, nullptr, out_ctype, nullptr, nullptr}
 int arp_atom_plane_fetch(arp_ctx* c, int64_t cap, int32_t* out_atom, int32_t* out_ring, double* out_dist, double* out_theta,
                          uint8_t* out_mask, uint8_t* out_ctype, int64_t* count) {
-    FETCH_PROLOGUE(c->bag_ap, "arp_atom_plane_fetch")
-    Bag& b = c->bag_ap;
-    CHK(stage_bags(c));
-    CHK(bag_download(c, b, out_atom, b.a, 0, m)); CHK(bag_download(c, b, out_ring, b.b, 1, m)); CHK(bag_download(c, b, out_dist, b.d0, 2, m));
-    CHK(bag_download(c, b, out_theta, b.d1, 3, m)); CHK(bag_download(c, b, out_mask, b.u0, 9, m)); CHK(bag_download(c, b, out_ctype, b.u1, 10, m));
-    if (!bag_is_staged(c, b)) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ARP_OK;
+    return bag_fetch(c, BAG_AP, cap, AP_COLS, count);
 }
 int arp_plane_plane_fetch(arp_ctx* c, int64_t cap, int32_t* out_bgn, int32_t* out_end, double* out_dist, double* out_dihedral,
                           double* out_theta_bgn, double* out_theta_end, uint8_t* out_type1, uint8_t* out_type2,
                           uint8_t* out_ctype, int64_t* count) {
-    FETCH_PROLOGUE(c->bag_pp, "arp_plane_plane_fetch")
-    Bag& b = c->bag_pp;
-    CHK(stage_bags(c));
-    CHK(bag_download(c, b, out_bgn, b.a, 0, m)); CHK(bag_download(c, b, out_end, b.b, 1, m)); CHK(bag_download(c, b, out_dist, b.d0, 2, m));
-    CHK(bag_download(c, b, out_dihedral, b.d1, 3, m)); CHK(bag_download(c, b, out_theta_bgn, b.d2, 4, m)); CHK(bag_download(c, b, out_theta_end, b.d3, 5, m));
-    CHK(bag_download(c, b, out_type1, b.u0, 9, m)); CHK(bag_download(c, b, out_type2, b.u1, 10, m)); CHK(bag_download(c, b, out_ctype, b.u2, 11, m));
-    if (!bag_is_staged(c, b)) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ARP_OK;
+    return bag_fetch(c, BAG_PP, cap, PP_COLS, count);
 }
 int arp_group_group_fetch(arp_ctx* c, int64_t cap, int32_t* out_bgn, int32_t* out_end, float* out_dist, float* out_dihedral,
                           float* out_theta, uint8_t* out_ctype, int64_t* count) {
-    FETCH_PROLOGUE(c->bag_gg, "arp_group_group_fetch")
-    Bag& b = c->bag_gg;
-    CHK(stage_bags(c));
-    CHK(bag_download(c, b, out_bgn, b.a, 0, m)); CHK(bag_download(c, b, out_end, b.b, 1, m)); CHK(bag_download(c, b, out_dist, b.f0, 6, m));
-    CHK(bag_download(c, b, out_dihedral, b.f1, 7, m)); CHK(bag_download(c, b, out_theta, b.f2, 8, m)); CHK(bag_download(c, b, out_ctype, b.u0, 9, m));
-    if (!bag_is_staged(c, b)) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ARP_OK;
+    return bag_fetch(c, BAG_GG, cap, GG_COLS, count);
 }
 int arp_group_plane_fetch(arp_ctx* c, int64_t cap, int32_t* out_amide, int32_t* out_ring, double* out_dist, double* out_dihedral,
                           double* out_theta, uint8_t* out_ctype, int64_t* count) {
-    FETCH_PROLOGUE(c->bag_gp, "arp_group_plane_fetch")
-    Bag& b = c->bag_gp;
-    CHK(stage_bags(c));
-    CHK(bag_download(c, b, out_amide, b.a, 0, m)); CHK(bag_download(c, b, out_ring, b.b, 1, m)); CHK(bag_download(c, b, out_dist, b.d0, 2, m));
-    CHK(bag_download(c, b, out_dihedral, b.d1, 3, m)); CHK(bag_download(c, b, out_theta, b.d2, 4, m)); CHK(bag_download(c, b, out_ctype, b.u0, 9, m));
-    if (!bag_is_staged(c, b)) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ARP_OK;
+    return bag_fetch(c, BAG_GP, cap, GP_COLS, count);
 }
 
 // launch + fetch.  A too-small caller buffer returns ARP_E_CAPACITY with the required count.
 int arp_atom_plane(arp_ctx* c, int64_t cap, int32_t* out_atom, int32_t* out_ring, double* out_dist, double* out_theta,
                    uint8_t* out_mask, uint8_t* out_ctype, int64_t* count) {
-    if (!c || !count || cap < 0) return ARP_E_ARG;
-    CHK(arp_atom_plane_launch(c, count));
-    return arp_atom_plane_fetch(c, cap, out_atom, out_ring, out_dist, out_theta, out_mask, out_ctype, count);
+    return bag_launch_fetch(c, BAG_AP, cap, AP_COLS, count);
 }
 int arp_plane_plane(arp_ctx* c, int64_t cap, int32_t* out_bgn, int32_t* out_end, double* out_dist, double* out_dihedral,
                     double* out_theta_bgn, double* out_theta_end, uint8_t* out_type1, uint8_t* out_type2, uint8_t* out_ctype,
                     int64_t* count) {
-    if (!c || !count || cap < 0) return ARP_E_ARG;
-    CHK(arp_plane_plane_launch(c, count));
-    return arp_plane_plane_fetch(c, cap, out_bgn, out_end, out_dist, out_dihedral, out_theta_bgn, out_theta_end, out_type1,
-                                 out_type2, out_ctype, count);
+    return bag_launch_fetch(c, BAG_PP, cap, PP_COLS, count);
 }
 int arp_group_group(arp_ctx* c, int64_t cap, int32_t* out_bgn, int32_t* out_end, float* out_dist, float* out_dihedral,
                     float* out_theta, uint8_t* out_ctype, int64_t* count) {
-    if (!c || !count || cap < 0) return ARP_E_ARG;
-    CHK(arp_group_group_launch(c, count));
-    return arp_group_group_fetch(c, cap, out_bgn, out_end, out_dist, out_dihedral, out_theta, out_ctype, count);
+    return bag_launch_fetch(c, BAG_GG, cap, GG_COLS, count);
 }
 int arp_group_plane(arp_ctx* c, int64_t cap, int32_t* out_amide, int32_t* out_ring, double* out_dist, double* out_dihedral,
                     double* out_theta, uint8_t* out_ctype, int64_t* count) {
-    if (!c || !count || cap < 0) return ARP_E_ARG;
-    CHK(arp_group_plane_launch(c, count));
-    return arp_group_plane_fetch(c, cap, out_amide, out_ring, out_dist, out_dihedral, out_theta, out_ctype, count);
+    return bag_launch_fetch(c, BAG_GP, cap, GP_COLS, count);
 }
+#undef AP_COLS
+#undef PP_COLS
+#undef GG_COLS
+#undef GP_COLS
 
 // ---- run_arpeggio (I:329-347): every stage enqueued back to back, ONE host synchronisation ---------
 namespace {
@@ -3802,7 +3762,7 @@ int run_pass_enqueue(arp_ctx* c, double cutoff, double vdw_comp, int include_seq
             c->sel_made = true;
             HIPCHK(c, c->plus.reserve((size_t)std::max<int64_t>(c->n, 1)));
             c->contacts_valid = false;
-            c->bag_ap.valid = c->bag_pp.valid = c->bag_gg.valid = c->bag_gp.valid = false;
+            c->void_bags();
             c->init_plus_in_bin = c->sel_all;      // selection_plus = selection: written by the contact grid's binning kernel
         } else {
             CHK(enqueue_expansion(c, expand_radius));                                // I:342 (I:1384-1424)
@@ -3845,10 +3805,12 @@ int run_pass_wait(arp_ctx* c, int64_t counts[5]) {
     pass_counts(c, counts);
     const int rc_dev = device_error(c);
     if (rc_dev == ARP_OK && c->sort_after_pass && c->contacts_valid && c->n_contacts > 0 && c->n_contacts < ((int64_t)1 << 31)) {
-        // (room for the ring / amide bags behind the sorted columns, as arp_fetch_packed lays them out: at most 52 bytes a record
-        // and twelve arrays a bag, each rounded up to 16 bytes)
-        const size_t extra = 52 * (size_t)(c->bag_pp.count + c->bag_ap.count + c->bag_gg.count + c->bag_gp.count) + 4 * 12 * 16;
-        CHK(sort_contacts(c, extra));
+        // (room for the ring / amide bags behind the sorted columns, as arp_fetch_packed lays them out.  An upper bound — every
+        // record counted as the table's largest, every column as rounded up by a whole 16 bytes —, so that the fetch finds the room
+        // and does not sort again)
+        size_t records = 0;
+        for (const Bag& b : c->bag) records += (size_t)b.count;
+        CHK(sort_contacts(c, bag_piece_bound(records)));
     }
     return rc_dev;
 }
@@ -4393,7 +4355,7 @@ static_assert(SIM_PLANES == ARP_SIM_PLANES && SIM_BY_RESIDUE == ARP_SIM_BY_RESID
 
 // ---- what a launch refuses
 bool five_bags_complete(const arp_ctx* c) {
-    return !c->pass_pending && c->contacts_valid && c->bag_ap.valid && c->bag_pp.valid && c->bag_gg.valid && c->bag_gp.valid;
+    return !c->pass_pending && c->contacts_valid && c->bags_valid();
 }
 int launch_refusals(arp_ctx* c, const std::string& fn, unsigned needs, const char* no_pass) {
     if ((needs & NEED_WHOLE) && (c->has_home || c->has_gid || c->shard_resident)) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
@@ -4600,15 +4562,14 @@ struct FiveBags {
     int64_t largest;
 };
 FiveBags five_bags(const arp_ctx* c, bool planes) {
-    const Bag* const bags[RESPAIR_PLANE_BAGS] = {&c->bag_ap, &c->bag_pp, &c->bag_gg, &c->bag_gp};
-    const int* const res_of[RESPAIR_PLANE_BAGS][2] = {{c->res_id.p, c->ring_res.p}, {c->ring_res.p, c->ring_res.p},
-                                                      {c->am_res.p, c->am_res.p}, {c->am_res.p, c->ring_res.p}};
+    static_assert(RESPAIR_PLANE_BAGS == BAG_KINDS, "arp_respair.h");
+    const int* const res_of[3] = {c->res_id.p, c->ring_res.p, c->am_res.p};      // by ENT_ATOM, ENT_RING, ENT_AMIDE
     FiveBags B{};
     B.k = (size_t)c->n_contacts;
     B.cap = std::max((size_t)c->n_contacts, c->out_i.cap);
     for (int m = 0; planes && m < RESPAIR_PLANE_BAGS; ++m) {
-        const Bag& b = *bags[m];
-        B.bag[m] = RespairBag{b.a.p, b.b.p, res_of[m][0], res_of[m][1], (long long)b.count, (long long)B.k};
+        const Bag& b = c->bag[m];
+        B.bag[m] = RespairBag{b.id(0), b.id(1), res_of[PLANE_TABLES[m].entity[0]], res_of[PLANE_TABLES[m].entity[1]], (long long)b.count, (long long)B.k};
         B.k += (size_t)b.count;
         B.planes += (size_t)b.count;
         B.cap += std::max((size_t)b.count, b.cap);
@@ -5411,31 +5372,22 @@ void enqueue_same_poses(arp_ctx* c, void* flag_word) {
                        (const uint32_t*)c->pplanes.xyz.p, words, (uint32_t*)flag_word);
 }
 
-// The four ring / amide tables (PplColumns, arp_poses_planes.h), of the poses-planes result and of a shortlist alike: two int32 id
-// columns, then per table this many value columns of this element size and this many byte columns, one of which holds ctype.
-// In a slab: table after table, column after column in that order, each on a 256-byte boundary.
-const struct { int n_val[4], n_byte[4]; size_t val_size[4]; int ctype_col[4]; } PLANE_TABLES = {
-    {2, 4, 3, 3}, {2, 3, 1, 1}, {sizeof(double), sizeof(double), sizeof(float), sizeof(double)}, {1, 2, 0, 0}};
-struct PlaneLayout { size_t i0[4], i1[4], d[4][4], u[4][3]; };
+// The four ring / amide tables of the poses-planes result and of a shortlist (PplColumns, arp_poses_planes.h): the columns
+// PLANE_TABLES names.  In a slab: table after table, column after column in that order, each on a 256-byte boundary.
+struct PlaneLayout { size_t col[BAG_KINDS][BAG_COLS]; };
 PlaneLayout plane_tables_layout(const size_t counts[4], size_t start, size_t* bytes) {
     PlaneLayout L{};
     size_t at = start;
-    for (int t = 0; t < 4; ++t) {
-        const size_t m = counts[t];
-        L.i0[t] = at; at += al256(m * sizeof(int));
-        L.i1[t] = at; at += al256(m * sizeof(int));
-        for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) { L.d[t][q] = at; at += al256(m * PLANE_TABLES.val_size[t]); }
-        for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) { L.u[t][q] = at; at += al256(m); }
-    }
+    for (int t = 0; t < BAG_KINDS; ++t) at = bag_slab_layout(t, counts[t], at, L.col[t]);
     *bytes = at;
     return L;
 }
 PplColumns bind_plane_columns(uint8_t* slab, const PlaneLayout& L) {      // (base, the tables' sorted positions, is the caller's)
     PplColumns col{};
-    for (int t = 0; t < 4; ++t) {
-        col.i0[t] = (int*)(slab + L.i0[t]); col.i1[t] = (int*)(slab + L.i1[t]);
-        for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) col.d[t][q] = (double*)(slab + L.d[t][q]);
-        for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) col.u[t][q] = slab + L.u[t][q];
+    for (int t = 0; t < BAG_KINDS; ++t) {
+        col.i0[t] = (int*)(slab + L.col[t][0]); col.i1[t] = (int*)(slab + L.col[t][1]);
+        for (int q = 0; q < PLANE_TABLES[t].n_val; ++q) col.d[t][q] = (double*)(slab + L.col[t][BAG_VAL0 + q]);
+        for (int q = 0; q < PLANE_TABLES[t].n_byte; ++q) col.u[t][q] = slab + L.col[t][BAG_BYTE0 + q];
     }
     return col;
 }
@@ -5460,11 +5412,11 @@ int stage_fetch(arp_ctx* c, const std::vector<StagePiece>& pieces) {
 int plane_fetch_columns(arp_ctx* c, const std::string& fn, int t, const void* first, const void* second, void* const v[4], uint8_t* const u[3], bool* records) {
     *records = first || second;
     for (int q = 0; q < 4; ++q) {
-        if (v[q] && q >= PLANE_TABLES.n_val[t]) FAIL(c, ARP_E_ARG, fn + "the table has no such value column");
+        if (v[q] && q >= PLANE_TABLES[t].n_val) FAIL(c, ARP_E_ARG, fn + "the table has no such value column");
         *records = *records || v[q];
     }
     for (int q = 0; q < 3; ++q) {
-        if (u[q] && q >= PLANE_TABLES.n_byte[t]) FAIL(c, ARP_E_ARG, fn + "the table has no such byte column");
+        if (u[q] && q >= PLANE_TABLES[t].n_byte) FAIL(c, ARP_E_ARG, fn + "the table has no such byte column");
         *records = *records || u[q];
     }
     return ARP_OK;
@@ -5473,8 +5425,8 @@ int plane_fetch_columns(arp_ctx* c, const std::string& fn, int t, const void* fi
 void plane_fetch_pieces(std::vector<StagePiece>& pieces, const PplColumns& col, int t, size_t k, void* first, void* second, void* const v[4], uint8_t* const u[3]) {
     want_piece(pieces, first, col.i0[t], k * sizeof(int32_t));
     want_piece(pieces, second, col.i1[t], k * sizeof(int32_t));
-    for (int q = 0; q < PLANE_TABLES.n_val[t]; ++q) want_piece(pieces, v[q], col.d[t][q], k * PLANE_TABLES.val_size[t]);
-    for (int q = 0; q < PLANE_TABLES.n_byte[t]; ++q) want_piece(pieces, u[q], col.u[t][q], k);
+    for (int q = 0; q < PLANE_TABLES[t].n_val; ++q) want_piece(pieces, v[q], col.d[t][q], k * PLANE_TABLES[t].val_size);
+    for (int q = 0; q < PLANE_TABLES[t].n_byte; ++q) want_piece(pieces, u[q], col.u[t][q], k);
 }
 
 // Append until it fits: `launch(cap)` reserves room for cap records, zeroes the counters and launches; the first `words` counters
@@ -5917,7 +5869,7 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     int64_t k_classes = 0;
     if (classes) {
         for (int t = 0; t < 4; ++t) {
-            T.first[t] = L.col.i0[t]; T.second[t] = L.col.i1[t]; T.ctype[t] = L.col.u[t][PLANE_TABLES.ctype_col[t]];
+            T.first[t] = L.col.i0[t]; T.second[t] = L.col.i1[t]; T.ctype[t] = L.col.u[t][PLANE_TABLES[t].ctype_col];
             T.count[t] = L.counts[t];
             k_classes = std::max(k_classes, L.counts[t]);
         }

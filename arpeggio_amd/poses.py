@@ -24,6 +24,7 @@ import os
 
 import numpy as np
 
+from . import tables
 from .core import config
 
 N_BITS = 15
@@ -201,15 +202,10 @@ def reference_rows(bag, sel_mask):
 # A result (``table``) is a dict with one sub-table per bag — the columns ``Context.fetch_bag`` gives that bag plus ``pose_off``
 # uint64 [P + 1], the records of a pose in the bag's canonical order —, ``summary`` uint32 [P, 16] and ``movable``.
 # ---------------------------------------------------------------------------------------------------------------------
-PLANE_TABLES = ('atom_plane', 'plane_plane', 'group_group', 'group_plane')
+PLANE_TABLES = tables.PLANE_BAGS
 # per table: id columns, value columns, byte columns, dtype of the value columns (the order of arp_poses_planes_fetch's arguments)
-PLANE_COLUMNS = {
-    'atom_plane': (('atom', 'ring'), ('dist', 'theta'), ('mask', 'ctype'), np.float64),
-    'plane_plane': (('bgn', 'end'), ('dist', 'dihedral', 'theta_bgn', 'theta_end'), ('type1', 'type2', 'ctype'), np.float64),
-    'group_group': (('bgn', 'end'), ('dist', 'dihedral', 'theta'), ('ctype',), np.float32),
-    'group_plane': (('amide', 'ring'), ('dist', 'dihedral', 'theta'), ('ctype',), np.float64),
-}
-PLANE_ORDER = {'atom_plane': ('ring', 'atom'), 'plane_plane': ('bgn', 'end'), 'group_group': ('bgn', 'end'), 'group_plane': ('amide', 'ring')}
+PLANE_COLUMNS = {name: (tuple(c for c, _ in b.ids), b.vals, b.bytes, b.vdt) for name, b in tables.BAGS.items()}
+PLANE_ORDER = {name: b.order for name, b in tables.BAGS.items()}
 PLANE_SUMMARY_SLOTS = ('atom_plane', 'plane_plane', 'group_group', 'group_plane', 'inter_carbonpi', 'inter_cationpi', 'inter_donorpi',
                        'inter_halogenpi', 'inter_metsulphurpi', 'inter_plane_plane', 'inter_group_group', 'inter_group_plane',
                        'affected_rings', 'rings_residue_changed', 'rings_without_residue', 'records')
@@ -218,8 +214,7 @@ CT_INTER = config.CONTACT_TYPE_NAMES.index('INTER')
 
 def plane_columns(name):
     """Every record column of table ``name`` with its dtype, in fetch order."""
-    ids, vals, byts, vdt = PLANE_COLUMNS[name]
-    return [(c, np.int32) for c in ids] + [(c, vdt) for c in vals] + [(c, np.uint8) for c in byts]
+    return [(c, dt) for c, dt, _ in tables.bag_columns(name)]
 
 
 def _kd2(a, b):

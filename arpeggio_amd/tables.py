@@ -14,8 +14,41 @@ import numpy as np
 from .core import config
 
 N_BITS = 15       # SIFt bits with a count of their own (ARP_*_BITS): config.SIFT_NAMES[:15]
-PLANE_BAGS = ('atom_plane', 'plane_plane', 'group_group', 'group_plane')
+
+
+class Bag(NamedTuple):
+    """One ring / amide bag: its columns in the order of the C fetches' arguments (PLANE_TABLES in csrc/arp_bag_table.h says the same)."""
+    ids: tuple          # the two int32 id columns, each (name, what it indexes: 'atom' | 'ring' | 'amide')
+    vals: tuple         # the value columns
+    vdt: type           # ... and their dtype
+    bytes: tuple        # the uint8 columns
+    order: tuple        # the id columns of the canonical order, major key first
+
+
+BAGS = {
+    'atom_plane': Bag((('atom', 'atom'), ('ring', 'ring')), ('dist', 'theta'), np.float64, ('mask', 'ctype'), ('ring', 'atom')),
+    'plane_plane': Bag((('bgn', 'ring'), ('end', 'ring')), ('dist', 'dihedral', 'theta_bgn', 'theta_end'), np.float64,
+                       ('type1', 'type2', 'ctype'), ('bgn', 'end')),
+    'group_group': Bag((('bgn', 'amide'), ('end', 'amide')), ('dist', 'dihedral', 'theta'), np.float32, ('ctype',), ('bgn', 'end')),
+    'group_plane': Bag((('amide', 'amide'), ('ring', 'ring')), ('dist', 'dihedral', 'theta'), np.float64, ('ctype',), ('amide', 'ring')),
+}
+PLANE_BAGS = tuple(BAGS)
+PACKED_ORDER = ('plane_plane', 'atom_plane', 'group_group', 'group_plane')      # get_contacts: arp_fetch_packed's counts[1..4] and b
 CLASSES = ('atom_atom',) + PLANE_BAGS
+
+
+def bag_columns(name):
+    """Every column of bag ``name`` as (name, dtype, slot), in fetch order.  slot: its place among the twelve offsets a bag has in
+    a packed fetch — ids 0 and 1, 8-byte values from 2, 4-byte values from 6, bytes from 9."""
+    b = BAGS[name]
+    v0 = 2 if np.dtype(b.vdt).itemsize == 8 else 6
+    return [(c, np.int32, q) for q, (c, _) in enumerate(b.ids)] + [(c, b.vdt, v0 + q) for q, c in enumerate(b.vals)] + \
+           [(c, np.uint8, 9 + q) for q, c in enumerate(b.bytes)]
+
+
+def bag_buffers(name, cap, make=np.empty):
+    """The columns of bag ``name`` for ``cap`` records, each made by ``make(cap, dtype)``."""
+    return [make(cap, dt) for _, dt, _ in bag_columns(name)]
 
 
 class Spec(NamedTuple):
