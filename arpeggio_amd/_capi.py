@@ -54,6 +54,8 @@ SYMBOLS = (
     'arp_poses_fingerprints_planes_launch',
     'arp_poses_shortlist_launch', 'arp_poses_shortlist_fetch', 'arp_poses_shortlist_planes_fetch', 'arp_poses_shortlist_info',
     'arp_poses_clusters_launch', 'arp_poses_clusters_fetch', 'arp_poses_clusters_info',
+    'arp_set_ligand_library', 'arp_library_contacts_launch', 'arp_library_contacts_fetch', 'arp_library_info',
+    'arp_library_best_launch', 'arp_library_best_fetch',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -68,6 +70,8 @@ POSEFP_ALL_PLANES = 29           # ARP_POSEFP_ALL_PLANES: the SIFt bits and the 
 # ... their shortlist (ARP_SHORTLIST_*)
 SHORTLIST_LIST, SHORTLIST_SUMMARY, SHORTLIST_TANIMOTO, SHORTLIST_TABLES, SHORTLIST_MAX_WEIGHT = 0, 1, 2, 5, 1 << 24
 INT64_MIN = -(1 << 63)
+# a ligand library on the resident receptor (ARP_LIBRARY_*)
+LIBRARY_MAX_LIGANDS, LIBRARY_MAX_ATOMS = 1 << 16, 256
 # ... their clusters (ARP_POSECL_*; the rounds enqueued between two waits of arp_poses_clusters_launch)
 POSECL_MAX_CLUSTERS, POSECL_ROUNDS_PER_WAIT = 4096, 64
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
@@ -262,6 +266,12 @@ def load():
     L.arp_poses_clusters_launch.argtypes = [vp, vp, i64, i64, C.c_uint64, i64, vp]
     L.arp_poses_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 6 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_poses_clusters_info.argtypes = [vp, vp]
+    L.arp_set_ligand_library.argtypes = [vp, i64] + [vp] * 7
+    L.arp_library_contacts_launch.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(i64)]
+    L.arp_library_contacts_fetch.argtypes = [vp, i64] + [vp] * 7 + [C.POINTER(i64)]
+    L.arp_library_info.argtypes = [vp, vp]
+    L.arp_library_best_launch.argtypes = [vp, vp]
+    L.arp_library_best_fetch.argtypes = [vp, i64, vp, vp, vp, C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1194,6 +1204,106 @@ class Context:
         info = np.zeros(8, np.int64)
         self._check(self._L.arp_poses_clusters_info(self._h, _p(info)), 'arp_poses_clusters_info')
         return dict(zip(('positions', 'clusters', 'unassigned', 'max_clusters', 'words', 'lanes', 'launches', 'threshold_q32'), (int(v) for v in info)))
+
+    # ---- a ligand library on the resident receptor (arp_library_*; ``arpeggio_amd.ligand_library``) ----
+    def set_ligand_library(self, lib):
+        """The ligand library beside the receptor (arp_set_ligand_library): ``lib`` as ``ligand_library.pack`` gives it.  It
+        stays resident through new structures; a new library replaces it and voids the library result."""
+        arr = dict(atom_off=np.ascontiguousarray(lib['atom_off'], np.int32), type_mask=np.ascontiguousarray(lib['type_mask'], np.uint16),
+                   flags=np.ascontiguousarray(lib['flags'], np.uint16), vdw=np.ascontiguousarray(lib['vdw'], np.float64),
+                   cov=np.ascontiguousarray(lib['cov'], np.float64), h_off=np.ascontiguousarray(lib['h_off'], np.int32),
+                   sb_nbr=np.ascontiguousarray(lib['sb_nbr'], np.int32))
+        L = len(arr['atom_off']) - 1
+        if L < 1 or arr['atom_off'].ndim != 1:
+            raise ValueError('set_ligand_library: atom_off must be [L + 1] with L >= 1')
+        TA = int(arr['atom_off'][-1])
+        # (the library reads TA entries of every per-atom array and TA + 1 offsets: their lengths are checked here)
+        for k in ('type_mask', 'flags', 'vdw', 'cov', 'sb_nbr'):
+            if arr[k].shape != (max(TA, 0),):
+                raise ValueError(f'set_ligand_library: {k} must hold atom_off[-1] = {TA} entries')
+        if arr['h_off'].shape != (max(TA, 0) + 1,):
+            raise ValueError(f'set_ligand_library: h_off must hold atom_off[-1] + 1 = {TA + 1} entries')
+        self._check(self._L.arp_set_ligand_library(self._h, L, _p(arr['atom_off']), _p(arr['type_mask']), _p(arr['flags']), _p(arr['vdw']),
+                                                   _p(arr['cov']), _p(arr['h_off']), _p(arr['sb_nbr'])), 'arp_set_ligand_library')
+        self._library = dict(atom_off=arr['atom_off'].astype(np.int64), h_off=arr['h_off'].astype(np.int64))
+
+    def _library_launch(self, pose_off, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent):
+        """Lengths checked against the resident library and ``pose_off``, then arp_library_contacts_launch; returns (T, records)."""
+        lib = getattr(self, '_library', None)
+        if lib is None:
+            raise ValueError('library_contacts: no ligand library (set_ligand_library)')
+        L = len(lib['atom_off']) - 1
+        off = np.ascontiguousarray(pose_off, np.int64)
+        if off.shape != (L + 1,):
+            raise ValueError(f'library_contacts: pose_off must be [{L + 1}] (one entry per ligand of the library, and the total)')
+        P = np.diff(off)
+        S = np.diff(lib['atom_off'])
+        SH = lib['h_off'][lib['atom_off'][1:]] - lib['h_off'][lib['atom_off'][:-1]]
+        ok = off[0] == 0 and (P >= 0).all()
+        nx, nh = (int((P * S).sum()) * 3, int((P * SH).sum()) * 3) if ok else (0, 0)
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1)
+        hx = np.zeros(0) if h_xyz is None else np.ascontiguousarray(h_xyz, np.float64).reshape(-1)
+        if ok and len(x) != nx:
+            raise ValueError(f'library_contacts: xyz must hold {nx} values (sum of P_l S_l 3, ligand-major then pose-major)')
+        if ok and len(hx) != nh:
+            raise ValueError(f'library_contacts: h_xyz must hold {nh} values (sum of P_l SH_l 3, ligand-major then pose-major)')
+        n = C.c_int64(0)
+        rc = self._L.arp_library_contacts_launch(self._h, _p(off), _p(x), _p(hx) if len(hx) else None, float(cutoff), float(vdw_comp),
+                                                 int(bool(include_sequence_adjacent)), C.byref(n))
+        try:
+            self._check(rc, 'arp_library_contacts_launch')
+        except NativeLibraryError as e:
+            e.n_records = int(n.value)
+            raise
+        return int(off[-1]), int(n.value), off
+
+    def library_contacts(self, pose_off, xyz, h_xyz, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False):
+        """Every (ligand, pose)'s receptor - ligand contacts in one launch (arp_library_contacts_*).  ``pose_off`` int64 [L + 1]
+        over the ligands of the resident library; ``xyz`` float32 and ``h_xyz`` float64, ligand-major then pose-major (flat or
+        any shape of the right size; ``ligand_library.flatten_poses`` makes them).  Returns a dict: ``i`` (the receptor's packed
+        id), ``a`` (the atom's index within its ligand), ``dist``, ``sift``, ``ctype`` in ascending (global pose, i, a),
+        ``pose_off`` uint64 [T + 1], ``summary`` uint32 [T, 16] and ``ligand_pose_off`` int64 [L + 1] (the argument)."""
+        T, k, off = self._library_launch(pose_off, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
+        t = dict(i=np.empty(k, np.int32), a=np.empty(k, np.int32), dist=np.empty(k, np.float32), sift=np.empty(k, np.uint16),
+                 ctype=np.empty(k, np.uint8), pose_off=np.empty(T + 1, np.uint64), summary=np.empty((T, POSES_SUMMARY), np.uint32))
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_contacts_fetch(self._h, k, _p(t['pose_off']), _p(t['i']), _p(t['a']), _p(t['dist']), _p(t['sift']),
+                                                       _p(t['ctype']), _p(t['summary']), C.byref(n)), 'arp_library_contacts_fetch')
+        t['ligand_pose_off'] = off
+        return t
+
+    def library_summary(self, pose_off, xyz, h_xyz, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False):
+        """``library_contacts`` with only the per-pose summary copied to the host: uint32 [T, 16]."""
+        T, _, _ = self._library_launch(pose_off, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
+        s = np.empty((T, POSES_SUMMARY), np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_contacts_fetch(self._h, 0, None, None, None, None, None, None, _p(s), C.byref(n)),
+                    'arp_library_contacts_fetch')
+        return s
+
+    def library_best(self, weights):
+        """The best pose of every ligand of the resident library result by ``weights`` int32 [16] over its summary row
+        (arp_library_best_*): a dict of ``n_poses`` int64 [L], ``best_pose`` int32 [L] (global pose id, -1: the ligand has no
+        pose) and ``score`` int64 [L] (INT64_MIN there).  20 bytes per ligand come back."""
+        w = np.ascontiguousarray(weights, np.int64).reshape(-1)
+        if w.shape != (POSES_SUMMARY,) or (np.abs(w) > SHORTLIST_MAX_WEIGHT).any():
+            raise ValueError('library_best: weights must be 16 integers with |w| <= SHORTLIST_MAX_WEIGHT')
+        w32 = w.astype(np.int32)
+        self._check(self._L.arp_library_best_launch(self._h, _p(w32)), 'arp_library_best_launch')
+        L = self.library_info()['ligands']
+        out = dict(n_poses=np.empty(L, np.int64), best_pose=np.empty(L, np.int32), score=np.empty(L, np.int64))
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_best_fetch(self._h, L, _p(out['n_poses']), _p(out['best_pose']), _p(out['score']), C.byref(n)),
+                    'arp_library_best_fetch')
+        return out
+
+    def library_info(self):
+        """arp_library_info: ligands, atoms, hydrogen rows and the largest ligand of the resident library; poses, records and
+        the blocks of the launch of the resident result (zeros while there is none); whether a best-pose table is resident."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_info(self._h, _p(info)), 'arp_library_info')
+        return dict(ligands=int(info[0]), poses=int(info[1]), records=int(info[2]), atoms=int(info[3]), hydrogens=int(info[4]),
+                    blocks=int(info[5]), max_atoms=int(info[6]), best=bool(info[7]))
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

@@ -454,6 +454,51 @@ class InteractionComplex:
             raise AttributeError('no poses yet: call run_poses() first')
         return _poses.write_poses(wd, self.id, self.poses, self.pc, self.component_types)
 
+    def run_ligand_library(self, ligands, poses, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None, weights=None):
+        """Extension beside the mirror: the contacts of many DIFFERENT ligands, each with its poses, against this structure as
+        the fixed receptor (``arpeggio_amd.ligand_library``; ``run_poses`` moves one ligand that is part of the structure).
+        ``ligands`` are packs of one residue each (``ligand_library.pack`` says what is refused); ``poses`` holds per ligand
+        ``(xyz float32 [P_l, S_l, 3], h_xyz float64 [P_l, SH_l, 3] or None)``, or None for a ligand without poses.  Per (ligand,
+        pose) the result holds exactly the atom-atom records between the receptor and the ligand that ``run_arpeggio`` would find
+        on the receptor with the ligand appended as one more residue and selected.  The receptor is uploaded once and the library
+        once; ``chunk`` cuts the launches by total poses (default: all at once, at most ``_capi.POSES_MAX_POSES``; a ligand's
+        poses may be cut between two launches).  Returns the table ``ligand_library`` describes (kept in ``self.ligand_library``,
+        the ligands in ``self.ligand_library_ligands``).  ``weights`` int [16]: also the best pose per ligand by the weighted sum
+        of its summary row (``self.ligand_library_best``): from the device when one launch held every pose, else the host mirror
+        over the joined summaries.  The results of the last ``run_arpeggio`` and of ``run_poses`` stay as they are."""
+        from .. import _capi, ligand_library as _ll
+        if self._ctx is None:
+            self.initialize()
+        ctx = self._ctx
+        ligands = list(ligands)
+        lib = _ll.pack(ligands)
+        off, x, h = _ll.flatten_poses(lib, poses)
+        if off[-1] < 1:
+            raise ValueError('run_ligand_library: no pose given')
+        ctx.set_ligand_library(lib)
+        S, SH = _ll.sizes(lib)
+        x_at = np.concatenate([[0], np.cumsum(np.diff(off) * S * 3)])
+        h_at = np.concatenate([[0], np.cumsum(np.diff(off) * SH * 3)])
+        parts = []
+        for off_c, a, b in _ll.chunk_plan(off, chunk if chunk else _capi.POSES_MAX_POSES):
+            # the coordinates of the global poses a ... b - 1: of every ligand its poses inside the range
+            first = np.clip(off, a, b) - off                       # (how many of the ligand's poses come before the range)
+            xs = [x[x_at[l] + first[l] * S[l] * 3:x_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * S[l] * 3] for l in range(len(S))]
+            hs = [h[h_at[l] + first[l] * SH[l] * 3:h_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * SH[l] * 3] for l in range(len(S))]
+            parts.append(ctx.library_contacts(off_c, np.concatenate(xs), np.concatenate(hs), interacting_cutoff, vdw_comp, include_sequence_adjacent))
+        self.ligand_library = parts[0] if len(parts) == 1 else _ll.concat(parts)
+        self.ligand_library_ligands = ligands
+        if weights is not None:
+            self.ligand_library_best = ctx.library_best(weights) if len(parts) == 1 else _ll.best(self.ligand_library, weights)
+        return self.ligand_library
+
+    def write_ligand_library(self, wd):
+        """'<id>.library': the table of the last ``run_ligand_library`` as CSV, one row per record (``ligand_library.write_csv``)."""
+        from .. import ligand_library as _ll
+        if getattr(self, 'ligand_library', None) is None:
+            raise AttributeError('no ligand library result yet: call run_ligand_library() first')
+        return _ll.write_library(wd, self.id, self.ligand_library, self.pc, self.ligand_library_ligands, self.component_types)
+
     def write_pose_planes(self, wd):
         """'<id>.poseplanes': the ring / amide tables of the last ``run_poses(..., planes=True)`` as CSV (``poses.write_planes_csv``)."""
         from .. import poses as _poses

@@ -44,6 +44,7 @@
 #include "arp_poses_fingerprints.h"
 #include "arp_poses_shortlist.h"
 #include "arp_poses_clusters.h"
+#include "arp_library.h"
 #include "arp_blob.h"
 
 namespace {
@@ -309,6 +310,42 @@ struct PosesResult {
     void release() {
         sel_h.release(); pos_of.release(); xyz.release(); hx.release(); ctr.release(); summary.release(); pose_off.release(); sort.release();
         slab.release(); movable_static = movable_sel = 0; valid = false;
+    }
+};
+
+// the ligand library (arp_set_ligand_library, arp_library.h): the ligands' per-atom table beside the receptor.  It reads nothing of
+// the resident structure and stays through new structures; the host keeps the offsets a launch lays its poses out by
+struct LigandLibrary {
+    DevBuf<int> atom_off, h_off, sb_nbr;
+    DevBuf<uint16_t> tmask, flags;
+    DevBuf<double2> rad;
+    std::vector<int> host_atom_off, host_hrows;         // [L + 1]; [L] hydrogen rows of ligand l
+    int64_t L = 0, atoms = 0, hrows = 0;
+    int max_atoms = 0;
+    bool resident = false;
+    void release() { atom_off.release(); h_off.release(); sb_nbr.release(); tmask.release(); flags.release(); rad.release(); resident = false; }
+};
+// the contacts of a launch over the library (arp_library_contacts_launch): the uploaded poses and their per-pose / per-ligand
+// tables, the appended records and their sort, the columns in one slab; and the best pose per ligand made from its summary
+// (arp_library_best_launch), which goes with it (void_pose_results)
+struct LibraryResult {
+    DevBuf<float> xyz;
+    DevBuf<double> hx;
+    DevBuf<int> lig_of;
+    DevBuf<long long> tab;                              // pose_off [L + 1] | xyz_at [L] | hx_at [L]
+    DevBuf<unsigned long long> ctr;                     // [0] records appended, [1] device error
+    DevBuf<uint32_t> summary;
+    DevBuf<unsigned long long> pose_off;
+    SortScratch sort;
+    DevBuf<uint8_t> slab;
+    size_t off[5] = {0, 0, 0, 0, 0};
+    DevBuf<long long> best_n, best_score;
+    DevBuf<int> best_pose;
+    int64_t L = 0, T = 0, count = 0, blocks = 0;
+    bool valid = false, best_valid = false;
+    void release() {
+        xyz.release(); hx.release(); lig_of.release(); tab.release(); ctr.release(); summary.release(); pose_off.release(); sort.release();
+        slab.release(); best_n.release(); best_score.release(); best_pose.release(); valid = best_valid = false;
     }
 };
 
@@ -649,6 +686,8 @@ struct arp_ctx {
     PoseFpResult posefp;                  // arp_poses_fingerprints_launch
     ShortlistResult shortlist;            // arp_poses_shortlist_launch
     ClustersResult clusters;              // arp_poses_clusters_launch
+    LigandLibrary library;                // arp_set_ligand_library
+    LibraryResult libres;                 // arp_library_contacts_launch, arp_library_best_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -851,14 +890,18 @@ void void_results(arp_ctx* c, unsigned lost) {
 
 // The same rule for the results of the ligand-pose family (DESIGN.md 5o ... 5s), which read no bag: `lost` names what was
 // replaced or is about to be — the structure, the selection, or one of the rows below itself.  A row goes when it
-// is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The fingerprint and the
+// is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The ligand-library result
+//  is a row of the same table: it reads the structure and the library (POSE_LIBRARY, lost by
+// arp_set_ligand_library) and NO selection.  The fingerprint and the
 // shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight; the
 // clusters read the fingerprint result only while their launch runs, so they stand behind what THAT was made from, not behind it.
 // A launch names its own result here before it writes it, and sets it valid again at its end.
 enum : unsigned {
     POSE_STRUCTURE = 1u << 0, POSE_SELECTION = 1u << 1, POSE_PLANE_ATOMS = 1u << 2, POSE_MOVABLE = 1u << 3, POSE_CONTACTS = 1u << 4,
     POSE_PLANES = 1u << 5, POSE_FINGERPRINT = 1u << 6, POSE_SHORTLIST = 1u << 7,
-    POSE_CLUSTERS = 1u << 8
+    POSE_CLUSTERS = 1u << 8,
+    POSE_LIBRARY = 1u << 9,           // the ligand library itself (arp_set_ligand_library)
+    POSE_LIBRARY_CONTACTS = 1u << 10, POSE_LIBRARY_BEST = 1u << 11
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -869,7 +912,10 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->poses.valid, POSE_CONTACTS, inputs},       // (its movable tables go by static_epoch / sel_epoch)
         {&c->posefp.valid, POSE_FINGERPRINT, POSE_CONTACTS | (c->posefp.classes ? POSE_PLANES : 0u)},
         {&c->shortlist.valid, POSE_SHORTLIST, POSE_CONTACTS | (c->shortlist.planes ? POSE_PLANES : 0u)},
-        {&c->clusters.valid, POSE_CLUSTERS, POSE_CONTACTS | (c->clusters.classes ? POSE_PLANES : 0u)}};
+        {&c->clusters.valid, POSE_CLUSTERS, POSE_CONTACTS | (c->clusters.classes ? POSE_PLANES : 0u)},
+        // the library result reads the structure and the library, no selection; the best-pose table reads its summary
+        {&c->libres.valid, POSE_LIBRARY_CONTACTS, POSE_STRUCTURE | POSE_LIBRARY},
+        {&c->libres.best_valid, POSE_LIBRARY_BEST, POSE_LIBRARY_CONTACTS}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -2478,6 +2524,8 @@ void arp_destroy(arp_ctx* c) {
     c->posefp.release();
     c->shortlist.release();
     c->clusters.release();
+    c->library.release();
+    c->libres.release();
     c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -5341,13 +5389,18 @@ int arp_models_coupling_info(arp_ctx* c, int64_t info[4]) {
 
 // ---- the ligand-pose family (DESIGN.md 5o ... 5s): what its entries share
 namespace {
-// what both pose launches refuse first, in this order
-int pose_launch_refusals(arp_ctx* c, const std::string& fn, int64_t n_poses) {
+// what every launch on a resident receptor refuses first, in this order (the pose launches, the ligand-library launch)
+int receptor_refusals(arp_ctx* c, const std::string& fn) {
     if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
     if (c->n <= 0) FAIL(c, ARP_E_ARG, fn + "no structure resident");
     if (c->models_n > 0) FAIL(c, ARP_E_ARG, fn + "models are resident (the receptor is one structure)");
     if (c->batch_n > 0) FAIL(c, ARP_E_ARG, fn + "a batch is resident (the receptor is one structure)");
     if (c->has_home || c->has_gid || c->shard_resident) FAIL(c, ARP_E_ARG, fn + "not for a shard of a distributed structure");
+    return ARP_OK;
+}
+// what both pose launches refuse first, in this order
+int pose_launch_refusals(arp_ctx* c, const std::string& fn, int64_t n_poses) {
+    CHK(receptor_refusals(c, fn));
     if (!c->sel_uploaded || c->nsel < 0) FAIL(c, ARP_E_ARG, fn + "no uploaded selection (arp_set_selection names the movable set)");
     if (c->sel_all || c->whole_structure || c->nsel >= c->n) FAIL(c, ARP_E_ARG, fn + "the selection is the whole structure (nothing is left as the receptor)");
     if (c->nsel < 1 || c->nsel > POSES_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "the movable set must hold 1 ... ARP_POSES_MAX_ATOMS selected atoms");
@@ -5581,6 +5634,238 @@ int arp_poses_contacts_info(arp_ctx* c, int64_t info[4]) {
     info[2] = R.valid ? R.SH : 0;
     info[3] = R.valid ? R.count : 0;
     return ARP_OK;
+}
+
+// ---- a ligand library on the resident receptor (arp_library.h): different ligands, each with its poses, one launch
+// The library is a table beside the receptor: nothing of the resident structure is read to make it and a new structure leaves it
+// resident.  A launch reads the receptor's static columns in the cell order of ensure_static(cutoff), the library and the
+// uploaded poses; records are appended as (key, payload), sorted by every bit of the key on the result's own scratch and unpacked
+// into a slab laid out as the sorted atom-atom bag is.  One wait a launch: the record count with the device's error word (the
+// hydrogen rows are known to the host: no wait for SH).
+static_assert(LIB_MAX_LIGANDS == ARP_LIBRARY_MAX_LIGANDS && LIB_MAX_ATOMS == ARP_LIBRARY_MAX_ATOMS, "arp_library.h names the header's limits");
+const int LIB_BLOCKS_PER_CU = 4;      // the grid of k_library_contacts: min(T, this many blocks per CU), poses taken with a grid stride
+
+int arp_set_ligand_library(arp_ctx* c, int64_t n_ligands, const int32_t* atom_off, const uint16_t* type_mask, const uint16_t* flags,
+                           const double* vdw, const double* cov, const int32_t* h_off, const int32_t* sb_nbr) {
+    if (!c) return ARP_E_ARG;
+    const std::string fn = "arp_set_ligand_library: ";
+    // ---- the refusals, in this order: none of them touches the resident library or its result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (n_ligands < 1 || n_ligands > LIB_MAX_LIGANDS) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_LIBRARY_MAX_LIGANDS ligands");
+    if (!atom_off || !type_mask || !flags || !vdw || !cov || !h_off || !sb_nbr) FAIL(c, ARP_E_ARG, fn + "an array is missing");
+    const int64_t L = n_ligands;
+    if (atom_off[0] != 0) FAIL(c, ARP_E_ARG, fn + "atom_off must start at 0");
+    int max_atoms = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const int64_t S = (int64_t)atom_off[l + 1] - atom_off[l];
+        if (S < 1 || S > LIB_MAX_ATOMS) FAIL(c, ARP_E_ARG, fn + "atom_off: a ligand must hold 1 ... ARP_LIBRARY_MAX_ATOMS atoms");
+        max_atoms = std::max(max_atoms, (int)S);
+    }
+    const int64_t TA = atom_off[L];
+    if (h_off[0] != 0) FAIL(c, ARP_E_ARG, fn + "h_off must start at 0");
+    for (int64_t a = 0; a < TA; ++a)
+        if (h_off[a + 1] < h_off[a]) FAIL(c, ARP_E_ARG, fn + "h_off must not decrease");
+    for (int64_t a = 0; a < TA; ++a)
+        if (!std::isfinite(vdw[a]) || !std::isfinite(cov[a]) || vdw[a] < 0 || cov[a] < 0) FAIL(c, ARP_E_ARG, fn + "radii must be finite and not negative");
+    for (int64_t l = 0; l < L; ++l)
+        for (int a = atom_off[l]; a < atom_off[l + 1]; ++a) {
+            const int k = sb_nbr[a], S = atom_off[l + 1] - atom_off[l];
+            if (k < -1 || k >= S || k == a - atom_off[l]) FAIL(c, ARP_E_ARG, fn + "sb_nbr must be -1 or the index of another atom of the same ligand");
+        }
+    // ---- from here on the library before is gone, and its result
+    HIPCHK(c, hipSetDevice(c->device));
+    void_pose_results(c, POSE_LIBRARY);
+    LigandLibrary& B = c->library;
+    B.resident = false;
+    std::vector<double2> rad((size_t)TA);
+    for (int64_t a = 0; a < TA; ++a) rad[(size_t)a] = make_double2(vdw[a], cov[a]);
+    CHK(upload_async(c, B.atom_off, atom_off, (size_t)L + 1));
+    CHK(upload_async(c, B.tmask, type_mask, (size_t)TA));
+    CHK(upload_async(c, B.flags, flags, (size_t)TA));
+    CHK(upload_async(c, B.h_off, h_off, (size_t)TA + 1));
+    CHK(upload_async(c, B.sb_nbr, sb_nbr, (size_t)TA));
+    CHK(upload(c, B.rad, rad.data(), (size_t)TA));      // (waits: the caller's arrays and `rad` are free after this)
+    B.host_atom_off.assign(atom_off, atom_off + L + 1);
+    B.host_hrows.resize((size_t)L);
+    for (int64_t l = 0; l < L; ++l) B.host_hrows[(size_t)l] = h_off[atom_off[l + 1]] - h_off[atom_off[l]];
+    B.L = L; B.atoms = TA; B.hrows = h_off[TA]; B.max_atoms = max_atoms; B.resident = true;
+    return ARP_OK;
+}
+
+int arp_library_contacts_launch(arp_ctx* c, const int64_t* pose_off, const float* xyz, const double* h_xyz, double cutoff, double vdw_comp,
+                                int include_sequence_adjacent, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    (void)include_sequence_adjacent;      // (accepted and without effect: the gate needs M_RES_HASSEQ on both atoms, a ligand has none)
+    const std::string fn = "arp_library_contacts_launch: ";
+    // ---- the refusals, in this order: none of them touches a resident result
+    CHK(receptor_refusals(c, fn));
+    if (c->n >= POSES_MAX_N) FAIL(c, ARP_E_ARG, fn + "2^21 atoms or more (the sort key holds 21 bits of the receptor's atom id)");
+    const LigandLibrary& B = c->library;
+    if (!B.resident) FAIL(c, ARP_E_ARG, fn + "no ligand library (arp_set_ligand_library)");
+    if (!pose_off) FAIL(c, ARP_E_ARG, fn + "pose_off missing");
+    const int64_t L = B.L;
+    if (pose_off[0] != 0) FAIL(c, ARP_E_ARG, fn + "pose_off must start at 0");
+    for (int64_t l = 0; l < L; ++l)
+        if (pose_off[l + 1] < pose_off[l]) FAIL(c, ARP_E_ARG, fn + "pose_off must not decrease");
+    const int64_t T = pose_off[L];
+    if (T < 1 || T > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    if (!(cutoff > 0) || !(cutoff <= ARP_POSES_MAX_CUTOFF)) FAIL(c, ARP_E_ARG, fn + "cutoff must be in (0, 6.0]");
+    if (!std::isfinite(vdw_comp)) FAIL(c, ARP_E_ARG, fn + "vdw_comp is not finite");
+    if (!xyz) FAIL(c, ARP_E_ARG, fn + "xyz missing");
+    // where every ligand's poses begin in the two coordinate arrays (ligand-major, then pose-major), and the ligand of every pose
+    std::vector<long long> tab(3 * (size_t)L + 1);
+    std::vector<int> lig_of((size_t)T);
+    long long nx = 0, nh = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const long long P = pose_off[l + 1] - pose_off[l], S = B.host_atom_off[(size_t)l + 1] - B.host_atom_off[(size_t)l];
+        tab[(size_t)l] = pose_off[l];
+        tab[(size_t)(L + 1 + l)] = nx;
+        tab[(size_t)(2 * L + 1 + l)] = nh;
+        nx += P * S * 3;
+        nh += P * (long long)B.host_hrows[(size_t)l] * 3;
+        std::fill(lig_of.begin() + pose_off[l], lig_of.begin() + pose_off[l + 1], (int)l);
+    }
+    tab[(size_t)L] = T;
+    if (nh > 0 && !h_xyz) FAIL(c, ARP_E_ARG, fn + "h_xyz missing (a posed ligand has hydrogen rows)");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    CHK(ensure_static(c, cutoff));
+    // ---- from here on the previous result is gone, and the best-pose table made from it
+    LibraryResult& R = c->libres;
+    void_pose_results(c, POSE_LIBRARY_CONTACTS);
+    R.count = 0;
+    HIPCHK(c, R.xyz.reserve((size_t)std::max<long long>(nx, 1)));
+    HIPCHK(c, R.hx.reserve((size_t)std::max<long long>(nh, 1)));
+    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (nh > 0) HIPCHK(c, hipMemcpyAsync(R.hx.p, h_xyz, (size_t)nh * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    CHK(upload_async(c, R.tab, tab.data(), tab.size()));
+    CHK(upload_async(c, R.lig_of, lig_of.data(), lig_of.size()));
+    HIPCHK(c, R.ctr.reserve(2));
+    HIPCHK(c, R.summary.reserve((size_t)T * POSES_SUMMARY));
+    HIPCHK(c, R.pose_off.reserve((size_t)T + 1));
+    LibraryArgs A{};
+    A.n = (int)c->n; A.T = (int)T;
+    A.atom_off = B.atom_off.p; A.tmask = B.tmask.p; A.flags = B.flags.p; A.lrad = B.rad.p; A.lh_off = B.h_off.p; A.lsb_nbr = B.sb_nbr.p;
+    A.lig_of = R.lig_of.p; A.first_pose = R.tab.p; A.xyz_at = R.tab.p + L + 1; A.hx_at = R.tab.p + 2 * L + 1;
+    A.pxyz = R.xyz.p; A.phx = R.hx.p;
+    A.rad = c->rad.p; A.sb = c->sb.p; A.h_off = c->h_off.p; A.h_xyz = c->h_xyz_d.p;
+    A.sp_xyzm = c->sp_xyzm.p; A.sp_aux = c->sp_aux.p; A.sp_qa = c->sp_qa.p; A.sp_h = c->sp_h.p;
+    A.start = c->sp_cnt.p + 4; A.g = c->sp_grid;
+    A.r2 = cutoff * cutoff; A.comp = vdw_comp;
+    A.ibits = index_bits(c->n); A.abits = index_bits(B.max_atoms);
+    A.count = R.ctr.p; A.err = (int*)(R.ctr.p + 1);
+    A.summary = R.summary.p;
+    const int keybits = A.ibits + A.abits + index_bits(T);
+    const unsigned blocks = (unsigned)std::min<int64_t>(T, (int64_t)LIB_BLOCKS_PER_CU * std::max(c->num_cu, 1));
+    unsigned long long h[2] = {0, 0};
+    const auto launch = [&](size_t cap) -> int {
+        CHK(reserve_key_sort(c, R.sort, cap, cap));
+        A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
+        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(k_library_contacts, dim3(blocks), dim3(LIB_THREADS), 0, c->stream, A);
+        return check_launch(c, "k_library_contacts");
+    };
+    const auto device_error = [&](int dev) -> int {
+        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
+        if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
+        FAIL(c, ARP_E_HIP, fn + "device error");
+    };
+    // (the first buffer: 32 records per posed ligand atom, as arp_poses_contacts_launch sizes it)
+    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)(nx / 3) * 32)), R.ctr.p, 2, h, 3, launch,
+                             device_error, count));
+    const size_t k = (size_t)h[0];
+    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)T, POSES_SUMMARY - 1, R.summary.p, R.pose_off.p);
+    if (k > 0) {
+        int sorted = 0;
+        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
+        size_t bytes = 0;
+        sorted_layout(k, R.off, &bytes, k);
+        HIPCHK(c, R.slab.reserve(bytes));
+        const Columns col{R.slab.p, R.off};
+        hipLaunchKernelGGL(k_library_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, A.ibits, A.abits,
+                           R.sort.key[sorted].p, R.sort.val[sorted].p, (int*)col[0], (int*)col[1], (float*)col[2], (uint16_t*)col[3], (uint8_t*)col[4]);
+    }
+    CHK(check_launch(c, "k_poses_offsets / sort / k_library_columns"));
+    R.L = L; R.T = T; R.count = (int64_t)k; R.blocks = (int64_t)blocks; R.valid = true;
+    *count = R.count;
+    return ARP_OK;
+}
+
+int arp_library_contacts_fetch(arp_ctx* c, int64_t cap, uint64_t* pose_off, int32_t* i, int32_t* a, float* dist, uint16_t* sift, uint8_t* ctype,
+                               uint32_t* summary, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const LibraryResult& R = c->libres;
+    if (!R.valid) FAIL(c, ARP_E_ARG, "arp_library_contacts_fetch: no result (arp_library_contacts_launch; the structure or the library changed since)");
+    *count = R.count;
+    const bool records = i || a || dist || sift || ctype;
+    if (records && R.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_library_contacts_fetch: output buffers too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)R.count;
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, pose_off, R.pose_off.p, ((size_t)R.T + 1) * sizeof(uint64_t));
+    want_piece(pieces, summary, R.summary.p, (size_t)R.T * POSES_SUMMARY * sizeof(uint32_t));
+    if (records && k > 0) {
+        const uint8_t* const slab = R.slab.p;
+        want_piece(pieces, i, slab + R.off[0], k * sizeof(int32_t));
+        want_piece(pieces, a, slab + R.off[1], k * sizeof(int32_t));
+        want_piece(pieces, dist, slab + R.off[2], k * sizeof(float));
+        want_piece(pieces, sift, slab + R.off[3], k * sizeof(uint16_t));
+        want_piece(pieces, ctype, slab + R.off[4], k * sizeof(uint8_t));
+    }
+    return stage_fetch(c, pieces);
+}
+
+int arp_library_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const LigandLibrary& B = c->library;
+    const LibraryResult& R = c->libres;
+    info[0] = B.resident ? B.L : 0;
+    info[1] = R.valid ? R.T : 0;
+    info[2] = R.valid ? R.count : 0;
+    info[3] = B.resident ? B.atoms : 0;
+    info[4] = B.resident ? B.hrows : 0;
+    info[5] = R.valid ? R.blocks : 0;
+    info[6] = B.resident ? B.max_atoms : 0;
+    info[7] = R.best_valid ? 1 : 0;
+    return ARP_OK;
+}
+
+int arp_library_best_launch(arp_ctx* c, const int32_t* weights) {
+    if (!c) return ARP_E_ARG;
+    const std::string fn = "arp_library_best_launch: ";
+    LibraryResult& R = c->libres;
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    if (!weights) FAIL(c, ARP_E_ARG, fn + "weights missing");
+    LibraryWeights W{};
+    for (int q = 0; q < POSES_SUMMARY; ++q) {
+        if (weights[q] > ARP_SHORTLIST_MAX_WEIGHT || weights[q] < -ARP_SHORTLIST_MAX_WEIGHT) FAIL(c, ARP_E_ARG, fn + "weights has an entry beyond +-ARP_SHORTLIST_MAX_WEIGHT = 2^24");
+        W.w[q] = weights[q];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    void_pose_results(c, POSE_LIBRARY_BEST);
+    HIPCHK(c, R.best_n.reserve((size_t)R.L));
+    HIPCHK(c, R.best_score.reserve((size_t)R.L));
+    HIPCHK(c, R.best_pose.reserve((size_t)R.L));
+    hipLaunchKernelGGL(k_library_best, dim3(nblocks(R.L * 64, 256, 2048)), dim3(256), 0, c->stream, (int)R.L, (const long long*)R.tab.p,
+                       (const uint32_t*)R.summary.p, W, R.best_n.p, R.best_pose.p, R.best_score.p);
+    CHK(check_launch(c, "k_library_best"));
+    R.best_valid = true;
+    return ARP_OK;
+}
+
+int arp_library_best_fetch(arp_ctx* c, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose, int64_t* score, int64_t* n_ligands) {
+    if (!c || !n_ligands) return ARP_E_ARG;
+    const LibraryResult& R = c->libres;
+    if (!R.valid || !R.best_valid) FAIL(c, ARP_E_ARG, "arp_library_best_fetch: no result (arp_library_best_launch; the library result was replaced or the structure or the library changed since)");
+    *n_ligands = R.L;
+    if ((n_poses || best_pose || score) && cap_ligands < R.L) FAIL(c, ARP_E_CAPACITY, "arp_library_best_fetch: output buffers too small (cap_ligands < *n_ligands)");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, n_poses, R.best_n.p, (size_t)R.L * sizeof(int64_t));
+    want_piece(pieces, best_pose, R.best_pose.p, (size_t)R.L * sizeof(int32_t));
+    want_piece(pieces, score, R.best_score.p, (size_t)R.L * sizeof(int64_t));
+    return stage_fetch(c, pieces);
 }
 
 // ---- ligand poses on the resident receptor, ring and amide contacts (arp_poses_planes.h)

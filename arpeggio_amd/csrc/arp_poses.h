@@ -141,10 +141,37 @@ __device__ __forceinline__ float4 pose_sb(const PoseArgs& A, int pose, int a) {
     return v;
 }
 
+// How k_poses_contacts reads what the decision needs beside the two atoms: everything by local id from the resident arrays, a
+// single-bond neighbour's coordinate from the pose when that neighbour moved.  (The ligand library, arp_library.h, gives
+// pose_pair_sift another reader: its ligand side is staged in LDS and is never bonded to the receptor.)
+struct PoseResidentReader {
+    const PoseArgs& A;
+    __device__ __forceinline__ double comp() const { return A.comp; }
+    __device__ __forceinline__ int* err() const { return A.err; }
+    // {vdw, cov} of bgn (of_b) or end
+    __device__ __forceinline__ double2 rad(const PoseAtom& a, bool) const { return A.rad[a.lid]; }
+    // the single-bond neighbour of bgn (of_b) or end: x, y, z, present
+    __device__ __forceinline__ float4 sb(int pose, const PoseAtom& B, const PoseAtom& E, bool of_b) const { return pose_sb(A, pose, of_b ? B.lid : E.lid); }
+    // interactions.py:748-757: end among the bonded neighbours of bgn, at ANY distance (neighbours of bgn's own residue are not in
+    // qa, and a pair of one residue never gets here: I:729)
+    __device__ __forceinline__ bool bonded(const PoseAtom& B, int e) const {
+        const unsigned nx_ = min(min((unsigned)(B.qa.y ^ e), (unsigned)(B.qa.z ^ e)), (unsigned)(B.qa.w ^ e));
+        bool cov = nx_ == 0u;
+        if (!cov && B.qa.w == -2) {
+            for (int k = A.bond_off[B.lid], k1 = A.bond_off[B.lid + 1]; k < k1; ++k)
+                if (A.bond_idx[k] == e) { cov = true; break; }
+        }
+        return cov;
+    }
+};
+
 // The decision for one accepted pair (B = bgn, the lower packed id; d = its float32 distance): the SIFt mask and, in *ct_out, the
 // contact type.  It follows interactions.py:715-936 line by line as sift_body does — stage A's straight-line mask code, then the
 // hydrogen geometry of sift_geometry — with the pose's coordinates wherever an atom, a hydrogen or a single-bond neighbour moved.
-__device__ __forceinline__ uint32_t pose_pair_sift(const PoseArgs& A, int pose, const PoseAtom& B, const PoseAtom& E, float d, int* ct_out) {
+// R says how an atom's radii, its single-bond neighbour and the bonded-neighbour test are read (PoseResidentReader above,
+// LibraryReader in arp_library.h): the one statement of the decision serves both kernels.
+template <class Reader>
+__device__ __forceinline__ uint32_t pose_pair_sift(const Reader& R, int pose, const PoseAtom& B, const PoseAtom& E, float d, int* ct_out) {
     const num::f3 xb = B.x, xe = E.x;
     const uint32_t mb = B.m, me = E.m;
     const uint32_t tb = mb & M_TMASK, te = me & M_TMASK;
@@ -153,9 +180,9 @@ __device__ __forceinline__ uint32_t pose_pair_sift(const PoseArgs& A, int pose, 
     const uint32_t ct_idx = ((mb / M_SEL) & 1u) | (((me / M_SEL) & 1u) << 1) | (bw << 2) | (ew << 3);
     *ct_out = (int)((contact_type_table() >> (4u * ct_idx)) & 15ull);
     // interactions.py:717-718 and the casts of 756-773
-    const double2 rb = A.rad[B.lid], re = A.rad[E.lid];      // {vdw, cov}
+    const double2 rb = R.rad(B, true), re = R.rad(E, false);      // {vdw, cov}
     const double sum_vdw = rb.x + re.x;
-    const float f_sum_cov = (float)(rb.y + re.y), f_sum_vdw = (float)sum_vdw, f_vdw_comp = (float)(sum_vdw + A.comp);
+    const float f_sum_cov = (float)(rb.y + re.y), f_sum_vdw = (float)sum_vdw, f_vdw_comp = (float)(sum_vdw + R.comp());
     // interactions.py:756-773: an exclusive ladder
     uint32_t s = ARP_S_PROXIMAL;
     s = (d <= f_vdw_comp) ? ARP_S_VDW : s;
@@ -196,15 +223,8 @@ __device__ __forceinline__ uint32_t pose_pair_sift(const PoseArgs& A, int pose, 
         dead |= (me & M_HAS_SB) ? 0u : 32u;
         need_ = ((need_ & ~dead) == 0u) ? 0u : need_;
     }
-    // interactions.py:748-757: end among the bonded neighbours of bgn, at ANY distance (neighbours of bgn's own residue are not in
-    // qa, and a pair of one residue never gets here: I:729)
-    const int e = E.lid;
-    const unsigned nx_ = min(min((unsigned)(B.qa.y ^ e), (unsigned)(B.qa.z ^ e)), (unsigned)(B.qa.w ^ e));
-    bool cov = nx_ == 0u;
-    if (!cov && B.qa.w == -2) {
-        for (int k = A.bond_off[B.lid], k1 = A.bond_off[B.lid + 1]; k < k1; ++k)
-            if (A.bond_idx[k] == e) { cov = true; break; }
-    }
+    // interactions.py:748-757: end among the bonded neighbours of bgn, at ANY distance
+    const bool cov = R.bonded(B, E.lid);
     s = cov ? ARP_S_COVALENT : s;
     s |= s_metal;
     // interactions.py:786: feature flags only for pairs that do not clash (covalent ones do get them) within 4.5 A
@@ -213,8 +233,8 @@ __device__ __forceinline__ uint32_t pose_pair_sift(const PoseArgs& A, int pose, 
     const unsigned need = feat ? need_ : 0u;
     // interactions.py:889-895 (halogen bond: float32 angle at the donor)
     if (feat & in_vc & ((XY & 4u) != 0u)) {
-        if (X & 4u) { if (xbond(pose_sb(A, pose, B.lid), xb, xe, A.err)) s |= ARP_S_XBOND; }
-        else if (xbond(pose_sb(A, pose, e), xe, xb, A.err)) s |= ARP_S_XBOND;
+        if (X & 4u) { if (xbond(R.sb(pose, B, E, true), xb, xe, R.err())) s |= ARP_S_XBOND; }
+        else if (xbond(R.sb(pose, B, E, false), xe, xb, R.err())) s |= ARP_S_XBOND;
     }
     if (need) {
         // the hydrogen geometry (sift_geometry): branch k of
@@ -230,11 +250,11 @@ __device__ __forceinline__ uint32_t pose_pair_sift(const PoseArgs& A, int pose, 
                 const double clast = (kind < 2) ? ARP_COS_LAST_GE_1_57 : ARP_COS_LAST_GE_2_27;
                 const double cmin = (kind < 2) ? ARP_COS_1_57 : ARP_COS_2_27;
                 r = hbond_like(donor_b ? xb : xe, donor_b ? B.hx : E.hx, donor_b ? B.h0 : E.h0, donor_b ? B.h1 : E.h1, donor_b ? xe : xb,
-                               donor_b ? re.x : rb.x, A.comp, cmin, clast);
+                               donor_b ? re.x : rb.x, R.comp(), cmin, clast);
             } else {
                 const bool hal_b = kind == 4;
-                r = halogen_weak(hal_b ? xb : xe, pose_sb(A, pose, hal_b ? B.lid : e), hal_b ? rb.x : re.x, hal_b ? E.hx : B.hx,
-                                 hal_b ? E.h0 : B.h0, hal_b ? E.h1 : B.h1, A.comp);
+                r = halogen_weak(hal_b ? xb : xe, R.sb(pose, B, E, hal_b), hal_b ? rb.x : re.x, hal_b ? E.hx : B.hx,
+                                 hal_b ? E.h0 : B.h0, hal_b ? E.h1 : B.h1, R.comp());
             }
             res |= (r ? 1u : 0u) << kind;
         }
@@ -364,7 +384,7 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
                     const PoseAtom Bg = pose_pick(h_first, H, J), En = pose_pick(h_first, J, H);
                     const float d = num::norm(num::sub(Bg.x, En.x));                    // interactions.py:745
                     int ct = 0;
-                    sft = pose_pair_sift(A, pose, Bg, En, d, &ct);
+                    sft = pose_pair_sift(PoseResidentReader{A}, pose, Bg, En, d, &ct);
                     key = ((u64)(unsigned)pose << (2 * A.idbits)) | ((u64)(unsigned)Bg.lid << A.idbits) | (u64)(unsigned)En.lid;
                     val = (u64)__float_as_uint(d) | ((u64)sft << 32) | ((u64)(unsigned)ct << 48);
                 }

@@ -744,3 +744,185 @@ def poses_of(pc: PackedComplex, sel, n_poses: int, seed: int = 0, shift: float =
                 h = a[parent] + (1.0 + stretch) * (h - a[parent])
             xyz[f], h_xyz[f] = a.astype(np.float32), h
     return xyz, h_xyz
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Ligands of a library (``arpeggio_amd.ligand_library``): small typed molecules of ONE residue each, centred on the origin
+# ---------------------------------------------------------------------------------------------------------------------
+LIGAND_KINDS = ('water', 'ion', 'amine', 'halo', 'chain')
+_LIG_VDW = {'C': 1.7, 'N': 1.55, 'O': 1.52, 'S': 1.8, 'H': 1.1, 'ZN': 1.39, 'CL': 1.75, 'BR': 1.85}
+_LIG_COV = {'C': 0.76, 'N': 0.71, 'O': 0.66, 'S': 1.05, 'H': 0.31, 'ZN': 1.22, 'CL': 1.02, 'BR': 1.2}
+
+
+def _ligand_pack(atoms, bonds, ring_bonds, res_name, id):
+    """atoms: dicts of xyz, el, name, tm, fl, rows (the hydrogen rows of this atom); bonds: index pairs."""
+    n = len(atoms)
+    xyz = np.array([a['xyz'] for a in atoms], np.float64).reshape(-1, 3)
+    mean = xyz[[not a['fl'] & config.F_HYDROGEN for a in atoms]].mean(axis=0)      # (centred on the heavy atoms)
+    xyz = xyz - mean
+    el = [a['el'] for a in atoms]
+    adj = [[] for _ in range(n)]
+    for i, j in bonds:
+        adj[i].append(j); adj[j].append(i)
+    rb = {frozenset(b) for b in ring_bonds}
+    sb = np.full(n, -1, np.int32)
+    for i in range(n):
+        for j in adj[i]:
+            if el[j] != 'H' and frozenset((i, j)) not in rb:
+                sb[i] = j
+                break
+    x32 = xyz.astype(np.float32)
+    # a hydrogen row is either a coordinate or the index of the hydrogen ATOM it repeats (then: as read from the float32 atom)
+    rows = [[x32[h].astype(np.float64) if isinstance(h, int) else np.asarray(h, np.float64) - mean for h in a['rows']] for a in atoms]
+    return PackedComplex(
+        xyz=x32, vdw=[_LIG_VDW[e] for e in el], cov=[_LIG_COV[e] for e in el], type_mask=[a['tm'] for a in atoms], flags=[a['fl'] for a in atoms],
+        res_id=np.zeros(n, np.int32), res_flags=[0], res_prev=[-1], res_next=[-1],
+        bond_off=np.concatenate([[0], np.cumsum([len(a) for a in adj])]), bond_idx=[j for a in adj for j in a],
+        h_off=np.concatenate([[0], np.cumsum([len(r) for r in rows])]), h_xyz=np.array([h for r in rows for h in r], np.float64).reshape(-1, 3),
+        sb_nbr=sb, ring_center=np.zeros((0, 3)), ring_normal=np.zeros((0, 3)), ring_res=np.zeros(0, np.int32),
+        atom_name=[a['name'] for a in atoms], element=el, serial=np.arange(1, n + 1, dtype=np.int32), res_name=[res_name], res_seq=[1],
+        res_icode=[' '], res_chain=['L'], component_types={res_name: 'W' if res_name == 'HOH' else 'B'}, id=id)
+
+
+def ligand(kind: str, seed: int = 0, size: int = None) -> PackedComplex:
+    """One synthetic ligand, centred on the origin (deterministic, splitmix64):
+
+    'water'  one oxygen (water flag, donor and acceptor) with two hydrogen ROWS and no hydrogen atoms: S = 1, SH = 2
+    'ion'    one metal ion: S = 1, SH = 0
+    'amine'  a lysine-like fragment CB - CG - CD - CE - NZ, every hydrogen BOTH an atom and a row of its parent: S = 16, SH = 11
+    'halo'   a six-membered aromatic ring with a chlorine and a bromine (xbond donors, each with its carbon as single-bond
+             neighbour), hydrogens of the other four carbons as atoms and rows: S = 12, SH = 4
+    'chain'  ``size`` heavy atoms (default 24) along a compact self-avoiding walk, typed from a palette — donors and weak
+             donors with hydrogen rows, acceptors, ionisable groups, carbonyls, aromatic carbons, a sulphur, halogens behind a
+             carbon —, hydrogens as rows only: S = size
+    """
+    def unit(v):
+        return v / np.linalg.norm(v)
+
+    def atom(xyz, el, name, tm=0, fl=0):
+        return dict(xyz=np.asarray(xyz, float), el=el, name=name, tm=tm, fl=fl, rows=[])
+
+    atoms, bonds, ring_bonds = [], [], []
+
+    def add_h(parent, direction, name, as_atom=True):
+        p = atoms[parent]
+        hx = p['xyz'] + 1.0 * unit(np.asarray(direction, float))
+        if as_atom:
+            atoms.append(atom(hx, 'H', name, 0, config.F_HYDROGEN | (p['fl'] & config.F_WATER)))
+            bonds.append((parent, len(atoms) - 1))
+            hx = len(atoms) - 1
+        p['rows'].append(hx)
+
+    if kind == 'water':
+        atoms.append(atom([0, 0, 0], 'O', 'O', T['hbond acceptor'] | T['hbond donor'], config.F_WATER))
+        d1 = _unit_vectors(seed, 70, np.arange(1, dtype=np.uint64))[0]
+        add_h(0, d1, 'H1', False); add_h(0, unit(np.cross(d1, [0.3, 0.5, 0.8]) - 0.3 * d1), 'H2', False)
+        return _ligand_pack(atoms, bonds, ring_bonds, 'HOH', f'water{seed}')
+    if kind == 'ion':
+        atoms.append(atom([0, 0, 0], 'ZN', 'ZN', 0, config.F_METAL))
+        return _ligand_pack(atoms, bonds, ring_bonds, 'ZN', f'ion{seed}')
+    if kind == 'amine':
+        up, side = np.array([0.0, 0.0, 1.0]), np.array([0.0, 1.0, 0.0])
+        for k, nm in enumerate(('CB', 'CG', 'CD', 'CE')):
+            atoms.append(atom([1.5 * k * 0.82, 0.85 * (k % 2), 0.0], 'C', nm, T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C))
+        atoms.append(atom([1.5 * 4 * 0.82, 0.0, 0.0], 'N', 'NZ', T['hbond donor'] | T['pos ionisable'], 0))
+        bonds.extend((k, k + 1) for k in range(4))
+        for k in range(4):
+            add_h(k, up + 0.3 * side * (1 - 2 * (k % 2)), f'H{k}A'); add_h(k, -up + 0.3 * side * (1 - 2 * (k % 2)), f'H{k}B')
+        add_h(4, [1.0, 0.2, 0.0], 'HZ1'); add_h(4, [0.3, -0.6, 0.8], 'HZ2'); add_h(4, [0.3, -0.6, -0.8], 'HZ3')
+        return _ligand_pack(atoms, bonds, ring_bonds, 'LYF', f'amine{seed}')
+    if kind == 'halo':
+        for q in range(6):
+            ang = q * np.pi / 3
+            atoms.append(atom(1.39 * np.array([np.cos(ang), np.sin(ang), 0.0]), 'C', f'C{q + 1}', T['aromatic'] | T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C))
+        for q in range(6):
+            bonds.append((q, (q + 1) % 6)); ring_bonds.append((q, (q + 1) % 6))
+        hal = T['xbond donor'] | T['weak hbond acceptor'] | T['hydrophobe']
+        atoms.append(atom(atoms[0]['xyz'] * (1 + 1.74 / 1.39), 'CL', 'CL1', hal, config.F_HALOGEN)); bonds.append((0, 6))
+        atoms.append(atom(atoms[3]['xyz'] * (1 + 1.90 / 1.39), 'BR', 'BR1', hal, config.F_HALOGEN)); bonds.append((3, 7))
+        for q in (1, 2, 4, 5):
+            add_h(q, atoms[q]['xyz'], f'H{q + 1}')
+        return _ligand_pack(atoms, bonds, ring_bonds, 'HAL', f'halo{seed}')
+    if kind != 'chain':
+        raise ValueError(f'ligand: kind must be one of {LIGAND_KINDS}')
+    n = 24 if size is None else int(size)
+    if n < 1:
+        raise ValueError('ligand: a chain needs at least one atom')
+    palette = (('C', T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C, 2), ('N', T['hbond donor'], 0, 1),
+               ('C', T['carbonyl carbon'], config.F_ELEM_C, 0), ('O', T['hbond acceptor'] | T['weak hbond acceptor'] | T['xbond acceptor'] | T['carbonyl oxygen'], 0, 0),
+               ('C', T['aromatic'] | T['hydrophobe'], config.F_ELEM_C, 0), ('N', T['hbond donor'] | T['pos ionisable'], 0, 2),
+               ('C', T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C, 1), ('CL', T['xbond donor'] | T['weak hbond acceptor'] | T['hydrophobe'], config.F_HALOGEN, 0),
+               ('O', T['hbond acceptor'] | T['neg ionisable'] | T['weak hbond acceptor'], 0, 0), ('S', T['hbond acceptor'] | T['hydrophobe'], config.F_ELEM_S, 0),
+               ('O', T['hbond acceptor'] | T['hbond donor'], 0, 1))
+    rs = np.random.RandomState(splitmix64(seed, [7000 + n])[0] % (2 ** 31))
+    pos = [np.zeros(3)]
+    for k in range(1, n):
+        cand = None
+        for _ in range(200):
+            cand = pos[-1] + 1.5 * unit(rs.normal(size=3) - 0.15 * (pos[-1] - np.mean(pos, axis=0)))
+            if all(np.linalg.norm(cand - p) > 1.35 for p in pos[:-1]):
+                break
+        pos.append(cand)
+    first = int(splitmix64(seed, [7100])[0] % len(palette))
+    for k in range(n):
+        el, tm, fl, nh = palette[(first + k) % len(palette)]
+        if el == 'CL' and k == 0:
+            el, tm, fl, nh = palette[0]
+        atoms.append(atom(pos[k], el, f'{el[0]}{k + 1}', tm, fl))
+        if k:
+            bonds.append((k - 1, k))
+        for q in range(nh):
+            add_h(k, rs.normal(size=3), f'H{k + 1}{"ABC"[q]}', False)
+    return _ligand_pack(atoms, bonds, ring_bonds, 'LIG', f'chain{n}_{seed}')
+
+
+def ligands(n: int, seed: int = 0, sizes=(20, 60), kinds=LIGAND_KINDS):
+    """``n`` ligands for a library: ligand k is of kind ``kinds[k % len(kinds)]``; a 'chain' gets a size drawn from
+    ``sizes = (smallest, largest)`` (or ``sizes[k]`` when ``sizes`` lists one size per ligand)."""
+    out = []
+    for k in range(int(n)):
+        kind = kinds[k % len(kinds)]
+        if len(sizes) == 2 and sizes[0] <= sizes[1]:
+            size = int(sizes[0] + splitmix64(seed, [7200 + k])[0] % (sizes[1] - sizes[0] + 1))
+        else:
+            size = int(sizes[k])
+        out.append(ligand(kind, seed=seed + k, size=size))
+    return out
+
+
+def library_poses_of(receptor: PackedComplex, ligand: PackedComplex, centre=None, n_poses: int = 1, seed: int = 0, shift: float = 3.0,
+                     jitter: float = 0.0, stretch: float = 0.0):
+    """Poses of ``ligand`` in ``receptor`` for ``Context.library_contacts``, in the manner of ``poses_of``: ``(xyz float32 [P, S,
+    3], h_xyz float64 [P, SH, 3])``.  Pose 0 is the ligand moved so that its centroid lies at ``centre`` (default: the
+    receptor's centroid); every other pose is that turned as a rigid body about the centroid (a random rotation) and shifted by
+    up to ``shift`` A per axis.  ``jitter`` and ``stretch`` as in ``poses_of``."""
+    P, S, SH = int(n_poses), ligand.n_atoms, int(ligand.h_xyz.shape[0])
+    c = np.asarray(receptor.xyz, np.float64).mean(axis=0) if centre is None else np.asarray(centre, np.float64)
+    x0 = np.asarray(ligand.xyz, np.float64)
+    own = x0.mean(axis=0) if S else np.zeros(3)
+    x0 = x0 - own + c
+    h0 = np.asarray(ligand.h_xyz, np.float64).reshape(-1, 3) - own + c
+    parent = np.repeat(np.arange(S), np.diff(np.asarray(ligand.h_off, np.int64)))
+    xyz = np.empty((P, S, 3), np.float32)
+    h_xyz = np.empty((P, SH, 3), np.float64)
+    if P < 1:
+        return xyz, h_xyz
+    rot = _rotation_matrices(seed, 60, np.arange(1, max(P, 2), dtype=np.uint64))
+    for f in range(P):
+        a, h = x0, h0
+        if f:
+            k = np.arange(3 * f, 3 * f + 3, dtype=np.uint64)
+            move = shift * (2.0 * u01(seed, 63, k) - 1.0)
+            R = rot[f - 1]
+            a = (x0 - c) @ R.T + c + move
+            h = (h0 - c) @ R.T + c + move
+            if jitter > 0:
+                idx = np.arange(3 * (S + SH), dtype=np.uint64) + np.uint64(f * 3 * (S + SH + 1))
+                g1, g2 = np.maximum(u01(seed, 66, idx), 1e-12), u01(seed, 67, idx)
+                noise = jitter * np.sqrt(-2.0 * np.log(g1)) * np.cos(2.0 * np.pi * g2)
+                a = a + noise[:3 * S].reshape(S, 3)
+                h = h + noise[3 * S:].reshape(SH, 3)
+        if stretch != 0.0 and SH:
+            h = a[parent] + (1.0 + stretch) * (h - a[parent])
+        xyz[f], h_xyz[f] = a.astype(np.float32), h
+    return xyz, h_xyz

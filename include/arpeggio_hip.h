@@ -1294,6 +1294,75 @@ int arp_poses_clusters_fetch(arp_ctx* ctx, int64_t cap_positions, int64_t cap_cl
                              int64_t* similarity, int32_t* leader, int32_t* leader_position, uint32_t* size, int64_t* n_positions,
                              int64_t* n_clusters);
 int arp_poses_clusters_info(arp_ctx* ctx, int64_t info[8]);
+/* Ligand library: DIFFERENT ligands, each with its poses, on one resident receptor in one launch (csrc/arp_library.h, DESIGN.md
+ * 5u).  The pose entries above move one ligand that is part of the resident structure; a screen runs thousands of different
+ * molecules against one receptor.  Here the receptor is resident ALONE and the ligands' per-atom facts are a table beside it.
+ * It is an extension beside the mirror.
+ *
+ * RECEPTOR.  ONE structure is resident (no batch, no models, no shard ownership: refused as the pose launches refuse them, in
+ *   the same order), n < 2^21.  No selection is needed and none is read.
+ * LIBRARY (arp_set_ligand_library).  L ligands, 1 <= L <= ARP_LIBRARY_MAX_LIGANDS; ligand l has S_l atoms, 1 <= S_l <=
+ *   ARP_LIBRARY_MAX_ATOMS, library atoms atom_off[l] ... atom_off[l + 1] - 1 (atom_off int32 [L + 1], atom_off[0] = 0), TA =
+ *   atom_off[L] atoms in all.  Per library atom: type_mask uint16 and flags uint16 (as arp_set_atoms takes them), vdw and cov
+ *   float64, h_off int32 [TA + 1] (its hydrogen rows, CSR over all library atoms, h_off[0] = 0, not decreasing; SH_l = the
+ *   rows of ligand l), sb_nbr int32 (the index WITHIN ITS LIGAND of the single-bond heavy neighbour, -1: none).
+ *   ARP_E_ARG with the cause named, checked in this order and before anything is touched: a pass not waited for; L out of
+ *   range; an array missing; atom_off not starting at 0; a ligand with fewer than 1 or more than ARP_LIBRARY_MAX_ATOMS atoms;
+ *   h_off not starting at 0; h_off decreasing; a radius that is not finite or negative; an sb_nbr outside its own ligand or
+ *   equal to its own atom.
+ *   The library reads nothing of the receptor and STAYS RESIDENT through new structures, models and batches: the same library
+ *   runs against several receptors.  arp_set_ligand_library replaces it and voids the library result.
+ * WHAT A LIGAND IS.  One residue of a chain of its own: no polypeptide residue, no sequence neighbours, no bond to the receptor.
+ *   Peptide ligands and covalent ligands are out of scope.
+ * POSES (arp_library_contacts_launch).  pose_off int64 [L + 1], pose_off[0] = 0, not decreasing: ligand l has P_l =
+ *   pose_off[l + 1] - pose_off[l] >= 0 poses, T = pose_off[L], 1 <= T <= ARP_POSES_MAX_POSES; pose_off[l] + p is the GLOBAL id
+ *   of pose p of ligand l.  Both coordinate arrays are ligand-major, then pose-major: xyz float32, sum of P_l S_l 3 values;
+ *   h_xyz float64, sum of P_l SH_l 3 values (may be NULL when that sum is 0).  The library cannot see their lengths: the
+ *   caller answers for them.  cutoff in (0, ARP_POSES_MAX_CUTOFF], vdw_comp finite; include_sequence_adjacent is accepted and
+ *   without effect (the gate needs a sequence on both residues; a ligand has none).
+ * RESULT.  For global pose t of ligand l exactly the atom-atom records with one receptor and one ligand atom that a pass would
+ *   emit on the COMPLEX — the receptor with ligand l appended after its last atom as one more residue, uploaded as ONE
+ *   structure, the pose's coordinates scattered in, the ligand's atoms as the selection, the same parameters.  A record is
+ *   (t, i, a): i the receptor's packed id, a the ligand atom's index within its ligand (in the complex that pair is i < j = n +
+ *   a: bgn is always the receptor atom); the same float32 distance bits, 15-bit SIFt and contact type.  Ascending (t, i, a).
+ *   pose_off uint64 [T + 1], i int32, a int32, dist float32, sift uint16, ctype uint8, summary uint32 [T][ARP_POSES_SUMMARY]
+ *   with the slots of arp_poses_contacts_fetch's summary.  Nothing is truncated: a record buffer that was too small is grown to
+ *   the counted size and the launch repeated.
+ *   ARP_E_ARG with the cause named, in this order, none touching a resident result: the receptor's refusals; n >= 2^21; no
+ *   library; pose_off missing, not starting at 0, decreasing; T out of range; cutoff; vdw_comp; xyz missing; h_xyz missing while
+ *   a posed ligand has hydrogen rows.  A non-finite pose coordinate, found on the device: ARP_E_ARG and NO result (a launch
+ *   that has passed its argument checks voids the result before it).  A halogen-bond donor without a single-bond neighbour:
+ *   ARP_E_XBOND_NBR, as in a pass.  ARP_E_CAPACITY: 2^31 records or more.
+ *   All work goes on the context's stream (arp_use_stream's, if set); ONE host wait a launch, for *count with the device's
+ *   error word.
+ * BEST POSE PER LIGAND (arp_library_best_launch / _fetch).  Reads the resident summary and nothing else.  weights int32
+ *   [ARP_POSES_SUMMARY], |w| <= ARP_SHORTLIST_MAX_WEIGHT; score[t] = sum over the slots s of w[s] summary[t][s] in int64.  Per
+ *   ligand: n_poses int64, best_pose int32 (the global pose id of the highest score, ties to the lower id), score int64.  A
+ *   ligand without poses: -1 and INT64_MIN.  20 bytes per ligand instead of 64 per pose.  arp_library_best_fetch: any array may
+ *   be NULL; ARP_E_CAPACITY when one is asked for and cap_ligands < *n_ligands = L.
+ * STATE.  The library result is void after a new structure, models, a batch, arp_set_ligand_library and a new library launch,
+ *   and the best-pose table goes with it (or is replaced by a new arp_library_best_launch).  arp_set_selection does NOT void it:
+ *   it reads no selection.  Making it voids nothing: the bags of the last pass, every table made from them and all five pose
+ *   results stay fetchable and byte-equal.
+ * arp_library_contacts_fetch: as arp_poses_contacts_fetch (ANY pointer may be NULL; cap is looked at only when a record column
+ *   is asked for).  arp_library_info: info[0] = L, [3] = TA, [4] = hydrogen rows, [6] = the largest S_l of the resident
+ *   library; [1] = T, [2] = records, [5] = blocks of k_library_contacts (poses are taken with a grid stride) of the resident
+ *   result; [7] = 1 while a best-pose table is resident.
+ * OUT OF SCOPE: the ligands' own rings and amides (the plane tables of a library); fingerprints, the shortlist and clusters over
+ *   a library result (the summary layout is that of the poses result, so that they can follow); peptide and covalent ligands;
+ *   cutoffs beyond 6.0; a batch, models or a shard as the receptor; the per-atom accumulators. */
+#define ARP_LIBRARY_MAX_LIGANDS (1 << 16)
+#define ARP_LIBRARY_MAX_ATOMS 256
+int arp_set_ligand_library(arp_ctx* ctx, int64_t n_ligands, const int32_t* atom_off, const uint16_t* type_mask, const uint16_t* flags,
+                           const double* vdw, const double* cov, const int32_t* h_off, const int32_t* sb_nbr);
+int arp_library_contacts_launch(arp_ctx* ctx, const int64_t* pose_off, const float* xyz, const double* h_xyz, double cutoff,
+                                double vdw_comp, int include_sequence_adjacent, int64_t* count);
+int arp_library_contacts_fetch(arp_ctx* ctx, int64_t cap, uint64_t* pose_off, int32_t* i, int32_t* a, float* dist, uint16_t* sift,
+                               uint8_t* ctype, uint32_t* summary, int64_t* count);
+int arp_library_info(arp_ctx* ctx, int64_t info[8]);
+int arp_library_best_launch(arp_ctx* ctx, const int32_t* weights);
+int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose, int64_t* score,
+                           int64_t* n_ligands);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
