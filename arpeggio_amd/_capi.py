@@ -918,6 +918,20 @@ class Context:
         self._check(self._L.arp_networks_labels_fetch(self._h, len(label), _p(label), C.byref(N)), 'arp_networks_labels_fetch')
         return label, table
 
+    def _pose_records_fetch(self, entry, second, P, k):
+        """The fetch of a launch over ``P`` poses with ``k`` records through C entry ``entry`` (arp_poses_contacts_fetch or
+        arp_library_contacts_fetch): a dict of the five columns — ``second`` names the second id column —, ``pose_off`` and
+        ``summary``; with ``second`` None only the summary, as an array."""
+        summary = np.empty((P, POSES_SUMMARY), np.uint32)
+        t = {}
+        if second is not None:
+            t = {'i': np.empty(k, np.int32), second: np.empty(k, np.int32), 'dist': np.empty(k, np.float32), 'sift': np.empty(k, np.uint16),
+                 'ctype': np.empty(k, np.uint8), 'pose_off': np.empty(P + 1, np.uint64), 'summary': summary}
+        n = C.c_int64(0)
+        self._check(getattr(self._L, entry)(self._h, k, *(_p(t[c]) if t else None for c in ('pose_off', 'i', second, 'dist', 'sift', 'ctype')),
+                                            _p(summary), C.byref(n)), entry)
+        return t if t else summary
+
     def _poses_launch(self, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent):
         """Shapes checked against the uploaded selection, then arp_poses_contacts_launch; returns (P, records, movable ids)."""
         sel = getattr(self, '_sel', None)
@@ -960,11 +974,7 @@ class Context:
         ``POSES_MAX_POSES`` poses a call (``poses.concat`` joins chunks); ``cutoff`` <= 6.0.  The bags of the last pass and
         every table made from them stay as they are."""
         P, k, atoms = self._poses_launch(xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
-        t = dict(i=np.empty(k, np.int32), j=np.empty(k, np.int32), dist=np.empty(k, np.float32), sift=np.empty(k, np.uint16),
-                 ctype=np.empty(k, np.uint8), pose_off=np.empty(P + 1, np.uint64), summary=np.empty((P, POSES_SUMMARY), np.uint32))
-        n = C.c_int64(0)
-        self._check(self._L.arp_poses_contacts_fetch(self._h, k, _p(t['pose_off']), _p(t['i']), _p(t['j']), _p(t['dist']), _p(t['sift']),
-                                                     _p(t['ctype']), _p(t['summary']), C.byref(n)), 'arp_poses_contacts_fetch')
+        t = self._pose_records_fetch('arp_poses_contacts_fetch', 'j', P, k)
         t['movable'] = atoms
         return t
 
@@ -972,11 +982,7 @@ class Context:
         """``poses_contacts`` with only the per-pose summary copied to the host: uint32 [P, 16], records per SIFt bit and, in
         slot 15, all records of the pose — for ranking many poses without copying a record."""
         P, _, _ = self._poses_launch(xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
-        s = np.empty((P, POSES_SUMMARY), np.uint32)
-        n = C.c_int64(0)
-        self._check(self._L.arp_poses_contacts_fetch(self._h, 0, None, None, None, None, None, None, _p(s), C.byref(n)),
-                    'arp_poses_contacts_fetch')
-        return s
+        return self._pose_records_fetch('arp_poses_contacts_fetch', None, P, 0)
 
     def poses_info(self):
         """(P, S, SH, records) of the resident poses result, zeros while there is none (arp_poses_contacts_info)."""
@@ -1264,22 +1270,14 @@ class Context:
         id), ``a`` (the atom's index within its ligand), ``dist``, ``sift``, ``ctype`` in ascending (global pose, i, a),
         ``pose_off`` uint64 [T + 1], ``summary`` uint32 [T, 16] and ``ligand_pose_off`` int64 [L + 1] (the argument)."""
         T, k, off = self._library_launch(pose_off, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
-        t = dict(i=np.empty(k, np.int32), a=np.empty(k, np.int32), dist=np.empty(k, np.float32), sift=np.empty(k, np.uint16),
-                 ctype=np.empty(k, np.uint8), pose_off=np.empty(T + 1, np.uint64), summary=np.empty((T, POSES_SUMMARY), np.uint32))
-        n = C.c_int64(0)
-        self._check(self._L.arp_library_contacts_fetch(self._h, k, _p(t['pose_off']), _p(t['i']), _p(t['a']), _p(t['dist']), _p(t['sift']),
-                                                       _p(t['ctype']), _p(t['summary']), C.byref(n)), 'arp_library_contacts_fetch')
+        t = self._pose_records_fetch('arp_library_contacts_fetch', 'a', T, k)
         t['ligand_pose_off'] = off
         return t
 
     def library_summary(self, pose_off, xyz, h_xyz, cutoff=5.0, vdw_comp=0.1, include_sequence_adjacent=False):
         """``library_contacts`` with only the per-pose summary copied to the host: uint32 [T, 16]."""
         T, _, _ = self._library_launch(pose_off, xyz, h_xyz, cutoff, vdw_comp, include_sequence_adjacent)
-        s = np.empty((T, POSES_SUMMARY), np.uint32)
-        n = C.c_int64(0)
-        self._check(self._L.arp_library_contacts_fetch(self._h, 0, None, None, None, None, None, None, _p(s), C.byref(n)),
-                    'arp_library_contacts_fetch')
-        return s
+        return self._pose_records_fetch('arp_library_contacts_fetch', None, T, 0)
 
     def library_best(self, weights):
         """The best pose of every ligand of the resident library result by ``weights`` int32 [16] over its summary row

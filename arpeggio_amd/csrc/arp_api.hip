@@ -292,11 +292,10 @@ struct CouplingScratch {
     uint32_t flags = 0;
 };
 
-// the contacts of ligand poses on the resident receptor (arp_poses_contacts_launch): the movable set's tables (made once per
-// structure and selection), the uploaded poses, the appended records and their sort, the result's columns in one slab
-struct PosesResult {
-    DevBuf<int> sel_h, pos_of;
-    uint64_t movable_static = 0, movable_sel = 0;       // static_epoch / sel_epoch the tables were made for (0: none)
+// What a launch over poses keeps of its records (arp_poses_contacts_launch and arp_library_contacts_launch, pose_records_launch):
+// the uploaded poses, the counters, the per-pose summary rows and record offsets, the appended records and their sort, the
+// result's five columns in one slab
+struct PoseRecords {
     DevBuf<float> xyz;
     DevBuf<double> hx;
     DevBuf<unsigned long long> ctr;                     // [0] records appended, [1] device error
@@ -305,12 +304,18 @@ struct PosesResult {
     SortScratch sort;
     DevBuf<uint8_t> slab;
     size_t off[5] = {0, 0, 0, 0, 0};
-    int64_t P = 0, S = 0, SH = 0, count = 0;
+    int64_t count = 0;
+    void release() { xyz.release(); hx.release(); ctr.release(); summary.release(); pose_off.release(); sort.release(); slab.release(); }
+};
+// the contacts of ligand poses on the resident receptor (arp_poses_contacts_launch): the movable set's tables (made once per
+// structure and selection) and the records
+struct PosesResult {
+    DevBuf<int> sel_h, pos_of;
+    uint64_t movable_static = 0, movable_sel = 0;       // static_epoch / sel_epoch the tables were made for (0: none)
+    PoseRecords rec;
+    int64_t P = 0, S = 0, SH = 0;
     bool valid = false;
-    void release() {
-        sel_h.release(); pos_of.release(); xyz.release(); hx.release(); ctr.release(); summary.release(); pose_off.release(); sort.release();
-        slab.release(); movable_static = movable_sel = 0; valid = false;
-    }
+    void release() { sel_h.release(); pos_of.release(); rec.release(); movable_static = movable_sel = 0; valid = false; }
 };
 
 // the ligand library (arp_set_ligand_library, arp_library.h): the ligands' per-atom table beside the receptor.  It reads nothing of
@@ -325,27 +330,19 @@ struct LigandLibrary {
     bool resident = false;
     void release() { atom_off.release(); h_off.release(); sb_nbr.release(); tmask.release(); flags.release(); rad.release(); resident = false; }
 };
-// the contacts of a launch over the library (arp_library_contacts_launch): the uploaded poses and their per-pose / per-ligand
-// tables, the appended records and their sort, the columns in one slab; and the best pose per ligand made from its summary
-// (arp_library_best_launch), which goes with it (void_pose_results)
+// the contacts of a launch over the library (arp_library_contacts_launch): the per-pose / per-ligand tables of the uploaded poses
+// and the records; and the best pose per ligand made from their summary (arp_library_best_launch), which goes with them
+// (void_pose_results)
 struct LibraryResult {
-    DevBuf<float> xyz;
-    DevBuf<double> hx;
     DevBuf<int> lig_of;
     DevBuf<long long> tab;                              // pose_off [L + 1] | xyz_at [L] | hx_at [L]
-    DevBuf<unsigned long long> ctr;                     // [0] records appended, [1] device error
-    DevBuf<uint32_t> summary;
-    DevBuf<unsigned long long> pose_off;
-    SortScratch sort;
-    DevBuf<uint8_t> slab;
-    size_t off[5] = {0, 0, 0, 0, 0};
+    PoseRecords rec;
     DevBuf<long long> best_n, best_score;
     DevBuf<int> best_pose;
-    int64_t L = 0, T = 0, count = 0, blocks = 0;
+    int64_t L = 0, T = 0, blocks = 0;
     bool valid = false, best_valid = false;
     void release() {
-        xyz.release(); hx.release(); lig_of.release(); tab.release(); ctr.release(); summary.release(); pose_off.release(); sort.release();
-        slab.release(); best_n.release(); best_score.release(); best_pose.release(); valid = best_valid = false;
+        lig_of.release(); tab.release(); rec.release(); best_n.release(); best_score.release(); best_pose.release(); valid = best_valid = false;
     }
 };
 
@@ -5421,7 +5418,7 @@ int need_planes_result_of_same_poses(arp_ctx* c, const std::string& fn) {
 // both results keep their uploaded poses: a word that differs ORs 1 into *flag_word (zeroed by the caller, read in its one wait)
 void enqueue_same_poses(arp_ctx* c, void* flag_word) {
     const long long words = (long long)(c->poses.P * c->poses.S * 3);
-    hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(words, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)c->poses.xyz.p,
+    hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(words, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)c->poses.rec.xyz.p,
                        (const uint32_t*)c->pplanes.xyz.p, words, (uint32_t*)flag_word);
 }
 
@@ -5501,6 +5498,71 @@ int append_until_it_fits(arp_ctx* c, const std::string& fn, size_t cap, const un
         cap = (size_t)h[0];
     }
 }
+
+// The frame of both launches over poses (arp_poses_contacts_launch, arp_library_contacts_launch), after the entry's own refusals
+// and voiding: the poses go up (nx floats, nh doubles), `enqueue(sink)` launches the entry's contact kernel over all `poses` of
+// them into `sink` — again with room for the exact count when the first buffer (32 records per posed atom) was too small —, and
+// the tail makes pose_off, sorts by the keybits bits of the key and unpacks the five columns (hi_bits above lo_bits: the two id
+// columns in the key).  One wait a launch of the kernel: the record count with the device's error word.  *count: the records,
+// also before a capacity failure.
+int pose_records_launch(arp_ctx* c, const std::string& fn, PoseRecords& R, int64_t poses, const float* xyz, size_t nx, const double* h_xyz, size_t nh,
+                        int keybits, int hi_bits, int lo_bits, const std::function<int(const PoseSink&)>& enqueue, int64_t* count) {
+    R.count = 0;
+    HIPCHK(c, R.xyz.reserve(std::max<size_t>(nx, 1)));
+    HIPCHK(c, R.hx.reserve(std::max<size_t>(nh, 1)));
+    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (nh > 0) HIPCHK(c, hipMemcpyAsync(R.hx.p, h_xyz, nh * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, R.ctr.reserve(2));
+    HIPCHK(c, R.summary.reserve((size_t)poses * POSES_SUMMARY));
+    HIPCHK(c, R.pose_off.reserve((size_t)poses + 1));
+    PoseSink sink{nullptr, nullptr, 0, R.ctr.p, R.summary.p, (int*)(R.ctr.p + 1)};
+    unsigned long long h[2] = {0, 0};
+    const auto launch = [&](size_t cap) -> int {
+        CHK(reserve_key_sort(c, R.sort, cap, cap));
+        sink.key = R.sort.key[0].p; sink.val = R.sort.val[0].p; sink.cap = cap;
+        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+        return enqueue(sink);
+    };
+    const auto device_error = [&](int dev) -> int {
+        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
+        if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
+        FAIL(c, ARP_E_HIP, fn + "device error");
+    };
+    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (nx / 3) * 32)), R.ctr.p, 2, h, 3, launch, device_error,
+                             count));
+    const size_t k = (size_t)h[0];
+    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)poses, POSES_SUMMARY - 1, R.summary.p, R.pose_off.p);
+    if (k > 0) {
+        int sorted = 0;
+        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
+        size_t bytes = 0;
+        sorted_layout(k, R.off, &bytes, k);
+        HIPCHK(c, R.slab.reserve(bytes));
+        const Columns col{R.slab.p, R.off};
+        hipLaunchKernelGGL(k_pose_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, hi_bits, lo_bits,
+                           R.sort.key[sorted].p, R.sort.val[sorted].p, (int*)col[0], (int*)col[1], (float*)col[2], (uint16_t*)col[3], (uint8_t*)col[4]);
+    }
+    CHK(check_launch(c, "k_poses_offsets / sort / k_pose_columns"));
+    R.count = (int64_t)k;
+    *count = R.count;
+    return ARP_OK;
+}
+// What a fetch of either copies, after the entry's own validity and capacity checks: pose_off and the summary rows of `poses`
+// poses and, `records`, the five columns — whichever the caller gave
+void pose_records_pieces(std::vector<StagePiece>& pieces, const PoseRecords& R, int64_t poses, bool records, uint64_t* pose_off, int32_t* first, int32_t* second,
+                         float* dist, uint16_t* sift, uint8_t* ctype, uint32_t* summary) {
+    const size_t k = (size_t)R.count;
+    want_piece(pieces, pose_off, R.pose_off.p, ((size_t)poses + 1) * sizeof(uint64_t));
+    want_piece(pieces, summary, R.summary.p, (size_t)poses * POSES_SUMMARY * sizeof(uint32_t));
+    if (records && k > 0) {
+        const uint8_t* const slab = R.slab.p;
+        want_piece(pieces, first, slab + R.off[0], k * sizeof(int32_t));
+        want_piece(pieces, second, slab + R.off[1], k * sizeof(int32_t));
+        want_piece(pieces, dist, slab + R.off[2], k * sizeof(float));
+        want_piece(pieces, sift, slab + R.off[3], k * sizeof(uint16_t));
+        want_piece(pieces, ctype, slab + R.off[4], k * sizeof(uint8_t));
+    }
+}
 }  // namespace
 
 // ---- ligand poses on the resident receptor (arp_poses.h): every pose's ligand - receptor records in one launch
@@ -5547,18 +5609,9 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     if (SH > 0 && !h_xyz) FAIL(c, ARP_E_ARG, fn + "h_xyz missing (the movable set has hydrogens)");
     // ---- from here on the previous result is gone, and what was made from it
     void_pose_results(c, POSE_CONTACTS);
-    R.count = 0;
-    HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
-    HIPCHK(c, R.hx.reserve(std::max<size_t>((size_t)P * (size_t)SH * 3, 1)));
-    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)P * S * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (SH > 0) HIPCHK(c, hipMemcpyAsync(R.hx.p, h_xyz, (size_t)P * (size_t)SH * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, R.ctr.reserve(2));
-    HIPCHK(c, R.summary.reserve((size_t)P * POSES_SUMMARY));
-    HIPCHK(c, R.pose_off.reserve((size_t)P + 1));
     PoseArgs A{};
     A.n = n; A.S = S; A.P = (int)P; A.SH = SH;
     A.sel_list = c->sel_list.p; A.sel_h = R.sel_h.p; A.pos_of = R.pos_of.p; A.sel = c->sel.p;
-    A.pxyz = R.xyz.p; A.phx = R.hx.p;
     A.st_xyzm = c->st_xyzm.p; A.st_aux = c->st_aux.p; A.st_qa = c->st_qa.p; A.h_off = c->h_off.p; A.rad = c->rad.p; A.sb = c->sb.p;
     A.sb_nbr = c->sb_index_src == 1 ? c->sb_idx.p : c->blob_sb_nbr.p;
     A.bond_off = c->bond_off.p; A.bond_idx = c->bond_idx.p; A.h_xyz = c->h_xyz_d.p;
@@ -5566,39 +5619,14 @@ int arp_poses_contacts_launch(arp_ctx* c, int64_t n_poses, const float* xyz, con
     A.start = c->sp_cnt.p + 4; A.g = c->sp_grid;
     A.r2 = cutoff * cutoff; A.comp = vdw_comp; A.include_seq_adj = include_sequence_adjacent ? 1 : 0;
     A.idbits = index_bits(c->n);
-    A.count = R.ctr.p; A.err = (int*)(R.ctr.p + 1);
-    A.summary = R.summary.p;
-    const int keybits = 2 * A.idbits + index_bits(P);
-    unsigned long long h[2] = {0, 0};
-    const auto launch = [&](size_t cap) -> int {
-        CHK(reserve_key_sort(c, R.sort, cap, cap));
-        A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
-        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const auto enqueue = [&](const PoseSink& sink) -> int {
+        A.pxyz = R.rec.xyz.p; A.phx = R.rec.hx.p; A.out = sink;
         hipLaunchKernelGGL(k_poses_contacts, dim3((unsigned)P), dim3(POSES_THREADS), 0, c->stream, A);
         return check_launch(c, "k_poses_contacts");
     };
-    const auto device_error = [&](int dev) -> int {
-        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
-        if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
-        FAIL(c, ARP_E_HIP, fn + "device error");
-    };
-    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)P * (size_t)S * 32)), R.ctr.p, 2, h, 3, launch,
-                             device_error, count));
-    const size_t k = (size_t)h[0];
-    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)P, POSES_SUMMARY - 1, R.summary.p, R.pose_off.p);
-    if (k > 0) {
-        int sorted = 0;
-        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
-        size_t bytes = 0;
-        sorted_layout(k, R.off, &bytes, k);
-        HIPCHK(c, R.slab.reserve(bytes));
-        const Columns col{R.slab.p, R.off};
-        hipLaunchKernelGGL(k_poses_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, A.idbits,
-                           R.sort.key[sorted].p, R.sort.val[sorted].p, (int*)col[0], (int*)col[1], (float*)col[2], (uint16_t*)col[3], (uint8_t*)col[4]);
-    }
-    CHK(check_launch(c, "k_poses_offsets / sort / k_poses_columns"));
-    R.P = P; R.count = (int64_t)k; R.valid = true;
-    *count = R.count;
+    CHK(pose_records_launch(c, fn, R.rec, P, xyz, (size_t)P * S * 3, h_xyz, (size_t)P * (size_t)SH * 3, 2 * A.idbits + index_bits(P), A.idbits, A.idbits,
+                            enqueue, count));
+    R.P = P; R.valid = true;
     return ARP_OK;
 }
 
@@ -5607,21 +5635,16 @@ int arp_poses_contacts_fetch(arp_ctx* c, int64_t cap, uint64_t* pose_off, int32_
     if (!c || !count) return ARP_E_ARG;
     const PosesResult& R = c->poses;
     if (!R.valid) FAIL(c, ARP_E_ARG, "arp_poses_contacts_fetch: no result (arp_poses_contacts_launch; an input or the selection changed since)");
-    *count = R.count;
+    *count = R.rec.count;
     const bool records = i || j || dist || sift || ctype;
-    if (records && R.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_poses_contacts_fetch: output buffers too small");
+    if (records && R.rec.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_poses_contacts_fetch: output buffers too small");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)R.count;
-    CHK(download_async(c, (unsigned long long*)pose_off, (const unsigned long long*)R.pose_off.p, (size_t)R.P + 1));
-    CHK(download_async(c, summary, (const uint32_t*)R.summary.p, (size_t)R.P * POSES_SUMMARY));
-    if (records && k > 0) {
-        const uint8_t* const slab = R.slab.p;
-        CHK(download_async(c, i, (const int32_t*)(slab + R.off[0]), k));
-        CHK(download_async(c, j, (const int32_t*)(slab + R.off[1]), k));
-        CHK(download_async(c, dist, (const float*)(slab + R.off[2]), k));
-        CHK(download_async(c, sift, (const uint16_t*)(slab + R.off[3]), k));
-        CHK(download_async(c, ctype, (const uint8_t*)(slab + R.off[4]), k));
-    }
+    // Straight into the caller's arrays, one wait: 6 M records of 16 384 poses are 93 MB, and a second copy of them on the host (the
+    // stage of the other fetches) costs this fetch more than pageable destinations do (the timing check)
+    std::vector<StagePiece> pieces;
+    pose_records_pieces(pieces, R.rec, R.P, records, pose_off, i, j, dist, sift, ctype, summary);
+    for (const StagePiece& q : pieces)
+        HIPCHK(c, hipMemcpyAsync(q.dst, q.src, q.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ARP_OK;
 }
@@ -5632,7 +5655,7 @@ int arp_poses_contacts_info(arp_ctx* c, int64_t info[4]) {
     info[0] = R.valid ? R.P : 0;
     info[1] = R.valid ? R.S : 0;
     info[2] = R.valid ? R.SH : 0;
-    info[3] = R.valid ? R.count : 0;
+    info[3] = R.valid ? R.rec.count : 0;
     return ARP_OK;
 }
 
@@ -5733,61 +5756,25 @@ int arp_library_contacts_launch(arp_ctx* c, const int64_t* pose_off, const float
     // ---- from here on the previous result is gone, and the best-pose table made from it
     LibraryResult& R = c->libres;
     void_pose_results(c, POSE_LIBRARY_CONTACTS);
-    R.count = 0;
-    HIPCHK(c, R.xyz.reserve((size_t)std::max<long long>(nx, 1)));
-    HIPCHK(c, R.hx.reserve((size_t)std::max<long long>(nh, 1)));
-    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (nh > 0) HIPCHK(c, hipMemcpyAsync(R.hx.p, h_xyz, (size_t)nh * sizeof(double), hipMemcpyHostToDevice, c->stream));
     CHK(upload_async(c, R.tab, tab.data(), tab.size()));
     CHK(upload_async(c, R.lig_of, lig_of.data(), lig_of.size()));
-    HIPCHK(c, R.ctr.reserve(2));
-    HIPCHK(c, R.summary.reserve((size_t)T * POSES_SUMMARY));
-    HIPCHK(c, R.pose_off.reserve((size_t)T + 1));
     LibraryArgs A{};
     A.n = (int)c->n; A.T = (int)T;
     A.atom_off = B.atom_off.p; A.tmask = B.tmask.p; A.flags = B.flags.p; A.lrad = B.rad.p; A.lh_off = B.h_off.p; A.lsb_nbr = B.sb_nbr.p;
     A.lig_of = R.lig_of.p; A.first_pose = R.tab.p; A.xyz_at = R.tab.p + L + 1; A.hx_at = R.tab.p + 2 * L + 1;
-    A.pxyz = R.xyz.p; A.phx = R.hx.p;
     A.rad = c->rad.p; A.sb = c->sb.p; A.h_off = c->h_off.p; A.h_xyz = c->h_xyz_d.p;
     A.sp_xyzm = c->sp_xyzm.p; A.sp_aux = c->sp_aux.p; A.sp_qa = c->sp_qa.p; A.sp_h = c->sp_h.p;
     A.start = c->sp_cnt.p + 4; A.g = c->sp_grid;
     A.r2 = cutoff * cutoff; A.comp = vdw_comp;
     A.ibits = index_bits(c->n); A.abits = index_bits(B.max_atoms);
-    A.count = R.ctr.p; A.err = (int*)(R.ctr.p + 1);
-    A.summary = R.summary.p;
-    const int keybits = A.ibits + A.abits + index_bits(T);
     const unsigned blocks = (unsigned)std::min<int64_t>(T, (int64_t)LIB_BLOCKS_PER_CU * std::max(c->num_cu, 1));
-    unsigned long long h[2] = {0, 0};
-    const auto launch = [&](size_t cap) -> int {
-        CHK(reserve_key_sort(c, R.sort, cap, cap));
-        A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
-        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    const auto enqueue = [&](const PoseSink& sink) -> int {
+        A.pxyz = R.rec.xyz.p; A.phx = R.rec.hx.p; A.out = sink;
         hipLaunchKernelGGL(k_library_contacts, dim3(blocks), dim3(LIB_THREADS), 0, c->stream, A);
         return check_launch(c, "k_library_contacts");
     };
-    const auto device_error = [&](int dev) -> int {
-        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
-        if (dev == ARP_E_XBOND_NBR) FAIL(c, ARP_E_XBOND_NBR, "xbond donor without a single-bond heavy neighbour (reference: AttributeError at utils.py:173)");
-        FAIL(c, ARP_E_HIP, fn + "device error");
-    };
-    // (the first buffer: 32 records per posed ligand atom, as arp_poses_contacts_launch sizes it)
-    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)(nx / 3) * 32)), R.ctr.p, 2, h, 3, launch,
-                             device_error, count));
-    const size_t k = (size_t)h[0];
-    hipLaunchKernelGGL(k_poses_offsets, dim3(1), dim3(1024), 0, c->stream, (int)T, POSES_SUMMARY - 1, R.summary.p, R.pose_off.p);
-    if (k > 0) {
-        int sorted = 0;
-        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
-        size_t bytes = 0;
-        sorted_layout(k, R.off, &bytes, k);
-        HIPCHK(c, R.slab.reserve(bytes));
-        const Columns col{R.slab.p, R.off};
-        hipLaunchKernelGGL(k_library_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, A.ibits, A.abits,
-                           R.sort.key[sorted].p, R.sort.val[sorted].p, (int*)col[0], (int*)col[1], (float*)col[2], (uint16_t*)col[3], (uint8_t*)col[4]);
-    }
-    CHK(check_launch(c, "k_poses_offsets / sort / k_library_columns"));
-    R.L = L; R.T = T; R.count = (int64_t)k; R.blocks = (int64_t)blocks; R.valid = true;
-    *count = R.count;
+    CHK(pose_records_launch(c, fn, R.rec, T, xyz, (size_t)nx, h_xyz, (size_t)nh, A.ibits + A.abits + index_bits(T), A.ibits, A.abits, enqueue, count));
+    R.L = L; R.T = T; R.blocks = (int64_t)blocks; R.valid = true;
     return ARP_OK;
 }
 
@@ -5796,22 +5783,12 @@ int arp_library_contacts_fetch(arp_ctx* c, int64_t cap, uint64_t* pose_off, int3
     if (!c || !count) return ARP_E_ARG;
     const LibraryResult& R = c->libres;
     if (!R.valid) FAIL(c, ARP_E_ARG, "arp_library_contacts_fetch: no result (arp_library_contacts_launch; the structure or the library changed since)");
-    *count = R.count;
+    *count = R.rec.count;
     const bool records = i || a || dist || sift || ctype;
-    if (records && R.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_library_contacts_fetch: output buffers too small");
+    if (records && R.rec.count > cap) FAIL(c, ARP_E_CAPACITY, "arp_library_contacts_fetch: output buffers too small");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)R.count;
     std::vector<StagePiece> pieces;
-    want_piece(pieces, pose_off, R.pose_off.p, ((size_t)R.T + 1) * sizeof(uint64_t));
-    want_piece(pieces, summary, R.summary.p, (size_t)R.T * POSES_SUMMARY * sizeof(uint32_t));
-    if (records && k > 0) {
-        const uint8_t* const slab = R.slab.p;
-        want_piece(pieces, i, slab + R.off[0], k * sizeof(int32_t));
-        want_piece(pieces, a, slab + R.off[1], k * sizeof(int32_t));
-        want_piece(pieces, dist, slab + R.off[2], k * sizeof(float));
-        want_piece(pieces, sift, slab + R.off[3], k * sizeof(uint16_t));
-        want_piece(pieces, ctype, slab + R.off[4], k * sizeof(uint8_t));
-    }
+    pose_records_pieces(pieces, R.rec, R.T, records, pose_off, i, a, dist, sift, ctype, summary);
     return stage_fetch(c, pieces);
 }
 
@@ -5821,7 +5798,7 @@ int arp_library_info(arp_ctx* c, int64_t info[8]) {
     const LibraryResult& R = c->libres;
     info[0] = B.resident ? B.L : 0;
     info[1] = R.valid ? R.T : 0;
-    info[2] = R.valid ? R.count : 0;
+    info[2] = R.valid ? R.rec.count : 0;
     info[3] = B.resident ? B.atoms : 0;
     info[4] = B.resident ? B.hrows : 0;
     info[5] = R.valid ? R.blocks : 0;
@@ -5848,7 +5825,7 @@ int arp_library_best_launch(arp_ctx* c, const int32_t* weights) {
     HIPCHK(c, R.best_score.reserve((size_t)R.L));
     HIPCHK(c, R.best_pose.reserve((size_t)R.L));
     hipLaunchKernelGGL(k_library_best, dim3(nblocks(R.L * 64, 256, 2048)), dim3(256), 0, c->stream, (int)R.L, (const long long*)R.tab.p,
-                       (const uint32_t*)R.summary.p, W, R.best_n.p, R.best_pose.p, R.best_score.p);
+                       (const uint32_t*)R.rec.summary.p, W, R.best_n.p, R.best_pose.p, R.best_score.p);
     CHK(check_launch(c, "k_library_best"));
     R.best_valid = true;
     return ARP_OK;
@@ -6125,7 +6102,7 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t N = by_res ? c->nres : c->n, NW = (N + 63) / 64;
     const int NP = __builtin_popcount(planes);
-    const size_t k = (size_t)R.count;
+    const size_t k = (size_t)R.rec.count;
     HIPCHK(c, F.presence.reserve((size_t)NW));
     HIPCHK(c, F.base.reserve((size_t)NW));
     HIPCHK(c, F.total.reserve(2));      // U; the same-poses flag
@@ -6133,10 +6110,10 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     HIPCHK(c, F.cross.reserve(std::max<size_t>((size_t)(P * Q), 1)));
     if (all_pairs) HIPCHK(c, F.inter.reserve((size_t)(P * P)));
     PoseFpArgs A{};
-    const uint8_t* const slab = R.slab.p;
-    A.ci = (const int*)(slab + R.off[0]); A.cj = (const int*)(slab + R.off[1]);
-    A.sift = (const uint16_t*)(slab + R.off[3]); A.ctype = slab + R.off[4];
-    A.pose_off = R.pose_off.p; A.pos_of = R.pos_of.p; A.res_id = c->res_id.p;
+    const uint8_t* const slab = R.rec.slab.p;
+    A.ci = (const int*)(slab + R.rec.off[0]); A.cj = (const int*)(slab + R.rec.off[1]);
+    A.sift = (const uint16_t*)(slab + R.rec.off[3]); A.ctype = slab + R.rec.off[4];
+    A.pose_off = R.rec.pose_off.p; A.pos_of = R.pos_of.p; A.res_id = c->res_id.p;
     A.k = (long long)k; A.P = (int)P; A.Q = (int)Q; A.N = N; A.by_res = by_res ? 1 : 0;
     A.planes = planes; A.ctype_mask = ctype_mask;
     A.presence = F.presence.p; A.base = F.base.p; A.NW = NW; A.total = F.total.p;
@@ -6342,13 +6319,13 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     HIPCHK(c, S.len.reserve((size_t)ncand * PSL_TABLES));
     HIPCHK(c, S.off.reserve(((size_t)ncand + 1) * PSL_TABLES));
     PslArgs A{};
-    const uint8_t* const slab = R.slab.p;      // (no record: the columns are never read, every segment is empty)
-    if (R.count > 0) {
-        A.ci = (const int*)(slab + R.off[0]); A.cj = (const int*)(slab + R.off[1]); A.cd = (const float*)(slab + R.off[2]);
-        A.cs = (const uint16_t*)(slab + R.off[3]); A.cct = slab + R.off[4];
+    const uint8_t* const slab = R.rec.slab.p;      // (no record: the columns are never read, every segment is empty)
+    if (R.rec.count > 0) {
+        A.ci = (const int*)(slab + R.rec.off[0]); A.cj = (const int*)(slab + R.rec.off[1]); A.cd = (const float*)(slab + R.rec.off[2]);
+        A.cs = (const uint16_t*)(slab + R.rec.off[3]); A.cct = slab + R.rec.off[4];
     }
-    A.aa_off = R.pose_off.p; A.aa_count = R.count;
-    A.summary = R.summary.p; A.P = (int)P;
+    A.aa_off = R.rec.pose_off.p; A.aa_count = R.rec.count;
+    A.summary = R.rec.summary.p; A.P = (int)P;
     if (planes) {
         A.pl = L.col; A.pl_off = L.pose_off.p; A.pl_summary = L.summary.p;
         for (int t = 0; t < 4; ++t) A.pl_count[t] = L.counts[t];

@@ -7,13 +7,13 @@
 // (ligand, pose) items: for global pose t of ligand l exactly the records with one receptor and one ligand atom that a pass
 // over the complex (the receptor with ligand l appended as one more residue, the pose scattered in, the ligand selected) emits.
 //
-//   k_library_contacts  a block per pose (grid stride over T), a wave per ligand heavy atom at a time; the cell walk, nine-row
-//                       flattening, box clamp and per-wave LDS queue of k_poses_contacts.  New: at the start of a pose the block
-//                       stages the ligand's table rows and the pose's coordinates in LDS, so the radii, the single-bond
-//                       neighbour's coordinate and the hydrogen range of the ligand side are LDS reads
-//   k_library_columns   the sorted (key, payload) pairs as the five columns
+//   k_library_contacts  a block per pose (grid stride over T), a wave per ligand heavy atom at a time; the cell walk, the
+//                       resident partner, the per-wave LDS queue and the summary are the inline pieces of arp_poses.h that
+//                       k_poses_contacts is made of.  Its own: at the start of a pose the block stages the ligand's table rows
+//                       and the pose's coordinates in LDS, so the radii, the single-bond neighbour's coordinate and the
+//                       hydrogen range of the ligand side are LDS reads
 //   k_library_best      per ligand the best pose by a weighted sum of its summary row: a wave per ligand, no atomics
-//   (k_poses_offsets of arp_poses.h makes pose_off, as it is)
+//   (k_poses_offsets of arp_poses.h makes pose_off and k_pose_columns the five columns, as they are)
 //
 // Why the filters of k_search vanish (arp_poses.h, the filter block of k_poses_contacts): a ligand is one residue of a chain of
 // its own, no polypeptide residue, without sequence neighbours and without a bond to the receptor.  So I:729 (same residue)
@@ -71,13 +71,7 @@ struct LibraryArgs {
     GridDesc g;
     double r2, comp;
     int ibits, abits;
-    // out
-    u64* key;
-    u64* val;
-    u64 cap;
-    u64* count;
-    uint32_t* summary;          // [T][16]
-    int* err;
+    PoseSink out;
 };
 
 // How k_library_contacts reads what pose_pair_sift needs beside the two atoms.  bgn is the receptor atom (resident arrays by local
@@ -88,7 +82,7 @@ struct LibraryReader {
     const float* s_x;
     const int* s_nbr;
     __device__ __forceinline__ double comp() const { return A.comp; }
-    __device__ __forceinline__ int* err() const { return A.err; }
+    __device__ __forceinline__ int* err() const { return A.out.err; }
     __device__ __forceinline__ double2 rad(const PoseAtom& a, bool of_b) const { return of_b ? A.rad[a.lid] : s_rad[a.lid]; }
     __device__ __forceinline__ float4 sb(int, const PoseAtom& B, const PoseAtom& E, bool of_b) const {
         if (of_b) return A.sb[B.lid];
@@ -111,16 +105,6 @@ __global__ __launch_bounds__(LIB_THREADS) void k_library_contacts(LibraryArgs A)
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const GridDesc g = A.g;
     int qn = 0;
-    auto flush = [&]() {
-        __builtin_amdgcn_wave_barrier();
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(A.count, (u64)qn);
-        base = __shfl(base, 0);
-        for (int k = lane; k < qn; k += 64)
-            if (base + k < A.cap) { A.key[base + k] = q_key[w][k]; A.val[base + k] = q_val[w][k]; }
-        __builtin_amdgcn_wave_barrier();
-        qn = 0;
-    };
     for (int pose = blockIdx.x; pose < A.T; pose += gridDim.x) {
         // ---- stage the ligand's table rows and the pose's coordinates (the host has checked every offset and index; S is clamped
         // all the same: the staging arrays hold LIB_MAX_ATOMS rows)
@@ -154,47 +138,26 @@ __global__ __launch_bounds__(LIB_THREADS) void k_library_contacts(LibraryArgs A)
         }
         for (int k = threadIdx.x; k < 3 * SH; k += LIB_THREADS) bad |= !isfinite(phx[k]);
         if (__syncthreads_or(bad ? 1 : 0)) {
-            if (threadIdx.x == 0) atomicExch(A.err, ARP_E_ARG);
-            if (threadIdx.x < POSES_SUMMARY) A.summary[(size_t)pose * POSES_SUMMARY + threadIdx.x] = 0u;
+            if (threadIdx.x == 0) atomicExch(A.out.err, ARP_E_ARG);
+            if (threadIdx.x < POSES_SUMMARY) A.out.summary[(size_t)pose * POSES_SUMMARY + threadIdx.x] = 0u;
             __syncthreads();      // (the next pose stages over these rows)
             continue;
         }
-        uint32_t cnt[POSES_SUMMARY];
-#pragma unroll
-        for (int b = 0; b < POSES_SUMMARY; ++b) cnt[b] = 0u;
+        PoseCounts cnt;
+        cnt.clear();
         const LibraryReader reader{A, s_rad, s_x, s_nbr};
         for (int s = w; s < S; s += LIB_WAVES) {
             const uint32_t mh = s_m[s];
             if (mh & M_HYDROGEN) continue;                               // I:712
             const float pxs = s_x[3 * s], pys = s_x[3 * s + 1], pzs = s_x[3 * s + 2];
             const int ph0 = s_h[s], ph1 = s_h[s + 1];
-            // the 27 cells around the pose atom, clamped to the grid: an atom a whole cell (>= the cutoff) beyond a face has no partner
-            const int cx = cell_coord_raw((double)pxs, g.ox, g.inv, g.nx), cy = cell_coord_raw((double)pys, g.oy, g.inv, g.ny),
-                      cz = cell_coord_raw((double)pzs, g.oz, g.inv, g.nz);
-            if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny || cz < -1 || cz > g.nz) continue;
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
-            // nine rows of up to three x-neighbours, each a contiguous range of the cell order: lane r < 9 holds row r
-            int rbeg = 0, rlen = 0;
-            if (lane < 9) {
-                const int z = cz - 1 + lane / 3, y = cy - 1 + lane % 3;
-                if (z >= 0 && z < g.nz && y >= 0 && y < g.ny && x0 <= x1) {
-                    const int row = (z * g.ny + y) * g.nx;
-                    const int b0 = A.start[row + x0], b1 = A.start[row + x1 + 1];
-                    rbeg = min(max(b0, 0), A.n);
-                    rlen = max(min(b1, A.n) - rbeg, 0);
-                }
-            }
-            int incl = rlen;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const int u = __shfl_up(incl, off);
-                if (lane >= off) incl += u;
-            }
-            const int total = __shfl(incl, 8);
+            const PoseRow row = pose_cell_rows(g, A.start, A.n, pxs, pys, pzs, lane);
+            if (!row.inside) continue;
+            const int total = __shfl(row.incl, 8);
             int rb_[9], re_[9];      // start of row r minus the candidates before it; candidates up to and including row r
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
-                const int i_ = __shfl(incl, r), l_ = __shfl(rlen, r), b_ = __shfl(rbeg, r);
+                const int i_ = __shfl(row.incl, r), l_ = __shfl(row.len, r), b_ = __shfl(row.beg, r);
                 re_[r] = i_;
                 rb_[r] = b_ - (i_ - l_);
             }
@@ -221,15 +184,9 @@ __global__ __launch_bounds__(LIB_THREADS) void k_library_contacts(LibraryArgs A)
                 uint32_t sft = 0;
                 u64 key = 0, val = 0;
                 if (pass) {
-                    PoseAtom H, J;
+                    PoseAtom H;
                     H.x = {pxs, pys, pzs}; H.m = mh; H.lid = s; H.qa = make_int4(s, -1, -1, -1); H.hx = phx; H.h0 = ph0; H.h1 = ph1;
-                    J.x = xyz_of(v); J.m = mj; J.lid = aj.x; J.qa = A.sp_qa[pos]; J.hx = A.h_xyz;
-                    J.h0 = A.sp_h[pos];
-                    {
-                        const unsigned hc = (mj >> M_HCNT_SHIFT) & 3u;
-                        J.h1 = (mj & M_HAS_H) ? J.h0 + 1 + (int)hc : J.h0;
-                        if ((mj & M_HAS_H) && hc == M_HCNT_ESC) J.h1 = A.h_off[aj.x + 1];
-                    }
+                    const PoseAtom J = pose_resident_atom(pos, v, aj, A.sp_qa, A.sp_h, A.h_off, A.h_xyz);
                     const float d = num::norm(num::sub(J.x, H.x));                      // interactions.py:745, bgn = the receptor atom
                     int ct = 0;
                     sft = pose_pair_sift(reader, pose, J, H, d, &ct);
@@ -237,59 +194,12 @@ __global__ __launch_bounds__(LIB_THREADS) void k_library_contacts(LibraryArgs A)
                     val = (u64)__float_as_uint(d) | ((u64)sft << 32) | ((u64)(unsigned)ct << 48);
                 }
                 const unsigned long long mp = __ballot(pass);
-                if (mp) {
-                    if (pass) {
-                        const int slot = qn + __popcll(mp & ((1ull << lane) - 1ull));
-                        q_key[w][slot] = key;
-                        q_val[w][slot] = val;
-                    }
-#pragma unroll
-                    for (int b = 0; b < POSES_SUMMARY - 1; ++b) cnt[b] += (uint32_t)__popcll(__ballot(pass && ((sft >> b) & 1u)));
-                    cnt[POSES_SUMMARY - 1] += (uint32_t)__popcll(mp);
-                    qn += __popcll(mp);
-                    if (qn > LIB_QCAP - 64) flush();
-                }
+                if (mp) pose_queue_push(A.out, q_key[w], q_val[w], qn, cnt, lane, mp, pass, key, val, sft);
             }
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int b = 0; b < POSES_SUMMARY; ++b)
-                if (cnt[b]) atomicAdd(&s_sum[b], cnt[b]);
-        }
-        __syncthreads();
-        if (threadIdx.x < POSES_SUMMARY) A.summary[(size_t)pose * POSES_SUMMARY + threadIdx.x] = s_sum[threadIdx.x];
-        __syncthreads();      // (the next pose stages over the rows and clears s_sum)
+        cnt.store(s_sum, lane, A.out.summary + (size_t)pose * POSES_SUMMARY);      // (the next pose stages over the rows, too)
     }
-    // end of block: what is left in the per-wave queues leaves with ONE atomic
-    if (lane == 0) s_qn[w] = qn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int k = 0; k < LIB_WAVES; ++k) tot += s_qn[k];
-        s_base = tot > 0 ? atomicAdd(A.count, (u64)tot) : 0ull;
-    }
-    __syncthreads();
-    if (qn > 0) {
-        u64 base = s_base;
-        for (int k = 0; k < w; ++k) base += (u64)s_qn[k];
-        for (int k = lane; k < qn; k += 64)
-            if (base + k < A.cap) { A.key[base + k] = q_key[w][k]; A.val[base + k] = q_val[w][k]; }
-    }
-}
-
-// the sorted (key, payload) pairs as the result's five columns: i the receptor's packed id, a the atom's index within its ligand
-__global__ __launch_bounds__(256) void k_library_columns(long long k, int ibits, int abits, const u64* __restrict__ key, const u64* __restrict__ val,
-                                                         int* __restrict__ ci, int* __restrict__ ca, float* __restrict__ cd,
-                                                         uint16_t* __restrict__ cs, uint8_t* __restrict__ cct) {
-    const u64 imask = (1ull << ibits) - 1ull, amask = (1ull << abits) - 1ull;
-    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < k; p += (long long)gridDim.x * blockDim.x) {
-        const u64 kk = key[p], v = val[p];
-        ci[p] = (int)((kk >> abits) & imask);
-        ca[p] = (int)(kk & amask);
-        cd[p] = __uint_as_float((uint32_t)v);
-        cs[p] = (uint16_t)(v >> 32);
-        cct[p] = (uint8_t)(v >> 48);
-    }
+    pose_queue_drain(A.out, q_key[w], q_val[w], qn, lane, w, s_qn, &s_base);
 }
 
 // Best pose per ligand: score[t] = sum over the slots of w[s] summary[t][s] in int64 (|w| <= 2^24, a slot < 2^32: the sum fits

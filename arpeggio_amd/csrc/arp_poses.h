@@ -10,8 +10,10 @@
 //                     rows (h_off order, parents selected), their number SH, and the position s of every selected local id
 //   k_poses_contacts  one block per pose, one wave per selected atom at a time: the 27 cells around the pose atom in the
 //                     resident cell order, filters, decision, records appended as (key, payload) for the radix sort of
-//                     arp_sort.h, and the per-pose summary (records per SIFt bit, total) reduced in LDS: one store per pose
-//   k_poses_columns   the sorted (key, payload) pairs as the five columns
+//                     arp_sort.h, and the per-pose summary (records per SIFt bit, total) reduced in LDS: one store per pose.
+//                     Its record queue, cell walk, resident partner and summary are the inline pieces (pose_queue_*,
+//                     pose_cell_rows, pose_resident_atom, PoseCounts) that k_library_contacts of arp_library.h uses too
+//   k_pose_columns    the sorted (key, payload) pairs as the five columns (of a library result as well)
 //   k_poses_offsets   pose_off[p] = exclusive prefix of the summaries' totals (block t: of slot first_slot + t; the poses-planes
 //                     result launches it too, a block per table)
 //
@@ -38,6 +40,17 @@
 #define POSES_WAVES (POSES_THREADS / 64)
 #define POSES_QCAP 256
 #define POSES_SUMMARY 16
+
+// Where a launch's records go: the unsorted (key, payload) buffers with their capacity, the exact count (also beyond cap), the
+// per-pose summary rows and the device's error word
+struct PoseSink {
+    u64* key;
+    u64* val;
+    u64 cap;
+    u64* count;
+    uint32_t* summary;          // [poses][16]
+    int* err;
+};
 
 struct PoseArgs {
     int n, S, P;
@@ -71,13 +84,7 @@ struct PoseArgs {
     double r2, comp;
     int include_seq_adj;
     int idbits;
-    // out
-    u64* key;
-    u64* val;
-    u64 cap;
-    u64* count;                 // records appended (exact, also beyond cap)
-    uint32_t* summary;          // [P][16]
-    int* err;
+    PoseSink out;
 };
 
 __global__ __launch_bounds__(1024) void k_poses_movable(int S, const int* __restrict__ sel_list, const int* __restrict__ h_off,
@@ -147,7 +154,7 @@ __device__ __forceinline__ float4 pose_sb(const PoseArgs& A, int pose, int a) {
 struct PoseResidentReader {
     const PoseArgs& A;
     __device__ __forceinline__ double comp() const { return A.comp; }
-    __device__ __forceinline__ int* err() const { return A.err; }
+    __device__ __forceinline__ int* err() const { return A.out.err; }
     // {vdw, cov} of bgn (of_b) or end
     __device__ __forceinline__ double2 rad(const PoseAtom& a, bool) const { return A.rad[a.lid]; }
     // the single-bond neighbour of bgn (of_b) or end: x, y, z, present
@@ -268,6 +275,122 @@ __device__ __forceinline__ uint32_t pose_pair_sift(const Reader& R, int pose, co
     return s;
 }
 
+// ---- what k_poses_contacts and k_library_contacts (arp_library.h) share.  Every piece is inlined and only scalars cross its
+// boundary: a helper that takes or returns the nine-row arrays of the walk gives both kernels scratch, so the
+// nine-entry fill and the position select stay in the kernels.
+
+// The per-pose summary: records per SIFt bit and, in the last slot, all of them.  A wave counts by ballot (add, mp != 0 the
+// ballot of pass); at the end of the pose lane 0 of every wave adds into s_sum (zeroed by the block before) and the block
+// stores the row (store: every thread calls it)
+struct PoseCounts {
+    uint32_t c[POSES_SUMMARY];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int b = 0; b < POSES_SUMMARY; ++b) c[b] = 0u;
+    }
+    __device__ __forceinline__ void add(unsigned long long mp, bool pass, uint32_t sft) {
+#pragma unroll
+        for (int b = 0; b < POSES_SUMMARY - 1; ++b) c[b] += (uint32_t)__popcll(__ballot(pass && ((sft >> b) & 1u)));
+        c[POSES_SUMMARY - 1] += (uint32_t)__popcll(mp);
+    }
+    __device__ __forceinline__ void store(uint32_t* s_sum, int lane, uint32_t* row) const {
+        if (lane == 0) {
+#pragma unroll
+            for (int b = 0; b < POSES_SUMMARY; ++b)
+                if (c[b]) atomicAdd(&s_sum[b], c[b]);
+        }
+        __syncthreads();
+        if (threadIdx.x < POSES_SUMMARY) row[threadIdx.x] = s_sum[threadIdx.x];
+        __syncthreads();      // (the next pose clears s_sum)
+    }
+};
+
+// The per-wave record queue: qk / qv are the wave's rows (POSES_QCAP entries each) of the kernel's LDS arrays, qn what they hold.
+// flush: the queued records leave with one atomic of lane 0
+__device__ __forceinline__ void pose_queue_flush(const PoseSink& o, const u64* qk, const u64* qv, int& qn, int lane) {
+    __builtin_amdgcn_wave_barrier();
+    u64 base = 0;
+    if (lane == 0) base = atomicAdd(o.count, (u64)qn);
+    base = __shfl(base, 0);
+    for (int k = lane; k < qn; k += 64)
+        if (base + k < o.cap) { o.key[base + k] = qk[k]; o.val[base + k] = qv[k]; }
+    __builtin_amdgcn_wave_barrier();
+    qn = 0;
+}
+// push: the survivors of one ballot (mp != 0) take consecutive slots and are counted; a queue that could not take 64 more is flushed
+__device__ __forceinline__ void pose_queue_push(const PoseSink& o, u64* qk, u64* qv, int& qn, PoseCounts& cnt, int lane, unsigned long long mp, bool pass,
+                                                u64 key, u64 val, uint32_t sft) {
+    if (pass) {
+        const int slot = qn + __popcll(mp & ((1ull << lane) - 1ull));
+        qk[slot] = key;
+        qv[slot] = val;
+    }
+    cnt.add(mp, pass, sft);
+    qn += __popcll(mp);
+    if (qn > POSES_QCAP - 64) pose_queue_flush(o, qk, qv, qn, lane);
+}
+// end of block (every thread calls it): what is left in the per-wave queues leaves with ONE atomic
+__device__ __forceinline__ void pose_queue_drain(const PoseSink& o, const u64* qk, const u64* qv, int qn, int lane, int w, int* s_qn, u64* s_base) {
+    if (lane == 0) s_qn[w] = qn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int k = 0; k < POSES_WAVES; ++k) tot += s_qn[k];
+        *s_base = tot > 0 ? atomicAdd(o.count, (u64)tot) : 0ull;
+    }
+    __syncthreads();
+    if (qn > 0) {
+        u64 base = *s_base;
+        for (int k = 0; k < w; ++k) base += (u64)s_qn[k];
+        for (int k = lane; k < qn; k += 64)
+            if (base + k < o.cap) { o.key[base + k] = qk[k]; o.val[base + k] = qv[k]; }
+    }
+}
+
+// The cell walk around a pose atom, per lane: the 27 cells around it, clamped to the grid.  A pose may lie outside the receptor's
+// box: an atom a whole cell (>= the cutoff) beyond a face has no partner (inside = false).  Else nine rows of up to three
+// x-neighbours, each a contiguous range of the cell order: lane r < 9 holds row r — its first position, its length, and the
+// candidates up to and including it (lane 8: all of them)
+struct PoseRow { int beg, len, incl; bool inside; };
+__device__ __forceinline__ PoseRow pose_cell_rows(const GridDesc& g, const int* __restrict__ start, int n, float px, float py, float pz, int lane) {
+    PoseRow R{0, 0, 0, false};
+    const int cx = cell_coord_raw((double)px, g.ox, g.inv, g.nx), cy = cell_coord_raw((double)py, g.oy, g.inv, g.ny),
+              cz = cell_coord_raw((double)pz, g.oz, g.inv, g.nz);
+    if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny || cz < -1 || cz > g.nz) return R;
+    R.inside = true;
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
+    if (lane < 9) {
+        const int z = cz - 1 + lane / 3, y = cy - 1 + lane % 3;
+        if (z >= 0 && z < g.nz && y >= 0 && y < g.ny && x0 <= x1) {
+            const int row = (z * g.ny + y) * g.nx;
+            const int b0 = start[row + x0], b1 = start[row + x1 + 1];
+            R.beg = min(max(b0, 0), n);
+            R.len = max(min(b1, n) - R.beg, 0);
+        }
+    }
+    R.incl = R.len;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+        const int u = __shfl_up(R.incl, off);
+        if (lane >= off) R.incl += u;
+    }
+    return R;
+}
+
+// The resident atom at position pos of the cell order as the decision reads it (v / aj: its sp_xyzm / sp_aux rows): its hydrogens
+// are the resident rows from sp_h on, as many as the meta word counts — or, at M_HCNT_ESC, up to the next atom's first row
+__device__ __forceinline__ PoseAtom pose_resident_atom(int pos, const float4& v, const int4& aj, const int4* __restrict__ sp_qa,
+                                                       const int* __restrict__ sp_h, const int* __restrict__ h_off, const double* h_xyz) {
+    const uint32_t mj = __float_as_uint(v.w);
+    PoseAtom J;
+    J.x = xyz_of(v); J.m = mj; J.lid = aj.x; J.qa = sp_qa[pos]; J.hx = h_xyz;
+    J.h0 = sp_h[pos];
+    const unsigned hc = (mj >> M_HCNT_SHIFT) & 3u;
+    J.h1 = (mj & M_HAS_H) ? J.h0 + 1 + (int)hc : J.h0;
+    if ((mj & M_HAS_H) && hc == M_HCNT_ESC) J.h1 = h_off[aj.x + 1];
+    return J;
+}
+
 __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
     __shared__ u64 q_key[POSES_WAVES][POSES_QCAP], q_val[POSES_WAVES][POSES_QCAP];
     __shared__ uint32_t s_sum[POSES_SUMMARY];
@@ -276,22 +399,11 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const GridDesc g = A.g;
     int qn = 0;
-    auto flush = [&]() {
-        __builtin_amdgcn_wave_barrier();
-        u64 base = 0;
-        if (lane == 0) base = atomicAdd(A.count, (u64)qn);
-        base = __shfl(base, 0);
-        for (int k = lane; k < qn; k += 64)
-            if (base + k < A.cap) { A.key[base + k] = q_key[w][k]; A.val[base + k] = q_val[w][k]; }
-        __builtin_amdgcn_wave_barrier();
-        qn = 0;
-    };
     for (int pose = blockIdx.x; pose < A.P; pose += gridDim.x) {
         if (threadIdx.x < POSES_SUMMARY) s_sum[threadIdx.x] = 0u;
         __syncthreads();
-        uint32_t cnt[POSES_SUMMARY];
-#pragma unroll
-        for (int b = 0; b < POSES_SUMMARY; ++b) cnt[b] = 0u;
+        PoseCounts cnt;
+        cnt.clear();
         const double* const phx = A.phx + (size_t)pose * (size_t)A.SH * 3;
         for (int s = w; s < A.S; s += POSES_WAVES) {
             const int lid = A.sel_list[s];
@@ -302,40 +414,19 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
             bool bad = !(isfinite(px) && isfinite(py) && isfinite(pz));
             for (int k = 3 * ph0 + lane; k < 3 * ph1; k += 64) bad |= !isfinite(phx[k]);
             if (__any(bad)) {
-                if (lane == 0) atomicExch(A.err, ARP_E_ARG);
+                if (lane == 0) atomicExch(A.out.err, ARP_E_ARG);
                 continue;
             }
             const uint32_t mh = __float_as_uint(A.st_xyzm[lid].w) | M_SEL;
             if (mh & M_HYDROGEN) continue;                               // I:712
             const int4 ah = A.st_aux[lid];
-            // the 27 cells around the pose atom, clamped to the grid.  A pose may lie outside the receptor's box: an atom a whole
-            // cell (>= the cutoff) beyond a face has no partner.
-            const int cx = cell_coord_raw((double)px, g.ox, g.inv, g.nx), cy = cell_coord_raw((double)py, g.oy, g.inv, g.ny),
-                      cz = cell_coord_raw((double)pz, g.oz, g.inv, g.nz);
-            if (cx < -1 || cx > g.nx || cy < -1 || cy > g.ny || cz < -1 || cz > g.nz) continue;
-            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
-            // nine rows of up to three x-neighbours, each a contiguous range of the cell order: lane r < 9 holds row r
-            int rbeg = 0, rlen = 0;
-            if (lane < 9) {
-                const int z = cz - 1 + lane / 3, y = cy - 1 + lane % 3;
-                if (z >= 0 && z < g.nz && y >= 0 && y < g.ny && x0 <= x1) {
-                    const int row = (z * g.ny + y) * g.nx;
-                    const int b0 = A.start[row + x0], b1 = A.start[row + x1 + 1];
-                    rbeg = min(max(b0, 0), A.n);
-                    rlen = max(min(b1, A.n) - rbeg, 0);
-                }
-            }
-            int incl = rlen;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const int u = __shfl_up(incl, off);
-                if (lane >= off) incl += u;
-            }
-            const int total = __shfl(incl, 8);
+            const PoseRow row = pose_cell_rows(g, A.start, A.n, px, py, pz, lane);
+            if (!row.inside) continue;
+            const int total = __shfl(row.incl, 8);
             int rb_[9], re_[9];      // start of row r minus the candidates before it; candidates up to and including row r
 #pragma unroll
             for (int r = 0; r < 9; ++r) {
-                const int i_ = __shfl(incl, r), l_ = __shfl(rlen, r), b_ = __shfl(rbeg, r);
+                const int i_ = __shfl(row.incl, r), l_ = __shfl(row.len, r), b_ = __shfl(row.beg, r);
                 re_[r] = i_;
                 rb_[r] = b_ - (i_ - l_);
             }
@@ -372,15 +463,9 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
                 uint32_t sft = 0;
                 u64 key = 0, val = 0;
                 if (pass) {
-                    PoseAtom H, J;
+                    PoseAtom H;
                     H.x = {px, py, pz}; H.m = mh; H.lid = lid; H.qa = A.st_qa[lid]; H.hx = phx; H.h0 = ph0; H.h1 = ph1;
-                    J.x = xyz_of(v); J.m = mj; J.lid = aj.x; J.qa = A.sp_qa[pos]; J.hx = A.h_xyz;
-                    J.h0 = A.sp_h[pos];
-                    {
-                        const unsigned hc = (mj >> M_HCNT_SHIFT) & 3u;
-                        J.h1 = (mj & M_HAS_H) ? J.h0 + 1 + (int)hc : J.h0;
-                        if ((mj & M_HAS_H) && hc == M_HCNT_ESC) J.h1 = A.h_off[aj.x + 1];
-                    }
+                    const PoseAtom J = pose_resident_atom(pos, v, aj, A.sp_qa, A.sp_h, A.h_off, A.h_xyz);
                     const PoseAtom Bg = pose_pick(h_first, H, J), En = pose_pick(h_first, J, H);
                     const float d = num::norm(num::sub(Bg.x, En.x));                    // interactions.py:745
                     int ct = 0;
@@ -389,44 +474,12 @@ __global__ __launch_bounds__(POSES_THREADS) void k_poses_contacts(PoseArgs A) {
                     val = (u64)__float_as_uint(d) | ((u64)sft << 32) | ((u64)(unsigned)ct << 48);
                 }
                 const unsigned long long mp = __ballot(pass);
-                if (mp) {
-                    if (pass) {
-                        const int slot = qn + __popcll(mp & ((1ull << lane) - 1ull));
-                        q_key[w][slot] = key;
-                        q_val[w][slot] = val;
-                    }
-#pragma unroll
-                    for (int b = 0; b < POSES_SUMMARY - 1; ++b) cnt[b] += (uint32_t)__popcll(__ballot(pass && ((sft >> b) & 1u)));
-                    cnt[POSES_SUMMARY - 1] += (uint32_t)__popcll(mp);
-                    qn += __popcll(mp);
-                    if (qn > POSES_QCAP - 64) flush();
-                }
+                if (mp) pose_queue_push(A.out, q_key[w], q_val[w], qn, cnt, lane, mp, pass, key, val, sft);
             }
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int b = 0; b < POSES_SUMMARY; ++b)
-                if (cnt[b]) atomicAdd(&s_sum[b], cnt[b]);
-        }
-        __syncthreads();
-        if (threadIdx.x < POSES_SUMMARY) A.summary[(size_t)pose * POSES_SUMMARY + threadIdx.x] = s_sum[threadIdx.x];
-        __syncthreads();
+        cnt.store(s_sum, lane, A.out.summary + (size_t)pose * POSES_SUMMARY);
     }
-    // end of block: what is left in the per-wave queues leaves with ONE atomic
-    if (lane == 0) s_qn[w] = qn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int k = 0; k < POSES_WAVES; ++k) tot += s_qn[k];
-        s_base = tot > 0 ? atomicAdd(A.count, (u64)tot) : 0ull;
-    }
-    __syncthreads();
-    if (qn > 0) {
-        u64 base = s_base;
-        for (int k = 0; k < w; ++k) base += (u64)s_qn[k];
-        for (int k = lane; k < qn; k += 64)
-            if (base + k < A.cap) { A.key[base + k] = q_key[w][k]; A.val[base + k] = q_val[w][k]; }
-    }
+    pose_queue_drain(A.out, q_key[w], q_val[w], qn, lane, w, s_qn, &s_base);
 }
 
 // Block t: pose_off[t][p] = what slot first_slot + t of the summary rows (POSES_SUMMARY words each) counts in the poses before p,
@@ -445,15 +498,16 @@ __global__ __launch_bounds__(1024) void k_poses_offsets(int P, int first_slot, c
     if (threadIdx.x == 0) out[P] = carry;
 }
 
-// the sorted (key, payload) pairs as the result's five columns
-__global__ __launch_bounds__(256) void k_poses_columns(long long k, int idbits, const u64* __restrict__ key, const u64* __restrict__ val,
-                                                       int* __restrict__ ci, int* __restrict__ cj, float* __restrict__ cd,
-                                                       uint16_t* __restrict__ cs, uint8_t* __restrict__ cct) {
-    const u64 mask = (1ull << idbits) - 1ull;
+// The sorted (key, payload) pairs as the result's five columns: the first id column is the key's hi_bits above its lowest
+// lo_bits, the second those lowest bits (a poses result: idbits twice; a library result, arp_library.h: ibits and abits)
+__global__ __launch_bounds__(256) void k_pose_columns(long long k, int hi_bits, int lo_bits, const u64* __restrict__ key, const u64* __restrict__ val,
+                                                      int* __restrict__ c0, int* __restrict__ c1, float* __restrict__ cd,
+                                                      uint16_t* __restrict__ cs, uint8_t* __restrict__ cct) {
+    const u64 hi_mask = (1ull << hi_bits) - 1ull, lo_mask = (1ull << lo_bits) - 1ull;
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < k; p += (long long)gridDim.x * blockDim.x) {
         const u64 kk = key[p], v = val[p];
-        ci[p] = (int)((kk >> idbits) & mask);
-        cj[p] = (int)(kk & mask);
+        c0[p] = (int)((kk >> lo_bits) & hi_mask);
+        c1[p] = (int)(kk & lo_mask);
         cd[p] = __uint_as_float((uint32_t)v);
         cs[p] = (uint16_t)(v >> 32);
         cct[p] = (uint8_t)(v >> 48);

@@ -34,11 +34,10 @@ import numpy as np
 
 from .core import config
 from .core.packed import PackedComplex
+from .poses import N_BITS, SUMMARY, join_poses, n_poses, pose_of, summarise      # (a library result is read as a poses result is)
 
 MAX_LIGANDS = 1 << 16
 MAX_ATOMS = 256
-SUMMARY = 16
-N_BITS = 15
 MAX_WEIGHT = 1 << 24
 INT64_MIN = -(1 << 63)
 COLUMNS = ('i', 'a', 'dist', 'sift', 'ctype')
@@ -189,15 +188,6 @@ def flatten_poses(lib, poses):
     return np.concatenate([[0], np.cumsum(P)]).astype(np.int64), np.concatenate(xs).astype(np.float32), np.concatenate(hs).astype(np.float64)
 
 
-def n_poses(table):
-    return len(table['pose_off']) - 1
-
-
-def pose_of(table):
-    """The global pose of every record (int64 [k])."""
-    return np.repeat(np.arange(n_poses(table)), np.diff(np.asarray(table['pose_off']).astype(np.int64)))
-
-
 def ligand_of(table):
     """The ligand of every global pose (int64 [T])."""
     lo = np.asarray(table['ligand_pose_off'], np.int64)
@@ -211,12 +201,6 @@ def empty(n_lig, ligand_pose_off=None):
     t['summary'] = np.zeros((int(lo[-1]), SUMMARY), np.uint32)
     t['ligand_pose_off'] = lo
     return t
-
-
-def summarise(sift):
-    """The summary row of one pose's records: per SIFt bit, then the total (what the device writes)."""
-    s = np.asarray(sift, np.uint16)
-    return np.array([int(((s >> k) & 1).sum()) for k in range(N_BITS)] + [len(s)], np.uint32)
 
 
 def from_rows(rows):
@@ -253,13 +237,7 @@ def concat(chunks):
     if any(len(c['ligand_pose_off']) != L for c in chunks):
         raise ValueError('concat: the launches are over libraries of different sizes')
     out = {k: np.concatenate([np.asarray(c[k]) for c in chunks]).astype(DTYPES[k]) for k in COLUMNS}
-    base, offs = 0, [np.zeros(1, np.uint64)]
-    for c in chunks:
-        o = np.asarray(c['pose_off']).astype(np.uint64)
-        offs.append(o[1:] + np.uint64(base))
-        base += int(o[-1])
-    out['pose_off'] = np.concatenate(offs)
-    out['summary'] = np.concatenate([np.asarray(c['summary'], np.uint32).reshape(-1, SUMMARY) for c in chunks])
+    out['pose_off'], out['summary'] = join_poses(chunks)
     P = np.sum([np.diff(np.asarray(c['ligand_pose_off'], np.int64)) for c in chunks], axis=0)
     out['ligand_pose_off'] = np.concatenate([[0], np.cumsum(P)]).astype(np.int64)
     # consecutive ranges of a ligand-major pose sequence: ligand ids never decrease along the joined poses

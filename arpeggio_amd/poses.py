@@ -96,6 +96,22 @@ def summarise(sift):
     return np.array([int(((s >> k) & 1).sum()) for k in range(N_BITS)] + [len(s)], np.uint32)
 
 
+def join_pose_off(offs):
+    """The ``pose_off`` arrays of consecutive chunks as one (uint64): a chunk's records follow those of the chunks before it."""
+    base, out = 0, [np.zeros(1, np.uint64)]
+    for o in offs:
+        o = np.asarray(o).astype(np.uint64)
+        out.append(o[1:] + np.uint64(base))
+        base += int(o[-1])
+    return np.concatenate(out)
+
+
+def join_poses(chunks):
+    """``(pose_off, summary)`` of consecutive chunks of poses as one: what every ``concat`` over pose results shares."""
+    return (join_pose_off(c['pose_off'] for c in chunks),
+            np.concatenate([np.asarray(c['summary'], np.uint32).reshape(-1, SUMMARY) for c in chunks]))
+
+
 def split(table):
     """One result per pose (a list of P dicts of the five columns)."""
     off = np.asarray(table['pose_off']).astype(np.int64)
@@ -108,13 +124,7 @@ def concat(chunks):
     if not chunks:
         return empty()
     out = {k: np.concatenate([np.asarray(c[k]) for c in chunks]) for k in COLUMNS}
-    base, offs = 0, [np.zeros(1, np.uint64)]
-    for c in chunks:
-        o = np.asarray(c['pose_off']).astype(np.uint64)
-        offs.append(o[1:] + np.uint64(base))
-        base += int(o[-1])
-    out['pose_off'] = np.concatenate(offs)
-    out['summary'] = np.concatenate([np.asarray(c['summary'], np.uint32).reshape(-1, SUMMARY) for c in chunks])
+    out['pose_off'], out['summary'] = join_poses(chunks)
     mv = [np.asarray(c['movable']) for c in chunks if 'movable' in c]
     if mv:
         if any(not np.array_equal(mv[0], m) for m in mv[1:]):
@@ -328,12 +338,7 @@ def concat_planes(chunks):
     out = {}
     for name in PLANE_TABLES:
         out[name] = {c: np.concatenate([np.asarray(ch[name][c]) for ch in chunks]).astype(dt) for c, dt in plane_columns(name)}
-        base, offs = 0, [np.zeros(1, np.uint64)]
-        for ch in chunks:
-            o = np.asarray(ch[name]['pose_off']).astype(np.uint64)
-            offs.append(o[1:] + np.uint64(base))
-            base += int(o[-1])
-        out[name]['pose_off'] = np.concatenate(offs)
+        out[name]['pose_off'] = join_pose_off(ch[name]['pose_off'] for ch in chunks)
     out['summary'] = np.concatenate([np.asarray(ch['summary'], np.uint32).reshape(-1, SUMMARY) for ch in chunks])
     mv = [np.asarray(ch['movable']) for ch in chunks if 'movable' in ch]
     if mv:

@@ -226,6 +226,17 @@ def _ctx(pc):
     return ctx
 
 
+def index_bits(count):
+    """The bits of the ids 0 ... count - 1 in a sort key (index_bits of csrc/arp_api.hip)."""
+    return max(int(count - 1).bit_length(), 1)
+
+
+def most_records_of_a_wave(t):
+    """The most records one wave of k_library_contacts queues within one pose: wave w takes the ligand's atoms a = w (mod 4).  More
+    than LIB_QCAP - 64 = 192 of them: the wave flushed its queue inside the pose."""
+    return int(np.bincount(ll.pose_of(t) * 4 + t['a'] % 4).max()) if len(t['a']) else 0
+
+
 def launch(ctx, lib, poses, params=PARAMS[0]):
     off, x, h = ll.flatten_poses(lib, poses)
     return ctx.library_contacts(off, x, h, *params)
@@ -442,6 +453,11 @@ def test_main_case_equals_the_pose_route_per_ligand(params):
     ctx = _ctx(rec)
     ctx.set_ligand_library(lib)
     got = launch(ctx, lib, poses, params)
+    # the two id columns have widths of their own (k_pose_columns with hi_bits != lo_bits): a receptor id that the ligand atoms'
+    # bits could not hold comes back whole
+    assert index_bits(rec.n_atoms) != index_bits(256) and int(got['i'].max()).bit_length() > index_bits(256)
+    # ligands of one atom: three waves of their blocks have no atom, and their empty queues go through the drain at the end
+    assert ll.sizes(lib)[0][0] == 1 and int(got['pose_off'][70]) > 0
     assert differences(got, want) == []
     check_consistent(got, lib)
     info = ctx.library_info()
@@ -522,6 +538,7 @@ def test_seams_far_away_half_outside_one_pose_and_more_poses_than_blocks():
     assert (per[2:8] > 0).sum() >= 4 and per[8] == per.max() > 300
     for p in (8, 0, 4):                                                                  # T = 1
         one = launch(ctx, lib, [(x[p:p + 1], None), None])
+        assert (len(one['i']) == 0) == (p == 0)                                          # pose 0 alone: a result of no record at all
         assert differences(one, ll.from_rows([rows[0][p:p + 1], []])) == [] and ctx.library_info()['poses'] == 1
     # 1030 poses of the water: more than one round of the offsets scan, and more poses than blocks (a second grid stride)
     centre = rec.xyz.astype(np.float64).mean(axis=0)
@@ -551,7 +568,8 @@ def test_capacity_null_pointers_and_the_summary_alone():
     params = PARAMS[2]
     t = launch(ctx, lib, poses, params)
     k = len(t['i'])
-    assert k > 24 * 256 * 32                                                          # the first buffer was too small
+    assert k > max(1 << 16, 24 * 256 * 32)                                            # the first buffer was too small
+    assert most_records_of_a_wave(t) > 192                                            # a wave flushed its queue inside a pose
     ref = _capi.Context(0)
     assert differences(t, ll.from_rows(pose_route_rows(ref, rec, (big,), poses, params))) == []
     ref.close()

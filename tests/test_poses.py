@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle
-from arpeggio_amd import _capi, poses, synth
+from arpeggio_amd import _capi, ligand_library, poses, synth
 from arpeggio_amd.core import config, utils
 from arpeggio_amd.core.interactions import EnsembleComplex, InteractionComplex
 from helpers import concat_packs, tiny_complex
@@ -230,6 +230,18 @@ def check_consistent(t, info=None):
         assert info['poses'] == P and info['records'] == len(t['i']) and info['atoms'] == len(t['movable'])
 
 
+def index_bits(count):
+    """The bits of the ids 0 ... count - 1 in a sort key (index_bits of csrc/arp_api.hip)."""
+    return max(int(count - 1).bit_length(), 1)
+
+
+def most_records_of_a_wave(t):
+    """The most records one wave of k_poses_contacts queues within one pose: wave w takes the movable atoms at positions
+    s = w (mod 4) of the ascending movable set.  More than POSES_QCAP - 64 = 192 of them: the wave flushed its queue inside the pose."""
+    wave = np.searchsorted(t['movable'], poses.partners(t)[0]) % 4
+    return int(np.bincount(poses.pose_of(t) * 4 + wave).max()) if len(wave) else 0
+
+
 def device_table(ctx, pc, idx, x, h, params):
     ctx.set_selection(_mask(pc, idx))
     return ctx.poses_contacts(x, h, *params)
@@ -317,6 +329,24 @@ def test_split_concat_and_summary_on_the_hand_made_table():
         poses.concat([t, as_table(rows, idx[:-1])])
 
 
+def test_the_library_module_shares_these_names_and_the_join_of_concat():
+    """ligand_library re-exports the objects of poses, and the helper both ``concat`` functions share reproduces them on the
+    hand-made tables of the two modules' tests."""
+    for name in ('SUMMARY', 'N_BITS', 'n_poses', 'pose_of', 'summarise'):
+        assert getattr(ligand_library, name) is getattr(poses, name), name
+    pc, idx, rows, t = hand_table()
+    off, summary = poses.join_poses([as_table(rows[:1], idx), as_table(rows[1:], idx)])
+    assert off.dtype == np.uint64 and np.array_equal(off, t['pose_off']) and summary.dtype == np.uint32 and np.array_equal(summary, t['summary'])
+    assert np.array_equal(poses.join_pose_off([[0, 2], [0], [0, 0, 3]]), [0, 2, 2, 5])
+    from test_ligand_library import hand_table as library_hand_table
+    r, lt = library_hand_table()
+    chunks = [ligand_library.from_rows([r[0], [], r[2][:1]]), ligand_library.from_rows([[], [], r[2][1:]])]
+    off, summary = poses.join_poses(chunks)
+    assert np.array_equal(off, lt['pose_off']) and np.array_equal(summary, lt['summary'])
+    joined = ligand_library.concat(chunks)
+    assert np.array_equal(joined['pose_off'], off) and np.array_equal(joined['summary'], summary) and joined['pose_off'].dtype == np.uint64
+
+
 def test_fingerprints_records_and_csv_of_the_hand_made_table(tmp_path):
     pc, idx, rows, t = hand_table()
     lig_atoms, rec_atoms = poses.partners(t)
@@ -364,6 +394,8 @@ def test_main_parity_with_the_ensemble_route(params):
     want = as_table(ensemble_rows('main', params), idx)
     ctx = _ctx(pc)
     got = device_table(ctx, pc, idx, x, h, params)
+    # both id columns are packed atom ids: one width for both (k_pose_columns with hi_bits == lo_bits), and neither outgrows it
+    assert max(int(got['i'].max()), int(got['j'].max())).bit_length() <= index_bits(pc.n_atoms)
     assert differences(got, want) == []
     check_consistent(got, ctx.poses_info())
     assert ctx.poses_info()['hydrogens'] == 0 and len(got['i']) > 70 * 100
@@ -425,6 +457,8 @@ def test_other_movable_sets_equal_the_ensemble_route(name):
     if name == 'water':       # one heavy atom: every record is the water's oxygen with a receptor atom
         heavy = [int(a) for a in idx if not pc.flags[a] & config.F_HYDROGEN]
         assert len(heavy) == 1 and (poses.partners(got)[0] == heavy[0]).all()
+        # fewer than 4 movable atoms: a wave of every block has no atom, and its empty queue goes through the drain at the end
+        assert len(idx) == 3 and len(got['i']) > 0
         # (a selected water beside an unselected atom that is no water is NON_SELECTION_WATER: the fifth assignment of I:643-691 overrides the fourth)
         assert set(got['ctype'].tolist()) == {CT['NON_SELECTION_WATER'], CT['WATER_WATER']} and len(got['i']) > 100
     if name == 'two':         # HEM and a water selected at once: no row joins the two
@@ -452,6 +486,7 @@ def test_box_seams_far_away_half_outside_and_one_pose():
     assert (per[2:8] > 0).sum() >= 4 and per[8] == per.max() > 300                       # most faces have partners, home has most
     for p in (8, 0, 4):                                                                  # P = 1
         one = ctx.poses_contacts(x[p:p + 1], None, *params)
+        assert (len(one['i']) == 0) == (p == 0)                                          # pose 0 alone: a result of no record at all
         assert differences(one, as_table(rows[p:p + 1], idx)) == [] and ctx.poses_info()['poses'] == 1
     ctx.close()
 
@@ -644,6 +679,22 @@ def test_capacity_null_pointers_and_the_summary_alone():
     assert rc == _capi.ARP_OK and np.array_equal(off, t['pose_off'])                  # no record asked for: cap is not looked at
     s = ctx.poses_summary(x[:6], h[:6], 5.0, 0.1, False)
     assert s.dtype == np.uint32 and np.array_equal(s, t['summary'])
+    # A first buffer that is too small: 24 poses of a movable set of 256 heavy atoms in the middle of the protein at the widest
+    # cutoff, 36.9 records per posed atom (tests/test_ligand_library.py counts them), more than the 32 the first buffer holds.
+    # The launch is repeated with room for all; four poses at a time fit the first buffer, and joined they are the same records.
+    lig = synth.ligand('chain', 6, size=256)
+    both = ligand_library.complex_of(pc, lig)
+    sel = np.arange(pc.n_atoms, both.n_atoms)
+    bx, bh = synth.library_poses_of(pc, lig, pc.xyz.astype(np.float64).mean(axis=0), 24, seed=4, shift=1.0)
+    ctx.set_complex(both)
+    big = device_table(ctx, both, sel, bx, bh, (6.0, 0.3, False))
+    assert len(big['i']) > max(1 << 16, 24 * 256 * 32)                                  # the first buffer was too small
+    assert most_records_of_a_wave(big) > 192                                            # a wave flushed its queue inside a pose
+    assert int(big['j'].max()).bit_length() == index_bits(both.n_atoms)                # the lower id column fills its width
+    parts = [ctx.poses_contacts(bx[a:a + 4], bh[a:a + 4], 6.0, 0.3, False) for a in range(0, 24, 4)]
+    assert all(len(q['i']) <= 1 << 16 for q in parts)                                   # ... and theirs was not
+    assert differences(poses.concat(parts), big) == []
+    check_consistent(big, None)
     ctx.close()
 
 
