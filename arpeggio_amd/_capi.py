@@ -56,6 +56,8 @@ SYMBOLS = (
     'arp_poses_clusters_launch', 'arp_poses_clusters_fetch', 'arp_poses_clusters_info',
     'arp_set_ligand_library', 'arp_library_contacts_launch', 'arp_library_contacts_fetch', 'arp_library_info',
     'arp_library_best_launch', 'arp_library_best_fetch',
+    'arp_library_fingerprints_launch', 'arp_library_fingerprints_fetch', 'arp_library_fingerprints_info',
+    'arp_library_fingerprints_best_launch', 'arp_library_fingerprints_best_fetch',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -72,6 +74,7 @@ SHORTLIST_LIST, SHORTLIST_SUMMARY, SHORTLIST_TANIMOTO, SHORTLIST_TABLES, SHORTLI
 INT64_MIN = -(1 << 63)
 # a ligand library on the resident receptor (ARP_LIBRARY_*)
 LIBRARY_MAX_LIGANDS, LIBRARY_MAX_ATOMS = 1 << 16, 256
+LIBFP_MAX_FEATURES = 1 << 22     # ARP_LIBFP_MAX_FEATURES: reference features of a library fingerprint launch
 # ... their clusters (ARP_POSECL_*; the rounds enqueued between two waits of arp_poses_clusters_launch)
 POSECL_MAX_CLUSTERS, POSECL_ROUNDS_PER_WAIT = 4096, 64
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
@@ -272,6 +275,11 @@ def load():
     L.arp_library_info.argtypes = [vp, vp]
     L.arp_library_best_launch.argtypes = [vp, vp]
     L.arp_library_best_fetch.argtypes = [vp, i64, vp, vp, vp, C.POINTER(i64)]
+    L.arp_library_fingerprints_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp, vp, vp, vp]
+    L.arp_library_fingerprints_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64)]
+    L.arp_library_fingerprints_info.argtypes = [vp, vp]
+    L.arp_library_fingerprints_best_launch.argtypes = [vp]
+    L.arp_library_fingerprints_best_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1302,6 +1310,66 @@ class Context:
         self._check(self._L.arp_library_info(self._h, _p(info)), 'arp_library_info')
         return dict(ligands=int(info[0]), poses=int(info[1]), records=int(info[2]), atoms=int(info[3]), hydrogens=int(info[4]),
                     blocks=int(info[5]), max_atoms=int(info[6]), best=bool(info[7]))
+
+    def library_fingerprints(self, refs, planes, ctype_mask=CTYPE_ALL, by_residue=True, bits=False):
+        """The resident library result (``library_contacts`` / ``library_summary``) reduced on the device to interaction
+        fingerprints and scored against reference interactions (arp_library_fingerprints_*; ``arpeggio_amd.library_fingerprints``).
+        ``refs`` are the references as ``library_fingerprints.references`` gives them (``ref_off`` int64 [Q + 1], ``ref_node``
+        int32 [F], ``ref_planes`` uint32 [F]; at most ``POSEFP_MAX_REFS``), or None for none: feature lists that need not come
+        from poses of the launch.  A feature is (node, plane): the receptor residue (``by_residue=False``: receptor atom) of a
+        record whose ``ctype`` bit is in ``ctype_mask``, and one of the SIFt bits of ``planes`` the record has.  Returns the
+        dict ``poses_fingerprints`` returns, over Q + T rows — the references first, then the global poses: ``ids``, ``count``
+        [Q + T], ``cross`` [Q + T, Q], ``occupancy`` [U, NP] over the poses, ``planes``, ``n_refs``, ``level``, with
+        ``bits=True`` the bit matrix.  No record is copied.  Every call launches."""
+        from . import library_fingerprints as _lfp
+        r = _lfp.references([]) if refs is None else refs
+        off = np.ascontiguousarray(r['ref_off'], np.int64).reshape(-1)
+        node = np.ascontiguousarray(r['ref_node'], np.int32).reshape(-1)
+        mask = np.ascontiguousarray(r['ref_planes'], np.uint32).reshape(-1)
+        Q = len(off) - 1
+        # (the library reads ref_off[Q] entries of both feature arrays: their lengths are checked here)
+        if Q < 0 or len(node) != len(mask) or (Q > 0 and 0 <= int(off[-1]) != len(node)):
+            raise ValueError('library_fingerprints: ref_node and ref_planes must hold ref_off[-1] entries each')
+        flags = POSEFP_BY_RESIDUE if by_residue else 0
+        info = np.zeros(8, np.int64)
+        give = Q > 0
+        self._check(self._L.arp_library_fingerprints_launch(self._h, int(planes), int(ctype_mask), flags, Q, _p(off) if give else None,
+                                                            _p(node) if give else None, _p(mask) if give else None, _p(info)),
+                    'arp_library_fingerprints_launch')
+        P, Q, U = (int(v) for v in info[:3])
+        NP = bin(int(planes)).count('1')
+        out = dict(ids=np.empty(U, np.int32), count=np.empty(P, np.uint32), cross=np.empty((P, Q), np.uint32), occupancy=np.empty((U, NP), np.uint32))
+        if bits:
+            out['bits'] = np.empty((P, NP, (U + 63) // 64), np.uint64)
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_fingerprints_fetch(self._h, U, _p(out['ids']), _p(out['count']), _p(out['cross']), _p(out['occupancy']),
+                                                           _p(out.get('bits')), C.byref(n)), 'arp_library_fingerprints_fetch')
+        out.update(planes=int(planes), n_refs=Q, level='residue' if by_residue else 'atom')
+        return out
+
+    def library_fingerprints_best(self):
+        """Per ligand and reference the best pose of the resident library fingerprint by Tanimoto similarity in 32 fractional
+        bits (arp_library_fingerprints_best_*; ``library_fingerprints.best`` is the host mirror): a dict of ``n_poses`` int64
+        [L], ``best_pose`` int32 [L, Q] (global pose id, ties to the lower one), ``tanimoto_q32`` int64 [L, Q], ``shared`` uint32
+        [L, Q] and ``count`` uint32 [L, Q] (the best pose's own feature count).  A ligand without poses: -1, -1, 0, 0."""
+        self._check(self._L.arp_library_fingerprints_best_launch(self._h), 'arp_library_fingerprints_best_launch')
+        nl, nq = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.arp_library_fingerprints_best_fetch(self._h, 0, None, None, None, None, None, C.byref(nl), C.byref(nq)),
+                    'arp_library_fingerprints_best_fetch')
+        L, Q = int(nl.value), int(nq.value)
+        out = dict(n_poses=np.empty(L, np.int64), best_pose=np.empty((L, Q), np.int32), tanimoto_q32=np.empty((L, Q), np.int64),
+                   shared=np.empty((L, Q), np.uint32), count=np.empty((L, Q), np.uint32))
+        self._check(self._L.arp_library_fingerprints_best_fetch(self._h, L, _p(out['n_poses']), _p(out['best_pose']), _p(out['tanimoto_q32']),
+                                                                _p(out['shared']), _p(out['count']), C.byref(nl), C.byref(nq)),
+                    'arp_library_fingerprints_best_fetch')
+        return out
+
+    def library_fingerprints_info(self):
+        """arp_library_fingerprints_info: rows (references and poses), references, columns, planes, words per row and word slices
+        of the resident library fingerprint (zeros while there is none), the launches so far, and the flags."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_fingerprints_info(self._h, _p(info)), 'arp_library_fingerprints_info')
+        return dict(zip(('rows', 'n_refs', 'nodes', 'planes', 'words', 'slices', 'launches', 'flags'), (int(v) for v in info)))
 
     def set_blob(self, blob, counts=None):
         """Upload a structure packed by ``pack_blob`` (one host-to-device copy); ``blob`` must stay alive during the call."""

@@ -476,16 +476,8 @@ class InteractionComplex:
         if off[-1] < 1:
             raise ValueError('run_ligand_library: no pose given')
         ctx.set_ligand_library(lib)
-        S, SH = _ll.sizes(lib)
-        x_at = np.concatenate([[0], np.cumsum(np.diff(off) * S * 3)])
-        h_at = np.concatenate([[0], np.cumsum(np.diff(off) * SH * 3)])
-        parts = []
-        for off_c, a, b in _ll.chunk_plan(off, chunk if chunk else _capi.POSES_MAX_POSES):
-            # the coordinates of the global poses a ... b - 1: of every ligand its poses inside the range
-            first = np.clip(off, a, b) - off                       # (how many of the ligand's poses come before the range)
-            xs = [x[x_at[l] + first[l] * S[l] * 3:x_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * S[l] * 3] for l in range(len(S))]
-            hs = [h[h_at[l] + first[l] * SH[l] * 3:h_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * SH[l] * 3] for l in range(len(S))]
-            parts.append(ctx.library_contacts(off_c, np.concatenate(xs), np.concatenate(hs), interacting_cutoff, vdw_comp, include_sequence_adjacent))
+        parts = [ctx.library_contacts(off_c, xc, hc, interacting_cutoff, vdw_comp, include_sequence_adjacent)
+                 for off_c, _, _, xc, hc in _ll.chunk_poses(lib, off, x, h, chunk if chunk else _capi.POSES_MAX_POSES)]
         self.ligand_library = parts[0] if len(parts) == 1 else _ll.concat(parts)
         self.ligand_library_ligands = ligands
         if weights is not None:
@@ -498,6 +490,61 @@ class InteractionComplex:
         if getattr(self, 'ligand_library', None) is None:
             raise AttributeError('no ligand library result yet: call run_ligand_library() first')
         return _ll.write_library(wd, self.id, self.ligand_library, self.pc, self.ligand_library_ligands, self.component_types)
+
+    def run_library_fingerprints(self, library, pose_off, xyz, h_xyz, refs, contacts=None, interacting_entities=None, level='residue',
+                                 chunk=None, interacting_cutoff=5.0, vdw_comp=0.1):
+        """Extension beside the mirror: which ligands of a library reproduce the interactions of known binders, scored ON THE
+        DEVICE — no record is copied (``arpeggio_amd.library_fingerprints``).  ``library`` is a list of ligand packs or what
+        ``ligand_library.pack`` made of one; ``pose_off`` int64 [L + 1], ``xyz`` and ``h_xyz`` are the flat arrays of
+        ``ligand_library.flatten_poses``.  ``refs`` are the references as ``library_fingerprints.references`` gives or takes
+        them: feature lists at ``level`` ('residue' or 'atom') that need not come from poses of this library
+        (``library_fingerprints.reference_from_records`` makes one from the records of a known complex).  ``contacts`` names the
+        planes (``pose_fingerprints.planes``: ``None`` = every contact but bare proximity), ``interacting_entities`` the kinds
+        of entities whose records take part.  Every chunk of ``chunk`` global poses (default: all at once; a ligand's poses may
+        be cut between two) is one ``Context.library_summary``, ``library_fingerprints`` and ``library_fingerprints_best``;
+        the chunks are merged (``pose_fingerprints.merge``, ``library_fingerprints.merge_best``).  Returns the result
+        ``pose_fingerprints`` describes with the reference rows moved to ``reference_count`` / ``reference_cross``, ``count`` [T],
+        ``cross`` [T, Q], and with ``best`` (the table ``library_fingerprints`` describes) and ``ligand_pose_off``; also kept in
+        ``self.library_fingerprints``.  The results of ``run_arpeggio`` and ``run_poses`` stay as they are."""
+        from .. import _capi, contact_filter, ligand_library as _ll, library_fingerprints as _lfp
+        if level not in _lfp.LEVELS:
+            raise ValueError(f"run_library_fingerprints: level must be 'residue' or 'atom', not {level!r}")
+        mask = _lfp.planes(contacts)
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        lib = library if isinstance(library, dict) else _ll.pack(list(library))
+        n_nodes = self.pc.n_residues if level == 'residue' else self.pc.n_atoms
+        r = _lfp.validate(refs, n_nodes) if isinstance(refs, dict) else _lfp.references(refs, n_nodes)
+        if _lfp.n_references(r) < 1:
+            raise ValueError('run_library_fingerprints: 1 ... MAX_REFS references')
+        off = np.ascontiguousarray(pose_off, np.int64)
+        if off.shape != (_ll.n_ligands(lib) + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] < 1:
+            raise ValueError('run_library_fingerprints: pose_off must be [L + 1], start at 0, not decrease and hold a pose')
+        if self._ctx is None:
+            self.initialize()
+        ctx = self._ctx
+        ctx.set_ligand_library(lib)
+        h = np.zeros(0) if h_xyz is None else h_xyz
+        parts, bests = [], []
+        for off_c, a, _, xc, hc in _ll.chunk_poses(lib, off, xyz, h, chunk if chunk else _capi.POSES_MAX_POSES):
+            ctx.library_summary(off_c, xc, hc, interacting_cutoff, vdw_comp, False)
+            parts.append(ctx.library_fingerprints(r, mask, ctype_mask, by_residue=level == 'residue'))
+            bests.append((ctx.library_fingerprints_best(), a))
+        out = _lfp.strip_references(parts[0] if len(parts) == 1 else _lfp.merge(parts))
+        out['best'] = bests[0][0] if len(bests) == 1 else _lfp.merge_best(bests)
+        out['ligand_pose_off'] = off
+        self.library_fingerprints = out
+        self.library_fingerprints_ligands = lib.get('ligands')
+        return out
+
+    def write_library_fingerprints(self, wd):
+        """'<id>.libraryfp': the best pose per ligand and reference of the last ``run_library_fingerprints`` as CSV
+        (``library_fingerprints.write_csv``)."""
+        from .. import library_fingerprints as _lfp
+        fp = getattr(self, 'library_fingerprints', None)
+        if fp is None:
+            raise AttributeError('no library fingerprints yet: call run_library_fingerprints() first')
+        return _lfp.write_library_fingerprints(wd, self.id, fp['best'], fp['reference_count'], fp['ligand_pose_off'],
+                                               getattr(self, 'library_fingerprints_ligands', None))
 
     def write_pose_planes(self, wd):
         """'<id>.poseplanes': the ring / amide tables of the last ``run_poses(..., planes=True)`` as CSV (``poses.write_planes_csv``)."""

@@ -45,6 +45,7 @@
 #include "arp_poses_shortlist.h"
 #include "arp_poses_clusters.h"
 #include "arp_library.h"
+#include "arp_library_fingerprints.h"
 #include "arp_blob.h"
 
 namespace {
@@ -361,6 +362,21 @@ struct PoseFpResult {
     void release() {
         presence.release(); bits.release(); base.release(); count.release(); cross.release(); occ.release(); inter.release();
         total.release(); ids.release(); valid = false;
+    }
+};
+
+// what the fingerprints of the resident library result (arp_library_fingerprints_launch, arp_library_fingerprints.h) keep beside
+// their PoseFpResult (arp_ctx::libfp): the uploaded references, and the best pose per (ligand, reference) made from count and
+// cross (arp_library_fingerprints_best_launch), which goes with them (void_pose_results)
+struct LibraryFpTables {
+    DevBuf<long long> ref_off, best_n, best_q32;
+    DevBuf<int> ref_node, best_pose;
+    DevBuf<uint32_t> ref_planes, best_shared, best_count;
+    int64_t L = 0, features = 0;
+    bool best_valid = false;
+    void release() {
+        ref_off.release(); best_n.release(); best_q32.release(); ref_node.release(); best_pose.release(); ref_planes.release();
+        best_shared.release(); best_count.release(); best_valid = false;
     }
 };
 
@@ -685,6 +701,8 @@ struct arp_ctx {
     ClustersResult clusters;              // arp_poses_clusters_launch
     LigandLibrary library;                // arp_set_ligand_library
     LibraryResult libres;                 // arp_library_contacts_launch, arp_library_best_launch
+    PoseFpResult libfp;                   // arp_library_fingerprints_launch: P = Q + T rows, the references first
+    LibraryFpTables libfpx;               // ... its references, arp_library_fingerprints_best_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -889,7 +907,8 @@ void void_results(arp_ctx* c, unsigned lost) {
 // replaced or is about to be — the structure, the selection, or one of the rows below itself.  A row goes when it
 // is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The ligand-library result
 //  is a row of the same table: it reads the structure and the library (POSE_LIBRARY, lost by
-// arp_set_ligand_library) and NO selection.  The fingerprint and the
+// arp_set_ligand_library) and NO selection; the library fingerprint reads that result's records, and its best-pose
+// table reads the fingerprint.  The fingerprint and the
 // shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight; the
 // clusters read the fingerprint result only while their launch runs, so they stand behind what THAT was made from, not behind it.
 // A launch names its own result here before it writes it, and sets it valid again at its end.
@@ -898,7 +917,8 @@ enum : unsigned {
     POSE_PLANES = 1u << 5, POSE_FINGERPRINT = 1u << 6, POSE_SHORTLIST = 1u << 7,
     POSE_CLUSTERS = 1u << 8,
     POSE_LIBRARY = 1u << 9,           // the ligand library itself (arp_set_ligand_library)
-    POSE_LIBRARY_CONTACTS = 1u << 10, POSE_LIBRARY_BEST = 1u << 11
+    POSE_LIBRARY_CONTACTS = 1u << 10, POSE_LIBRARY_BEST = 1u << 11,
+    POSE_LIBRARY_FINGERPRINT = 1u << 12, POSE_LIBRARY_FP_BEST = 1u << 13
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -912,7 +932,10 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->clusters.valid, POSE_CLUSTERS, POSE_CONTACTS | (c->clusters.classes ? POSE_PLANES : 0u)},
         // the library result reads the structure and the library, no selection; the best-pose table reads its summary
         {&c->libres.valid, POSE_LIBRARY_CONTACTS, POSE_STRUCTURE | POSE_LIBRARY},
-        {&c->libres.best_valid, POSE_LIBRARY_BEST, POSE_LIBRARY_CONTACTS}};
+        {&c->libres.best_valid, POSE_LIBRARY_BEST, POSE_LIBRARY_CONTACTS},
+        // the library fingerprint reads the library result's records; its best-pose table reads its count and cross
+        {&c->libfp.valid, POSE_LIBRARY_FINGERPRINT, POSE_LIBRARY_CONTACTS},
+        {&c->libfpx.best_valid, POSE_LIBRARY_FP_BEST, POSE_LIBRARY_FINGERPRINT}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -2523,6 +2546,8 @@ void arp_destroy(arp_ctx* c) {
     c->clusters.release();
     c->library.release();
     c->libres.release();
+    c->libfp.release();
+    c->libfpx.release();
     c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -6069,6 +6094,30 @@ static void posefp_info(const PoseFpResult& F, int64_t info[8]) {
     for (int q = 0; q < 8; ++q) info[q] = (F.valid || q == 6) ? v[q] : 0;
 }
 
+// What both fingerprint launches (poses, library) enqueue over a finished bit matrix of A.P rows whose first A.Q are the
+// references (A.bits, A.W; F.count and F.cross reserved): k_pfp_cross and k_pfp_occupancy.  *slices: the word slices of the first.
+static int enqueue_cross_and_occupancy(arp_ctx* c, PoseFpResult& F, PoseFpArgs& A, long long* slices) {
+    const long long P = A.P, Q = A.Q, W = A.W;
+    // ---- cross = B R^T and count: the pose tiles times as many word slices as fill the device
+    const long long tiles = (P + POSEFP_TILE - 1) / POSEFP_TILE;
+    long long per = 0;
+    popcount_slices(c, W, tiles, &per, slices);
+    A.per = per; A.slices = (int)*slices;
+    if (*slices > 1) {
+        HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)P * sizeof(uint32_t), c->stream));
+        if (Q > 0) HIPCHK(c, hipMemsetAsync(F.cross.p, 0, (size_t)(P * Q) * sizeof(uint32_t), c->stream));
+    }
+    hipLaunchKernelGGL(k_pfp_cross, dim3((unsigned)tiles, (unsigned)*slices), dim3(256), 0, c->stream, A);
+    // ---- occupancy: column sums over the poses behind the references, the pose tiles cut into as many slices as fill the device
+    const long long chunks = (W + POSEFP_KC - 1) / POSEFP_KC;
+    // (a block keeps at least eight pose tiles where there are that many: its sums stay in registers, and fewer blocks meet on
+    // a counter at the end)
+    const long long pose_slices = std::max<long long>(1, std::min<long long>((tiles + 7) / 8, (2ll * c->num_cu + chunks - 1) / chunks));
+    A.occ_tiles = (int)((tiles + pose_slices - 1) / pose_slices);
+    hipLaunchKernelGGL(k_pfp_occupancy, dim3((unsigned)chunks, (unsigned)((tiles + A.occ_tiles - 1) / A.occ_tiles)), dim3(256), 0, c->stream, A);
+    return ARP_OK;
+}
+
 // Both entries: arp_poses_fingerprints_launch admits the 15 SIFt bits and reads the poses result alone; with a bit from
 // ARP_POSEFP_PLANES on (arp_poses_fingerprints_planes_launch) the four tables of the poses-planes result are
 // marked and walked as well, after a check on the device that both results were made from the same pose coordinates — its flag
@@ -6181,23 +6230,9 @@ static int posefp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32
     hipLaunchKernelGGL(k_pfp_ids, dim3(nblocks(NW, 256, 1024)), dim3(256), 0, c->stream, A);
     if (k > 0) hipLaunchKernelGGL(k_pfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A);
     if (k_classes > 0) hipLaunchKernelGGL(k_pfp_bits_planes, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A, T);
-    // ---- cross = B R^T and count: the pose tiles times as many word slices as fill the device
     const long long tiles = (P + POSEFP_TILE - 1) / POSEFP_TILE;
-    long long per = 0, slices = 0;
-    popcount_slices(c, W, tiles, &per, &slices);
-    A.per = per; A.slices = (int)slices;
-    if (slices > 1) {
-        HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)P * sizeof(uint32_t), c->stream));
-        if (Q > 0) HIPCHK(c, hipMemsetAsync(F.cross.p, 0, (size_t)(P * Q) * sizeof(uint32_t), c->stream));
-    }
-    hipLaunchKernelGGL(k_pfp_cross, dim3((unsigned)tiles, (unsigned)slices), dim3(256), 0, c->stream, A);
-    // ---- occupancy: column sums over the poses behind the references, the pose tiles cut into as many slices as fill the device
-    const long long chunks = (W + POSEFP_KC - 1) / POSEFP_KC;
-    // (a block keeps at least eight pose tiles where there are that many: its sums stay in registers, and fewer blocks meet on
-    // a counter at the end)
-    const long long pose_slices = std::max<long long>(1, std::min<long long>((tiles + 7) / 8, (2ll * c->num_cu + chunks - 1) / chunks));
-    A.occ_tiles = (int)((tiles + pose_slices - 1) / pose_slices);
-    hipLaunchKernelGGL(k_pfp_occupancy, dim3((unsigned)chunks, (unsigned)((tiles + A.occ_tiles - 1) / A.occ_tiles)), dim3(256), 0, c->stream, A);
+    long long slices = 0;
+    CHK(enqueue_cross_and_occupancy(c, F, A, &slices));
     // ---- all pairs: k_sim_gram on this matrix, the poses as its models
     if (all_pairs) {
         SimArgs G{};
@@ -6247,6 +6282,198 @@ int arp_poses_fingerprints_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     posefp_info(c->posefp, info);
     return ARP_OK;
+}
+
+// ---- library fingerprints (arp_library_fingerprints.h): the resident library result -> bit matrix -> scores
+// Only the library result is read (its sorted slab, pose_off, the ligands' pose ranges) and res_id; only this result's own
+// buffers are written.  The references are the caller's feature lists: rows 0 ... Q - 1 of a matrix of Q + T rows, so that
+// k_pfp_scan, k_pfp_ids, k_pfp_cross and k_pfp_occupancy are launched as they are.  One wait: U, which sizes the matrix.
+static_assert(LIBFP_MAX_FEATURES == ARP_LIBFP_MAX_FEATURES, "arp_library_fingerprints.h names the header's limit");
+int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, const int64_t* ref_off,
+                                    const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_library_fingerprints_launch: ";
+    PoseFpResult& F = c->libfp;
+    LibraryFpTables& X = c->libfpx;
+    const LibraryResult& R = c->libres;
+    // ---- the refusals, in this order: none of them touches a resident result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
+    if (planes & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no record");
+    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
+    if (flags & ~ARP_POSEFP_BY_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag (ARP_POSEFP_BY_RESIDUE is the only one)");
+    const bool by_res = (flags & ARP_POSEFP_BY_RESIDUE) != 0;
+    if (by_res && (!c->has_res || c->nres <= 0)) FAIL(c, ARP_E_ARG, fn + "no residues resident (ARP_POSEFP_BY_RESIDUE)");
+    const int64_t Q = n_refs, T = R.T, P = Q + T;
+    if (Q < 0 || Q > ARP_POSEFP_MAX_REFS) FAIL(c, ARP_E_ARG, fn + "n_refs must be 0 ... ARP_POSEFP_MAX_REFS");
+    if (Q > 0 && (!ref_off || !ref_node || !ref_planes)) FAIL(c, ARP_E_ARG, fn + "a reference array is missing");
+    const int64_t N = by_res ? c->nres : c->n, NW = (N + 63) / 64;
+    int64_t nf = 0;
+    if (Q > 0) {
+        if (ref_off[0] != 0) FAIL(c, ARP_E_ARG, fn + "ref_off must start at 0");
+        for (int64_t q = 0; q < Q; ++q)
+            if (ref_off[q + 1] < ref_off[q]) FAIL(c, ARP_E_ARG, fn + "ref_off must not decrease");
+        nf = ref_off[Q];
+        if (nf > ARP_LIBFP_MAX_FEATURES) FAIL(c, ARP_E_ARG, fn + "more than ARP_LIBFP_MAX_FEATURES reference features");
+        for (int64_t f = 0; f < nf; ++f)
+            if (ref_node[f] < 0 || (int64_t)ref_node[f] >= N) FAIL(c, ARP_E_ARG, fn + "a reference node outside [0, nodes of the level)");
+        for (int64_t q = 0; q < Q; ++q)
+            for (int64_t f = ref_off[q] + 1; f < ref_off[q + 1]; ++f)
+                if (ref_node[f] <= ref_node[f - 1]) FAIL(c, ARP_E_ARG, fn + "the nodes of a reference must be strictly ascending");
+        for (int64_t f = 0; f < nf; ++f)
+            if (ref_planes[f] & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "a reference mask has bits beyond the 15 SIFt bits");
+    }
+    const int NP = __builtin_popcount(planes);
+    // ---- from here on the fingerprint before is gone, and its best-pose table
+    void_pose_results(c, POSE_LIBRARY_FINGERPRINT);
+    F.classes = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)R.rec.count;
+    HIPCHK(c, F.presence.reserve((size_t)NW));
+    HIPCHK(c, F.base.reserve((size_t)NW));
+    HIPCHK(c, F.total.reserve(2));
+    HIPCHK(c, F.count.reserve((size_t)P));
+    HIPCHK(c, F.cross.reserve(std::max<size_t>((size_t)(P * Q), 1)));
+    LibFpRefs V{};
+    if (Q > 0) {
+        CHK(upload_async(c, X.ref_off, (const long long*)ref_off, (size_t)Q + 1));
+        CHK(upload_async(c, X.ref_node, (const int*)ref_node, (size_t)nf));
+        CHK(upload_async(c, X.ref_planes, ref_planes, (size_t)nf));
+        V.ref_off = X.ref_off.p; V.ref_node = X.ref_node.p; V.ref_planes = X.ref_planes.p; V.F = nf;
+    }
+    PoseFpArgs A{};
+    const uint8_t* const slab = R.rec.slab.p;
+    if (k > 0) {
+        A.ci = (const int*)(slab + R.rec.off[0]);      // (the ligand side, column 1, names no node: not read)
+        A.sift = (const uint16_t*)(slab + R.rec.off[3]); A.ctype = slab + R.rec.off[4];
+    }
+    A.pose_off = R.rec.pose_off.p; A.res_id = c->res_id.p;
+    A.k = (long long)k; A.P = (int)P; A.Q = (int)Q; A.N = N; A.by_res = by_res ? 1 : 0;
+    A.planes = planes; A.ctype_mask = ctype_mask;
+    A.presence = F.presence.p; A.base = F.base.p; A.NW = NW; A.total = F.total.p;
+    A.NP = NP; A.count = F.count.p; A.cross = F.cross.p;
+    const auto done = [&](long long U, long long W, long long slices) {
+        F.P = P; F.Q = Q; F.U = U; F.NP = NP; F.W = W; F.slices = slices;
+        F.planes = planes; F.ctype_mask = ctype_mask; F.flags = flags;
+        F.valid = true;
+        X.L = R.L; X.features = nf;
+        ++F.launches;
+        posefp_info(F, info);
+        return ARP_OK;
+    };
+    // ---- the columns: presence bitmap of the nodes of records and references, popcounts, scan; the host learns U (the one wait,
+    // after which the caller's reference arrays are free)
+    long long U = 0;
+    if (k > 0 || Q > 0) {
+        HIPCHK(c, hipMemsetAsync(F.presence.p, 0, (size_t)NW * sizeof(unsigned long long), c->stream));
+        if (k + (size_t)nf > 0) hipLaunchKernelGGL(k_lfp_mark, dim3(nblocks((int64_t)k + nf, 256, c->num_cu)), dim3(256), 0, c->stream, A, V);
+        hipLaunchKernelGGL(k_pfp_scan, dim3(1), dim3(POSEFP_SCAN_THREADS), 0, c->stream, A);
+        CHK(check_launch(c, (fn + "mark / scan").c_str()));
+        CHK(stage_copy(c, F.total.p, sizeof(long long)));
+        memcpy(&U, c->table_stage, sizeof(U));
+        if (U < 0 || U > N) FAIL(c, ARP_E_HIP, fn + "column count out of range");
+    }
+    if (U == 0) {      // no participating record and no reference feature: no column, no feature in any row
+        HIPCHK(c, hipMemsetAsync(F.count.p, 0, (size_t)P * sizeof(uint32_t), c->stream));
+        if (Q > 0) HIPCHK(c, hipMemsetAsync(F.cross.p, 0, (size_t)(P * Q) * sizeof(uint32_t), c->stream));
+        return done(0, 0, 0);
+    }
+    // ---- the bit matrix: NP planes of ceil(U / 64) words a row, OR-ed into zeroed memory by a wave per row
+    // (the two capacity limits of the pose fingerprints, over Q + T rows: they need U, so they come after the wait and leave no
+    // fingerprint resident)
+    const long long wpp = (U + 63) / 64, W = (long long)NP * wpp;
+    if ((long long)NP * U >= (1ll << 32)) FAIL(c, ARP_E_CAPACITY, fn + "2^32 features or more (a count would not fit uint32)");
+    if (P * W >= (1ll << 29)) FAIL(c, ARP_E_CAPACITY, fn + "a bit matrix of 4 GiB or more (launch fewer poses)");
+    HIPCHK(c, F.ids.reserve((size_t)U));
+    HIPCHK(c, F.occ.reserve((size_t)(U * NP)));
+    HIPCHK(c, F.bits.reserve((size_t)(P * W)));
+    HIPCHK(c, hipMemsetAsync(F.bits.p, 0, (size_t)(P * W) * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(F.occ.p, 0, (size_t)(U * NP) * sizeof(uint32_t), c->stream));
+    A.ids = F.ids.p; A.U = U; A.bits = F.bits.p; A.wpp = wpp; A.W = W; A.occ = F.occ.p;
+    hipLaunchKernelGGL(k_pfp_ids, dim3(nblocks(NW, 256, 1024)), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_lfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A, V);
+    long long slices = 0;
+    CHK(enqueue_cross_and_occupancy(c, F, A, &slices));
+    CHK(check_launch(c, (fn + "ids / bits / cross / occupancy").c_str()));
+    return done(U, W, slices);
+}
+
+int arp_library_fingerprints_fetch(arp_ctx* c, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy, uint64_t* bits,
+                                   int64_t* n_nodes) {
+    if (!c || !n_nodes) return ARP_E_ARG;
+    const PoseFpResult& F = c->libfp;
+    if (!F.valid)
+        FAIL(c, ARP_E_ARG, "arp_library_fingerprints_fetch: no result (arp_library_fingerprints_launch; the library result was replaced or the structure or the library changed since)");
+    *n_nodes = F.U;
+    if ((ids || occupancy || bits) && F.U > cap_nodes) FAIL(c, ARP_E_CAPACITY, "arp_library_fingerprints_fetch: output buffers too small (cap_nodes < *n_nodes)");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, ids, F.ids.p, (size_t)F.U * sizeof(int32_t));
+    want_piece(pieces, count, F.count.p, (size_t)F.P * sizeof(uint32_t));
+    want_piece(pieces, cross, F.cross.p, (size_t)(F.P * F.Q) * sizeof(uint32_t));
+    want_piece(pieces, occupancy, F.occ.p, (size_t)(F.U * F.NP) * sizeof(uint32_t));
+    // (the bit matrix, the one large piece, goes straight to the caller's array, as arp_poses_fingerprints_fetch copies it)
+    CHK(download_async(c, (unsigned long long*)bits, (const unsigned long long*)F.bits.p, (size_t)(F.P * F.W)));
+    return stage_fetch(c, pieces);
+}
+
+int arp_library_fingerprints_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    posefp_info(c->libfp, info);
+    return ARP_OK;
+}
+
+int arp_library_fingerprints_best_launch(arp_ctx* c) {
+    if (!c) return ARP_E_ARG;
+    const std::string fn = "arp_library_fingerprints_best_launch: ";
+    const PoseFpResult& F = c->libfp;
+    LibraryFpTables& X = c->libfpx;
+    const LibraryResult& R = c->libres;
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!F.valid || !R.valid) FAIL(c, ARP_E_ARG, fn + "no library fingerprint (arp_library_fingerprints_launch; the library result was replaced or the structure or the library changed since)");
+    if (F.Q < 1) FAIL(c, ARP_E_ARG, fn + "the library fingerprint has no reference (n_refs = 0)");
+    HIPCHK(c, hipSetDevice(c->device));
+    void_pose_results(c, POSE_LIBRARY_FP_BEST);
+    const size_t L = (size_t)R.L, LQ = L * (size_t)F.Q;
+    HIPCHK(c, X.best_n.reserve(L));
+    HIPCHK(c, X.best_pose.reserve(LQ));
+    HIPCHK(c, X.best_q32.reserve(LQ));
+    HIPCHK(c, X.best_shared.reserve(LQ));
+    HIPCHK(c, X.best_count.reserve(LQ));
+    LibFpBest B{};
+    B.L = (int)R.L; B.Q = (int)F.Q; B.Qp = 1;
+    while (B.Qp < B.Q) B.Qp <<= 1;
+    B.pose_off = R.tab.p; B.count = F.count.p; B.cross = F.cross.p;
+    B.n_poses = X.best_n.p; B.best_pose = X.best_pose.p; B.q32 = X.best_q32.p; B.shared = X.best_shared.p; B.best_count = X.best_count.p;
+    hipLaunchKernelGGL(k_lfp_best, dim3(nblocks(R.L * 64, 256, 2048)), dim3(256), 0, c->stream, B);
+    CHK(check_launch(c, "k_lfp_best"));
+    X.L = R.L;
+    X.best_valid = true;
+    return ARP_OK;
+}
+
+int arp_library_fingerprints_best_fetch(arp_ctx* c, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose, int64_t* tanimoto_q32, uint32_t* shared,
+                                        uint32_t* count, int64_t* n_ligands, int64_t* n_refs) {
+    if (!c || !n_ligands || !n_refs) return ARP_E_ARG;
+    const PoseFpResult& F = c->libfp;
+    const LibraryFpTables& X = c->libfpx;
+    if (!F.valid || !X.best_valid)
+        FAIL(c, ARP_E_ARG, "arp_library_fingerprints_best_fetch: no result (arp_library_fingerprints_best_launch; the library fingerprint was replaced or the library result, the structure or the library changed since)");
+    *n_ligands = X.L;
+    *n_refs = F.Q;
+    if ((n_poses || best_pose || tanimoto_q32 || shared || count) && cap_ligands < X.L)
+        FAIL(c, ARP_E_CAPACITY, "arp_library_fingerprints_best_fetch: output buffers too small (cap_ligands < *n_ligands)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t L = (size_t)X.L, LQ = L * (size_t)F.Q;
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, n_poses, X.best_n.p, L * sizeof(int64_t));
+    want_piece(pieces, best_pose, X.best_pose.p, LQ * sizeof(int32_t));
+    want_piece(pieces, tanimoto_q32, X.best_q32.p, LQ * sizeof(int64_t));
+    want_piece(pieces, shared, X.best_shared.p, LQ * sizeof(uint32_t));
+    want_piece(pieces, count, X.best_count.p, LQ * sizeof(uint32_t));
+    return stage_fetch(c, pieces);
 }
 
 // ---- pose shortlist (arp_poses_shortlist.h): the resident poses result -> ranked poses -> the chosen ones' records

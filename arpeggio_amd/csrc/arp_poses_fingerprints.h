@@ -84,6 +84,23 @@ __device__ __forceinline__ void pfp_set_bit(unsigned long long* word, unsigned l
     (void)__hip_atomic_fetch_or(word, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The two steps of a bits kernel (k_pfp_bits, k_pfp_bits_planes, and k_lfp_bits of arp_library_fingerprints.h):
+// the column of a node whose presence bit is set: the set bits in front of it
+__device__ __forceinline__ long long pfp_column(const PoseFpArgs& A, long long node) {
+    return (long long)A.base[node >> 6] + __popcll(A.presence[node >> 6] & ((1ull << (node & 63)) - 1ull));
+}
+// column `col` of every plane of m into `row`: plane b of the launch is the compact plane popcount(planes below b)
+__device__ __forceinline__ void pfp_or_planes(const PoseFpArgs& A, unsigned long long* row, long long col, uint32_t m) {
+    const unsigned long long bit = 1ull << (col & 63);
+    unsigned long long* const mine = row + (col >> 6);
+    while (m) {
+        const int b = __ffs((int)m) - 1;
+        m &= m - 1u;
+        const long long q = (long long)__popc(A.planes & ((1u << b) - 1u));
+        pfp_set_bit(mine + q * A.wpp, bit);
+    }
+}
+
 // does record r take part, and with which planes
 __device__ __forceinline__ uint32_t pfp_record_planes(const PoseFpArgs& A, long long r) {
     const uint32_t ct = A.ctype[r];
@@ -155,16 +172,9 @@ __global__ __launch_bounds__(256) void k_pfp_bits(PoseFpArgs A) {
             if (!m) continue;
             const long long node = pfp_node(A, r);
             if (node < 0) continue;
-            const long long col = (long long)A.base[node >> 6] + __popcll(A.presence[node >> 6] & ((1ull << (node & 63)) - 1ull));
+            const long long col = pfp_column(A, node);
             if (col >= A.U) continue;      // (never: k_pfp_mark set this node's bit)
-            const unsigned long long bit = 1ull << (col & 63);
-            unsigned long long* const mine = row + (col >> 6);
-            while (m) {
-                const int b = __ffs((int)m) - 1;
-                m &= m - 1u;
-                const long long q = (long long)__popc(A.planes & ((1u << b) - 1u));
-                pfp_set_bit(mine + q * A.wpp, bit);
-            }
+            pfp_or_planes(A, row, col, m);
         }
     }
 }
@@ -288,16 +298,9 @@ __device__ __forceinline__ void pfp_bits_table(const PoseFpArgs& A, const PoseFp
         long long node = -1;
         uint32_t m = pfp_class_planes<t>(A, T, r, &node);
         if (!m || node < 0) continue;
-        const long long col = (long long)A.base[node >> 6] + __popcll(A.presence[node >> 6] & ((1ull << (node & 63)) - 1ull));
+        const long long col = pfp_column(A, node);
         if (col >= A.U) continue;      // (never: k_pfp_mark_planes set this node's bit)
-        const unsigned long long bit = 1ull << (col & 63);
-        unsigned long long* const mine = row + (col >> 6);
-        while (m) {
-            const int b = __ffs((int)m) - 1;
-            m &= m - 1u;
-            const long long q = (long long)__popc(A.planes & ((1u << b) - 1u));
-            pfp_set_bit(mine + q * A.wpp, bit);
-        }
+        pfp_or_planes(A, row, col, m);
     }
 }
 __global__ __launch_bounds__(256) void k_pfp_bits_planes(PoseFpArgs A, PoseFpTables T) {

@@ -228,6 +228,21 @@ def chunk_plan(pose_off, chunk):
     return [(np.clip(off, a, min(a + step, T)) - a, a, min(a + step, T)) for a in range(0, T, step)]
 
 
+def chunk_poses(lib, pose_off, xyz, h_xyz, chunk):
+    """``chunk_plan`` with every launch's coordinates: yields ``(pose_off_c, first global pose, last + 1, xyz_c, h_xyz_c)``, the
+    flat arrays of ``flatten_poses`` cut to the global poses of the range — of every ligand its poses inside it."""
+    off = np.asarray(pose_off, np.int64)
+    x, h = np.asarray(xyz).reshape(-1), np.asarray(h_xyz).reshape(-1)
+    S, SH = sizes(lib)
+    x_at = np.concatenate([[0], np.cumsum(np.diff(off) * S * 3)])
+    h_at = np.concatenate([[0], np.cumsum(np.diff(off) * SH * 3)])
+    for off_c, a, b in chunk_plan(off, chunk):
+        first = np.clip(off, a, b) - off                       # (how many of the ligand's poses come before the range)
+        xs = [x[x_at[l] + first[l] * S[l] * 3:x_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * S[l] * 3] for l in range(len(S))]
+        hs = [h[h_at[l] + first[l] * SH[l] * 3:h_at[l] + (first[l] + off_c[l + 1] - off_c[l]) * SH[l] * 3] for l in range(len(S))]
+        yield off_c, a, b, np.concatenate(xs), np.concatenate(hs)
+
+
 def concat(chunks):
     """The results of launches over consecutive ranges of the global poses (``chunk_plan``) as one result."""
     chunks = list(chunks)

@@ -1348,8 +1348,8 @@ int arp_poses_clusters_info(arp_ctx* ctx, int64_t info[8]);
  *   is asked for).  arp_library_info: info[0] = L, [3] = TA, [4] = hydrogen rows, [6] = the largest S_l of the resident
  *   library; [1] = T, [2] = records, [5] = blocks of k_library_contacts (poses are taken with a grid stride) of the resident
  *   result; [7] = 1 while a best-pose table is resident.
- * OUT OF SCOPE: the ligands' own rings and amides (the plane tables of a library); fingerprints, the shortlist and clusters over
- *   a library result (the summary layout is that of the poses result, so that they can follow); peptide and covalent ligands;
+ * OUT OF SCOPE: the ligands' own rings and amides (the plane tables of a library); the shortlist and clusters over a library
+ *   result (fingerprints: arp_library_fingerprints_launch below); peptide and covalent ligands;
  *   cutoffs beyond 6.0; a batch, models or a shard as the receptor; the per-atom accumulators. */
 #define ARP_LIBRARY_MAX_LIGANDS (1 << 16)
 #define ARP_LIBRARY_MAX_ATOMS 256
@@ -1363,6 +1363,55 @@ int arp_library_info(arp_ctx* ctx, int64_t info[8]);
 int arp_library_best_launch(arp_ctx* ctx, const int32_t* weights);
 int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose, int64_t* score,
                            int64_t* n_ligands);
+/* Library fingerprints: the resident library result reduced on the device to interaction fingerprints and scored against
+ * reference interactions (csrc/arp_library_fingerprints.h).  An extension beside the mirror.
+ *
+ * FEATURE.  (node, plane).  The node is the receptor atom i of a participating library record, with ARP_POSEFP_BY_RESIDUE
+ *   res_id[i]; the plane is one of the 15 SIFt bits selected by `planes`.  A record participates when bit ctype of ctype_mask
+ *   is set and sift & planes != 0.  The ligand side a never names a node.  There are no class planes (a library has no ring or
+ *   amide tables) and no all-pairs matrix (T reaches 2^20).
+ * REFERENCES need not be poses of the launch: the known binder is usually another molecule.  Q = n_refs <=
+ *   ARP_POSEFP_MAX_REFS references are given as feature lists: ref_off int64 [Q + 1] (ref_off[0] = 0, not decreasing, F =
+ *   ref_off[Q] <= ARP_LIBFP_MAX_FEATURES), ref_node int32 [F] (nodes of the launch's level, strictly ascending within a
+ *   reference), ref_planes uint32 [F] (plane masks BEFORE selection).  The device ANDs every mask with `planes`; a feature whose
+ *   mask becomes 0 is dropped; a node that keeps a plane is a column EVEN IF NO POSE TOUCHES IT, so a reference's count is
+ *   complete and the chunks of one screen carry identical reference rows.  All three may be NULL when Q = 0.
+ * RESULT.  Q + T rows: row q < Q is reference q, row Q + t is global pose t of the resident library result.  The arrays are
+ *   those of arp_poses_fingerprints_fetch with P = Q + T: ids int32 [U] ascending; count uint32 [Q + T]; cross uint32 [Q + T][Q];
+ *   occupancy uint32 [U][NP], over the rows >= Q only; bits uint64 [Q + T][NP][ceil(U / 64)].  info[8] as
+ *   arp_poses_fingerprints_info: rows (Q + T), Q, U, NP, words a row, word slices of the cross product, launches, flags
+ *   (info[6] counts EVERY launch that passed its refusals: there is no "same arguments" shortcut — the references are the
+ *   caller's arrays and comparing them costs what uploading them does).
+ *   ARP_E_ARG with the cause named, in this order, none touching a resident result: a pass not waited for; no library result
+ *   resident; planes 0 or beyond the 15 bits; ctype_mask 0 or beyond the 7 types; a flag other than ARP_POSEFP_BY_RESIDUE; by
+ *   residue without residues resident; Q outside 0 ... ARP_POSEFP_MAX_REFS; a reference array NULL with Q > 0; ref_off not
+ *   starting at 0, or decreasing; F > ARP_LIBFP_MAX_FEATURES; a node outside [0, N) (N = atoms, or residues); nodes not
+ *   strictly ascending within a reference; a mask beyond the 15 bits.  Then, once U is known (the fingerprint before is void by
+ *   then and none is resident afterwards), ARP_E_CAPACITY as arp_poses_fingerprints_launch with P = Q + T: NP U >= 2^32; a bit
+ *   matrix of 4 GiB or more.
+ *   All work goes on the context's stream; ONE host wait a launch, for U — the caller's reference arrays are free after it.
+ * BEST POSE PER LIGAND (arp_library_fingerprints_best_launch / _fetch).  Reads count and cross of the resident fingerprint and
+ *   the ligands' pose ranges.  For ligand l and reference q the global pose t of the highest Tanimoto in 32 fractional bits:
+ *   with x = cross[Q + t][q] and u = count[Q + t] + count[q] - x it is floor(x 2^32 / u), and 2^32 where u = 0.  Ties go to the
+ *   lower global pose.  n_poses int64 [L]; best_pose int32 [L][Q]; tanimoto_q32 int64 [L][Q]; shared uint32 [L][Q] (that x);
+ *   count uint32 [L][Q] (the best pose's own feature count, so that recovery follows).  A ligand without poses: -1, -1, 0, 0.
+ *   Refused (ARP_E_ARG) without a resident fingerprint and when that was made with Q = 0.  _fetch: any array may be NULL;
+ *   ARP_E_CAPACITY when one is asked for and cap_ligands < *n_ligands = L; *n_refs = Q.
+ * STATE.  The fingerprint is void wherever the library result is (a new structure, models, a batch, arp_set_ligand_library, a
+ *   new library launch) and after a new fingerprint launch; its best-pose table goes with it.  arp_set_selection voids neither.
+ *   Making either voids nothing else: the library result, its best-pose table and every pose result stay fetchable and
+ *   byte-equal.
+ * OUT OF SCOPE: class planes; the all-pairs matrix; a shortlist or clusters over the library fingerprint. */
+#define ARP_LIBFP_MAX_FEATURES (1 << 22)
+int arp_library_fingerprints_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
+                                    const int64_t* ref_off, const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]);
+int arp_library_fingerprints_fetch(arp_ctx* ctx, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross,
+                                   uint32_t* occupancy, uint64_t* bits, int64_t* n_nodes);
+int arp_library_fingerprints_info(arp_ctx* ctx, int64_t info[8]);
+int arp_library_fingerprints_best_launch(arp_ctx* ctx);
+int arp_library_fingerprints_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose,
+                                        int64_t* tanimoto_q32, uint32_t* shared, uint32_t* count, int64_t* n_ligands,
+                                        int64_t* n_refs);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
