@@ -58,6 +58,7 @@ SYMBOLS = (
     'arp_library_best_launch', 'arp_library_best_fetch',
     'arp_library_fingerprints_launch', 'arp_library_fingerprints_fetch', 'arp_library_fingerprints_info',
     'arp_library_fingerprints_best_launch', 'arp_library_fingerprints_best_fetch',
+    'arp_set_ligand_library_planes', 'arp_library_planes_launch', 'arp_library_planes_fetch', 'arp_library_planes_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -280,6 +281,10 @@ def load():
     L.arp_library_fingerprints_info.argtypes = [vp, vp]
     L.arp_library_fingerprints_best_launch.argtypes = [vp]
     L.arp_library_fingerprints_best_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_set_ligand_library_planes.argtypes = [vp] * 6
+    L.arp_library_planes_launch.argtypes = [vp, vp, vp, vp]
+    L.arp_library_planes_fetch.argtypes = [vp, C.c_int, i64] + [vp] * 11 + [C.POINTER(i64)]
+    L.arp_library_planes_info.argtypes = [vp, vp]
     L.arp_comm_unique_id.argtypes = [vp, C.c_uint64]
     L.arp_comm_init.argtypes = [vp, i32, i32, vp]
     L.arp_comm_destroy.argtypes = [vp]
@@ -1310,6 +1315,92 @@ class Context:
         self._check(self._L.arp_library_info(self._h, _p(info)), 'arp_library_info')
         return dict(ligands=int(info[0]), poses=int(info[1]), records=int(info[2]), atoms=int(info[3]), hydrogens=int(info[4]),
                     blocks=int(info[5]), max_atoms=int(info[6]), best=bool(info[7]))
+
+    def set_ligand_library_planes(self, lib):
+        """The plane table of the resident ligand library (arp_set_ligand_library_planes): the five arrays ``ring_off``,
+        ``ring_atom_off``, ``ring_atom_idx``, ``amide_off`` and ``amide_atoms`` of ``lib`` as ``ligand_library.pack`` gives it — ring
+        paths and amide atoms by index within the ligand.  It is dropped by ``set_ligand_library`` and replaced by a new call."""
+        res = getattr(self, '_library', None)
+        if res is None:
+            raise ValueError('set_ligand_library_planes: no ligand library (set_ligand_library)')
+        L = len(res['atom_off']) - 1
+        arr = {k: np.ascontiguousarray(lib[k], np.int32) for k in ('ring_off', 'ring_atom_off', 'ring_atom_idx', 'amide_off')}
+        am = np.ascontiguousarray(lib['amide_atoms'], np.int32).reshape(-1, 4)
+        # (the library reads L + 1 offsets, ring_off[-1] + 1 ring offsets and as many indices and amides as those name: checked here)
+        for k in ('ring_off', 'amide_off'):
+            if arr[k].shape != (L + 1,):
+                raise ValueError(f'set_ligand_library_planes: {k} must be [{L + 1}] (one entry per ligand of the library, and the total)')
+        TR, TM = int(arr['ring_off'][-1]), int(arr['amide_off'][-1])
+        if arr['ring_atom_off'].shape != (max(TR, 0) + 1,):
+            raise ValueError(f'set_ligand_library_planes: ring_atom_off must hold ring_off[-1] + 1 = {TR + 1} entries')
+        if arr['ring_atom_idx'].shape != (max(int(arr['ring_atom_off'][-1]), 0),):
+            raise ValueError(f'set_ligand_library_planes: ring_atom_idx must hold ring_atom_off[-1] = {int(arr["ring_atom_off"][-1])} entries')
+        if len(am) != max(TM, 0):
+            raise ValueError(f'set_ligand_library_planes: amide_atoms must be [{TM}, 4]')
+        self._check(self._L.arp_set_ligand_library_planes(self._h, _p(arr['ring_off']), _p(arr['ring_atom_off']),
+                                                          _p(arr['ring_atom_idx']) if len(arr['ring_atom_idx']) else None, _p(arr['amide_off']),
+                                                          _p(am) if len(am) else None), 'arp_set_ligand_library_planes')
+
+    def _library_planes_launch(self, pose_off, xyz):
+        """Lengths checked against the resident library and ``pose_off``, then arp_library_planes_launch; returns (T, counts, off)."""
+        lib = getattr(self, '_library', None)
+        if lib is None:
+            raise ValueError('library_planes: no ligand library (set_ligand_library)')
+        L = len(lib['atom_off']) - 1
+        off = np.ascontiguousarray(pose_off, np.int64)
+        if off.shape != (L + 1,):
+            raise ValueError(f'library_planes: pose_off must be [{L + 1}] (one entry per ligand of the library, and the total)')
+        P = np.diff(off)
+        ok = off[0] == 0 and (P >= 0).all()
+        nx = int((P * np.diff(lib['atom_off'])).sum()) * 3 if ok else 0
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1)
+        if ok and len(x) != nx:
+            raise ValueError(f'library_planes: xyz must hold {nx} values (sum of P_l S_l 3, ligand-major then pose-major)')
+        counts = np.zeros(4, np.int64)
+        self._check(self._L.arp_library_planes_launch(self._h, _p(off), _p(x), _p(counts)), 'arp_library_planes_launch')
+        return int(off[-1]), counts, off
+
+    def library_planes(self, pose_off, xyz):
+        """Every (ligand, pose)'s ring and amide contacts in one launch (arp_library_planes_*; ``arpeggio_amd.ligand_library``).
+        ``pose_off`` int64 [L + 1] and ``xyz`` float32 as ``library_contacts`` takes them.  Returns a dict with one table per bag
+        — ``atom_plane``, ``plane_plane``, ``group_group``, ``group_plane``: the columns of ``fetch_bag`` plus ``pose_off`` uint64
+        [T + 1], per global pose exactly the records of the complex's bag that involve an affected entity, in the bag's canonical
+        order, with the complex's ids (ligand atom n + a, ring n_rings + q, amide n_amides + g) —, ``summary`` uint32 [T, 16] and
+        ``ligand_pose_off`` int64 [L + 1] (the argument)."""
+        from . import poses as _poses
+        T, counts, off = self._library_planes_launch(pose_off, xyz)
+        out = {}
+        n = C.c_int64(0)
+        summary = np.empty((T, POSES_PLANES_SUMMARY), np.uint32)
+        for t, name in enumerate(_poses.PLANE_TABLES):
+            k = int(counts[t])
+            tab, args = self._plane_table_buffers(name, k, T + 1)
+            self._check(self._L.arp_library_planes_fetch(self._h, t, k, _p(tab['pose_off']), *args, _p(summary) if t == 0 else None, C.byref(n)),
+                        'arp_library_planes_fetch')
+            out[name] = tab
+        out['summary'] = summary
+        out['ligand_pose_off'] = off
+        return out
+
+    def library_planes_summary(self, pose_off, xyz):
+        """``library_planes`` with only the per-pose summary copied to the host: uint32 [T, 16] (``poses.PLANE_SUMMARY_SLOTS``)."""
+        T, _, _ = self._library_planes_launch(pose_off, xyz)
+        s = np.empty((T, POSES_PLANES_SUMMARY), np.uint32)
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_planes_fetch(self._h, 0, 0, *([None] * 10), _p(s), C.byref(n)), 'arp_library_planes_fetch')
+        return s
+
+    def library_planes_info(self):
+        """arp_library_planes_info: ligands, rings and amides of the resident plane table; poses, records per table and the blocks
+        of the launch of the resident result (zeros while there is none); the kernel launches so far; whether a plane table and
+        the per-structure set-up are resident."""
+        from . import poses as _poses
+        info = np.zeros(12, np.int64)
+        self._check(self._L.arp_library_planes_info(self._h, _p(info)), 'arp_library_planes_info')
+        d = dict(ligands=int(info[0]), rings=int(info[1]), amides=int(info[2]), poses=int(info[3]))
+        d.update({name: int(info[4 + t]) for t, name in enumerate(_poses.PLANE_TABLES)})
+        d.update(blocks=int(info[8]), launches=int(info[9]), plane_table=bool(info[10]), setup=bool(info[11]))
+        return d
 
     def library_fingerprints(self, refs, planes, ctype_mask=CTYPE_ALL, by_residue=True, bits=False):
         """The resident library result (``library_contacts`` / ``library_summary``) reduced on the device to interaction

@@ -454,7 +454,7 @@ class InteractionComplex:
             raise AttributeError('no poses yet: call run_poses() first')
         return _poses.write_poses(wd, self.id, self.poses, self.pc, self.component_types)
 
-    def run_ligand_library(self, ligands, poses, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None, weights=None):
+    def run_ligand_library(self, ligands, poses, interacting_cutoff, vdw_comp, include_sequence_adjacent, chunk=None, weights=None, planes=False):
         """Extension beside the mirror: the contacts of many DIFFERENT ligands, each with its poses, against this structure as
         the fixed receptor (``arpeggio_amd.ligand_library``; ``run_poses`` moves one ligand that is part of the structure).
         ``ligands`` are packs of one residue each (``ligand_library.pack`` says what is refused); ``poses`` holds per ligand
@@ -465,7 +465,10 @@ class InteractionComplex:
         poses may be cut between two launches).  Returns the table ``ligand_library`` describes (kept in ``self.ligand_library``,
         the ligands in ``self.ligand_library_ligands``).  ``weights`` int [16]: also the best pose per ligand by the weighted sum
         of its summary row (``self.ligand_library_best``): from the device when one launch held every pose, else the host mirror
-        over the joined summaries.  The results of the last ``run_arpeggio`` and of ``run_poses`` stay as they are."""
+        over the joined summaries.  ``planes``: every chunk is also launched as ``Context.library_planes`` — the ring and amide
+        contacts of the same poses, from the ligands' ``ring_atoms`` / ``amide_atoms`` —, kept in ``self.library_planes``
+        (``ligand_library.concat_planes`` over the chunks; None after a run without ``planes``).  The results of the last ``run_arpeggio`` and of ``run_poses`` stay as
+        they are."""
         from .. import _capi, ligand_library as _ll
         if self._ctx is None:
             self.initialize()
@@ -476,9 +479,16 @@ class InteractionComplex:
         if off[-1] < 1:
             raise ValueError('run_ligand_library: no pose given')
         ctx.set_ligand_library(lib)
-        parts = [ctx.library_contacts(off_c, xc, hc, interacting_cutoff, vdw_comp, include_sequence_adjacent)
-                 for off_c, _, _, xc, hc in _ll.chunk_poses(lib, off, x, h, chunk if chunk else _capi.POSES_MAX_POSES)]
+        if planes:
+            ctx.set_ligand_library_planes(lib)
+        parts, plane_parts = [], []
+        for off_c, _, _, xc, hc in _ll.chunk_poses(lib, off, x, h, chunk if chunk else _capi.POSES_MAX_POSES):
+            parts.append(ctx.library_contacts(off_c, xc, hc, interacting_cutoff, vdw_comp, include_sequence_adjacent))
+            if planes:
+                plane_parts.append(ctx.library_planes(off_c, xc))
         self.ligand_library = parts[0] if len(parts) == 1 else _ll.concat(parts)
+        # (without planes an earlier planes result is dropped: it belongs to the ligands of that run)
+        self.library_planes = None if not planes else plane_parts[0] if len(plane_parts) == 1 else _ll.concat_planes(plane_parts)
         self.ligand_library_ligands = ligands
         if weights is not None:
             self.ligand_library_best = ctx.library_best(weights) if len(parts) == 1 else _ll.best(self.ligand_library, weights)
@@ -490,6 +500,14 @@ class InteractionComplex:
         if getattr(self, 'ligand_library', None) is None:
             raise AttributeError('no ligand library result yet: call run_ligand_library() first')
         return _ll.write_library(wd, self.id, self.ligand_library, self.pc, self.ligand_library_ligands, self.component_types)
+
+    def write_library_planes(self, wd):
+        """'<id>.libraryplanes': the ring and amide table of the last ``run_ligand_library(planes=True)`` as CSV, one row per record
+        (``ligand_library.write_planes_csv``)."""
+        from .. import ligand_library as _ll
+        if getattr(self, 'library_planes', None) is None:
+            raise AttributeError('no library planes result yet: call run_ligand_library(planes=True) first')
+        return _ll.write_library_planes(wd, self.id, self.library_planes, self.pc, self.ligand_library_ligands, self.component_types)
 
     def run_library_fingerprints(self, library, pose_off, xyz, h_xyz, refs, contacts=None, interacting_entities=None, level='residue',
                                  chunk=None, interacting_cutoff=5.0, vdw_comp=0.1):

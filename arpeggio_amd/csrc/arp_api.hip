@@ -46,6 +46,7 @@
 #include "arp_poses_clusters.h"
 #include "arp_library.h"
 #include "arp_library_fingerprints.h"
+#include "arp_library_planes.h"
 #include "arp_blob.h"
 
 namespace {
@@ -452,6 +453,42 @@ struct PosesPlanesResult {
     }
 };
 
+// the plane table of the ligand library (arp_set_ligand_library_planes, arp_library_planes.h): ring paths and amide atoms by index
+// within the ligand, CSR over the ligands.  Like the library it reads nothing of the resident structure
+struct LibraryPlaneAtoms {
+    DevBuf<int> ring_off, ring_atom_off, ring_atom_idx, amide_off, amide_atoms;
+    int64_t L = 0, TR = 0, TM = 0;
+    bool resident = false;
+    void release() { ring_off.release(); ring_atom_off.release(); ring_atom_idx.release(); amide_off.release(); amide_atoms.release(); resident = false; }
+};
+// the ring / amide contacts of a launch over the library (arp_library_planes_launch): the per-structure set-up (an all-atom 6 A
+// grid of its own by local id and the residue -> atoms CSR of the receptor), the per-pose / per-ligand tables of the uploaded
+// poses, the per-block lists, the records and their sort, the four tables in one slab
+struct LibraryPlanesResult {
+    DevBuf<int> hist, res_off, res_atoms, sums;
+    Grid grid;
+    bool setup = false;
+    DevBuf<int> lig_of;
+    DevBuf<long long> tab;                              // pose_off [L + 1] | xyz_at [L]
+    DevBuf<float> xyz;
+    DevBuf<PplRing> ws_ring;
+    DevBuf<PplAmide> ws_amide;
+    DevBuf<PlaneRec> rec;
+    DevBuf<unsigned long long> ctr, pose_off;
+    DevBuf<uint32_t> summary;
+    SortScratch sort;
+    DevBuf<uint8_t> slab;
+    PplColumns col{};
+    int64_t counts[4] = {0, 0, 0, 0};
+    int64_t L = 0, T = 0, blocks = 0, launches = 0;
+    bool valid = false;
+    void release() {
+        hist.release(); res_off.release(); res_atoms.release(); sums.release(); grid.release(); lig_of.release(); tab.release(); xyz.release();
+        ws_ring.release(); ws_amide.release(); rec.release(); ctr.release(); pose_off.release(); summary.release(); sort.release(); slab.release();
+        setup = valid = false;
+    }
+};
+
 struct arp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless arp_use_stream)
@@ -703,6 +740,8 @@ struct arp_ctx {
     LibraryResult libres;                 // arp_library_contacts_launch, arp_library_best_launch
     PoseFpResult libfp;                   // arp_library_fingerprints_launch: P = Q + T rows, the references first
     LibraryFpTables libfpx;               // ... its references, arp_library_fingerprints_best_launch
+    LibraryPlaneAtoms libplanes;          // arp_set_ligand_library_planes
+    LibraryPlanesResult libpl;            // arp_library_planes_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -908,7 +947,9 @@ void void_results(arp_ctx* c, unsigned lost) {
 // is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The ligand-library result
 //  is a row of the same table: it reads the structure and the library (POSE_LIBRARY, lost by
 // arp_set_ligand_library) and NO selection; the library fingerprint reads that result's records, and its best-pose
-// table reads the fingerprint.  The fingerprint and the
+// table reads the fingerprint; the library-planes result reads the structure, the library and the library's
+// plane table (POSE_LIBRARY_PLANE_ATOMS, lost with the library and by arp_set_ligand_library_planes), its per-structure set-up the
+// structure alone.  The fingerprint and the
 // shortlist read the poses-planes result only when they were made with class planes / with a ring or amide table or weight; the
 // clusters read the fingerprint result only while their launch runs, so they stand behind what THAT was made from, not behind it.
 // A launch names its own result here before it writes it, and sets it valid again at its end.
@@ -918,7 +959,9 @@ enum : unsigned {
     POSE_CLUSTERS = 1u << 8,
     POSE_LIBRARY = 1u << 9,           // the ligand library itself (arp_set_ligand_library)
     POSE_LIBRARY_CONTACTS = 1u << 10, POSE_LIBRARY_BEST = 1u << 11,
-    POSE_LIBRARY_FINGERPRINT = 1u << 12, POSE_LIBRARY_FP_BEST = 1u << 13
+    POSE_LIBRARY_FINGERPRINT = 1u << 12, POSE_LIBRARY_FP_BEST = 1u << 13,
+    POSE_LIBRARY_PLANE_ATOMS = 1u << 14,      // the library's plane table (arp_set_ligand_library_planes)
+    POSE_LIBRARY_PLANES_SETUP = 1u << 15, POSE_LIBRARY_PLANES = 1u << 16
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -935,7 +978,12 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->libres.best_valid, POSE_LIBRARY_BEST, POSE_LIBRARY_CONTACTS},
         // the library fingerprint reads the library result's records; its best-pose table reads its count and cross
         {&c->libfp.valid, POSE_LIBRARY_FINGERPRINT, POSE_LIBRARY_CONTACTS},
-        {&c->libfpx.best_valid, POSE_LIBRARY_FP_BEST, POSE_LIBRARY_FINGERPRINT}};
+        {&c->libfpx.best_valid, POSE_LIBRARY_FP_BEST, POSE_LIBRARY_FINGERPRINT},
+        // the library's plane table names atoms of the library's ligands; the set-up of the library-planes result (grid, residue
+        // CSR) reads the structure alone; the result reads the structure, the library and the plane table, and no selection
+        {&c->libplanes.resident, POSE_LIBRARY_PLANE_ATOMS, POSE_LIBRARY},
+        {&c->libpl.setup, POSE_LIBRARY_PLANES_SETUP, POSE_STRUCTURE},
+        {&c->libpl.valid, POSE_LIBRARY_PLANES, POSE_STRUCTURE | POSE_LIBRARY | POSE_LIBRARY_PLANE_ATOMS}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -2548,6 +2596,8 @@ void arp_destroy(arp_ctx* c) {
     c->libres.release();
     c->libfp.release();
     c->libfpx.release();
+    c->libplanes.release();
+    c->libpl.release();
     c->sb_idx.release();
     c->coupling.slab.release(); c->couple.rowbits.release(); c->couple.bits.release(); c->couple.n_row.release(); c->couple.n.release();
     if (c->table_stage) (void)hipHostFree(c->table_stage);
@@ -5588,6 +5638,67 @@ void pose_records_pieces(std::vector<StagePiece>& pieces, const PoseRecords& R, 
         want_piece(pieces, ctype, slab + R.off[4], k * sizeof(uint8_t));
     }
 }
+// The frame of both launches over poses that give ring / amide records (arp_poses_planes_launch, arp_library_planes_launch), after
+// the entry's own refusals, voiding and uploads: the counters, the summary rows and the offsets of `poses` poses are reserved,
+// `enqueue(sink)` launches the entry's kernel into `sink` (it reads R.ctr and R.summary, reserved by then) — again with room for
+// the exact count when the first buffer (64 records a pose, 65 536 at the least) was too small —, and the tail makes the four
+// pose_off tables, sorts by the keybits bits of the key and gathers the four tables into one slab.  One wait a launch of the
+// kernel: the counters (records, the device's error word, records per table).  `near_cause` names the entry's PPL_E_NEAR.
+struct PlaneRecords {
+    DevBuf<PlaneRec>& rec;
+    DevBuf<unsigned long long>& ctr;
+    DevBuf<unsigned long long>& pose_off;
+    DevBuf<uint32_t>& summary;
+    SortScratch& sort;
+    DevBuf<uint8_t>& slab;
+    PplColumns& col;
+    int64_t* counts;      // [4]
+    int64_t& launches;
+};
+struct PlaneSink { PlaneRec* rec; u64* key; u64* val; u64 cap; };
+int plane_records_launch(arp_ctx* c, const std::string& fn, PlaneRecords R, int64_t poses, int keybits, const char* kernel, const std::string& near_cause,
+                         const std::function<void(const PlaneSink&)>& enqueue, int64_t counts[4]) {
+    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
+    HIPCHK(c, R.ctr.reserve(8));
+    HIPCHK(c, R.summary.reserve((size_t)poses * PPL_SUMMARY));
+    HIPCHK(c, R.pose_off.reserve(4 * ((size_t)poses + 1)));
+    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+    const auto launch = [&](size_t cap) -> int {
+        CHK(reserve_key_sort(c, R.sort, cap, cap));
+        HIPCHK(c, R.rec.reserve(cap));
+        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 6 * sizeof(unsigned long long), c->stream));
+        enqueue(PlaneSink{R.rec.p, R.sort.key[0].p, R.sort.val[0].p, (u64)cap});
+        CHK(check_launch(c, kernel));
+        ++R.launches;
+        return ARP_OK;
+    };
+    const auto device_error = [&](int dev) -> int {
+        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
+        if (dev == PPL_E_NEAR) FAIL(c, ARP_E_ARG, fn + near_cause);
+        FAIL(c, ARP_E_HIP, fn + "device error");
+    };
+    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)poses * 64)), R.ctr.p, 6, h, 2, launch, device_error,
+                             nullptr));
+    const size_t k = (size_t)h[0];
+    if (h[2] + h[3] + h[4] + h[5] != h[0]) FAIL(c, ARP_E_HIP, fn + "the tables' record counts do not add up");
+    hipLaunchKernelGGL(k_poses_offsets, dim3(4), dim3(1024), 0, c->stream, (int)poses, 0, R.summary.p, R.pose_off.p);
+    // the four tables in one slab
+    const size_t m[4] = {(size_t)h[2], (size_t)h[3], (size_t)h[4], (size_t)h[5]};
+    size_t bytes = 0;
+    const PlaneLayout lay = plane_tables_layout(m, 0, &bytes);
+    HIPCHK(c, R.slab.reserve(std::max<size_t>(bytes, 256)));
+    PplColumns col = bind_plane_columns(R.slab.p, lay);
+    for (int t = 0; t < 4; ++t) col.base[t + 1] = col.base[t] + (long long)m[t];
+    if (k > 0) {
+        int sorted = 0;
+        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
+        hipLaunchKernelGGL(k_ppl_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, R.sort.val[sorted].p, R.rec.p, col);
+    }
+    CHK(check_launch(c, "k_poses_offsets / sort / k_ppl_columns"));
+    R.col = col;
+    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = (int64_t)h[2 + t];
+    return ARP_OK;
+}
 }  // namespace
 
 // ---- ligand poses on the resident receptor (arp_poses.h): every pose's ligand - receptor records in one launch
@@ -5965,16 +6076,12 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     const int64_t P = n_poses;
     // ---- from here on the previous result is gone, and what was made with it
     void_pose_results(c, POSE_PLANES);
-    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = 0;
     const int blocks = (int)std::min<int64_t>(P, PPL_MAX_BLOCKS);
     const int ws_rings = R.n_mring + R.n_hring + PPL_MAX_NEAR;
     HIPCHK(c, R.xyz.reserve((size_t)P * S * 3));
     HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)P * S * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, R.ws_ring.reserve((size_t)blocks * ws_rings));
     HIPCHK(c, R.ws_amide.reserve((size_t)blocks * std::max(R.n_mamide, 1)));
-    HIPCHK(c, R.ctr.reserve(8));
-    HIPCHK(c, R.summary.reserve((size_t)P * PPL_SUMMARY));
-    HIPCHK(c, R.pose_off.reserve(4 * ((size_t)P + 1)));
     PplArgs A{};
     A.n = n; A.S = S; A.P = (int)P; A.nring = (int)c->nring; A.namide = (int)c->namide;
     A.sel_list = c->sel_list.p; A.pos_of = R.pos_of.p; A.sel = c->sel.p; A.pxyz = R.xyz.p;
@@ -5989,46 +6096,15 @@ int arp_poses_planes_launch(arp_ctx* c, int64_t n_poses, const float* xyz, int64
     if (c->nring > 0) { A.gr = c->ring_grid.d; A.r_start = c->ring_grid.start.p; A.r_perm = c->ring_grid.perm.p; }
     if (c->namide > 0) { A.gm = c->amide_grid.d; A.m_start = c->amide_grid.start.p; A.m_perm = c->amide_grid.perm.p; }
     A.ws_ring = R.ws_ring.p; A.ws_amide = R.ws_amide.p; A.ws_rings = ws_rings;
-    A.ctr = R.ctr.p; A.summary = R.summary.p;
     A.idbits = index_bits(std::max({c->n, c->nring, c->namide})); A.pbits = index_bits(P);
-    const int keybits = 2 + A.pbits + 2 * A.idbits;
-    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
-    const auto launch = [&](size_t cap) -> int {
-        CHK(reserve_key_sort(c, R.sort, cap, cap));
-        HIPCHK(c, R.rec.reserve(cap));
-        A.rec = R.rec.p; A.key = R.sort.key[0].p; A.val = R.sort.val[0].p; A.cap = cap;
-        HIPCHK(c, hipMemsetAsync(R.ctr.p, 0, 6 * sizeof(unsigned long long), c->stream));
+    const auto enqueue = [&](const PlaneSink& sink) {
+        A.rec = sink.rec; A.key = sink.key; A.val = sink.val; A.cap = sink.cap; A.ctr = R.ctr.p; A.summary = R.summary.p;
         hipLaunchKernelGGL(k_poses_planes, dim3((unsigned)blocks), dim3(PPL_THREADS), 0, c->stream, A);
-        CHK(check_launch(c, "k_poses_planes"));
-        ++R.launches;
-        return ARP_OK;
     };
-    const auto device_error = [&](int dev) -> int {
-        if (dev == ARP_E_ARG) FAIL(c, ARP_E_ARG, fn + "non-finite pose coordinate");
-        if (dev == PPL_E_NEAR) FAIL(c, ARP_E_ARG, fn + "a pose brings more than ARP_POSES_PLANES_MAX_NEAR further rings within 3 A of a movable atom");
-        FAIL(c, ARP_E_HIP, fn + "device error");
-    };
-    CHK(append_until_it_fits(c, fn, std::min(POSE_RECORD_LIMIT, std::max<size_t>((size_t)1 << 16, (size_t)P * 64)), R.ctr.p, 6, h, 2, launch, device_error,
-                             nullptr));
-    const size_t k = (size_t)h[0];
-    if (h[2] + h[3] + h[4] + h[5] != h[0]) FAIL(c, ARP_E_HIP, fn + "the tables' record counts do not add up");
-    hipLaunchKernelGGL(k_poses_offsets, dim3(4), dim3(1024), 0, c->stream, (int)P, 0, R.summary.p, R.pose_off.p);
-    // the four tables in one slab
-    const size_t m[4] = {(size_t)h[2], (size_t)h[3], (size_t)h[4], (size_t)h[5]};
-    size_t bytes = 0;
-    const PlaneLayout lay = plane_tables_layout(m, 0, &bytes);
-    HIPCHK(c, R.slab.reserve(std::max<size_t>(bytes, 256)));
-    PplColumns col = bind_plane_columns(R.slab.p, lay);
-    for (int t = 0; t < 4; ++t) col.base[t + 1] = col.base[t] + (long long)m[t];
-    if (k > 0) {
-        int sorted = 0;
-        enqueue_key_sort(c, R.sort, k, keybits, &sorted);
-        hipLaunchKernelGGL(k_ppl_columns, dim3(nblocks((int64_t)k, 256, 1 << 16)), dim3(256), 0, c->stream, (long long)k, R.sort.val[sorted].p, R.rec.p, col);
-    }
-    CHK(check_launch(c, "k_poses_offsets / sort / k_ppl_columns"));
-    R.col = col;
+    CHK(plane_records_launch(c, fn, PlaneRecords{R.rec, R.ctr, R.pose_off, R.summary, R.sort, R.slab, R.col, R.counts, R.launches}, P,
+                             2 + A.pbits + 2 * A.idbits, "k_poses_planes", "a pose brings more than ARP_POSES_PLANES_MAX_NEAR further rings within 3 A of a movable atom",
+                             enqueue, counts));
     R.P = P; R.S = S; R.valid = true;
-    for (int t = 0; t < 4; ++t) R.counts[t] = counts[t] = (int64_t)h[2 + t];
     return ARP_OK;
 }
 
@@ -6065,6 +6141,189 @@ int arp_poses_planes_info(arp_ctx* c, int64_t info[12]) {
     info[9] = R.have_atoms ? 1 : 0;
     info[10] = R.launches;
     info[11] = 0;
+    return ARP_OK;
+}
+
+// ---- a ligand library on the resident receptor, ring and amide contacts (arp_library_planes.h)
+// No bag is read and none is written, and no selection.  The receptor's resident centres, normals and residues, the two centre
+// grids and an all-atom grid of this result's own (by local id, for the reason of arp_poses_planes_launch) are read beside the
+// library and its plane table; records are appended unsorted with a key, sorted by every bit of it and gathered into four
+// tables.  One wait a launch: the counters (records, error word, records per table).
+static_assert(LPL_MAX_RINGS == ARP_LIBRARY_PLANES_MAX_RINGS && LPL_MAX_AMIDES == ARP_LIBRARY_PLANES_MAX_AMIDES, "arp_library_planes.h names the header's limits");
+
+int arp_set_ligand_library_planes(arp_ctx* c, const int32_t* ring_off, const int32_t* ring_atom_off, const int32_t* ring_atom_idx,
+                                  const int32_t* amide_off, const int32_t* amide_atoms) {
+    if (!c) return ARP_E_ARG;
+    const std::string fn = "arp_set_ligand_library_planes: ";
+    // ---- the refusals, in this order: none of them touches the resident table or a result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    const LigandLibrary& B = c->library;
+    if (!B.resident) FAIL(c, ARP_E_ARG, fn + "no ligand library (arp_set_ligand_library)");
+    const int64_t L = B.L;
+    if (!ring_off || !ring_atom_off || !amide_off || (ring_off[L] > 0 && !ring_atom_idx) || (amide_off[L] > 0 && !amide_atoms))
+        FAIL(c, ARP_E_ARG, fn + "an array is missing");
+    if (!csr_ok(ring_off, L)) FAIL(c, ARP_E_ARG, fn + "ring_off must start at 0 and never decrease");
+    const int64_t TR = ring_off[L];
+    if (!csr_ok(ring_atom_off, TR)) FAIL(c, ARP_E_ARG, fn + "ring_atom_off must start at 0 and never decrease");
+    if (!csr_ok(amide_off, L)) FAIL(c, ARP_E_ARG, fn + "amide_off must start at 0 and never decrease");
+    const int64_t TM = amide_off[L];
+    for (int64_t l = 0; l < L; ++l) {
+        if (ring_off[l + 1] - ring_off[l] > LPL_MAX_RINGS) FAIL(c, ARP_E_ARG, fn + "a ligand has more than ARP_LIBRARY_PLANES_MAX_RINGS rings");
+        if (amide_off[l + 1] - amide_off[l] > LPL_MAX_AMIDES) FAIL(c, ARP_E_ARG, fn + "a ligand has more than ARP_LIBRARY_PLANES_MAX_AMIDES amides");
+    }
+    for (int64_t r = 0; r < TR; ++r)
+        if (ring_atom_off[r + 1] - ring_atom_off[r] < 3) FAIL(c, ARP_E_ARG, fn + "a ring needs at least three atoms");
+    for (int64_t l = 0; l < L; ++l) {
+        const int S = B.host_atom_off[(size_t)l + 1] - B.host_atom_off[(size_t)l];
+        for (int64_t k = ring_atom_off[ring_off[l]]; k < ring_atom_off[ring_off[l + 1]]; ++k)
+            if (ring_atom_idx[k] < 0 || ring_atom_idx[k] >= S) FAIL(c, ARP_E_ARG, fn + "ring atom index outside its own ligand");
+        for (int64_t k = 4 * (int64_t)amide_off[l]; k < 4 * (int64_t)amide_off[l + 1]; ++k)
+            if ((k & 3) != 3 && (amide_atoms[k] < 0 || amide_atoms[k] >= S)) FAIL(c, ARP_E_ARG, fn + "amide atom index outside its own ligand");
+    }
+    // ---- from here on the table before is gone, and its result
+    HIPCHK(c, hipSetDevice(c->device));
+    void_pose_results(c, POSE_LIBRARY_PLANE_ATOMS);
+    LibraryPlaneAtoms& P = c->libplanes;
+    const int32_t zero[4] = {0, 0, 0, 0};
+    const size_t nidx = (size_t)ring_atom_off[TR];
+    CHK(upload_async(c, P.ring_off, ring_off, (size_t)L + 1));
+    CHK(upload_async(c, P.ring_atom_off, ring_atom_off, (size_t)TR + 1));
+    CHK(upload_async(c, P.ring_atom_idx, nidx > 0 ? ring_atom_idx : zero, std::max<size_t>(nidx, 1)));
+    CHK(upload_async(c, P.amide_off, amide_off, (size_t)L + 1));
+    CHK(upload(c, P.amide_atoms, TM > 0 ? amide_atoms : zero, std::max<size_t>(4 * (size_t)TM, 4)));      // (waits: the caller's arrays are free after this)
+    P.L = L; P.TR = TR; P.TM = TM; P.resident = true;
+    return ARP_OK;
+}
+
+static int library_planes_setup(arp_ctx* c) {
+    LibraryPlanesResult& R = c->libpl;
+    const int n = (int)c->n;
+    const int nres = (int)std::max<int64_t>(c->nres, 1);
+    HIPCHK(c, R.hist.reserve(scan_padded(nres)));
+    HIPCHK(c, R.res_off.reserve(scan_padded(nres)));
+    HIPCHK(c, R.res_atoms.reserve((size_t)n));
+    HIPCHK(c, hipMemsetAsync(R.hist.p, 0, R.hist.cap * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_lpl_hist, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->res_id.p, R.hist.p);
+    CHK(check_launch(c, "k_lpl_hist"));
+    // residue -> atoms: the scan and the scatter of the point grids (the histogram is counted down to zero again)
+    CHK(enqueue_scan(c, c->stream, R.hist.p, nres, R.res_off.p, R.sums));
+    hipLaunchKernelGGL(k_scatter, dim3(nblocks(n, 256)), dim3(256), 0, c->stream, n, c->res_id.p, R.res_off.p, R.hist.p, R.res_atoms.p);
+    CHK(check_launch(c, "k_scatter (residue atoms)"));
+    // the all-atom grid of this result, cell edge 6 A, entries = local ids
+    CHK(build_grid<PtsF4>(c, R.grid, PtsF4{c->xyz.p}, n, c->lo, c->hi, 6.0, nullptr));
+    R.setup = true;
+    return ARP_OK;
+}
+
+int arp_library_planes_launch(arp_ctx* c, const int64_t* pose_off, const float* xyz, int64_t counts[4]) {
+    if (!c || !counts) return ARP_E_ARG;
+    const std::string fn = "arp_library_planes_launch: ";
+    // ---- the refusals, in this order: none of them touches a resident result
+    CHK(receptor_refusals(c, fn));
+    if (c->n + LIB_MAX_ATOMS >= POSES_MAX_N || c->nring + LPL_MAX_RINGS >= POSES_MAX_N || c->namide + LPL_MAX_AMIDES >= POSES_MAX_N)
+        FAIL(c, ARP_E_ARG, fn + "2^21 atoms, rings or amides of the complex, or more (the sort key holds 21 bits per id)");
+    const LigandLibrary& B = c->library;
+    if (!B.resident) FAIL(c, ARP_E_ARG, fn + "no ligand library (arp_set_ligand_library)");
+    const LibraryPlaneAtoms& PA = c->libplanes;
+    if (!PA.resident) FAIL(c, ARP_E_ARG, fn + "no library plane table (arp_set_ligand_library_planes after the library)");
+    if (!pose_off) FAIL(c, ARP_E_ARG, fn + "pose_off missing");
+    const int64_t L = B.L;
+    if (pose_off[0] != 0) FAIL(c, ARP_E_ARG, fn + "pose_off must start at 0");
+    for (int64_t l = 0; l < L; ++l)
+        if (pose_off[l + 1] < pose_off[l]) FAIL(c, ARP_E_ARG, fn + "pose_off must not decrease");
+    const int64_t T = pose_off[L];
+    if (T < 1 || T > POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "1 ... ARP_POSES_MAX_POSES poses a launch (chunk them)");
+    if (!xyz) FAIL(c, ARP_E_ARG, fn + "xyz missing");
+    // (the ligand's residue is the receptor's residue count: without a residue table it would coincide with residue 0 of the atoms)
+    if (c->nres < 1) FAIL(c, ARP_E_ARG, fn + "no residue table resident (arp_set_residues): the ligand is one more residue behind the receptor's");
+    CHK(check_residue_ranges(c));
+    // where every ligand's poses begin in the coordinate array (ligand-major, then pose-major), and the ligand of every pose
+    std::vector<long long> tab(2 * (size_t)L + 1);
+    std::vector<int> lig_of((size_t)T);
+    long long nx = 0;
+    for (int64_t l = 0; l < L; ++l) {
+        const long long P = pose_off[l + 1] - pose_off[l], S = B.host_atom_off[(size_t)l + 1] - B.host_atom_off[(size_t)l];
+        tab[(size_t)l] = pose_off[l];
+        tab[(size_t)(L + 1 + l)] = nx;
+        nx += P * S * 3;
+        std::fill(lig_of.begin() + pose_off[l], lig_of.begin() + pose_off[l + 1], (int)l);
+    }
+    tab[(size_t)L] = T;
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(join_upload_lists(c));
+    CHK(ensure_static(c));               // (radius 0: the order in place stays, only missing columns are made)
+    CHK(ensure_center_grids(c));
+    LibraryPlanesResult& R = c->libpl;
+    if (!R.setup) CHK(library_planes_setup(c));
+    // ---- from here on the previous result is gone
+    void_pose_results(c, POSE_LIBRARY_PLANES);
+    const int blocks = (int)std::min<int64_t>(T, (int64_t)LIB_BLOCKS_PER_CU * std::max(c->num_cu, 1));
+    CHK(upload_async(c, R.tab, tab.data(), tab.size()));
+    CHK(upload_async(c, R.lig_of, lig_of.data(), lig_of.size()));
+    HIPCHK(c, R.xyz.reserve(std::max<size_t>((size_t)nx, 1)));
+    HIPCHK(c, hipMemcpyAsync(R.xyz.p, xyz, (size_t)nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, R.ws_ring.reserve((size_t)blocks * LPL_WS_RINGS));
+    HIPCHK(c, R.ws_amide.reserve((size_t)blocks * LPL_MAX_AMIDES));
+    LplArgs A{};
+    A.n = (int)c->n; A.T = (int)T; A.nring = (int)c->nring; A.namide = (int)c->namide; A.nres = (int)c->nres;
+    A.atom_off = B.atom_off.p; A.tmask = B.tmask.p; A.flags = B.flags.p; A.lh_off = B.h_off.p; A.lsb_nbr = B.sb_nbr.p;
+    A.lring_off = PA.ring_off.p; A.lring_atom_off = PA.ring_atom_off.p; A.lring_atom_idx = PA.ring_atom_idx.p;
+    A.lamide_off = PA.amide_off.p; A.lamide_atoms = PA.amide_atoms.p;
+    A.lig_of = R.lig_of.p; A.first_pose = R.tab.p; A.xyz_at = R.tab.p + L + 1; A.pxyz = R.xyz.p;
+    A.res_off = R.res_off.p; A.res_atoms = R.res_atoms.p;
+    A.xyz = c->xyz.p; A.st_xyzm = c->st_xyzm.p; A.res_id = c->res_id.p;
+    A.ring_c = c->ring_c.p; A.ring_n = c->ring_n.p; A.ring_res = c->ring_res.p;
+    A.am_c = c->am_c.p; A.am_n = c->am_n.p; A.am_res = c->am_res.p;
+    A.ga = R.grid.d; A.a_start = R.grid.start.p; A.a_perm = R.grid.perm.p;
+    if (c->nring > 0) { A.gr = c->ring_grid.d; A.r_start = c->ring_grid.start.p; A.r_perm = c->ring_grid.perm.p; }
+    if (c->namide > 0) { A.gm = c->amide_grid.d; A.m_start = c->amide_grid.start.p; A.m_perm = c->amide_grid.perm.p; }
+    A.ws_ring = R.ws_ring.p; A.ws_amide = R.ws_amide.p;
+    A.idbits = index_bits(std::max({c->n + LIB_MAX_ATOMS, c->nring + LPL_MAX_RINGS, c->namide + LPL_MAX_AMIDES})); A.pbits = index_bits(T);
+    const auto enqueue = [&](const PlaneSink& sink) {
+        A.rec = sink.rec; A.key = sink.key; A.val = sink.val; A.cap = sink.cap; A.ctr = R.ctr.p; A.summary = R.summary.p;
+        hipLaunchKernelGGL(k_library_planes, dim3((unsigned)blocks), dim3(LPL_THREADS), 0, c->stream, A);
+    };
+    CHK(plane_records_launch(c, fn, PlaneRecords{R.rec, R.ctr, R.pose_off, R.summary, R.sort, R.slab, R.col, R.counts, R.launches}, T,
+                             2 + A.pbits + 2 * A.idbits, "k_library_planes", "a pose brings more than ARP_POSES_PLANES_MAX_NEAR receptor rings within 3 A of a ligand atom",
+                             enqueue, counts));
+    R.L = L; R.T = T; R.blocks = blocks; R.valid = true;
+    return ARP_OK;
+}
+
+int arp_library_planes_fetch(arp_ctx* c, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0, void* v1, void* v2,
+                             void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const LibraryPlanesResult& R = c->libpl;
+    if (!R.valid) FAIL(c, ARP_E_ARG, "arp_library_planes_fetch: no result (arp_library_planes_launch; the structure, the library or its plane table changed since)");
+    if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_library_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
+    const int t = table;
+    *count = R.counts[t];
+    void* const v[4] = {v0, v1, v2, v3};
+    uint8_t* const u[3] = {u0, u1, u2};
+    bool records = false;
+    CHK(plane_fetch_columns(c, "arp_library_planes_fetch: ", t, first, second, v, u, &records));
+    if (records && R.counts[t] > cap) FAIL(c, ARP_E_CAPACITY, "arp_library_planes_fetch: output buffers too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, pose_off, R.pose_off.p + (size_t)t * ((size_t)R.T + 1), ((size_t)R.T + 1) * sizeof(unsigned long long));
+    want_piece(pieces, summary, R.summary.p, (size_t)R.T * PPL_SUMMARY * sizeof(uint32_t));
+    if (records) plane_fetch_pieces(pieces, R.col, t, (size_t)R.counts[t], first, second, v, u);
+    return stage_fetch(c, pieces);
+}
+
+int arp_library_planes_info(arp_ctx* c, int64_t info[12]) {
+    if (!c || !info) return ARP_E_ARG;
+    const LibraryPlaneAtoms& P = c->libplanes;
+    const LibraryPlanesResult& R = c->libpl;
+    info[0] = P.resident ? P.L : 0;
+    info[1] = P.resident ? P.TR : 0;
+    info[2] = P.resident ? P.TM : 0;
+    info[3] = R.valid ? R.T : 0;
+    for (int t = 0; t < 4; ++t) info[4 + t] = R.valid ? R.counts[t] : 0;
+    info[8] = R.valid ? R.blocks : 0;
+    info[9] = R.launches;
+    info[10] = P.resident ? 1 : 0;
+    info[11] = R.setup ? 1 : 0;
     return ARP_OK;
 }
 

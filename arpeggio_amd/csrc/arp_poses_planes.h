@@ -170,19 +170,20 @@ __device__ __forceinline__ num::f3 ppl_coord(const PplArgs& A, const float* px, 
     return {v.x, v.y, v.z};
 }
 
-// k_ring_geometry's operation sequence over the pose's coordinates
-__device__ __forceinline__ void ppl_ring_geometry(const PplArgs& A, const float* px, int r, double* c, double* nrm) {
-    const int a0 = A.ring_off[r], na = A.ring_off[r + 1] - a0;
+// k_ring_geometry's operation sequence over a pose's coordinates: `at(k)` is the pose's coordinate of the atom that the path names k
+// (k_poses_planes: a local id; k_library_planes: an index within the ligand)
+template <class Coord>
+__device__ __forceinline__ void ppl_ring_geometry_of(const Coord& at, const int* idx, int na, double* c, double* nrm) {
     double cx = 0, cy = 0, cz = 0;
     for (int j = 0; j < na; ++j) {
-        const num::f3 v = ppl_coord(A, px, A.ring_idx[a0 + j]);
+        const num::f3 v = at(idx[j]);
         cx += (double)v.x; cy += (double)v.y; cz += (double)v.z;
     }
     const double inv_n = 1.0 / (double)na;
     cx *= inv_n; cy *= inv_n; cz *= inv_n;
     double nx = 0, ny = 0, nz = 0;
     for (int j = 0; j < na; ++j) {
-        const num::f3 p = ppl_coord(A, px, A.ring_idx[a0 + j]), q = ppl_coord(A, px, A.ring_idx[a0 + ((j + 1 == na) ? 0 : j + 1)]);
+        const num::f3 p = at(idx[j]), q = at(idx[(j + 1 == na) ? 0 : j + 1]);
         const double ax = (double)p.x - cx, ay = (double)p.y - cy, az = (double)p.z - cz;
         const double bx = (double)q.x - cx, by = (double)q.y - cy, bz = (double)q.z - cz;
         nx += ay * bz - az * by;
@@ -198,10 +199,15 @@ __device__ __forceinline__ void ppl_ring_geometry(const PplArgs& A, const float*
     c[0] = cx; c[1] = cy; c[2] = cz;
     nrm[0] = nx; nrm[1] = ny; nrm[2] = nz;
 }
+__device__ __forceinline__ void ppl_ring_geometry(const PplArgs& A, const float* px, int r, double* c, double* nrm) {
+    const int a0 = A.ring_off[r];
+    ppl_ring_geometry_of([&](int lid) { return ppl_coord(A, px, lid); }, A.ring_idx + a0, A.ring_off[r + 1] - a0, c, nrm);
+}
 
-// k_amide_geometry's
-__device__ __forceinline__ void ppl_amide_geometry(const PplArgs& A, const float* px, int a, float* c, float* nrm) {
-    const num::f3 N = ppl_coord(A, px, A.amide_atoms[4 * a]), Cc = ppl_coord(A, px, A.amide_atoms[4 * a + 1]), O = ppl_coord(A, px, A.amide_atoms[4 * a + 2]);
+// k_amide_geometry's, over the amide's N, C, O (atoms[0 .. 2])
+template <class Coord>
+__device__ __forceinline__ void ppl_amide_geometry_of(const Coord& at, const int* atoms, float* c, float* nrm) {
+    const num::f3 N = at(atoms[0]), Cc = at(atoms[1]), O = at(atoms[2]);
     c[0] = (Cc.x + N.x) / 2.0f;
     c[1] = (Cc.y + N.y) / 2.0f;
     c[2] = (Cc.z + N.z) / 2.0f;
@@ -212,6 +218,9 @@ __device__ __forceinline__ void ppl_amide_geometry(const PplArgs& A, const float
     const double l = sqrt(nx * nx + ny * ny + nz * nz);
     if (l > 0) { nx /= l; ny /= l; nz /= l; }
     nrm[0] = (float)nx; nrm[1] = (float)ny; nrm[2] = (float)nz;
+}
+__device__ __forceinline__ void ppl_amide_geometry(const PplArgs& A, const float* px, int a, float* c, float* nrm) {
+    ppl_amide_geometry_of([&](int lid) { return ppl_coord(A, px, lid); }, A.amide_atoms + 4 * a, c, nrm);
 }
 
 // an unselected atom at x: within 6.0 A (inclusive, float64) of a movable atom's pose coordinate
@@ -302,11 +311,39 @@ __device__ __forceinline__ PplAmideV ppl_amide(const PplArgs& A, const PplAmide*
     return G;
 }
 
+// How k_poses_planes reads the operands of phase 2: a reference < 0 names entry -ref - 1 of the pose's lists (a movable atom: of
+// sel_list), one >= 0 a resident id.  k_library_planes (arp_library_planes.h) reads the same decisions through a reader of its own.
+// A reader gives ring(ref), amide(ref), atom(ref, ...) and, as `A`, the record sink: rec, key, val, cap, ctr, idbits, pbits.
+struct PplReader {
+    const PplArgs& A;
+    const PplRing* wsr;
+    const PplAmide* wsa;
+    const float* px;
+    __device__ __forceinline__ PplRingV ring(int ref) const { return ppl_ring(A, wsr, px, ref); }
+    __device__ __forceinline__ PplAmideV amide(int ref) const { return ppl_amide(A, wsa, px, ref); }
+    // atom `ref`: its id, coordinate and meta word in the pose, and whether it is in the pose's selection_plus
+    __device__ __forceinline__ void atom(int ref, int* lid, num::d3* x, uint32_t* m, bool* plus) const {
+        if (ref < 0) {
+            const int s = -ref - 1;
+            *lid = A.sel_list[s];
+            *x = {(double)px[3 * s], (double)px[3 * s + 1], (double)px[3 * s + 2]};
+            *m = __float_as_uint(A.st_xyzm[*lid].w) | M_SEL;
+        } else {
+            *lid = ref;
+            const float4 v = A.st_xyzm[ref];
+            *x = {(double)v.x, (double)v.y, (double)v.z};
+            *m = __float_as_uint(v.w) & ~(uint32_t)M_SEL;
+            *plus = ppl_atom_plus(A, px, *x);
+        }
+    }
+};
+
 // Phase 2: one candidate per lane, e = {table, first reference, second reference}.  The decisions and the arithmetic are those of
-// ap_eval, pp_eval, gg_eval and gp_eval (arp_planes.h), expression by expression.
-__device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const PplRing* wsr, const PplAmide* wsa, int pose, bool live, int4 e,
-                                         int lane) {
-    const float* px = sh->px;
+// ap_eval, pp_eval, gg_eval and gp_eval (arp_planes.h), expression by expression: the ONE text for the poses of one ligand and
+// for a ligand library.  `sum`: the block's summary row in LDS.
+template <class Reader>
+__device__ __forceinline__ void ppl_eval(const Reader& rd, uint32_t* sum, int pose, bool live, int4 e, int lane) {
+    const auto& A = rd.A;
     const int kind = e.x;
     bool emit = false;
     PlaneRec rec;
@@ -315,23 +352,12 @@ __device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const 
     int k0 = 0, k1 = 0;         // the two ids of the sort key
     int ct = 0;
     if (live && kind == 0) {                 // ring e.y, atom e.z
-        const PplRingV R = ppl_ring(A, wsr, px, e.y);
+        const PplRingV R = rd.ring(e.y);
         int lid;
         num::d3 x;
         uint32_t m;
         bool plus = true;
-        if (e.z < 0) {
-            const int s = -e.z - 1;
-            lid = A.sel_list[s];
-            x = {(double)px[3 * s], (double)px[3 * s + 1], (double)px[3 * s + 2]};
-            m = __float_as_uint(A.st_xyzm[lid].w) | M_SEL;
-        } else {
-            lid = e.z;
-            const float4 v = A.st_xyzm[lid];
-            x = {(double)v.x, (double)v.y, (double)v.z};
-            m = __float_as_uint(v.w) & ~(uint32_t)M_SEL;
-            plus = ppl_atom_plus(A, px, x);
-        }
+        rd.atom(e.z, &lid, &x, &m, &plus);
         if (R.plus && plus) {
             const double dist = num::norm(num::sub(x, R.c));
             ct = plane_ctype(R.sel, (m & M_SEL) != 0, true, true);
@@ -354,7 +380,7 @@ __device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const 
             k0 = R.id; k1 = lid;
         }
     } else if (live && kind == 1) {          // two rings
-        PplRingV Ra = ppl_ring(A, wsr, px, e.y), Rb = ppl_ring(A, wsr, px, e.z);
+        PplRingV Ra = rd.ring(e.y), Rb = rd.ring(e.z);
         if (Ra.id > Rb.id) { const PplRingV t = Ra; Ra = Rb; Rb = t; }
         if (Ra.plus && Rb.plus) {
             const num::d3 pab = num::sub(Ra.c, Rb.c);
@@ -389,7 +415,7 @@ __device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const 
             }
         }
     } else if (live && kind == 2) {          // ordered pair of amides
-        const PplAmideV Ga = ppl_amide(A, wsa, px, e.y), Gb = ppl_amide(A, wsa, px, e.z);
+        const PplAmideV Ga = rd.amide(e.y), Gb = rd.amide(e.z);
         if (Ga.plus && Gb.plus) {
             const num::f3 pab = num::sub(Ga.c, Gb.c);
             const float dist = num::norm(pab);
@@ -407,8 +433,8 @@ __device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const 
             }
         }
     } else if (live && kind == 3) {          // amide e.y, ring e.z
-        const PplAmideV G = ppl_amide(A, wsa, px, e.y);
-        const PplRingV R = ppl_ring(A, wsr, px, e.z);
+        const PplAmideV G = rd.amide(e.y);
+        const PplRingV R = rd.ring(e.z);
         if (G.plus && R.plus) {
             const num::d3 cad = num::to_d3(G.c);
             const num::d3 par = num::sub(cad, R.c);
@@ -456,7 +482,7 @@ __device__ __forceinline__ void ppl_eval(const PplArgs& A, PplShared* sh, const 
     if (lane == 0) {
 #pragma unroll
         for (int b = 0; b < PPL_SUMMARY; ++b)
-            if (add[b]) atomicAdd(&sh->sum[b], add[b]);
+            if (add[b]) atomicAdd(&sum[b], add[b]);
     }
 }
 
@@ -602,6 +628,7 @@ __global__ __launch_bounds__(PPL_THREADS) void k_poses_planes(PplArgs A) {
         // ---- the four loops: a wave per home item, candidates to the wave's queue, 64 at a time through phase 2
         int4* const q = sh->q[w];
         int qn = 0;
+        const PplReader reader{A, wsr, wsa, px};
         auto push = [&](bool ok, int kind, int x, int y) {
             const unsigned long long m = __ballot(ok);
             if (!m) return;
@@ -612,7 +639,7 @@ __global__ __launch_bounds__(PPL_THREADS) void k_poses_planes(PplArgs A) {
                 qn -= 64;
                 const int4 e = q[qn + lane];
                 __builtin_amdgcn_wave_barrier();
-                ppl_eval(A, sh, wsr, wsa, pose, true, e, lane);
+                ppl_eval(reader, sh->sum, pose, true, e, lane);
             }
         };
         const int items = nAff + A.S + A.n_mamide;
@@ -750,7 +777,7 @@ __global__ __launch_bounds__(PPL_THREADS) void k_poses_planes(PplArgs A) {
         if (qn > 0) {       // (wave-uniform)
             const bool live = lane < qn;
             const int4 e = live ? q[lane] : make_int4(-1, 0, 0, 0);
-            ppl_eval(A, sh, wsr, wsa, pose, live, e, lane);
+            ppl_eval(reader, sh->sum, pose, live, e, lane);
             qn = 0;
         }
         __syncthreads();

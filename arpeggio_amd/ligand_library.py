@@ -5,8 +5,9 @@ with a few poses, against one receptor.  The receptor is resident alone; the lig
 (``pack``), and one launch walks every (ligand, pose).
 
 A ligand is a ``PackedComplex`` of ONE residue that is no polypeptide residue and has no sequence neighbours (peptide ligands
-and covalent ligands are out of scope); only its atoms, hydrogens and single-bond neighbours are read, its rings and amides are
-not (the plane tables of a library are out of scope).
+and covalent ligands are out of scope).  ``library_contacts`` reads its atoms, hydrogens and single-bond neighbours;
+``library_planes`` reads the atoms of its rings and amides as well (``ring_atoms`` in ring-path order, ``amide_atoms``), never
+their geometry: that is made per pose.
 
 A library (``pack``) is a dict:
 
@@ -15,6 +16,16 @@ A library (``pack``) is a dict:
     h_off      int32 [TA + 1]   the hydrogen rows of every library atom, CSR over all of them
     sb_nbr     int32 [TA]       the index WITHIN ITS LIGAND of the single-bond heavy neighbour, -1: none
     ligands    the packs it was made from (labels for ``to_records`` / ``write_csv``)
+
+and the plane table of ``Context.set_ligand_library_planes`` (indices WITHIN THE LIGAND; empty ranges for a ligand without):
+
+    ring_off       int32 [L + 1]    CSR over the ligands: rings ring_off[l] ... ring_off[l + 1] - 1 are ligand l's, TR in all
+    ring_atom_off  int32 [TR + 1];  ring_atom_idx  int32, every ring in ring-path order
+    amide_off      int32 [L + 1];   amide_atoms    int32 [TM, 4]: N, C, O, C-alpha (the fourth is not read, may be -1)
+
+A planes result (``Context.library_planes``) is a dict with one sub-table per ring / amide bag — the columns ``Context.fetch_bag``
+gives that bag plus ``pose_off`` uint64 [T + 1] —, ``summary`` uint32 [T, 16] (``poses.PLANE_SUMMARY_SLOTS``) and
+``ligand_pose_off``.  Its ids are those of the complex (``complex_of``): ligand atom n + a, ring n_rings + q, amide n_amides + g.
 
 A result (``table``) is a dict:
 
@@ -34,6 +45,7 @@ import numpy as np
 
 from .core import config
 from .core.packed import PackedComplex
+from . import poses as _poses
 from .poses import N_BITS, SUMMARY, join_poses, n_poses, pose_of, summarise      # (a library result is read as a poses result is)
 
 MAX_LIGANDS = 1 << 16
@@ -43,6 +55,9 @@ INT64_MIN = -(1 << 63)
 COLUMNS = ('i', 'a', 'dist', 'sift', 'ctype')
 DTYPES = dict(i=np.int32, a=np.int32, dist=np.float32, sift=np.uint16, ctype=np.uint8)
 ARRAYS = ('atom_off', 'type_mask', 'flags', 'vdw', 'cov', 'h_off', 'sb_nbr')
+PLANE_ARRAYS = ('ring_off', 'ring_atom_off', 'ring_atom_idx', 'amide_off', 'amide_atoms')
+PLANES_MAX_RINGS = 32            # ARP_LIBRARY_PLANES_MAX_RINGS: rings of one ligand
+PLANES_MAX_AMIDES = 32           # ARP_LIBRARY_PLANES_MAX_AMIDES
 
 
 def validate(lib):
@@ -76,10 +91,48 @@ def validate(lib):
     return lib
 
 
+def validate_planes(lib):
+    """What arp_set_ligand_library_planes refuses, in its order and with its causes, checked on the host (ValueError)."""
+    L = len(np.asarray(lib['atom_off'])) - 1
+    for k in PLANE_ARRAYS:
+        if lib.get(k) is None:
+            raise ValueError(f'library planes: an array is missing ({k})')
+    ro, rao, ao = (np.asarray(lib[k], np.int64) for k in ('ring_off', 'ring_atom_off', 'amide_off'))
+    for k, off, n in (('ring_off', ro, L), ('ring_atom_off', rao, int(ro[-1]) if ro.shape == (L + 1,) and (np.diff(ro) >= 0).all() else None),
+                      ('amide_off', ao, L)):
+        if n is None or off.shape != (n + 1,) or off[0] != 0 or (np.diff(off) < 0).any():
+            raise ValueError(f'library planes: {k} must start at 0 and never decrease (one entry per ' + ('ring' if k == 'ring_atom_off' else 'ligand') + ', and the total)')
+    idx, am = np.asarray(lib['ring_atom_idx'], np.int64), np.asarray(lib['amide_atoms'], np.int64).reshape(-1, 4)
+    if idx.shape != (int(rao[-1]),) or len(am) != int(ao[-1]):
+        raise ValueError('library planes: ring_atom_idx must hold ring_atom_off[-1] entries and amide_atoms amide_off[-1] rows of 4')
+    if (np.diff(ro) > PLANES_MAX_RINGS).any():
+        raise ValueError('library planes: a ligand has more than PLANES_MAX_RINGS rings')
+    if (np.diff(ao) > PLANES_MAX_AMIDES).any():
+        raise ValueError('library planes: a ligand has more than PLANES_MAX_AMIDES amides')
+    if (np.diff(rao) < 3).any():
+        raise ValueError('library planes: a ring needs at least three atoms')
+    S = np.diff(np.asarray(lib['atom_off'], np.int64))
+    s_idx = np.repeat(np.repeat(S, np.diff(ro)), np.diff(rao))
+    if ((idx < 0) | (idx >= s_idx)).any():
+        raise ValueError('library planes: ring atom index outside its own ligand')
+    s_am = np.repeat(S, np.diff(ao))[:, None]
+    if len(am) and ((am[:, :3] < 0) | (am[:, :3] >= s_am)).any():
+        raise ValueError('library planes: amide atom index outside its own ligand')
+    return lib
+
+
+def _plane_atoms(pc):
+    """``(ring paths, amide rows [A, 4])`` of a ligand pack: the rings it names atoms for, the amides whose N, C and O it names."""
+    rings = [np.asarray(a, np.int32).reshape(-1) for a in (pc.ring_atoms or [])]
+    am = np.asarray(pc.amide_atoms, np.int32).reshape(-1, 4)
+    return rings, am[(am[:, :3] >= 0).all(axis=1)]
+
+
 def pack(ligands):
-    """The library arrays of ``ligands`` (PackedComplex each).  Refused (ValueError, the cause named): no ligand or too many; a
+    """The library arrays of ``ligands`` (PackedComplex each), with the plane table made from the packs' ``ring_atoms`` and
+    ``amide_atoms`` (a pack without them gives empty ranges).  Refused (ValueError, the cause named): no ligand or too many; a
     pack with more than one residue; a polypeptide residue or one with sequence neighbours; a ligand with no atom or more than
-    ``MAX_ATOMS``; and what ``validate`` refuses."""
+    ``MAX_ATOMS``; and what ``validate`` and ``validate_planes`` refuse."""
     ligands = list(ligands)
     if not 1 <= len(ligands) <= MAX_LIGANDS:
         raise ValueError('ligand library: 1 ... MAX_LIGANDS ligands')
@@ -100,7 +153,14 @@ def pack(ligands):
                h_off=np.concatenate([[0], np.cumsum(hcnt)]).astype(np.int32),
                sb_nbr=np.concatenate([pc.sb_nbr for pc in ligands]).astype(np.int32),
                ligands=ligands)
-    return validate(lib)
+    planes = [_plane_atoms(pc) for pc in ligands]
+    rings = [a for r, _ in planes for a in r]
+    lib.update(ring_off=np.concatenate([[0], np.cumsum([len(r) for r, _ in planes])]).astype(np.int32),
+               ring_atom_off=np.concatenate([[0], np.cumsum([len(a) for a in rings])]).astype(np.int32),
+               ring_atom_idx=(np.concatenate(rings) if rings else np.zeros(0)).astype(np.int32),
+               amide_off=np.concatenate([[0], np.cumsum([len(a) for _, a in planes])]).astype(np.int32),
+               amide_atoms=np.concatenate([a for _, a in planes]).astype(np.int32).reshape(-1, 4))
+    return validate_planes(validate(lib))
 
 
 def n_ligands(lib):
@@ -113,9 +173,30 @@ def sizes(lib):
     return np.diff(off), h[off[1:]] - h[off[:-1]]
 
 
-def from_residue(pc, r):
+def host_plane_geometry(xyz, ring_atoms, amide_atoms):
+    """Ring centres and unit normals (float64) and amide centres and normals (float32) of ``xyz`` in NumPy, by the formulas of
+    the geometry kernels: what a ligand pack carries so that it is a consistent pack.  No result depends on these values — the
+    device makes a pose's geometry itself."""
+    x = np.asarray(xyz, np.float32).astype(np.float64)
+    rc, rn = np.zeros((len(ring_atoms), 3)), np.zeros((len(ring_atoms), 3))
+    for k, a in enumerate(ring_atoms):
+        p = x[np.asarray(a, np.int64)]
+        rc[k] = p.mean(axis=0)
+        v = np.cross(p - rc[k], np.roll(p, -1, axis=0) - rc[k]).sum(axis=0) / len(p)
+        rn[k] = v / np.linalg.norm(v) if np.linalg.norm(v) >= 2e-6 else v
+    am = np.asarray(amide_atoms, np.int64).reshape(-1, 4)
+    N, Cc, O = x[am[:, 0]], x[am[:, 1]], x[am[:, 2]]
+    m = (Cc + O + N) / 3.0
+    v = np.cross(Cc - m, O - m)
+    l = np.linalg.norm(v, axis=1, keepdims=True)
+    return rc, rn, ((Cc + N) / 2.0).astype(np.float32), np.where(l > 0, v / np.where(l > 0, l, 1.0), v).astype(np.float32)
+
+
+def from_residue(pc, r, planes=False):
     """Residue ``r`` of ``pc`` cut out as a ligand: its atoms in packed order with their hydrogens, bonds and single-bond
-    neighbours re-indexed, its labels, no rings and no amides.  Refused when the residue has a bond to another residue."""
+    neighbours re-indexed, its labels.  Refused when the residue has a bond to another residue.  ``planes``: keep the residue's
+    rings and amides (``ring_atoms`` / ``amide_atoms`` re-indexed, their geometry taken over); refused when a ring or an amide
+    (its N, C or O) shares atoms with another residue.  Without it: no rings and no amides."""
     idx = np.nonzero(np.asarray(pc.res_id) == r)[0].astype(np.int64)
     if len(idx) == 0:
         raise ValueError(f'from_residue: residue {r} has no atom')
@@ -130,13 +211,30 @@ def from_residue(pc, r):
     hrows = [np.arange(pc.h_off[i], pc.h_off[i + 1]) for i in idx]
     pc.ensure_labels()
     rn = pc.res_name[r]
+    ring_kw = dict(ring_center=np.zeros((0, 3)), ring_normal=np.zeros((0, 3)), ring_res=np.zeros(0, np.int32))
+    if planes:
+        if pc.n_rings and len(pc.ring_atoms) != pc.n_rings:
+            raise ValueError('from_residue: planes=True needs the atoms of every ring (ring_atoms)')
+        inside = [pos[np.asarray(a, np.int64)] >= 0 for a in pc.ring_atoms]
+        if any(m.any() and not m.all() for m in inside):
+            raise ValueError(f'from_residue: a ring of residue {r} shares atoms with another residue')
+        keep = [k for k, m in enumerate(inside) if m.all()]
+        am = np.asarray(pc.amide_atoms, np.int64).reshape(-1, 4)
+        known = (am[:, :3] >= 0).all(axis=1) if len(am) else np.zeros(0, bool)
+        ins = (pos[np.maximum(am[:, :3], 0)] >= 0) & known[:, None] if len(am) else np.zeros((0, 3), bool)
+        if (ins.any(axis=1) & ~ins.all(axis=1)).any():
+            raise ValueError(f'from_residue: an amide of residue {r} shares atoms with another residue')
+        ka = np.nonzero(ins.all(axis=1))[0]
+        ring_kw = dict(ring_center=pc.ring_center[keep], ring_normal=pc.ring_normal[keep], ring_res=np.zeros(len(keep), np.int32),
+                       ring_atoms=[pos[np.asarray(pc.ring_atoms[k], np.int64)].astype(np.int32) for k in keep],
+                       amide_center=pc.amide_center[ka], amide_normal=pc.amide_normal[ka], amide_res=np.zeros(len(ka), np.int32),
+                       amide_atoms=np.where(am[ka] >= 0, pos[np.maximum(am[ka], 0)], -1).astype(np.int32).reshape(-1, 4))
     return PackedComplex(
         xyz=pc.xyz[idx], vdw=pc.vdw[idx], cov=pc.cov[idx], type_mask=pc.type_mask[idx], flags=pc.flags[idx], res_id=np.zeros(len(idx), np.int32),
         res_flags=pc.res_flags[r:r + 1], res_prev=[-1], res_next=[-1],
         bond_off=np.concatenate([[0], np.cumsum([len(b) for b in bonds])]), bond_idx=pos[np.concatenate(bonds)] if bonds else [],
         h_off=np.concatenate([[0], np.cumsum([len(h) for h in hrows])]), h_xyz=np.asarray(pc.h_xyz).reshape(-1, 3)[np.concatenate(hrows).astype(np.int64)],
-        sb_nbr=np.where(nbr >= 0, pos[np.maximum(nbr, 0)], -1),
-        ring_center=np.zeros((0, 3)), ring_normal=np.zeros((0, 3)), ring_res=np.zeros(0, np.int32),
+        sb_nbr=np.where(nbr >= 0, pos[np.maximum(nbr, 0)], -1), **ring_kw,
         atom_name=[pc.atom_name[i] for i in idx], element=[pc.element[i] for i in idx], serial=np.asarray(pc.serial)[idx],
         res_name=[rn], res_seq=[int(pc.res_seq[r])], res_icode=[pc.res_icode[r]], res_chain=[pc.res_chain[r]],
         component_types={rn: pc.component_types.get(rn, 'B')}, id=f'{pc.id}:{rn}{int(pc.res_seq[r])}')
@@ -146,7 +244,13 @@ def complex_of(receptor, ligand, xyz=None, h_xyz=None):
     """The complex of the contract: ``receptor`` with ``ligand`` appended after its last atom as one more residue
     (``batch.concat_complexes([receptor, ligand])[0]``, to be uploaded as ONE structure), with the pose ``xyz`` float32 [S, 3] /
     ``h_xyz`` float64 [SH, 3] in place of the ligand's own coordinates when given.  The ligand's atoms are the ids
-    ``receptor.n_atoms + a``."""
+    ``receptor.n_atoms + a``.  The ligand's ``ring_atoms`` and ``amide_atoms`` are carried into the complex, shifted by
+    ``receptor.n_atoms`` and appended after the receptor's: ring ``receptor.n_rings + q``, amide ``receptor.n_amides + g``.  The
+    ligand's ring and amide GEOMETRY is carried as the pack has it (for its home coordinates): whoever evaluates the complex
+    makes the planes of the pose (``initialize()``, the device).  Refused (ValueError) when the receptor or the ligand names
+    the atoms of some of its rings only.  The complex also carries the LABELS of both packs, the receptor's first — atom
+    names, elements, serials, residue names, numbers, insertion codes and chains (``ensure_labels`` gives either pack its
+    defaults first) — and the union of their ``component_types``; where both name a component, the receptor's type holds."""
     from .batch import concat_complexes
     lig = ligand
     if xyz is not None or h_xyz is not None:
@@ -163,6 +267,21 @@ def complex_of(receptor, ligand, xyz=None, h_xyz=None):
             lig.h_xyz = h
     both = concat_complexes([receptor, lig])[0]
     both.id = f'{receptor.id}+{ligand.id}'
+    n = receptor.n_atoms
+    if receptor.ring_atoms or ligand.ring_atoms:
+        if len(receptor.ring_atoms) != receptor.n_rings or len(ligand.ring_atoms) != ligand.n_rings:
+            raise ValueError('complex_of: ring_atoms must name the atoms of every ring of the receptor and of the ligand, or of none')
+        both.ring_atoms = [np.asarray(a, np.int32) for a in receptor.ring_atoms] + [np.asarray(a, np.int32) + n for a in ligand.ring_atoms]
+    la = np.asarray(ligand.amide_atoms, np.int32).reshape(-1, 4)
+    both.amide_atoms = np.concatenate([np.asarray(receptor.amide_atoms, np.int32).reshape(-1, 4), np.where(la >= 0, la + n, la)]).astype(np.int32)
+    # the labels of both (the writers of the planes tables name entities of the complex)
+    receptor.ensure_labels()
+    ligand.ensure_labels()
+    for k in ('atom_name', 'element', 'res_name', 'res_icode', 'res_chain'):
+        setattr(both, k, list(getattr(receptor, k)) + list(getattr(ligand, k)))
+    both.serial = np.concatenate([np.asarray(receptor.serial), np.asarray(ligand.serial)]).astype(np.int32)
+    both.res_seq = np.concatenate([np.asarray(receptor.res_seq), np.asarray(ligand.res_seq)]).astype(np.int32)
+    both.component_types = {**ligand.component_types, **receptor.component_types}
     return both
 
 
@@ -330,3 +449,136 @@ def reference_rows(bag, n_receptor):
     out = {k: np.asarray(bag[k])[keep][order] for k in ('i', 'dist', 'sift', 'ctype')}
     out['a'] = (j[keep][order] - n_receptor).astype(np.int32)
     return {k: np.asarray(out[k]).astype(DTYPES[k]) for k in COLUMNS}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Ring and amide contacts of the library's poses: host side of ``Context.library_planes`` (arp_library_planes_*,
+# csrc/arp_library_planes.h).  The tables are laid out as those of ``Context.poses_planes``: the helpers of ``poses`` serve.
+# ---------------------------------------------------------------------------------------------------------------------
+PLANE_TABLES = _poses.PLANE_TABLES
+plane_columns = _poses.plane_columns
+
+
+def affected_rings(receptor, xyz_pose):
+    """The RECEPTOR rings one pose affects, ascending ids: a ligand atom lies within 3.0 A (inclusive, float64 sum of squares)
+    of the ring's resident centre at its pose coordinate ``xyz_pose`` [S, 3].  (A library ligand has no resident coordinate: the
+    "or at home" clause of ``poses.affected`` does not exist here.  The ligand's own rings are always affected.)"""
+    if receptor.n_rings == 0:
+        return np.zeros(0, np.int64)
+    x = np.asarray(xyz_pose, np.float32).reshape(-1, 3).astype(np.float64)
+    ctr = np.asarray(receptor.ring_center, np.float64).reshape(-1, 3)
+    return np.nonzero((_poses._kd2(ctr, x) <= 9.0).any(axis=1))[0].astype(np.int64)
+
+
+def plane_reference_rows(bags, receptor, ligand, xyz_pose):
+    """Of the four ring / amide bags of a pass over the complex of one pose (``complex_of``, the ligand selected): the rows that
+    involve an affected entity — a ligand atom, ring or amide, or a receptor ring of ``affected_rings`` —, each bag in its
+    canonical order: what the pose's records must equal.  ``receptor`` carries the resident ring centres."""
+    n, nr, na = receptor.n_atoms, receptor.n_rings, receptor.n_amides
+    m = np.zeros(n + ligand.n_atoms, bool)
+    m[n:] = True
+    rg = np.zeros(nr + ligand.n_rings, bool)
+    rg[nr:] = True
+    rg[affected_rings(receptor, xyz_pose)] = True
+    am = np.zeros(na + ligand.n_amides, bool)
+    am[na:] = True
+    keep = {'atom_plane': lambda b: m[b['atom']] | rg[b['ring']], 'plane_plane': lambda b: rg[b['bgn']] | rg[b['end']],
+            'group_group': lambda b: am[b['bgn']] | am[b['end']], 'group_plane': lambda b: am[b['amide']] | rg[b['ring']]}
+    out = {}
+    for name in PLANE_TABLES:
+        b = {c: np.asarray(bags[name][c]) for c, _ in plane_columns(name)}
+        first, second = _poses.PLANE_ORDER[name]
+        k = keep[name](b) if len(b[first]) else np.zeros(0, bool)
+        order = np.lexsort((b[second][k], b[first][k]))
+        out[name] = {c: b[c][k][order].astype(dt) for c, dt in plane_columns(name)}
+    return out
+
+
+def planes_from_rows(rows, summary=None):
+    """``rows``: per ligand a list of per-pose ``plane_reference_rows`` results; the table the device must return for them
+    (summary slots 12 - 14 from ``summary`` when given, else 0)."""
+    flat = [r for lig in rows for r in lig]
+    t = _poses.planes_from_rows(flat, (), summary)
+    del t['movable']
+    t['ligand_pose_off'] = np.concatenate([[0], np.cumsum([len(lig) for lig in rows])]).astype(np.int64)
+    return t
+
+
+def empty_planes(n_lig, ligand_pose_off=None):
+    lo = np.zeros(n_lig + 1, np.int64) if ligand_pose_off is None else np.asarray(ligand_pose_off, np.int64)
+    t = _poses.empty_planes(int(lo[-1]))
+    del t['movable']
+    t['ligand_pose_off'] = lo
+    return t
+
+
+def split_planes(table):
+    """Per ligand, per pose: a list of L lists of dicts of four bags."""
+    per = _poses.split_planes(table)
+    lo = np.asarray(table['ligand_pose_off'], np.int64)
+    return [per[lo[l]:lo[l + 1]] for l in range(len(lo) - 1)]
+
+
+def concat_planes(chunks):
+    """The planes results of launches over consecutive ranges of the global poses (``chunk_plan``) as one result."""
+    chunks = list(chunks)
+    if not chunks:
+        raise ValueError('concat_planes: no launch given')
+    L = len(chunks[0]['ligand_pose_off'])
+    if any(len(c['ligand_pose_off']) != L for c in chunks):
+        raise ValueError('concat_planes: the launches are over libraries of different sizes')
+    out = _poses.concat_planes([{k: v for k, v in c.items() if k != 'ligand_pose_off'} for c in chunks])
+    out.pop('movable', None)
+    P = np.sum([np.diff(np.asarray(c['ligand_pose_off'], np.int64)) for c in chunks], axis=0)
+    out['ligand_pose_off'] = np.concatenate([[0], np.cumsum(P)]).astype(np.int64)
+    if (np.diff(np.concatenate([ligand_of(c) for c in chunks])) < 0).any():
+        raise ValueError('concat_planes: the launches are not consecutive ranges of one ligand-major pose sequence')
+    return out
+
+
+def _planes_per_pose(table, receptor, ligands):
+    """(ligand, pose within it, the complex the ids are of, the pose's four bags) for every global pose."""
+    both = {}
+    for l, per in enumerate(split_planes(table)):
+        for p, bags in enumerate(per):
+            if l not in both:
+                both[l] = complex_of(receptor, ligands[l])
+                both[l].ensure_labels()
+            yield l, p, both[l], bags
+
+
+def planes_to_records(table, receptor, ligands, component_types=None):
+    """The records as the dicts ``get_contacts`` returns for the four bags (export.py), each with its 'ligand' and 'pose' (the
+    pose within the ligand).  Entities are labelled from the complex of the ligand (``complex_of``)."""
+    from .core import export
+    out = []
+    for l, p, both, bags in _planes_per_pose(table, receptor, ligands):
+        for rec in export.contacts_json(both, bags, {**both.component_types, **(component_types or {})}):
+            rec['ligand'], rec['pose'] = l, p
+            out.append(rec)
+    return out
+
+
+PLANES_CSV_HEADER = ['ligand'] + _poses.PLANES_CSV_HEADER
+
+
+def write_planes_csv(path, table, receptor, ligands, component_types=None):
+    """One row per record: ligand, pose within the ligand, then the columns of ``poses.write_planes_csv`` — bag, the two entities
+    ('A/508/O' for an atom, 'ring/<id>' and 'amide/<id>' with the complex's ids), distance, contacts, interacting entities."""
+    from .core import export
+    labs = {}
+    with open(path, 'w', newline='') as fh:
+        w = csv.writer(fh, delimiter=',', quotechar='"', quoting=csv.QUOTE_MINIMAL)
+        w.writerow(PLANES_CSV_HEADER)
+        for l, p, both, bags in _planes_per_pose(table, receptor, ligands):
+            if l not in labs:
+                labs[l] = export.Labels(both, {**both.component_types, **(component_types or {})})
+            for row in _poses.planes_csv_rows(labs[l], bags):
+                w.writerow([l, p] + row)
+
+
+def write_library_planes(wd, sid, table, receptor, ligands, component_types=None):
+    """'<id>.libraryplanes' in ``wd``."""
+    path = os.path.join(wd, sid + '.libraryplanes')
+    write_planes_csv(path, table, receptor, ligands, component_types)
+    return path

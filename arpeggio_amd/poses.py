@@ -424,29 +424,37 @@ def planes_to_records(table, pc, component_types=None):
 PLANES_CSV_HEADER = ['pose', 'type', 'bgn', 'end', 'distance', 'contacts', 'interacting_entities']
 
 
+def planes_csv_rows(lab, bags):
+    """The CSV rows of one pose's four bags, without the pose column: bag, the two entities, distance, contacts, interacting
+    entities.  ``lab``: ``export.Labels`` of the structure the ids are of."""
+    from .core import export
+    ct, pp, ap = config.CONTACT_TYPE_NAMES, config.PLANE_PLANE_NAMES, config.ATOM_PLANE_NAMES
+    b = bags['atom_plane']
+    for a, r, d, m, c in zip(b['atom'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['mask'].tolist(), b['ctype'].tolist()):
+        yield ['atom-plane', lab.atom_macro(a), f'ring/{r}', d, '|'.join(n for k, n in enumerate(ap) if (m >> k) & 1), ct[c]]
+    b = bags['plane_plane']
+    for r1, r2, d, t1, t2, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['type1'].tolist(), b['type2'].tolist(),
+                                    b['ctype'].tolist()):
+        yield ['plane-plane', f'ring/{r1}', f'ring/{r2}', d, '|'.join([pp[t1]] + ([pp[t2]] if t2 < config.PP_SAME else [])), ct[c]]
+    b = bags['group_group']
+    for a1, a2, d, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
+        yield ['group-group', f'amide/{a1}', f'amide/{a2}', d, 'AMIDEAMIDE', ct[c]]
+    b = bags['group_plane']
+    for a, r, d, c in zip(b['amide'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
+        yield ['group-plane', f'amide/{a}', f'ring/{r}', d, 'AMIDERING', ct[c]]
+
+
 def write_planes_csv(path, table, pc, component_types=None):
     """One row per record: pose, bag, the two entities ('A/508/O' for an atom, 'ring/<id>' and 'amide/<id>' otherwise), the
     distance rounded as ``get_contacts`` rounds it, the contacts by name joined with '|', the interacting entities."""
     from .core import export
     lab = export.Labels(pc, pc.component_types if component_types is None else component_types)
-    ct, pp, ap = config.CONTACT_TYPE_NAMES, config.PLANE_PLANE_NAMES, config.ATOM_PLANE_NAMES
     with open(path, 'w', newline='') as fh:
         w = csv.writer(fh, delimiter=',', quotechar='"', quoting=csv.QUOTE_MINIMAL)
         w.writerow(PLANES_CSV_HEADER)
         for p, bags in enumerate(split_planes(table)):
-            b = bags['atom_plane']
-            for a, r, d, m, c in zip(b['atom'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['mask'].tolist(), b['ctype'].tolist()):
-                w.writerow([p, 'atom-plane', lab.atom_macro(a), f'ring/{r}', d, '|'.join(n for k, n in enumerate(ap) if (m >> k) & 1), ct[c]])
-            b = bags['plane_plane']
-            for r1, r2, d, t1, t2, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['type1'].tolist(), b['type2'].tolist(),
-                                            b['ctype'].tolist()):
-                w.writerow([p, 'plane-plane', f'ring/{r1}', f'ring/{r2}', d, '|'.join([pp[t1]] + ([pp[t2]] if t2 < config.PP_SAME else [])), ct[c]])
-            b = bags['group_group']
-            for a1, a2, d, c in zip(b['bgn'].tolist(), b['end'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
-                w.writerow([p, 'group-group', f'amide/{a1}', f'amide/{a2}', d, 'AMIDEAMIDE', ct[c]])
-            b = bags['group_plane']
-            for a, r, d, c in zip(b['amide'].tolist(), b['ring'].tolist(), export.rounded(b['dist']), b['ctype'].tolist()):
-                w.writerow([p, 'group-plane', f'amide/{a}', f'ring/{r}', d, 'AMIDERING', ct[c]])
+            for row in planes_csv_rows(lab, bags):
+                w.writerow([p] + row)
 
 
 def write_pose_planes(wd, sid, table, pc, component_types=None):

@@ -750,12 +750,14 @@ def poses_of(pc: PackedComplex, sel, n_poses: int, seed: int = 0, shift: float =
 # Ligands of a library (``arpeggio_amd.ligand_library``): small typed molecules of ONE residue each, centred on the origin
 # ---------------------------------------------------------------------------------------------------------------------
 LIGAND_KINDS = ('water', 'ion', 'amine', 'halo', 'chain')
+PLANE_LIGAND_KINDS = ('arylamide', 'biaryl')      # ligands with rings / an amide: always made with their plane atoms
 _LIG_VDW = {'C': 1.7, 'N': 1.55, 'O': 1.52, 'S': 1.8, 'H': 1.1, 'ZN': 1.39, 'CL': 1.75, 'BR': 1.85}
 _LIG_COV = {'C': 0.76, 'N': 0.71, 'O': 0.66, 'S': 1.05, 'H': 0.31, 'ZN': 1.22, 'CL': 1.02, 'BR': 1.2}
 
 
-def _ligand_pack(atoms, bonds, ring_bonds, res_name, id):
-    """atoms: dicts of xyz, el, name, tm, fl, rows (the hydrogen rows of this atom); bonds: index pairs."""
+def _ligand_pack(atoms, bonds, ring_bonds, res_name, id, rings=(), amides=()):
+    """atoms: dicts of xyz, el, name, tm, fl, rows (the hydrogen rows of this atom); bonds: index pairs; rings: atom indices in
+    ring-path order; amides: (N, C, O, fourth atom)."""
     n = len(atoms)
     xyz = np.array([a['xyz'] for a in atoms], np.float64).reshape(-1, 3)
     mean = xyz[[not a['fl'] & config.F_HYDROGEN for a in atoms]].mean(axis=0)      # (centred on the heavy atoms)
@@ -774,18 +776,27 @@ def _ligand_pack(atoms, bonds, ring_bonds, res_name, id):
     x32 = xyz.astype(np.float32)
     # a hydrogen row is either a coordinate or the index of the hydrogen ATOM it repeats (then: as read from the float32 atom)
     rows = [[x32[h].astype(np.float64) if isinstance(h, int) else np.asarray(h, np.float64) - mean for h in a['rows']] for a in atoms]
+    planes = dict(ring_center=np.zeros((0, 3)), ring_normal=np.zeros((0, 3)), ring_res=np.zeros(0, np.int32))
+    if len(rings) or len(amides):
+        from .ligand_library import host_plane_geometry
+        ring_atoms = [np.asarray(r, np.int32) for r in rings]
+        am = np.asarray(amides, np.int32).reshape(-1, 4)
+        rc, rn, ac, an = host_plane_geometry(x32, ring_atoms, am)
+        planes = dict(ring_center=rc, ring_normal=rn, ring_res=np.zeros(len(ring_atoms), np.int32), ring_atoms=ring_atoms,
+                      amide_center=ac, amide_normal=an, amide_res=np.zeros(len(am), np.int32), amide_atoms=am)
     return PackedComplex(
         xyz=x32, vdw=[_LIG_VDW[e] for e in el], cov=[_LIG_COV[e] for e in el], type_mask=[a['tm'] for a in atoms], flags=[a['fl'] for a in atoms],
         res_id=np.zeros(n, np.int32), res_flags=[0], res_prev=[-1], res_next=[-1],
         bond_off=np.concatenate([[0], np.cumsum([len(a) for a in adj])]), bond_idx=[j for a in adj for j in a],
         h_off=np.concatenate([[0], np.cumsum([len(r) for r in rows])]), h_xyz=np.array([h for r in rows for h in r], np.float64).reshape(-1, 3),
-        sb_nbr=sb, ring_center=np.zeros((0, 3)), ring_normal=np.zeros((0, 3)), ring_res=np.zeros(0, np.int32),
+        sb_nbr=sb, **planes,
         atom_name=[a['name'] for a in atoms], element=el, serial=np.arange(1, n + 1, dtype=np.int32), res_name=[res_name], res_seq=[1],
         res_icode=[' '], res_chain=['L'], component_types={res_name: 'W' if res_name == 'HOH' else 'B'}, id=id)
 
 
-def ligand(kind: str, seed: int = 0, size: int = None) -> PackedComplex:
-    """One synthetic ligand, centred on the origin (deterministic, splitmix64):
+def ligand(kind: str, seed: int = 0, size: int = None, planes: bool = False) -> PackedComplex:
+    """One synthetic ligand, centred on the origin (deterministic, splitmix64).  ``planes``: a 'halo' carries the atoms of its
+    ring (``ring_atoms``, with a consistent geometry); the kinds of ``PLANE_LIGAND_KINDS`` always do.
 
     'water'  one oxygen (water flag, donor and acceptor) with two hydrogen ROWS and no hydrogen atoms: S = 1, SH = 2
     'ion'    one metal ion: S = 1, SH = 0
@@ -795,6 +806,11 @@ def ligand(kind: str, seed: int = 0, size: int = None) -> PackedComplex:
     'chain'  ``size`` heavy atoms (default 24) along a compact self-avoiding walk, typed from a palette — donors and weak
              donors with hydrogen rows, acceptors, ionisable groups, carbonyls, aromatic carbons, a sulphur, halogens behind a
              carbon —, hydrogens as rows only: S = size
+    'arylamide'  an anilide: a benzene ring, on C1 an amide N - C(=O) - CH3 in the ring's plane (amide atoms N, C, O and the ring
+             carbon as fourth), on C4 a CH2 - NH3+ whose hydrogens are rows only; the ring's four hydrogens are atoms and rows:
+             S = 16, one ring, one amide
+    'biaryl' two six-membered aromatic rings joined by a single bond, the second twisted by 40 degrees about it and with a
+             chlorine opposite the bond; nine hydrogens as atoms and rows: S = 22, two rings
     """
     def unit(v):
         return v / np.linalg.norm(v)
@@ -842,9 +858,50 @@ def ligand(kind: str, seed: int = 0, size: int = None) -> PackedComplex:
         atoms.append(atom(atoms[3]['xyz'] * (1 + 1.90 / 1.39), 'BR', 'BR1', hal, config.F_HALOGEN)); bonds.append((3, 7))
         for q in (1, 2, 4, 5):
             add_h(q, atoms[q]['xyz'], f'H{q + 1}')
-        return _ligand_pack(atoms, bonds, ring_bonds, 'HAL', f'halo{seed}')
+        return _ligand_pack(atoms, bonds, ring_bonds, 'HAL', f'halo{seed}', rings=[list(range(6))] if planes else ())
+    aro = T['aromatic'] | T['hydrophobe'] | T['weak hbond donor']
+
+    def six_ring(centre, twist, prefix):
+        """Six aromatic carbons about ``centre``, turned by ``twist`` about the x axis; returns their indices."""
+        first = len(atoms)
+        ct, st = np.cos(twist), np.sin(twist)
+        for q in range(6):
+            ang = q * np.pi / 3
+            y = 1.39 * np.sin(ang)
+            atoms.append(atom(np.asarray(centre, float) + [1.39 * np.cos(ang), y * ct, y * st], 'C', f'{prefix}{q + 1}', aro, config.F_ELEM_C))
+        for q in range(6):
+            bonds.append((first + q, first + (q + 1) % 6)); ring_bonds.append((first + q, first + (q + 1) % 6))
+        return list(range(first, first + 6))
+
+    if kind == 'arylamide':
+        ring = six_ring([0.0, 0.0, 0.0], 0.0, 'C')
+        e = lambda deg: np.array([np.cos(np.radians(deg)), np.sin(np.radians(deg)), 0.0])
+        atoms.append(atom(atoms[0]['xyz'] + 1.41 * e(0), 'N', 'N7', T['hbond donor'], 0)); bonds.append((0, 6))
+        atoms.append(atom(atoms[6]['xyz'] + 1.34 * e(60), 'C', 'C8', T['carbonyl carbon'], config.F_ELEM_C)); bonds.append((6, 7))
+        atoms.append(atom(atoms[7]['xyz'] + 1.23 * e(120), 'O', 'O9', T['hbond acceptor'] | T['weak hbond acceptor'] | T['xbond acceptor'] | T['carbonyl oxygen'], 0))
+        bonds.append((7, 8))
+        atoms.append(atom(atoms[7]['xyz'] + 1.51 * e(0), 'C', 'C10', T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C)); bonds.append((7, 9))
+        atoms.append(atom(atoms[3]['xyz'] + 1.51 * e(180), 'C', 'C11', T['hydrophobe'] | T['weak hbond donor'], config.F_ELEM_C)); bonds.append((3, 10))
+        atoms.append(atom(atoms[10]['xyz'] + 1.47 * unit(np.array([-0.5, 0.0, 0.85])), 'N', 'NZ', T['hbond donor'] | T['pos ionisable'], 0)); bonds.append((10, 11))
+        add_h(6, e(-60), 'H7', False)
+        for k, d in enumerate(([-0.6, 0.0, 0.8], [0.4, 0.8, 0.45], [0.4, -0.8, 0.45])):
+            add_h(11, d, f'HZ{k + 1}', False)
+        for q in (1, 2, 4, 5):
+            add_h(q, atoms[q]['xyz'], f'H{q + 1}')
+        return _ligand_pack(atoms, bonds, ring_bonds, 'ARA', f'arylamide{seed}', rings=[ring], amides=[(6, 7, 8, 0)])
+    if kind == 'biaryl':
+        cx = 2 * 1.39 + 1.48
+        a_ring = six_ring([0.0, 0.0, 0.0], 0.0, 'CA')
+        b_ring = six_ring([cx, 0.0, 0.0], np.radians(40.0), 'CB')
+        bonds.append((a_ring[0], b_ring[3]))                                       # CA1 - CB4, along x: the twist leaves it in place
+        atoms.append(atom(atoms[b_ring[0]]['xyz'] + [1.74, 0.0, 0.0], 'CL', 'CL1', T['xbond donor'] | T['weak hbond acceptor'] | T['hydrophobe'], config.F_HALOGEN))
+        bonds.append((b_ring[0], len(atoms) - 1))
+        for ring, centre, free in ((a_ring, np.zeros(3), (1, 2, 3, 4, 5)), (b_ring, np.array([cx, 0.0, 0.0]), (1, 2, 4, 5))):
+            for q in free:
+                add_h(ring[q], atoms[ring[q]]['xyz'] - centre, f'H{atoms[ring[q]]["name"][1:]}')
+        return _ligand_pack(atoms, bonds, ring_bonds, 'BIA', f'biaryl{seed}', rings=[a_ring, b_ring])
     if kind != 'chain':
-        raise ValueError(f'ligand: kind must be one of {LIGAND_KINDS}')
+        raise ValueError(f'ligand: kind must be one of {LIGAND_KINDS + PLANE_LIGAND_KINDS}')
     n = 24 if size is None else int(size)
     if n < 1:
         raise ValueError('ligand: a chain needs at least one atom')
@@ -876,9 +933,9 @@ def ligand(kind: str, seed: int = 0, size: int = None) -> PackedComplex:
     return _ligand_pack(atoms, bonds, ring_bonds, 'LIG', f'chain{n}_{seed}')
 
 
-def ligands(n: int, seed: int = 0, sizes=(20, 60), kinds=LIGAND_KINDS):
+def ligands(n: int, seed: int = 0, sizes=(20, 60), kinds=LIGAND_KINDS, planes: bool = False):
     """``n`` ligands for a library: ligand k is of kind ``kinds[k % len(kinds)]``; a 'chain' gets a size drawn from
-    ``sizes = (smallest, largest)`` (or ``sizes[k]`` when ``sizes`` lists one size per ligand)."""
+    ``sizes = (smallest, largest)`` (or ``sizes[k]`` when ``sizes`` lists one size per ligand).  ``planes`` as in ``ligand``."""
     out = []
     for k in range(int(n)):
         kind = kinds[k % len(kinds)]
@@ -886,7 +943,7 @@ def ligands(n: int, seed: int = 0, sizes=(20, 60), kinds=LIGAND_KINDS):
             size = int(sizes[0] + splitmix64(seed, [7200 + k])[0] % (sizes[1] - sizes[0] + 1))
         else:
             size = int(sizes[k])
-        out.append(ligand(kind, seed=seed + k, size=size))
+        out.append(ligand(kind, seed=seed + k, size=size, planes=planes))
     return out
 
 

@@ -1348,8 +1348,8 @@ int arp_poses_clusters_info(arp_ctx* ctx, int64_t info[8]);
  *   is asked for).  arp_library_info: info[0] = L, [3] = TA, [4] = hydrogen rows, [6] = the largest S_l of the resident
  *   library; [1] = T, [2] = records, [5] = blocks of k_library_contacts (poses are taken with a grid stride) of the resident
  *   result; [7] = 1 while a best-pose table is resident.
- * OUT OF SCOPE: the ligands' own rings and amides (the plane tables of a library); the shortlist and clusters over a library
- *   result (fingerprints: arp_library_fingerprints_launch below); peptide and covalent ligands;
+ * OUT OF SCOPE: the shortlist and clusters over a library result (fingerprints: arp_library_fingerprints_launch below; the
+ *   ligands' own rings and amides: arp_library_planes_launch below); peptide and covalent ligands;
  *   cutoffs beyond 6.0; a batch, models or a shard as the receptor; the per-atom accumulators. */
 #define ARP_LIBRARY_MAX_LIGANDS (1 << 16)
 #define ARP_LIBRARY_MAX_ATOMS 256
@@ -1368,8 +1368,8 @@ int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, 
  *
  * FEATURE.  (node, plane).  The node is the receptor atom i of a participating library record, with ARP_POSEFP_BY_RESIDUE
  *   res_id[i]; the plane is one of the 15 SIFt bits selected by `planes`.  A record participates when bit ctype of ctype_mask
- *   is set and sift & planes != 0.  The ligand side a never names a node.  There are no class planes (a library has no ring or
- *   amide tables) and no all-pairs matrix (T reaches 2^20).
+ *   is set and sift & planes != 0.  The ligand side a never names a node.  There are no class planes yet (the library's ring and
+ *   amide tables, arp_library_planes_launch, are not read here) and no all-pairs matrix (T reaches 2^20).
  * REFERENCES need not be poses of the launch: the known binder is usually another molecule.  Q = n_refs <=
  *   ARP_POSEFP_MAX_REFS references are given as feature lists: ref_off int64 [Q + 1] (ref_off[0] = 0, not decreasing, F =
  *   ref_off[Q] <= ARP_LIBFP_MAX_FEATURES), ref_node int32 [F] (nodes of the launch's level, strictly ascending within a
@@ -1412,6 +1412,71 @@ int arp_library_fingerprints_best_launch(arp_ctx* ctx);
 int arp_library_fingerprints_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, int32_t* best_pose,
                                         int64_t* tanimoto_q32, uint32_t* shared, uint32_t* count, int64_t* n_ligands,
                                         int64_t* n_refs);
+/* Library planes: the ring and amide contacts of every pose of every ligand of the library, in one launch
+ * (csrc/arp_library_planes.h).  What arp_poses_planes_launch is to arp_poses_contacts_launch, this is to
+ * arp_library_contacts_launch: pi-stacking, cation-pi, donor-pi, halogen-pi and amide stacking of a screen.  An extension
+ * beside the mirror; independent of the contacts launch (sharing one upload of the poses between the two is out of scope).
+ *
+ * RECEPTOR.  As for arp_library_contacts_launch (one structure, refused in the same order).  Its ring centres, normals and ring
+ *   residues and its amide centres, normals and residues are resident as initialize() makes them; nring = 0 or namide = 0 is
+ *   allowed.  No arp_set_plane_atoms of the receptor is needed: no receptor ring or amide ever moves.  No selection is read.
+ * LIBRARY PLANE TABLE (arp_set_ligand_library_planes).  Beside the resident library of L ligands (the call takes no count: L is
+ *   the library's): ring_off int32 [L + 1], a CSR over the ligands, TR = ring_off[L] rings in all; ring_atom_off int32 [TR + 1];
+ *   ring_atom_idx int32 [ring_atom_off[TR]], every ring in ring-path order, indices WITHIN THE LIGAND; amide_off int32 [L + 1],
+ *   TM = amide_off[L] amides in all; amide_atoms int32 [TM][4]: N, C, O, C-alpha, indices within the ligand (the fourth is not
+ *   read and may be -1).  At most ARP_LIBRARY_PLANES_MAX_RINGS rings and ARP_LIBRARY_PLANES_MAX_AMIDES amides a ligand; a ring
+ *   has at least three atoms.  ring_atom_idx may be NULL when there is no ring, amide_atoms when there is no amide.
+ *   ARP_E_ARG with the cause named, checked in this order and before anything is touched: a pass not waited for; no library;
+ *   an array missing; an offset array not starting at 0 or decreasing (ring_off, ring_atom_off, amide_off); a ligand over a
+ *   limit; a ring of fewer than three atoms; an index outside its own ligand.
+ *   Like the library the table reads nothing of the receptor and stays resident through new structures.  It is dropped by
+ *   arp_set_ligand_library and replaced by a new arp_set_ligand_library_planes; either voids the result.
+ * POSES (arp_library_planes_launch).  pose_off, xyz and T exactly as in arp_library_contacts_launch.  There is no h_xyz, no
+ *   cutoff and no vdw_comp: none of the four loops reads them.
+ * RESULT.  The COMPLEX of pose t of ligand l is the receptor with ligand l appended as one more residue, uploaded as ONE
+ *   structure: the pose's coordinates scattered in, the ligand's rings and amides appended after the receptor's, ring and amide
+ *   geometry and ALL ring residues made again as initialize() makes them, the ligand's atoms the selection, _make_selection
+ *   with the 6.0 A expansion.  Ids are the complex's: atoms i (receptor) and n + a (ligand), rings r and nring + q, amides m
+ *   and namide + g; the ligand's residue is the receptor's residue count.  AFFECTED by a pose are every ligand atom, every
+ *   ligand ring, every ligand amide, and every receptor ring with a ligand atom within 3.0 A of its centre at the pose
+ *   coordinate (dist2_kd <= 9.0, float64, inclusive).  (arp_poses_planes_launch's "or at its resident coordinate" does not
+ *   exist here: a library ligand has no resident coordinate.)  The result of pose t is exactly the records of the complex's
+ *   four bags (atom_plane, plane_plane, group_group, group_plane) that involve an affected entity: every column as the pass
+ *   gives it — ids, distances and angles to the bit, masks, classes, contact type —; per table ascending (global pose, then
+ *   the bag's canonical pair), as arp_poses_planes_fetch.  summary uint32 [T][ARP_POSES_PLANES_SUMMARY] with the slots of
+ *   arp_poses_planes_fetch; slot 12 counts the affected rings, the ligand's included; slot 13 the receptor rings whose residue
+ *   differs from the resident one (a ligand atom took the ring over); slot 14 the affected rings with residue -1.  Nothing is
+ *   truncated: a record buffer that was too small is grown to the counted size and the launch repeated.  Deterministic.
+ *   ARP_E_ARG with the cause named, in this order, none touching a resident result: the receptor's refusals; n +
+ *   ARP_LIBRARY_MAX_ATOMS, nring + ARP_LIBRARY_PLANES_MAX_RINGS or namide + ARP_LIBRARY_PLANES_MAX_AMIDES not below 2^21 (the
+ *   64-bit sort key of arp_poses_planes_launch); no library; no library plane table; pose_off missing, not starting at 0,
+ *   decreasing; T out of range; xyz missing; no residue table resident (arp_set_residues: the ligand is one more residue behind
+ *   the receptor's, and without a table it would coincide with residue 0).  Found on the device (the result before is void by then and none is resident
+ *   afterwards): a non-finite pose coordinate, ARP_E_ARG; more than ARP_POSES_PLANES_MAX_NEAR receptor rings near one pose,
+ *   ARP_E_ARG by that name — a ring is never dropped.  ARP_E_CAPACITY: 2^31 records or more.
+ *   All work goes on the context's stream (arp_use_stream's, if set); ONE host wait a launch, for the counters with the
+ *   device's error word.
+ * arp_library_planes_fetch: the shape and column rules of arp_poses_planes_fetch with T for P (ANY pointer may be NULL; cap is
+ *   looked at only when a record column is asked for; a column the table does not have: ARP_E_ARG).
+ * arp_library_planes_info: info[0] = L, [1] = TR, [2] = TM of the resident plane table (zeros while there is none), [10] = 1
+ *   while one is resident; [3] = T, [4 .. 7] = records per table, [8] = blocks of k_library_planes (poses are taken with a grid
+ *   stride) of the resident result; [9] = launches of the kernel so far (a repeated launch counts twice); [11] = 1 while the
+ *   per-structure set-up (all-atom grid, residue -> atoms) is resident.
+ * STATE.  The result is void after a new structure, models, a batch, arp_set_ligand_library, arp_set_ligand_library_planes and a
+ *   new launch.  arp_set_selection does NOT void it.  Making it voids nothing: the bags of the last pass, every table made from
+ *   them, every pose result, the library contacts, their best-pose table and the library fingerprints stay fetchable and
+ *   byte-equal.
+ * OUT OF SCOPE: class planes of the library fingerprints, the shortlist and clusters over a library (the next steps, which read
+ *   this table); arp_library_best_launch over this summary; peptide and covalent ligands; a batch, models or a shard as the
+ *   receptor; receptor - receptor records between unaffected entities. */
+#define ARP_LIBRARY_PLANES_MAX_RINGS 32
+#define ARP_LIBRARY_PLANES_MAX_AMIDES 32
+int arp_set_ligand_library_planes(arp_ctx* ctx, const int32_t* ring_off, const int32_t* ring_atom_off, const int32_t* ring_atom_idx,
+                                  const int32_t* amide_off, const int32_t* amide_atoms);
+int arp_library_planes_launch(arp_ctx* ctx, const int64_t* pose_off, const float* xyz, int64_t counts[4]);
+int arp_library_planes_fetch(arp_ctx* ctx, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0,
+                             void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count);
+int arp_library_planes_info(arp_ctx* ctx, int64_t info[12]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
