@@ -59,6 +59,7 @@ SYMBOLS = (
     'arp_library_fingerprints_launch', 'arp_library_fingerprints_fetch', 'arp_library_fingerprints_info',
     'arp_library_fingerprints_best_launch', 'arp_library_fingerprints_best_fetch',
     'arp_set_ligand_library_planes', 'arp_library_planes_launch', 'arp_library_planes_fetch', 'arp_library_planes_info',
+    'arp_library_shortlist_launch', 'arp_library_shortlist_fetch', 'arp_library_shortlist_planes_fetch', 'arp_library_shortlist_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -73,6 +74,7 @@ POSEFP_ALL_PLANES = 29           # ARP_POSEFP_ALL_PLANES: the SIFt bits and the 
 # ... their shortlist (ARP_SHORTLIST_*)
 SHORTLIST_LIST, SHORTLIST_SUMMARY, SHORTLIST_TANIMOTO, SHORTLIST_TABLES, SHORTLIST_MAX_WEIGHT = 0, 1, 2, 5, 1 << 24
 INT64_MIN = -(1 << 63)
+LIBRARY_SHORTLIST_POSES, LIBRARY_SHORTLIST_LIGANDS = 0, 1      # ARP_LIBRARY_SHORTLIST_*
 # a ligand library on the resident receptor (ARP_LIBRARY_*)
 LIBRARY_MAX_LIGANDS, LIBRARY_MAX_ATOMS = 1 << 16, 256
 LIBFP_MAX_FEATURES = 1 << 22     # ARP_LIBFP_MAX_FEATURES: reference features of a library fingerprint launch
@@ -267,6 +269,10 @@ def load():
     L.arp_poses_shortlist_fetch.argtypes = [vp, i64, i64] + [vp] * 10 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_poses_shortlist_planes_fetch.argtypes = [vp, C.c_int, i64, i64] + [vp] * 10 + [C.POINTER(i64)]
     L.arp_poses_shortlist_info.argtypes = [vp, vp]
+    L.arp_library_shortlist_launch.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, i64, i64, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.arp_library_shortlist_fetch.argtypes = [vp, i64, i64] + [vp] * 11 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_library_shortlist_planes_fetch.argtypes = [vp, C.c_int, i64, i64] + [vp] * 10 + [C.POINTER(i64)]
+    L.arp_library_shortlist_info.argtypes = [vp, vp]
     L.arp_poses_clusters_launch.argtypes = [vp, vp, i64, i64, C.c_uint64, i64, vp]
     L.arp_poses_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 6 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_poses_clusters_info.argtypes = [vp, vp]
@@ -1454,6 +1460,79 @@ class Context:
                                                                 _p(out['shared']), _p(out['count']), C.byref(nl), C.byref(nq)),
                     'arp_library_fingerprints_best_fetch')
         return out
+
+    def library_shortlist(self, kind, *, unit=None, weights=None, ref=0, pose_ids=None, k=None, min_score=None, tables=('atom_atom',),
+                          sift_mask=0, ctype_mask=CTYPE_ALL):
+        """The global poses of the resident library result (``library_contacts`` / ``library_summary``) — or, ``unit='ligands'``
+        (the default of a ranked kind), its ligands, each by its best pose — ranked on the device and the chosen poses' records
+        fetched, no other record copied (arp_library_shortlist_*; ``arpeggio_amd.library_shortlist``).  ``kind``: 'summary' —
+        score = ``weights`` (int32 [32], ``library_shortlist.weights``) times the summary slots of the library result and,
+        second half, of the resident ``library_planes`` result of the same poses; 'tanimoto' — the Tanimoto similarity (32
+        fractional bits) to reference ``ref`` of the resident ``library_fingerprints`` result, ``ref=-1`` the best over its
+        references; 'list' — the global poses ``pose_ids`` in that order (no ``unit``, ``k`` or ``min_score``).  Order:
+        descending score, ties by ascending global pose; chosen are the first ``k`` (default: all) with a score of at least
+        ``min_score``.  ``tables`` / ``sift_mask`` / ``ctype_mask`` as ``poses_shortlist``.  Returns a library table of K
+        one-pose entries — ``i``, ``a``, ``dist``, ``sift``, ``ctype``, ``pose_off`` uint64 [K + 1] (for 'atom_atom'), ``summary``
+        uint32 [K, 16], ``ligand_pose_off`` = 0 ... K (entry r stands where a ligand does: ``ligand_library.split`` works on it,
+        ``library_shortlist.to_records`` names the real ligand) — with ``ligand`` int32 [K], ``pose`` int32 [K] (global pose),
+        ``score`` int64 [K], ``planes_summary`` when the planes result was read, and per ring / amide table a dict shaped as
+        ``library_planes`` gives it."""
+        from . import pose_shortlist as _sl, poses as _poses
+        if kind not in _sl.KINDS:
+            raise ValueError(f'library_shortlist: kind must be one of {_sl.KINDS}')
+        units = ('poses', 'ligands')
+        code = _sl.KINDS.index(kind)
+        if unit is None:
+            unit = 'poses' if code == SHORTLIST_LIST else 'ligands'
+        if unit not in units:
+            raise ValueError(f'library_shortlist: unit must be one of {units}')
+        mask = _sl.tables_mask(tables)
+        w = None if weights is None else np.ascontiguousarray(weights, np.int32).reshape(-1)
+        if w is not None and len(w) != 32:
+            raise ValueError('library_shortlist: weights must be int32 [32] (library_shortlist.weights)')
+        ids = None if pose_ids is None else np.ascontiguousarray(pose_ids, np.int32).reshape(-1)
+        kk = (0 if code == SHORTLIST_LIST else POSES_MAX_POSES) if k is None else int(k)
+        ms = INT64_MIN if min_score is None else int(min_score)
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_shortlist_launch(self._h, code, units.index(unit), _p(w), int(ref), _p(ids), 0 if ids is None else len(ids),
+                                                         kk, ms, mask, int(sift_mask), int(ctype_mask), _p(info)), 'arp_library_shortlist_launch')
+        K = int(info[0])
+        planes_read = (mask >> 1) != 0 or (code == SHORTLIST_SUMMARY and w is not None and bool(np.any(w[16:])))
+        out = dict(ligand=np.empty(K, np.int32), pose=np.empty(K, np.int32), score=np.empty(K, np.int64),
+                   summary=np.empty((K, POSES_SUMMARY), np.uint32))
+        if planes_read:
+            out['planes_summary'] = np.empty((K, POSES_PLANES_SUMMARY), np.uint32)
+        n, m = C.c_int64(0), C.c_int64(0)
+        kept = int(info[1]) if mask & 1 else 0
+        if mask & 1:
+            out.update(i=np.empty(kept, np.int32), a=np.empty(kept, np.int32), dist=np.empty(kept, np.float32), sift=np.empty(kept, np.uint16),
+                       ctype=np.empty(kept, np.uint8), pose_off=np.empty(K + 1, np.uint64))
+        self._check(self._L.arp_library_shortlist_fetch(self._h, K, kept, _p(out['ligand']), _p(out['pose']), _p(out['score']), _p(out['summary']),
+                                                        _p(out.get('planes_summary')), _p(out.get('pose_off')), _p(out.get('i')), _p(out.get('a')),
+                                                        _p(out.get('dist')), _p(out.get('sift')), _p(out.get('ctype')), C.byref(n), C.byref(m)),
+                    'arp_library_shortlist_fetch')
+        for t, name in enumerate(_poses.PLANE_TABLES):
+            if not (mask >> (t + 1)) & 1:
+                continue
+            kept = int(info[2 + t])
+            tab, args = self._plane_table_buffers(name, kept, K + 1)
+            self._check(self._L.arp_library_shortlist_planes_fetch(self._h, t, K, kept, _p(tab['pose_off']), *args, C.byref(m)),
+                        'arp_library_shortlist_planes_fetch')
+            out[name] = tab
+        out['ligand_pose_off'] = np.arange(K + 1, dtype=np.int64)
+        out['kind'], out['unit'] = kind, unit
+        return out
+
+    def library_shortlist_info(self):
+        """arp_library_shortlist_info: the chosen entries and the kept records per table of the resident library shortlist (zeros
+        while there is none), the launches that did work so far, the kind and the unit."""
+        from . import pose_shortlist as _sl
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_shortlist_info(self._h, _p(info)), 'arp_library_shortlist_info')
+        d = dict(chosen=int(info[0]))
+        d.update({name: int(info[1 + t]) for t, name in enumerate(_sl.TABLES)})
+        d.update(launches=int(info[6]), kind=int(info[7]) & 0xFF, unit=int(info[7]) >> 8)
+        return d
 
     def library_fingerprints_info(self):
         """arp_library_fingerprints_info: rows (references and poses), references, columns, planes, words per row and word slices

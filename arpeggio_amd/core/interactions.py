@@ -564,6 +564,84 @@ class InteractionComplex:
         return _lfp.write_library_fingerprints(wd, self.id, fp['best'], fp['reference_count'], fp['ligand_pose_off'],
                                                getattr(self, 'library_fingerprints_ligands', None))
 
+    def run_library_shortlist(self, library, pose_off, xyz, h_xyz, k, by='summary', unit='ligands', weights=None, refs=None, min_score=None,
+                              planes=False, chunk=None, contacts=None, interacting_entities=None, level='residue', interacting_cutoff=5.0,
+                              vdw_comp=0.1):
+        """Extension beside the mirror: the best ``k`` ligands of a library (``unit='ligands'``: each by its best pose) or its best
+        ``k`` global poses (``unit='poses'``), ranked ON THE DEVICE, with the chosen poses' records — no other pose's record is
+        copied (``arpeggio_amd.library_shortlist``).  ``library``, ``pose_off``, ``xyz`` and ``h_xyz`` as
+        ``run_library_fingerprints`` takes them.  ``by='summary'``: the score is ``weights`` (``library_shortlist.weights``;
+        default: one per record) times the summary slots; ``by='tanimoto'``: the Tanimoto similarity of the pose's fingerprint
+        (``contacts`` as ``library_fingerprints.planes`` reads it, at ``level``) to the references ``refs``
+        (``library_fingerprints.references``), the best over them, in 32 fractional bits.  Higher is better, a tie goes to the
+        lower global pose; ``min_score`` drops entries below it.  ``contacts`` / ``interacting_entities`` also name the records
+        that are fetched (``contact_filter.masks``; ``None`` = all).  ``planes=True``: the ring and amide tables of the chosen
+        poses as well, and the planes half of ``weights`` (the ligand packs need ``ring_atoms`` and ``amide_atoms``).  Every chunk
+        of ``chunk`` global poses (default: all at once; a ligand's poses may be cut between two) is one
+        ``Context.library_summary`` (``library_planes_summary``, ``library_fingerprints``) and
+        ``Context.library_shortlist(k)`` — no full fetch; the chunks' shortlists are shifted to the caller's global poses and
+        merged on the host (``library_shortlist.merge``).  Returns the shortlist ``arpeggio_amd.library_shortlist`` describes
+        (also kept in ``self.library_shortlist``, the ligands in ``self.library_shortlist_ligands``)."""
+        from .. import _capi, contact_filter, ligand_library as _ll, library_fingerprints as _lfp, library_shortlist as _lsl
+        if by not in ('summary', 'tanimoto'):
+            raise ValueError(f"run_library_shortlist: by must be 'summary' or 'tanimoto', not {by!r}")
+        if unit not in _lsl.UNITS:
+            raise ValueError(f'run_library_shortlist: unit must be one of {_lsl.UNITS}')
+        if int(k) < 1:
+            raise ValueError('run_library_shortlist: k must be at least 1')
+        sift_mask = 0 if contacts is None else contact_filter.masks(contacts, None)[0]
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        lib = library if isinstance(library, dict) else _ll.pack(list(library))
+        off = np.ascontiguousarray(pose_off, np.int64)
+        if off.shape != (_ll.n_ligands(lib) + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] < 1:
+            raise ValueError('run_library_shortlist: pose_off must be [L + 1], start at 0, not decrease and hold a pose')
+        if by == 'tanimoto':
+            if level not in _lfp.LEVELS:
+                raise ValueError(f"run_library_shortlist: level must be 'residue' or 'atom', not {level!r}")
+            n_nodes = self.pc.n_residues if level == 'residue' else self.pc.n_atoms
+            r = _lfp.validate(refs, n_nodes) if isinstance(refs, dict) else _lfp.references(refs or [], n_nodes)
+            if _lfp.n_references(r) < 1:
+                raise ValueError('run_library_shortlist: 1 ... MAX_REFS references')
+            fp_planes = _lfp.planes(contacts)
+        elif weights is None:
+            weights = _lsl.weights(atom_atom={'records': 1})
+        if self._ctx is None:
+            self.initialize()
+        ctx = self._ctx
+        ctx.set_ligand_library(lib)
+        if planes:
+            ctx.set_ligand_library_planes(lib)
+        tables = _lsl.TABLES if planes else ('atom_atom',)
+        h = np.zeros(0) if h_xyz is None else h_xyz
+        parts = []
+        for off_c, a, _, xc, hc in _ll.chunk_poses(lib, off, xyz, h, chunk if chunk else _capi.POSES_MAX_POSES):
+            ctx.library_summary(off_c, xc, hc, interacting_cutoff, vdw_comp, False)
+            if planes:
+                ctx.library_planes_summary(off_c, xc)
+            if by == 'tanimoto':
+                ctx.library_fingerprints(r, fp_planes, ctype_mask, by_residue=level == 'residue')
+                part = ctx.library_shortlist('tanimoto', unit=unit, ref=-1, k=int(k), min_score=min_score, tables=tables, sift_mask=sift_mask,
+                                             ctype_mask=ctype_mask)
+            else:
+                part = ctx.library_shortlist('summary', unit=unit, weights=weights, k=int(k), min_score=min_score, tables=tables,
+                                             sift_mask=sift_mask, ctype_mask=ctype_mask)
+            parts.append(_lsl.shift(part, a))
+        out = _lsl.merge(parts, int(k), unit)
+        out.update(by=by, unit=unit)
+        self.library_shortlist = out
+        self.library_shortlist_ligands = lib.get('ligands')
+        return out
+
+    def write_library_shortlist(self, wd):
+        """'<id>.libraryshortlist': the atom-atom records of the last ``run_library_shortlist`` as CSV
+        (``library_shortlist.write_csv``)."""
+        from .. import library_shortlist as _lsl
+        if getattr(self, 'library_shortlist', None) is None:
+            raise AttributeError('no library shortlist yet: call run_library_shortlist() first')
+        if getattr(self, 'library_shortlist_ligands', None) is None:
+            raise AttributeError('the library of the last run_library_shortlist() carried no ligand packs (labels)')
+        return _lsl.write_library_shortlist(wd, self.id, self.library_shortlist, self.pc, self.library_shortlist_ligands, self.component_types)
+
     def write_pose_planes(self, wd):
         """'<id>.poseplanes': the ring / amide tables of the last ``run_poses(..., planes=True)`` as CSV (``poses.write_planes_csv``)."""
         from .. import poses as _poses

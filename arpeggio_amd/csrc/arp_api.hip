@@ -43,6 +43,7 @@
 #include "arp_poses_planes.h"
 #include "arp_poses_fingerprints.h"
 #include "arp_poses_shortlist.h"
+#include "arp_library_shortlist.h"
 #include "arp_poses_clusters.h"
 #include "arp_library.h"
 #include "arp_library_fingerprints.h"
@@ -341,7 +342,8 @@ struct LibraryResult {
     PoseRecords rec;
     DevBuf<long long> best_n, best_score;
     DevBuf<int> best_pose;
-    int64_t L = 0, T = 0, blocks = 0;
+    std::vector<int64_t> host_pose_off;                 // [L + 1] as the launch took it (the library shortlist: candidates, same poses)
+    int64_t L = 0, T = 0, blocks = 0, nx = 0;           // nx: the floats of the uploaded poses
     bool valid = false, best_valid = false;
     void release() {
         lig_of.release(); tab.release(); rec.release(); best_n.release(); best_score.release(); best_pose.release(); valid = best_valid = false;
@@ -384,10 +386,11 @@ struct LibraryFpTables {
 // the shortlist of the resident poses result (arp_poses_shortlist_launch, arp_poses_shortlist.h): a sort scratch of its own (the
 // source's sorted buffers are not disturbed), the chosen poses with their scores and summary rows, lengths and offsets per table,
 // the word block of the one wait, and the chosen poses' records in one slab.  Valid only while the poses result is; one that
-// read the poses-planes result (`planes`) goes with that as well
+// read the poses-planes result (`planes`) goes with that as well.  The library shortlist (arp_library_shortlist_launch,
+// arp_library_shortlist.h) is a second object of the same shape over the library's results: `ligand` and `unit` are its own
 struct ShortlistResult {
     SortScratch sort;
-    DevBuf<int> ids, pose;
+    DevBuf<int> ids, pose, ligand;
     DevBuf<long long> score;
     DevBuf<uint32_t> summary, pl_summary;
     DevBuf<unsigned long long> len, off, words;
@@ -395,11 +398,11 @@ struct ShortlistResult {
     size_t aa_off[5] = {0, 0, 0, 0, 0};
     PplColumns col{};
     int64_t K = 0, ncand = 0, total[PSL_TABLES] = {0, 0, 0, 0, 0}, launches = 0;
-    int kind = 0;
+    int kind = 0, unit = 0;
     uint32_t tables = 0;
     bool valid = false, planes = false;
     void release() {
-        sort.release(); ids.release(); pose.release(); score.release(); summary.release(); pl_summary.release(); len.release(); off.release();
+        sort.release(); ids.release(); pose.release(); ligand.release(); score.release(); summary.release(); pl_summary.release(); len.release(); off.release();
         words.release(); slab.release(); valid = false;
     }
 };
@@ -480,7 +483,8 @@ struct LibraryPlanesResult {
     DevBuf<uint8_t> slab;
     PplColumns col{};
     int64_t counts[4] = {0, 0, 0, 0};
-    int64_t L = 0, T = 0, blocks = 0, launches = 0;
+    std::vector<int64_t> host_pose_off;                 // [L + 1] as the launch took it
+    int64_t L = 0, T = 0, blocks = 0, launches = 0, nx = 0;
     bool valid = false;
     void release() {
         hist.release(); res_off.release(); res_atoms.release(); sums.release(); grid.release(); lig_of.release(); tab.release(); xyz.release();
@@ -742,6 +746,7 @@ struct arp_ctx {
     LibraryFpTables libfpx;               // ... its references, arp_library_fingerprints_best_launch
     LibraryPlaneAtoms libplanes;          // arp_set_ligand_library_planes
     LibraryPlanesResult libpl;            // arp_library_planes_launch
+    ShortlistResult libshortlist;         // arp_library_shortlist_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -961,7 +966,8 @@ enum : unsigned {
     POSE_LIBRARY_CONTACTS = 1u << 10, POSE_LIBRARY_BEST = 1u << 11,
     POSE_LIBRARY_FINGERPRINT = 1u << 12, POSE_LIBRARY_FP_BEST = 1u << 13,
     POSE_LIBRARY_PLANE_ATOMS = 1u << 14,      // the library's plane table (arp_set_ligand_library_planes)
-    POSE_LIBRARY_PLANES_SETUP = 1u << 15, POSE_LIBRARY_PLANES = 1u << 16
+    POSE_LIBRARY_PLANES_SETUP = 1u << 15, POSE_LIBRARY_PLANES = 1u << 16,
+    POSE_LIBRARY_SHORTLIST = 1u << 17
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -983,7 +989,10 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         // CSR) reads the structure alone; the result reads the structure, the library and the plane table, and no selection
         {&c->libplanes.resident, POSE_LIBRARY_PLANE_ATOMS, POSE_LIBRARY},
         {&c->libpl.setup, POSE_LIBRARY_PLANES_SETUP, POSE_STRUCTURE},
-        {&c->libpl.valid, POSE_LIBRARY_PLANES, POSE_STRUCTURE | POSE_LIBRARY | POSE_LIBRARY_PLANE_ATOMS}};
+        {&c->libpl.valid, POSE_LIBRARY_PLANES, POSE_STRUCTURE | POSE_LIBRARY | POSE_LIBRARY_PLANE_ATOMS},
+        // the library shortlist reads the library result and, made with a ring or amide table or weight, the
+        // library-planes result; the library fingerprint only while its launch runs (scores are taken then)
+        {&c->libshortlist.valid, POSE_LIBRARY_SHORTLIST, POSE_LIBRARY_CONTACTS | (c->libshortlist.planes ? POSE_LIBRARY_PLANES : 0u)}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -2591,6 +2600,7 @@ void arp_destroy(arp_ctx* c) {
     c->pplanes.release();
     c->posefp.release();
     c->shortlist.release();
+    c->libshortlist.release();
     c->clusters.release();
     c->library.release();
     c->libres.release();
@@ -5910,7 +5920,7 @@ int arp_library_contacts_launch(arp_ctx* c, const int64_t* pose_off, const float
         return check_launch(c, "k_library_contacts");
     };
     CHK(pose_records_launch(c, fn, R.rec, T, xyz, (size_t)nx, h_xyz, (size_t)nh, A.ibits + A.abits + index_bits(T), A.ibits, A.abits, enqueue, count));
-    R.L = L; R.T = T; R.blocks = (int64_t)blocks; R.valid = true;
+    R.L = L; R.T = T; R.blocks = (int64_t)blocks; R.nx = nx; R.host_pose_off.assign(pose_off, pose_off + L + 1); R.valid = true;
     return ARP_OK;
 }
 
@@ -6286,7 +6296,7 @@ int arp_library_planes_launch(arp_ctx* c, const int64_t* pose_off, const float* 
     CHK(plane_records_launch(c, fn, PlaneRecords{R.rec, R.ctr, R.pose_off, R.summary, R.sort, R.slab, R.col, R.counts, R.launches}, T,
                              2 + A.pbits + 2 * A.idbits, "k_library_planes", "a pose brings more than ARP_POSES_PLANES_MAX_NEAR receptor rings within 3 A of a ligand atom",
                              enqueue, counts));
-    R.L = L; R.T = T; R.blocks = blocks; R.valid = true;
+    R.L = L; R.T = T; R.blocks = blocks; R.nx = nx; R.host_pose_off.assign(pose_off, pose_off + L + 1); R.valid = true;
     return ARP_OK;
 }
 
@@ -6748,6 +6758,91 @@ static void shortlist_info(const ShortlistResult& S, int64_t info[8]) {
     for (int q = 0; q < 8; ++q) info[q] = (S.valid || q == 6) ? v[q] : 0;
 }
 
+// the checks of tables and the record filter that both shortlist launches make, in this order
+static int shortlist_filter_refusals(arp_ctx* c, const std::string& fn, uint32_t tables, uint32_t sift_mask, uint32_t ctype_mask) {
+    if (!tables || (tables & ~((1u << ARP_SHORTLIST_TABLES) - 1u))) FAIL(c, ARP_E_ARG, fn + "tables must be a non-zero mask of the five tables");
+    if (sift_mask & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_mask has bits beyond the 15 SIFt bits");
+    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
+    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 keeps no record");
+    return ARP_OK;
+}
+
+// What the pose shortlist and the library shortlist share once their refusals are through and the previous shortlist is void:
+// A names the sources, the score's arguments, the threshold and the filter; this fills in the result.  `ids`: the caller's list
+// (kind LIST), else `score` enqueues the keys and payloads of the M ranked candidates into A.key / A.val.  `same_poses` (when the
+// planes source is read) enqueues the comparison into the flag word; `riders` is enqueued once the candidates stand (A.skey /
+// A.sval or A.ids).  One wait.
+struct ShortlistSteps {
+    std::function<void(void*)> same_poses;
+    std::function<void(const PslArgs&)> score, riders;
+    const char* differ;
+};
+static int shortlist_make(arp_ctx* c, const std::string& fn, ShortlistResult& S, PslArgs& A, const int32_t* ids, int64_t M, int64_t ncand,
+                          const ShortlistSteps& steps) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool list = A.kind == PSL_LIST;
+    HIPCHK(c, S.words.reserve(8));
+    HIPCHK(c, S.pose.reserve((size_t)ncand));
+    HIPCHK(c, S.score.reserve((size_t)ncand));
+    HIPCHK(c, S.summary.reserve((size_t)ncand * PSL_SLOTS));
+    HIPCHK(c, S.pl_summary.reserve((size_t)ncand * PSL_SLOTS));
+    HIPCHK(c, S.len.reserve((size_t)ncand * PSL_TABLES));
+    HIPCHK(c, S.off.reserve(((size_t)ncand + 1) * PSL_TABLES));
+    A.ncand = (int)ncand;
+    A.pose = S.pose.p; A.score = S.score.p; A.out_summary = S.summary.p; A.out_pl_summary = S.pl_summary.p;
+    A.len = S.len.p; A.off = S.off.p; A.words = S.words.p;
+    HIPCHK(c, hipMemsetAsync(S.words.p, 0, 8 * sizeof(unsigned long long), c->stream));
+    if (S.planes) steps.same_poses(S.words.p + PSL_W_DIFFER);
+    if (list) {
+        CHK(upload_async(c, S.ids, (const int*)ids, (size_t)ncand));      // (the wait below is before the caller's array goes away)
+        A.ids = S.ids.p;
+    } else {
+        // ---- score and rank: keys of all 64 bits, stable, so that ties stay in ascending pose
+        CHK(reserve_key_sort(c, S.sort, (size_t)M, (size_t)M));
+        A.key = S.sort.key[0].p; A.val = S.sort.val[0].p;
+        steps.score(A);
+        int sorted = 0;
+        enqueue_key_sort(c, S.sort, (size_t)M, 64, &sorted);
+        A.skey = S.sort.key[sorted].p; A.sval = S.sort.val[sorted].p;
+    }
+    // ---- lengths, offsets, and the one wait
+    hipLaunchKernelGGL(k_psl_lengths, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_psl_offsets, dim3(PSL_TABLES), dim3(1024), 0, c->stream, A);
+    if (steps.riders) steps.riders(A);
+    CHK(check_launch(c, (fn + "score / sort / lengths / offsets").c_str()));
+    CHK(stage_copy(c, S.words.p, 8 * sizeof(unsigned long long)));
+    unsigned long long h[8];
+    memcpy(h, c->table_stage, sizeof(h));
+    ++S.launches;
+    if (S.planes && h[PSL_W_DIFFER] != 0) FAIL(c, ARP_E_ARG, fn + steps.differ);
+    if (h[PSL_W_ERR] != 0) FAIL(c, ARP_E_HIP, fn + "device error (a pose id out of range)");
+    if (h[PSL_W_K] > (unsigned long long)ncand) FAIL(c, ARP_E_HIP, fn + "chosen count out of range");
+    for (int t = 0; t < PSL_TABLES; ++t)
+        if (h[PSL_W_TOTAL + t] >= (1ull << 31)) FAIL(c, ARP_E_CAPACITY, fn + "a table of 2^31 records or more (a smaller k)");
+    // ---- the columns of the requested tables in one slab: atom-atom as the sorted slab is laid out, the others as the
+    // poses-planes result lays out its own
+    size_t bytes = 0;
+    sorted_layout((size_t)h[PSL_W_TOTAL], S.aa_off, &bytes, (size_t)h[PSL_W_TOTAL]);
+    const size_t m[4] = {(size_t)h[PSL_W_TOTAL + 1], (size_t)h[PSL_W_TOTAL + 2], (size_t)h[PSL_W_TOTAL + 3], (size_t)h[PSL_W_TOTAL + 4]};
+    const PlaneLayout lay = plane_tables_layout(m, bytes, &bytes);
+    HIPCHK(c, S.slab.reserve(std::max<size_t>(bytes, 256)));
+    const PplColumns col = bind_plane_columns(S.slab.p, lay);
+    const Columns aa{S.slab.p, S.aa_off};
+    A.oi = aa[0]; A.oj = aa[1]; A.od = aa[2]; A.os = aa[3]; A.oct = aa[4];
+    A.opl = col;
+    int64_t all = 0;
+    for (int t = 0; t < PSL_TABLES; ++t) { A.total[t] = (long long)h[PSL_W_TOTAL + t]; all += A.total[t]; }
+    if (all > 0) {
+        hipLaunchKernelGGL(k_psl_gather, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
+        CHK(check_launch(c, (fn + "gather").c_str()));
+    }
+    S.col = col;
+    S.K = (int64_t)h[PSL_W_K]; S.ncand = ncand; S.kind = A.kind; S.tables = A.tables;
+    for (int t = 0; t < PSL_TABLES; ++t) S.total[t] = A.total[t];
+    S.valid = true;
+    return ARP_OK;
+}
+
 int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, int64_t ref, const int32_t* pose_ids, int64_t n_ids, int64_t skip,
                                int64_t k, int64_t min_score, uint32_t tables, uint32_t sift_mask, uint32_t ctype_mask, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
@@ -6762,10 +6857,7 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     if (kind != ARP_SHORTLIST_LIST && kind != ARP_SHORTLIST_SUMMARY && kind != ARP_SHORTLIST_TANIMOTO)
         FAIL(c, ARP_E_ARG, fn + "unknown kind (ARP_SHORTLIST_LIST, ARP_SHORTLIST_SUMMARY or ARP_SHORTLIST_TANIMOTO)");
     const int64_t P = R.P;
-    if (!tables || (tables & ~((1u << ARP_SHORTLIST_TABLES) - 1u))) FAIL(c, ARP_E_ARG, fn + "tables must be a non-zero mask of the five tables");
-    if (sift_mask & ~ARP_FILTER_SIFT_ALL) FAIL(c, ARP_E_ARG, fn + "sift_mask has bits beyond the 15 SIFt bits");
-    if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
-    if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 keeps no record");
+    CHK(shortlist_filter_refusals(c, fn, tables, sift_mask, ctype_mask));
     bool planes = (tables >> 1) != 0;
     if (kind == ARP_SHORTLIST_LIST) {
         if (!pose_ids) FAIL(c, ARP_E_ARG, fn + "pose_ids missing (ARP_SHORTLIST_LIST)");
@@ -6794,16 +6886,8 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     // ---- from here on the previous shortlist is gone
     void_pose_results(c, POSE_SHORTLIST);
     S.planes = planes;
-    HIPCHK(c, hipSetDevice(c->device));
     const bool list = kind == ARP_SHORTLIST_LIST;
     const int64_t M = P - skip, ncand = list ? n_ids : std::min(k, M);
-    HIPCHK(c, S.words.reserve(8));
-    HIPCHK(c, S.pose.reserve((size_t)ncand));
-    HIPCHK(c, S.score.reserve((size_t)ncand));
-    HIPCHK(c, S.summary.reserve((size_t)ncand * PSL_SLOTS));
-    HIPCHK(c, S.pl_summary.reserve((size_t)ncand * PSL_SLOTS));
-    HIPCHK(c, S.len.reserve((size_t)ncand * PSL_TABLES));
-    HIPCHK(c, S.off.reserve(((size_t)ncand + 1) * PSL_TABLES));
     PslArgs A{};
     const uint8_t* const slab = R.rec.slab.p;      // (no record: the columns are never read, every segment is empty)
     if (R.rec.count > 0) {
@@ -6820,87 +6904,46 @@ int arp_poses_shortlist_launch(arp_ctx* c, int kind, const int32_t* weights32, i
     if (kind == ARP_SHORTLIST_SUMMARY)
         for (int q = 0; q < 2 * PSL_SLOTS; ++q) A.w[q] = weights32[q];
     if (kind == ARP_SHORTLIST_TANIMOTO) { A.fp_count = F.count.p; A.fp_cross = F.cross.p; A.Q = (int)F.Q; A.ref = (int)ref; }
-    A.ncand = (int)ncand; A.min_score = list ? INT64_MIN : min_score;
+    A.min_score = list ? INT64_MIN : min_score;
     A.tables = tables; A.sift_mask = sift_mask; A.ctype_mask = ctype_mask;
-    A.pose = S.pose.p; A.score = S.score.p; A.out_summary = S.summary.p; A.out_pl_summary = S.pl_summary.p;
-    A.len = S.len.p; A.off = S.off.p; A.words = S.words.p;
-    HIPCHK(c, hipMemsetAsync(S.words.p, 0, 8 * sizeof(unsigned long long), c->stream));
-    if (planes) enqueue_same_poses(c, S.words.p + PSL_W_DIFFER);
-    if (list) {
-        CHK(upload_async(c, S.ids, (const int*)pose_ids, (size_t)n_ids));      // (the wait below is before the caller's array goes away)
-        A.ids = S.ids.p;
-    } else {
-        // ---- score and rank: keys of all 64 bits, stable, so that ties stay in ascending pose
-        CHK(reserve_key_sort(c, S.sort, (size_t)M, (size_t)M));
-        A.key = S.sort.key[0].p; A.val = S.sort.val[0].p;
-        hipLaunchKernelGGL(k_psl_score, dim3(nblocks(M, 256)), dim3(256), 0, c->stream, A);
-        int sorted = 0;
-        enqueue_key_sort(c, S.sort, (size_t)M, 64, &sorted);
-        A.skey = S.sort.key[sorted].p; A.sval = S.sort.val[sorted].p;
-    }
-    // ---- lengths, offsets, and the one wait
-    hipLaunchKernelGGL(k_psl_lengths, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
-    hipLaunchKernelGGL(k_psl_offsets, dim3(PSL_TABLES), dim3(1024), 0, c->stream, A);
-    CHK(check_launch(c, (fn + "score / sort / lengths / offsets").c_str()));
-    CHK(stage_copy(c, S.words.p, 8 * sizeof(unsigned long long)));
-    unsigned long long h[8];
-    memcpy(h, c->table_stage, sizeof(h));
-    ++S.launches;
-    if (planes && h[PSL_W_DIFFER] != 0) FAIL(c, ARP_E_ARG, fn + "the poses result and the poses-planes result were made from different poses");
-    if (h[PSL_W_ERR] != 0) FAIL(c, ARP_E_HIP, fn + "device error (a pose id out of range)");
-    if (h[PSL_W_K] > (unsigned long long)ncand) FAIL(c, ARP_E_HIP, fn + "chosen count out of range");
-    for (int t = 0; t < PSL_TABLES; ++t)
-        if (h[PSL_W_TOTAL + t] >= (1ull << 31)) FAIL(c, ARP_E_CAPACITY, fn + "a table of 2^31 records or more (a smaller k)");
-    // ---- the columns of the requested tables in one slab: atom-atom as the sorted slab is laid out, the others as the
-    // poses-planes result lays out its own
-    size_t bytes = 0;
-    sorted_layout((size_t)h[PSL_W_TOTAL], S.aa_off, &bytes, (size_t)h[PSL_W_TOTAL]);
-    const size_t m[4] = {(size_t)h[PSL_W_TOTAL + 1], (size_t)h[PSL_W_TOTAL + 2], (size_t)h[PSL_W_TOTAL + 3], (size_t)h[PSL_W_TOTAL + 4]};
-    const PlaneLayout lay = plane_tables_layout(m, bytes, &bytes);
-    HIPCHK(c, S.slab.reserve(std::max<size_t>(bytes, 256)));
-    const PplColumns col = bind_plane_columns(S.slab.p, lay);
-    const Columns aa{S.slab.p, S.aa_off};
-    A.oi = aa[0]; A.oj = aa[1]; A.od = aa[2]; A.os = aa[3]; A.oct = aa[4];
-    A.opl = col;
-    int64_t all = 0;
-    for (int t = 0; t < PSL_TABLES; ++t) { A.total[t] = (long long)h[PSL_W_TOTAL + t]; all += A.total[t]; }
-    if (all > 0) {
-        hipLaunchKernelGGL(k_psl_gather, dim3(nblocks(ncand, 4, 4096), PSL_TABLES), dim3(256), 0, c->stream, A);
-        CHK(check_launch(c, (fn + "gather").c_str()));
-    }
-    S.col = col;
-    S.K = (int64_t)h[PSL_W_K]; S.ncand = ncand; S.kind = kind; S.tables = A.tables;
-    for (int t = 0; t < PSL_TABLES; ++t) S.total[t] = A.total[t];
-    S.valid = true;
+    ShortlistSteps steps{};
+    steps.same_poses = [&](void* flag) { enqueue_same_poses(c, flag); };
+    steps.score = [&](const PslArgs& B) { hipLaunchKernelGGL(k_psl_score, dim3(nblocks(M, 256)), dim3(256), 0, c->stream, B); };
+    steps.differ = "the poses result and the poses-planes result were made from different poses";
+    CHK(shortlist_make(c, fn, S, A, pose_ids, M, ncand, steps));
     shortlist_info(S, info);
     return ARP_OK;
 }
 
 // a shortlist fetch: the device's error word rides along with the pieces (the gather runs after the launch's wait)
-static int shortlist_stage(arp_ctx* c, std::vector<StagePiece>& pieces, const char* fn) {
+static int shortlist_stage(arp_ctx* c, const ShortlistResult& S, std::vector<StagePiece>& pieces, const std::string& fn) {
     unsigned long long err = 0;
-    pieces.push_back(StagePiece{&err, c->shortlist.words.p + PSL_W_ERR, sizeof(err)});
+    pieces.push_back(StagePiece{&err, S.words.p + PSL_W_ERR, sizeof(err)});
     CHK(stage_fetch(c, pieces));
-    if (err != 0) FAIL(c, ARP_E_HIP, std::string(fn) + ": device error (a record beyond its table's total)");
+    if (err != 0) FAIL(c, ARP_E_HIP, fn + ": device error (a record beyond its table's total)");
     return ARP_OK;
 }
 
-int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_t* pose, int64_t* score, uint32_t* summary, uint32_t* planes_summary,
-                              uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift, uint8_t* ctype, int64_t* n_chosen, int64_t* count) {
-    if (!c || !n_chosen || !count) return ARP_E_ARG;
-    const ShortlistResult& S = c->shortlist;
-    if (!S.valid)      // (voided wherever the poses result is; with the poses-planes result when it read that)
-        FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: no result (arp_poses_shortlist_launch; a result it was made from was replaced or an input or the selection changed since)");
+// The two fetches of a shortlist, for the pose shortlist and the library shortlist alike.  `fn` names the entry, `launch` the
+// launch and what voids the result, `cap_name` the capacity of the per-entry arrays, `planes_result` the planes source.
+struct ShortlistNames { const char *fn, *launch, *cap_name, *planes_result; };
+static int shortlist_fetch(arp_ctx* c, const ShortlistResult& S, const ShortlistNames& N, int64_t cap_entries, int64_t cap, int32_t* ligand, int32_t* pose,
+                           int64_t* score, uint32_t* summary, uint32_t* planes_summary, uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift,
+                           uint8_t* ctype, int64_t* n_chosen, int64_t* count) {
+    const std::string fn = N.fn;
+    if (!S.valid) FAIL(c, ARP_E_ARG, fn + ": no result (" + N.launch + ")");
     *n_chosen = S.K;
     *count = S.total[0];
     const bool records = i || j || dist || sift || ctype;
-    if ((off || records) && !(S.tables & 1u)) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: the atom-atom table was not requested (tables bit 0)");
-    if (planes_summary && !S.planes) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_fetch: the launch did not read the poses-planes result (no planes_summary)");
-    if ((pose || score || summary || planes_summary || off) && cap_poses < S.K) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_fetch: output buffers too small (cap_poses < *n_chosen)");
-    if (records && cap < S.total[0]) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_fetch: output buffers too small (cap < *count)");
+    if ((off || records) && !(S.tables & 1u)) FAIL(c, ARP_E_ARG, fn + ": the atom-atom table was not requested (tables bit 0)");
+    if (planes_summary && !S.planes) FAIL(c, ARP_E_ARG, fn + ": the launch did not read the " + N.planes_result + " result (no planes_summary)");
+    if ((ligand || pose || score || summary || planes_summary || off) && cap_entries < S.K)
+        FAIL(c, ARP_E_CAPACITY, fn + ": output buffers too small (" + N.cap_name + " < *n_chosen)");
+    if (records && cap < S.total[0]) FAIL(c, ARP_E_CAPACITY, fn + ": output buffers too small (cap < *count)");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t K = (size_t)S.K, n = (size_t)S.total[0];
     std::vector<StagePiece> pieces;
+    want_piece(pieces, ligand, S.ligand.p, K * sizeof(int32_t));
     want_piece(pieces, pose, S.pose.p, K * sizeof(int32_t));
     want_piece(pieces, score, S.score.p, K * sizeof(int64_t));
     want_piece(pieces, summary, S.summary.p, K * PSL_SLOTS * sizeof(uint32_t));
@@ -6914,35 +6957,183 @@ int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_
         want_piece(pieces, sift, slab + S.aa_off[3], n * sizeof(uint16_t));
         want_piece(pieces, ctype, slab + S.aa_off[4], n * sizeof(uint8_t));
     }
-    return shortlist_stage(c, pieces, "arp_poses_shortlist_fetch");
+    return shortlist_stage(c, S, pieces, fn);
+}
+static int shortlist_planes_fetch(arp_ctx* c, const ShortlistResult& S, const ShortlistNames& N, int table, int64_t cap_entries, int64_t cap, uint64_t* off,
+                                  int32_t* first, int32_t* second, void* const v[4], uint8_t* const u[3], int64_t* count) {
+    const std::string fn = N.fn;
+    if (!S.valid) FAIL(c, ARP_E_ARG, fn + ": no result (" + N.launch + ")");
+    if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, fn + ": table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
+    const int t = table;
+    if (!((S.tables >> (t + 1)) & 1u)) FAIL(c, ARP_E_ARG, fn + ": the table was not requested (tables bit table + 1)");
+    *count = S.total[t + 1];
+    bool records = false;
+    CHK(plane_fetch_columns(c, fn + ": ", t, first, second, v, u, &records));
+    if (off && cap_entries < S.K) FAIL(c, ARP_E_CAPACITY, fn + ": output buffers too small (" + N.cap_name + " < chosen poses)");
+    if (records && cap < S.total[t + 1]) FAIL(c, ARP_E_CAPACITY, fn + ": output buffers too small (cap < *count)");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, off, S.off.p + (size_t)(t + 1) * ((size_t)S.ncand + 1), ((size_t)S.K + 1) * sizeof(unsigned long long));
+    if (records) plane_fetch_pieces(pieces, S.col, t, (size_t)S.total[t + 1], first, second, v, u);
+    return shortlist_stage(c, S, pieces, fn);
+}
+
+// (the pose shortlist is voided wherever the poses result is; with the poses-planes result when it read that)
+static const char* const POSE_SHORTLIST_LAUNCH = "arp_poses_shortlist_launch; a result it was made from was replaced or an input or the selection changed since";
+int arp_poses_shortlist_fetch(arp_ctx* c, int64_t cap_poses, int64_t cap, int32_t* pose, int64_t* score, uint32_t* summary, uint32_t* planes_summary,
+                              uint64_t* off, int32_t* i, int32_t* j, float* dist, uint16_t* sift, uint8_t* ctype, int64_t* n_chosen, int64_t* count) {
+    if (!c || !n_chosen || !count) return ARP_E_ARG;
+    return shortlist_fetch(c, c->shortlist, ShortlistNames{"arp_poses_shortlist_fetch", POSE_SHORTLIST_LAUNCH, "cap_poses", "poses-planes"}, cap_poses, cap,
+                           nullptr, pose, score, summary, planes_summary, off, i, j, dist, sift, ctype, n_chosen, count);
 }
 
 int arp_poses_shortlist_planes_fetch(arp_ctx* c, int table, int64_t cap_poses, int64_t cap, uint64_t* off, int32_t* first, int32_t* second, void* v0,
                                      void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, int64_t* count) {
     if (!c || !count) return ARP_E_ARG;
-    const ShortlistResult& S = c->shortlist;
-    if (!S.valid)
-        FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: no result (arp_poses_shortlist_launch; a result it was made from was replaced or an input or the selection changed since)");
-    if (table < 0 || table > 3) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: table must be ARP_POSES_PLANES_ATOM_PLANE ... ARP_POSES_PLANES_GROUP_PLANE");
-    const int t = table;
-    if (!((S.tables >> (t + 1)) & 1u)) FAIL(c, ARP_E_ARG, "arp_poses_shortlist_planes_fetch: the table was not requested (tables bit table + 1)");
-    *count = S.total[t + 1];
     void* const v[4] = {v0, v1, v2, v3};
     uint8_t* const u[3] = {u0, u1, u2};
-    bool records = false;
-    CHK(plane_fetch_columns(c, "arp_poses_shortlist_planes_fetch: ", t, first, second, v, u, &records));
-    if (off && cap_poses < S.K) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap_poses < chosen poses)");
-    if (records && cap < S.total[t + 1]) FAIL(c, ARP_E_CAPACITY, "arp_poses_shortlist_planes_fetch: output buffers too small (cap < *count)");
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<StagePiece> pieces;
-    want_piece(pieces, off, S.off.p + (size_t)(t + 1) * ((size_t)S.ncand + 1), ((size_t)S.K + 1) * sizeof(unsigned long long));
-    if (records) plane_fetch_pieces(pieces, S.col, t, (size_t)S.total[t + 1], first, second, v, u);
-    return shortlist_stage(c, pieces, "arp_poses_shortlist_planes_fetch");
+    return shortlist_planes_fetch(c, c->shortlist, ShortlistNames{"arp_poses_shortlist_planes_fetch", POSE_SHORTLIST_LAUNCH, "cap_poses", "poses-planes"},
+                                  table, cap_poses, cap, off, first, second, v, u, count);
 }
 
 int arp_poses_shortlist_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     shortlist_info(c->shortlist, info);
+    return ARP_OK;
+}
+
+// ---- library shortlist (arp_library_shortlist.h): the resident library results -> ranked poses or ligands -> the
+// chosen poses' records.  The library result, and depending on the arguments the library-planes result and the library
+// fingerprint, are read; only this result's own buffers are written.  The launch is the pose shortlist's (shortlist_make) with the
+// library's arrays behind PslArgs and k_lsl_score as the score step.
+static_assert(LSL_POSES == ARP_LIBRARY_SHORTLIST_POSES && LSL_LIGANDS == ARP_LIBRARY_SHORTLIST_LIGANDS, "arp_library_shortlist.h names the header's constants");
+
+static void library_shortlist_info(const ShortlistResult& S, int64_t info[8]) {
+    shortlist_info(S, info);
+    if (S.valid) info[7] = (int64_t)S.kind | ((int64_t)S.unit << 8);
+}
+
+int arp_library_shortlist_launch(arp_ctx* c, int kind, int unit, const int32_t* weights32, int64_t ref, const int32_t* pose_ids, int64_t n_ids, int64_t k,
+                                 int64_t min_score, uint32_t tables, uint32_t sift_mask, uint32_t ctype_mask, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_library_shortlist_launch: ";
+    ShortlistResult& S = c->libshortlist;
+    const LibraryResult& R = c->libres;
+    const LibraryPlanesResult& L = c->libpl;
+    const PoseFpResult& F = c->libfp;
+    // ---- the refusals, in this order: none of them touches a resident result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    if (kind != ARP_SHORTLIST_LIST && kind != ARP_SHORTLIST_SUMMARY && kind != ARP_SHORTLIST_TANIMOTO)
+        FAIL(c, ARP_E_ARG, fn + "unknown kind (ARP_SHORTLIST_LIST, ARP_SHORTLIST_SUMMARY or ARP_SHORTLIST_TANIMOTO)");
+    if (unit != ARP_LIBRARY_SHORTLIST_POSES && unit != ARP_LIBRARY_SHORTLIST_LIGANDS)
+        FAIL(c, ARP_E_ARG, fn + "unknown unit (ARP_LIBRARY_SHORTLIST_POSES or ARP_LIBRARY_SHORTLIST_LIGANDS)");
+    const int64_t T = R.T;
+    CHK(shortlist_filter_refusals(c, fn, tables, sift_mask, ctype_mask));
+    bool planes = (tables >> 1) != 0;
+    if (kind == ARP_SHORTLIST_LIST) {
+        if (!pose_ids) FAIL(c, ARP_E_ARG, fn + "pose_ids missing (ARP_SHORTLIST_LIST)");
+        if (n_ids < 1 || n_ids > ARP_POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "n_ids must be 1 ... ARP_POSES_MAX_POSES");
+        for (int64_t q = 0; q < n_ids; ++q)
+            if (pose_ids[q] < 0 || pose_ids[q] >= T) FAIL(c, ARP_E_ARG, fn + "pose_ids has an id outside [0, T)");
+        if (unit != ARP_LIBRARY_SHORTLIST_POSES || k != 0 || min_score != INT64_MIN)
+            FAIL(c, ARP_E_ARG, fn + "ARP_SHORTLIST_LIST takes unit = ARP_LIBRARY_SHORTLIST_POSES, k = 0 and min_score = INT64_MIN (the list is the choice)");
+    } else if (k < 1) FAIL(c, ARP_E_ARG, fn + "k must be at least 1");
+    if (kind == ARP_SHORTLIST_SUMMARY) {
+        if (!weights32) FAIL(c, ARP_E_ARG, fn + "weights missing (ARP_SHORTLIST_SUMMARY)");
+        for (int q = 0; q < 2 * PSL_SLOTS; ++q) {
+            if (weights32[q] > ARP_SHORTLIST_MAX_WEIGHT || weights32[q] < -ARP_SHORTLIST_MAX_WEIGHT) FAIL(c, ARP_E_ARG, fn + "weights has an entry beyond +-ARP_SHORTLIST_MAX_WEIGHT = 2^24");
+            if (q >= PSL_SLOTS && weights32[q] != 0) planes = true;
+        }
+    }
+    if (kind == ARP_SHORTLIST_TANIMOTO) {
+        if (!F.valid) FAIL(c, ARP_E_ARG, fn + "no library fingerprint (arp_library_fingerprints_launch; ARP_SHORTLIST_TANIMOTO)");
+        if (F.Q < 1) FAIL(c, ARP_E_ARG, fn + "the library fingerprint has no references (n_refs = 0)");
+        if (ref < -1 || ref >= F.Q) FAIL(c, ARP_E_ARG, fn + "ref must be -1 or in [0, n_refs)");
+        if (F.P != F.Q + T) FAIL(c, ARP_E_HIP, fn + "the library fingerprint and the library result differ in T");      // (never: it goes with the result)
+    }
+    if (planes) {
+        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no library-planes result (arp_library_planes_launch; the structure, the library or its plane table changed since)");
+        if (L.L != R.L || L.T != T || L.host_pose_off != R.host_pose_off || L.nx != R.nx)
+            FAIL(c, ARP_E_ARG, fn + "the library result and the library-planes result differ in ligands, poses or pose ranges (launch both on the same poses)");
+    }
+    // ---- from here on the previous library shortlist is gone
+    void_pose_results(c, POSE_LIBRARY_SHORTLIST);
+    S.planes = planes;
+    S.unit = unit;
+    const bool list = kind == ARP_SHORTLIST_LIST, ligands = unit == ARP_LIBRARY_SHORTLIST_LIGANDS;
+    int64_t posed = 0;      // the ligands with at least one pose: the candidates of unit ligands
+    for (int64_t l = 0; l < R.L; ++l) posed += R.host_pose_off[(size_t)l + 1] > R.host_pose_off[(size_t)l] ? 1 : 0;
+    const int64_t M = ligands ? R.L : T, ncand = list ? n_ids : std::min(k, ligands ? posed : T);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, S.ligand.reserve((size_t)ncand));
+    PslArgs A{};
+    const uint8_t* const slab = R.rec.slab.p;      // (no record: the columns are never read, every segment is empty)
+    if (R.rec.count > 0) {
+        A.ci = (const int*)(slab + R.rec.off[0]); A.cj = (const int*)(slab + R.rec.off[1]); A.cd = (const float*)(slab + R.rec.off[2]);
+        A.cs = (const uint16_t*)(slab + R.rec.off[3]); A.cct = slab + R.rec.off[4];
+    }
+    A.aa_off = R.rec.pose_off.p; A.aa_count = R.rec.count;
+    A.summary = R.rec.summary.p; A.P = (int)T;
+    if (planes) {
+        A.pl = L.col; A.pl_off = L.pose_off.p; A.pl_summary = L.summary.p;
+        for (int t = 0; t < 4; ++t) A.pl_count[t] = L.counts[t];
+    }
+    A.kind = kind; A.M = (int)M;
+    A.min_score = list ? INT64_MIN : min_score;
+    A.tables = tables; A.sift_mask = sift_mask; A.ctype_mask = ctype_mask;
+    LslScore W{};
+    W.L = (int)R.L; W.T = (int)T; W.lig_pose_off = R.tab.p;
+    W.summary = A.summary; W.pl_summary = A.pl_summary;
+    if (kind == ARP_SHORTLIST_SUMMARY)
+        for (int q = 0; q < 2 * PSL_SLOTS; ++q) W.w[q] = weights32[q];
+    if (kind == ARP_SHORTLIST_TANIMOTO) { W.fp_count = F.count.p; W.fp_cross = F.cross.p; W.Q = (int)F.Q; W.ref = (int)ref; }
+    ShortlistSteps steps{};
+    steps.same_poses = [&](void* flag) {
+        hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(R.nx, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.rec.xyz.p,
+                           (const uint32_t*)L.xyz.p, (long long)R.nx, (uint32_t*)flag);
+    };
+    steps.score = [&](const PslArgs& B) {
+        W.key = B.key; W.val = B.val;
+        const bool summary = kind == ARP_SHORTLIST_SUMMARY;
+        const auto kernel = ligands ? (summary ? k_lsl_score<LSL_LIGANDS, PSL_SUMMARY> : k_lsl_score<LSL_LIGANDS, PSL_TANIMOTO>)
+                                    : (summary ? k_lsl_score<LSL_POSES, PSL_SUMMARY> : k_lsl_score<LSL_POSES, PSL_TANIMOTO>);
+        hipLaunchKernelGGL(kernel, dim3(ligands ? nblocks(M * 64, 256, 2048) : nblocks(M, 256)), dim3(256), 0, c->stream, W);
+    };
+    steps.riders = [&](const PslArgs& B) {
+        hipLaunchKernelGGL(k_lsl_ligands, dim3(nblocks(ncand, 256)), dim3(256), 0, c->stream, B, (const int*)R.lig_of.p, S.ligand.p);
+    };
+    steps.differ = "the library result and the library-planes result were made from different poses";
+    CHK(shortlist_make(c, fn, S, A, pose_ids, M, ncand, steps));
+    library_shortlist_info(S, info);
+    return ARP_OK;
+}
+
+// (the library shortlist is voided wherever the library result is; with the library-planes result when it read that)
+static const ShortlistNames library_shortlist_names(const char* fn) {
+    return ShortlistNames{fn, "arp_library_shortlist_launch; a result it was made from was replaced or the structure, the library or its plane table changed since",
+                          "cap_entries", "library-planes"};
+}
+int arp_library_shortlist_fetch(arp_ctx* c, int64_t cap_entries, int64_t cap, int32_t* ligand, int32_t* pose, int64_t* score, uint32_t* summary,
+                                uint32_t* planes_summary, uint64_t* off, int32_t* i, int32_t* a, float* dist, uint16_t* sift, uint8_t* ctype,
+                                int64_t* n_chosen, int64_t* count) {
+    if (!c || !n_chosen || !count) return ARP_E_ARG;
+    return shortlist_fetch(c, c->libshortlist, library_shortlist_names("arp_library_shortlist_fetch"), cap_entries, cap, ligand, pose, score, summary,
+                           planes_summary, off, i, a, dist, sift, ctype, n_chosen, count);
+}
+
+int arp_library_shortlist_planes_fetch(arp_ctx* c, int table, int64_t cap_entries, int64_t cap, uint64_t* off, int32_t* first, int32_t* second, void* v0,
+                                       void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    void* const v[4] = {v0, v1, v2, v3};
+    uint8_t* const u[3] = {u0, u1, u2};
+    return shortlist_planes_fetch(c, c->libshortlist, library_shortlist_names("arp_library_shortlist_planes_fetch"), table, cap_entries, cap, off, first,
+                                  second, v, u, count);
+}
+
+int arp_library_shortlist_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    library_shortlist_info(c->libshortlist, info);
     return ARP_OK;
 }
 

@@ -1348,8 +1348,8 @@ int arp_poses_clusters_info(arp_ctx* ctx, int64_t info[8]);
  *   is asked for).  arp_library_info: info[0] = L, [3] = TA, [4] = hydrogen rows, [6] = the largest S_l of the resident
  *   library; [1] = T, [2] = records, [5] = blocks of k_library_contacts (poses are taken with a grid stride) of the resident
  *   result; [7] = 1 while a best-pose table is resident.
- * OUT OF SCOPE: the shortlist and clusters over a library result (fingerprints: arp_library_fingerprints_launch below; the
- *   ligands' own rings and amides: arp_library_planes_launch below); peptide and covalent ligands;
+ * OUT OF SCOPE: clusters over a library result (fingerprints: arp_library_fingerprints_launch below; the ligands' own rings and
+ *   amides: arp_library_planes_launch below; the shortlist: arp_library_shortlist_launch below); peptide and covalent ligands;
  *   cutoffs beyond 6.0; a batch, models or a shard as the receptor; the per-atom accumulators. */
 #define ARP_LIBRARY_MAX_LIGANDS (1 << 16)
 #define ARP_LIBRARY_MAX_ATOMS 256
@@ -1401,7 +1401,8 @@ int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, 
  *   new library launch) and after a new fingerprint launch; its best-pose table goes with it.  arp_set_selection voids neither.
  *   Making either voids nothing else: the library result, its best-pose table and every pose result stay fetchable and
  *   byte-equal.
- * OUT OF SCOPE: class planes; the all-pairs matrix; a shortlist or clusters over the library fingerprint. */
+ * OUT OF SCOPE: class planes; the all-pairs matrix; clusters over the library fingerprint (the shortlist by it:
+ *   arp_library_shortlist_launch below). */
 #define ARP_LIBFP_MAX_FEATURES (1 << 22)
 int arp_library_fingerprints_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
                                     const int64_t* ref_off, const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]);
@@ -1466,8 +1467,8 @@ int arp_library_fingerprints_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64
  *   new launch.  arp_set_selection does NOT void it.  Making it voids nothing: the bags of the last pass, every table made from
  *   them, every pose result, the library contacts, their best-pose table and the library fingerprints stay fetchable and
  *   byte-equal.
- * OUT OF SCOPE: class planes of the library fingerprints, the shortlist and clusters over a library (the next steps, which read
- *   this table); arp_library_best_launch over this summary; peptide and covalent ligands; a batch, models or a shard as the
+ * OUT OF SCOPE: class planes of the library fingerprints and clusters over a library (the shortlist, with the best pose per
+ *   ligand over this summary: arp_library_shortlist_launch below); peptide and covalent ligands; a batch, models or a shard as the
  *   receptor; receptor - receptor records between unaffected entities. */
 #define ARP_LIBRARY_PLANES_MAX_RINGS 32
 #define ARP_LIBRARY_PLANES_MAX_AMIDES 32
@@ -1477,6 +1478,82 @@ int arp_library_planes_launch(arp_ctx* ctx, const int64_t* pose_off, const float
 int arp_library_planes_fetch(arp_ctx* ctx, int table, int64_t cap, uint64_t* pose_off, int32_t* first, int32_t* second, void* v0,
                              void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1, uint8_t* u2, uint32_t* summary, int64_t* count);
 int arp_library_planes_info(arp_ctx* ctx, int64_t info[12]);
+/* Library shortlist: the global poses of the resident library results — or its ligands, each by its best pose — ranked on the
+ * device, and only the chosen poses' records — optionally filtered — compacted for the fetch (csrc/arp_library_shortlist.h,
+ * DESIGN.md 5x).  What arp_poses_shortlist_launch is to the pose results, this is to the library's.
+ *
+ * SOURCES: the resident library result (arp_library_contacts_launch), T global poses of L ligands; wherever bits 1 ... 4 of
+ *   `tables` or a non-zero weight 16 ... 31 ask for it the resident library-planes result (arp_library_planes_launch); for
+ *   ARP_SHORTLIST_TANIMOTO the resident library fingerprint (arp_library_fingerprints_launch).  Nothing of them is written.
+ * POSE SCORE: an int64 of one of the three kinds of arp_poses_shortlist_launch.
+ *   ARP_SHORTLIST_LIST      no score (0).  The chosen poses are the caller's global poses pose_ids[n_ids] in the caller's order:
+ *                           each id in [0, T), repeats allowed, 1 <= n_ids <= ARP_POSES_MAX_POSES.  unit, k and min_score must
+ *                           be ARP_LIBRARY_SHORTLIST_POSES, 0 and INT64_MIN.
+ *   ARP_SHORTLIST_SUMMARY   score[t] = sum_{s<16} w[s] summary[t][s] + sum_{s<16} w[16 + s] planes_summary[t][s], weights32 =
+ *                           int32[32] with |w| <= ARP_SHORTLIST_MAX_WEIGHT (the sum fits 60 bits).  The second half is the
+ *                           library-planes result's summary of the SAME POSES (below).
+ *   ARP_SHORTLIST_TANIMOTO  pose t is row Q + t of the library fingerprint (Q = n_refs >= 1).  For reference q: x =
+ *                           cross[Q + t][q], u = count[Q + t] + count[q] - x, score_q = (u == 0) ? 2^32 : floor(x 2^32 / u) in
+ *                           unsigned 64-bit arithmetic.  ref in [0, Q) names the reference, ref = -1 takes the largest score_q.
+ *                           The reference rows are never candidates (there is no `skip`).  The scores are taken at launch: the
+ *                           shortlist does not read the fingerprint afterwards.
+ * UNIT: ARP_LIBRARY_SHORTLIST_POSES — the candidates are all T global poses.  ARP_LIBRARY_SHORTLIST_LIGANDS — the candidates
+ *   are the ligands that have at least one pose, each represented by its best pose: the highest pose score, ties to the lower
+ *   global pose.  A ligand without poses is never a candidate and never counts towards K.
+ * ORDER: descending score, ties by ascending global pose (poses are ligand-major: for ligands that is ascending ligand).  The
+ *   chosen entries are the first K = min(k, candidates) of that order whose score is >= min_score, k >= 1; INT64_MIN: no
+ *   threshold.  K = 0 is a valid, empty shortlist.
+ * TABLES, RECORD FILTER: as arp_poses_shortlist_launch; bits 1 ... 4 name the four tables of the library-planes result.
+ * RESULT: ligand int32 [K]; pose int32 [K] (the global pose); score int64 [K]; summary uint32 [K][16] and planes_summary uint32
+ *   [K][16], the source rows of the chosen poses, unfiltered; per requested table off uint64 [K + 1] and the table's columns:
+ *   the records of entry r are [off[r], off[r + 1]), the kept records of its pose in the order the source holds them, every
+ *   column with the source's type and bits — atom-atom (i, a, dist, sift, ctype) as arp_library_contacts_fetch, ring / amide
+ *   columns as arp_library_planes_fetch with the complex's ids.  Nothing is truncated; the result is deterministic.
+ * SAME POSES: wherever the library-planes result is read it must have the library result's L, T and per-ligand pose ranges,
+ *   and must have been made from the same uploaded coordinates (the two launches upload their poses independently; compared on
+ *   the device as 32-bit words, the outcome read in the launch's one wait).
+ *
+ * arp_library_shortlist_launch: info[8] as arp_library_shortlist_info gives it.  One host wait (K, the five totals, the
+ *   same-poses flag, the device's error word); every launch and copy goes on the context's stream (arp_use_stream's, if set).
+ *   Refusals are ARP_E_ARG with the cause named, in this order, and none of them touches a resident result: a pass not waited
+ *   for; no library result; unknown kind; unknown unit; tables 0 or beyond bit 4, sift_mask beyond 15 bits, ctype_mask beyond 7
+ *   bits or 0; ARP_SHORTLIST_LIST with pose_ids missing, n_ids out of range, an id outside [0, T), or unit / k / min_score
+ *   set; k < 1; ARP_SHORTLIST_SUMMARY with weights missing or beyond +-2^24; ARP_SHORTLIST_TANIMOTO without a library
+ *   fingerprint, with n_refs = 0, with ref out of range; "no library-planes result"; "differ in ligands, poses or pose
+ *   ranges".  "Made from different poses" is ARP_E_ARG too, found on the device: no shortlist is left after it.
+ *   ARP_E_CAPACITY: a table of 2^31 records or more (no shortlist left).  Every successful launch remakes the result.
+ *   The shortlist is void exactly when the library result is void or replaced (a new structure, models, a batch,
+ *   arp_set_ligand_library, a new arp_library_contacts_launch); one that read the library-planes result also when that is
+ *   (arp_library_planes_launch, arp_set_ligand_library_planes).  arp_set_selection does NOT void it, and neither does a later
+ *   arp_library_fingerprints_launch.  Making it voids nothing: the bags of the last pass, every table made from them, every
+ *   pose result — the pose shortlist included, which is an object of its own —, the library result with its best-pose table,
+ *   the library-planes result and the library fingerprint with its best-pose table stay fetchable and byte-equal.
+ *
+ * arp_library_shortlist_fetch: the per-entry arrays and the atom-atom table; ANY pointer but n_chosen and count may be NULL.
+ *   *n_chosen = K, *count = kept atom-atom records.  ARP_E_CAPACITY when a per-entry array (ligand, pose, score, summary,
+ *   planes_summary, off) is asked for and cap_entries < K, or a record column is asked for and cap < *count.  ARP_E_ARG: no
+ *   valid result; off or a record column of a launch without tables bit 0; planes_summary of a launch that did not read the
+ *   library-planes result.
+ * arp_library_shortlist_planes_fetch: one ring / amide table a call (ARP_POSES_PLANES_ATOM_PLANE ...), columns and their types
+ *   as arp_library_planes_fetch; *count = kept records of the table.  ARP_E_ARG for a table that was not requested and for a
+ *   column the table does not have; ARP_E_CAPACITY as above.  Both fetches pass every piece through the page-locked stage in
+ *   one wait.
+ * arp_library_shortlist_info: info[0] = K, [1] ... [5] = kept records of the five tables (0 for a table not requested), [6] =
+ *   launches that did work so far, [7] = kind | unit << 8.  [0] ... [5] and [7] are 0 while there is no result.
+ * OUT OF SCOPE: clusters over a library; class planes of the library fingerprints; the top m > 1 poses per ligand; a shortlist
+ *   that spans several launches on the device (chunks are merged on the host); multi-GPU. */
+#define ARP_LIBRARY_SHORTLIST_POSES 0
+#define ARP_LIBRARY_SHORTLIST_LIGANDS 1
+int arp_library_shortlist_launch(arp_ctx* ctx, int kind, int unit, const int32_t* weights32, int64_t ref, const int32_t* pose_ids,
+                                 int64_t n_ids, int64_t k, int64_t min_score, uint32_t tables, uint32_t sift_mask,
+                                 uint32_t ctype_mask, int64_t info[8]);
+int arp_library_shortlist_fetch(arp_ctx* ctx, int64_t cap_entries, int64_t cap, int32_t* ligand, int32_t* pose, int64_t* score,
+                                uint32_t* summary, uint32_t* planes_summary, uint64_t* off, int32_t* i, int32_t* a, float* dist,
+                                uint16_t* sift, uint8_t* ctype, int64_t* n_chosen, int64_t* count);
+int arp_library_shortlist_planes_fetch(arp_ctx* ctx, int table, int64_t cap_entries, int64_t cap, uint64_t* off, int32_t* first,
+                                       int32_t* second, void* v0, void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1,
+                                       uint8_t* u2, int64_t* count);
+int arp_library_shortlist_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
