@@ -60,6 +60,7 @@ SYMBOLS = (
     'arp_library_fingerprints_best_launch', 'arp_library_fingerprints_best_fetch',
     'arp_set_ligand_library_planes', 'arp_library_planes_launch', 'arp_library_planes_fetch', 'arp_library_planes_info',
     'arp_library_shortlist_launch', 'arp_library_shortlist_fetch', 'arp_library_shortlist_planes_fetch', 'arp_library_shortlist_info',
+    'arp_library_clusters_launch', 'arp_library_clusters_fetch', 'arp_library_clusters_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -80,6 +81,8 @@ LIBRARY_MAX_LIGANDS, LIBRARY_MAX_ATOMS = 1 << 16, 256
 LIBFP_MAX_FEATURES = 1 << 22     # ARP_LIBFP_MAX_FEATURES: reference features of a library fingerprint launch
 # ... their clusters (ARP_POSECL_*; the rounds enqueued between two waits of arp_poses_clusters_launch)
 POSECL_MAX_CLUSTERS, POSECL_ROUNDS_PER_WAIT = 4096, 64
+# ... the clusters of a library (ARP_LIBCL_*; the rounds enqueued between two waits of arp_library_clusters_launch)
+LIBCL_ALL, LIBCL_LIST, LIBCL_SHORTLIST, LIBCL_WINDOW, LIBCL_LDS_WORDS, LIBCL_ROUNDS_PER_WAIT = 0, 1, 2, 32, 2048, 32
 WBP_BY_RESIDUE = 1 << 1          # ARP_WBP_BY_RESIDUE (beside water_bridges.SAME_RESIDUE, ARP_WB_SAME_RESIDUE)
 PERSIST_STAGE_MAX = 0
 SIM_PLANES, SIM_MAX_MODELS, SIM_BY_RESIDUE = 20, 4096, 1      # ARP_SIM_PLANES, ARP_SIM_MAX_MODELS, ARP_SIM_BY_RESIDUE
@@ -276,6 +279,9 @@ def load():
     L.arp_poses_clusters_launch.argtypes = [vp, vp, i64, i64, C.c_uint64, i64, vp]
     L.arp_poses_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 6 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_poses_clusters_info.argtypes = [vp, vp]
+    L.arp_library_clusters_launch.argtypes = [vp, C.c_int, vp, i64, C.c_uint64, i64, vp]
+    L.arp_library_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 7 + [C.POINTER(i64), C.POINTER(i64)]
+    L.arp_library_clusters_info.argtypes = [vp, vp]
     L.arp_set_ligand_library.argtypes = [vp, i64] + [vp] * 7
     L.arp_library_contacts_launch.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(i64)]
     L.arp_library_contacts_fetch.argtypes = [vp, i64] + [vp] * 7 + [C.POINTER(i64)]
@@ -1534,6 +1540,42 @@ class Context:
         d.update(launches=int(info[6]), kind=int(info[7]) & 0xFF, unit=int(info[7]) >> 8)
         return d
 
+    def library_clusters(self, threshold_q32, *, source='all', order=None, max_clusters=256):
+        """Leader clustering of poses of the resident library result by the Tanimoto similarity of their library fingerprints
+        (``library_fingerprints``, any references), on the device (arp_library_clusters_*; ``arpeggio_amd.library_clusters``).
+        ``source``: 'all' — position m is global pose m; 'list' — global pose ``order[m]`` (int32 ids in [0, T), repeats
+        allowed); 'shortlist' — the entries of the resident ``library_shortlist`` in rank order, read on the device.  Walking
+        the positions, a pose whose similarity (32 fractional bits) to some leader's pose reaches ``threshold_q32``
+        (``library_clusters.threshold_q32``) joins the FIRST such leader; otherwise it becomes the next leader while there are
+        fewer than ``max_clusters`` (at most ``POSECL_MAX_CLUSTERS``), and stays unassigned after that.  Returns a dict:
+        ``pose`` int32 [M] (global pose); ``ligand`` int32 [M]; ``cluster`` int32 [M], -1 when unassigned; ``similarity`` int64
+        [M], to its own leader, 2^32 for a leader, -1 when unassigned; ``leader`` int32 [C]; ``leader_position`` int32 [C];
+        ``size`` uint32 [C]; ``threshold_q32``, ``max_clusters``, ``unassigned``.  No record and no bit is copied."""
+        sources = ('all', 'list', 'shortlist')
+        if source not in sources:
+            raise ValueError(f'library_clusters: source must be one of {sources}')
+        ids = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_clusters_launch(self._h, sources.index(source), _p(ids), 0 if ids is None else len(ids), int(threshold_q32),
+                                                        int(max_clusters), _p(info)), 'arp_library_clusters_launch')
+        M, Cn = int(info[0]), int(info[1])
+        out = dict(pose=np.empty(M, np.int32), ligand=np.empty(M, np.int32), cluster=np.empty(M, np.int32), similarity=np.empty(M, np.int64),
+                   leader=np.empty(Cn, np.int32), leader_position=np.empty(Cn, np.int32), size=np.empty(Cn, np.uint32))
+        n, m = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.arp_library_clusters_fetch(self._h, M, Cn, _p(out['pose']), _p(out['ligand']), _p(out['cluster']), _p(out['similarity']),
+                                                       _p(out['leader']), _p(out['leader_position']), _p(out['size']), C.byref(n), C.byref(m)),
+                    'arp_library_clusters_fetch')
+        out.update(threshold_q32=int(info[7]), max_clusters=int(info[3]), unassigned=int(info[2]))
+        return out
+
+    def library_clusters_info(self):
+        """arp_library_clusters_info: positions, clusters, unassigned positions, ``max_clusters``, words per row and the rounds
+        that elected a leader of the resident library clusters (zeros while there are none), the launches that did work so far,
+        and the threshold."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_clusters_info(self._h, _p(info)), 'arp_library_clusters_info')
+        return dict(zip(('positions', 'clusters', 'unassigned', 'max_clusters', 'words', 'rounds', 'launches', 'threshold_q32'), (int(v) for v in info)))
+
     def library_fingerprints_info(self):
         """arp_library_fingerprints_info: rows (references and poses), references, columns, planes, words per row and word slices
         of the resident library fingerprint (zeros while there is none), the launches so far, and the flags."""
@@ -1979,11 +2021,14 @@ class Context:
         self._check(self._L.arp_poses_fingerprints_info(self._h, _p(fp)), 'arp_poses_fingerprints_info')
         cl = np.zeros(8, np.int64)
         self._check(self._L.arp_poses_clusters_info(self._h, _p(cl)), 'arp_poses_clusters_info')
+        lc = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_clusters_info(self._h, _p(lc)), 'arp_library_clusters_info')
         return dict(candidates=int(s[0]), accepted=int(s[1]), emitted=int(s[2]), binned=int(s[3]), cells=int(s[4]),
                     expand_candidates=int(s[5]), expand_hits=int(s[6]), batch_restarts=int(s[7]),
                     sim_rows=int(m[0]), sim_words=int(m[1]), sim_slices=int(m[2]), sim_launches=int(m[3]),
                     posefp_nodes=int(fp[2]), posefp_words=int(fp[4]), posefp_slices=int(fp[5]), posefp_launches=int(fp[6]),
                     posecl_positions=int(cl[0]), posecl_clusters=int(cl[1]), posecl_launches=int(cl[6]),
+                    libcl_positions=int(lc[0]), libcl_clusters=int(lc[1]), libcl_launches=int(lc[6]),
                     lifetimes_rows=int(lt[0]), lifetimes_launches=int(lt[1]),
                     couple_rows=int(cp[0]), couple_features=int(cp[1]), couple_tile_pairs=int(cp[2]), couple_launches=int(cp[3]),
                     networks_rows=int(nw[0]), networks_nodes=int(nw[1]), networks_launches=int(nw[2]))

@@ -642,6 +642,69 @@ class InteractionComplex:
             raise AttributeError('the library of the last run_library_shortlist() carried no ligand packs (labels)')
         return _lsl.write_library_shortlist(wd, self.id, self.library_shortlist, self.pc, self.library_shortlist_ligands, self.component_types)
 
+    def run_library_clusters(self, library, pose_off, xyz, h_xyz, k, threshold=0.5, by='summary', unit='ligands', weights=None, refs=None,
+                             max_clusters=256, records=False, contacts=None, interacting_entities=None, level='residue',
+                             interacting_cutoff=5.0, vdw_comp=0.1):
+        """Extension beside the mirror: the DIVERSE hits of a library — its best ``k`` ligands (``unit='ligands'``) or global poses
+        ranked as ``run_library_shortlist`` ranks them, then clustered in rank order ON THE DEVICE by the Tanimoto similarity of
+        their library fingerprints (``arpeggio_amd.library_clusters``): one representative per interaction pattern, how many
+        entries stand behind it, and their ligands.  ``library``, ``pose_off``, ``xyz``, ``h_xyz``, ``by``, ``unit``, ``weights``
+        and ``refs`` as ``run_library_shortlist`` takes them (``refs`` may be empty for ``by='summary'``); ``contacts`` / ``level``
+        name the fingerprint's planes and nodes.  Two poses are similar when their similarity is at least ``threshold``
+        (a float in [0, 1]); a pose joins the FIRST similar leader in rank order.  One launch each of
+        ``Context.library_summary``, ``library_fingerprints``, ``library_shortlist`` and ``library_clusters(source='shortlist')``:
+        no bit crosses to the host.  ``records=True``: also ``representatives``, a ``library_shortlist('list')`` over the
+        leaders — only the representatives' records are copied.  There is no ``chunk``: a clustering does not decompose over
+        launches, and a library of more than ``_capi.POSES_MAX_POSES`` global poses is refused.  Returns the clusters
+        ``arpeggio_amd.library_clusters`` describes (also kept in ``self.library_clusters``)."""
+        from .. import _capi, contact_filter, ligand_library as _ll, library_clusters as _lcl, library_fingerprints as _lfp, library_shortlist as _lsl
+        if by not in ('summary', 'tanimoto'):
+            raise ValueError(f"run_library_clusters: by must be 'summary' or 'tanimoto', not {by!r}")
+        if unit not in _lsl.UNITS:
+            raise ValueError(f'run_library_clusters: unit must be one of {_lsl.UNITS}')
+        if int(k) < 1:
+            raise ValueError('run_library_clusters: k must be at least 1')
+        if level not in _lfp.LEVELS:
+            raise ValueError(f"run_library_clusters: level must be 'residue' or 'atom', not {level!r}")
+        thr = _lcl.threshold_q32(threshold)
+        lib = library if isinstance(library, dict) else _ll.pack(list(library))
+        off = np.ascontiguousarray(pose_off, np.int64)
+        if off.shape != (_ll.n_ligands(lib) + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] < 1:
+            raise ValueError('run_library_clusters: pose_off must be [L + 1], start at 0, not decrease and hold a pose')
+        if len(_ll.chunk_plan(off, _capi.POSES_MAX_POSES)) != 1:
+            raise ValueError(f'run_library_clusters: {int(off[-1])} global poses are more than one launch takes ({_capi.POSES_MAX_POSES}); '
+                             'a clustering does not decompose over launches (shortlist the library in chunks first)')
+        n_nodes = self.pc.n_residues if level == 'residue' else self.pc.n_atoms
+        r = _lfp.validate(refs, n_nodes) if isinstance(refs, dict) else _lfp.references(refs or [], n_nodes)
+        if by == 'tanimoto' and _lfp.n_references(r) < 1:
+            raise ValueError('run_library_clusters: 1 ... MAX_REFS references (by tanimoto)')
+        if by == 'summary' and weights is None:
+            weights = _lsl.weights(atom_atom={'records': 1})
+        ctype_mask = contact_filter.masks(None, interacting_entities)[1]
+        if self._ctx is None:
+            self.initialize()
+        ctx = self._ctx
+        ctx.set_ligand_library(lib)
+        ctx.library_summary(off, xyz, np.zeros(0) if h_xyz is None else h_xyz, interacting_cutoff, vdw_comp, False)
+        ctx.library_fingerprints(r, _lfp.planes(contacts), ctype_mask, by_residue=level == 'residue')
+        if by == 'tanimoto':
+            ctx.library_shortlist('tanimoto', unit=unit, ref=-1, k=int(k), tables=('atom_atom',), ctype_mask=ctype_mask)
+        else:
+            ctx.library_shortlist('summary', unit=unit, weights=weights, k=int(k), tables=('atom_atom',), ctype_mask=ctype_mask)
+        out = ctx.library_clusters(thr, source='shortlist', max_clusters=max_clusters)
+        out.update(by=by, unit=unit)
+        if records:
+            out['representatives'] = ctx.library_shortlist('list', pose_ids=out['leader'], tables=('atom_atom',), ctype_mask=ctype_mask)
+        self.library_clusters = out
+        return out
+
+    def write_library_clusters(self, wd):
+        """'<id>.libraryclusters': the clusters of the last ``run_library_clusters`` as CSV (``library_clusters.write_csv``)."""
+        from .. import library_clusters as _lcl
+        if getattr(self, 'library_clusters', None) is None:
+            raise AttributeError('no library clusters yet: call run_library_clusters() first')
+        return _lcl.write_library_clusters(wd, self.id, self.library_clusters)
+
     def write_pose_planes(self, wd):
         """'<id>.poseplanes': the ring / amide tables of the last ``run_poses(..., planes=True)`` as CSV (``poses.write_planes_csv``)."""
         from .. import poses as _poses

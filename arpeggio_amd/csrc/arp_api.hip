@@ -45,6 +45,7 @@
 #include "arp_poses_shortlist.h"
 #include "arp_library_shortlist.h"
 #include "arp_poses_clusters.h"
+#include "arp_library_clusters.h"
 #include "arp_library.h"
 #include "arp_library_fingerprints.h"
 #include "arp_library_planes.h"
@@ -425,6 +426,24 @@ struct ClustersResult {
     }
 };
 
+// the leader clustering of the resident library fingerprint (arp_library_clusters_launch, arp_library_clusters.h): the window
+// form's round state (`start`, the leaders of each round `wl` with their number `nl`, `made`), the per-position and per-cluster
+// arrays with `ligand` beside `pose`, the uploaded list (or none) and the word block of the last wait.  The fingerprint and the
+// shortlist are read only while the launch runs: valid while the library result is (void_pose_results)
+struct LibClustersResult {
+    DevBuf<uint32_t> start, nl, made, size;
+    DevBuf<int> order, wl, pose, ligand, cluster, leader, leader_position;
+    DevBuf<long long> similarity;
+    DevBuf<unsigned long long> words;
+    int64_t M = 0, C = 0, unassigned = 0, max_clusters = 0, W = 0, rounds = 0, launches = 0;
+    uint64_t threshold = 0;
+    bool valid = false;
+    void release() {
+        start.release(); nl.release(); made.release(); size.release(); order.release(); wl.release(); pose.release(); ligand.release();
+        cluster.release(); leader.release(); leader_position.release(); similarity.release(); words.release(); valid = false;
+    }
+};
+
 // the ring / amide contacts of ligand poses (arp_poses_planes_launch, arp_poses_planes.h): the atoms of the resident rings and
 // amides (arp_set_plane_atoms), the movable set's tables (made once per structure, selection and plane atoms), an all-atom 6 A
 // grid of its own by local id (the static order of the passes is left alone), the per-block lists, the records and their sort
@@ -747,6 +766,7 @@ struct arp_ctx {
     LibraryPlaneAtoms libplanes;          // arp_set_ligand_library_planes
     LibraryPlanesResult libpl;            // arp_library_planes_launch
     ShortlistResult libshortlist;         // arp_library_shortlist_launch
+    LibClustersResult libclusters;        // arp_library_clusters_launch
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -967,7 +987,8 @@ enum : unsigned {
     POSE_LIBRARY_FINGERPRINT = 1u << 12, POSE_LIBRARY_FP_BEST = 1u << 13,
     POSE_LIBRARY_PLANE_ATOMS = 1u << 14,      // the library's plane table (arp_set_ligand_library_planes)
     POSE_LIBRARY_PLANES_SETUP = 1u << 15, POSE_LIBRARY_PLANES = 1u << 16,
-    POSE_LIBRARY_SHORTLIST = 1u << 17
+    POSE_LIBRARY_SHORTLIST = 1u << 17,
+    POSE_LIBRARY_CLUSTERS = 1u << 18
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -992,7 +1013,10 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->libpl.valid, POSE_LIBRARY_PLANES, POSE_STRUCTURE | POSE_LIBRARY | POSE_LIBRARY_PLANE_ATOMS},
         // the library shortlist reads the library result and, made with a ring or amide table or weight, the
         // library-planes result; the library fingerprint only while its launch runs (scores are taken then)
-        {&c->libshortlist.valid, POSE_LIBRARY_SHORTLIST, POSE_LIBRARY_CONTACTS | (c->libshortlist.planes ? POSE_LIBRARY_PLANES : 0u)}};
+        {&c->libshortlist.valid, POSE_LIBRARY_SHORTLIST, POSE_LIBRARY_CONTACTS | (c->libshortlist.planes ? POSE_LIBRARY_PLANES : 0u)},
+        // the library clusters read the library result (lig_of, T); the library fingerprint and the library
+        // shortlist only while their launch runs, so they stand behind the library result alone
+        {&c->libclusters.valid, POSE_LIBRARY_CLUSTERS, POSE_LIBRARY_CONTACTS}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -2602,6 +2626,7 @@ void arp_destroy(arp_ctx* c) {
     c->shortlist.release();
     c->libshortlist.release();
     c->clusters.release();
+    c->libclusters.release();
     c->library.release();
     c->libres.release();
     c->libfp.release();
@@ -7262,6 +7287,160 @@ int arp_poses_clusters_fetch(arp_ctx* c, int64_t cap_positions, int64_t cap_clus
 int arp_poses_clusters_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     clusters_info(c->clusters, info);
+    return ARP_OK;
+}
+
+// ---- library clusters (arp_library_clusters.h): the resident library fingerprint -> leaders and members
+// The library fingerprint (bits, count from row Q on), the library result (lig_of) and, for ARP_LIBCL_SHORTLIST, the library
+// shortlist (its pose column) are read while the launch runs; only this result's own buffers are written.  A round is two
+// launches (k_lcl_window, k_lcl_sweep) and elects up to 32 leaders; the rounds are enqueued LIBCL_ROUNDS_PER_WAIT at a time, and
+// after a group that is not the last one word — the next round's start — comes back through the stage; the sentinel ends the
+// rounds.  32 rounds are 64 launches: enqueued in vain (2.3 - 2.9 us a no-op launch) they cost 0.15 - 0.19 ms,
+// under half of the 0.4 - 0.5 ms of the wait they stand in for, and they cover 1024 positions that all lead.
+static_assert(LCL_WINDOW == ARP_LIBCL_WINDOW && LCL_LDS_WORDS == ARP_LIBCL_LDS_WORDS, "arp_library_clusters.h names the header's constants");
+static_assert(LCL_ALL == ARP_LIBCL_ALL && LCL_LIST == ARP_LIBCL_LIST && LCL_SHORTLIST == ARP_LIBCL_SHORTLIST, "... and its sources");
+const int64_t LIBCL_ROUNDS_PER_WAIT = 32;
+
+static void library_clusters_info(const LibClustersResult& S, int64_t info[8]) {
+    const int64_t v[8] = {S.M, S.C, S.unassigned, S.max_clusters, S.W, S.rounds, S.launches, (int64_t)S.threshold};
+    for (int q = 0; q < 8; ++q) info[q] = (S.valid || q == 6) ? v[q] : 0;
+}
+
+int arp_library_clusters_launch(arp_ctx* c, int source, const int32_t* order, int64_t n_order, uint64_t threshold_q32, int64_t max_clusters,
+                                int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const std::string fn = "arp_library_clusters_launch: ";
+    LibClustersResult& S = c->libclusters;
+    const LibraryResult& R = c->libres;
+    const PoseFpResult& F = c->libfp;
+    const ShortlistResult& K = c->libshortlist;
+    // ---- the refusals, in this order: none of them touches a resident result
+    if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    if (!F.valid) FAIL(c, ARP_E_ARG, fn + "no library fingerprint (arp_library_fingerprints_launch)");
+    const int64_t T = R.T, Q = F.Q;
+    if (F.P != Q + T) FAIL(c, ARP_E_ARG, fn + "the library fingerprint and the library result differ in T (P is not Q + T)");
+    if (threshold_q32 > PCL_ONE_Q32) FAIL(c, ARP_E_ARG, fn + "threshold_q32 must be 0 ... 2^32 (1.0)");
+    if (max_clusters < 1 || max_clusters > ARP_POSECL_MAX_CLUSTERS) FAIL(c, ARP_E_ARG, fn + "max_clusters must be 1 ... ARP_POSECL_MAX_CLUSTERS");
+    if (source != ARP_LIBCL_ALL && source != ARP_LIBCL_LIST && source != ARP_LIBCL_SHORTLIST)
+        FAIL(c, ARP_E_ARG, fn + "unknown source (ARP_LIBCL_ALL, ARP_LIBCL_LIST or ARP_LIBCL_SHORTLIST)");
+    if (source == ARP_LIBCL_LIST) {
+        if (!order) FAIL(c, ARP_E_ARG, fn + "order missing (ARP_LIBCL_LIST)");
+        if (n_order < 1 || n_order > ARP_POSES_MAX_POSES) FAIL(c, ARP_E_ARG, fn + "n_order must be 1 ... ARP_POSES_MAX_POSES");
+        for (int64_t q = 0; q < n_order; ++q)
+            if (order[q] < 0 || order[q] >= T) FAIL(c, ARP_E_ARG, fn + "order has an id outside [0, T)");
+    } else if (order || n_order != 0)
+        FAIL(c, ARP_E_ARG, fn + "an order goes with ARP_LIBCL_LIST alone (order = NULL and n_order = 0 otherwise)");
+    if (source == ARP_LIBCL_SHORTLIST) {
+        if (!K.valid) FAIL(c, ARP_E_ARG, fn + "no library shortlist (arp_library_shortlist_launch; ARP_LIBCL_SHORTLIST)");
+        if (K.K < 1) FAIL(c, ARP_E_ARG, fn + "the library shortlist is empty (K = 0)");
+    }
+    // ---- from here on the previous library clusters are gone
+    void_pose_results(c, POSE_LIBRARY_CLUSTERS);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t M = source == ARP_LIBCL_ALL ? T : source == ARP_LIBCL_LIST ? n_order : K.K, W = F.U > 0 ? F.W : 0;
+    const int64_t rounds = std::min(max_clusters, (M + LCL_WINDOW - 1) / LCL_WINDOW);
+    const size_t mc = (size_t)max_clusters, nr = (size_t)rounds;
+    HIPCHK(c, S.words.reserve(4));
+    HIPCHK(c, S.made.reserve(1));
+    HIPCHK(c, S.start.reserve(nr + 1));
+    HIPCHK(c, S.nl.reserve(nr));
+    HIPCHK(c, S.wl.reserve(nr * LCL_WINDOW));
+    HIPCHK(c, S.size.reserve(mc));
+    HIPCHK(c, S.leader.reserve(mc));
+    HIPCHK(c, S.leader_position.reserve(mc));
+    HIPCHK(c, S.pose.reserve((size_t)M));
+    HIPCHK(c, S.ligand.reserve((size_t)M));
+    HIPCHK(c, S.cluster.reserve((size_t)M));
+    HIPCHK(c, S.similarity.reserve((size_t)M));
+    LclArgs A{};
+    A.bits = W > 0 ? F.bits.p + Q * W : nullptr;      // (pose t is row Q + t; U = 0: the matrix was never allocated)
+    A.count = F.count.p + Q; A.W = W;
+    A.lig_of = R.lig_of.p; A.M = (int)M;
+    A.threshold = threshold_q32; A.max_clusters = (int)max_clusters;
+    A.g = pcl_group_width(W); A.g_log2 = __builtin_ctz((unsigned)A.g);
+    A.rounds = (int)rounds;
+    A.start = S.start.p; A.nl = S.nl.p; A.wl = S.wl.p; A.made = S.made.p;
+    A.pose = S.pose.p; A.ligand = S.ligand.p; A.cluster = S.cluster.p; A.similarity = S.similarity.p;
+    A.leader = S.leader.p; A.leader_position = S.leader_position.p; A.size = S.size.p; A.words = S.words.p;
+    if (source == ARP_LIBCL_LIST) {
+        CHK(upload_async(c, S.order, (const int*)order, (size_t)n_order));      // (the wait below is before the caller's array goes away)
+        A.ids = S.order.p;
+    } else if (source == ARP_LIBCL_SHORTLIST) A.ids = K.pose.p;      // (read by k_lcl_positions alone: no id crosses to the host)
+    // ---- nothing assigned: cluster = -1, similarity = -1, no leader made, every start but the first the sentinel
+    HIPCHK(c, hipMemsetAsync(S.words.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.made.p, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.nl.p, 0, nr * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.size.p, 0, mc * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.cluster.p, 0xFF, (size_t)M * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.similarity.p, 0xFF, (size_t)M * sizeof(long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.start.p, 0xFF, (nr + 1) * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(S.start.p, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_lcl_positions, dim3(nblocks(M, LCL_THREADS, 1 << 20)), dim3(LCL_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "positions").c_str()));
+    // ---- the rounds
+    const int per_block = LCL_THREADS / A.g;
+    const dim3 grid(nblocks(M, per_block, 16 * std::max(c->num_cu, 1)));
+    int64_t enqueued = 0;
+    while (enqueued < rounds) {
+        const int64_t end = std::min(rounds, enqueued + LIBCL_ROUNDS_PER_WAIT);
+        for (; enqueued < end; ++enqueued) {
+            hipLaunchKernelGGL(k_lcl_window, dim3(1), dim3(LCL_THREADS), 0, c->stream, A, (int)enqueued);
+            hipLaunchKernelGGL(k_lcl_sweep, grid, dim3(LCL_THREADS), 0, c->stream, A, (int)enqueued);
+        }
+        CHK(check_launch(c, (fn + "rounds").c_str()));
+        if (enqueued < rounds) {
+            CHK(stage_copy(c, S.start.p + enqueued, sizeof(uint32_t)));
+            uint32_t next_start;
+            memcpy(&next_start, c->table_stage, sizeof(next_start));
+            if (next_start == PCL_SENTINEL) break;
+        }
+    }
+    hipLaunchKernelGGL(k_lcl_finish, dim3(nblocks(M, LCL_THREADS, 256)), dim3(LCL_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "finish").c_str()));
+    CHK(stage_copy(c, S.words.p, 4 * sizeof(unsigned long long)));
+    unsigned long long h[4];
+    memcpy(h, c->table_stage, sizeof(h));
+    ++S.launches;
+    if (h[LCL_W_CLUSTERS] < 1 || h[LCL_W_CLUSTERS] > (unsigned long long)std::min(max_clusters, M) || h[LCL_W_UNASSIGNED] > (unsigned long long)M ||
+        h[LCL_W_ROUNDS] < 1 || h[LCL_W_ROUNDS] > (unsigned long long)rounds)
+        FAIL(c, ARP_E_HIP, fn + "cluster count out of range");
+    S.M = M; S.C = (int64_t)h[LCL_W_CLUSTERS]; S.unassigned = (int64_t)h[LCL_W_UNASSIGNED]; S.max_clusters = max_clusters;
+    S.W = W; S.rounds = (int64_t)h[LCL_W_ROUNDS]; S.threshold = threshold_q32;
+    S.valid = true;
+    library_clusters_info(S, info);
+    return ARP_OK;
+}
+
+int arp_library_clusters_fetch(arp_ctx* c, int64_t cap_positions, int64_t cap_clusters, int32_t* pose, int32_t* ligand, int32_t* cluster,
+                               int64_t* similarity, int32_t* leader, int32_t* leader_position, uint32_t* size, int64_t* n_positions,
+                               int64_t* n_clusters) {
+    if (!c || !n_positions || !n_clusters) return ARP_E_ARG;
+    const LibClustersResult& S = c->libclusters;
+    if (!S.valid)      // (voided wherever the library result is)
+        FAIL(c, ARP_E_ARG, "arp_library_clusters_fetch: no result (arp_library_clusters_launch; the library result was replaced or the structure or the library changed since)");
+    *n_positions = S.M;
+    *n_clusters = S.C;
+    if ((pose || ligand || cluster || similarity) && cap_positions < S.M)
+        FAIL(c, ARP_E_CAPACITY, "arp_library_clusters_fetch: output buffers too small (cap_positions < *n_positions)");
+    if ((leader || leader_position || size) && cap_clusters < S.C)
+        FAIL(c, ARP_E_CAPACITY, "arp_library_clusters_fetch: output buffers too small (cap_clusters < *n_clusters)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t M = (size_t)S.M, C = (size_t)S.C;
+    std::vector<StagePiece> pieces;
+    want_piece(pieces, pose, S.pose.p, M * sizeof(int32_t));
+    want_piece(pieces, ligand, S.ligand.p, M * sizeof(int32_t));
+    want_piece(pieces, cluster, S.cluster.p, M * sizeof(int32_t));
+    want_piece(pieces, similarity, S.similarity.p, M * sizeof(int64_t));
+    want_piece(pieces, leader, S.leader.p, C * sizeof(int32_t));
+    want_piece(pieces, leader_position, S.leader_position.p, C * sizeof(int32_t));
+    want_piece(pieces, size, S.size.p, C * sizeof(uint32_t));
+    return stage_fetch(c, pieces);
+}
+
+int arp_library_clusters_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    library_clusters_info(c->libclusters, info);
     return ARP_OK;
 }
 

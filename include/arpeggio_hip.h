@@ -1554,6 +1554,69 @@ int arp_library_shortlist_planes_fetch(arp_ctx* ctx, int table, int64_t cap_entr
                                        int32_t* second, void* v0, void* v1, void* v2, void* v3, uint8_t* u0, uint8_t* u1,
                                        uint8_t* u2, int64_t* count);
 int arp_library_shortlist_info(arp_ctx* ctx, int64_t info[8]);
+/* Library clusters: leader clustering (sphere exclusion in rank order) of poses of the resident library result by the Tanimoto
+ * similarity of their library fingerprints, on the device, in a WINDOW form that elects up to ARP_LIBCL_WINDOW = 32 leaders a
+ * round (csrc/arp_library_clusters.h).  One representative per interaction pattern of a screen, how many poses
+ * stand behind it, and their ligands; no bit and no record is copied.
+ *
+ * SOURCES: three resident results are read while the launch runs and none is written: the library fingerprint
+ *   (arp_library_fingerprints_launch; any level, any planes, Q = 0 ... 64 references): W, bits [Q + T][W], count [Q + T]; the
+ *   library result (arp_library_contacts_launch): lig_of and T; for ARP_LIBCL_SHORTLIST the library shortlist
+ *   (arp_library_shortlist_launch): K and its pose column.
+ * POSITIONS: position m names a GLOBAL pose in [0, T).  source = ARP_LIBCL_ALL: pose m, M = T; order must be NULL and n_order 0.
+ *   ARP_LIBCL_LIST: pose order[m], M = n_order, 1 <= n_order <= ARP_POSES_MAX_POSES, every id in [0, T), checked on the host
+ *   before anything is touched; repeats allowed.  ARP_LIBCL_SHORTLIST: the K >= 1 entries of the resident library shortlist in
+ *   rank order (either unit, any kind), M = K; the pose column is copied on the device, no id crosses to the host; order must
+ *   be NULL and n_order 0.  The positions are materialised by the launch: a later shortlist does not change the clusters.
+ *   Pose t is ROW Q + t of the fingerprint; the reference rows are never positions.
+ * SIMILARITY of poses a and b, exactly arp_poses_clusters_launch's: t = sum over the W words of popcount(bits[a][w] & bits[b][w]),
+ *   u = count[a] + count[b] - t, q(a, b) = (u == 0) ? 2^32 : floor(t 2^32 / u) in unsigned 64-bit arithmetic; a and b are SIMILAR
+ *   when q >= threshold_q32, 0 <= threshold_q32 <= 2^32.
+ * CLUSTERING, defined sequentially and exactly arp_poses_clusters_launch's: walk the positions m = 0 ... M - 1; a position whose
+ *   pose is similar to some leader's pose joins the FIRST such leader in leader order; otherwise, while fewer than max_clusters
+ *   leaders exist (1 <= max_clusters <= ARP_POSECL_MAX_CLUSTERS), it becomes the next leader; otherwise it stays unassigned.
+ *   U = 0 (no feature in any row) gives q = 2^32 everywhere: one cluster of M members.
+ * RESULT: per position: pose int32 [M], the global pose; ligand int32 [M] = lig_of[pose]; cluster int32 [M], the index in leader
+ *   order, -1 when unassigned; similarity int64 [M], q to its own leader's pose, 2^32 for a leader, -1 when unassigned.  Per
+ *   cluster: leader int32 [C], the leaders' poses; leader_position int32 [C], strictly ascending; size uint32 [C], the leader
+ *   included.  Sum of size + unassigned = M.  Everything is an integer: a pure function of the arguments and the three sources.
+ *
+ * arp_library_clusters_launch: info[8] as arp_library_clusters_info gives it.  One launch materialises the positions; a round is
+ *   two launches: the window kernel (one block) resolves the 32 positions from the lowest unassigned one among themselves and
+ *   elects up to 32 leaders, the sweep compares every unassigned position behind the window with those leaders in leader order
+ *   and finds the next round's start.  rounds <= min(max_clusters, ceil(M / 32)).  The rounds are enqueued on the context's
+ *   stream 32 at a time; after a group that is not the last one word (the next start) is read back and the rounds end when no
+ *   position is left; then one launch and the one wait for C, the unassigned count and the rounds that ran.  Refusals are
+ *   ARP_E_ARG with the cause named, in this order, and none of them touches a resident result: a pass not waited for; no library
+ *   result; no library fingerprint; the fingerprint's P is not Q + T; threshold_q32 > 2^32; max_clusters outside [1, 4096]; an
+ *   unknown source; ARP_LIBCL_LIST with order == NULL, with n_order out of range, with an id outside [0, T); another source with
+ *   order != NULL or n_order != 0; ARP_LIBCL_SHORTLIST without a valid library shortlist, or with an empty one.  Every successful
+ *   launch remakes the result.
+ *   The fingerprint and the shortlist are read only while the launch runs: a later arp_library_fingerprints_launch or
+ *   arp_library_shortlist_launch leaves the clusters valid.  They are void exactly when the library result is void or replaced
+ *   (arp_set_ligand_library, a new arp_library_contacts_launch, a new structure, models or a batch); arp_set_selection does not
+ *   void them.  Making them voids nothing; the pose clusters (arp_poses_clusters_launch) are another object and stay resident.
+ * arp_library_clusters_fetch: ANY pointer but n_positions and n_clusters may be NULL.  *n_positions = M, *n_clusters = C.
+ *   ARP_E_CAPACITY when a per-position array (pose, ligand, cluster, similarity) is asked for and cap_positions < M, or a
+ *   per-cluster array (leader, leader_position, size) and cap_clusters < C.  ARP_E_ARG: no valid result.  Every piece goes
+ *   through the page-locked stage in one wait.
+ * arp_library_clusters_info: info[0] = M, [1] = C, [2] = unassigned, [3] = max_clusters, [4] = W, [5] = rounds that elected a
+ *   leader, [6] = launches that did work so far, [7] = threshold_q32.  All but [6] are 0 while there is no result.
+ * ARP_LIBCL_LDS_WORDS: the 32 rows a round compares against are staged in LDS when 32 W <= this many words (16 KiB a block: W <= 64), and
+ *   read through L2 otherwise; the result does not depend on it.
+ * OUT OF SCOPE: the window form for arp_poses_clusters_launch; similarity between ligands as the best over all pose pairs; class
+ *   planes of the library fingerprints; clustering across launches; joining the most similar leader; multi-GPU. */
+#define ARP_LIBCL_ALL 0
+#define ARP_LIBCL_LIST 1
+#define ARP_LIBCL_SHORTLIST 2
+#define ARP_LIBCL_WINDOW 32
+#define ARP_LIBCL_LDS_WORDS 2048
+int arp_library_clusters_launch(arp_ctx* ctx, int source, const int32_t* order, int64_t n_order, uint64_t threshold_q32,
+                                int64_t max_clusters, int64_t info[8]);
+int arp_library_clusters_fetch(arp_ctx* ctx, int64_t cap_positions, int64_t cap_clusters, int32_t* pose, int32_t* ligand,
+                               int32_t* cluster, int64_t* similarity, int32_t* leader, int32_t* leader_position, uint32_t* size,
+                               int64_t* n_positions, int64_t* n_clusters);
+int arp_library_clusters_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
