@@ -58,6 +58,7 @@ SYMBOLS = (
     'arp_library_best_launch', 'arp_library_best_fetch',
     'arp_library_fingerprints_launch', 'arp_library_fingerprints_fetch', 'arp_library_fingerprints_info',
     'arp_library_fingerprints_best_launch', 'arp_library_fingerprints_best_fetch',
+    'arp_library_fingerprints_planes_launch',
     'arp_set_ligand_library_planes', 'arp_library_planes_launch', 'arp_library_planes_fetch', 'arp_library_planes_info',
     'arp_library_shortlist_launch', 'arp_library_shortlist_fetch', 'arp_library_shortlist_planes_fetch', 'arp_library_shortlist_info',
     'arp_library_clusters_launch', 'arp_library_clusters_fetch', 'arp_library_clusters_info',
@@ -289,6 +290,7 @@ def load():
     L.arp_library_best_launch.argtypes = [vp, vp]
     L.arp_library_best_fetch.argtypes = [vp, i64, vp, vp, vp, C.POINTER(i64)]
     L.arp_library_fingerprints_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp, vp, vp, vp]
+    L.arp_library_fingerprints_planes_launch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, i64, vp, vp, vp, vp]
     L.arp_library_fingerprints_fetch.argtypes = [vp, i64] + [vp] * 5 + [C.POINTER(i64)]
     L.arp_library_fingerprints_info.argtypes = [vp, vp]
     L.arp_library_fingerprints_best_launch.argtypes = [vp]
@@ -1423,7 +1425,12 @@ class Context:
         record whose ``ctype`` bit is in ``ctype_mask``, and one of the SIFt bits of ``planes`` the record has.  Returns the
         dict ``poses_fingerprints`` returns, over Q + T rows — the references first, then the global poses: ``ids``, ``count``
         [Q + T], ``cross`` [Q + T, Q], ``occupancy`` [U, NP] over the poses, ``planes``, ``n_refs``, ``level``, with
-        ``bits=True`` the bit matrix.  No record is copied.  Every call launches."""
+        ``bits=True`` the bit matrix.  No record is copied.  Every call launches.
+
+        A ``planes`` mask or a reference mask with a bit from ``POSEFP_PLANES`` on (``library_fingerprints.planes(classes=...)``,
+        ``library_fingerprints.reference_from_plane_records``) adds the ring and amide classes as planes
+        (arp_library_fingerprints_planes_launch): the resident ``library_planes`` result of the SAME poses is reduced into the
+        same matrix, residue level only; ``planes`` in the result is the unified mask."""
         from . import library_fingerprints as _lfp
         r = _lfp.references([]) if refs is None else refs
         off = np.ascontiguousarray(r['ref_off'], np.int64).reshape(-1)
@@ -1436,9 +1443,10 @@ class Context:
         flags = POSEFP_BY_RESIDUE if by_residue else 0
         info = np.zeros(8, np.int64)
         give = Q > 0
-        self._check(self._L.arp_library_fingerprints_launch(self._h, int(planes), int(ctype_mask), flags, Q, _p(off) if give else None,
-                                                            _p(node) if give else None, _p(mask) if give else None, _p(info)),
-                    'arp_library_fingerprints_launch')
+        wide = int(planes) >> POSEFP_PLANES or (len(mask) and int(mask.max()) >> POSEFP_PLANES)
+        entry = 'arp_library_fingerprints_planes_launch' if wide else 'arp_library_fingerprints_launch'
+        self._check(getattr(self._L, entry)(self._h, int(planes), int(ctype_mask), flags, Q, _p(off) if give else None,
+                                            _p(node) if give else None, _p(mask) if give else None, _p(info)), entry)
         P, Q, U = (int(v) for v in info[:3])
         NP = bin(int(planes)).count('1')
         out = dict(ids=np.empty(U, np.int32), count=np.empty(P, np.uint32), cross=np.empty((P, Q), np.uint32), occupancy=np.empty((U, NP), np.uint32))

@@ -510,7 +510,7 @@ class InteractionComplex:
         return _ll.write_library_planes(wd, self.id, self.library_planes, self.pc, self.ligand_library_ligands, self.component_types)
 
     def run_library_fingerprints(self, library, pose_off, xyz, h_xyz, refs, contacts=None, interacting_entities=None, level='residue',
-                                 chunk=None, interacting_cutoff=5.0, vdw_comp=0.1):
+                                 chunk=None, interacting_cutoff=5.0, vdw_comp=0.1, classes=()):
         """Extension beside the mirror: which ligands of a library reproduce the interactions of known binders, scored ON THE
         DEVICE — no record is copied (``arpeggio_amd.library_fingerprints``).  ``library`` is a list of ligand packs or what
         ``ligand_library.pack`` made of one; ``pose_off`` int64 [L + 1], ``xyz`` and ``h_xyz`` are the flat arrays of
@@ -523,15 +523,24 @@ class InteractionComplex:
         the chunks are merged (``pose_fingerprints.merge``, ``library_fingerprints.merge_best``).  Returns the result
         ``pose_fingerprints`` describes with the reference rows moved to ``reference_count`` / ``reference_cross``, ``count`` [T],
         ``cross`` [T, Q], and with ``best`` (the table ``library_fingerprints`` describes) and ``ligand_pose_off``; also kept in
-        ``self.library_fingerprints``.  The results of ``run_arpeggio`` and ``run_poses`` stay as they are."""
+        ``self.library_fingerprints``.  The results of ``run_arpeggio`` and ``run_poses`` stay as they are.
+
+        ``classes`` names ring / amide classes as further planes (``pose_fingerprints.planes``: names of ``CLASS_PLANE_NAMES``,
+        a table, or 'all'; ``contacts=[]`` gives them alone): pi-stacking, cation-pi, donor-pi, halogen-pi, Met-sulphur-pi and
+        amide stacking of every pose, residue level only (``level='atom'`` raises ``ValueError``).  Every chunk is then also one
+        ``Context.library_planes_summary`` on the same poses (the ligand packs need ``ring_atoms`` and ``amide_atoms``), and the
+        reference masks may carry the class planes (``library_fingerprints.reference_from_plane_records``)."""
         from .. import _capi, contact_filter, ligand_library as _ll, library_fingerprints as _lfp
         if level not in _lfp.LEVELS:
             raise ValueError(f"run_library_fingerprints: level must be 'residue' or 'atom', not {level!r}")
-        mask = _lfp.planes(contacts)
+        with_classes = len((classes,) if isinstance(classes, str) else tuple(classes)) > 0
+        if with_classes and level != 'residue':
+            raise ValueError("run_library_fingerprints: ring / amide classes need level='residue' (their nodes are residues)")
+        mask = _lfp.planes(contacts, classes)
         ctype_mask = contact_filter.masks(None, interacting_entities)[1]
         lib = library if isinstance(library, dict) else _ll.pack(list(library))
         n_nodes = self.pc.n_residues if level == 'residue' else self.pc.n_atoms
-        r = _lfp.validate(refs, n_nodes) if isinstance(refs, dict) else _lfp.references(refs, n_nodes)
+        r = _lfp.validate(refs, n_nodes, with_classes) if isinstance(refs, dict) else _lfp.references(refs, n_nodes, with_classes)
         if _lfp.n_references(r) < 1:
             raise ValueError('run_library_fingerprints: 1 ... MAX_REFS references')
         off = np.ascontiguousarray(pose_off, np.int64)
@@ -541,10 +550,14 @@ class InteractionComplex:
             self.initialize()
         ctx = self._ctx
         ctx.set_ligand_library(lib)
+        if with_classes:
+            ctx.set_ligand_library_planes(lib)
         h = np.zeros(0) if h_xyz is None else h_xyz
         parts, bests = [], []
         for off_c, a, _, xc, hc in _ll.chunk_poses(lib, off, xyz, h, chunk if chunk else _capi.POSES_MAX_POSES):
             ctx.library_summary(off_c, xc, hc, interacting_cutoff, vdw_comp, False)
+            if with_classes:
+                ctx.library_planes_summary(off_c, xc)
             parts.append(ctx.library_fingerprints(r, mask, ctype_mask, by_residue=level == 'residue'))
             bests.append((ctx.library_fingerprints_best(), a))
         out = _lfp.strip_references(parts[0] if len(parts) == 1 else _lfp.merge(parts))

@@ -971,7 +971,8 @@ void void_results(arp_ctx* c, unsigned lost) {
 // replaced or is about to be — the structure, the selection, or one of the rows below itself.  A row goes when it
 // is lost or reads something lost, and what reads it goes with it (it stands behind its source).  The ligand-library result
 //  is a row of the same table: it reads the structure and the library (POSE_LIBRARY, lost by
-// arp_set_ligand_library) and NO selection; the library fingerprint reads that result's records, and its best-pose
+// arp_set_ligand_library) and NO selection; the library fingerprint reads that result's records (made with class
+// planes, DESIGN.md 5z: `classes`, the library-planes result's as well, and goes with either), and its best-pose
 // table reads the fingerprint; the library-planes result reads the structure, the library and the library's
 // plane table (POSE_LIBRARY_PLANE_ATOMS, lost with the library and by arp_set_ligand_library_planes), its per-structure set-up the
 // structure alone.  The fingerprint and the
@@ -1003,14 +1004,15 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         // the library result reads the structure and the library, no selection; the best-pose table reads its summary
         {&c->libres.valid, POSE_LIBRARY_CONTACTS, POSE_STRUCTURE | POSE_LIBRARY},
         {&c->libres.best_valid, POSE_LIBRARY_BEST, POSE_LIBRARY_CONTACTS},
-        // the library fingerprint reads the library result's records; its best-pose table reads its count and cross
-        {&c->libfp.valid, POSE_LIBRARY_FINGERPRINT, POSE_LIBRARY_CONTACTS},
-        {&c->libfpx.best_valid, POSE_LIBRARY_FP_BEST, POSE_LIBRARY_FINGERPRINT},
         // the library's plane table names atoms of the library's ligands; the set-up of the library-planes result (grid, residue
         // CSR) reads the structure alone; the result reads the structure, the library and the plane table, and no selection
         {&c->libplanes.resident, POSE_LIBRARY_PLANE_ATOMS, POSE_LIBRARY},
         {&c->libpl.setup, POSE_LIBRARY_PLANES_SETUP, POSE_STRUCTURE},
         {&c->libpl.valid, POSE_LIBRARY_PLANES, POSE_STRUCTURE | POSE_LIBRARY | POSE_LIBRARY_PLANE_ATOMS},
+        // the library fingerprint reads the library result's records and, made with class planes, the
+        // library-planes result's (so its row stands behind that one's); its best-pose table reads its count and cross
+        {&c->libfp.valid, POSE_LIBRARY_FINGERPRINT, POSE_LIBRARY_CONTACTS | (c->libfp.classes ? POSE_LIBRARY_PLANES : 0u)},
+        {&c->libfpx.best_valid, POSE_LIBRARY_FP_BEST, POSE_LIBRARY_FINGERPRINT},
         // the library shortlist reads the library result and, made with a ring or amide table or weight, the
         // library-planes result; the library fingerprint only while its launch runs (scores are taken then)
         {&c->libshortlist.valid, POSE_LIBRARY_SHORTLIST, POSE_LIBRARY_CONTACTS | (c->libshortlist.planes ? POSE_LIBRARY_PLANES : 0u)},
@@ -6579,22 +6581,36 @@ int arp_poses_fingerprints_info(arp_ctx* c, int64_t info[8]) {
 }
 
 // ---- library fingerprints (arp_library_fingerprints.h): the resident library result -> bit matrix -> scores
-// Only the library result is read (its sorted slab, pose_off, the ligands' pose ranges) and res_id; only this result's own
+// Only the library result is read (its sorted slab, pose_off, the ligands' pose ranges) and res_id — with class planes (5z) also
+// the library-planes result's four tables and offsets and the receptor's ring_res and am_res —; only this result's own
 // buffers are written.  The references are the caller's feature lists: rows 0 ... Q - 1 of a matrix of Q + T rows, so that
 // k_pfp_scan, k_pfp_ids, k_pfp_cross and k_pfp_occupancy are launched as they are.  One wait: U, which sizes the matrix.
 static_assert(LIBFP_MAX_FEATURES == ARP_LIBFP_MAX_FEATURES, "arp_library_fingerprints.h names the header's limit");
-int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, const int64_t* ref_off,
-                                    const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]) {
-    if (!c || !info) return ARP_E_ARG;
-    const std::string fn = "arp_library_fingerprints_launch: ";
+// Both entries: arp_library_fingerprints_launch admits the 15 SIFt bits (n_planes) and reads the library result alone; with a bit
+// from ARP_POSEFP_PLANES on (arp_library_fingerprints_planes_launch) the four tables of the library-planes result
+// are marked and walked as well, after a check on the device that both results were made from the same pose coordinates — its
+// flag comes back with U, in the one wait.
+static int libfp_launch(arp_ctx* c, const std::string& fn, int n_planes, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
+                        const int64_t* ref_off, const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]) {
     PoseFpResult& F = c->libfp;
     LibraryFpTables& X = c->libfpx;
     const LibraryResult& R = c->libres;
+    const LibraryPlanesResult& L = c->libpl;
+    const bool wide = n_planes > ARP_POSEFP_PLANES;
+    const bool classes = wide && (planes >> ARP_POSEFP_PLANES) != 0;
     // ---- the refusals, in this order: none of them touches a resident result
     if (c->pass_pending) FAIL(c, ARP_E_ARG, fn + "a pass has not been waited for (arp_run_wait)");
     if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    if (classes) {
+        if (!L.valid) FAIL(c, ARP_E_ARG, fn + "no library-planes result (arp_library_planes_launch; the structure, the library or its plane table changed since)");
+        // (equal T with other pose ranges is refused here as well: the check on the device compares R.nx words of both)
+        if (L.T != R.T || L.L != R.L || L.host_pose_off != R.host_pose_off || L.nx != R.nx)
+            FAIL(c, ARP_E_ARG, fn + "the library result and the library-planes result differ in T or in their pose ranges (launch both on the same poses)");
+        if (!(flags & ARP_POSEFP_BY_RESIDUE)) FAIL(c, ARP_E_ARG, fn + "ring / amide class planes need ARP_POSEFP_BY_RESIDUE (their nodes are residues)");
+    }
     if (!planes) FAIL(c, ARP_E_ARG, fn + "a planes mask of 0 makes no feature");
-    if (planes & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (!wide && (planes & ~((1u << ARP_POSEFP_PLANES) - 1u))) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 15 SIFt bits");
+    if (planes & ~((1u << ARP_POSEFP_ALL_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "planes has bits beyond the 29 planes (15 SIFt bits, 14 ring / amide classes)");
     if (!ctype_mask) FAIL(c, ARP_E_ARG, fn + "a ctype_mask of 0 admits no record");
     if (ctype_mask & ~ARP_FILTER_CTYPE_ALL) FAIL(c, ARP_E_ARG, fn + "ctype_mask has bits beyond the 7 contact types");
     if (flags & ~ARP_POSEFP_BY_RESIDUE) FAIL(c, ARP_E_ARG, fn + "unknown flag (ARP_POSEFP_BY_RESIDUE is the only one)");
@@ -6616,13 +6632,15 @@ int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_
         for (int64_t q = 0; q < Q; ++q)
             for (int64_t f = ref_off[q] + 1; f < ref_off[q + 1]; ++f)
                 if (ref_node[f] <= ref_node[f - 1]) FAIL(c, ARP_E_ARG, fn + "the nodes of a reference must be strictly ascending");
-        for (int64_t f = 0; f < nf; ++f)
-            if (ref_planes[f] & ~((1u << ARP_POSEFP_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "a reference mask has bits beyond the 15 SIFt bits");
+        for (int64_t f = 0; f < nf; ++f) {
+            if (!wide && (ref_planes[f] & ~((1u << ARP_POSEFP_PLANES) - 1u))) FAIL(c, ARP_E_ARG, fn + "a reference mask has bits beyond the 15 SIFt bits");
+            if (ref_planes[f] & ~((1u << ARP_POSEFP_ALL_PLANES) - 1u)) FAIL(c, ARP_E_ARG, fn + "a reference mask has bits beyond the 29 planes");
+        }
     }
     const int NP = __builtin_popcount(planes);
     // ---- from here on the fingerprint before is gone, and its best-pose table
     void_pose_results(c, POSE_LIBRARY_FINGERPRINT);
-    F.classes = false;
+    F.classes = classes;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)R.rec.count;
     HIPCHK(c, F.presence.reserve((size_t)NW));
@@ -6657,16 +6675,43 @@ int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_
         posefp_info(F, info);
         return ARP_OK;
     };
+    // ---- the ring / amide tables (class planes): the library-planes result's columns and offsets, the receptor's resident
+    // ring and amide residues
+    LibFpTables Tb{};
+    int64_t k_classes = 0;
+    if (classes) {
+        for (int t = 0; t < 4; ++t) {
+            Tb.first[t] = L.col.i0[t]; Tb.second[t] = L.col.i1[t]; Tb.ctype[t] = L.col.u[t][PLANE_TABLES[t].ctype_col];
+            Tb.count[t] = L.counts[t];
+            k_classes = std::max(k_classes, L.counts[t]);
+        }
+        Tb.ap_mask = L.col.u[0][0];
+        Tb.pose_off = L.pose_off.p;
+        Tb.ring_res = c->ring_res.p; Tb.am_res = c->am_res.p;
+        Tb.n = (int)c->n; Tb.nring = (int)c->nring; Tb.namide = (int)c->namide;
+        Tb.T = T;
+    }
     // ---- the columns: presence bitmap of the nodes of records and references, popcounts, scan; the host learns U (the one wait,
     // after which the caller's reference arrays are free)
     long long U = 0;
-    if (k > 0 || Q > 0) {
+    if (k > 0 || Q > 0 || classes) {
         HIPCHK(c, hipMemsetAsync(F.presence.p, 0, (size_t)NW * sizeof(unsigned long long), c->stream));
+        if (classes) HIPCHK(c, hipMemsetAsync(F.total.p + 1, 0, sizeof(long long), c->stream));
         if (k + (size_t)nf > 0) hipLaunchKernelGGL(k_lfp_mark, dim3(nblocks((int64_t)k + nf, 256, c->num_cu)), dim3(256), 0, c->stream, A, V);
+        if (classes) {
+            // both results keep their uploaded poses: compared as 32-bit words, the flag word beside U
+            if (R.nx > 0)
+                hipLaunchKernelGGL(k_pfp_same_poses, dim3(nblocks(R.nx, 256, c->num_cu)), dim3(256), 0, c->stream, (const uint32_t*)R.rec.xyz.p,
+                                   (const uint32_t*)L.xyz.p, (long long)R.nx, (uint32_t*)(F.total.p + 1));
+            if (k_classes > 0) hipLaunchKernelGGL(k_lfp_mark_planes, dim3(nblocks(k_classes, 256, c->num_cu), 4), dim3(256), 0, c->stream, A, Tb);
+        }
         hipLaunchKernelGGL(k_pfp_scan, dim3(1), dim3(POSEFP_SCAN_THREADS), 0, c->stream, A);
         CHK(check_launch(c, (fn + "mark / scan").c_str()));
-        CHK(stage_copy(c, F.total.p, sizeof(long long)));
-        memcpy(&U, c->table_stage, sizeof(U));
+        CHK(stage_copy(c, F.total.p, (classes ? 2 : 1) * sizeof(long long)));
+        long long h[2] = {0, 0};
+        memcpy(h, c->table_stage, (classes ? 2 : 1) * sizeof(long long));
+        if (classes && h[1] != 0) FAIL(c, ARP_E_ARG, fn + "the library result and the library-planes result were made from different poses");
+        U = h[0];
         if (U < 0 || U > N) FAIL(c, ARP_E_HIP, fn + "column count out of range");
     }
     if (U == 0) {      // no participating record and no reference feature: no column, no feature in any row
@@ -6688,10 +6733,24 @@ int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_
     A.ids = F.ids.p; A.U = U; A.bits = F.bits.p; A.wpp = wpp; A.W = W; A.occ = F.occ.p;
     hipLaunchKernelGGL(k_pfp_ids, dim3(nblocks(NW, 256, 1024)), dim3(256), 0, c->stream, A);
     hipLaunchKernelGGL(k_lfp_bits, dim3(nblocks(P, 4, 16384)), dim3(256), 0, c->stream, A, V);
+    if (k_classes > 0) hipLaunchKernelGGL(k_lfp_bits_planes, dim3(nblocks(T, 4, 16384)), dim3(256), 0, c->stream, A, Tb);
     long long slices = 0;
     CHK(enqueue_cross_and_occupancy(c, F, A, &slices));
     CHK(check_launch(c, (fn + "ids / bits / cross / occupancy").c_str()));
     return done(U, W, slices);
+}
+
+int arp_library_fingerprints_launch(arp_ctx* c, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, const int64_t* ref_off,
+                                    const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    return libfp_launch(c, "arp_library_fingerprints_launch: ", ARP_POSEFP_PLANES, planes, ctype_mask, flags, n_refs, ref_off, ref_node, ref_planes, info);
+}
+
+int arp_library_fingerprints_planes_launch(arp_ctx* c, uint32_t planes29, uint32_t ctype_mask, uint32_t flags, int64_t n_refs, const int64_t* ref_off,
+                                           const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    return libfp_launch(c, "arp_library_fingerprints_planes_launch: ", ARP_POSEFP_ALL_PLANES, planes29, ctype_mask, flags, n_refs, ref_off, ref_node,
+                        ref_planes, info);
 }
 
 int arp_library_fingerprints_fetch(arp_ctx* c, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross, uint32_t* occupancy, uint64_t* bits,

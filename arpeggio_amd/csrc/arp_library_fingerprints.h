@@ -96,6 +96,104 @@ __global__ __launch_bounds__(256) void k_lfp_bits(PoseFpArgs A, LibFpRefs R) {
     }
 }
 
+// ---- the ring / amide classes as planes: the four tables of the library-planes result (arp_library_planes.h), which
+// is resident beside the library result and sorted by global pose as well.  Planes 15 ... 28 are those of
+// arp_poses_fingerprints.h (POSEFP_PLANE_*).  Ids are the complex's: an entity is on the LIGAND side when it is an atom with id
+// >= n, a ring with id >= nring or an amide with id >= namide; everything else is the receptor's, an affected receptor ring
+// included.  A record takes part when bit ctype of ctype_mask is set, exactly one of its two entities is the ligand's and its
+// plane is selected.  Its node is the residue of the receptor entity: res_id[atom], am_res[amide], and for a ring the RESIDENT
+// ring_res[ring] of the receptor alone — no receptor ring path is resident here, and the reason the pose route avoids ring_res
+// does not apply: the ligand is no part of the resident structure, so no ligand atom can have taken a ring's residue over.  The
+// posed residue that k_library_planes makes per pose is not read.  The ligand side never names a node.
+//   k_lfp_mark_planes  grid (x, 4), a row per table: the sibling of k_lfp_mark, into the same presence bitmap, before k_pfp_scan
+//   k_lfp_bits_planes  a wave per row >= Q walks the pose's slice of each table (its pose_off): the sibling of k_lfp_bits, into
+//                      the same rows, after it.  The reference rows are k_lfp_bits's: lfp_feature_planes ANDs with the unified mask
+struct LibFpTables {
+    const int* first[4];                     // atom, bgn, bgn, amide
+    const int* second[4];                    // ring, end, end, ring
+    const uint8_t* ctype[4];
+    const uint8_t* ap_mask;                  // atom_plane: ARP_AP_* bits
+    const unsigned long long* pose_off;      // [4][T + 1]
+    long long count[4];
+    const int* ring_res;                     // [nring] the receptor's, resident
+    const int* am_res;                       // [namide]
+    int n, nring, namide;                    // the receptor's atoms, rings, amides
+    long long T;                             // global poses
+};
+
+// the selected planes of record r of table t and its node (-1: none); 0 when the record takes no part.  The table is a template
+// parameter for the reason pfp_class_planes gives: a run-time index would send the pointer arrays to scratch memory
+template <int t>
+__device__ __forceinline__ uint32_t lfp_class_planes(const PoseFpArgs& A, const LibFpTables& T, long long r, long long* node) {
+    const uint32_t ct = T.ctype[t][r];
+    if (ct >= POSEFP_CTYPES || !((A.ctype_mask >> ct) & 1u)) return 0u;
+    const int a = T.first[t][r], b = T.second[t][r];
+    if (a < 0 || b < 0) return 0u;      // (never: the ids are those k_library_planes wrote)
+    const int na = t == 0 ? T.n : t == 1 ? T.nring : T.namide, nb = (t == 0 || t == 1 || t == 3) ? T.nring : T.namide;
+    const bool la = a >= na, lb = b >= nb;
+    uint32_t m;
+    if (t == 0) m = ((uint32_t)T.ap_mask[r] & ((1u << POSEFP_AP_BITS) - 1u)) << (la ? POSEFP_PLANE_AP_ATOM : POSEFP_PLANE_AP_RING);
+    else if (t == 1) m = 1u << POSEFP_PLANE_PP;
+    else if (t == 2) m = 1u << POSEFP_PLANE_GG;
+    else m = 1u << (la ? POSEFP_PLANE_GP_AMIDE : POSEFP_PLANE_GP_RING);
+    m &= A.planes;
+    if (la == lb || !m) return 0u;
+    // (the receptor entity's id is below its count: the one index that is read)
+    int res;
+    if (t == 0) res = la ? T.ring_res[b] : A.res_id[a];
+    else if (t == 1) res = T.ring_res[la ? b : a];
+    else if (t == 2) res = T.am_res[la ? b : a];
+    else res = la ? T.ring_res[b] : T.am_res[a];
+    *node = (res >= 0 && (long long)res < A.N) ? (long long)res : -1;
+    return m;
+}
+
+template <int t>
+__device__ __forceinline__ void lfp_mark_table(const PoseFpArgs& A, const LibFpTables& T) {
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < T.count[t]; r += (long long)gridDim.x * blockDim.x) {
+        long long node = -1;
+        if (!lfp_class_planes<t>(A, T, r, &node) || node < 0) continue;
+        pfp_set_bit(A.presence + (node >> 6), 1ull << (node & 63));
+    }
+}
+// grid (x, 4): row y marks table y
+__global__ __launch_bounds__(256) void k_lfp_mark_planes(PoseFpArgs A, LibFpTables T) {
+    switch (blockIdx.y) {
+        case 0: lfp_mark_table<0>(A, T); break;
+        case 1: lfp_mark_table<1>(A, T); break;
+        case 2: lfp_mark_table<2>(A, T); break;
+        default: lfp_mark_table<3>(A, T); break;
+    }
+}
+
+// the slice of table t that belongs to global pose p, 64 records a step, into the pose's row
+template <int t>
+__device__ __forceinline__ void lfp_bits_table(const PoseFpArgs& A, const LibFpTables& T, long long p, int lane, unsigned long long* row) {
+    if (T.count[t] == 0) return;
+    const unsigned long long* const off = T.pose_off + (long long)t * (T.T + 1) + p;
+    const long long s = (long long)off[0], e = min((long long)off[1], T.count[t]);
+    for (long long r = s + lane; r < e; r += 64) {
+        long long node = -1;
+        const uint32_t m = lfp_class_planes<t>(A, T, r, &node);
+        if (!m || node < 0) continue;
+        const long long col = pfp_column(A, node);
+        if (col >= A.U) continue;      // (never: k_lfp_mark_planes set this node's bit)
+        pfp_or_planes(A, row, col, m);
+    }
+}
+// A.P = Q + T rows; the rows below Q are the references': k_lfp_bits wrote them
+__global__ __launch_bounds__(256) void k_lfp_bits_planes(PoseFpArgs A, LibFpTables T) {
+    const int lane = threadIdx.x & 63;
+    const long long waves = (long long)gridDim.x * (blockDim.x >> 6);
+    for (long long p = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); p < T.T; p += waves) {
+        unsigned long long* const row = A.bits + ((long long)A.Q + p) * A.W;
+        lfp_bits_table<0>(A, T, p, lane, row);
+        lfp_bits_table<1>(A, T, p, lane, row);
+        lfp_bits_table<2>(A, T, p, lane, row);
+        lfp_bits_table<3>(A, T, p, lane, row);
+    }
+}
+
 struct LibFpBest {
     int L, Q, Qp;                            // ligands; references; the power of two >= Q (<= 64)
     const long long* pose_off;               // [L + 1] the global poses of ligand l (LibraryResult::tab)

@@ -4,7 +4,10 @@ which molecules of a ligand library reproduce the interactions of a known binder
 The device delivers a ``result`` made from the resident library result (csrc/arp_library_fingerprints.h), shaped as
 ``pose_fingerprints`` describes it, over Q + T rows: the Q references first, then the global poses of the library result.  A
 feature is (node, plane): a receptor residue (``level='residue'``) or receptor atom (``'atom'``) and one of the 15 SIFt bits.
-The ligand atom of a record never names a node; there are no class planes and no all-pairs matrix.
+The ligand atom of a record never names a node; there is no all-pairs matrix.  With a mask beyond bit 14
+(``planes(classes=...)``) the ring and amide records of the resident library-planes result of the same poses enter as the 14 class
+planes of ``pose_fingerprints.CLASS_PLANE_NAMES``, residue level only (``ligand_library.plane_fingerprints`` is the host route and
+says how a record's node is found); reference masks may then carry those bits too (``reference_from_plane_records``).
 
 The references need not be poses of the launch.  They are feature lists (``references``):
 
@@ -31,21 +34,23 @@ import os
 
 import numpy as np
 
-from .pose_fingerprints import (LEVELS, MAX_REFS, N_PLANES, merge, plane_names, planes, rank, recovery, reference_counts,      # noqa: F401
-                                strip_references, tanimoto, unpack)
+from .pose_fingerprints import (CLASS_PLANE_NAMES, LEVELS, MAX_REFS, N_ALL_PLANES, N_PLANES, merge, plane_names, planes, rank,      # noqa: F401
+                                recovery, reference_counts, strip_references, tanimoto, unpack)
 
 MAX_FEATURES = 1 << 22      # ARP_LIBFP_MAX_FEATURES
 ONE_Q32 = 1 << 32
 ALL_PLANES = (1 << N_PLANES) - 1
+ALL_CLASS_PLANES = (1 << N_ALL_PLANES) - 1      # the 15 SIFt bits and the 14 ring / amide class planes
 BEST_KEYS = ('best_pose', 'tanimoto_q32', 'shared', 'count')
 BEST_DTYPES = dict(best_pose=np.int32, tanimoto_q32=np.int64, shared=np.uint32, count=np.uint32)
 
 
-def validate(refs, n_nodes=None):
+def validate(refs, n_nodes=None, classes=False):
     """What arp_library_fingerprints_launch refuses of its reference arrays, in its order and with its causes, checked on the
     host (ValueError).  ``n_nodes``: the nodes of the level (atoms, or residues) when known.  Two things the launch cannot see
     are checked here as well: a ``ref_off`` that is not one-dimensional shares the message of the Q range, and the lengths of
-    ``ref_node`` / ``ref_planes`` against ``ref_off[-1]`` come between the feature limit and the node range."""
+    ``ref_node`` / ``ref_planes`` against ``ref_off[-1]`` come between the feature limit and the node range.  ``classes``: the
+    masks are those of arp_library_fingerprints_planes_launch, 29 bits (the class planes 15 ... 28 as well)."""
     off = np.asarray(refs['ref_off'])
     node, mask = np.asarray(refs['ref_node']), np.asarray(refs['ref_planes'])
     if off.ndim != 1 or not 0 <= len(off) - 1 <= MAX_REFS:
@@ -67,14 +72,16 @@ def validate(refs, n_nodes=None):
     inner[off[:-1][off[:-1] < F]] = False                  # (the first feature of a reference has no predecessor in it)
     if F and (np.diff(node, prepend=node[0])[inner] <= 0).any():
         raise ValueError('library fingerprints: the nodes of a reference must be strictly ascending')
-    if ((mask < 0) | (mask > ALL_PLANES)).any():
+    if not classes and ((mask < 0) | (mask > ALL_PLANES)).any():
         raise ValueError('library fingerprints: a reference mask has bits beyond the 15 SIFt bits')
+    if ((mask < 0) | (mask > ALL_CLASS_PLANES)).any():
+        raise ValueError('library fingerprints: a reference mask has bits beyond the 29 planes')
     return refs
 
 
-def references(lists, n_nodes=None):
+def references(lists, n_nodes=None, classes=False):
     """The reference arrays of ``lists``: per reference a ``(nodes, masks)`` pair of equally long integer sequences, or a dict
-    ``{node: mask}`` (sorted by node here).  ``validate`` names what is refused."""
+    ``{node: mask}`` (sorted by node here).  ``validate`` names what is refused; ``classes`` admits 29-bit masks."""
     lists = list(lists)
     if len(lists) > MAX_REFS:
         raise ValueError('library fingerprints: 0 ... MAX_REFS references')
@@ -92,7 +99,7 @@ def references(lists, n_nodes=None):
     off = np.concatenate([[0], np.cumsum([len(n) for n in nodes])]).astype(np.int64)
     node = np.concatenate(nodes) if nodes else np.zeros(0, np.int64)
     mask = np.concatenate(masks) if masks else np.zeros(0, np.int64)
-    validate(dict(ref_off=off, ref_node=node, ref_planes=mask), n_nodes)
+    validate(dict(ref_off=off, ref_node=node, ref_planes=mask), n_nodes, classes)
     return dict(ref_off=off, ref_node=node.astype(np.int32), ref_planes=mask.astype(np.uint32))
 
 
@@ -124,14 +131,48 @@ def reference_from_records(i, sift, ctype, res_id=None, planes=ALL_PLANES, ctype
     return nodes.astype(np.int32), masks.astype(np.uint32)
 
 
-def reference_from_pose(library_result, t, res_id=None, planes=ALL_PLANES, ctype_mask=0x7F, level='residue'):
-    """``reference_from_records`` over the records of global pose ``t`` of a library result (``Context.library_contacts``)."""
+def reference_from_plane_records(planes_table, receptor, t=None, planes=ALL_CLASS_PLANES, ctype_mask=0x7F):
+    """One reference as a ``(nodes, masks)`` pair from the ring / amide records of a known binder: global pose ``t`` of a
+    ``Context.library_planes`` table on ``receptor`` (``None``: every pose of the table joined).  The features are those of
+    ``ligand_library.plane_fingerprints`` — residue nodes, class planes 15 ... 28 — that ``planes`` selects."""
+    from . import ligand_library as _ll
+    per = _ll.plane_fingerprints(planes_table, receptor, ctype_mask)
+    if t is not None and not 0 <= int(t) < len(per):
+        raise ValueError(f'reference_from_plane_records: no global pose {t}')
+    feats = set().union(*per) if t is None else per[int(t)]
+    masks = {}
+    for node, plane in feats:
+        if (int(planes) >> plane) & 1:
+            masks[node] = masks.get(node, 0) | (1 << plane)
+    nodes = sorted(masks)
+    return np.array(nodes, np.int32), np.array([masks[u] for u in nodes], np.uint32)
+
+
+def reference_from_pose(library_result, t, res_id=None, planes=None, ctype_mask=0x7F, level='residue', planes_result=None, receptor=None):
+    """``reference_from_records`` over the records of global pose ``t`` of a library result (``Context.library_contacts``).
+    ``planes_result``: the ``Context.library_planes`` table of the same poses on ``receptor`` (its pack, required then); the
+    pose's ring / amide features (``reference_from_plane_records``) are merged in per node, residue level only.  ``planes``
+    defaults to the 15 SIFt bits, with ``planes_result`` to all 29 planes."""
     off = np.asarray(library_result['pose_off']).astype(np.int64)
     if not 0 <= int(t) < len(off) - 1:
         raise ValueError(f'reference_from_pose: no global pose {t}')
+    if planes is None:
+        planes = ALL_PLANES if planes_result is None else ALL_CLASS_PLANES
+    if planes_result is not None:
+        if receptor is None or level != 'residue':
+            raise ValueError("reference_from_pose: planes_result needs the receptor's pack and level='residue'")
+        if res_id is None:
+            res_id = receptor.res_id
     a, b = off[int(t)], off[int(t) + 1]
-    return reference_from_records(np.asarray(library_result['i'])[a:b], np.asarray(library_result['sift'])[a:b],
-                                  np.asarray(library_result['ctype'])[a:b], res_id, planes, ctype_mask, level)
+    nodes, masks = reference_from_records(np.asarray(library_result['i'])[a:b], np.asarray(library_result['sift'])[a:b],
+                                          np.asarray(library_result['ctype'])[a:b], res_id, planes, ctype_mask, level)
+    if planes_result is None:
+        return nodes, masks
+    both = dict(zip(nodes.tolist(), masks.tolist()))
+    for u, m in zip(*(v.tolist() for v in reference_from_plane_records(planes_result, receptor, t, planes, ctype_mask))):
+        both[u] = both.get(u, 0) | m
+    keys = sorted(both)
+    return np.array(keys, np.int32), np.array([both[u] for u in keys], np.uint32)
 
 
 def _q32(result):

@@ -536,6 +536,69 @@ def concat_planes(chunks):
     return out
 
 
+CLASS_PLANE = _poses.CLASS_PLANE      # the first class plane of a fingerprint (pose_fingerprints.CLASS_PLANE_NAMES)
+
+
+def ligand_side(receptor, kind, ids):
+    """Which entities of a planes result are the ligand's (bool, the shape of ``ids``): ids are the complex's, so an atom with id
+    >= ``receptor.n_atoms``, a ring with id >= ``n_rings`` or an amide with id >= ``n_amides`` (``kind``: 'atom', 'ring',
+    'amide').  Everything else is the receptor's, a receptor ring a pose affects included."""
+    if kind not in ('atom', 'ring', 'amide'):
+        raise ValueError("ligand_side: kind must be 'atom', 'ring' or 'amide'")
+    n = dict(atom=receptor.n_atoms, ring=receptor.n_rings, amide=receptor.n_amides)[kind]
+    return np.asarray(ids, np.int64) >= n
+
+
+def plane_fingerprints(planes_table, receptor, ctype_mask=0x7F):
+    """The host route to the class planes of the library fingerprints, over a fetched ``Context.library_planes`` table: per global
+    pose the set of ``(node, plane)`` — plane 15 ... 28 as ``pose_fingerprints.CLASS_PLANE_NAMES`` numbers them — of the records
+    whose ``ctype`` bit is in ``ctype_mask`` and of whose two entities exactly one is the ligand's (``ligand_side``).  The node
+    is the residue of the receptor entity: ``res_id`` of an atom, ``amide_res`` of an amide and the RESIDENT ``ring_res`` of a
+    ring, all of ``receptor`` alone (``poses.plane_fingerprints`` takes the first atom of the ring path instead: there the
+    ligand is part of the structure and can have taken the ring's residue over).  A node outside [0, n_residues) is skipped.
+    Returns a list of T sets."""
+    res_id = np.asarray(receptor.res_id, np.int64).reshape(-1)
+    ring_res = np.asarray(receptor.ring_res, np.int64).reshape(-1)
+    am_res = np.asarray(receptor.amide_res, np.int64).reshape(-1)
+    T = len(planes_table['summary'])
+    out = [set() for _ in range(T)]
+
+    def at(table, ids, lig):      # the residue of the receptor entities among ids (0 stands in where the ligand's are)
+        ids = np.where(lig, 0, ids)
+        return table[ids] if len(table) else np.full(ids.shape, -1, np.int64)
+
+    def add(name, keep, node, plane):
+        off = np.asarray(planes_table[name]['pose_off']).astype(np.int64)
+        pose = np.repeat(np.arange(T), np.diff(off))
+        ct = np.asarray(planes_table[name]['ctype']).astype(np.int64)
+        keep = keep & (((int(ctype_mask) >> np.minimum(ct, 31)) & 1) != 0) & (ct < 7) & (node >= 0) & (node < receptor.n_residues)
+        for t, u, q in zip(pose[keep].tolist(), node[keep].tolist(), np.broadcast_to(plane, keep.shape)[keep].tolist()):
+            out[t].add((u, q))
+
+    b = planes_table['atom_plane']
+    a, r, mask = np.asarray(b['atom'], np.int64), np.asarray(b['ring'], np.int64), np.asarray(b['mask'], np.int64)
+    la, lr = ligand_side(receptor, 'atom', a), ligand_side(receptor, 'ring', r)
+    for bit in range(5 if len(a) else 0):
+        add('atom_plane', (la != lr) & (((mask >> bit) & 1) != 0), np.where(la, at(ring_res, r, lr), at(res_id, a, la)),
+            np.where(la, CLASS_PLANE + bit, CLASS_PLANE + 5 + bit))
+    b = planes_table['plane_plane']
+    r1, r2 = np.asarray(b['bgn'], np.int64), np.asarray(b['end'], np.int64)
+    if len(r1):
+        l1, l2 = ligand_side(receptor, 'ring', r1), ligand_side(receptor, 'ring', r2)
+        add('plane_plane', l1 != l2, np.where(l1, at(ring_res, r2, l2), at(ring_res, r1, l1)), CLASS_PLANE + 10)
+    b = planes_table['group_group']
+    a1, a2 = np.asarray(b['bgn'], np.int64), np.asarray(b['end'], np.int64)
+    if len(a1):
+        l1, l2 = ligand_side(receptor, 'amide', a1), ligand_side(receptor, 'amide', a2)
+        add('group_group', l1 != l2, np.where(l1, at(am_res, a2, l2), at(am_res, a1, l1)), CLASS_PLANE + 11)
+    b = planes_table['group_plane']
+    a, r = np.asarray(b['amide'], np.int64), np.asarray(b['ring'], np.int64)
+    if len(a):
+        la, lr = ligand_side(receptor, 'amide', a), ligand_side(receptor, 'ring', r)
+        add('group_plane', la != lr, np.where(la, at(ring_res, r, lr), at(am_res, a, la)), np.where(la, CLASS_PLANE + 12, CLASS_PLANE + 13))
+    return out
+
+
 def _planes_per_pose(table, receptor, ligands):
     """(ligand, pose within it, the complex the ids are of, the pose's four bags) for every global pose."""
     both = {}

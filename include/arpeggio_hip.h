@@ -1368,8 +1368,8 @@ int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, 
  *
  * FEATURE.  (node, plane).  The node is the receptor atom i of a participating library record, with ARP_POSEFP_BY_RESIDUE
  *   res_id[i]; the plane is one of the 15 SIFt bits selected by `planes`.  A record participates when bit ctype of ctype_mask
- *   is set and sift & planes != 0.  The ligand side a never names a node.  There are no class planes yet (the library's ring and
- *   amide tables, arp_library_planes_launch, are not read here) and no all-pairs matrix (T reaches 2^20).
+ *   is set and sift & planes != 0.  The ligand side a never names a node.  This entry has no class planes (the library's ring and
+ *   amide tables enter through arp_library_fingerprints_planes_launch, below) and there is no all-pairs matrix (T reaches 2^20).
  * REFERENCES need not be poses of the launch: the known binder is usually another molecule.  Q = n_refs <=
  *   ARP_POSEFP_MAX_REFS references are given as feature lists: ref_off int64 [Q + 1] (ref_off[0] = 0, not decreasing, F =
  *   ref_off[Q] <= ARP_LIBFP_MAX_FEATURES), ref_node int32 [F] (nodes of the launch's level, strictly ascending within a
@@ -1401,11 +1401,42 @@ int arp_library_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64_t* n_poses, 
  *   new library launch) and after a new fingerprint launch; its best-pose table goes with it.  arp_set_selection voids neither.
  *   Making either voids nothing else: the library result, its best-pose table and every pose result stay fetchable and
  *   byte-equal.
- * OUT OF SCOPE: class planes; the all-pairs matrix; clusters over the library fingerprint (the shortlist by it:
- *   arp_library_shortlist_launch below). */
+ * THE RING AND AMIDE CLASSES AS PLANES (arp_library_fingerprints_planes_launch).  planes29 is a mask over
+ *   ARP_POSEFP_ALL_PLANES = 29 planes: the 15 SIFt bits and the 14 class planes of arp_poses_fingerprints_planes_launch, with
+ *   its bit numbers and its table -> plane map, fed by the four tables of the resident library-planes result
+ *   (arp_library_planes_launch) of the SAME poses.  Without a bit from ARP_POSEFP_PLANES on, the entry does exactly what
+ *   arp_library_fingerprints_launch does (reference masks may still carry bits up to 28; the selection drops them).
+ *   Ids in the library-planes result are the complex's.  An entity is on the LIGAND side when it is an atom with id >= n, a
+ *   ring with id >= nring or an amide with id >= namide (n, nring, namide the receptor's); everything else is the receptor's,
+ *   an affected receptor ring included.  A ring / amide record takes part when bit ctype of ctype_mask is set, EXACTLY ONE of
+ *   its two entities is the ligand's (ligand - ligand records of a biaryl and receptor atom - affected receptor ring records do
+ *   not take part) and its plane is selected.  The node is the residue of the receptor entity: res_id[atom] of a receptor atom,
+ *   the resident amide_res[amide] of a receptor amide, and the RESIDENT ring_res[ring] OF THE RECEPTOR ALONE of a receptor
+ *   ring.  That is a deliberate difference from the pose route, which takes the first atom of the ring path: no receptor ring
+ *   path is resident here (arp_set_plane_atoms is not needed), and the ligand is no part of the resident structure, so no ligand
+ *   atom can have taken a ring's residue over.  The posed residue k_library_planes makes per pose is NOT used.  A node outside
+ *   [0, nres) (a ring with residue -1) is skipped.  Class planes exist at residue level only; the ligand side never names a
+ *   node.  ref_planes may carry bits up to 28.  Rows, ids, count, cross, occupancy, bits, info (info[3] = NP counts the class
+ *   planes) and the best-pose table keep their meaning over the widened feature set; _fetch, _info, _best_launch and
+ *   _best_fetch serve both entries.
+ *   With a class plane set the launch reads the library result and the library-planes result, and checks ON THE DEVICE that
+ *   both were made from the same pose coordinates (the flag comes back with U: still ONE host wait).
+ *   ARP_E_ARG with the cause named, in this order, none touching a resident result: a pass not waited for; no library result;
+ *   with a bit from ARP_POSEFP_PLANES on: no library-planes result; the two results differ in T (or in their pose ranges);
+ *   class planes without ARP_POSEFP_BY_RESIDUE; then a mask of 0 or beyond bit 28; the refusals of
+ *   arp_library_fingerprints_launch from ctype_mask on; a reference mask beyond bit 28.  Found after the wait (the fingerprint
+ *   before is void by then and none is resident afterwards): "made from different poses".
+ *   STATE.  A fingerprint made with class planes is void wherever the library result OR the library-planes result is
+ *   (arp_library_planes_launch, arp_set_ligand_library_planes included); its best-pose table goes with it.  One made without
+ *   survives both calls.  Making it voids nothing.
+ * OUT OF SCOPE: atom-level nodes for rings and amides; the finer ARP_PP_* classes as planes; the all-pairs matrix; one shared
+ *   pose upload for the two library launches. */
 #define ARP_LIBFP_MAX_FEATURES (1 << 22)
 int arp_library_fingerprints_launch(arp_ctx* ctx, uint32_t planes, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
                                     const int64_t* ref_off, const int32_t* ref_node, const uint32_t* ref_planes, int64_t info[8]);
+int arp_library_fingerprints_planes_launch(arp_ctx* ctx, uint32_t planes29, uint32_t ctype_mask, uint32_t flags, int64_t n_refs,
+                                           const int64_t* ref_off, const int32_t* ref_node, const uint32_t* ref_planes,
+                                           int64_t info[8]);
 int arp_library_fingerprints_fetch(arp_ctx* ctx, int64_t cap_nodes, int32_t* ids, uint32_t* count, uint32_t* cross,
                                    uint32_t* occupancy, uint64_t* bits, int64_t* n_nodes);
 int arp_library_fingerprints_info(arp_ctx* ctx, int64_t info[8]);
@@ -1467,7 +1498,8 @@ int arp_library_fingerprints_best_fetch(arp_ctx* ctx, int64_t cap_ligands, int64
  *   new launch.  arp_set_selection does NOT void it.  Making it voids nothing: the bags of the last pass, every table made from
  *   them, every pose result, the library contacts, their best-pose table and the library fingerprints stay fetchable and
  *   byte-equal.
- * OUT OF SCOPE: class planes of the library fingerprints and clusters over a library (the shortlist, with the best pose per
+ * OUT OF SCOPE: clusters over a library (the class planes of the library fingerprints:
+ *   arp_library_fingerprints_planes_launch above; the shortlist, with the best pose per
  *   ligand over this summary: arp_library_shortlist_launch below); peptide and covalent ligands; a batch, models or a shard as the
  *   receptor; receptor - receptor records between unaffected entities. */
 #define ARP_LIBRARY_PLANES_MAX_RINGS 32
