@@ -62,6 +62,7 @@ SYMBOLS = (
     'arp_set_ligand_library_planes', 'arp_library_planes_launch', 'arp_library_planes_fetch', 'arp_library_planes_info',
     'arp_library_shortlist_launch', 'arp_library_shortlist_fetch', 'arp_library_shortlist_planes_fetch', 'arp_library_shortlist_info',
     'arp_library_clusters_launch', 'arp_library_clusters_fetch', 'arp_library_clusters_info',
+    'arp_library_water_bridges_launch', 'arp_library_water_bridges_fetch', 'arp_library_water_bridges_info',
 )
 
 # the three device-reduced tables (tables.py holds their columns, in the order of their fetch's arguments) and ARP_PERSIST_STAGE_MAX
@@ -283,6 +284,9 @@ def load():
     L.arp_library_clusters_launch.argtypes = [vp, C.c_int, vp, i64, C.c_uint64, i64, vp]
     L.arp_library_clusters_fetch.argtypes = [vp, i64, i64] + [vp] * 7 + [C.POINTER(i64), C.POINTER(i64)]
     L.arp_library_clusters_info.argtypes = [vp, vp]
+    L.arp_library_water_bridges_launch.argtypes = [vp, C.c_uint32, C.POINTER(i64)]
+    L.arp_library_water_bridges_fetch.argtypes = [vp, i64, i64] + [vp] * 11 + [C.POINTER(i64)]
+    L.arp_library_water_bridges_info.argtypes = [vp, vp]
     L.arp_set_ligand_library.argtypes = [vp, i64] + [vp] * 7
     L.arp_library_contacts_launch.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(i64)]
     L.arp_library_contacts_fetch.argtypes = [vp, i64] + [vp] * 7 + [C.POINTER(i64)]
@@ -1583,6 +1587,40 @@ class Context:
         info = np.zeros(8, np.int64)
         self._check(self._L.arp_library_clusters_info(self._h, _p(info)), 'arp_library_clusters_info')
         return dict(zip(('positions', 'clusters', 'unassigned', 'max_clusters', 'words', 'rounds', 'launches', 'threshold_q32'), (int(v) for v in info)))
+
+    def library_water_bridges(self, contacts=('hbond', 'polar'), sift_any=None):
+        """The ligand-water-receptor contacts of every pose of the resident library result, joined on the device with the atom-atom
+        bag of a pass over the receptor alone, everything selected (arp_library_water_bridges_*; ``arpeggio_amd.library_bridges``
+        describes the table).  ``contacts`` names the SIFt bits a leg needs one of (``library_bridges.mask``; ``None``: any), or
+        ``sift_any`` gives the mask itself.  Returns a dict of the eight columns ``library_bridges.COLUMNS`` in ascending (pose,
+        water, lig_atom, rec_atom) and, per pose, ``bridge_off`` uint64 [T + 1], ``waters`` uint32 [T] and ``legs`` uint32 [T].
+        Only the table is copied to the host."""
+        from . import library_bridges as _lb
+        m = _lb.mask(contacts) if sift_any is None else int(sift_any)
+        if m < 0 or m >= 1 << 32:
+            raise ValueError('library_water_bridges: sift_any must fit 32 bits')
+        n = C.c_int64(0)
+        self._check(self._L.arp_library_water_bridges_launch(self._h, m, C.byref(n)), 'arp_library_water_bridges_launch')
+        info = self.library_water_bridges_info()
+        B, T = int(n.value), info['poses']
+        out = {k: np.empty(B, dt) for k, dt in _lb.COLUMNS}
+        out.update(bridge_off=np.empty(T + 1, np.uint64), waters=np.empty(T, np.uint32), legs=np.empty(T, np.uint32))
+        # (the fetch writes B rows of every column and T + 1 / T / T per-pose entries: the arrays above are exactly that long)
+        self._check(self._L.arp_library_water_bridges_fetch(self._h, B, T, *(_p(out[k]) for k, _ in _lb.COLUMNS), _p(out['bridge_off']),
+                                                            _p(out['waters']), _p(out['legs']), C.byref(n)), 'arp_library_water_bridges_fetch')
+        out['sift_any'] = m
+        return out
+
+    def library_water_bridges_info(self):
+        """arp_library_water_bridges_info: poses, rows, ligand legs, receptor legs, waters with a receptor leg and the mask of the
+        resident library water bridges (zeros while there are none), the launches that did work so far, and ``ready``: a library
+        result and the atom-atom bag of a pass over the receptor with everything selected and the same cutoff and vdw_comp are
+        resident, so a launch would not be refused for its sources."""
+        info = np.zeros(8, np.int64)
+        self._check(self._L.arp_library_water_bridges_info(self._h, _p(info)), 'arp_library_water_bridges_info')
+        out = dict(zip(('poses', 'rows', 'ligand_legs', 'receptor_legs', 'receptor_waters', 'sift_any', 'launches'), (int(v) for v in info[:7])))
+        out['ready'] = bool(info[7])
+        return out
 
     def library_fingerprints_info(self):
         """arp_library_fingerprints_info: rows (references and poses), references, columns, planes, words per row and word slices

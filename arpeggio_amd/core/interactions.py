@@ -501,6 +501,50 @@ class InteractionComplex:
             raise AttributeError('no ligand library result yet: call run_ligand_library() first')
         return _ll.write_library(wd, self.id, self.ligand_library, self.pc, self.ligand_library_ligands, self.component_types)
 
+    def run_library_water_bridges(self, library, poses, contacts=('hbond', 'polar'), chunk=None, interacting_cutoff=5.0, vdw_comp=0.1):
+        """Extension beside the mirror: which ligand atom of which pose is tied to which receptor atom through which structural
+        water, joined ON THE DEVICE (``arpeggio_amd.library_bridges`` describes the table).  ``library`` is a list of ligand packs
+        and ``poses`` holds per ligand ``(xyz, h_xyz or None)`` or None, as ``run_ligand_library`` takes them; ``contacts`` names the
+        SIFt bits a leg needs one of (``None``: any).  The atom-atom bag of a pass over this structure alone with everything
+        selected is the second source: when none with the same ``interacting_cutoff`` and ``vdw_comp`` is resident, that pass is
+        run here first (the selection on the device is everything from then on).  Every chunk of ``chunk`` global poses (default:
+        all at once; a ligand's poses may be cut between two) is one ``Context.library_summary`` and one
+        ``Context.library_water_bridges``; the chunks are joined by global pose (``library_bridges.concat``).  Returns the table,
+        with ``ligand_pose_off``; also kept in ``self.library_water_bridges`` (the ligands in ``self.library_water_bridges_ligands``)."""
+        from .. import _capi, ligand_library as _ll, library_bridges as _lb
+        sift_any = _lb.mask(contacts)
+        if self._ctx is None:
+            self.initialize()
+        ctx = self._ctx
+        ligands = list(library)
+        lib = _ll.pack(ligands)
+        off, x, h = _ll.flatten_poses(lib, poses)
+        if off[-1] < 1:
+            raise ValueError('run_library_water_bridges: no pose given')
+        ctx.set_ligand_library(lib)
+        parts = []
+        for off_c, _, _, xc, hc in _ll.chunk_poses(lib, off, x, h, chunk if chunk else _capi.POSES_MAX_POSES):
+            ctx.library_summary(off_c, xc, hc, interacting_cutoff, vdw_comp, False)
+            if not ctx.library_water_bridges_info()['ready']:
+                # no bag of a pass over the whole receptor with these parameters is resident: that pass, once (it voids no library result)
+                ctx.set_selection(np.ones(self.pc.n_atoms, np.uint8))
+                ctx.atom_contacts_launch(interacting_cutoff, vdw_comp, False)
+            parts.append(ctx.library_water_bridges(sift_any=sift_any))
+        out = parts[0] if len(parts) == 1 else _lb.concat(parts)
+        out['ligand_pose_off'] = off
+        self.library_water_bridges = out
+        self.library_water_bridges_ligands = ligands
+        return out
+
+    def write_library_water_bridges(self, wd):
+        """'<id>.librarybridges': the table of the last ``run_library_water_bridges`` as CSV, one row per bridge
+        (``library_bridges.write_csv``)."""
+        from .. import library_bridges as _lb
+        t = getattr(self, 'library_water_bridges', None)
+        if t is None:
+            raise AttributeError('no library water bridges yet: call run_library_water_bridges() first')
+        return _lb.write_library_bridges(wd, self.id, t, self.pc, self.library_water_bridges_ligands, t['ligand_pose_off'], self.component_types)
+
     def write_library_planes(self, wd):
         """'<id>.libraryplanes': the ring and amide table of the last ``run_ligand_library(planes=True)`` as CSV, one row per record
         (``ligand_library.write_planes_csv``)."""

@@ -49,6 +49,7 @@
 #include "arp_library.h"
 #include "arp_library_fingerprints.h"
 #include "arp_library_planes.h"
+#include "arp_library_bridges.h"
 #include "arp_blob.h"
 
 namespace {
@@ -345,6 +346,7 @@ struct LibraryResult {
     DevBuf<int> best_pose;
     std::vector<int64_t> host_pose_off;                 // [L + 1] as the launch took it (the library shortlist: candidates, same poses)
     int64_t L = 0, T = 0, blocks = 0, nx = 0;           // nx: the floats of the uploaded poses
+    double cutoff = 0.0, vdw_comp = 0.0;                // of the launch (the library water bridges: the receptor's pass must match)
     bool valid = false, best_valid = false;
     void release() {
         lig_of.release(); tab.release(); rec.release(); best_n.release(); best_score.release(); best_pose.release(); valid = best_valid = false;
@@ -441,6 +443,27 @@ struct LibClustersResult {
     void release() {
         start.release(); nl.release(); made.release(); size.release(); order.release(); wl.release(); pose.release(); ligand.release();
         cluster.release(); leader.release(); leader_position.release(); similarity.release(); words.release(); valid = false;
+    }
+};
+
+// the ligand-water-receptor contacts of the resident library result (arp_library_water_bridges_launch, arp_library_bridges.h): a sort
+// scratch of its own for the receptor's legs (the shared one and the water-bridge table are left alone), the table of every
+// water's legs by atom id, the per-tile counts with their totals, the prefixes at every pose's first record, the per-pose arrays
+// and the eight columns in one slab.  Valid while the library result AND the atom-atom bag are (void_pose_results, void_results)
+struct LibBridgesResult {
+    SortScratch sort;
+    DevBuf<uint2> water_legs;
+    DevBuf<long long> tile, totals, at;
+    DevBuf<unsigned long long> bridge_off;
+    DevBuf<uint32_t> waters, legs;
+    DevBuf<uint8_t> slab;
+    size_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t T = 0, rows = 0, lig_legs = 0, rec_legs = 0, rec_waters = 0, launches = 0;
+    uint32_t sift_any = 0;
+    bool valid = false;
+    void release() {
+        sort.release(); water_legs.release(); tile.release(); totals.release(); at.release(); bridge_off.release(); waters.release(); legs.release();
+        slab.release(); valid = false;
     }
 };
 
@@ -659,6 +682,8 @@ struct arp_ctx {
     int pending_seq_adj = 0;
     int64_t contacts_expected = 0;   // contacts the previous pass over this structure found (0: none yet): sizes the sift launch
     bool contacts_valid = false;
+    double bag_cutoff = 0.0, bag_comp = 0.0;   // of the pass that made the atom-atom bag, and whether everything was selected in it
+    bool bag_sel_all = false;
     u64* d_ctr = nullptr;        // C_COUNT device counters
     u64 h_ctr[C_COUNT] = {0};
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -695,7 +720,7 @@ struct arp_ctx {
     bool init_plus_in_bin = false; // ... and writes selection_plus = selection (whole-structure selection)
     // ---- device-resident result bags of the ring / amide kernels
     Bag bag[BAG_KINDS];
-    void void_bags() { for (Bag& b : bag) b.valid = false; }
+    void void_bags();               // (defined behind the results that go with the bags)
     bool bags_valid() const { bool v = true; for (const Bag& b : bag) v = v && b.valid; return v; }
     DevBuf<uint32_t> bag_perm_big[4];   // ... of a bag beyond BAG_SORT_MAX records (bag_order_large)
     SortScratch sort_bags;                // ... the radix sort's scratch for them
@@ -767,6 +792,7 @@ struct arp_ctx {
     LibraryPlanesResult libpl;            // arp_library_planes_launch
     ShortlistResult libshortlist;         // arp_library_shortlist_launch
     LibClustersResult libclusters;        // arp_library_clusters_launch
+    LibBridgesResult libbridges;          // arp_library_water_bridges_launch: reads the library result and the atom-atom bag
     // ---- profiling
     bool profiling = false;
     std::vector<EventPair> ev_pool;
@@ -774,6 +800,11 @@ struct arp_ctx {
     double k_ms[NSLOT] = {0};
     int64_t k_launches[NSLOT] = {0};
 };
+// (the library water bridges read the atom-atom bag as well: they go wherever the bags go, and by void_results)
+void arp_ctx::void_bags() {
+    for (Bag& b : bag) b.valid = false;
+    libbridges.valid = false;
+}
 
 namespace {
 
@@ -958,6 +989,7 @@ void void_results(arp_ctx* c, unsigned lost) {
         {&c->networks.valid, RES_AA, 0},
         {&c->bridges.valid, RES_AA, RES_BRIDGES},
         {&c->bridgepersist.valid, RES_BRIDGES, 0},
+        {&c->libbridges.valid, RES_AA, 0},      // (the library water bridges, DESIGN.md 5aa: also a row of void_pose_results)
         {&c->respair.valid, bags, 0},
         {&c->respersist.valid, bags, 0},
         {&c->filtered.valid, bags | RES_LAYOUT, 0},      // (its slab is sized for the four bags packed behind the kept records)
@@ -989,7 +1021,8 @@ enum : unsigned {
     POSE_LIBRARY_PLANE_ATOMS = 1u << 14,      // the library's plane table (arp_set_ligand_library_planes)
     POSE_LIBRARY_PLANES_SETUP = 1u << 15, POSE_LIBRARY_PLANES = 1u << 16,
     POSE_LIBRARY_SHORTLIST = 1u << 17,
-    POSE_LIBRARY_CLUSTERS = 1u << 18
+    POSE_LIBRARY_CLUSTERS = 1u << 18,
+    POSE_LIBRARY_BRIDGES = 1u << 19
 };
 void void_pose_results(arp_ctx* c, unsigned lost) {
     const unsigned inputs = POSE_STRUCTURE | POSE_SELECTION;
@@ -1018,7 +1051,10 @@ void void_pose_results(arp_ctx* c, unsigned lost) {
         {&c->libshortlist.valid, POSE_LIBRARY_SHORTLIST, POSE_LIBRARY_CONTACTS | (c->libshortlist.planes ? POSE_LIBRARY_PLANES : 0u)},
         // the library clusters read the library result (lig_of, T); the library fingerprint and the library
         // shortlist only while their launch runs, so they stand behind the library result alone
-        {&c->libclusters.valid, POSE_LIBRARY_CLUSTERS, POSE_LIBRARY_CONTACTS}};
+        {&c->libclusters.valid, POSE_LIBRARY_CLUSTERS, POSE_LIBRARY_CONTACTS},
+        // the library water bridges read the library result's records; and the atom-atom bag of the receptor's
+        // pass, by which they are a row of void_results as well
+        {&c->libbridges.valid, POSE_LIBRARY_BRIDGES, POSE_LIBRARY_CONTACTS}};
     for (const auto& r : results)
         if ((r.is | r.reads) & lost) { *r.valid = false; lost |= r.is; }
 }
@@ -1975,6 +2011,7 @@ auto with_bits(bool s, bool g, F f) {
 int enqueue_contacts(arp_ctx* c, double cutoff, double vdw_comp, int include_seq_adj, bool with_planes) {
     struct Defer { arp_ctx* c; ~Defer() { c->uplists_defer = false; } } defer{c};
     c->uplists_defer = !c->external_stream;
+    c->bag_cutoff = cutoff; c->bag_comp = vdw_comp; c->bag_sel_all = c->sel_made && c->sel_all;      // (what the bag is made under)
     // the tree is built on selection_plus (I:1442); hydrogens are dropped at I:712
     if (!c->ctr_clean) CHK(zero_counter(c, C_BINNED, 1));
     CHK(zero_counter(c, C_ERR, 1));      // (before the grid build: its chained scan may raise the flag)
@@ -2629,6 +2666,7 @@ void arp_destroy(arp_ctx* c) {
     c->libshortlist.release();
     c->clusters.release();
     c->libclusters.release();
+    c->libbridges.release();
     c->library.release();
     c->libres.release();
     c->libfp.release();
@@ -4953,6 +4991,45 @@ int arp_fetch_packed_filtered(arp_ctx* c, void* host, uint64_t host_bytes, int64
     return fetch_packed_from(c, PackedAtomBag{"arp_fetch_packed_filtered", F.count, F.csr, &F}, host, host_bytes, counts, offsets, bytes_used);
 }
 
+// What both joins on waters share (arp_water_bridges_launch, arp_library_water_bridges_launch): the legs of the resident atom-atom
+// bag (k > 0 records) counted per tile and scanned — the host learns L, one wait —, keyed by (water, partner) into the scratch `s`,
+// sorted by every bit so that a water's legs become one run with ascending partners, the runs counted and their starts made for L
+// runs (the most there can be): U stays on the device, in table_total.  L = 0: nothing more was enqueued.
+struct SortedLegs {
+    BridgeLegArgs A;
+    RunArgs R;
+    const unsigned long long *key, *val;      // the sorted legs
+    long long L;
+};
+int sorted_water_legs(arp_ctx* c, const std::string& fn, uint32_t sift_any, SortScratch& s, SortedLegs* S) {
+    const size_t k = (size_t)c->n_contacts;
+    BridgeLegArgs& A = S->A;
+    A = BridgeLegArgs{};
+    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
+    A.k = (long long)k; A.flags = c->flags.p; A.sift_any = sift_any;
+    A.pbits = index_bits(c->n);      // (key = w << pbits | partner: at most 62 bits)
+    const int tiles = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
+    CHK(reserve_tile_counts(c, tiles));
+    A.tile_keep = c->table_tiles.p;
+    hipLaunchKernelGGL(k_bridge_legs_count, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    long long L = 0;
+    CHK(wait_tile_total(c, tiles, &L, fn + "legs count / scan"));
+    if (L < 0 || L > (long long)k) FAIL(c, ARP_E_HIP, fn + "leg count out of range");
+    S->L = L;
+    if (L == 0) return ARP_OK;
+    CHK(reserve_key_sort(c, s, (size_t)L, (size_t)L));
+    A.key = s.key[0].p; A.val = s.val[0].p; A.legs = L;
+    hipLaunchKernelGGL(k_bridge_legs_write, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    int sorted = 0;
+    enqueue_key_sort(c, s, (size_t)L, 2 * A.pbits, &sorted);
+    S->key = s.key[sorted].p; S->val = s.val[sorted].p;
+    RunArgs& R = S->R;
+    R = RunArgs{};
+    R.key = S->key; R.k = L; R.shift = A.pbits;
+    enqueue_run_count(c, R);      // (R.T <= tiles: table_tiles is large enough, and the legs' prefixes are consumed in stream order)
+    return enqueue_run_starts(c, R, L);
+}
+
 // ---- water-mediated contacts (arp_bridge.h): the atom-atom bag joined with itself on its water atoms
 // Two waits — L legs, then B rows —: a shape of its own, from the shared steps.  U, the waters with a leg, is never read by the
 // host: row_start is made for L runs (the most there can be) and the kernels take U from table_total.  Of the results only the
@@ -4974,36 +5051,18 @@ int arp_water_bridges_launch(arp_ctx* c, uint32_t sift_any, uint32_t flags, int6
     CHK(records_fit(c, fn, k));
     const auto done = [&](long long rows) { return table_done(T, sift_any, flags, rows, count); };
     if (k == 0) return done(0);
-    // ---- legs per tile, scanned; the host learns L (wait 1)
-    BridgeLegArgs A{};
-    A.ci = c->out_i.p; A.cj = c->out_j.p; A.d_in = c->out_d.p; A.s_in = c->out_s.p; A.ct_in = c->out_ct.p;
-    A.k = (long long)k; A.flags = c->flags.p; A.sift_any = sift_any;
-    A.pbits = index_bits(c->n);      // (key = w << pbits | partner: at most 62 bits)
-    const int tiles = (int)((k + FILTER_TILE - 1) / FILTER_TILE);
-    CHK(reserve_tile_counts(c, tiles));
-    A.tile_keep = c->table_tiles.p;
-    hipLaunchKernelGGL(k_bridge_legs_count, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
-    long long L = 0;
-    CHK(wait_tile_total(c, tiles, &L, fn + "legs count / scan"));
-    if (L < 0 || L > (long long)k) FAIL(c, ARP_E_HIP, fn + "leg count out of range");
+    // ---- the legs, sorted by (water, partner), and their runs; the host learns L (wait 1)
+    SortedLegs S{};
+    CHK(sorted_water_legs(c, fn, sift_any, c->table_sort, &S));
+    const long long L = S.L;
     if (L == 0) return done(0);
-    // ---- the legs keyed by (water, partner), sorted by every bit: a water's legs become one run, partners ascending
-    SortScratch& s = c->table_sort;
-    CHK(reserve_key_sort(c, s, (size_t)L, (size_t)L));
-    A.key = s.key[0].p; A.val = s.val[0].p; A.legs = L;
-    hipLaunchKernelGGL(k_bridge_legs_write, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
-    int sorted = 0;
-    enqueue_key_sort(c, s, (size_t)L, 2 * A.pbits, &sorted);
-    // ---- the runs: at most L of them, so their starts are made for L and U stays on the device (no wait of its own)
-    RunArgs R{};
-    R.key = s.key[sorted].p; R.k = L; R.shift = A.pbits;
-    enqueue_run_count(c, R);      // (R.T <= tiles: table_tiles is large enough, and the legs' prefixes are consumed in stream order)
-    CHK(enqueue_run_starts(c, R, L));
+    const BridgeLegArgs& A = S.A;
+    const RunArgs& R = S.R;
     // ---- kept pairs per run, scanned in 64 bits; the host learns B (wait 2)
     HIPCHK(c, c->bridge_off.reserve((size_t)L + 1));
     HIPCHK(c, c->bridge_res.reserve((size_t)L));
     BridgePairArgs P{};
-    P.key = R.key; P.val = s.val[sorted].p; P.legs = L; P.pbits = A.pbits;
+    P.key = S.key; P.val = S.val; P.legs = L; P.pbits = A.pbits;
     P.row_start = R.row_start; P.runs = c->table_total.p; P.res_id = c->res_id.p; P.leg_res = c->bridge_res.p;
     P.flags = flags; P.row_off = c->bridge_off.p;
     const int pair_blocks = nblocks(L, 4, 16384);       // (one wave per run; U <= L)
@@ -5948,6 +6007,7 @@ int arp_library_contacts_launch(arp_ctx* c, const int64_t* pose_off, const float
     };
     CHK(pose_records_launch(c, fn, R.rec, T, xyz, (size_t)nx, h_xyz, (size_t)nh, A.ibits + A.abits + index_bits(T), A.ibits, A.abits, enqueue, count));
     R.L = L; R.T = T; R.blocks = (int64_t)blocks; R.nx = nx; R.host_pose_off.assign(pose_off, pose_off + L + 1); R.valid = true;
+    R.cutoff = cutoff; R.vdw_comp = vdw_comp;
     return ARP_OK;
 }
 
@@ -7500,6 +7560,139 @@ int arp_library_clusters_fetch(arp_ctx* c, int64_t cap_positions, int64_t cap_cl
 int arp_library_clusters_info(arp_ctx* c, int64_t info[8]) {
     if (!c || !info) return ARP_E_ARG;
     library_clusters_info(c->libclusters, info);
+    return ARP_OK;
+}
+
+// ---- ligand-water-receptor contacts of the library result (arp_library_bridges.h): two resident results joined
+// The library result's records and the atom-atom bag of a pass over the receptor alone, everything selected, are read; nothing
+// resident but this result is written (its own sort scratch; the shared tile counts, run starts and stage are scratch of every
+// table).  Two waits: L_r, the receptor's legs (sorted_water_legs), then the ligand legs with B, the rows.
+// What the launch refuses of its two sources, behind its mask and in this order: the one statement, which
+// arp_library_water_bridges_info asks as well (word [7])
+static int library_bridge_sources(arp_ctx* c, const std::string& fn) {
+    const LibraryResult& R = c->libres;
+    if (!R.valid) FAIL(c, ARP_E_ARG, fn + "no library result (arp_library_contacts_launch; the structure or the library changed since)");
+    // (models or a batch as the structure need no refusal of their own: making either voids the library result — POSE_STRUCTURE —,
+    // and arp_library_contacts_launch refuses both, so "no library result" above has answered)
+    CHK(launch_refusals(c, fn, NEED_WHOLE | NEED_AA_BAG, NO_AA_PASS));
+    if (!c->bag_sel_all) FAIL(c, ARP_E_ARG, fn + "the atom-atom bag was made under a partial selection (a pass over the receptor with everything selected first)");
+    if (c->bag_cutoff != R.cutoff || c->bag_comp != R.vdw_comp)
+        FAIL(c, ARP_E_ARG, fn + "cutoff or vdw_comp of the receptor's pass differ from those of the library launch");
+    return ARP_OK;
+}
+
+int arp_library_water_bridges_launch(arp_ctx* c, uint32_t sift_any, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const std::string fn = "arp_library_water_bridges_launch: ";
+    // ---- the refusals, in this order: none of them touches a resident result
+    CHK(check_leg_mask(c, fn, sift_any));
+    CHK(library_bridge_sources(c, fn));
+    const LibraryResult& R = c->libres;
+    LibBridgesResult& X = c->libbridges;
+    if (X.valid && X.sift_any == sift_any) { *count = X.rows; return ARP_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    void_pose_results(c, POSE_LIBRARY_BRIDGES);
+    const int64_t T = R.T;
+    X.T = T; X.rows = X.lig_legs = X.rec_legs = X.rec_waters = 0; X.sift_any = sift_any;
+    *count = 0;
+    const size_t k = (size_t)c->n_contacts, kl = (size_t)R.rec.count;
+    CHK(records_fit(c, fn, k));
+    CHK(records_fit(c, fn, kl));
+    HIPCHK(c, X.bridge_off.reserve((size_t)T + 1));
+    HIPCHK(c, X.waters.reserve((size_t)T));
+    HIPCHK(c, X.legs.reserve((size_t)T));
+    const auto done = [&](long long rows) -> int {
+        CHK(check_launch(c, (fn + "enqueue").c_str()));
+        X.rows = rows; X.valid = true;
+        *count = rows;
+        return ARP_OK;
+    };
+    const auto zeros = [&]() -> int {      // no row and no leg counted: the per-pose arrays are valid, all zero
+        HIPCHK(c, hipMemsetAsync(X.bridge_off.p, 0, ((size_t)T + 1) * sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipMemsetAsync(X.waters.p, 0, (size_t)T * sizeof(uint32_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(X.legs.p, 0, (size_t)T * sizeof(uint32_t), c->stream));
+        return done(0);
+    };
+    if (k == 0 || kl == 0) return zeros();
+    // ---- the receptor's legs, sorted by (water, partner), and their runs; the host learns L_r (wait 1)
+    SortedLegs S{};
+    CHK(sorted_water_legs(c, fn, sift_any, X.sort, &S));
+    if (S.L == 0) return zeros();
+    ++X.launches;
+    // ---- every water's (first leg, legs) by atom id; ligand legs, rows and heads per tile, scanned (wait 2, the last)
+    const int tiles = (int)((kl + FILTER_TILE - 1) / FILTER_TILE);
+    HIPCHK(c, X.water_legs.reserve((size_t)c->n));
+    HIPCHK(c, X.tile.reserve(3 * (size_t)tiles));
+    HIPCHK(c, X.totals.reserve(4));
+    HIPCHK(c, X.at.reserve(3 * (size_t)T));
+    HIPCHK(c, hipMemsetAsync(X.water_legs.p, 0, (size_t)c->n * sizeof(uint2), c->stream));
+    const Columns rec{R.rec.slab.p, R.rec.off};
+    LibBridgeArgs A{};
+    A.ri = rec[0]; A.ra = rec[1]; A.rd = rec[2]; A.rs = rec[3]; A.k = (long long)kl;
+    A.pose_off = R.rec.pose_off.p; A.T = (int)T; A.lig_of = R.lig_of.p; A.atom_off = c->library.atom_off.p;
+    A.rec_flags = c->flags.p; A.lib_flags = c->library.flags.p; A.n = (int)c->n; A.sift_any = sift_any;
+    A.lkey = S.key; A.lval = S.val; A.rlegs = S.L; A.pbits = S.A.pbits; A.row_start = S.R.row_start; A.runs = c->table_total.p;
+    A.water_legs = X.water_legs.p; A.tile = X.tile.p; A.tiles = tiles; A.totals = X.totals.p; A.at = X.at.p;
+    A.bridge_off = X.bridge_off.p; A.waters = X.waters.p; A.legs = X.legs.p;
+    hipLaunchKernelGGL(k_libbridge_table, dim3(nblocks(S.L, 256, 2048)), dim3(256), 0, c->stream, A);
+    hipLaunchKernelGGL(k_libbridge_count, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_libbridge_scan, dim3(1), dim3(SORT_THREADS), 0, c->stream, A);
+    CHK(check_launch(c, (fn + "table / count / scan").c_str()));
+    long long tot[4] = {0, 0, 0, 0};
+    CHK(stage_copy(c, X.totals.p, sizeof(tot)));
+    memcpy(tot, c->table_stage, sizeof(tot));
+    const long long LL = tot[0], B = tot[1];
+    if (LL < 0 || LL > (long long)kl || B < 0 || tot[3] < 0 || tot[3] > S.L) FAIL(c, ARP_E_HIP, fn + "counts out of range");
+    X.rec_legs = S.L; X.rec_waters = tot[3];
+    if (B >= (1ll << 31)) { *count = B; FAIL(c, ARP_E_CAPACITY, fn + "2^31 rows or more"); }
+    if (LL == 0) return zeros();
+    X.lig_legs = LL;
+    // ---- the rows, each at its rank, and the per-pose arrays from the same prefixes
+    static const size_t es[8] = {4, 4, 4, 4, 4, 4, 2, 2};
+    size_t at = 0;
+    for (int q = 0; q < 8; ++q) { X.off[q] = at; at += ((size_t)B * es[q] + 255) & ~(size_t)255; }
+    HIPCHK(c, X.slab.reserve(std::max<size_t>(at, 256)));
+    const Columns col{X.slab.p, X.off};
+    A.rows = B;
+    A.t_pose = col[0]; A.t_water = col[1]; A.t_lig = col[2]; A.t_rec = col[3]; A.t_dl = col[4]; A.t_dr = col[5]; A.t_sl = col[6]; A.t_sr = col[7];
+    hipLaunchKernelGGL(k_libbridge_write, dim3(tiles), dim3(FILTER_THREADS), 0, c->stream, A);
+    hipLaunchKernelGGL(k_libbridge_poses, dim3(nblocks(T + 1, 256, 1 << 16)), dim3(256), 0, c->stream, A);
+    return done(B);
+}
+
+int arp_library_water_bridges_fetch(arp_ctx* c, int64_t cap_rows, int64_t cap_poses, int32_t* pose, int32_t* water, int32_t* lig_atom, int32_t* rec_atom,
+                                    float* dist_lig, float* dist_rec, uint16_t* sift_lig, uint16_t* sift_rec, uint64_t* bridge_off, uint32_t* waters,
+                                    uint32_t* legs, int64_t* count) {
+    if (!c || !count) return ARP_E_ARG;
+    const LibBridgesResult& X = c->libbridges;
+    const std::string fn = "arp_library_water_bridges_fetch: ";
+    if (!X.valid) FAIL(c, ARP_E_ARG, fn + "no result (arp_library_water_bridges_launch; the library result or the atom-atom bag changed since)");
+    *count = X.rows;
+    const bool columns = pose || water || lig_atom || rec_atom || dist_lig || dist_rec || sift_lig || sift_rec;
+    if (columns && X.rows > cap_rows) FAIL(c, ARP_E_CAPACITY, fn + "output buffers too small (cap_rows < *count)");
+    if ((bridge_off || waters || legs) && X.T > cap_poses) FAIL(c, ARP_E_CAPACITY, fn + "output buffers too small (cap_poses < T)");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StagePiece> pieces;
+    const size_t B = (size_t)X.rows, T = (size_t)X.T;
+    void* const dst[8] = {pose, water, lig_atom, rec_atom, dist_lig, dist_rec, sift_lig, sift_rec};
+    static const size_t es[8] = {4, 4, 4, 4, 4, 4, 2, 2};
+    for (int q = 0; q < 8; ++q) want_piece(pieces, dst[q], X.slab.p + X.off[q], B * es[q]);
+    want_piece(pieces, bridge_off, X.bridge_off.p, (T + 1) * sizeof(uint64_t));
+    want_piece(pieces, waters, X.waters.p, T * sizeof(uint32_t));
+    want_piece(pieces, legs, X.legs.p, T * sizeof(uint32_t));
+    return stage_fetch(c, pieces);
+}
+
+int arp_library_water_bridges_info(arp_ctx* c, int64_t info[8]) {
+    if (!c || !info) return ARP_E_ARG;
+    const LibBridgesResult& X = c->libbridges;
+    // [7]: the two sources are resident and fit — a launch would pass every refusal behind its mask (what a caller asks before it
+    // decides to run the receptor's pass)
+    const std::string kept = c->err;       // (asking is no failure: the last error's text stays)
+    const bool fit = library_bridge_sources(c, "") == ARP_OK;
+    c->err = kept;
+    const int64_t v[8] = {X.T, X.rows, X.lig_legs, X.rec_legs, X.rec_waters, (int64_t)X.sift_any, X.launches, fit ? 1 : 0};
+    for (int q = 0; q < 8; ++q) info[q] = (X.valid || q >= 6) ? v[q] : 0;
     return ARP_OK;
 }
 

@@ -1649,6 +1649,57 @@ int arp_library_clusters_fetch(arp_ctx* ctx, int64_t cap_positions, int64_t cap_
                                int32_t* cluster, int64_t* similarity, int32_t* leader, int32_t* leader_position, uint32_t* size,
                                int64_t* n_positions, int64_t* n_clusters);
 int arp_library_clusters_info(arp_ctx* ctx, int64_t info[8]);
+
+/* ---- ligand-water-receptor contacts of every pose of the library result, joined on the device ----------
+ * Which ligand atom of which pose is tied to which receptor atom through which structural water.  TWO resident results are
+ * joined and nothing else is read: the library result (arp_library_contacts_launch: T global poses, records (t, i, a) sorted by
+ * (t, i, a)) and the atom-atom bag of a finished pass over the RECEPTOR ALONE WITH EVERYTHING SELECTED (arp_run_launch /
+ * arp_atom_contacts_launch on the resident structure, same cutoff and vdw_comp as the library launch).  A pass over the receptor
+ * voids no library result and a library launch voids no bag, so both can be resident together.
+ * RECEPTOR LEG: a bag record (i, j) in which exactly one atom has ARP_F_WATER and (sift & sift_any) != 0; the water is w, the
+ *   other atom j (arp_water_bridges_launch's leg, unchanged).
+ * LIGAND LEG of pose t: a library record (t, i, a) with ARP_F_WATER on receptor atom i, NO ARP_F_WATER on library atom a and
+ *   (sift & sift_any) != 0; the water is w = i.
+ * ROWS: one row (t, w, a, j) for every ligand leg (t, w, a) and every receptor leg (w, j), ascending by (t, w, a, j).  There is
+ *   no same-residue rule (a ligand is a residue of its own).  A water ligand bridges nothing in this table (its own atom is the
+ *   water), and a water-water record is no leg.
+ * COLUMNS, in the order of the fetch: pose int32 (global pose t), water int32 (receptor id w), lig_atom int32 (a, index within the
+ *   ligand), rec_atom int32 (j, receptor id), dist_lig / dist_rec float32 (the float32 bits of the two source records),
+ *   sift_lig / sift_rec uint16 (whole, not masked).  Contact types are NOT columns: a record's type depends on the selection it was
+ *   made under — the ligand selected for the library record, everything selected for the receptor's pass — and neither is what a
+ *   pass over the complex would print for a bridge.
+ * PER POSE: bridge_off uint64 [T + 1], the row offsets; waters uint32 [T], the distinct waters with at least one row; legs
+ *   uint32 [T], the ligand legs, whether or not their water has a receptor leg.
+ * YARDSTICK: for pose t of ligand l, a whole-structure pass over the complex (receptor + ligand l in that pose, everything
+ *   selected, same cutoff and vdw_comp) and arp_water_bridges_launch's join over its bag: the rows of pose t are exactly that
+ *   table's rows (w, x, y) in which exactly one of x, y is a ligand atom n + a.  (A pair's SIFt and distance depend on the two
+ *   atoms, their hydrogens and single-bond neighbours only; the ligand has no bond to the receptor; everything selected emits
+ *   every pair within the cutoff.)
+ * arp_library_water_bridges_launch: *count = rows.  sift_any: low 15 bits, not 0.  Refusals are ARP_E_ARG with the cause named,
+ *   in this order, and none touches anything resident: sift_any beyond the 15 bits, sift_any 0; no valid library result; a shard
+ *   of a distributed structure, no atom-contact results (or a pass not waited for); a bag made under a partial selection; cutoff
+ *   or vdw_comp of the pass differ from the library launch's (include_sequence_adjacent need not match: a water has no sequence
+ *   neighbours).  ARP_E_CAPACITY at 2^31 rows (*count = rows).  No ligand leg or no receptor leg: *count = 0 and ARP_OK, the
+ *   per-pose arrays valid and all zero, nothing more launched.  The same sift_any on the same two sources returns the stored
+ *   count without work.  Two waits: the receptor's legs, then ligand legs and rows.
+ *   The result is void when the library result is void or replaced (arp_set_ligand_library, a new arp_library_contacts_launch, a
+ *   new structure) and when the atom-atom bag is (a new pass, and whatever voids the bag: arp_set_selection among it).  Making
+ *   it voids nothing: the five bags, the water-bridge table and every library result stay as they are.
+ * arp_library_water_bridges_fetch: ANY pointer but count may be NULL.  *count = rows.  ARP_E_CAPACITY when a column is asked for
+ *   and cap_rows < rows, or a per-pose array and cap_poses < T.  ARP_E_ARG: no valid result.  One copy through the page-locked
+ *   stage.
+ * arp_library_water_bridges_info: info[0] = T, [1] = rows, [2] = ligand legs, [3] = receptor legs, [4] = waters with a receptor
+ *   leg, [5] = sift_any, [6] = launches that did work so far, [7] = 1 when both sources are resident and fit (a launch would
+ *   pass every refusal behind its mask: what a caller asks before it decides to run the receptor's pass), else 0.  [0] ... [5]
+ *   are 0 while there is no result.
+ * OUT OF SCOPE: bridges through a LIGAND's water atom; second-order (water-water) bridges; bridge planes in the library
+ *   fingerprint; a bridge slot in the shortlist's weights (ARP_SHORTLIST_LIST with a host order of the per-pose counts serves);
+ *   restricting the join to a pose subset; the pose route (arp_poses_contacts_launch). */
+int arp_library_water_bridges_launch(arp_ctx* ctx, uint32_t sift_any, int64_t* count);
+int arp_library_water_bridges_fetch(arp_ctx* ctx, int64_t cap_rows, int64_t cap_poses, int32_t* pose, int32_t* water, int32_t* lig_atom,
+                                    int32_t* rec_atom, float* dist_lig, float* dist_rec, uint16_t* sift_lig, uint16_t* sift_rec,
+                                    uint64_t* bridge_off, uint32_t* waters, uint32_t* legs, int64_t* count);
+int arp_library_water_bridges_info(arp_ctx* ctx, int64_t info[8]);
 /* Host side of arp_run_launch, accumulated over *passes calls: us[0] = time spent enqueueing the pass
  * (kernel launches, memsets, events), us[1] = time spent blocked in the one synchronisation. */
 int arp_get_host_times(arp_ctx* ctx, double us[2], int64_t* passes, int reset);
